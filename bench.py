@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Rollout-throughput bench for the MI355X rollout engine (contract: see DESIGN.md "Measurement").
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload target|c2|c3|c4|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload target|c2|c3|c4|c5] [--dump-outputs DIR]
 
 A "step" is one full rollout step of the hot path (state update -> node features -> radius graph -> destination sort
 -> edge features -> encode / 10x process / decode -> Euler integration), the loop body of compute_rollout
@@ -57,6 +57,7 @@ WORKLOADS = {
 MFMA_F32_PEAK_TFLOPS = 157.3    # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, dense, exact fp32
 MFMA_16BIT_PEAK_TFLOPS = 2500.0  # MI355X_MICROARCH.md: ~2.5 PF dense bf16 / fp16 MFMA
 HBM_PEAK_GBS = 8000.0
+DUMP_LIMIT_BYTES = 64 << 20      # --dump-outputs: all files together, headers included
 
 
 def edge_kernel_alg_flops(E, H=128, num_layers=2):
@@ -139,6 +140,26 @@ def cpu_baseline(obs, model, stats, scene, hidden):
                        f"oracle graph build + features (numpy, single thread), the full oracle/torch_epd.py forward -- encoder, all 10 "
                        f"message-passing steps, decoder -- with torch.set_num_threads({threads}) (the faster of 32 and {cores} threads, chosen on a "
                        f"short pass: encoder + decoder + one step), integration")
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one `path/<name>.npy` per array (float32 / float64 as computed).  Arrays of up to 1 MB are written whole.
+    If the larger ones (state windows) do not fit in what is left of DUMP_LIMIT_BYTES, each keeps a fixed, seeded sample of its
+    rows along axis 1 (the particle axis) in ascending order, and the row numbers it kept go to `<name>_rows.npy` (float64); the
+    same arguments give the same rows in every run."""
+    os.makedirs(path, exist_ok=True)
+    large = {name for name, a in arrays.items() if a.nbytes > (1 << 20) and a.ndim >= 2}
+    header = 256   # an .npy header is 128 bytes: room for the array's file and its rows file
+    budget = DUMP_LIMIT_BYTES - header * len(arrays) - sum(a.nbytes for name, a in arrays.items() if name not in large)
+    total = sum(arrays[name].nbytes for name in large)
+    for name, a in arrays.items():
+        if name in large and total > budget:
+            per_row = a.nbytes // a.shape[1] + 8   # the row itself and its float64 row number
+            keep = int(budget * (a.nbytes / total)) // per_row
+            rows = np.sort(np.random.Generator(np.random.PCG64(0)).choice(a.shape[1], keep, replace=False))
+            a = a[:, rows]
+            np.save(os.path.join(path, name + "_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
 
 
 def build_engine(wl, dev, rank, candidates, edge_kernel, total_steps):
@@ -240,7 +261,9 @@ def roofline_record(model, ek, hidden, edges, n_nodes, workload_key):
     return rec, k_ms
 
 
-def measure(wl_key, dev, rank, world, dist, cdev, args, steps, warmup, candidates=1):
+def measure(wl_key, dev, rank, world, dist, cdev, args, steps, warmup, candidates=1, outputs=None):
+    """outputs: a dict that receives, after the timed region, what its rollout handed back: `state`, the [k, N, D] window run()
+    leaves in place, and with collectives `gathered_results`, the [world, 3] per-rank results of the all-gather."""
     from gnn_manip_amd import _lib
     wl = WORKLOADS[wl_key]
     total = steps + warmup
@@ -291,6 +314,10 @@ def measure(wl_key, dev, rank, world, dist, cdev, args, steps, warmup, candidate
         t = torch.tensor([el], dtype=torch.float64, device=cdev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
+    if outputs is not None:   # before the profiling pass below, which rolls `obs` further
+        outputs["state"] = obs.cpu().numpy()
+        if dist:
+            outputs["gathered_results"] = torch.stack(gathered).cpu().numpy()
     rec = None
     if rank == 0:
         # Kernel timings: the same K steps once more, untimed, with HIP events (on the launch stream) around every model kernel
@@ -329,10 +356,10 @@ def measure(wl_key, dev, rank, world, dist, cdev, args, steps, warmup, candidate
     return rec, (model, obs_np, stats, scene, ek)
 
 
-def run_c5(dev, rank, world, dist, cdev, args):
+def run_c5(dev, rank, world, dist, cdev, args, outputs=None):
     """One CMA-ES generation of BASELINE config C5: 64 candidates x 200 rollout steps at N = 5k sharded over the ranks in
     block-diagonal batches, one device Sinkhorn loss per candidate, candidates broadcast and losses all-gathered inside the
-    timed region (planner.CandidateEvaluator)."""
+    timed region (planner.CandidateEvaluator).  outputs: a dict that receives the generation's `losses` [popsize]."""
     from gnn_manip_amd import GraphBoundedMultimaterialControl, RolloutEngine, planner
     from gnn_manip_amd.losses import SamplesLoss
     wl = WORKLOADS["c5"]
@@ -385,6 +412,8 @@ def run_c5(dev, rank, world, dist, cdev, args):
         t = torch.tensor([el], dtype=torch.float64, device=cdev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
+    if outputs is not None:
+        outputs["losses"] = np.asarray(losses, np.float64)
     if rank != 0:
         return None
     return {"metric": "rollout steps/sec (N particles, 10 MP steps, hidden=128)", "value": popsize * horizon / el, "unit": "rollout steps/s",
@@ -565,6 +594,10 @@ def main():
     ap.add_argument("--no-extra", action="store_true", help="skip the C2 / C3 / C4 sub-records")
     ap.add_argument("--edge-kernel", default="auto", choices=["auto", "sys", "sys_all", "hm"],
                     help="processor edge kernel (per-model option): auto = systolic fp16 x 3 kernel for hidden 128 (DESIGN.md 5.1)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, rank 0 writes what the timed path computed in its last step as DIR/<name>.npy: "
+                         "`state`, the [k, N, D] state window (c5: `losses`, one per candidate); at most 64 MB in all, larger "
+                         "states as a fixed, seeded sample of particle rows")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -602,16 +635,22 @@ def main():
         else:
             dist.init_process_group("nccl", device_id=dev, timeout=tmo)
     cdev = torch.device("cpu") if rehearse else dev  # where collective payloads live
+    outputs = {} if args.dump_outputs and rank == 0 else None
 
     if args.workload == "c5":
-        out = run_c5(dev, rank, world, dist, cdev, args)
+        out = run_c5(dev, rank, world, dist, cdev, args, outputs)
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, outputs)
         if rank == 0:
             print(json.dumps(out))
     else:
         wl = WORKLOADS[args.workload]
         steps = args.steps if args.steps > 0 else wl["steps"]
         warmup = args.warmup if args.warmup >= 0 else wl["warmup"]
-        rec, (model, obs_np, stats, scene, ek) = measure(args.workload, dev, rank, world, dist, cdev, args, steps, warmup, args.candidates)
+        rec, (model, obs_np, stats, scene, ek) = measure(args.workload, dev, rank, world, dist, cdev, args, steps, warmup, args.candidates,
+                                                         outputs)
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, outputs)
         if rank == 0:
             hidden = wl["hidden"]
             out = {"metric": f"rollout steps/sec (N particles, 10 MP steps, hidden={hidden})",
