@@ -135,7 +135,6 @@ struct CsrWs {
     int* dst;      // [cap] aggregation node of sorted position p
     int* src;      // [cap]
     int* eid;      // [cap] original edge id (row in the caller's edge order)
-    int* scan_tmp;  // block sums of the three-kernel scan (csr_from_edge_index)
     int* scan_in;   // state of the single-pass scan over the in-degrees (scan_state_ints)
     int* sort_tmp;  // [2 * cap] copies of long segments during the destination sort
     int64_t cap;
@@ -189,8 +188,6 @@ int csr_from_edge_index(const int64_t* ei, int64_t n, int64_t e, int flow, void*
 // next build clears it); hdr->order_skip tells the consumers (launched after this) that perm is to be read as the identity.
 int cell_order(const float* pos, int64_t pos_stride, int64_t n, int64_t n_per, double conn_r, int K, void* graph_ws, size_t graph_ws_bytes,
                int* perm, hipStream_t s);
-int exclusive_scan_i32(const int* in, int* out, int64_t n_max, const int* n_dev, int* tmp, hipStream_t s, int* total_out);
-size_t scan_tmp_ints(int64_t n_max);
 
 // Single-pass exclusive scan (decoupled look-back: a tile publishes its sum, then its inclusive prefix, in one 64-bit status word;
 // tiles are handed out by a ticket so that a tile only ever waits for tiles that are already running): ONE launch per scan, and two
@@ -221,7 +218,13 @@ struct StepClear {
     GraphHeader* gh = nullptr;   // reset for a build
     CsrHeader* ch = nullptr;     // reset for a destination sort (flow = `flow`)
     int flow = 0;
-    void add(int* p, long long n, int v) { if (p && n > 0 && n_jobs < kClearJobsMax) job[n_jobs++] = ClearJob{p, n, v}; }
+    // a job past kClearJobsMax would go unrecorded: an error, which the entry point that assembles the list returns
+    int add(int* p, long long n, int v) {
+        if (!p || n <= 0) return GM_OK;
+        GM_REQUIRE(n_jobs < kClearJobsMax, GM_ERR_INVALID_ARGUMENT, "StepClear: more than %d resets in one pass", kClearJobsMax);
+        job[n_jobs++] = ClearJob{p, n, v};
+        return GM_OK;
+    }
 };
 int launch_step_clear(const StepClear& c, hipStream_t s);
 #if defined(__HIPCC__)
@@ -268,8 +271,8 @@ __device__ inline void step_clear_run(const StepClear& c, long long t, long long
 #endif
 struct GraphWs;
 struct CsrWs;
-void graph_clear_jobs(StepClear& c, const GraphWs& g, int64_t n);             // what gm_radius_graph_build resets
-void csr_clear_jobs(StepClear& c, const CsrWs& w, int64_t n, int flow);        // what the destination sort of a radius graph resets
+int graph_clear_jobs(StepClear& c, const GraphWs& g, int64_t n);              // what gm_radius_graph_build resets
+int csr_clear_jobs(StepClear& c, const CsrWs& w, int64_t n, int flow);         // what the destination sort of a radius graph resets
 
 // The rollout step's graph path with its resets already done (StepClear in the step's first launch) and the in-degree count
 // riding in the neighbour search: radius graph -> destination sort + edge features + block tables in 9 launches.

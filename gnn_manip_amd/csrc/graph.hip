@@ -63,13 +63,9 @@ ProfScope::~ProfScope() {
 }
 
 // ------------------------------------------------------------------------------------------
-// exclusive scan of int32, n known on the host or read from device memory
+// block-wide scan helpers
 // ------------------------------------------------------------------------------------------
 constexpr int SCAN_BLOCK = 256;
-constexpr int SCAN_ITEMS = 4;
-constexpr int SCAN_TILE = SCAN_BLOCK * SCAN_ITEMS;
-
-size_t scan_tmp_ints(int64_t n_max) { return (size_t)cdiv(n_max, SCAN_TILE) + 1; }
 
 __device__ __forceinline__ int wave_incl_scan(int v, int lane) {
 #pragma unroll
@@ -97,111 +93,6 @@ __device__ __forceinline__ int block_excl_scan(int v, int* sm, int* total) {
     __syncthreads();
     *total = tot;
     return base + incl - v;
-}
-
-__global__ void __launch_bounds__(SCAN_BLOCK) scan_reduce_kernel(const int* __restrict__ in, int64_t n_host,
-                                                                  const int* __restrict__ n_dev,
-                                                                  int* __restrict__ tmp) {
-    __shared__ int sm[4];
-    const int64_t n = n_dev ? (int64_t)(*n_dev) : n_host;
-    const int64_t base = (int64_t)blockIdx.x * SCAN_TILE;
-    if (base >= n) return;
-    int v = 0;
-#pragma unroll
-    for (int k = 0; k < SCAN_ITEMS; ++k) {
-        int64_t i = base + (int64_t)threadIdx.x * SCAN_ITEMS + k;
-        if (i < n) v += in[i];
-    }
-    int tot;
-    block_excl_scan(v, sm, &tot);
-    if (threadIdx.x == 0) tmp[blockIdx.x] = tot;
-}
-
-// second pass: every block adds up the tile sums in front of its tile itself (a few hundred values at most: cheaper than a
-// launch of its own for a one-block scan of them), scans its tile and -- the block that holds the last item -- writes the total
-__global__ void __launch_bounds__(SCAN_BLOCK) scan_apply_kernel(const int* in, int64_t n_host,
-                                                                 const int* __restrict__ n_dev,
-                                                                 const int* __restrict__ tmp, int* out, int* total_out) {
-    __shared__ int sm[4];
-    const int64_t n = n_dev ? (int64_t)(*n_dev) : n_host;
-    const int64_t base = (int64_t)blockIdx.x * SCAN_TILE;
-    if (base >= n) return;
-    int item[SCAN_ITEMS];
-    int v = 0;
-#pragma unroll
-    for (int k = 0; k < SCAN_ITEMS; ++k) {
-        int64_t i = base + (int64_t)threadIdx.x * SCAN_ITEMS + k;
-        item[k] = i < n ? in[i] : 0;
-        v += item[k];
-    }
-    int before = 0;
-    for (int i = threadIdx.x; i < (int)blockIdx.x; i += SCAN_BLOCK) before += tmp[i];
-    int prefix;
-    (void)block_excl_scan(before, sm, &prefix);   // prefix = sum of the tile sums of the blocks in front
-    int tot;
-    int ex = block_excl_scan(v, sm, &tot) + prefix;
-#pragma unroll
-    for (int k = 0; k < SCAN_ITEMS; ++k) {
-        int64_t i = base + (int64_t)threadIdx.x * SCAN_ITEMS + k;
-        if (i < n) out[i] = ex;
-        if (total_out && i == n - 1) *total_out = ex;   // callers that ask for the total append a zero item: the last output is the sum
-        ex += item[k];
-    }
-}
-
-// small arrays: one 1024-thread block walks the array in chunks with a running carry (one launch instead
-// of three; at N = 5k every scan of the graph build is this small)
-constexpr int SCAN1_THREADS = 1024;
-constexpr int64_t SCAN1_MAX = 40000;  // one workgroup up to here (~10 us at 32k); above, the three-kernel scan (~15 us) wins
-__global__ void __launch_bounds__(SCAN1_THREADS) scan_single_kernel(const int* in, int64_t n, int* out, int* total_out) {
-    __shared__ int wsum[SCAN1_THREADS / 64];
-    __shared__ int carry_s;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) carry_s = 0;
-    __syncthreads();
-    for (int64_t b = 0; b < n; b += SCAN1_THREADS * SCAN_ITEMS) {
-        int item[SCAN_ITEMS];
-        int v = 0;
-#pragma unroll
-        for (int k = 0; k < SCAN_ITEMS; ++k) {
-            const int64_t i = b + (int64_t)threadIdx.x * SCAN_ITEMS + k;
-            item[k] = i < n ? in[i] : 0;
-            v += item[k];
-        }
-        const int incl = wave_incl_scan(v, lane);
-        if (lane == 63) wsum[wave] = incl;
-        __syncthreads();
-        int base = carry_s;
-        for (int w = 0; w < wave; ++w) base += wsum[w];
-        int ex = base + incl - v;
-#pragma unroll
-        for (int k = 0; k < SCAN_ITEMS; ++k) {
-            const int64_t i = b + (int64_t)threadIdx.x * SCAN_ITEMS + k;
-            if (i < n) out[i] = ex;
-            ex += item[k];
-        }
-        __syncthreads();
-        if (threadIdx.x == SCAN1_THREADS - 1) carry_s = base + incl;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0 && total_out) *total_out = carry_s;
-}
-
-// out may alias in.  Scans n items (n = *n_dev when n_dev != nullptr, bounded by n_max).  total_out (optional)
-// receives the sum; callers that ask for it append a zero item, so the sum is also the last output.
-int exclusive_scan_i32(const int* in, int* out, int64_t n_max, const int* n_dev, int* tmp, hipStream_t s, int* total_out) {
-    if (n_max <= 0) return GM_OK;
-    if (!n_dev && n_max <= SCAN1_MAX) {
-        hipLaunchKernelGGL(scan_single_kernel, dim3(1), dim3(SCAN1_THREADS), 0, s, in, n_max, out, total_out);
-        GM_LAUNCH_CHECK();
-        return GM_OK;
-    }
-    const int nb = (int)cdiv(n_max, SCAN_TILE);
-    GM_REQUIRE(!total_out || !n_dev, GM_ERR_INVALID_ARGUMENT, "exclusive_scan_i32: total_out needs a host-side length");
-    hipLaunchKernelGGL(scan_reduce_kernel, dim3(nb), dim3(SCAN_BLOCK), 0, s, in, n_max, n_dev, tmp);
-    hipLaunchKernelGGL(scan_apply_kernel, dim3(nb), dim3(SCAN_BLOCK), 0, s, in, n_max, n_dev, tmp, out, total_out);
-    GM_LAUNCH_CHECK();
-    return GM_OK;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -307,20 +198,22 @@ int launch_step_clear(const StepClear& c, hipStream_t s) {
     GM_LAUNCH_CHECK();
     return GM_OK;
 }
-void graph_clear_jobs(StepClear& c, const GraphWs& g, int64_t n) {
+int graph_clear_jobs(StepClear& c, const GraphWs& g, int64_t n) {
     c.gh = g.hdr;
-    c.add(g.cell_start, (long long)g.max_cells + 1, 0);   // counts -> offsets
-    c.add(g.cell_cursor, g.max_cells, 0);
-    c.add(g.cnt + n, 1, 0);                                // cnt[0 .. n) is written by the neighbour search; cnt[n] closes the scan
-    c.add(g.scan_cells, (long long)scan_state_ints((int64_t)g.max_cells + 1), 0);
-    c.add(g.scan_cnt, (long long)scan_state_ints(n + 1), 0);
+    int rc = c.add(g.cell_start, (long long)g.max_cells + 1, 0);   // counts -> offsets
+    if (rc == GM_OK) rc = c.add(g.cell_cursor, g.max_cells, 0);
+    if (rc == GM_OK) rc = c.add(g.cnt + n, 1, 0);                   // cnt[0 .. n) is written by the neighbour search; cnt[n] closes the scan
+    if (rc == GM_OK) rc = c.add(g.scan_cells, (long long)scan_state_ints((int64_t)g.max_cells + 1), 0);
+    if (rc == GM_OK) rc = c.add(g.scan_cnt, (long long)scan_state_ints(n + 1), 0);
+    return rc;
 }
-void csr_clear_jobs(StepClear& c, const CsrWs& w, int64_t n, int flow) {
+int csr_clear_jobs(StepClear& c, const CsrWs& w, int64_t n, int flow) {
     c.ch = w.hdr;
     c.flow = flow;
-    c.add(w.in_ptr, n + 1, 0);
-    c.add(w.scan_in, (long long)scan_state_ints(n + 1), 0);
-    c.add(carve_edge_blocks(w.blocks, n, w.cap).stitch, n, -1);
+    int rc = c.add(w.in_ptr, n + 1, 0);
+    if (rc == GM_OK) rc = c.add(w.scan_in, (long long)scan_state_ints(n + 1), 0);
+    if (rc == GM_OK) rc = c.add(carve_edge_blocks(w.blocks, n, w.cap).stitch, n, -1);
+    return rc;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -360,7 +253,6 @@ CsrWs carve_csr(void* ws, int64_t n, int64_t cap) {
     w.dst = c.take<int>(cap);
     w.src = c.take<int>(cap);
     w.eid = c.take<int>(cap);
-    w.scan_tmp = c.take<int>(scan_tmp_ints(n + 1));
     w.scan_in = c.take<int>(scan_state_ints(n + 1));
     w.sort_tmp = c.take<int>(2 * (size_t)cap);   // copies of long segments (in-degree > 96) while they are rank-sorted
     w.cap = cap;
@@ -907,8 +799,8 @@ int cell_order(const float* pos, int64_t pos_stride, int64_t n, int64_t n_per, d
     GM_REQUIRE(graph_ws_bytes >= g.bytes, GM_ERR_WORKSPACE, "cell_order: workspace %zu < %zu", graph_ws_bytes, g.bytes);
     const int nb = (int)cdiv(n, 256);
     StepClear clr;
-    graph_clear_jobs(clr, g, n);
-    int rc = launch_step_clear(clr, s);
+    int rc = graph_clear_jobs(clr, g, n);
+    if (rc == GM_OK) rc = launch_step_clear(clr, s);
     if (rc != GM_OK) return rc;
     hipLaunchKernelGGL(bbox_kernel, dim3(nb < 64 ? nb : 64), dim3(256), 0, s, pos, pos_stride, n, g.hdr, conn_r, g.max_cells, n_per);
     hipLaunchKernelGGL(cell_assign_kernel, dim3(nb), dim3(256), 0, s, pos, pos_stride, n, g.hdr, g.cell_of, g.cell_start);
@@ -1019,8 +911,8 @@ int gm_radius_graph_build_batched(const float* pos, int64_t pos_stride, int64_t 
     GM_REQUIRE(ws_bytes >= g.bytes, GM_ERR_WORKSPACE, "gm_radius_graph_build: workspace %zu < %zu", ws_bytes, g.bytes);
     hipStream_t s = (hipStream_t)stream;
     StepClear clr;
-    graph_clear_jobs(clr, g, n);
-    rc = launch_step_clear(clr, s);
+    rc = graph_clear_jobs(clr, g, n);
+    if (rc == GM_OK) rc = launch_step_clear(clr, s);
     if (rc == GM_OK) rc = radius_graph_build_core(pos, pos_stride, n, n_per, conn_r, K, g, nullptr, nullptr, 0, s);
     if (rc != GM_OK) return rc;
     const ScanJob sj{g.cnt, g.out_ptr, (long long)n + 1, &g.hdr->n_edges, g.scan_cnt};
@@ -1104,8 +996,8 @@ int csr_from_graph_with_features(const void* graph_ws, int64_t n, int K, void* c
     GM_REQUIRE(csr_ws_bytes >= c.bytes, GM_ERR_WORKSPACE, "gm_csr_from_graph: workspace %zu < %zu", csr_ws_bytes, c.bytes);
     hipStream_t s = (hipStream_t)stream;
     StepClear clr;
-    csr_clear_jobs(clr, c, n, flow);
-    int rc = launch_step_clear(clr, s);
+    int rc = csr_clear_jobs(clr, c, n, flow);
+    if (rc == GM_OK) rc = launch_step_clear(clr, s);
     if (rc != GM_OK || n <= 0) return rc;
     hipLaunchKernelGGL(indeg_graph_kernel, dim3((unsigned)cdiv(cap, 256)), dim3(256), 0, s, g.cnt, g.nbr, n, K, flow, c.in_ptr, c.sort_tmp);
     return csr_tail(g, n, K, c, pos, pos_stride, conn_r, edge_attr, flow, false, s);
@@ -1159,9 +1051,9 @@ int csr_from_edge_index(const int64_t* ei, int64_t n, int64_t e, int flow, void*
     hipStream_t s = (hipStream_t)stream;
     {
         StepClear clr;
-        csr_clear_jobs(clr, c, n, flow);
-        clr.add(c.cursor, n + 1, 0);
-        const int rc = launch_step_clear(clr, s);
+        int rc = csr_clear_jobs(clr, c, n, flow);
+        if (rc == GM_OK) rc = clr.add(c.cursor, n + 1, 0);
+        if (rc == GM_OK) rc = launch_step_clear(clr, s);
         if (rc != GM_OK) return rc;
     }
     if (e > 0) {

@@ -349,7 +349,7 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_edge_kernel(const CsrHeade
             SYS_STAMP(t, 0);
             auto prepare = [&]() {   // accumulator = (P_i[dst] + P_j[src]) * T1: row-major sum -> tile -> accumulator layout
 #pragma unroll
-                for (int j = 0; j < 4; ++j) LDS(floatx4, ps_w + j * TILE_ROW_B) = pi[j] + pj[j];   // P arrives times T1 (NodeArgs::p_scale)
+                for (int j = 0; j < 4; ++j) LDS(floatx4, ps_w + j * TILE_ROW_B) = pi[j] + pj[j];   // P arrives times T1 (HmNodeArgs::p_scale)
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     const floatx4 v = LDS(floatx4, ps_r + 32 * g);
@@ -1074,7 +1074,7 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_node_kernel(const float* a
 // ------------------------------------------------------------------------------------------
 // Projections of a step's h for the NEXT step, weight-stationary: twelve waves, wave w = output block w of
 //   [ P_i | P_j | Q ] = h [ W_i | W_j | W_h ]^T + [ b1(phi_e) | 0 | b1(phi_v) ]      (3 x 128 outputs, 128 inputs)
-// P leaves at the scale of the edge kernel that adds it into its accumulators, Q at the node kernel's (NodeArgs::p_scale).  One
+// P leaves at the scale of the edge kernel that adds it into its accumulators, Q at the node kernel's (HmNodeArgs::p_scale).  One
 // block of 32 rows per tick and ONE barrier: rows of block x+2 requested, rows of block x+1 -> operand image (waves 0 .. 7, two
 // (row group, slab) units each), 24 MFMAs on the image of block x, accumulators -> the wave's own tile -> whole 128-byte lines.
 // ------------------------------------------------------------------------------------------
@@ -1457,7 +1457,7 @@ bool edge_sys_fits(int64_t n_nodes, int64_t edge_capacity) {
 constexpr uint64_t kStreamStoreBytes = (uint64_t)HEDGE_STREAM_MB << 20;
 int launch_edge_sys(const EdgeArgs& a, const EdgeBlocks& t, int64_t edge_capacity, hipStream_t s) {
     GM_REQUIRE(a.hdr && a.wstream_h3 && a.agg && a.side && !a.eid && !a.eid_out, GM_ERR_INVALID_ARGUMENT, "launch_edge_sys: unsupported argument combination");
-    GM_REQUIRE(a.P_prescaled, GM_ERR_INVALID_ARGUMENT, "launch_edge_sys: P must carry the weight scale of this step (NodeArgs::p_scale = edge_sys_p_scale(image))");
+    GM_REQUIRE(a.P_prescaled, GM_ERR_INVALID_ARGUMENT, "launch_edge_sys: P must carry the weight scale of this step (HmNodeArgs::p_scale = edge_sys_p_scale(image))");
     // the scatter-add addresses agg rows and side rows with 32-bit byte offsets from agg (carve_fwd puts them in one workspace)
     const uint64_t agg_bytes = ((uint64_t)(a.side - a.agg) + (uint64_t)(t.max_blocks / 4 + 1) * H) * 4;
     GM_REQUIRE(a.side >= a.agg && agg_bytes < (1ull << 32) && (uint64_t)a.n_nodes_tab * 2 * H * 4 < (1ull << 32), GM_ERR_INVALID_ARGUMENT,

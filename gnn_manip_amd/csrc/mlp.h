@@ -1,9 +1,11 @@
-// Argument blocks and launchers of the fused MLP kernels (mlp.hip), used by model.hip.
+// Argument block and launcher of the edge MLP kernels (mlp.hip), used by model.hip.
 #pragma once
 #include "common.h"
 
 namespace gm {
 
+// What the edge kernels read: launch_edge_sys / launch_edge_sys_enc (hedge.h) take it as is, the streamed path copies it into an
+// HmEdgeArgs (hmlp.h).
 struct EdgeArgs {
     const CsrHeader* hdr;  // device-side edge count (rollout path) or nullptr
     int n_edges_host;
@@ -17,51 +19,19 @@ struct EdgeArgs {
     float* agg;            // [N][H] pre-zeroed, or nullptr
     float* side;           // [n_groups][H] head partials of the scatter-add (hedge.h), sys / hm kernels
     const float* wstream_h3; // fp16 hi / lo image of the systolic kernel (hedge.h), or nullptr
-    const float* wstream_hm; // fp16 hi / lo Linear images of this MLP for the streamed kernels (hmlp.h), or nullptr
+    const float* wstream_hm; // fp16 hi / lo Linear images of this MLP for the streamed kernels (hmlp.h)
     const int* edge_blocks;  // block / chunk tables of the edge list (carve_edge_blocks), or nullptr
     int64_t n_nodes_tab;     // n_nodes the tables were carved for
     ProfState* prof;         // timing of this launch (gm_model_profile), or nullptr
-    int kernel_choice;       // 0 automatic, 5 systolic fp16 x 3, 6 streamed fp16 x 3
-    const float* bias;     // processor: biases of layers 2..; encoder: biases of layers 1..
     const float* ln_g;
     const float* ln_b;
     float eps;
     int residual;          // e_out = e' + e_in
     int discard_e_out;     // nobody reads e_out after this launch (the last step of a forward): a kernel may leave it unwritten
-    int P_prescaled;       // P was written times the systolic kernel's weight scale T1 (NodeArgs::p_scale): only that kernel may take the launch
+    int P_prescaled;       // P was written times the systolic kernel's weight scale T1 (HmNodeArgs::p_scale): that kernel's launch
     int k1;                // encoder: edge_dim
     int h_valid;           // the model's hidden_size (<= the width H the kernel runs at; LayerNorm statistics are over these features)
-    int zero_pad_rows;     // encoder: e_out is a forward's latent array -- keep kEdgePadRows zero rows behind row n_edges (hedge.h)
-    int* pad_rows_done;    // encoder: set to 1 when the launch has taken care of zero_pad_rows itself (else the caller launches zero_edge_pad_rows)
-};
-
-struct NodeArgs {
-    int n_nodes;
-    const float* x_in;     // mode 0: raw node features [N][k1]; mode 1/2: h [N][H]
-    int k1;
-    const float* agg;      // mode 1: [N][H]
-    const int* edge_blocks;  // mode 1: block tables whose stitch / head lists say which side-buffer rows to add to agg (hedge.h), or nullptr
-    int64_t n_nodes_tab, edge_capacity_tab;
-    const float* side;
-    int* err_flags;        // error flags of the forward (CsrHeader::error_flags: ERRF_SPLIT_RANGE), or nullptr
-    int h_valid;           // the model's hidden_size (<= the width H the kernel runs at)
-    float* h_out;          // [N][H] (may alias x_in)
-    int residual;
-    const float* wstream_hm;  // fp16 hi / lo Linear images of this MLP (hmlp.h), or nullptr
-    const float* tail_hm;     // images of the tail
-    ProfState* prof;
-    int kernel_choice;        // as EdgeArgs (the node MLPs always take the streamed fp16 x 3 kernel)
-    const float* bias;     // [NL+1][H]
-    const float* ln_g;
-    const float* ln_b;
-    float eps;
-    int tail;              // 0 none, 1 projection, 2 decoder
-    const float* proj_bias;  // [H] layer-1 bias of the next edge MLP
-    float* P_out;            // [N][2H]
-    const float* p_scale;    // device pointer to the power of two P_out is multiplied with (edge_sys_p_scale), or nullptr
-    const float* dec_bias;   // [NL][H] then [32] (out bias zero-padded)
-    float* dec_out;          // [N][out_dim]
-    int out_dim;
+    int zero_pad_rows;     // systolic encoder: e_out is a forward's latent array -- keep kEdgePadRows zero rows behind row n_edges (hedge.h)
 };
 
 struct VecJob {
@@ -76,9 +46,7 @@ struct VecJobs {
     VecJob job[kVecJobsMax];
 };
 int launch_vec_batch(const VecJobs& jobs, float* base, hipStream_t s);
-int launch_edge(int H, int NL, bool enc, const EdgeArgs& a, int64_t edge_capacity, hipStream_t s);
-// whether launch_edge hands this processor launch to the systolic kernel (which then expects P pre-scaled: NodeArgs::p_scale)
-bool edge_launch_is_sys(int H, int NL, const EdgeArgs& a, int64_t edge_capacity);
-int launch_node(int H, int NL, int mode, const NodeArgs& a, hipStream_t s);
+// sys: the systolic form (hedge.hip) that the forward's route chose for this MLP, else the streamed one (hmlp.hip)
+int launch_edge(int H, int NL, bool enc, bool sys, const EdgeArgs& a, int64_t edge_capacity, hipStream_t s);
 
 }  // namespace gm

@@ -5,6 +5,16 @@
 #include "common.h"
 #include "hmlp.h"
 
+namespace gm {
+// choices of gm_model_set_edge_kernel (ABI values; 1 .. 4 were the round-1 fp32 / bf16 x 6 kernels, removed in round 5)
+enum EdgeKernel : int {
+    EK_AUTO = 0,      // the systolic kernels where they exist and the graph fits them, the systolic node path from kSysNodeMinNodes
+    EK_SYS = 5,       // as EK_AUTO; needs the systolic images (hidden 128, num_layers 2)
+    EK_HM = 6,        // the streamed kernels everywhere
+    EK_SYS_ALL = 7,   // as EK_SYS, and the systolic node path at any graph size
+};
+}  // namespace gm
+
 struct gm_model {
     gm_model_desc d;
     int H, NL, M;                 // H: the model's hidden_size
@@ -21,9 +31,9 @@ struct gm_model {
     size_t hm_floats = 0, hm_enc_edge = 0, hm_enc_node = 0, hm_enc_node_tail = 0;
     std::vector<size_t> hm_edge, hm_node, hm_node_tail;
     std::vector<size_t> hm_node_q;   // Linear image of Q = h W_h^T + b1 of node step k (systolic node path: hedge.h)
-    bool legacy = false;         // hidden 64 / 128 / 256: the bf16 x 3 streams (packed_t3) of the training kernels exist
+    bool has_train_streams = false;   // hidden 64 / 128 / 256: the bf16 x 3 streams (packed_t3) of the training kernels exist
     gm::ProfState* prof = nullptr;  // gm_model_profile
-    int edge_kernel = 0;         // processor edge kernel of this model: 0 automatic, 5 / 6 see gm_model_set_edge_kernel
+    int edge_kernel = gm::EK_AUTO;   // gm_model_set_edge_kernel: which kernels the forwards of this model may take (gm::EdgeKernel)
     float* vec = nullptr;     // per-MLP contiguous [bias_0..bias_NL, ln_gamma, ln_beta]
     size_t vec_floats = 0;
     // vec offsets (floats): start of MLP block

@@ -73,8 +73,8 @@ size_t tensor_floats(const gm_model* m, int ti) {
 }
 
 // (re)build the operand images + vec from the caller's tensors (device pointers)
-constexpr int kPackCommon = 1;      // vec + the training streams (+ the fp32 images of development builds)
-constexpr int kPackInference = 2;   // packed_hm, packed_h3 (+ the bf16 x 6 image of development builds)
+constexpr int kPackCommon = 1;      // vec + the training streams
+constexpr int kPackInference = 2;   // packed_hm, packed_h3
 int load_weights_device(gm_model* m, const float* const* T, hipStream_t s, int what) {
     // H: the width the kernels run at (hidden_size zero-padded to 64 / 128 / 256: strides, image sizes); Hv: the model's hidden_size
     const int H = m->Hp, Hv = m->H, NL = m->NL, M = m->M;
@@ -149,7 +149,7 @@ int load_weights_device(gm_model* m, const float* const* T, hipStream_t s, int w
     }
 
     if (what & kPackCommon) {
-    // biases + LayerNorm vectors (fp32 kernels, training, LayerNorm of every kernel)
+    // biases + LayerNorm vectors (training, LayerNorm of every kernel)
     VecJobs vj;
     vj.n = 0;
     auto flush_vec = [&]() {
@@ -349,7 +349,7 @@ int gm_model_create(const gm_model_desc* desc, const float* const* tensors, int 
     const int NL = m->NL = desc->num_layers, M = m->M = desc->m_steps;
     if (desc->col_i || desc->col_j || desc->col_e) { m->ci = desc->col_i; m->cj = desc->col_j; m->ce = desc->col_e; }
     if (desc->node_agg_first) { m->ch = 1; m->ca = 0; }
-    m->legacy = m->H == 64 || m->H == 128 || m->H == 256;   // widths the fp32 training kernels (and their operand images) exist for
+    m->has_train_streams = m->H == 64 || m->H == 128 || m->H == 256;   // widths the training kernels (and their bf16 x 3 streams) exist for
     {   // bf16 x 3 streams of the training kernels, one MLP after the other
         m->T_HH = layer_stages_b3(H, H);
         m->T_e0 = layer_stages_b3(desc->edge_dim, H);
@@ -409,8 +409,8 @@ int gm_model_create(const gm_model_desc* desc, const float* const* tensors, int 
         gm_model_destroy(m);
         return GM_ERR_HIP;
     }
-    m->edge_kernel = 0;   // automatic; gm_model_set_edge_kernel changes it per handle (no process-wide switch)
-    if ((m->legacy && hipMalloc(&m->packed_t3, m->packed_t3_floats * sizeof(float)) != hipSuccess) ||
+    m->edge_kernel = EK_AUTO;   // gm_model_set_edge_kernel changes it per handle (no process-wide switch)
+    if ((m->has_train_streams && hipMalloc(&m->packed_t3, m->packed_t3_floats * sizeof(float)) != hipSuccess) ||
         hipMalloc(&m->vec, m->vec_floats * sizeof(float)) != hipSuccess) {
         gm::set_error("gm_model_create: hipMalloc failed");
         gm_model_destroy(m);
@@ -459,75 +459,106 @@ size_t gm_block_workspace_bytes(const gm_model_desc* desc, int64_t n, int64_t ca
 
 namespace {
 
+// Which form each MLP of one forward takes: decided once per forward, followed by every launch of it.  The systolic kernels
+// (hedge.h) exist for hidden 128 / num_layers 2 (packed_h3); the streamed ones (hmlp.h) take every other launch.
+struct Route {
+    bool sys_enc;    // edge encoder: sys_enc_kernel, which zeroes the pad rows behind the edge list itself (else hm_edge_kernel)
+    bool sys_edge;   // processor edge: sys_edge_kernel, which reads P pre-scaled by its image's T1 (else hm_edge_kernel)
+    bool sys_node;   // processor node: sys_node_kernel + sys_proj_kernel, then the streamed decoder (else hm_node_kernel and its tail)
+};
+enum class Entry { Fused, Independent, Block };   // gm_epd_forward / gm_rollout_step, gm_graph_independent_forward, gm_interaction_network_forward
+// attr_sorted: the raw edge features are in sorted order (no eid gather); n_per_graph: nodes of ONE graph of a block-diagonal batch, or n
+Route route_forward(const gm_model* m, Entry entry, int64_t n, int64_t n_per_graph, int64_t cap, bool attr_sorted) {
+    // the systolic kernels need rows in sorted order behind a CSR header's device-side edge count: the fused forward's (the
+    // independent forward has no header, a block forward reads its edge rows through eid)
+    const bool sys = entry == Entry::Fused && m->packed_h3 && m->edge_kernel != EK_HM;
+    Route r;
+    r.sys_enc = sys && attr_sorted && m->d.edge_dim == 4;
+    r.sys_edge = sys && cap > 0 && edge_sys_fits(n, cap);   // larger graphs than its 32-bit offsets cover take the streamed kernel
+    // by the size of ONE graph, not of the batch (batch invariance: hedge.h, kSysNodeMinNodes)
+    r.sys_node = r.sys_edge && (m->edge_kernel == EK_SYS_ALL || (n_per_graph > 0 ? n_per_graph : n) >= kSysNodeMinNodes);
+    return r;
+}
+
+// LayerNorm of the MLP whose vec block starts at voff ([bias_0 .. bias_NL, gamma, beta])
+template <class A>
+void set_ln(const gm_model* m, A& a, size_t voff) {
+    const float* v = m->vec + voff;
+    a.ln_g = v + (size_t)(m->NL + 1) * m->Hp; a.ln_b = v + (size_t)(m->NL + 2) * m->Hp; a.eps = m->d.ln_eps;
+}
+
 EdgeArgs enc_edge_args(const gm_model* m, const float* edge_attr, const int* eid, const CsrHeader* hdr, int e_host, float* e_out) {
     EdgeArgs a{};
     a.hdr = hdr; a.n_edges_host = e_host; a.eid = eid;
     a.e_in = edge_attr; a.e_out = e_out; a.k1 = m->d.edge_dim;
     a.wstream_hm = m->packed_hm + m->hm_enc_edge;
     a.wstream_h3 = m->packed_h3 ? m->packed_h3 + (size_t)m->M * h3_image_floats() : nullptr;   // the encoder's image follows the steps'
-    a.kernel_choice = m->edge_kernel; a.prof = m->prof;
-    const float* v = m->vec + m->v_enc_edge;
-    a.bias = v; a.ln_g = v + (size_t)(m->NL + 1) * m->Hp; a.ln_b = v + (size_t)(m->NL + 2) * m->Hp; a.eps = m->d.ln_eps;
+    a.prof = m->prof;
+    set_ln(m, a, m->v_enc_edge);
     a.h_valid = m->H;
     return a;
 }
-EdgeArgs proc_edge_args(const gm_model* m, int k, const CsrWs& c, int64_t n, const CsrHeader* hdr, int e_host, const int* eid,
-                        const float* P, const float* e_in, float* e_out, float* agg, float* side, int residual) {
+EdgeArgs proc_edge_args(const gm_model* m, int k, const CsrWs& c, int64_t n, const int* eid, const float* P, const float* e_in,
+                        float* e_out, float* agg, float* side, int residual) {
     EdgeArgs a{};
-    a.hdr = hdr; a.n_edges_host = e_host; a.dst = c.dst; a.src = c.src; a.eid = eid; a.eid_out = eid;
+    a.hdr = c.hdr; a.dst = c.dst; a.src = c.src; a.eid = eid; a.eid_out = eid;
     a.P = P; a.e_in = e_in; a.e_out = e_out; a.agg = agg; a.side = side; a.residual = residual;
     a.wstream_hm = m->packed_hm + m->hm_edge[k];
     a.wstream_h3 = m->packed_h3 ? m->packed_h3 + (size_t)k * h3_image_floats() : nullptr;
     a.edge_blocks = c.blocks;
     a.n_nodes_tab = n;
-    a.kernel_choice = m->edge_kernel; a.prof = m->prof;
-    const float* v = m->vec + m->v_edge[k];
-    a.bias = v + m->Hp;  // layer-1 bias lives in P_i
-    a.ln_g = v + (size_t)(m->NL + 1) * m->Hp; a.ln_b = v + (size_t)(m->NL + 2) * m->Hp; a.eps = m->d.ln_eps;
+    a.prof = m->prof;
+    set_ln(m, a, m->v_edge[k]);
     a.h_valid = m->H;
     return a;
 }
-void set_tail(const gm_model* m, NodeArgs& a, int next_edge_step /* -1: none, M: decoder */, float* P, float* out, bool sys_edge = false) {
-    if (next_edge_step < 0) { a.tail = 0; return; }
-    // P for a step the systolic edge kernel takes leaves the node kernel at that kernel's weight scale
-    a.p_scale = (sys_edge && next_edge_step < m->M && m->packed_h3) ? edge_sys_p_scale(m->packed_h3 + (size_t)next_edge_step * h3_image_floats()) : nullptr;
-    a.tail_hm = m->packed_hm + (next_edge_step == 0 ? m->hm_enc_node_tail : m->hm_node_tail[next_edge_step - 1]);
-    if (next_edge_step < m->M) {
+
+// The streamed node kernel (hmlp.h, launch_node_hm): mode 0 the encoder, mode 1 a processor step, mode 2 a tail alone.
+HmNodeArgs node_args(const gm_model* m, int64_t n, const float* x_in, int* flags) {
+    HmNodeArgs a{};
+    a.n_nodes = (int)n; a.x_in = x_in; a.nl = m->NL; a.h_valid = m->H; a.flags = flags; a.prof = m->prof;
+    return a;
+}
+HmNodeArgs enc_node_args(const gm_model* m, int64_t n, const float* x, float* h_out, int* flags) {
+    HmNodeArgs a = node_args(m, n, x, flags);
+    a.k1 = m->d.node_dim; a.h_out = h_out;
+    a.w = m->packed_hm + m->hm_enc_node;
+    set_ln(m, a, m->v_enc_node);
+    return a;
+}
+// node MLP of step k on [h | agg], agg completed by the head partials of the edge kernel's scatter-add (hedge.h) in the same launch
+HmNodeArgs proc_node_args(const gm_model* m, int k, const CsrWs& c, int64_t n, int64_t cap, const float* h, const float* agg,
+                          const float* side, float* h_out, int residual) {
+    HmNodeArgs a = node_args(m, n, h, &c.hdr->error_flags);
+    a.agg = agg; a.h_out = h_out; a.residual = residual;
+    a.w = m->packed_hm + m->hm_node[k];
+    set_ln(m, a, m->v_node[k]);
+    const EdgeBlocks t = carve_edge_blocks(c.blocks, n, cap);
+    a.stitch = t.stitch; a.head = t.head; a.side = side; a.tab = t.hdr;
+    return a;
+}
+// the tail behind a node MLP: the projection P of edge step `next` (< M), or the decoder (next == M).  p_scaled: the systolic edge
+// kernel takes that step, and P leaves at its weight scale
+void set_tail(const gm_model* m, HmNodeArgs& a, int next, float* P, float* out, bool p_scaled) {
+    a.w_tail = m->packed_hm + (next == 0 ? m->hm_enc_node_tail : m->hm_node_tail[next - 1]);
+    if (next < m->M) {
         a.tail = 1;
-        a.proj_bias = m->vec + m->v_edge[next_edge_step];
         a.P_out = P;
+        a.p_scale = p_scaled ? edge_sys_p_scale(m->packed_h3 + (size_t)next * h3_image_floats()) : nullptr;
     } else {
         a.tail = 2;
-        a.dec_bias = m->vec + m->v_dec;
         a.dec_out = out;
         a.out_dim = m->d.out_dim;
     }
 }
+HmNodeArgs tail_args(const gm_model* m, int next, int64_t n, const float* h, float* P, float* out, int* flags) {
+    HmNodeArgs a = node_args(m, n, h, flags);
+    set_tail(m, a, next, P, out, false);
+    return a;
+}
 
-}  // namespace
-
-extern "C" {
-
-}  // extern "C"
-
-namespace {
 // agg_cleared: the caller's first launch has zeroed agg (the rollout step's StepClear); n_per_graph: nodes of ONE graph of a
 // block-diagonal batch of equal-sized graphs (the kernel choice must not depend on how many graphs share the call), or n
-int epd_forward_impl(const gm_model* m, const float* nodes, int64_t n, const float* edge_attr, int attr_is_csr_order,
-                     const void* csr_ws, int64_t cap, float* out, void* fwd_ws, size_t fwd_ws_bytes, void* stream, bool agg_cleared,
-                     int64_t n_per_graph);
-}
-
-extern "C" {
-
-int gm_epd_forward(const gm_model* m, const float* nodes, int64_t n, const float* edge_attr, int attr_is_csr_order,
-                   const void* csr_ws, int64_t cap, float* out, void* fwd_ws, size_t fwd_ws_bytes, void* stream) {
-    return epd_forward_impl(m, nodes, n, edge_attr, attr_is_csr_order, csr_ws, cap, out, fwd_ws, fwd_ws_bytes, stream, false, n);
-}
-
-}  // extern "C"
-
-namespace {
 int epd_forward_impl(const gm_model* m, const float* nodes, int64_t n, const float* edge_attr, int attr_is_csr_order,
                      const void* csr_ws, int64_t cap, float* out, void* fwd_ws, size_t fwd_ws_bytes, void* stream, bool agg_cleared,
                      int64_t n_per_graph) {
@@ -540,48 +571,40 @@ int epd_forward_impl(const gm_model* m, const float* nodes, int64_t n, const flo
     FwdWs f = carve_fwd(fwd_ws, H, n, cap, cap);
     GM_REQUIRE(fwd_ws_bytes >= f.bytes, GM_ERR_WORKSPACE, "gm_epd_forward: workspace %zu < %zu", fwd_ws_bytes, f.bytes);
     CsrWs c = carve_csr(const_cast<void*>(csr_ws), n, cap);
+    int* flags = &c.hdr->error_flags;
     hipStream_t s = (hipStream_t)stream;
     int rc = ensure_inference_images(m, s);
     if (rc != GM_OK) return rc;
-    int pad_done = 0;
+    const Route route = route_forward(m, Entry::Fused, n, n_per_graph, cap, attr_is_csr_order != 0);
     {
         EdgeArgs ee = enc_edge_args(m, edge_attr, attr_is_csr_order ? nullptr : c.eid, c.hdr, 0, f.e);
         ee.zero_pad_rows = 1;
-        ee.pad_rows_done = &pad_done;
-        rc = launch_edge(H, NL, true, ee, cap, s);
+        rc = launch_edge(H, NL, true, route.sys_enc, ee, cap, s);
     }
     if (rc != GM_OK) return rc;
-    if (cap > 0 && !pad_done) {
+    if (cap > 0 && !route.sys_enc) {
         ProfScope prof(m->prof, PROF_REST, s);
         rc = zero_edge_pad_rows(c.hdr, f.e, H, s);
         if (rc != GM_OK) return rc;
     }
-    NodeArgs na{};
-    na.h_valid = m->H;
-    na.n_nodes = (int)n; na.x_in = nodes; na.k1 = m->d.node_dim; na.h_out = f.h;
-    na.wstream_hm = m->packed_hm + m->hm_enc_node; na.kernel_choice = m->edge_kernel; na.prof = m->prof;
-    na.err_flags = &c.hdr->error_flags;
-    const float* v = m->vec + m->v_enc_node;
-    na.bias = v; na.ln_g = v + (size_t)(NL + 1) * H; na.ln_b = v + (size_t)(NL + 2) * H; na.eps = m->d.ln_eps;
-    // which kernel the processor edge launches of this forward take (the same for every step: it depends on sizes and the handle's choice)
-    const bool sys_edge = cap > 0 && edge_launch_is_sys(H, NL, proc_edge_args(m, 0, c, n, c.hdr, 0, nullptr, f.P, f.e, f.e, f.agg, f.side, 1), cap);
-    // The systolic node path (hedge.h): graphs with enough 32-row blocks per workgroup to pipeline (or the handle's choice 7).  Its
-    // node MLP takes the h half of its first Linear as Q, written with P by the projection kernel behind every step.
-    const bool sys_node = sys_edge && m->packed_h3 && (m->edge_kernel == 7 || (n_per_graph > 0 ? n_per_graph : n) >= kSysNodeMinNodes);
+    // The systolic node path (hedge.h) takes the h half of its node MLP's first Linear as Q, written with P by the projection kernel
+    // behind every step.
     const size_t h3f = h3_image_floats();
     auto project = [&](int k) {   // h -> P of edge step k, Q of node step k
         ProjSysArgs pa{};
-        pa.h = f.h; pa.P = f.P; pa.Q = f.Q; pa.n = (int)n; pa.flags = &c.hdr->error_flags; pa.prof = m->prof;
+        pa.h = f.h; pa.P = f.P; pa.Q = f.Q; pa.n = (int)n; pa.flags = flags; pa.prof = m->prof;
         pa.img_p = m->packed_hm + (k == 0 ? m->hm_enc_node_tail : m->hm_node_tail[k - 1]);
         pa.img_q = m->packed_hm + m->hm_node_q[k];
         pa.scale_p = edge_sys_p_scale(m->packed_h3 + (size_t)k * h3f);
         pa.scale_q = edge_sys_p_scale(m->packed_h3 + (size_t)(M + 1 + k) * h3f);
         return launch_proj_sys(pa, s);
     };
-    if (sys_node) na.tail = 0;
-    else set_tail(m, na, 0, f.P, out, sys_edge);
-    rc = launch_node(H, NL, 0, na, s);
-    if (rc == GM_OK && sys_node) rc = project(0);
+    {
+        HmNodeArgs na = enc_node_args(m, n, nodes, f.h, flags);
+        if (!route.sys_node) set_tail(m, na, 0, f.P, out, route.sys_edge);
+        rc = launch_node_hm(H, 0, na, s);
+    }
+    if (rc == GM_OK && route.sys_node) rc = project(0);
     if (rc != GM_OK) return rc;
     // agg is zeroed once (nodes without in-edges read zeros; rows with in-edges are stored whole by every edge launch)
     if (!agg_cleared) {
@@ -589,39 +612,25 @@ int epd_forward_impl(const gm_model* m, const float* nodes, int64_t n, const flo
         GM_HIP_CHECK(hipMemsetAsync(f.agg, 0, (size_t)n * H * sizeof(float), s));
     }
     for (int k = 0; k < M; ++k) {
-        EdgeArgs ea = proc_edge_args(m, k, c, n, c.hdr, 0, nullptr, f.P, f.e, f.e, f.agg, f.side, 1);
+        EdgeArgs ea = proc_edge_args(m, k, c, n, nullptr, f.P, f.e, f.e, f.agg, f.side, 1);
         ea.discard_e_out = k + 1 == M;   // the decoder reads h only (epd_gnn.py:96): the last step's e + e' is never looked at
-        ea.P_prescaled = sys_edge;
-        rc = launch_edge(H, NL, false, ea, cap, s);
+        ea.P_prescaled = route.sys_edge;
+        rc = launch_edge(H, NL, false, route.sys_edge, ea, cap, s);
         if (rc != GM_OK) return rc;
-        if (sys_node) {
+        if (route.sys_node) {
             // head partials of the scatter-add into agg, the node MLP (h in place), then the next step's projections -- or the decoder
             rc = launch_agg_stitch(f.agg, f.side, carve_edge_blocks(c.blocks, n, cap), n, m->prof, s);
             NodeSysArgs ns{};
             ns.h = f.h; ns.agg = f.agg; ns.Q = f.Q; ns.h_out = f.h; ns.image = m->packed_h3 + (size_t)(M + 1 + k) * h3f;
-            ns.n = (int)n; ns.flags = &c.hdr->error_flags; ns.eps = m->d.ln_eps; ns.prof = m->prof;
+            ns.n = (int)n; ns.flags = flags; ns.eps = m->d.ln_eps; ns.prof = m->prof;
             if (rc == GM_OK) rc = launch_node_sys(ns, s);
             if (rc == GM_OK && k + 1 < M) rc = project(k + 1);
-            if (rc == GM_OK && k + 1 == M) {
-                NodeArgs d{};
-                d.h_valid = m->H; d.n_nodes = (int)n; d.x_in = f.h; d.err_flags = &c.hdr->error_flags;
-                d.kernel_choice = m->edge_kernel; d.prof = m->prof;
-                set_tail(m, d, M, f.P, out);
-                rc = launch_node(H, NL, 3, d, s);
-            }
-            if (rc != GM_OK) return rc;
-            continue;
+            if (rc == GM_OK && k + 1 == M) rc = launch_node_hm(H, 2, tail_args(m, M, n, f.h, f.P, out, flags), s);
+        } else {
+            HmNodeArgs a = proc_node_args(m, k, c, n, cap, f.h, f.agg, f.side, f.h, 1);
+            set_tail(m, a, k + 1, f.P, out, route.sys_edge);
+            rc = launch_node_hm(H, 1, a, s);
         }
-        NodeArgs a{};
-        a.h_valid = m->H;
-        a.n_nodes = (int)n; a.x_in = f.h; a.agg = f.agg; a.h_out = f.h; a.residual = 1;
-        a.edge_blocks = c.blocks; a.n_nodes_tab = n; a.edge_capacity_tab = cap; a.side = f.side;
-        a.err_flags = &c.hdr->error_flags;
-        a.wstream_hm = m->packed_hm + m->hm_node[k]; a.kernel_choice = m->edge_kernel; a.prof = m->prof;
-        const float* vn = m->vec + m->v_node[k];
-        a.bias = vn; a.ln_g = vn + (size_t)(NL + 1) * H; a.ln_b = vn + (size_t)(NL + 2) * H; a.eps = m->d.ln_eps;
-        set_tail(m, a, k + 1, f.P, out, sys_edge);
-        rc = launch_node(H, NL, 1, a, s);
         if (rc != GM_OK) return rc;
     }
     return GM_OK;
@@ -629,6 +638,11 @@ int epd_forward_impl(const gm_model* m, const float* nodes, int64_t n, const flo
 }  // namespace
 
 extern "C" {
+
+int gm_epd_forward(const gm_model* m, const float* nodes, int64_t n, const float* edge_attr, int attr_is_csr_order,
+                   const void* csr_ws, int64_t cap, float* out, void* fwd_ws, size_t fwd_ws_bytes, void* stream) {
+    return epd_forward_impl(m, nodes, n, edge_attr, attr_is_csr_order, csr_ws, cap, out, fwd_ws, fwd_ws_bytes, stream, false, n);
+}
 
 int gm_graph_independent_forward(const gm_model* m, const float* x, int64_t n, const float* edge_attr, int64_t e,
                                  float* h_out, float* e_out, void* stream) {
@@ -639,16 +653,10 @@ int gm_graph_independent_forward(const gm_model* m, const float* x, int64_t n, c
     hipStream_t s = (hipStream_t)stream;
     int rc = ensure_inference_images(m, s);
     if (rc != GM_OK) return rc;
-    rc = launch_edge(m->Hp, m->NL, true, enc_edge_args(m, edge_attr, nullptr, nullptr, (int)e, e_out), e, s);
-    if (rc != GM_OK) return rc;
-    NodeArgs na{};
-    na.h_valid = m->H;
-    na.n_nodes = (int)n; na.x_in = x; na.k1 = m->d.node_dim; na.h_out = h_out;
-    na.wstream_hm = m->packed_hm + m->hm_enc_node; na.kernel_choice = m->edge_kernel; na.prof = m->prof;
-    const float* v = m->vec + m->v_enc_node;
-    na.bias = v; na.ln_g = v + (size_t)(m->NL + 1) * m->Hp; na.ln_b = v + (size_t)(m->NL + 2) * m->Hp; na.eps = m->d.ln_eps;
-    na.tail = 0; na.h_valid = m->H;
-    return launch_node(m->Hp, m->NL, 0, na, s);
+    const Route route = route_forward(m, Entry::Independent, n, n, e, true);
+    rc = launch_edge(m->Hp, m->NL, true, route.sys_enc, enc_edge_args(m, edge_attr, nullptr, nullptr, (int)e, e_out), e, s);
+    if (rc != GM_OK || n == 0) return rc;
+    return launch_node_hm(m->Hp, 0, enc_node_args(m, n, x, h_out, nullptr), s);
 }
 
 int gm_interaction_network_forward(const gm_model* m, int k, const float* h, int64_t n, const float* e,
@@ -665,32 +673,16 @@ int gm_interaction_network_forward(const gm_model* m, int k, const float* h, int
     GM_REQUIRE(fwd_ws_bytes >= f.bytes, GM_ERR_WORKSPACE, "gm_interaction_network_forward: workspace %zu < %zu", fwd_ws_bytes, f.bytes);
     CsrWs c = carve_csr(const_cast<void*>(csr_ws), n, cap);
     hipStream_t s = (hipStream_t)stream;
-    {
-        const int rc_img = ensure_inference_images(m, s);
-        if (rc_img != GM_OK) return rc_img;
-    }
+    int rc = ensure_inference_images(m, s);
+    if (rc != GM_OK) return rc;
+    const Route route = route_forward(m, Entry::Block, n, n, cap, false);
     // projection P = h [W_i | W_j]^T (+ b1): the tail section of the preceding node stream
-    NodeArgs pa{};
-    pa.h_valid = m->H;
-    pa.n_nodes = (int)n; pa.x_in = h;
-    pa.kernel_choice = m->edge_kernel; pa.prof = m->prof;
-    pa.err_flags = &c.hdr->error_flags;
-    set_tail(m, pa, k, f.P, nullptr);
-    int rc = launch_node(H, NL, 2, pa, s);
+    rc = launch_node_hm(H, 2, tail_args(m, k, n, h, f.P, nullptr, &c.hdr->error_flags), s);
     if (rc != GM_OK) return rc;
     GM_HIP_CHECK(hipMemsetAsync(f.agg, 0, (size_t)n * H * sizeof(float), s));
-    rc = launch_edge(H, NL, false, proc_edge_args(m, k, c, n, c.hdr, 0, c.eid, f.P, e, e_out, f.agg, f.side, 0), cap, s);
+    rc = launch_edge(H, NL, false, route.sys_edge, proc_edge_args(m, k, c, n, c.eid, f.P, e, e_out, f.agg, f.side, 0), cap, s);
     if (rc != GM_OK) return rc;
-    NodeArgs a{};
-    a.h_valid = m->H;
-    a.n_nodes = (int)n; a.x_in = h; a.agg = f.agg; a.h_out = h_out; a.residual = 0;
-    a.edge_blocks = c.blocks; a.n_nodes_tab = n; a.edge_capacity_tab = cap; a.side = f.side;
-    a.err_flags = &c.hdr->error_flags;
-    a.wstream_hm = m->packed_hm + m->hm_node[k]; a.kernel_choice = m->edge_kernel; a.prof = m->prof;
-    const float* vn = m->vec + m->v_node[k];
-    a.bias = vn; a.ln_g = vn + (size_t)(NL + 1) * H; a.ln_b = vn + (size_t)(NL + 2) * H; a.eps = m->d.ln_eps;
-    a.tail = 0;
-    return launch_node(H, NL, 1, a, s);
+    return launch_node_hm(H, 1, proc_node_args(m, k, c, n, cap, h, f.agg, f.side, h_out, 0), s);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -747,10 +739,10 @@ extern "C" {
 
 int gm_model_set_edge_kernel(gm_model* m, int choice) {
     GM_REQUIRE(m, GM_ERR_INVALID_ARGUMENT, "gm_model_set_edge_kernel: null model");
-    GM_REQUIRE(choice >= 0 && choice <= 7, GM_ERR_INVALID_ARGUMENT, "gm_model_set_edge_kernel: choice %d out of range", choice);
-    GM_REQUIRE(choice == 0 || choice >= 5, GM_ERR_UNSUPPORTED,
+    GM_REQUIRE(choice >= EK_AUTO && choice <= EK_SYS_ALL, GM_ERR_INVALID_ARGUMENT, "gm_model_set_edge_kernel: choice %d out of range", choice);
+    GM_REQUIRE(choice == EK_AUTO || choice >= EK_SYS, GM_ERR_UNSUPPORTED,
                "gm_model_set_edge_kernel: choices 1..4 (the round-1 fp32 / bf16 x 6 kernels) were removed from the library (round 5)");
-    GM_REQUIRE((choice != 5 && choice != 7) || m->packed_h3, GM_ERR_UNSUPPORTED, "gm_model_set_edge_kernel: the systolic kernel is for hidden_size 128, num_layers 2");
+    GM_REQUIRE((choice != EK_SYS && choice != EK_SYS_ALL) || m->packed_h3, GM_ERR_UNSUPPORTED, "gm_model_set_edge_kernel: the systolic kernel is for hidden_size 128, num_layers 2");
     m->edge_kernel = choice;
     return GM_OK;
 }
@@ -808,10 +800,11 @@ int gm_rollout_step(const gm_model* m, float* obs, int64_t n, const gm_feature_d
     // destination-sort workspaces (headers, cell counts, in-degrees, scan states, stitch table) and the forward's agg rows
     {
         StepClear clr;
-        graph_clear_jobs(clr, carve_graph(r.graph, n, K), n);
-        csr_clear_jobs(clr, carve_csr(r.csr, n, cap), n, m->d.flow);
+        rc = graph_clear_jobs(clr, carve_graph(r.graph, n, K), n);
+        if (rc == GM_OK) rc = csr_clear_jobs(clr, carve_csr(r.csr, n, cap), n, m->d.flow);
         FwdWs f = carve_fwd(r.fwd, m->Hp, n, cap, cap);
-        clr.add(reinterpret_cast<int*>(f.agg), (long long)n * m->Hp, 0);
+        if (rc == GM_OK) rc = clr.add(reinterpret_cast<int*>(f.agg), (long long)n * m->Hp, 0);
+        if (rc != GM_OK) return rc;
         ProfScope prof(m->prof, PROF_REST, hs);
         rc = gm::rollout_pre_features(obs, n, fd, rigid_rank, rigid_target, r.x, hs, &clr);
     }
