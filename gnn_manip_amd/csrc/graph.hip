@@ -1068,7 +1068,7 @@ int csr_from_edge_index(const int64_t* ei, int64_t n, int64_t e, int flow, void*
         hipLaunchKernelGGL(segment_sort_kernel, dim3((unsigned)cdiv(n, SEG_PER_WG)), dim3(256), 0, s, c.in_ptr, n, c.src, c.eid, c.hdr, nullptr, 3, 1.f, nullptr, 0, c.sort_tmp, c.sort_tmp + c.cap, BlockTabArgs{});
     GM_LAUNCH_CHECK();
     if (!with_blocks) return GM_OK;
-    return build_edge_blocks(c.in_ptr, c.dst, n, e, nullptr, (int)n, carve_edge_blocks(c.blocks, n, e), s);
+    return build_edge_blocks(c.in_ptr, c.dst, n, nullptr, (int)n, carve_edge_blocks(c.blocks, n, e), s);
 }
 }  // namespace gm
 

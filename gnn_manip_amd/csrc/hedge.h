@@ -36,8 +36,7 @@ size_t edge_groups_max(int64_t n_nodes, int64_t edge_capacity);   // rows of the
 EdgeBlocks carve_edge_blocks(int* base, int64_t n_nodes, int64_t edge_capacity);
 // in_ptr / dst: the destination-sorted edge structure; n_per_graph: device pointer (GraphHeader::n_per_graph of the
 // radius-graph build) or, if null, the host value (<= 0: one graph)
-int build_edge_blocks(const int* in_ptr, const int* dst, int64_t n_nodes, int64_t edge_capacity, const int* n_per_graph_dev,
-                      int n_per_graph_host, const EdgeBlocks& t, hipStream_t s);
+int build_edge_blocks(const int* in_ptr, const int* dst, int64_t n_nodes, const int* n_per_graph_dev, int n_per_graph_host, const EdgeBlocks& t, hipStream_t s);
 
 // ---- weight image of one processor step's phi_e for the systolic kernel
 constexpr int kPackH3Max = 16;

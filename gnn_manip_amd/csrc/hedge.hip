@@ -153,6 +153,11 @@ __device__ __forceinline__ int s_clamp0(int v, int hi) {
     return r;
 }
 
+// The systolic kernels' dynamic LDS (maps L_*, LE_*, LN_*, LP_* below).  sys_prologue, publish_ln_stats and LnGroup address it
+// through this array, as the kernels' own code does: through a char* parameter hipcc assumes the pointee's natural alignment and
+// schedules the edge epilogue differently.  The older helpers and vec_to_acc take it as a parameter (smem): vec_to_acc through the
+// array folds its LDS addresses differently inside edge role 2's tick loop.
+extern __shared__ __attribute__((aligned(16))) char smem[];
 #define LDS(T, off) (*reinterpret_cast<T*>(smem + (off)))
 // A lane-constant LDS / buffer base: made opaque so that hipcc addresses "base register + 16-bit immediate" instead of folding
 // every region offset into a register of its own (the DS immediate reaches 64 KiB, the regions lie further apart than that).
@@ -255,6 +260,114 @@ __device__ __forceinline__ void scan3(float& ya, float& yb, float& yc, float ypr
     }
 }
 
+// ---- scaffolding shared by the four systolic kernels (12 waves, weight-stationary, one 32-row block per tick)
+
+// [x, y): the units (blocks, or groups of 4 blocks) of the workgroup, numbered XCD-major or in launch order
+__device__ __forceinline__ int2 wg_range(int units, bool xcd_major) {
+    const int wg = xcd_major ? xcd_major_wg() : (int)blockIdx.x;
+    return make_int2((int)((long long)wg * units / gridDim.x), (int)((long long)(wg + 1) * units / gridDim.x));
+}
+
+// Prologue: the wave's weight registers -- fragments [slice][8 ks][2 parts][64 lanes] of the image; one_kgroup: the wave
+// multiplies k-group 0 only (its image holds zeros beyond) and loads that one --, LDS [0, zero_end) zeroed, n_vec floats of
+// vec to vec_b, and a workgroup barrier.  I: type of the fragment index (sys_proj_kernel's images, hmlp.h, are addressed with
+// size_t; the kernel reads its bias from global memory before the prologue).
+template <class I = int>
+__device__ __forceinline__ void sys_prologue(half8 (&wh)[8], half8 (&wl)[8], const half8* frag, int slice, bool one_kgroup, int zero_end, int vec_b, const float* vec, int n_vec) {
+    const int tid = threadIdx.x, lane0 = tid & 63;
+#pragma unroll
+    for (int ks = 0; ks < 8; ++ks) {
+        const int kq = one_kgroup ? 0 : ks;
+        wh[ks] = frag[(((I)slice * 8 + kq) * 2 + 0) * 64 + lane0];
+        wl[ks] = frag[(((I)slice * 8 + kq) * 2 + 1) * 64 + lane0];
+    }
+    // every buffer starts finite: the pipeline's fill / drain ticks compute on them
+    for (int i = tid; i < zero_end / 16; i += SYS_THREADS) LDS(uintx4, i * 16) = uintx4{0u, 0u, 0u, 0u};
+    for (int i = tid; i < n_vec; i += SYS_THREADS) LDS(float, vec_b + 4 * i) = vec[i];
+    // The weight registers must have ARRIVED before the tick loops: otherwise hipcc places their counted vmcnt waits at the first
+    // uses inside the loop, where (loads and stores share the counter, in issue order) they wait for the tick's own accesses.
+    __builtin_amdgcn_s_waitcnt(0x0f70);   // vmcnt(0), a form the compiler's wait-count bookkeeping sees
+    __syncthreads();
+}
+
+// Instruction arbitration: role 2 (Linear 3 + statistics, and the edge kernel's scatter-add scan) is the longest instruction
+// stream of a tick and role 0 feeds the pipeline.
+__device__ __forceinline__ void set_role_prio(int role) {
+    if (role == 2) __builtin_amdgcn_s_setprio(HEDGE_PRIO2);        // the builtin takes an immediate
+    else if (role == 0) __builtin_amdgcn_s_setprio(HEDGE_PRIO0);
+    else __builtin_amdgcn_s_setprio(HEDGE_PRIO1);
+}
+
+// 32 floats of a bias (this wave's output block jb) in accumulator layout, from the LDS vec block (vec_b: its byte address,
+// f: the slot's first float)
+__device__ __forceinline__ floatx16 vec_to_acc(char* smem, int vec_b, int f, int jb, int hi) {
+    floatx16 a;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const floatx4 v = LDS(floatx4, vec_b + (f + 32 * jb + 4 * hi + 8 * g) * 4);
+#pragma unroll
+        for (int tt = 0; tt < 4; ++tt) a[4 * g + tt] = v[tt];
+    }
+    return a;
+}
+
+// LayerNorm statistics of a block's scaled Linear-3 accumulators (W3 / b3 centred over the output features: variance = mean
+// square): sum of squares of this wave's 32 features of row n (16 per lane half) -> st_w; raw accumulators -> the Z tile at z_w
+__device__ __forceinline__ void publish_ln_stats(const floatx16& acc, unsigned st_w, unsigned z_w) {
+    float q = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) q = fmaf(acc[r], acc[r], q);
+    LDS(float, st_w) = sum_of_halves(q);
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        floatx4 z;
+#pragma unroll
+        for (int tt = 0; tt < 4; ++tt) z[tt] = acc[4 * g + tt];
+        LDS(floatx4, z_w + 32 * g) = z;
+    }
+}
+
+// One row group (8 rows, row-major quads: 8 lanes per row) of a LayerNorm + residual epilogue, in two steps that sit in
+// different MFMA slots: load() the rows' 1 / (T sigma) and raw Linear-3 outputs, then store() res_w e + gamma x_hat + beta to
+// rows r0 + 8 j .. r0 + 8 j + 7 of out and request the residual rows e of the next block (res_row: its first row in srd_e).
+struct LnGroup {
+    float k;
+    floatx4 z;
+    __device__ __forceinline__ void load(unsigned km, unsigned zt) {
+        k = LDS(float, km);
+        z = LDS(floatx4, zt);
+    }
+    template <int AUX>
+    __device__ __forceinline__ void store(float* out, unsigned r0, int j, int cnt, unsigned v_off, const floatx4& gm, const floatx4& bt, floatx4& e,
+                                          float res_w, srd_t srd_e, unsigned res_row) const {
+        floatx4 o;
+#pragma unroll
+        for (int tt = 0; tt < 4; ++tt) o[tt] = fmaf(e[tt], res_w, fmaf(z[tt] * k, gm[tt], bt[tt]));
+        // rows past the block's end (and every row of a fill / drain tick: cnt = 0) lie beyond the resource's byte count: dropped
+        // (the block's position is in the resource's base: gfx9 subtracts a scalar offset from the byte count)
+        bst4s<AUX>(make_srd(out + (size_t)(r0 + 8 * j) * H, (unsigned)s_clamp0(cnt - 8 * j, 8) * 512u), v_off, 0, o);
+        e = bld4(srd_e, v_off, res_row * 512 + j * 4096);   // a whole tick to arrive
+    }
+};
+
+// The tick loop: ticks FIRST .. last (+ 1), taken in pairs so that the parity of a tick -- which half of every double buffer
+// it uses -- is a compile-time constant (FIRST & 1 for the first of a pair).  A macro: written as a function, the loop is
+// optimised before hipcc inlines it into the kernel, and the tick bodies come out different (the range-check merge, the
+// loop guard).
+#define RUN_TICKS(FIRST, last, tick)                                                   \
+    _Pragma("unroll 1") for (int t_ = (FIRST); t_ <= (last); t_ += 2) {                \
+        tick(std::integral_constant<int, (FIRST) & 1>{}, t_);                          \
+        tick(std::integral_constant<int, 1 - ((FIRST) & 1)>{}, t_ + 1);                \
+    }
+
+// range check of the fp16 split (rng: set once an accumulator row turned NaN): one report per wave.  flags may be null, except
+// in the edge kernel: there it is the header's error word, &hdr->error_flags, and launch_edge_sys requires hdr (a null test
+// in that kernel changes how hipcc keeps rng in the tick loops).
+template <bool MAY_BE_NULL = true>
+__device__ __forceinline__ void report_split_range(int rng, int lane0, int* flags) {
+    if (rng && lane0 == 0 && (!MAY_BE_NULL || flags)) atomicOr(flags, ERRF_SPLIT_RANGE);
+}
+
 // WRITE_E = false: the launch whose e_out nobody reads (the last message-passing step of a forward: the decoder takes h only,
 // epd_gnn.py:96) -- LayerNorm statistics and the scatter-add run as always, the row-major epilogue (residual read, e + e', store)
 // does not exist: 1 GB less written and 1 GB less re-read at the target.
@@ -265,7 +378,6 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_edge_kernel(const CsrHeade
                                                                        const int2* __restrict__ a_blk, const int2* __restrict__ a_seg, const int* __restrict__ a_head,
                                                                        const EdgeBlockHeader* __restrict__ a_tab, unsigned a_side_off, unsigned a_agg_bytes, unsigned a_P_bytes,
                                                                        int* a_flags, float a_eps, int a_residual) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane0 = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 #ifdef HEDGE_FORCE_ROLE   // development: register census of one role (tools/kernel_resources.py ... -DHEDGE_FORCE_ROLE=k)
@@ -274,31 +386,15 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_edge_kernel(const CsrHeade
     const int role = wave >> 2, jb = wave & 3;
 #endif
     const int E = a_hdr->n_edges;
-    const int nchunks = a_tab->n_groups;   // the workgroup takes a contiguous range of whole groups (4 blocks each)
-    const int wg = xcd_major_wg();
-    const int c0 = (int)((long long)wg * nchunks / gridDim.x);
-    const int c1 = (int)((long long)(wg + 1) * nchunks / gridDim.x);
-    if (c1 <= c0) return;
-    const int b0 = 4 * c0, b1 = 4 * c1;
+    const int2 cr = wg_range(a_tab->n_groups, true);   // the workgroup takes a contiguous range of whole groups (4 blocks each)
+    if (cr.y <= cr.x) return;
+    const int b0 = 4 * cr.x, b1 = 4 * cr.y;
     const int nb = b1 - b0;
     if (nb <= 0) return;
     const float inv_T = a_hw[1];
-    const float* hvec = a_hw + HW_HEADER_FLOATS;
-    const half8* wimg = reinterpret_cast<const half8*>(a_hw + HW_HEADER_FLOATS + HW_VEC_FLOATS);
-
     half8 wh[8], wl[8];
-#pragma unroll
-    for (int ks = 0; ks < 8; ++ks) {
-        wh[ks] = wimg[(((role * 4 + jb) * 8 + ks) * 2 + 0) * 64 + lane0];
-        wl[ks] = wimg[(((role * 4 + jb) * 8 + ks) * 2 + 1) * 64 + lane0];
-    }
-    // every buffer starts finite: the pipeline's fill / drain ticks compute on them
-    for (int i = tid; i < L_ZERO_END / 16; i += SYS_THREADS) LDS(uintx4, i * 16) = uintx4{0u, 0u, 0u, 0u};
-    for (int i = tid; i < 4 * H; i += SYS_THREADS) LDS(float, L_VEC + 4 * i) = hvec[i];
-    // The weight registers must have ARRIVED before the tick loops: otherwise hipcc places their counted vmcnt waits at the first
-    // uses inside the loop, where (loads and stores share the counter, in issue order) they wait for the tick's own accesses.
-    __builtin_amdgcn_s_waitcnt(0x0f70);   // vmcnt(0), a form the compiler's wait-count bookkeeping sees
-    __syncthreads();
+    sys_prologue(wh, wl, reinterpret_cast<const half8*>(a_hw + HW_HEADER_FLOATS + HW_VEC_FLOATS), role * 4 + jb, false, L_ZERO_END, L_VEC,
+                      a_hw + HW_HEADER_FLOATS, 4 * H);
     auto ok = [&](int x) { return x >= b0 && x < b1; };
     auto clampb = [&](int x) { return x < b0 ? b0 : (x < b1 ? x : b1 - 1); };
     // The workgroup's edges are contiguous: its e rows and indices are addressed relative to its first edge, so the scalar
@@ -308,14 +404,7 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_edge_kernel(const CsrHeade
     const srd_t srd_ein = make_srd(a_e_in + (size_t)e0 * H, 0xffffffffu);
     const int n = lane0 & 31, hi = lane0 >> 5, rr = lane0 >> 3, cq = lane0 & 7;
     const unsigned v_eoff = opaque(rr * 512 + jb * 128 + cq * 16);   // row 8 j + rr of a block, this wave's 128-byte slab: + 4096 j by the scalar offset
-    std::integral_constant<int, 0> even;
-    std::integral_constant<int, 1> odd;
-
-    // Instruction arbitration: role 2 (Linear 3 + statistics + the scatter-add's scan) is the longest instruction stream of
-    // a tick and role 0 feeds the pipeline.
-    if (role == 2) __builtin_amdgcn_s_setprio(HEDGE_PRIO2);        // the builtin takes an immediate
-    else if (role == 0) __builtin_amdgcn_s_setprio(HEDGE_PRIO0);
-    else __builtin_amdgcn_s_setprio(HEDGE_PRIO1);
+    set_role_prio(role);
     if (role == 0) {
         // ------------------------------------------------------------------ role 0
         // Rows of a block are dealt to the lanes two ways: e rows as 8 j + rr (the image E's swizzle needs j in the high bits),
@@ -411,12 +500,8 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_edge_kernel(const CsrHeade
         // Ticks -1 .. nb + 2: one tick of fill (the e rows and indices of the first block come from the prologue), nb ticks in
         // which blocks enter, three that drain the pipeline: an even count (nb is a multiple of 4), taken as (odd, even) pairs --
         // at N = 5k a workgroup has 12 blocks, and every fill / drain tick counts.
-#pragma unroll 1
-        for (int t = -1; t <= nb + 1; t += 2) {
-            tick(odd, t);
-            tick(even, t + 1);
-        }
-        if (rng && lane0 == 0) atomicOr(a_flags, ERRF_SPLIT_RANGE);
+        RUN_TICKS(-1, nb + 1, tick);
+        report_split_range<false>(rng, lane0, a_flags);
     } else if (role == 1) {
         // ------------------------------------------------------------------ role 1
         // This role runs Linear 2 of block x-1 and its share of the epilogue of block x-3.
@@ -431,16 +516,7 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_edge_kernel(const CsrHeade
         // LayerNorm gamma / beta of this lane's feature quad and the bias of Linear 2 in accumulator layout: constant over the launch
         const floatx4 gm = LDS(floatx4, L_VEC + (2 * H + 32 * jb + 4 * cq) * 4);
         const floatx4 bt = LDS(floatx4, L_VEC + (3 * H + 32 * jb + 4 * cq) * 4);
-        floatx16 b2v;   // b2 T2 in accumulator layout: constant over the launch (this role has the registers)
-        auto init_acc = [&](floatx16& dstv) {
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const floatx4 v = LDS(floatx4, L_VEC + (32 * jb + 4 * hi + 8 * g) * 4);
-#pragma unroll
-                for (int tt = 0; tt < 4; ++tt) dstv[4 * g + tt] = v[tt];
-            }
-        };
-        init_acc(b2v);
+        const floatx16 b2v = vec_to_acc(smem, L_VEC, 0, jb, hi);   // b2 T2: constant over the launch (this role has the registers)
         const unsigned st_r = opaque(L_ST + n * 4);
         const unsigned km_w = opaque(L_KM + jb * 128 + n * 4), km_r = opaque(L_KM + jb * 128 + rr * 4);
         const unsigned z_r = opaque(L_Z + jb * TILE_B + rr * TILE_ROW_B + cq * 16);
@@ -458,23 +534,13 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_edge_kernel(const CsrHeade
             const int2 bi_n = a_blk[clampb(x)];         // requested now, used at the end of the tick: the barrier's wait for the
                                                         // scalar-memory counter then finds it done
             const unsigned rel_a = (unsigned)(st_a - e0), rel_b = (unsigned)(st_b - e0);
-            float kr;
-            floatx4 zq;
+            LnGroup lg;
             auto side = [&](int slot) {   // LayerNorm + e_out of block x-3, row group slot / SIDE_STRIDE
                 if (!WRITE_E || slot >= EPI_SPLIT * SIDE_STRIDE) return;   // the other row groups are role 2's (balance of the roles' ticks)
                 const int j = slot / SIDE_STRIDE;
-                if (slot % SIDE_STRIDE == 0) {
-                    kr = LDS(float, km_r + j * 32);
-                    zq = LDS(floatx4, z_r + P3 * 4 * TILE_B + j * 8 * TILE_ROW_B);
-                } else if (slot % SIDE_STRIDE == 2) {
-                    floatx4 o;
-#pragma unroll
-                    for (int tt = 0; tt < 4; ++tt) o[tt] = fmaf(er[j][tt], res_w, fmaf(zq[tt] * kr, gm[tt], bt[tt]));
-                    // rows past the block's end (and every row of a fill / drain tick) lie beyond the resource's byte count: dropped
-                    // (the block's position is in the resource's base: gfx9 subtracts a scalar offset from the byte count)
-                    bst4s<STREAM ? ST_STREAM_E : 0>(make_srd(e_out_wg + (size_t)(rel_a + 8 * j) * H, (unsigned)s_clamp0(cnt_st - 8 * j, 8) * 512u), v_eoff, 0, o);
-                    er[j] = bld4(srd_ein, v_eoff, rel_b * 512 + j * 4096);   // residual rows of block x-2: a whole tick to arrive
-                }
+                if (slot % SIDE_STRIDE == 0) lg.load(km_r + j * 32, z_r + P3 * 4 * TILE_B + j * 8 * TILE_ROW_B);
+                else if (slot % SIDE_STRIDE == 2)   // then the residual rows of block x-2
+                    lg.store<STREAM ? ST_STREAM_E : 0>(e_out_wg, rel_a, j, cnt_st, v_eoff, gm, bt, er[j], res_w, srd_ein, rel_b);
             };
             SYS_STAMP(t, 1);
             SYS_STAMP(t, 2);
@@ -491,12 +557,8 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_edge_kernel(const CsrHeade
             lds_barrier();
             SYS_STAMP(t, 6);
         };
-#pragma unroll 1
-        for (int t = -1; t <= nb + 1; t += 2) {
-            tick(odd, t);
-            tick(even, t + 1);
-        }
-        if (rng && lane0 == 0) atomicOr(a_flags, ERRF_SPLIT_RANGE);
+        RUN_TICKS(-1, nb + 1, tick);
+        report_split_range<false>(rng, lane0, a_flags);
     } else {
         // ------------------------------------------------------------------ role 2
         // Aggregation of block x-3 on a TRANSPOSED view of its LayerNorm input: lane (f, h) = feature 32 jb + f, rows 16 h ..
@@ -531,16 +593,7 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_edge_kernel(const CsrHeade
         const unsigned x_in = opaque(L_X2 + lane0 * 16);
         const unsigned dr_r = opaque(L_DR + 64 * hi);
         const srd_t srd_agg = make_srd(reinterpret_cast<const char*>(a_agg) - L_ST, a_agg_bytes + L_ST);   // see v_aoff
-        floatx16 b3v;   // stays in LDS: read at the top of every tick
-        auto init_acc = [&]() {
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const floatx4 v = LDS(floatx4, L_VEC + (H + 32 * jb + 4 * hi + 8 * g) * 4);
-#pragma unroll
-                for (int tt = 0; tt < 4; ++tt) b3v[4 * g + tt] = v[tt];
-            }
-        };
-        init_acc();
+        floatx16 b3v = vec_to_acc(smem, L_VEC, H, jb, hi);   // stays in LDS: read at the top of every tick
         auto fetch = [&](int x, int2 bi, int2 si, int hd, int& st, int& cnt, int& fl, unsigned& cont, unsigned& last, int& head) {
             st = bi.x;
             if (!ok(x)) { cnt = 0; fl = 0; cont = 0; last = 0; return; }
@@ -556,7 +609,7 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_edge_kernel(const CsrHeade
             // table entries of block x (decoded next tick): requested at the top, so that the barrier's scalar-memory wait finds them done
             const int2 bn_n = a_blk[clampb(x)], sn_n = a_seg[clampb(x)];
             const int hd_n = a_head[clampb(x - 1) >> 2];   // head of block x-1's group (used if that block opens its group)
-            init_acc();                                     // b3' T3 -> the first MFMA's C operand (lands under the statistics merge)
+            b3v = vec_to_acc(smem, L_VEC, H, jb, hi);  // b3' T3 -> the first MFMA's C operand (lands under the statistics merge)
             const bool agg_on = ok(x - 3);
             SYS_STAMP(t, 0);
             // 1 / (T sigma) of the rows of block x-3 (lane = row) -> this wave's table, read back per register row below
@@ -568,8 +621,7 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_edge_kernel(const CsrHeade
             floatx16 y;     // a vector: the store loop below indexes it with a (wave-uniform) run-time row
             floatx4 kq;
             float zz[4];
-            float ek;
-            floatx4 ezq;
+            LnGroup lg;
             float cpend = 0.f;
             // value of an open segment handed to the next half: half 0 -> half 1 inside the tick, half 1 -> half 0 of the next block
             auto side = [&](int slot) {
@@ -599,20 +651,13 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_edge_kernel(const CsrHeade
                     cpend = hi ? c1v : c0v;
                 } else if (WRITE_E && EPI_SPLIT < 4 && slot >= 14 && slot < 14 + 2 * (4 - EPI_SPLIT)) {
                     // this role's share of the e_out epilogue: row group j, loads at an even slot, arithmetic + store at the next
-                    {
-                        const int j = EPI_SPLIT + ((slot - 14) >> 1);
-                        if (!((slot - 14) & 1)) {
-                            ek = LDS(float, km_re + j * 32);
-                            ezq = LDS(floatx4, z_e + P3 * 4 * TILE_B + j * 8 * TILE_ROW_B);
-                        } else {
-                            const floatx4 gmq = LDS(floatx4, L_VEC + (2 * H + 32 * jb + 4 * cq) * 4);   // read per use: registers are scarcer than LDS slots here
-                            const floatx4 btq = LDS(floatx4, L_VEC + (3 * H + 32 * jb + 4 * cq) * 4);
-                            floatx4 o;
-#pragma unroll
-                            for (int tt = 0; tt < 4; ++tt) o[tt] = fmaf(er[j - EPI_SPLIT][tt], res_w, fmaf(ezq[tt] * ek, gmq[tt], btq[tt]));
-                            bst4s<STREAM ? ST_STREAM_E : 0>(make_srd(e_out_wg + (size_t)(rel_a + 8 * j) * H, (unsigned)s_clamp0(cnt_st - 8 * j, 8) * 512u), v_eoff, 0, o);
-                            er[j - EPI_SPLIT] = bld4(srd_ein, v_eoff, rel_b * 512 + j * 4096);   // residual rows of block x-2: a whole tick to arrive
-                        }
+                    const int j = EPI_SPLIT + ((slot - 14) >> 1);
+                    if (!((slot - 14) & 1)) {
+                        lg.load(km_re + j * 32, z_e + P3 * 4 * TILE_B + j * 8 * TILE_ROW_B);
+                    } else {
+                        const floatx4 gmq = LDS(floatx4, L_VEC + (2 * H + 32 * jb + 4 * cq) * 4);   // read per use: registers are scarcer than LDS slots here
+                        const floatx4 btq = LDS(floatx4, L_VEC + (3 * H + 32 * jb + 4 * cq) * 4);
+                        lg.store<STREAM ? ST_STREAM_E : 0>(e_out_wg, rel_a, j, cnt_st, v_eoff, gmq, btq, er[j - EPI_SPLIT], res_w, srd_ein, rel_b);
                     }
                 }
             };
@@ -644,6 +689,7 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_edge_kernel(const CsrHeade
             SYS_STAMP(t, 3);   // 24 MFMAs with the scatter-add between them
             rng |= __any(acc[0] != acc[0]) ? 1 : 0;
             {
+                // (publish_ln_stats written out: through the helper hipcc moves slot 13's carry selects behind the statistics)
                 // LayerNorm statistics of the scaled accumulators: the image's W3 / b3 are centred over the output features, so a
                 // row's outputs have zero mean and its variance is the mean square.  Sum of squares of this wave's 32 features
                 // of row n (16 per lane half); raw accumulators to Z.
@@ -671,12 +717,8 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_edge_kernel(const CsrHeade
             lds_barrier();
             SYS_STAMP(t, 6);   // every wave of the workgroup has finished the tick
         };
-#pragma unroll 1
-        for (int t = -1; t <= nb + 1; t += 2) {
-            tick(odd, t);
-            tick(even, t + 1);
-        }
-        if (rng && lane0 == 0) atomicOr(a_flags, ERRF_SPLIT_RANGE);
+        RUN_TICKS(-1, nb + 1, tick);
+        report_split_range<false>(rng, lane0, a_flags);
     }
 }
 
@@ -701,14 +743,13 @@ constexpr size_t ENC_LDS_BYTES = LE_VEC + 5 * H * 4;
 
 __global__ void __launch_bounds__(SYS_THREADS, 1) sys_enc_kernel(const CsrHeader* a_hdr, const float* __restrict__ a_x, float* __restrict__ a_e_out,
                                                                       const float* __restrict__ a_hw, int* a_flags, float a_eps, int a_pad_rows) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane0 = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int role = wave >> 2, jb = wave & 3;
     const int E = a_hdr->n_edges;
     const int nblk = (E + BE - 1) / BE;
-    const int wg = xcd_major_wg();
-    const int b0 = (int)((long long)wg * nblk / gridDim.x), b1 = (int)((long long)(wg + 1) * nblk / gridDim.x);
+    const int2 br = wg_range(nblk, true);
+    const int b0 = br.x, b1 = br.y;
     const int nb = b1 - b0;
     // The processor edge kernel reads whole 32-row blocks: the kEdgePadRows rows behind row E hold zeros (zero_edge_pad_rows does that
     // for the other encoders).  Nobody else writes them: stores past a block's last row are dropped by their buffer bound.
@@ -716,24 +757,12 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_enc_kernel(const CsrHeader
         for (int i = tid; i < kEdgePadRows * H / 4; i += SYS_THREADS) reinterpret_cast<floatx4*>(a_e_out + (size_t)E * H)[i] = floatx4{0.f, 0.f, 0.f, 0.f};
     if (nb <= 0) return;
     const float inv_T = a_hw[1], cap = a_hw[2];
-    const float* hvec = a_hw + HW_HEADER_FLOATS;
-    const half8* wimg = reinterpret_cast<const half8*>(a_hw + HW_HEADER_FLOATS + HW_VEC_FLOATS);
     half8 wh[8], wl[8];
-#pragma unroll
-    for (int ks = 0; ks < 8; ++ks) {   // role 0 multiplies one k-group only (its image holds zeros beyond): it loads that one
-        const int kq = role == 0 ? 0 : ks;
-        wh[ks] = wimg[(((role * 4 + jb) * 8 + kq) * 2 + 0) * 64 + lane0];
-        wl[ks] = wimg[(((role * 4 + jb) * 8 + kq) * 2 + 1) * 64 + lane0];
-    }
-    for (int i = tid; i < LE_ZERO_END / 16; i += SYS_THREADS) LDS(uintx4, i * 16) = uintx4{0u, 0u, 0u, 0u};
-    for (int i = tid; i < 5 * H; i += SYS_THREADS) LDS(float, LE_VEC + 4 * i) = hvec[i];
-    __builtin_amdgcn_s_waitcnt(0x0f70);
-    __syncthreads();
+    sys_prologue(wh, wl, reinterpret_cast<const half8*>(a_hw + HW_HEADER_FLOATS + HW_VEC_FLOATS), role * 4 + jb, role == 0, LE_ZERO_END, LE_VEC,
+                      a_hw + HW_HEADER_FLOATS, 5 * H);
     const int n = lane0 & 31, hi = lane0 >> 5, rr = lane0 >> 3, cq = lane0 & 7;
     const int e0 = b0 * BE;                               // first row of the workgroup
     const int rows_wg = (b1 * BE < E ? b1 * BE : E) - e0;  // its rows
-    std::integral_constant<int, 0> even;
-    std::integral_constant<int, 1> odd;
     // bias of this role's Linear in accumulator layout (vec slot: role 0 -> b1 T1 (4), role 1 -> b2 T2 (0), role 2 -> b3' T3 (1))
     floatx16 bv;
     {
@@ -819,11 +848,7 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_enc_kernel(const CsrHeader
             acc_to_image(acc, smem, x1_w + PAR * IMG_B);
             lds_barrier();
         };
-#pragma unroll 1
-        for (int t = 0; t <= nb + 2; t += 2) {   // ticks 0 .. nb + 2 (one more when nb is even: it drains like the one before it)
-            tick(even, t);
-            tick(odd, t + 1);
-        }
+        RUN_TICKS(0, nb + 2, tick);   // ticks 0 .. nb + 2 (one more when nb is even: it drains like the one before it)
     } else if (role == 1) {
         const unsigned x_in = opaque(LE_X1 + lane0 * 16), x_out = opaque(LE_X2 + 4 * jb * 1024 + lane0 * 16);
         auto nothing = [](int) {};
@@ -837,11 +862,7 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_enc_kernel(const CsrHeader
             acc_to_image(acc, smem, x_out + P1 * IMG_B);
             lds_barrier();
         };
-#pragma unroll 1
-        for (int t = 0; t <= nb + 2; t += 2) {   // ticks 0 .. nb + 2 (one more when nb is even: it drains like the one before it)
-            tick(even, t);
-            tick(odd, t + 1);
-        }
+        RUN_TICKS(0, nb + 2, tick);   // ticks 0 .. nb + 2 (one more when nb is even: it drains like the one before it)
     } else {
         const unsigned x_in = opaque(LE_X2 + lane0 * 16);
         const unsigned st_w = opaque(LE_ST + jb * 128 + n * 4);
@@ -853,26 +874,12 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_enc_kernel(const CsrHeader
             const floatx16 c0v = scaled_bias(LDS(float, rs_l + ((x - 2) & (RS_SLOTS - 1)) * 128));
             mlp_layer(acc, c0v, wh, wl, smem, x_in + P2 * IMG_B, x_in + P2 * IMG_B, nothing);
             rng |= __any(acc[0] != acc[0]) ? 1 : 0;
-            float q = 0.f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) q = fmaf(acc[r], acc[r], q);
-            LDS(float, st_w + P2 * 512) = sum_of_halves(q);
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                floatx4 z;
-#pragma unroll
-                for (int tt = 0; tt < 4; ++tt) z[tt] = acc[4 * g + tt];
-                LDS(floatx4, z_w + P2 * 4 * TILE_B + 32 * g) = z;
-            }
+            publish_ln_stats(acc, st_w + P2 * 512, z_w + P2 * 4 * TILE_B);
             lds_barrier();
         };
-#pragma unroll 1
-        for (int t = 0; t <= nb + 2; t += 2) {   // ticks 0 .. nb + 2 (one more when nb is even: it drains like the one before it)
-            tick(even, t);
-            tick(odd, t + 1);
-        }
+        RUN_TICKS(0, nb + 2, tick);   // ticks 0 .. nb + 2 (one more when nb is even: it drains like the one before it)
     }
-    if (rng && lane0 == 0 && a_flags) atomicOr(a_flags, ERRF_SPLIT_RANGE);
+    report_split_range(rng, lane0, a_flags);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -903,7 +910,6 @@ static_assert(NODE_LDS_BYTES <= 160 * 1024, "LDS budget");
 
 __global__ void __launch_bounds__(SYS_THREADS, 1) sys_node_kernel(const float* a_h, const float* __restrict__ a_agg, const float* __restrict__ a_Q,
                                                                        float* a_h_out, const float* __restrict__ a_hw, int a_n, int* a_flags, float a_eps) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane0 = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int role = wave >> 2, jb = wave & 3;
@@ -914,29 +920,16 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_node_kernel(const float* a
     const int nb = b1 - b0;
     if (nb <= 0) return;
     const float inv_T = a_hw[1];
-    const float* hvec = a_hw + HW_HEADER_FLOATS;
-    const half8* wimg = reinterpret_cast<const half8*>(a_hw + HW_HEADER_FLOATS + HW_VEC_FLOATS);
     half8 wh[8], wl[8];
-#pragma unroll
-    for (int ks = 0; ks < 8; ++ks) {
-        wh[ks] = wimg[(((role * 4 + jb) * 8 + ks) * 2 + 0) * 64 + lane0];
-        wl[ks] = wimg[(((role * 4 + jb) * 8 + ks) * 2 + 1) * 64 + lane0];
-    }
-    for (int i = tid; i < LN_ZERO_END / 16; i += SYS_THREADS) LDS(uintx4, i * 16) = uintx4{0u, 0u, 0u, 0u};
-    for (int i = tid; i < 4 * H; i += SYS_THREADS) LDS(float, LN_VEC + 4 * i) = hvec[i];
-    __builtin_amdgcn_s_waitcnt(0x0f70);
-    __syncthreads();
+    sys_prologue(wh, wl, reinterpret_cast<const half8*>(a_hw + HW_HEADER_FLOATS + HW_VEC_FLOATS), role * 4 + jb, false, LN_ZERO_END, LN_VEC,
+                 a_hw + HW_HEADER_FLOATS, 4 * H);
     const int n = lane0 & 31, hi = lane0 >> 5, rr = lane0 >> 3, cq = lane0 & 7;
     const int r0 = b0 * BE;                                 // first row of the workgroup
     const int rows_wg = (b1 * BE < N ? b1 * BE : N) - r0;   // its rows
     const unsigned wg_bytes = (unsigned)(rows_wg > 0 ? rows_wg : 0) * 512u;   // reads past them return zeros, stores are dropped
-    std::integral_constant<int, 0> even;
-    std::integral_constant<int, 1> odd;
     const unsigned v_eoff = opaque(rr * 512 + jb * 128 + cq * 16);   // row 8 j + rr of a block, this wave's 128-byte slab: + 4096 j
     int rng = 0;
-    if (role == 2) __builtin_amdgcn_s_setprio(HEDGE_PRIO2);
-    else if (role == 0) __builtin_amdgcn_s_setprio(HEDGE_PRIO0);
-    else __builtin_amdgcn_s_setprio(HEDGE_PRIO1);
+    set_role_prio(role);
     if (role == 0) {
         const srd_t srd_q = make_srd(a_Q + (size_t)r0 * H, wg_bytes), srd_a = make_srd(a_agg + (size_t)r0 * H, wg_bytes);
         const unsigned v_qoff = opaque(rr * 2048 + jb * 128 + cq * 16);   // row 4 rr + j: + 512 j
@@ -986,11 +979,7 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_node_kernel(const float* a
             }
             lds_barrier();
         };
-#pragma unroll 1
-        for (int t = -1; t <= nb + 2; t += 2) {   // one tick of fill, nb blocks, three (four when nb is odd) that drain the pipeline
-            tick(odd, t);
-            tick(even, t + 1);
-        }
+        RUN_TICKS(-1, nb + 2, tick);   // one tick of fill, nb blocks, three (four when nb is odd) that drain the pipeline
     } else {
         // roles 1 / 2: Linear 2 of block x-1 / Linear 3 of block x-2; each runs two row groups of the epilogue of block x-3
         const bool r2 = role == 2;
@@ -999,13 +988,7 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_node_kernel(const float* a
         float* const h_out_wg = a_h_out + (size_t)r0 * H;
         const floatx4 gm = LDS(floatx4, LN_VEC + (2 * H + 32 * jb + 4 * cq) * 4);
         const floatx4 bt = LDS(floatx4, LN_VEC + (3 * H + 32 * jb + 4 * cq) * 4);
-        floatx16 bv;   // bias of this role's Linear in accumulator layout
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const floatx4 v = LDS(floatx4, LN_VEC + ((r2 ? H : 0) + 32 * jb + 4 * hi + 8 * g) * 4);
-#pragma unroll
-            for (int tt = 0; tt < 4; ++tt) bv[4 * g + tt] = v[tt];
-        }
+        const floatx16 bv = vec_to_acc(smem, LN_VEC, r2 ? H : 0, jb, hi);   // bias of this role's Linear in accumulator layout
         const unsigned st_r = opaque(LN_ST + n * 4);
         const unsigned km_w = opaque(LN_KM + (r2 ? 512 : 0) + jb * 128 + n * 4), km_r = opaque(LN_KM + (r2 ? 512 : 0) + jb * 128 + rr * 4);
         const unsigned z_r = opaque(LN_Z + jb * TILE_B + rr * TILE_ROW_B + cq * 16);
@@ -1048,27 +1031,13 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_node_kernel(const float* a
             } else {
                 mlp_layer(acc, bv, wh, wl, smem, x_in + PAR * IMG_B, x_in + PAR * IMG_B, side);
                 rng |= __any(acc[0] != acc[0]) ? 1 : 0;
-                float q = 0.f;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) q = fmaf(acc[r], acc[r], q);
-                LDS(float, st_w + PAR * 512) = sum_of_halves(q);
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    floatx4 z;
-#pragma unroll
-                    for (int tt = 0; tt < 4; ++tt) z[tt] = acc[4 * g + tt];
-                    LDS(floatx4, z_w + PAR * 4 * TILE_B + 32 * g) = z;
-                }
+                publish_ln_stats(acc, st_w + PAR * 512, z_w + PAR * 4 * TILE_B);
             }
             lds_barrier();
         };
-#pragma unroll 1
-        for (int t = -1; t <= nb + 2; t += 2) {
-            tick(odd, t);
-            tick(even, t + 1);
-        }
+        RUN_TICKS(-1, nb + 2, tick);
     }
-    if (rng && lane0 == 0 && a_flags) atomicOr(a_flags, ERRF_SPLIT_RANGE);
+    report_split_range(rng, lane0, a_flags);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1088,7 +1057,6 @@ constexpr size_t PROJ_LDS_BYTES = LP_T + 12 * TILE_B;
 __global__ void __launch_bounds__(SYS_THREADS, 1) sys_proj_kernel(const float* __restrict__ a_h, float* __restrict__ a_P, float* __restrict__ a_Q,
                                                                        const float* __restrict__ a_wp, const float* __restrict__ a_wq,
                                                                        const float* __restrict__ a_sp, const float* __restrict__ a_sq, int a_n, int* a_flags) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane0 = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int N = a_n;
@@ -1102,13 +1070,6 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_proj_kernel(const float* _
     const int ob = isq ? wave - 8 : wave;                 // output block inside its image
     const int out_pad = isq ? H : 2 * H;
     const float out_scale = img[1] * (isq ? (a_sq ? *a_sq : 1.f) : (a_sp ? *a_sp : 1.f));
-    const half8* frag = reinterpret_cast<const half8*>(img + 4 + out_pad);
-    half8 wh[8], wl[8];
-#pragma unroll
-    for (int ks = 0; ks < 8; ++ks) {
-        wh[ks] = frag[((size_t)(ob * 8 + ks) * 2 + 0) * 64 + lane0];
-        wl[ks] = frag[((size_t)(ob * 8 + ks) * 2 + 1) * 64 + lane0];
-    }
     const int n = lane0 & 31, hi = lane0 >> 5, rr = lane0 >> 3, cq = lane0 & 7;
     floatx16 bv;   // bias (times U) of this wave's 32 outputs in accumulator layout
 #pragma unroll
@@ -1117,9 +1078,8 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_proj_kernel(const float* _
 #pragma unroll
         for (int tt = 0; tt < 4; ++tt) bv[4 * g + tt] = v[tt];
     }
-    for (int i = tid; i < 2 * IMG_B / 16; i += SYS_THREADS) LDS(uintx4, LP_E + i * 16) = uintx4{0u, 0u, 0u, 0u};
-    __builtin_amdgcn_s_waitcnt(0x0f70);
-    __syncthreads();
+    half8 wh[8], wl[8];
+    sys_prologue<size_t>(wh, wl, reinterpret_cast<const half8*>(img + 4 + out_pad), ob, false, LP_E + 2 * IMG_B, 0, nullptr, 0);
     const int r0 = b0 * BE;
     const int rows_wg = (b1 * BE < N ? b1 * BE : N) - r0;
     const unsigned wg_bytes = (unsigned)(rows_wg > 0 ? rows_wg : 0) * 512u;
@@ -1140,8 +1100,6 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_proj_kernel(const float* _
     float* const out_wg = isq ? a_Q + (size_t)r0 * H + 32 * ob : a_P + (size_t)r0 * 2 * H + 32 * ob;
     const unsigned out_row_b = isq ? 512u : 1024u;
     const unsigned v_out = opaque((unsigned)(rr * out_row_b + cq * 16));                  // row 8 j + rr: + 8 j rows by the resource's base
-    std::integral_constant<int, 0> even;
-    std::integral_constant<int, 1> odd;
     auto clampb = [&](int x) { return x < b0 ? b0 : (x < b1 ? x : b1 - 1); };
     floatx4 hq[2];
 #pragma unroll
@@ -1187,12 +1145,8 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_proj_kernel(const float* _
         }
         lds_barrier();
     };
-#pragma unroll 1
-    for (int t = -1; t <= nb; t += 2) {   // one tick of fill, nb blocks (one more when nb is even: it recomputes the last block, stores nothing)
-        tick(odd, t);
-        tick(even, t + 1);
-    }
-    if (rng && lane0 == 0 && a_flags) atomicOr(a_flags, ERRF_SPLIT_RANGE);
+    RUN_TICKS(-1, nb, tick);   // one tick of fill, nb blocks (one more when nb is even: it recomputes the last block, stores nothing)
+    report_split_range(rng, lane0, a_flags);
 }
 
 // agg rows of the nodes whose in-edge segment crosses groups of the scatter-add: + the head partials the later groups hold, in
@@ -1425,14 +1379,7 @@ EdgeBlocks carve_edge_blocks(int* base, int64_t n_nodes, int64_t edge_capacity) 
     return t;
 }
 
-static int device_cus() {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    return cus;
-}
-
-int build_edge_blocks(const int* in_ptr, const int* dst, int64_t n_nodes, int64_t edge_capacity, const int* n_per_graph_dev,
-                      int n_per_graph_host, const EdgeBlocks& t, hipStream_t s) {
+int build_edge_blocks(const int* in_ptr, const int* dst, int64_t n_nodes, const int* n_per_graph_dev, int n_per_graph_host, const EdgeBlocks& t, hipStream_t s) {
     // t.stitch is -1 everywhere: the destination sort's clear pass set it (csr_clear_jobs)
     hipLaunchKernelGGL(edge_blocks_plan_kernel, dim3(1), dim3(64), 0, s, in_ptr, (int)n_nodes, n_per_graph_dev, n_per_graph_host,
                        t.hdr, t.gblk, (int)n_nodes + 1);
@@ -1441,7 +1388,6 @@ int build_edge_blocks(const int* in_ptr, const int* dst, int64_t n_nodes, int64_
     hipLaunchKernelGGL(edge_blocks_fill_kernel, dim3(gb), dim3(256), 0, s, in_ptr, dst, (int)n_nodes, t.hdr, t.gblk, t.blk, t.seg, t.head, t.stitch,
                        t.stitch_list);
     GM_LAUNCH_CHECK();
-    (void)edge_capacity;
     return GM_OK;
 }
 
@@ -1455,89 +1401,63 @@ bool edge_sys_fits(int64_t n_nodes, int64_t edge_capacity) {
 #define HEDGE_STREAM_MB 128   // A/B builds move it; 0 = always stream (round 5's policy), a huge value = never
 #endif
 constexpr uint64_t kStreamStoreBytes = (uint64_t)HEDGE_STREAM_MB << 20;
+
+// One launch of a systolic kernel: one workgroup per CU, SYS_THREADS threads, `lds` bytes of dynamic LDS (the attribute is set
+// once per device and kernel), timed under the profiler kind `kind`.
+template <auto KERNEL, class... Args>
+static int launch_sys(size_t lds, ProfState* prof_state, int kind, hipStream_t s, Args... args) {
+    static PerDeviceOnce attr_done;
+    const int rc_attr = attr_done.run([lds]() -> int {
+        GM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        return GM_OK;
+    });
+    if (rc_attr != GM_OK) return rc_attr;
+    {
+        ProfScope prof(prof_state, kind, s);
+        hipLaunchKernelGGL(KERNEL, dim3(device_cus()), dim3(SYS_THREADS), lds, s, args...);
+    }
+    GM_LAUNCH_CHECK();
+    return GM_OK;
+}
+template <auto KERNEL>
+using kernel_c = std::integral_constant<decltype(KERNEL), KERNEL>;   // a kernel as a type (launch_edge_sys picks one at run time)
 int launch_edge_sys(const EdgeArgs& a, const EdgeBlocks& t, int64_t edge_capacity, hipStream_t s) {
+    // a.hdr non-null: the kernel reports into &a.hdr->error_flags without a null test (report_split_range<false>)
     GM_REQUIRE(a.hdr && a.wstream_h3 && a.agg && a.side && !a.eid && !a.eid_out, GM_ERR_INVALID_ARGUMENT, "launch_edge_sys: unsupported argument combination");
     GM_REQUIRE(a.P_prescaled, GM_ERR_INVALID_ARGUMENT, "launch_edge_sys: P must carry the weight scale of this step (HmNodeArgs::p_scale = edge_sys_p_scale(image))");
     // the scatter-add addresses agg rows and side rows with 32-bit byte offsets from agg (carve_fwd puts them in one workspace)
     const uint64_t agg_bytes = ((uint64_t)(a.side - a.agg) + (uint64_t)(t.max_blocks / 4 + 1) * H) * 4;
     GM_REQUIRE(a.side >= a.agg && agg_bytes < (1ull << 32) && (uint64_t)a.n_nodes_tab * 2 * H * 4 < (1ull << 32), GM_ERR_INVALID_ARGUMENT,
                "launch_edge_sys: P and agg + side buffer must each stay below 4 GiB (edge_sys_fits)");
-    static PerDeviceOnce attr_done;
-    const int rc_attr = attr_done.run([]() -> int {
-        GM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(sys_edge_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SYS_LDS_BYTES));
-        GM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(sys_edge_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SYS_LDS_BYTES));
-        GM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(sys_edge_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SYS_LDS_BYTES));
-        GM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(sys_edge_kernel<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SYS_LDS_BYTES));
-        return GM_OK;
-    });
-    if (rc_attr != GM_OK) return rc_attr;
-    {
-        ProfScope prof(a.prof, PROF_EDGE, s);
-        // pointers as separate __restrict__ parameters (e_in / e_out may be the same array): the table reads are then provably
-        // unclobbered and become scalar loads
-        // Store policy by size (ST_STREAM_*): the edge rows of the launch's capacity against what the 256 MB Infinity Cache can keep from
-        // one launch to the next beside h, P and agg.  The capacity, not the device-side edge count: no host synchronisation.
-        const bool stream = (uint64_t)edge_capacity * H * 4 > kStreamStoreBytes;
-        auto go = [&](auto kern) {
-            hipLaunchKernelGGL(kern, dim3(device_cus()), dim3(SYS_THREADS), SYS_LDS_BYTES, s, a.hdr, a.dst, a.src, a.P, a.e_in, a.e_out,
-                               a.agg, a.wstream_h3, t.blk, t.seg, t.head, t.hdr, (unsigned)(a.side - a.agg), (unsigned)agg_bytes,
-                               (unsigned)((uint64_t)a.n_nodes_tab * 2 * H * 4), const_cast<int*>(&a.hdr->error_flags), a.eps, a.residual);
-        };
-        if (a.discard_e_out) { if (stream) go(sys_edge_kernel<false, true>); else go(sys_edge_kernel<false, false>); }
-        else { if (stream) go(sys_edge_kernel<true, true>); else go(sys_edge_kernel<true, false>); }
-    }
-    GM_LAUNCH_CHECK();
-    return GM_OK;
+    // Store policy by size (ST_STREAM_*): the edge rows of the launch's capacity against what the 256 MB Infinity Cache can keep from
+    // one launch to the next beside h, P and agg.  The capacity, not the device-side edge count: no host synchronisation.
+    const bool stream = (uint64_t)edge_capacity * H * 4 > kStreamStoreBytes;
+    // pointers as separate __restrict__ parameters (e_in / e_out may be the same array): the table reads are then provably
+    // unclobbered and become scalar loads
+    auto go = [&](auto kern) {
+        return launch_sys<decltype(kern)::value>(SYS_LDS_BYTES, a.prof, PROF_EDGE, s, a.hdr, a.dst, a.src, a.P, a.e_in, a.e_out, a.agg, a.wstream_h3,
+                                                 t.blk, t.seg, t.head, t.hdr, (unsigned)(a.side - a.agg), (unsigned)agg_bytes,
+                                                 (unsigned)((uint64_t)a.n_nodes_tab * 2 * H * 4), const_cast<int*>(&a.hdr->error_flags), a.eps, a.residual);
+    };
+    if (a.discard_e_out) return stream ? go(kernel_c<sys_edge_kernel<false, true>>{}) : go(kernel_c<sys_edge_kernel<false, false>>{});
+    return stream ? go(kernel_c<sys_edge_kernel<true, true>>{}) : go(kernel_c<sys_edge_kernel<true, false>>{});
 }
 
 int launch_edge_sys_enc(const EdgeArgs& a, hipStream_t s) {
     GM_REQUIRE(a.hdr && a.wstream_h3 && a.e_in && a.e_out && !a.eid && !a.eid_out && a.k1 == 4, GM_ERR_INVALID_ARGUMENT,
                "launch_edge_sys_enc: unsupported argument combination");
-    static PerDeviceOnce attr_done;
-    const int rc_attr = attr_done.run([]() -> int {
-        GM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(sys_enc_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ENC_LDS_BYTES));
-        return GM_OK;
-    });
-    if (rc_attr != GM_OK) return rc_attr;
-    {
-        ProfScope prof(a.prof, PROF_ENC, s);
-        hipLaunchKernelGGL(sys_enc_kernel, dim3(device_cus()), dim3(SYS_THREADS), ENC_LDS_BYTES, s, a.hdr, a.e_in, a.e_out, a.wstream_h3,
-                           const_cast<int*>(&a.hdr->error_flags), a.eps, a.zero_pad_rows ? 1 : 0);
-    }
-    GM_LAUNCH_CHECK();
-    return GM_OK;
+    return launch_sys<sys_enc_kernel>(ENC_LDS_BYTES, a.prof, PROF_ENC, s, a.hdr, a.e_in, a.e_out, a.wstream_h3, const_cast<int*>(&a.hdr->error_flags), a.eps,
+                                      a.zero_pad_rows ? 1 : 0);
 }
 
 int launch_node_sys(const NodeSysArgs& a, hipStream_t s) {
     GM_REQUIRE(a.h && a.agg && a.Q && a.h_out && a.image && a.n > 0, GM_ERR_INVALID_ARGUMENT, "launch_node_sys: bad argument");
-    static PerDeviceOnce attr_done;
-    const int rc_attr = attr_done.run([]() -> int {
-        GM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(sys_node_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)NODE_LDS_BYTES));
-        return GM_OK;
-    });
-    if (rc_attr != GM_OK) return rc_attr;
-    {
-        ProfScope prof(a.prof, PROF_NODE, s);
-        hipLaunchKernelGGL(sys_node_kernel, dim3(device_cus()), dim3(SYS_THREADS), NODE_LDS_BYTES, s, a.h, a.agg, a.Q, a.h_out, a.image, a.n, a.flags, a.eps);
-    }
-    GM_LAUNCH_CHECK();
-    return GM_OK;
+    return launch_sys<sys_node_kernel>(NODE_LDS_BYTES, a.prof, PROF_NODE, s, a.h, a.agg, a.Q, a.h_out, a.image, a.n, a.flags, a.eps);
 }
 
 int launch_proj_sys(const ProjSysArgs& a, hipStream_t s) {
     GM_REQUIRE(a.h && a.P && a.Q && a.img_p && a.img_q && a.n > 0, GM_ERR_INVALID_ARGUMENT, "launch_proj_sys: bad argument");
-    static PerDeviceOnce attr_done;
-    const int rc_attr = attr_done.run([]() -> int {
-        GM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(sys_proj_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)PROJ_LDS_BYTES));
-        return GM_OK;
-    });
-    if (rc_attr != GM_OK) return rc_attr;
-    {
-        ProfScope prof(a.prof, PROF_NODE, s);
-        hipLaunchKernelGGL(sys_proj_kernel, dim3(device_cus()), dim3(SYS_THREADS), PROJ_LDS_BYTES, s, a.h, a.P, a.Q, a.img_p, a.img_q, a.scale_p, a.scale_q, a.n, a.flags);
-    }
-    GM_LAUNCH_CHECK();
-    return GM_OK;
+    return launch_sys<sys_proj_kernel>(PROJ_LDS_BYTES, a.prof, PROF_NODE, s, a.h, a.P, a.Q, a.img_p, a.img_q, a.scale_p, a.scale_q, a.n, a.flags);
 }
 
 int launch_agg_stitch(float* agg, const float* side, const EdgeBlocks& t, int64_t n, ProfState* prof_state, hipStream_t s) {

@@ -102,7 +102,6 @@ struct HmNodeArgs {
     ProfState* prof;
 };
 
-bool hm_supported(int H);
 // width the kernels run a model of hidden size h at: h (1 .. 256) zero-padded to 64 / 128 / 256, else 0
 static inline int hm_padded_hidden(int h) { return (h < 1 || h > 256) ? 0 : (h <= 64 ? 64 : (h <= 128 ? 128 : 256)); }
 int launch_edge_hm(int H, bool enc, const HmEdgeArgs& a, hipStream_t s);

@@ -1034,12 +1034,6 @@ __global__ void __launch_bounds__(HM_PACK_THREADS) pack_hm_kernel(PackHmJobs J, 
     }
 }
 
-int device_cus() {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    return cus;
-}
-
 template <class K>
 int set_lds_attr(K kernel, size_t bytes = HM_LDS_BYTES) {
     GM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
@@ -1130,8 +1124,6 @@ extern "C" int gm_debug_hm_stamps(unsigned long long* out) {   // 4 workgroups x
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_hm_stamps), sizeof(unsigned long long) * 4 * 4 * 16) == hipSuccess ? 0 : -1;
 }
 #endif
-
-bool hm_supported(int H) { return H == 64 || H == 128 || H == 256; }   // instantiated widths (hm_padded_hidden maps a model onto one)
 
 int launch_edge_hm(int H, bool enc, const HmEdgeArgs& a, hipStream_t s) {
     GM_REQUIRE(a.w && a.e_in && a.e_out && a.ln_g && a.ln_b, GM_ERR_INVALID_ARGUMENT, "launch_edge_hm: null pointer");

@@ -91,7 +91,11 @@ __device__ __forceinline__ void issue_stage3(const WStream& ws, int stage, int b
 }
 
 // One Linear: acc[jb] += W(block jb) . act.  NKG = K / 16 k-groups, NJB = OUT / 32 blocks, act in the accumulator layout.
-// more / PEND: as run_layer (fchain.h).
+// `more` = another stage will be consumed after this layer's last one (this tile or the next).
+// PEND: number of vector-memory instructions (stores of results that nothing in this layer reads) the
+// caller has issued, on EVERY path and in every wave, after the previous run_layer_b3 returned.  vmcnt
+// retires in issue order, so waiting for "at most PEND outstanding" still guarantees the stage's DMA
+// (issued earlier) has landed, without draining those stores in front of the MFMAs.
 template <int NKG, int NJB, int NKB, int PEND = 0>
 __device__ __forceinline__ void run_layer_b3(floatx16 (&acc)[NJB], const floatx16 (&act)[NKB], WStream& ws, bool more_tiles) {
     constexpr int NG = NKG * NJB;
@@ -388,7 +392,7 @@ __global__ void __launch_bounds__(THREADS, H <= 128 ? 2 : 1) train_fwd_kernel(Tr
         }
         // hidden layers 2..NL and the output layer; bias_tail = bias of layer 2
         // Tape stores are issued by every lane (rows past the end write a duplicate of the last row: same
-        // inputs, same values) so that their count is exact for run_layer<.., PEND>, which then does not
+        // inputs, same values) so that their count is exact for run_layer_b3<.., PEND>, which then does not
         // drain them; the bias loads go first so that waiting for them does not wait for the stores either.
         constexpr int NST = H / 8;  // vector stores of one store_feat
 #pragma unroll 1
@@ -523,7 +527,7 @@ __global__ void __launch_bounds__(THREADS, H <= 128 ? 2 : 1) train_bwd_kernel(Tr
             else load_feat(act, A.tape.xhat + pc * H, hi);
             if (NORMED && A.ln_part) ln_param_sums(acc, act, valid, lnacc + wave * 2 * H, n, hi);
             layer_norm_bwd(acc, act, A.ln_g, A.tape.rstd[pc], hi);
-            // dz stores: every lane (duplicates of the last row past the end), counted by run_layer<.., PEND>
+            // dz stores: every lane (duplicates of the last row past the end), counted by run_layer_b3<.., PEND>
             if (TRAIN_LINES & 8) store_feat_lines(act, A.dz + (size_t)NL * A.dz_stride + (size_t)row0 * H, H, R - row0, turn, lane);
             else store_feat(act, A.dz + (size_t)NL * A.dz_stride + pc * H, hi);
             zero_feat(acc);
@@ -943,11 +947,6 @@ int launch_train_fwd(int H, int kind, const TrainFwdArgs& a, hipStream_t s) {
     return H == 64 ? launch_train_fwd_h<64>(kind, a, s) : H == 128 ? launch_train_fwd_h<128>(kind, a, s) : launch_train_fwd_h<256>(kind, a, s);
 }
 
-static int device_cus() {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    return cus;
-}
 size_t train_bwd_ln_part_floats(int H) { return (size_t)2 * 1024 * 2 * H; }   // workgroups of a backward launch: <= 2 per CU
 
 template <int H>
