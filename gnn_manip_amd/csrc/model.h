@@ -42,9 +42,9 @@ struct gm_model {
     // bf16 x 3 weight streams of the training kernels (train.hip): MLP after MLP, stages of kStageFloatsB3
     float* packed_t3 = nullptr;
     size_t packed_t3_floats = 0;
-    size_t t_enc_edge = 0, t_enc_node = 0;
+    size_t t_enc_edge = 0, t_enc_node = 0, t_dec = 0;
     std::vector<size_t> t_edge, t_node;
-    int T_HH = 0, T_e0 = 0, T_n0 = 0, T_out = 0;
+    std::vector<size_t> t_proj;   // [W_i | W_j] images of step k: the tail of the node encoder (k = 0) or of node step k - 1
     // The model's own copy of the raw tensors (device).  A weight update refreshes it and the cheap images (vec, the training
     // streams); the inference images (packed_hm, packed_h3) are re-packed from it by the first inference call that follows
     // (ensure_inference_images): a training loop, which updates the weights every step, never pays for them.

@@ -201,9 +201,13 @@ int load_weights_device(gm_model* m, const float* const* T, hipStream_t s, int w
         off = m->t_enc_node;
         pack3(b_enc_node, H, m->d.node_dim, 0, m->d.node_dim, off);
         hidden3(b_enc_node, off);
-        pack3(b_edge(0), H, 3 * H, m->ci * H, H, off);  // W_i of processor 0
-        pack3(b_edge(0), H, 3 * H, m->cj * H, H, off);  // W_j
+        // the node encoder's stream and each node step's go on into the next step's W_i, W_j and the last one's into the decoder:
+        // the training entry points read those images where gm_model_create recorded them
         for (int k = 0; k < M; ++k) {
+            GM_REQUIRE(off == m->t_proj[k], GM_ERR_INVALID_ARGUMENT, "model: training stream of step %d's W_i, W_j at %zu, recorded at %zu", k,
+                       off, m->t_proj[k]);
+            pack3(b_edge(k), H, 3 * H, m->ci * H, H, off);  // W_i
+            pack3(b_edge(k), H, 3 * H, m->cj * H, H, off);  // W_j
             off = m->t_edge[k];
             pack3(b_edge(k), H, 3 * H, m->ce * H, H, off);  // W_e
             hidden3(b_edge(k), off);
@@ -211,14 +215,10 @@ int load_weights_device(gm_model* m, const float* const* T, hipStream_t s, int w
             pack3(b_node(k), H, 2 * H, m->ch * H, H, off);  // W_h
             pack3(b_node(k), H, 2 * H, m->ca * H, H, off);  // W_agg
             hidden3(b_node(k), off);
-            if (k + 1 < M) {
-                pack3(b_edge(k + 1), H, 3 * H, m->ci * H, H, off);
-                pack3(b_edge(k + 1), H, 3 * H, m->cj * H, H, off);
-            } else {
-                for (int l = 0; l < NL; ++l) pack3(b_dec + 2 * l, H, H, 0, H, off);
-                pack3(b_dec + 2 * NL, m->d.out_dim, H, 0, H, off);
-            }
         }
+        GM_REQUIRE(off == m->t_dec, GM_ERR_INVALID_ARGUMENT, "model: training stream of the decoder at %zu, recorded at %zu", off, m->t_dec);
+        for (int l = 0; l < NL; ++l) pack3(b_dec + 2 * l, H, H, 0, H, off);
+        pack3(b_dec + 2 * NL, m->d.out_dim, H, 0, H, off);
         flush_t();
         if (rc != GM_OK) return rc;
     }
@@ -350,20 +350,20 @@ int gm_model_create(const gm_model_desc* desc, const float* const* tensors, int 
     if (desc->col_i || desc->col_j || desc->col_e) { m->ci = desc->col_i; m->cj = desc->col_j; m->ce = desc->col_e; }
     if (desc->node_agg_first) { m->ch = 1; m->ca = 0; }
     m->has_train_streams = m->H == 64 || m->H == 128 || m->H == 256;   // widths the training kernels (and their bf16 x 3 streams) exist for
-    {   // bf16 x 3 streams of the training kernels, one MLP after the other
-        m->T_HH = layer_stages_b3(H, H);
-        m->T_e0 = layer_stages_b3(desc->edge_dim, H);
-        m->T_n0 = layer_stages_b3(desc->node_dim, H);
-        m->T_out = layer_stages_b3(H, desc->out_dim);
+    {   // bf16 x 3 streams of the training kernels, one MLP after the other (stages)
+        const size_t T_HH = layer_stages_b3(H, H);
         size_t t = 0;
-        m->t_enc_edge = t * kStageFloatsB3; t += m->T_e0 + NL * m->T_HH;
-        m->t_enc_node = t * kStageFloatsB3; t += m->T_n0 + NL * m->T_HH + 2 * m->T_HH;
+        m->t_enc_edge = t * kStageFloatsB3; t += layer_stages_b3(desc->edge_dim, H) + NL * T_HH;
+        m->t_enc_node = t * kStageFloatsB3; t += layer_stages_b3(desc->node_dim, H) + NL * T_HH;
+        m->t_proj.resize(M);
         m->t_edge.resize(M);
         m->t_node.resize(M);
-        for (int k = 0; k < M; ++k) {
-            m->t_edge[k] = t * kStageFloatsB3; t += (NL + 1) * m->T_HH;
-            m->t_node[k] = t * kStageFloatsB3; t += (NL + 2) * m->T_HH + (k + 1 < M ? 2 * m->T_HH : NL * m->T_HH + m->T_out);
+        for (int k = 0; k < M; ++k) {   // the [W_i | W_j] images of step k follow the node MLP before it
+            m->t_proj[k] = t * kStageFloatsB3; t += 2 * T_HH;
+            m->t_edge[k] = t * kStageFloatsB3; t += (NL + 1) * T_HH;
+            m->t_node[k] = t * kStageFloatsB3; t += (NL + 2) * T_HH;
         }
+        m->t_dec = t * kStageFloatsB3; t += NL * T_HH + layer_stages_b3(H, desc->out_dim);
         m->packed_t3_floats = t * kStageFloatsB3;
     }
     size_t v = 0;

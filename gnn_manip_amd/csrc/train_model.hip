@@ -12,16 +12,31 @@ using namespace gm;
 
 namespace {
 
-struct Tape {
-    void *csr_dst, *csr_src;
-    size_t csr_bytes;
-    int64_t* ei2;
-    std::vector<float*> h, e, agg;  // block inputs: h[0..M], e[0..M], agg[0..M-1]
-    float* P;
-    TapePtr ee, en, dec;
-    std::vector<TapePtr> te, tn;
-    size_t bytes;
+// first state_dict tensor of an MLP (epd_gnn.py:63-84): edge encoder 0, node encoder PM, step k's edge and node MLPs, decoder
+int base_edge(const gm_model* m, int k) { return (2 + 2 * k) * tensors_per_normed_mlp(m->NL); }
+int base_node(const gm_model* m, int k) { return (3 + 2 * k) * tensors_per_normed_mlp(m->NL); }
+int base_dec(const gm_model* m) { return base_edge(m, m->M); }
+
+// The destination-sorted edges (aggregation index i = edge_index[1]) and the source-grouped view of the sorted list.  It starts
+// every tape that has one: epd_gnn.py (_HeaderWatch) reads the edge_index verdict from the destination sort's header at byte 0.
+struct TrainCsr {
+    CsrWs dst, src;   // each view's header starts its csr workspace
+    int64_t* ei2;     // [2][e] the sorted list with its rows swapped: the input of the source sort
 };
+TrainCsr take_csr(Carver& c, int64_t n, int64_t e) {
+    TrainCsr t;
+    const size_t bytes = gm_csr_workspace_bytes(n, e);
+    t.dst = carve_csr(c.take<char>(bytes), n, e);
+    t.src = carve_csr(c.take<char>(bytes), n, e);
+    t.ei2 = c.take<int64_t>((size_t)2 * e);
+    return t;
+}
+int build_csr(const TrainCsr& t, const int64_t* edge_index, int64_t n, int64_t e, int flow, hipStream_t s) {
+    int rc = gm::csr_from_edge_index(edge_index, n, e, flow, t.dst.hdr, t.dst.bytes, false, s);
+    if (rc == GM_OK) rc = launch_swap_index(t.dst.src, e, t.ei2, s);
+    if (rc == GM_OK) rc = gm::csr_from_edge_index(t.ei2, n, e, 0, t.src.hdr, t.src.bytes, false, s);
+    return rc;
+}
 
 TapePtr take_tape(Carver& c, int64_t rows, int H, int NL, bool normed) {
     TapePtr t{};
@@ -34,30 +49,74 @@ TapePtr take_tape(Carver& c, int64_t rows, int H, int NL, bool normed) {
     return t;
 }
 
+struct EncTape {
+    TapePtr ee, en;
+};
+struct StepTape {   // one processor step
+    float* agg;
+    TapePtr te, tn;
+};
+
+struct Tape {
+    TrainCsr csr;
+    std::vector<float*> h, e;   // block inputs: h[0..M], e[0..M]
+    std::vector<StepTape> step;
+    float* P;
+    EncTape enc;
+    TapePtr dec;
+    size_t bytes;
+};
+
 Tape carve_tape(void* ws, const gm_model_desc* d, int64_t n, int64_t e) {
     Tape t;
     const int H = d->hidden_size, M = d->m_steps, NL = d->num_layers;
     Carver c(ws);
-    t.csr_bytes = gm_csr_workspace_bytes(n, e);
-    t.csr_dst = c.take<char>(t.csr_bytes);
-    t.csr_src = c.take<char>(t.csr_bytes);
-    t.ei2 = c.take<int64_t>((size_t)2 * e);
+    t.csr = take_csr(c, n, e);
     t.h.resize(M + 1);
     t.e.resize(M + 1);
-    t.agg.resize(M);
+    t.step.resize(M);
     for (int k = 0; k <= M; ++k) t.h[k] = c.take<float>((size_t)n * H);
     for (int k = 0; k <= M; ++k) t.e[k] = c.take<float>((size_t)e * H);
-    for (int k = 0; k < M; ++k) t.agg[k] = c.take<float>((size_t)n * H);
+    for (int k = 0; k < M; ++k) t.step[k].agg = c.take<float>((size_t)n * H);
     t.P = c.take<float>((size_t)n * 2 * H);
-    t.ee = take_tape(c, e, H, NL, true);
-    t.en = take_tape(c, n, H, NL, true);
-    t.te.resize(M);
-    t.tn.resize(M);
+    t.enc.ee = take_tape(c, e, H, NL, true);
+    t.enc.en = take_tape(c, n, H, NL, true);
     for (int k = 0; k < M; ++k) {
-        t.te[k] = take_tape(c, e, H, NL, true);
-        t.tn[k] = take_tape(c, n, H, NL, true);
+        t.step[k].te = take_tape(c, e, H, NL, true);
+        t.step[k].tn = take_tape(c, n, H, NL, true);
     }
     t.dec = take_tape(c, n, H, NL, false);
+    t.bytes = c.used();
+    return t;
+}
+
+// ---- tapes of the two standalone blocks (torch_graphnet API surface)
+struct GiTape {
+    EncTape enc;
+    size_t bytes;
+};
+GiTape carve_gi_tape(void* ws, int H, int NL, int64_t n, int64_t e) {
+    GiTape t;
+    Carver c(ws);
+    t.enc.ee = take_tape(c, e, H, NL, true);
+    t.enc.en = take_tape(c, n, H, NL, true);
+    t.bytes = c.used();
+    return t;
+}
+struct InTape {
+    TrainCsr csr;
+    float* P;
+    StepTape st;
+    size_t bytes;
+};
+InTape carve_in_tape(void* ws, int H, int NL, int64_t n, int64_t e) {
+    InTape t;
+    Carver c(ws);
+    t.csr = take_csr(c, n, e);
+    t.P = c.take<float>((size_t)n * 2 * H);
+    t.st.agg = c.take<float>((size_t)n * H);
+    t.st.te = take_tape(c, e, H, NL, true);
+    t.st.tn = take_tape(c, n, H, NL, true);
     t.bytes = c.used();
     return t;
 }
@@ -71,7 +130,9 @@ struct BwdWs {
     // weight-gradient jobs over an edge chain's dz and those over the node chain's that follows run as ONE batch
     size_t dzn_stride;
     float* dznl(int l) const { return dzn + (size_t)(l - 1) * dzn_stride; }
-    size_t off_dec, off_enc_edge, off_enc_node;
+    // slots of packT, one per backward chain's transposed stream (filled by PackBwd); off_proj: W_i^T, W_j^T of one step, which the
+    // node encoder's chain reads in front of its own images (off_enc_node) and a block's projection backward alone
+    size_t off_dec, off_proj, off_enc_edge, off_enc_node;
     std::vector<size_t> off_edge, off_node;
     size_t bytes;
 };
@@ -89,7 +150,8 @@ BwdWs carve_bwd(void* ws, const gm_model_desc* d, int64_t n, int64_t e) {
         b.off_edge[k] = off; off += (size_t)(NL + 1) * U;
     }
     const size_t UIN = (size_t)layer_stages_b3(H, 32) * kStageFloatsB3;  // W1^T of an encoder (input gradient, block API)
-    b.off_enc_node = off; off += 2 * U + (size_t)NL * U + UIN;
+    b.off_proj = off; off += 2 * U;
+    b.off_enc_node = off; off += (size_t)NL * U + UIN;
     b.off_enc_edge = off; off += (size_t)NL * U + UIN;
     Carver c(ws);
     b.packT = c.take<float>(off);
@@ -108,6 +170,122 @@ BwdWs carve_bwd(void* ws, const gm_model_desc* d, int64_t n, int64_t e) {
     b.bytes = c.used();
     return b;
 }
+// backward scratch of a single block: same carve as the whole model with one processor step
+BwdWs carve_block_bwd(void* ws, const gm_model_desc* d, int64_t n, int64_t e) {
+    gm_model_desc d1 = *d;
+    d1.m_steps = 1;
+    return carve_bwd(ws, &d1, n, e);
+}
+
+// Queues the transposed images of the backward chains into the slots of BwdWs::packT, each MLP's Linears in the order its chain
+// consumes them: the one place that knows what a slot holds.  k: the step whose tensors are packed; j: its slot (a block's is 0).
+struct PackBwd {
+    const gm_model* m;
+    const float* const* T;
+    const BwdWs& b;
+    hipStream_t s;
+    PackTJobs jobs{};
+    int rc = GM_OK;
+    int flush() {   // also when a batch is full
+        if (rc == GM_OK && jobs.n > 0) rc = launch_pack_b3_batch(jobs, b.packT, s);
+        jobs.n = 0;
+        return rc;
+    }
+    void job(const float* W, int w_rows, int ld, int col0, int ksub, size_t& off) {
+        if (jobs.n == kPackTJobsMax) flush();
+        PackTJob& j = jobs.job[jobs.n++];
+        j.W = W; j.w_rows = w_rows; j.ld = ld; j.col0 = col0; j.ksub = ksub; j.fwd = 0; j.dst_off = off;
+        off += (size_t)layer_stages_b3(w_rows, ksub) * kStageFloatsB3;
+    }
+    // the hidden Linears NL + 1 .. 2 of the MLP whose first tensor is `base`
+    void hidden(int base, size_t& off) { for (int l = m->NL; l >= 1; --l) job(T[base + 2 * l], m->H, m->H, 0, m->H, off); }
+    void ij(int k, size_t& off) {   // W_i, W_j: the column blocks of step k's first edge Linear that multiply h_i, h_j
+        job(T[base_edge(m, k)], m->H, 3 * m->H, m->ci * m->H, m->H, off);
+        job(T[base_edge(m, k)], m->H, 3 * m->H, m->cj * m->H, m->H, off);
+    }
+    // input: W_1^T as well, for the gradient w.r.t. the raw features (block API)
+    void enc(int base, size_t off, int k1, bool input) {
+        hidden(base, off);
+        if (input) job(T[base], m->H, k1, 0, k1, off);
+    }
+    void dec() {
+        const int H = m->H, bd = base_dec(m);
+        size_t off = b.off_dec;
+        job(T[bd + 2 * m->NL], m->d.out_dim, H, 0, H, off);
+        for (int l = m->NL - 1; l >= 0; --l) job(T[bd + 2 * l], H, H, 0, H, off);
+    }
+    void edge(int k, int j) {
+        size_t off = b.off_edge[j];
+        hidden(base_edge(m, k), off);
+        job(T[base_edge(m, k)], m->H, 3 * m->H, m->ce * m->H, m->H, off);
+    }
+    void node(int k, int j) {
+        size_t off = b.off_node[j];
+        if (j + 1 < (int)b.off_node.size()) ij(k + 1, off);   // a step with a next one: its chain also takes that step's Gi / Gj
+        hidden(base_node(m, k), off);
+        job(T[base_node(m, k)], m->H, 2 * m->H, m->ch * m->H, m->H, off);
+        job(T[base_node(m, k)], m->H, 2 * m->H, m->ca * m->H, m->H, off);
+    }
+    void proj(int k) { size_t off = b.off_proj; ij(k, off); }
+    void enc_node(bool input) { enc(tensors_per_normed_mlp(m->NL), b.off_enc_node, m->d.node_dim, input); }
+    void enc_edge(bool input) { enc(0, b.off_enc_edge, m->d.edge_dim, input); }
+};
+
+// The launches of one backward call after its images are packed.  Every call does nothing once rc holds an error.
+struct BwdRun {
+    const gm_model* m;
+    float* const* grads;
+    const BwdWs& b;
+    hipStream_t s;
+    WgradBatch wb;   // weight-gradient jobs run a batch per launch; flushed before anything overwrites their operands
+    int rc = GM_OK;
+    BwdRun(const gm_model* m_, float* const* grads_, const BwdWs& b_, hipStream_t s_) : m(m_), grads(grads_), b(b_), s(s_) {
+        wgrad_batch_init(wb, b.part, m->H, s);
+    }
+    void wgrad(const float* dz, int ldz, int Mo, const float* X, int ldx, int K, const int* xidx, int64_t rows, float* out, int ldw,
+               int col0, float* db) {
+        if (rc == GM_OK) rc = wgrad_enqueue(wb, dz, ldz, Mo, X, ldx, K, xidx, rows, out, ldw, col0, db);
+    }
+    // flush: the chain overwrites operands of the waiting jobs.  w: the batch that takes the chain's LayerNorm partials (or none)
+    void launch(int kind, const TrainBwdArgs& a, bool flush, WgradBatch* w) {
+        if (rc == GM_OK && flush) rc = wgrad_flush(wb);
+        if (rc == GM_OK) rc = launch_train_bwd(m->H, kind, a, s, w);
+    }
+    // dW = dz_(l+1)^T a_l (+ the bias) of Linears l + 1 = top + 1 .. 2 of the MLP whose chain `a` just ran
+    void tail(const TrainBwdArgs& a, int base, int top) {
+        for (int l = top; l >= 1; --l)
+            wgrad(a.dz + (size_t)l * a.dz_stride, m->H, m->H, a.tape.a + (size_t)(l - 1) * a.rows * m->H, m->H, m->H, nullptr, a.rows,
+                  grads[base + 2 * l], m->H, 0, grads[base + 2 * l + 1]);
+    }
+    // the LayerNorm and dz fields of a normed MLP's chain: its LayerNorm parameter gradients are summed inside the chain kernel;
+    // node_set: dz goes to the node-sized set (BwdWs::dzn), which no waiting job reads
+    void set_normed(TrainBwdArgs& a, int base, size_t voff, bool node_set) const {
+        const int NL = m->NL;
+        a.ln_g = m->vec + voff + (size_t)(NL + 1) * m->H;
+        a.ln_part = b.part; a.dgamma = grads[base + 2 * (NL + 1)]; a.dbeta = grads[base + 2 * (NL + 1) + 1];
+        a.dz = node_set ? b.dzn : b.dz; a.dz_stride = node_set ? b.dzn_stride : b.dz_stride; a.nl = NL;
+    }
+    // a normed MLP's chain and the weight gradients of its Linears 2 .. NL + 1 (Linear 1's differ at every call site).  A chain
+    // that writes the edge-sized dz set flushes first; one that writes the node-sized set adds its jobs to the waiting ones.
+    void chain(int kind, TrainBwdArgs a, int base, size_t voff, bool node_set) {
+        set_normed(a, base, voff, node_set);
+        launch(kind, a, !node_set, &wb);
+        tail(a, base, m->NL);
+    }
+    // node-level sums of an edge chain's dz_1 (G_i over each edge's destination, G_j over its source): everything the factorised
+    // Linear 1 needs -- its W_i / W_j gradients (input h) here, the input gradient W_i^T G_i + W_j^T G_j in the next node chain
+    void ij_grads(const TrainCsr& csr, const float* h, int be, int64_t n) {
+        if (rc == GM_OK)
+            rc = launch_segment_sum_pair(m->H, csr.dst.in_ptr, nullptr, csr.src.in_ptr, csr.src.eid, b.dzl(1), nullptr, nullptr, b.Gi, b.Gj,
+                                         n, s);
+        wgrad(b.Gi, m->H, m->H, h, m->H, m->H, nullptr, n, grads[be], 3 * m->H, m->ci * m->H, nullptr);
+        wgrad(b.Gj, m->H, m->H, h, m->H, m->H, nullptr, n, grads[be], 3 * m->H, m->cj * m->H, nullptr);
+    }
+    int finish() {
+        if (rc == GM_OK) rc = wgrad_flush(wb);
+        return rc;
+    }
+};
 
 // A training forward does not synchronise: an edge_index entry outside [0, n) is flagged by the destination sort in the tape's CSR
 // headers and reported at a later forward / status() (epd_gnn.py).  Until then the step must not do damage: the flagged forward's
@@ -126,55 +304,72 @@ unsigned small_grid(size_t count) {
     return (unsigned)(g < 1 ? 1 : (g > 512 ? 512 : g));
 }
 
-int check_sizes(const gm_model* m, int64_t n, int64_t e, const char* who) {
+// The checks every training entry point starts with, before any device call.
+int check_model(const gm_model* m, int64_t n, int64_t e, const char* who) {
+    GM_REQUIRE(!m || m->has_train_streams, GM_ERR_UNSUPPORTED, "%s: the training kernels are instantiated for hidden_size 64 / 128 / 256", who);
     GM_REQUIRE(m, GM_ERR_INVALID_ARGUMENT, "%s: null model", who);
     GM_REQUIRE(n >= 1 && e >= 0 && n < ((int64_t)1 << 31) && e < ((int64_t)1 << 31) / m->H, GM_ERR_INVALID_ARGUMENT,
                "%s: sizes out of range (n=%lld, e=%lld)", who, (long long)n, (long long)e);
     return GM_OK;
 }
-
-const float* mlp_vec(const gm_model* m, size_t voff) { return m->vec + voff; }
-
-// ---- tapes of the two standalone blocks (torch_graphnet API surface)
-struct GiTape {
-    TapePtr ee, en;
-    size_t bytes;
-};
-GiTape carve_gi_tape(void* ws, int H, int NL, int64_t n, int64_t e) {
-    GiTape t;
-    Carver c(ws);
-    t.ee = take_tape(c, e, H, NL, true);
-    t.en = take_tape(c, n, H, NL, true);
-    t.bytes = c.used();
-    return t;
+// a backward's state_dict: all of it, and the tensors and gradients [lo, hi) of the MLPs it reads non-null
+int check_tensors(const gm_model* m, const float* const* T, float* const* grads, int n_tensors, int lo, int hi, const char* who) {
+    const int nt = gm_model_num_tensors(&m->d);
+    GM_REQUIRE(n_tensors == nt, GM_ERR_INVALID_ARGUMENT, "%s: expected %d tensors, got %d", who, nt, n_tensors);
+    for (int i = lo; i < hi; ++i) GM_REQUIRE(T[i] && grads[i], GM_ERR_INVALID_ARGUMENT, "%s: tensor / gradient %d is null", who, i);
+    return GM_OK;
 }
-struct InTape {
-    void *csr_dst, *csr_src;
-    size_t csr_bytes;
-    int64_t* ei2;
-    float *P, *agg;
-    TapePtr te, tn;
-    size_t bytes;
-};
-InTape carve_in_tape(void* ws, int H, int NL, int64_t n, int64_t e) {
-    InTape t;
-    Carver c(ws);
-    t.csr_bytes = gm_csr_workspace_bytes(n, e);
-    t.csr_dst = c.take<char>(t.csr_bytes);
-    t.csr_src = c.take<char>(t.csr_bytes);
-    t.ei2 = c.take<int64_t>((size_t)2 * e);
-    t.P = c.take<float>((size_t)n * 2 * H);
-    t.agg = c.take<float>((size_t)n * H);
-    t.te = take_tape(c, e, H, NL, true);
-    t.tn = take_tape(c, n, H, NL, true);
-    t.bytes = c.used();
-    return t;
+// after the entry point's own checks: the caller's buffers are large enough, the kernels set up, the weight streams ready on s
+int ready_to_launch(const gm_model* m, size_t tape_bytes, size_t tape_need, size_t ws_bytes, size_t ws_need, hipStream_t s, const char* who) {
+    GM_REQUIRE(tape_bytes >= tape_need, GM_ERR_WORKSPACE, "%s: tape %zu < %zu", who, tape_bytes, tape_need);
+    GM_REQUIRE(ws_bytes >= ws_need, GM_ERR_WORKSPACE, "%s: workspace %zu < %zu", who, ws_bytes, ws_need);
+    int rc = train_kernels_init();
+    if (rc != GM_OK) return rc;
+    return weights_ready_on(m, s);   // the weight streams may have been packed on another stream (model.h)
 }
-// backward scratch of a single block: same carve as the whole model with one processor step
-BwdWs carve_block_bwd(void* ws, const gm_model_desc* d, int64_t n, int64_t e) {
-    gm_model_desc d1 = *d;
-    d1.m_steps = 1;
-    return carve_bwd(ws, &d1, n, e);
+
+void set_normed(const gm_model* m, TrainFwdArgs& a, size_t voff) {
+    const float* v = m->vec + voff;
+    const int H = m->H, NL = m->NL;
+    a.bias = v; a.bias_tail = v + H; a.ln_g = v + (size_t)(NL + 1) * H; a.ln_b = v + (size_t)(NL + 2) * H; a.eps = m->d.ln_eps; a.nl = NL;
+}
+
+// The two encoders.  rowidx: the edge_attr row of each destination-sorted edge (nullptr: the caller's order); P: the node
+// encoder's tail writes step 0's P = h_0 [W_i | W_j]^T (+ b1) there (nullptr: no tail).
+int fwd_encoders(const gm_model* m, int64_t n, int64_t e, const float* x, const float* edge_attr, const int* rowidx, const EncTape& t,
+                 float* h_out, float* e_out, float* P, hipStream_t s) {
+    TrainFwdArgs ea{};
+    ea.rows = (int)e; ea.x_in = edge_attr; ea.rowidx = rowidx; ea.k1 = m->d.edge_dim; ea.wstream = m->packed_t3 + m->t_enc_edge;
+    set_normed(m, ea, m->v_enc_edge);
+    ea.tape = t.ee; ea.out = e_out;
+    TrainFwdArgs na{};
+    na.rows = (int)n; na.x_in = x; na.k1 = m->d.node_dim; na.wstream = m->packed_t3 + m->t_enc_node;
+    set_normed(m, na, m->v_enc_node);
+    na.tape = t.en; na.out = h_out;
+    if (P) { na.P_out = P; na.proj_bias = m->vec + m->v_edge[0]; }
+    int rc = launch_train_fwd(m->H, TK_ENC_EDGE, ea, s);
+    if (rc == GM_OK) rc = launch_train_fwd(m->H, TK_ENC_NODE, na, s);
+    return rc;
+}
+
+// Processor step k: edge MLP -> segment sum of its LayerNorm output -> node MLP.  rowidx: the e_in / e_out row of each sorted
+// edge (nullptr: the sorted order); residual: out = MLP(x) + x; tail: the node MLP then writes step k + 1's P over P.
+int fwd_step(const gm_model* m, int k, const CsrWs& c, int64_t n, int64_t e, const float* h, const float* e_in, float* P,
+             const StepTape& st, float* h_out, float* e_out, const int* rowidx, int residual, bool tail, hipStream_t s) {
+    TrainFwdArgs ea{};
+    ea.rows = (int)e; ea.x_in = e_in; ea.rowidx = rowidx; ea.dst = c.dst; ea.src = c.src; ea.P = P; ea.wstream = m->packed_t3 + m->t_edge[k];
+    set_normed(m, ea, m->v_edge[k]);
+    ea.tape = st.te; ea.out = e_out; ea.residual = residual;
+    TrainFwdArgs na{};
+    na.rows = (int)n; na.x_in = h; na.agg = st.agg; na.wstream = m->packed_t3 + m->t_node[k];
+    set_normed(m, na, m->v_node[k]);
+    na.tape = st.tn; na.out = h_out; na.residual = residual;
+    if (tail) { na.P_out = P; na.proj_bias = m->vec + m->v_edge[k + 1]; }
+    int rc = launch_train_fwd(m->H, TK_PROC_EDGE, ea, s);
+    // agg_i = sum over edges into i of e' = gamma * sum xhat + deg * beta
+    if (rc == GM_OK) rc = launch_segment_sum(m->H, c.in_ptr, nullptr, st.te.xhat, ea.ln_g, ea.ln_b, st.agg, n, s);
+    if (rc == GM_OK) rc = launch_train_fwd(m->H, TK_PROC_NODE, na, s);
+    return rc;
 }
 
 }  // namespace
@@ -193,86 +388,34 @@ size_t gm_train_backward_workspace_bytes(const gm_model_desc* desc, int64_t n, i
 
 int gm_epd_forward_train(const gm_model* m, const float* nodes, int64_t n, const float* edge_attr, const int64_t* edge_index,
                          int64_t e, float* out, void* tape, size_t tape_bytes, void* stream) {
-    GM_REQUIRE(!m || m->has_train_streams, GM_ERR_UNSUPPORTED, "%s: the training kernels are instantiated for hidden_size 64 / 128 / 256", "gm_epd_forward_train");
+    int rc = check_model(m, n, e, __func__);
+    if (rc != GM_OK) return rc;
+    GM_REQUIRE(nodes && out && tape && (e == 0 || (edge_attr && edge_index)), GM_ERR_INVALID_ARGUMENT, "%s: null pointer", __func__);
     gm::DevGuard dev_guard(nodes);
-    int rc = check_sizes(m, n, e, "gm_epd_forward_train");
-    if (rc != GM_OK) return rc;
-    GM_REQUIRE(nodes && out && tape && (e == 0 || (edge_attr && edge_index)), GM_ERR_INVALID_ARGUMENT, "gm_epd_forward_train: null pointer");
-    const int H = m->H, NL = m->NL, M = m->M;
-    Tape t = carve_tape(tape, &m->d, n, e);
-    GM_REQUIRE(tape_bytes >= t.bytes, GM_ERR_WORKSPACE, "gm_epd_forward_train: tape %zu < %zu", tape_bytes, t.bytes);
-    rc = train_kernels_init();
-    if (rc != GM_OK) return rc;
-    rc = weights_ready_on(m, (hipStream_t)stream);   // the weight streams may have been packed on another stream (model.h)
-    if (rc != GM_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
-    // destination-sorted edges (aggregation index i = edge_index[1]) and the source-grouped view of the sorted list
-    rc = gm::csr_from_edge_index(edge_index, n, e, m->d.flow, t.csr_dst, t.csr_bytes, false, (hipStream_t)stream);
+    const int M = m->M;
+    Tape t = carve_tape(tape, &m->d, n, e);
+    rc = ready_to_launch(m, tape_bytes, t.bytes, 0, 0, s, __func__);
     if (rc != GM_OK) return rc;
-    CsrWs c = carve_csr(t.csr_dst, n, e);
-    rc = launch_swap_index(c.src, e, t.ei2, s);
+    rc = build_csr(t.csr, edge_index, n, e, m->d.flow, s);
     if (rc != GM_OK) return rc;
-    rc = gm::csr_from_edge_index(t.ei2, n, e, 0, t.csr_src, t.csr_bytes, false, (hipStream_t)stream);
+    rc = fwd_encoders(m, n, e, nodes, edge_attr, t.csr.dst.eid, t.enc, t.h[0], t.e[0], t.P, s);
     if (rc != GM_OK) return rc;
-
-    const size_t U = (size_t)m->T_HH * kStageFloatsB3;
-    auto normed = [&](TrainFwdArgs& a, size_t voff) {
-        const float* v = mlp_vec(m, voff);
-        a.bias = v; a.bias_tail = v + H; a.ln_g = v + (size_t)(NL + 1) * H; a.ln_b = v + (size_t)(NL + 2) * H; a.eps = m->d.ln_eps; a.nl = NL;
-    };
-    {
-        TrainFwdArgs a{};
-        a.rows = (int)e; a.x_in = edge_attr; a.rowidx = c.eid; a.k1 = m->d.edge_dim; a.wstream = m->packed_t3 + m->t_enc_edge;
-        normed(a, m->v_enc_edge);
-        a.tape = t.ee; a.out = t.e[0];
-        rc = launch_train_fwd(H, TK_ENC_EDGE, a, s);
-        if (rc != GM_OK) return rc;
-    }
-    {
-        TrainFwdArgs a{};
-        a.rows = (int)n; a.x_in = nodes; a.k1 = m->d.node_dim; a.wstream = m->packed_t3 + m->t_enc_node;
-        normed(a, m->v_enc_node);
-        a.tape = t.en; a.out = t.h[0];
-        // tail: P = h_0 [W_i | W_j]^T (+ b1) of the first edge step -- the projection section that follows this MLP in its stream
-        a.P_out = t.P; a.proj_bias = m->vec + m->v_edge[0];
-        rc = launch_train_fwd(H, TK_ENC_NODE, a, s);
-        if (rc != GM_OK) return rc;
-    }
     for (int k = 0; k < M; ++k) {
-        const float* ve = mlp_vec(m, m->v_edge[k]);
-        {
-            TrainFwdArgs a{};
-            a.rows = (int)e; a.x_in = t.e[k]; a.dst = c.dst; a.src = c.src; a.P = t.P; a.wstream = m->packed_t3 + m->t_edge[k];
-            normed(a, m->v_edge[k]);
-            a.tape = t.te[k]; a.out = t.e[k + 1]; a.residual = 1;
-            rc = launch_train_fwd(H, TK_PROC_EDGE, a, s);
-            if (rc != GM_OK) return rc;
-        }
-        // agg_i = sum over edges into i of e' = gamma * sum xhat + deg * beta
-        rc = launch_segment_sum(H, c.in_ptr, nullptr, t.te[k].xhat, ve + (size_t)(NL + 1) * H, ve + (size_t)(NL + 2) * H, t.agg[k], n, s);
+        rc = fwd_step(m, k, t.csr.dst, n, e, t.h[k], t.e[k], t.P, t.step[k], t.h[k + 1], t.e[k + 1], nullptr, 1, k + 1 < M, s);
         if (rc != GM_OK) return rc;
-        {
-            TrainFwdArgs a{};
-            a.rows = (int)n; a.x_in = t.h[k]; a.agg = t.agg[k]; a.wstream = m->packed_t3 + m->t_node[k];
-            normed(a, m->v_node[k]);
-            a.tape = t.tn[k]; a.out = t.h[k + 1]; a.residual = 1;
-            if (k + 1 < M) { a.P_out = t.P; a.proj_bias = m->vec + m->v_edge[k + 1]; }   // tail: the next edge step's P (after the decoder's h_M: none)
-            rc = launch_train_fwd(H, TK_PROC_NODE, a, s);
-            if (rc != GM_OK) return rc;
-        }
     }
     {
         TrainFwdArgs a{};
-        a.rows = (int)n; a.x_in = t.h[M]; a.wstream = m->packed_t3 + m->t_node[M - 1] + (size_t)(NL + 2) * U;
-        const float* v = mlp_vec(m, m->v_dec);
-        a.bias = v; a.bias_tail = v + H; a.nl = NL;
+        a.rows = (int)n; a.x_in = t.h[M]; a.wstream = m->packed_t3 + m->t_dec;
+        a.bias = m->vec + m->v_dec; a.bias_tail = a.bias + m->H; a.nl = m->NL;
         a.tape = t.dec; a.out = out; a.out_dim = m->d.out_dim;
-        rc = launch_train_fwd(H, TK_DEC, a, s);
+        rc = launch_train_fwd(m->H, TK_DEC, a, s);
         if (rc != GM_OK) return rc;
     }
     {   // a flagged edge_index: the prediction is NaN, not a plausible number computed on a different graph
         const size_t cnt = (size_t)n * m->d.out_dim;
-        hipLaunchKernelGGL(poison_if_flagged_kernel, dim3(small_grid(cnt)), dim3(256), 0, s, c.hdr, carve_csr(t.csr_src, n, e).hdr, out, cnt);
+        hipLaunchKernelGGL(poison_if_flagged_kernel, dim3(small_grid(cnt)), dim3(256), 0, s, t.csr.dst.hdr, t.csr.src.hdr, out, cnt);
         GM_LAUNCH_CHECK();
     }
     return GM_OK;
@@ -281,174 +424,87 @@ int gm_epd_forward_train(const gm_model* m, const float* nodes, int64_t n, const
 int gm_epd_backward(const gm_model* m, const float* const* T, int n_tensors, const float* nodes, const float* edge_attr, int64_t n,
                     int64_t e, const float* grad_out, float* const* grads, void* tape, size_t tape_bytes, void* ws, size_t ws_bytes,
                     void* stream) {
-    GM_REQUIRE(!m || m->has_train_streams, GM_ERR_UNSUPPORTED, "%s: the training kernels are instantiated for hidden_size 64 / 128 / 256", "gm_epd_backward");
+    int rc = check_model(m, n, e, __func__);
+    if (rc != GM_OK) return rc;
+    GM_REQUIRE(T && grads && nodes && grad_out && tape && ws && (e == 0 || edge_attr), GM_ERR_INVALID_ARGUMENT, "%s: null pointer", __func__);
+    rc = check_tensors(m, T, grads, n_tensors, 0, n_tensors, __func__);
+    if (rc != GM_OK) return rc;
     gm::DevGuard dev_guard(nodes);
-    int rc = check_sizes(m, n, e, "gm_epd_backward");
-    if (rc != GM_OK) return rc;
-    GM_REQUIRE(T && grads && nodes && grad_out && tape && ws && (e == 0 || edge_attr), GM_ERR_INVALID_ARGUMENT, "gm_epd_backward: null pointer");
-    GM_REQUIRE(n_tensors == gm_model_num_tensors(&m->d), GM_ERR_INVALID_ARGUMENT, "gm_epd_backward: expected %d tensors, got %d",
-               gm_model_num_tensors(&m->d), n_tensors);
-    for (int i = 0; i < n_tensors; ++i)
-        GM_REQUIRE(T[i] && grads[i], GM_ERR_INVALID_ARGUMENT, "gm_epd_backward: tensor / gradient %d is null", i);
-    const int H = m->H, NL = m->NL, M = m->M, OD = m->d.out_dim;
-    Tape t = carve_tape(tape, &m->d, n, e);
-    GM_REQUIRE(tape_bytes >= t.bytes, GM_ERR_WORKSPACE, "gm_epd_backward: tape %zu < %zu", tape_bytes, t.bytes);
-    BwdWs b = carve_bwd(ws, &m->d, n, e);
-    GM_REQUIRE(ws_bytes >= b.bytes, GM_ERR_WORKSPACE, "gm_epd_backward: workspace %zu < %zu", ws_bytes, b.bytes);
-    rc = train_kernels_init();
-    if (rc != GM_OK) return rc;
-    rc = weights_ready_on(m, (hipStream_t)stream);   // the weight streams may have been packed on another stream (model.h)
-    if (rc != GM_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
-    WgradBatch wb;   // weight-gradient jobs run a batch per launch; flushed before anything overwrites their operands
-    wgrad_batch_init(wb, b.part, H, s);
-    CsrWs c = carve_csr(t.csr_dst, n, e);
-    CsrWs c2 = carve_csr(t.csr_src, n, e);
-    const int PM = tensors_per_normed_mlp(NL);
-    const int b_enc_edge = 0, b_enc_node = PM, b_dec = (2 + 2 * M) * PM;
-    auto b_edge = [&](int k) { return (2 + 2 * k) * PM; };
-    auto b_node = [&](int k) { return (3 + 2 * k) * PM; };
-    const size_t U = (size_t)m->T_HH * kStageFloatsB3;
+    const int H = m->H, NL = m->NL, M = m->M, OD = m->d.out_dim, PM = tensors_per_normed_mlp(NL);
+    Tape t = carve_tape(tape, &m->d, n, e);
+    BwdWs b = carve_bwd(ws, &m->d, n, e);
+    rc = ready_to_launch(m, tape_bytes, t.bytes, ws_bytes, b.bytes, s, __func__);
+    if (rc != GM_OK) return rc;
+    BwdRun bw(m, grads, b, s);
+    const CsrWs& c = t.csr.dst;
 
     // ---- transposed operand images of every Linear on the backward path (batched: a few launches)
-    {
-        PackTJobs jobs;
-        jobs.n = 0;
-        auto flush = [&]() {
-            if (rc == GM_OK && jobs.n > 0) rc = launch_pack_b3_batch(jobs, b.packT, s);
-            jobs.n = 0;
-        };
-        auto packT = [&](const float* W, int w_rows, int ld, int col0, int ksub, size_t& off) {
-            if (jobs.n == kPackTJobsMax) flush();
-            PackTJob& j = jobs.job[jobs.n++];
-            j.W = W; j.w_rows = w_rows; j.ld = ld; j.col0 = col0; j.ksub = ksub; j.fwd = 0; j.dst_off = off;
-            off += (size_t)layer_stages_b3(w_rows, ksub) * kStageFloatsB3;
-        };
-        // the hidden Linears NL + 1 .. 2 of an MLP, in the order its backward chain consumes them
-        auto packT_hidden = [&](int base, size_t& off) { for (int l = NL; l >= 1; --l) packT(T[base + 2 * l], H, H, 0, H, off); };
-        size_t off = b.off_dec;
-        packT(T[b_dec + 2 * NL], OD, H, 0, H, off);
-        for (int l = NL - 1; l >= 0; --l) packT(T[b_dec + 2 * l], H, H, 0, H, off);
-        for (int k = 0; k < M; ++k) {
-            off = b.off_node[k];
-            if (k + 1 < M) {
-                packT(T[b_edge(k + 1)], H, 3 * H, m->ci * H, H, off);
-                packT(T[b_edge(k + 1)], H, 3 * H, m->cj * H, H, off);
-            }
-            packT_hidden(b_node(k), off);
-            packT(T[b_node(k)], H, 2 * H, m->ch * H, H, off);
-            packT(T[b_node(k)], H, 2 * H, m->ca * H, H, off);
-            off = b.off_edge[k];
-            packT_hidden(b_edge(k), off);
-            packT(T[b_edge(k)], H, 3 * H, m->ce * H, H, off);
-        }
-        off = b.off_enc_node;
-        packT(T[b_edge(0)], H, 3 * H, m->ci * H, H, off);
-        packT(T[b_edge(0)], H, 3 * H, m->cj * H, H, off);
-        packT_hidden(b_enc_node, off);
-        off = b.off_enc_edge;
-        packT_hidden(b_enc_edge, off);
-        flush();
-        if (rc != GM_OK) return rc;
+    PackBwd pk{m, T, b, s};
+    pk.dec();
+    for (int k = 0; k < M; ++k) {
+        pk.node(k, k);
+        pk.edge(k, k);
     }
-
-    auto wgrad = [&](const float* dz, int ldz, int Mo, const float* X, int ldx, int K, const int* xidx, int64_t rows, float* out, int ldw,
-                     int col0, float* db) {
-        if (rc == GM_OK) rc = wgrad_enqueue(wb, dz, ldz, Mo, X, ldx, K, xidx, rows, out, ldw, col0, db);
-    };
-    // W3 (+ b3), W2 (+ b2) and the LayerNorm gradients of a normed MLP whose chain kernel has just run over `rows`
-    // (b1 comes with the first-layer weight gradient at the call site)
-    auto act = [&](const TapePtr& tp, int l, int64_t rows) { return tp.a + (size_t)(l - 1) * rows * H; };   // a_l
-    // `node_set`: the chain left its dz in the node-sized set (BwdWs::dzn) -- the node MLPs and the node encoder, so that their
-    // jobs and those of the edge chain before them (edge-sized set) wait in one batch: a flush only before each EDGE chain
-    auto dz_of = [&](bool node_set, int l) { return node_set ? b.dznl(l) : b.dzl(l); };
-    auto normed_tail_grads = [&](int base, const TapePtr& tp, int64_t rows, bool node_set) {
-        for (int l = NL; l >= 1; --l)   // Linear l + 1: dW = dz_(l+1)^T a_l
-            wgrad(dz_of(node_set, l + 1), H, H, act(tp, l, rows), H, H, nullptr, rows, grads[base + 2 * l], H, 0, grads[base + 2 * l + 1]);
-    };
-    auto chain = [&](TrainBwdArgs& a) { a.dz = b.dz; a.dz_stride = b.dz_stride; a.nl = NL; };
-    // (the LayerNorm parameter gradients are summed inside the chain kernels: TrainBwdArgs.ln_part / dgamma / dbeta)
-    auto ln_gamma = [&](size_t voff) { return m->vec + voff + (size_t)(NL + 1) * H; };
+    pk.proj(0);
+    pk.enc_node(false);
+    pk.enc_edge(false);
+    rc = pk.flush();
+    if (rc != GM_OK) return rc;
 
     // ---- the upstream gradient as the chains see it: zero for a forward whose edge_index was flagged (see gate_grad_out_kernel)
     {
         const size_t cnt = (size_t)n * OD;
-        hipLaunchKernelGGL(gate_grad_out_kernel, dim3(small_grid(cnt)), dim3(256), 0, s, c.hdr, c2.hdr, grad_out, b.go, cnt);
+        hipLaunchKernelGGL(gate_grad_out_kernel, dim3(small_grid(cnt)), dim3(256), 0, s, c.hdr, t.csr.src.hdr, grad_out, b.go, cnt);
         GM_LAUNCH_CHECK();
-        grad_out = b.go;
     }
     // ---- decoder
     {
+        const int bd = base_dec(m);
         TrainBwdArgs a{};
-        a.rows = (int)n; a.dY = grad_out; a.out_dim = OD; a.tape = t.dec; a.wstream = b.packT + b.off_dec;
-        chain(a); a.dx = b.dh;
-        rc = wgrad_flush(wb);
-        if (rc == GM_OK) rc = launch_train_bwd(H, TB_DEC, a, s);
-        if (rc != GM_OK) return rc;
-        wgrad(grad_out, OD, OD, act(t.dec, NL, n), H, H, nullptr, n, grads[b_dec + 2 * NL], H, 0, grads[b_dec + 2 * NL + 1]);
-        for (int l = NL - 1; l >= 1; --l)
-            wgrad(b.dzl(l + 1), H, H, act(t.dec, l, n), H, H, nullptr, n, grads[b_dec + 2 * l], H, 0, grads[b_dec + 2 * l + 1]);
-        wgrad(b.dzl(1), H, H, t.h[M], H, H, nullptr, n, grads[b_dec + 0], H, 0, grads[b_dec + 1]);
-        if (rc != GM_OK) return rc;
+        a.rows = (int)n; a.dY = b.go; a.out_dim = OD; a.tape = t.dec; a.wstream = b.packT + b.off_dec;
+        a.dz = b.dz; a.dz_stride = b.dz_stride; a.nl = NL; a.dx = b.dh;
+        bw.launch(TB_DEC, a, true, nullptr);
+        bw.wgrad(b.go, OD, OD, t.dec.a + (size_t)(NL - 1) * n * H, H, H, nullptr, n, grads[bd + 2 * NL], H, 0, grads[bd + 2 * NL + 1]);
+        bw.tail(a, bd, NL - 1);
+        bw.wgrad(b.dzl(1), H, H, t.h[M], H, H, nullptr, n, grads[bd], H, 0, grads[bd + 1]);
     }
     // ---- processor blocks, last to first
     for (int k = M - 1; k >= 0; --k) {
         const bool has_next = k + 1 < M;
+        const int be = base_edge(m, k), bn = base_node(m, k);
         {
             TrainBwdArgs a{};
-            a.rows = (int)n; a.dY = b.dh; a.Gi = has_next ? b.Gi : nullptr; a.Gj = has_next ? b.Gj : nullptr;
-            a.tape = t.tn[k]; a.ln_g = ln_gamma(m->v_node[k]); a.wstream = b.packT + b.off_node[k];
-            a.ln_part = b.part; a.dgamma = grads[b_node(k) + 2 * (NL + 1)]; a.dbeta = grads[b_node(k) + 2 * (NL + 1) + 1]; a.dz = b.dzn; a.dz_stride = b.dzn_stride; a.nl = NL; a.dx_resid = b.dh; a.dx = b.dh; a.dagg_out = b.dagg;
-            // no flush: the waiting jobs read the edge-sized dz set, Gi / Gj and tapes -- nothing this chain writes
-            rc = launch_train_bwd(H, TB_NODE, a, s, &wb);
-            if (rc != GM_OK) return rc;
-            normed_tail_grads(b_node(k), t.tn[k], n, true);
-            wgrad(b.dznl(1), H, H, t.h[k], H, H, nullptr, n, grads[b_node(k)], 2 * H, m->ch * H, grads[b_node(k) + 1]);
-            wgrad(b.dznl(1), H, H, t.agg[k], H, H, nullptr, n, grads[b_node(k)], 2 * H, m->ca * H, nullptr);
-            if (rc != GM_OK) return rc;
+            a.rows = (int)n; a.dY = b.dh; a.Gi = has_next ? b.Gi : nullptr; a.Gj = has_next ? b.Gj : nullptr; a.tape = t.step[k].tn;
+            a.wstream = b.packT + b.off_node[k]; a.dx_resid = b.dh; a.dx = b.dh; a.dagg_out = b.dagg;
+            // node-sized dz set: the waiting jobs read the edge-sized one, Gi / Gj and tapes -- nothing this chain writes
+            bw.chain(TB_NODE, a, bn, m->v_node[k], true);
+            bw.wgrad(b.dznl(1), H, H, t.h[k], H, H, nullptr, n, grads[bn], 2 * H, m->ch * H, grads[bn + 1]);
+            bw.wgrad(b.dznl(1), H, H, t.step[k].agg, H, H, nullptr, n, grads[bn], 2 * H, m->ca * H, nullptr);
         }
         {
             TrainBwdArgs a{};
-            a.rows = (int)e; a.dY = has_next ? b.de : nullptr; a.dagg = b.dagg; a.dst = c.dst;
-            a.tape = t.te[k]; a.ln_g = ln_gamma(m->v_edge[k]); a.wstream = b.packT + b.off_edge[k];
-            a.ln_part = b.part; a.dgamma = grads[b_edge(k) + 2 * (NL + 1)]; a.dbeta = grads[b_edge(k) + 2 * (NL + 1) + 1]; a.dz = b.dz; a.dz_stride = b.dz_stride; a.nl = NL; a.dx = b.de; a.residual = 1;
-            rc = wgrad_flush(wb);
-        if (rc == GM_OK) rc = launch_train_bwd(H, TB_EDGE, a, s, &wb);
-            if (rc != GM_OK) return rc;
-            normed_tail_grads(b_edge(k), t.te[k], e, false);
-            wgrad(b.dzl(1), H, H, t.e[k], H, H, nullptr, e, grads[b_edge(k)], 3 * H, m->ce * H, grads[b_edge(k) + 1]);
-            if (rc != GM_OK) return rc;
-            // node-level sums of dz1: everything the factorised layer 1 needs
-            rc = launch_segment_sum_pair(H, c.in_ptr, nullptr, c2.in_ptr, c2.eid, b.dzl(1), nullptr, nullptr, b.Gi, b.Gj, n, s);
-            wgrad(b.Gi, H, H, t.h[k], H, H, nullptr, n, grads[b_edge(k)], 3 * H, m->ci * H, nullptr);
-            wgrad(b.Gj, H, H, t.h[k], H, H, nullptr, n, grads[b_edge(k)], 3 * H, m->cj * H, nullptr);
-            if (rc != GM_OK) return rc;
+            a.rows = (int)e; a.dY = has_next ? b.de : nullptr; a.dagg = b.dagg; a.dst = c.dst; a.tape = t.step[k].te;
+            a.wstream = b.packT + b.off_edge[k]; a.dx = b.de; a.residual = 1;
+            bw.chain(TB_EDGE, a, be, m->v_edge[k], false);
+            bw.wgrad(b.dzl(1), H, H, t.e[k], H, H, nullptr, e, grads[be], 3 * H, m->ce * H, grads[be + 1]);
+            bw.ij_grads(t.csr, t.h[k], be, n);
         }
     }
     // ---- encoders
     {
         TrainBwdArgs a{};
-        a.rows = (int)n; a.dY = b.dh; a.Gi = b.Gi; a.Gj = b.Gj; a.tape = t.en; a.ln_g = ln_gamma(m->v_enc_node);
-        a.wstream = b.packT + b.off_enc_node;
-        a.ln_part = b.part; a.dgamma = grads[b_enc_node + 2 * (NL + 1)]; a.dbeta = grads[b_enc_node + 2 * (NL + 1) + 1]; a.dz = b.dzn; a.dz_stride = b.dzn_stride; a.nl = NL;
-        rc = launch_train_bwd(H, TB_ENC, a, s, &wb);   // no flush: as the node MLPs
-        if (rc != GM_OK) return rc;
-        normed_tail_grads(b_enc_node, t.en, n, true);
-        wgrad(b.dznl(1), H, H, nodes, m->d.node_dim, m->d.node_dim, nullptr, n, grads[b_enc_node], m->d.node_dim, 0, grads[b_enc_node + 1]);
-        if (rc != GM_OK) return rc;
+        a.rows = (int)n; a.dY = b.dh; a.Gi = b.Gi; a.Gj = b.Gj; a.tape = t.enc.en; a.wstream = b.packT + b.off_proj;
+        bw.chain(TB_ENC, a, PM, m->v_enc_node, true);   // as the node MLPs
+        bw.wgrad(b.dznl(1), H, H, nodes, m->d.node_dim, m->d.node_dim, nullptr, n, grads[PM], m->d.node_dim, 0, grads[PM + 1]);
     }
     if (e > 0) {
         TrainBwdArgs a{};
-        a.rows = (int)e; a.dY = b.de; a.tape = t.ee; a.ln_g = ln_gamma(m->v_enc_edge); a.wstream = b.packT + b.off_enc_edge;
-        a.ln_part = b.part; a.dgamma = grads[b_enc_edge + 2 * (NL + 1)]; a.dbeta = grads[b_enc_edge + 2 * (NL + 1) + 1]; a.dz = b.dz; a.dz_stride = b.dz_stride; a.nl = NL;
-        rc = wgrad_flush(wb);
-        if (rc == GM_OK) rc = launch_train_bwd(H, TB_ENC, a, s, &wb);
-        if (rc != GM_OK) return rc;
-        normed_tail_grads(b_enc_edge, t.ee, e, false);
-        wgrad(b.dzl(1), H, H, edge_attr, m->d.edge_dim, m->d.edge_dim, c.eid, e, grads[b_enc_edge], m->d.edge_dim, 0, grads[b_enc_edge + 1]);
-        if (rc != GM_OK) return rc;
+        a.rows = (int)e; a.dY = b.de; a.tape = t.enc.ee; a.wstream = b.packT + b.off_enc_edge;
+        bw.chain(TB_ENC, a, 0, m->v_enc_edge, false);
+        bw.wgrad(b.dzl(1), H, H, edge_attr, m->d.edge_dim, m->d.edge_dim, c.eid, e, grads[0], m->d.edge_dim, 0, grads[1]);
     }
-    return wgrad_flush(wb);
+    return bw.finish();
 }
 
 
@@ -467,240 +523,118 @@ size_t gm_block_backward_workspace_bytes(const gm_model_desc* desc, int64_t n, i
 
 int gm_graph_independent_forward_train(const gm_model* m, const float* x, int64_t n, const float* edge_attr, int64_t e, float* h_out,
                                        float* e_out, void* tape, size_t tape_bytes, void* stream) {
-    GM_REQUIRE(!m || m->has_train_streams, GM_ERR_UNSUPPORTED, "%s: the training kernels are instantiated for hidden_size 64 / 128 / 256", "gm_graph_independent_forward_train");
+    int rc = check_model(m, n, e, __func__);
+    if (rc != GM_OK) return rc;
+    GM_REQUIRE(x && h_out && tape && (e == 0 || (edge_attr && e_out)), GM_ERR_INVALID_ARGUMENT, "%s: null pointer", __func__);
     gm::DevGuard dev_guard(x ? (const void*)x : (const void*)edge_attr);
-    int rc = check_sizes(m, n, e, "gm_graph_independent_forward_train");
-    if (rc != GM_OK) return rc;
-    GM_REQUIRE(x && h_out && tape && (e == 0 || (edge_attr && e_out)), GM_ERR_INVALID_ARGUMENT, "gm_graph_independent_forward_train: null pointer");
-    const int H = m->H, NL = m->NL;
-    GiTape t = carve_gi_tape(tape, H, NL, n, e);
-    GM_REQUIRE(tape_bytes >= t.bytes, GM_ERR_WORKSPACE, "gm_graph_independent_forward_train: tape %zu < %zu", tape_bytes, t.bytes);
-    rc = train_kernels_init();
-    if (rc != GM_OK) return rc;
-    rc = weights_ready_on(m, (hipStream_t)stream);   // the weight streams may have been packed on another stream (model.h)
-    if (rc != GM_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
-    auto normed = [&](TrainFwdArgs& a, size_t voff) {
-        const float* v = mlp_vec(m, voff);
-        a.bias = v; a.bias_tail = v + H; a.ln_g = v + (size_t)(NL + 1) * H; a.ln_b = v + (size_t)(NL + 2) * H; a.eps = m->d.ln_eps; a.nl = NL;
-    };
-    TrainFwdArgs a{};
-    a.rows = (int)e; a.x_in = edge_attr; a.k1 = m->d.edge_dim; a.wstream = m->packed_t3 + m->t_enc_edge;
-    normed(a, m->v_enc_edge);
-    a.tape = t.ee; a.out = e_out;
-    rc = launch_train_fwd(H, TK_ENC_EDGE, a, s);
+    GiTape t = carve_gi_tape(tape, m->H, m->NL, n, e);
+    rc = ready_to_launch(m, tape_bytes, t.bytes, 0, 0, s, __func__);
     if (rc != GM_OK) return rc;
-    TrainFwdArgs b{};
-    b.rows = (int)n; b.x_in = x; b.k1 = m->d.node_dim; b.wstream = m->packed_t3 + m->t_enc_node;
-    normed(b, m->v_enc_node);
-    b.tape = t.en; b.out = h_out;
-    return launch_train_fwd(H, TK_ENC_NODE, b, s);
+    return fwd_encoders(m, n, e, x, edge_attr, nullptr, t.enc, h_out, e_out, nullptr, s);
 }
 
 int gm_graph_independent_backward(const gm_model* m, const float* const* T, int n_tensors, const float* x, const float* edge_attr, int64_t n,
                                   int64_t e, const float* dh, const float* de, float* dx, float* dedge_attr, float* const* grads,
                                   void* tape, size_t tape_bytes, void* ws, size_t ws_bytes, void* stream) {
-    GM_REQUIRE(!m || m->has_train_streams, GM_ERR_UNSUPPORTED, "%s: the training kernels are instantiated for hidden_size 64 / 128 / 256", "gm_graph_independent_backward");
+    int rc = check_model(m, n, e, __func__);
+    if (rc != GM_OK) return rc;
+    GM_REQUIRE(T && grads && x && dh && tape && ws && (e == 0 || (edge_attr && de)), GM_ERR_INVALID_ARGUMENT, "%s: null pointer", __func__);
+    const int H = m->H, NL = m->NL, PM = tensors_per_normed_mlp(NL);
+    rc = check_tensors(m, T, grads, n_tensors, 0, 2 * PM, __func__);
+    if (rc != GM_OK) return rc;
     gm::DevGuard dev_guard(x ? (const void*)x : (const void*)edge_attr);
-    int rc = check_sizes(m, n, e, "gm_graph_independent_backward");
-    if (rc != GM_OK) return rc;
-    GM_REQUIRE(T && grads && x && dh && tape && ws && (e == 0 || (edge_attr && de)), GM_ERR_INVALID_ARGUMENT, "gm_graph_independent_backward: null pointer");
-    GM_REQUIRE(n_tensors == gm_model_num_tensors(&m->d), GM_ERR_INVALID_ARGUMENT, "gm_graph_independent_backward: expected %d tensors, got %d",
-               gm_model_num_tensors(&m->d), n_tensors);
-    const int H = m->H, NL = m->NL;
-    const int PM = tensors_per_normed_mlp(NL);
-    for (int i = 0; i < 2 * PM; ++i) GM_REQUIRE(T[i] && grads[i], GM_ERR_INVALID_ARGUMENT, "gm_graph_independent_backward: tensor / gradient %d is null", i);
-    GiTape t = carve_gi_tape(tape, H, NL, n, e);
-    GM_REQUIRE(tape_bytes >= t.bytes, GM_ERR_WORKSPACE, "gm_graph_independent_backward: tape %zu < %zu", tape_bytes, t.bytes);
-    BwdWs b = carve_block_bwd(ws, &m->d, n, e);
-    GM_REQUIRE(ws_bytes >= b.bytes, GM_ERR_WORKSPACE, "gm_graph_independent_backward: workspace %zu < %zu", ws_bytes, b.bytes);
-    rc = train_kernels_init();
-    if (rc != GM_OK) return rc;
-    rc = weights_ready_on(m, (hipStream_t)stream);   // the weight streams may have been packed on another stream (model.h)
-    if (rc != GM_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
-    WgradBatch wb;   // weight-gradient jobs run a batch per launch; flushed before anything overwrites their operands
-    wgrad_batch_init(wb, b.part, H, s);
-    const size_t U = (size_t)m->T_HH * kStageFloatsB3;
-    PackTJobs jobs;
-    jobs.n = 0;
-    auto packT = [&](const float* W, size_t off) {
-        PackTJob& j = jobs.job[jobs.n++];
-        j.W = W; j.w_rows = H; j.ld = H; j.col0 = 0; j.ksub = H; j.fwd = 0; j.dst_off = off;
-    };
-    // node stream sits behind the (unused) projection slots of the model layout
-    for (int l = NL; l >= 1; --l) {
-        packT(T[PM + 2 * l], b.off_enc_node + (size_t)(2 + NL - l) * U);
-        packT(T[2 * l], b.off_enc_edge + (size_t)(NL - l) * U);
-    }
-    auto packT_in = [&](const float* W, int k1, size_t off) {  // (W1 [H, k1])^T as a Linear with k1 outputs, H inputs
-        PackTJob& j = jobs.job[jobs.n++];
-        j.W = W; j.w_rows = H; j.ld = k1; j.col0 = 0; j.ksub = k1; j.fwd = 0; j.dst_off = off;
-    };
-    if (dx) packT_in(T[PM], m->d.node_dim, b.off_enc_node + (size_t)(NL + 2) * U);
-    if (dedge_attr) packT_in(T[0], m->d.edge_dim, b.off_enc_edge + (size_t)NL * U);
-    rc = launch_pack_b3_batch(jobs, b.packT, s);
+    GiTape t = carve_gi_tape(tape, H, NL, n, e);
+    BwdWs b = carve_block_bwd(ws, &m->d, n, e);
+    rc = ready_to_launch(m, tape_bytes, t.bytes, ws_bytes, b.bytes, s, __func__);
+    if (rc != GM_OK) return rc;
+    BwdRun bw(m, grads, b, s);
+    PackBwd pk{m, T, b, s};
+    pk.enc_node(dx != nullptr);
+    pk.enc_edge(dedge_attr != nullptr);
+    rc = pk.flush();
     if (rc != GM_OK) return rc;
     auto run = [&](int base, const TapePtr& tp, int64_t rows, const float* dY, size_t voff, size_t woff, const float* X, int k1, float* dxin) {
-        if (rows <= 0 || rc != GM_OK) return;
+        if (rows <= 0) return;
         TrainBwdArgs a{};
-        a.rows = (int)rows; a.dY = dY; a.tape = tp; a.ln_g = m->vec + voff + (size_t)(NL + 1) * H; a.wstream = b.packT + woff;
-        a.dx_in = dxin; a.k1 = k1;
-        a.ln_part = b.part; a.dgamma = grads[base + 2 * (NL + 1)]; a.dbeta = grads[base + 2 * (NL + 1) + 1]; a.dz = b.dz; a.dz_stride = b.dz_stride; a.nl = NL;
-        rc = wgrad_flush(wb);
-        if (rc == GM_OK) rc = launch_train_bwd(H, TB_ENC, a, s, &wb);
-        for (int l = NL; l >= 1 && rc == GM_OK; --l)
-            rc = wgrad_enqueue(wb, b.dzl(l + 1), H, H, tp.a + (size_t)(l - 1) * rows * H, H, H, nullptr, rows, grads[base + 2 * l], H, 0,
-                              grads[base + 2 * l + 1]);
-        if (rc == GM_OK) rc = wgrad_enqueue(wb, b.dzl(1), H, H, X, k1, k1, nullptr, rows, grads[base], k1, 0, grads[base + 1]);
+        a.rows = (int)rows; a.dY = dY; a.tape = tp; a.wstream = b.packT + woff; a.dx_in = dxin; a.k1 = k1;
+        bw.chain(TB_ENC, a, base, voff, false);
+        bw.wgrad(b.dzl(1), H, H, X, k1, k1, nullptr, rows, grads[base], k1, 0, grads[base + 1]);
     };
-    run(PM, t.en, n, dh, m->v_enc_node, b.off_enc_node + 2 * U, x, m->d.node_dim, dx);
-    run(0, t.ee, e, de, m->v_enc_edge, b.off_enc_edge, edge_attr, m->d.edge_dim, dedge_attr);
-    if (rc == GM_OK) rc = wgrad_flush(wb);
-    return rc;
+    run(PM, t.enc.en, n, dh, m->v_enc_node, b.off_enc_node, x, m->d.node_dim, dx);
+    run(0, t.enc.ee, e, de, m->v_enc_edge, b.off_enc_edge, edge_attr, m->d.edge_dim, dedge_attr);
+    return bw.finish();
 }
 
 int gm_interaction_network_forward_train(const gm_model* m, int k, const float* h, int64_t n, const float* e_in, const int64_t* edge_index,
                                          int64_t e, float* h_out, float* e_out, void* tape, size_t tape_bytes, void* stream) {
-    GM_REQUIRE(!m || m->has_train_streams, GM_ERR_UNSUPPORTED, "%s: the training kernels are instantiated for hidden_size 64 / 128 / 256", "gm_interaction_network_forward_train");
+    int rc = check_model(m, n, e, __func__);
+    if (rc != GM_OK) return rc;
+    GM_REQUIRE(k >= 0 && k < m->M, GM_ERR_INVALID_ARGUMENT, "%s: block %d out of range", __func__, k);
+    GM_REQUIRE(h && h_out && tape && (e == 0 || (e_in && e_out && edge_index)), GM_ERR_INVALID_ARGUMENT, "%s: null pointer", __func__);
     gm::DevGuard dev_guard(h);
-    int rc = check_sizes(m, n, e, "gm_interaction_network_forward_train");
-    if (rc != GM_OK) return rc;
-    GM_REQUIRE(k >= 0 && k < m->M, GM_ERR_INVALID_ARGUMENT, "gm_interaction_network_forward_train: block %d out of range", k);
-    GM_REQUIRE(h && h_out && tape && (e == 0 || (e_in && e_out && edge_index)), GM_ERR_INVALID_ARGUMENT, "gm_interaction_network_forward_train: null pointer");
-    const int H = m->H, NL = m->NL;
-    InTape t = carve_in_tape(tape, H, NL, n, e);
-    GM_REQUIRE(tape_bytes >= t.bytes, GM_ERR_WORKSPACE, "gm_interaction_network_forward_train: tape %zu < %zu", tape_bytes, t.bytes);
-    rc = train_kernels_init();
-    if (rc != GM_OK) return rc;
-    rc = weights_ready_on(m, (hipStream_t)stream);   // the weight streams may have been packed on another stream (model.h)
-    if (rc != GM_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
-    rc = gm::csr_from_edge_index(edge_index, n, e, m->d.flow, t.csr_dst, t.csr_bytes, false, (hipStream_t)stream);
+    InTape t = carve_in_tape(tape, m->H, m->NL, n, e);
+    rc = ready_to_launch(m, tape_bytes, t.bytes, 0, 0, s, __func__);
     if (rc != GM_OK) return rc;
-    CsrWs c = carve_csr(t.csr_dst, n, e);
-    rc = launch_swap_index(c.src, e, t.ei2, s);
+    rc = build_csr(t.csr, edge_index, n, e, m->d.flow, s);
     if (rc != GM_OK) return rc;
-    rc = gm::csr_from_edge_index(t.ei2, n, e, 0, t.csr_src, t.csr_bytes, false, (hipStream_t)stream);
-    if (rc != GM_OK) return rc;
-    const size_t U = (size_t)m->T_HH * kStageFloatsB3;
     {
         TrainFwdArgs pa{};   // P = [h W_i^T + b1 | h W_j^T] of this block's edge MLP
-        pa.rows = (int)n; pa.x_in = h; pa.bias = m->vec + m->v_edge[k]; pa.out = t.P; pa.nl = NL;
-        pa.wstream = k == 0 ? m->packed_t3 + m->t_enc_node + (size_t)(m->T_n0 + NL * m->T_HH) * kStageFloatsB3
-                            : m->packed_t3 + m->t_node[k - 1] + (size_t)(NL + 2) * U;
-        rc = launch_train_fwd(H, TK_PROJ, pa, s);
-    }
-    if (rc != GM_OK) return rc;
-    auto normed = [&](TrainFwdArgs& a, size_t voff) {
-        const float* v = mlp_vec(m, voff);
-        a.bias = v; a.bias_tail = v + H; a.ln_g = v + (size_t)(NL + 1) * H; a.ln_b = v + (size_t)(NL + 2) * H; a.eps = m->d.ln_eps; a.nl = NL;
-    };
-    {
-        TrainFwdArgs a{};
-        a.rows = (int)e; a.x_in = e_in; a.rowidx = c.eid; a.dst = c.dst; a.src = c.src; a.P = t.P; a.wstream = m->packed_t3 + m->t_edge[k];
-        normed(a, m->v_edge[k]);
-        a.tape = t.te; a.out = e_out; a.residual = 0;
-        rc = launch_train_fwd(H, TK_PROC_EDGE, a, s);
+        pa.rows = (int)n; pa.x_in = h; pa.bias = m->vec + m->v_edge[k]; pa.out = t.P; pa.nl = m->NL; pa.wstream = m->packed_t3 + m->t_proj[k];
+        rc = launch_train_fwd(m->H, TK_PROJ, pa, s);
         if (rc != GM_OK) return rc;
     }
-    const float* ve = mlp_vec(m, m->v_edge[k]);
-    rc = launch_segment_sum(H, c.in_ptr, nullptr, t.te.xhat, ve + (size_t)(NL + 1) * H, ve + (size_t)(NL + 2) * H, t.agg, n, s);
-    if (rc != GM_OK) return rc;
-    TrainFwdArgs a{};
-    a.rows = (int)n; a.x_in = h; a.agg = t.agg; a.wstream = m->packed_t3 + m->t_node[k];
-    normed(a, m->v_node[k]);
-    a.tape = t.tn; a.out = h_out; a.residual = 0;
-    return launch_train_fwd(H, TK_PROC_NODE, a, s);
+    return fwd_step(m, k, t.csr.dst, n, e, h, e_in, t.P, t.st, h_out, e_out, t.csr.dst.eid, 0, false, s);
 }
 
 int gm_interaction_network_backward(const gm_model* m, int k, const float* const* T, int n_tensors, const float* h, const float* e_in,
                                     int64_t n, int64_t e, const float* dh_out, const float* de_out, float* dh_in, float* de_in,
                                     float* const* grads, void* tape, size_t tape_bytes, void* ws, size_t ws_bytes, void* stream) {
-    GM_REQUIRE(!m || m->has_train_streams, GM_ERR_UNSUPPORTED, "%s: the training kernels are instantiated for hidden_size 64 / 128 / 256", "gm_interaction_network_backward");
-    gm::DevGuard dev_guard(h);
-    int rc = check_sizes(m, n, e, "gm_interaction_network_backward");
+    int rc = check_model(m, n, e, __func__);
     if (rc != GM_OK) return rc;
-    GM_REQUIRE(k >= 0 && k < m->M, GM_ERR_INVALID_ARGUMENT, "gm_interaction_network_backward: block %d out of range", k);
+    GM_REQUIRE(k >= 0 && k < m->M, GM_ERR_INVALID_ARGUMENT, "%s: block %d out of range", __func__, k);
     GM_REQUIRE(T && grads && h && dh_out && dh_in && tape && ws && (e == 0 || (e_in && de_out && de_in)), GM_ERR_INVALID_ARGUMENT,
-               "gm_interaction_network_backward: null pointer");
-    GM_REQUIRE(n_tensors == gm_model_num_tensors(&m->d), GM_ERR_INVALID_ARGUMENT, "gm_interaction_network_backward: expected %d tensors, got %d",
-               gm_model_num_tensors(&m->d), n_tensors);
-    const int H = m->H, NL = m->NL;
-    const int PM = tensors_per_normed_mlp(NL);
-    const int be = (2 + 2 * k) * PM, bn = (3 + 2 * k) * PM;
-    for (int i = be; i < bn + PM; ++i) GM_REQUIRE(T[i] && grads[i], GM_ERR_INVALID_ARGUMENT, "gm_interaction_network_backward: tensor / gradient %d is null", i);
-    InTape t = carve_in_tape(tape, H, NL, n, e);
-    GM_REQUIRE(tape_bytes >= t.bytes, GM_ERR_WORKSPACE, "gm_interaction_network_backward: tape %zu < %zu", tape_bytes, t.bytes);
-    BwdWs b = carve_block_bwd(ws, &m->d, n, e);
-    GM_REQUIRE(ws_bytes >= b.bytes, GM_ERR_WORKSPACE, "gm_interaction_network_backward: workspace %zu < %zu", ws_bytes, b.bytes);
-    rc = train_kernels_init();
+               "%s: null pointer", __func__);
+    const int H = m->H, be = base_edge(m, k), bn = base_node(m, k);
+    rc = check_tensors(m, T, grads, n_tensors, be, bn + tensors_per_normed_mlp(m->NL), __func__);
     if (rc != GM_OK) return rc;
-    rc = weights_ready_on(m, (hipStream_t)stream);   // the weight streams may have been packed on another stream (model.h)
-    if (rc != GM_OK) return rc;
+    gm::DevGuard dev_guard(h);
     hipStream_t s = (hipStream_t)stream;
-    WgradBatch wb;   // weight-gradient jobs run a batch per launch; flushed before anything overwrites their operands
-    wgrad_batch_init(wb, b.part, H, s);
-    CsrWs c = carve_csr(t.csr_dst, n, e);
-    CsrWs c2 = carve_csr(t.csr_src, n, e);
-    const size_t U = (size_t)m->T_HH * kStageFloatsB3;
-    {
-        PackTJobs jobs;
-        jobs.n = 0;
-        auto packT = [&](const float* W, int ld, int col0, size_t off) {
-            PackTJob& j = jobs.job[jobs.n++];
-            j.W = W; j.w_rows = H; j.ld = ld; j.col0 = col0; j.ksub = H; j.fwd = 0; j.dst_off = off;
-        };
-        for (int l = NL; l >= 1; --l) {
-            packT(T[bn + 2 * l], H, 0, b.off_node[0] + (size_t)(NL - l) * U);
-            packT(T[be + 2 * l], H, 0, b.off_edge[0] + (size_t)(NL - l) * U);
-        }
-        packT(T[bn], 2 * H, m->ch * H, b.off_node[0] + (size_t)NL * U);
-        packT(T[bn], 2 * H, m->ca * H, b.off_node[0] + (size_t)(NL + 1) * U);
-        packT(T[be], 3 * H, m->ce * H, b.off_edge[0] + (size_t)NL * U);
-        packT(T[be], 3 * H, m->ci * H, b.off_enc_node);       // W_i^T, W_j^T: projection backward
-        packT(T[be], 3 * H, m->cj * H, b.off_enc_node + U);
-        rc = launch_pack_b3_batch(jobs, b.packT, s);
-        if (rc != GM_OK) return rc;
-    }
-    auto wgrad = [&](const float* dz, const float* X, int64_t rows, float* out, int ldw, int col0, float* db) {
-        if (rc == GM_OK) rc = wgrad_enqueue(wb, dz, H, H, X, H, H, nullptr, rows, out, ldw, col0, db);
-    };
+    InTape t = carve_in_tape(tape, H, m->NL, n, e);
+    BwdWs b = carve_block_bwd(ws, &m->d, n, e);
+    rc = ready_to_launch(m, tape_bytes, t.bytes, ws_bytes, b.bytes, s, __func__);
+    if (rc != GM_OK) return rc;
+    BwdRun bw(m, grads, b, s);
+    const CsrWs& c = t.csr.dst;
+    PackBwd pk{m, T, b, s};
+    pk.node(k, 0);
+    pk.edge(k, 0);
+    pk.proj(k);
+    rc = pk.flush();
+    if (rc != GM_OK) return rc;
     // node MLP: dY = dh_out (no residual inside the block); dx = W_h^T dz1 -> b.dh, dagg -> b.dagg
     {
         TrainBwdArgs a{};
-        a.rows = (int)n; a.dY = dh_out; a.tape = t.tn; a.ln_g = m->vec + m->v_node[k] + (size_t)(NL + 1) * H; a.wstream = b.packT + b.off_node[0];
-        a.ln_part = b.part; a.dgamma = grads[bn + 2 * (NL + 1)]; a.dbeta = grads[bn + 2 * (NL + 1) + 1]; a.dz = b.dz; a.dz_stride = b.dz_stride; a.nl = NL; a.dx = b.dh; a.dagg_out = b.dagg;
-        rc = wgrad_flush(wb);
-        if (rc == GM_OK) rc = launch_train_bwd(H, TB_NODE, a, s, &wb);
-        if (rc != GM_OK) return rc;
-        for (int l = NL; l >= 1; --l) wgrad(b.dzl(l + 1), t.tn.a + (size_t)(l - 1) * n * H, n, grads[bn + 2 * l], H, 0, grads[bn + 2 * l + 1]);
-        wgrad(b.dzl(1), h, n, grads[bn], 2 * H, m->ch * H, grads[bn + 1]);
-        wgrad(b.dzl(1), t.agg, n, grads[bn], 2 * H, m->ca * H, nullptr);
-        if (rc != GM_OK) return rc;
+        a.rows = (int)n; a.dY = dh_out; a.tape = t.st.tn; a.wstream = b.packT + b.off_node[0]; a.dx = b.dh; a.dagg_out = b.dagg;
+        bw.chain(TB_NODE, a, bn, m->v_node[k], false);
+        bw.wgrad(b.dzl(1), H, H, h, H, H, nullptr, n, grads[bn], 2 * H, m->ch * H, grads[bn + 1]);
+        bw.wgrad(b.dzl(1), H, H, t.st.agg, H, H, nullptr, n, grads[bn], 2 * H, m->ca * H, nullptr);
     }
     if (e > 0) {
         TrainBwdArgs a{};
-        a.rows = (int)e; a.dY = de_out; a.dyidx = c.eid; a.dagg = b.dagg; a.dst = c.dst; a.tape = t.te;
-        a.ln_g = m->vec + m->v_edge[k] + (size_t)(NL + 1) * H; a.wstream = b.packT + b.off_edge[0];
-        a.ln_part = b.part; a.dgamma = grads[be + 2 * (NL + 1)]; a.dbeta = grads[be + 2 * (NL + 1) + 1]; a.dz = b.dz; a.dz_stride = b.dz_stride; a.nl = NL; a.dx = de_in; a.dxidx = c.eid; a.residual = 0;
-        rc = wgrad_flush(wb);
-        if (rc == GM_OK) rc = launch_train_bwd(H, TB_EDGE, a, s, &wb);
-        if (rc != GM_OK) return rc;
-        for (int l = NL; l >= 1; --l) wgrad(b.dzl(l + 1), t.te.a + (size_t)(l - 1) * e * H, e, grads[be + 2 * l], H, 0, grads[be + 2 * l + 1]);
-        if (rc == GM_OK) rc = wgrad_enqueue(wb, b.dzl(1), H, H, e_in, H, H, c.eid, e, grads[be], 3 * H, m->ce * H, grads[be + 1]);
-        if (rc != GM_OK) return rc;
+        a.rows = (int)e; a.dY = de_out; a.dyidx = c.eid; a.dagg = b.dagg; a.dst = c.dst; a.tape = t.st.te; a.wstream = b.packT + b.off_edge[0];
+        a.dx = de_in; a.dxidx = c.eid;
+        bw.chain(TB_EDGE, a, be, m->v_edge[k], false);
+        bw.wgrad(b.dzl(1), H, H, e_in, H, H, c.eid, e, grads[be], 3 * H, m->ce * H, grads[be + 1]);
     }
-    rc = launch_segment_sum_pair(H, c.in_ptr, nullptr, c2.in_ptr, c2.eid, b.dzl(1), nullptr, nullptr, b.Gi, b.Gj, n, s);
-    wgrad(b.Gi, h, n, grads[be], 3 * H, m->ci * H, nullptr);
-    wgrad(b.Gj, h, n, grads[be], 3 * H, m->cj * H, nullptr);
-    if (rc != GM_OK) return rc;
+    bw.ij_grads(t.csr, h, be, n);
     // dh_in = W_h^T dz1 (node MLP) + W_i^T G_i + W_j^T G_j (edge MLP, factorised layer 1)
     TrainBwdArgs a{};
-    a.rows = (int)n; a.dY = b.dh; a.Gi = b.Gi; a.Gj = b.Gj; a.wstream = b.packT + b.off_enc_node; a.dx = dh_in;
-    rc = wgrad_flush(wb);
-    if (rc != GM_OK) return rc;
-    return launch_train_bwd(H, TB_PROJ, a, s);
+    a.rows = (int)n; a.dY = b.dh; a.Gi = b.Gi; a.Gj = b.Gj; a.wstream = b.packT + b.off_proj; a.dx = dh_in;
+    bw.launch(TB_PROJ, a, true, nullptr);
+    return bw.rc;
 }
 
 }  // extern "C"

@@ -59,3 +59,44 @@ def test_state_dict_layout_matches_reference_fixture(golden):
     assert sum(p.numel() for p in m.parameters()) == 1591299
     m3 = EncProcDecGNN(25, 4, 3, 64, 3, 2)
     assert sorted(m3.state_dict().keys()) == list(g7["h64_l3_m2.keys"])
+
+
+# (hidden_size, num_layers, m_steps), (n, e) -> gm_train_tape_bytes, gm_train_backward_workspace_bytes, gm_block_tape_bytes of the
+# GraphIndependent and of the InteractionNetwork, gm_block_backward_workspace_bytes: the training tape and workspace layouts
+TRAIN_BYTES = {
+    ((64, 2, 1), (1, 0)): (7168, 73345792, 1280, 4608, 73345792),
+    ((64, 2, 1), (300, 4000)): (9651456, 77980416, 3388672, 3902720, 77980416),
+    ((64, 5, 10), (1, 0)): (32512, 77033728, 2048, 5376, 73715968),
+    ((64, 5, 10), (300, 4000)): (88446720, 84969216, 6794240, 7308288, 81651456),
+    ((128, 2, 10), (1, 0)): (38144, 84514048, 2048, 6144, 76551424),
+    ((128, 2, 10), (300, 4000)): (101020672, 93779712, 6759936, 7504384, 85817088),
+    ((128, 5, 2), (1, 0)): (19712, 79503616, 3584, 7680, 78029056),
+    ((128, 5, 2), (300, 4000)): (49008128, 95371008, 13571072, 14315520, 93896448),
+    ((256, 2, 2), (1, 0)): (22784, 88762624, 3584, 9216, 85223680),
+    ((256, 2, 2), (300, 4000)): (55862272, 107290368, 13502208, 14707456, 103751424),
+    ((256, 5, 1), (1, 0)): (26368, 91128064, 6656, 12288, 91128064),
+    ((256, 5, 1), (300, 4000)): (65845248, 122859264, 27124736, 28329984, 122859264),
+}
+
+
+def test_training_tape_and_workspace_sizes_are_pinned():
+    import ctypes as C
+    from gnn_manip_amd import _lib
+    L = _lib.lib()
+    for ((hidden, num_layers, m_steps), (n, e)), want in TRAIN_BYTES.items():
+        d = C.byref(_lib.ModelDesc(25, 4, 3, hidden, num_layers, m_steps, 1e-5))
+        got = (L.gm_train_tape_bytes(d, n, e), L.gm_train_backward_workspace_bytes(d, n, e), L.gm_block_tape_bytes(d, 0, n, e),
+               L.gm_block_tape_bytes(d, 1, n, e), L.gm_block_backward_workspace_bytes(d, n, e))
+        assert got == want, (hidden, num_layers, m_steps, n, e, got)
+
+
+def test_training_entry_points_reject_a_null_model():
+    """Every other argument null or zero: the null model is what each one reports, before any device call."""
+    import ctypes as C
+    from gnn_manip_amd import _lib
+    L = _lib.lib()
+    for name in ("gm_epd_forward_train", "gm_epd_backward", "gm_graph_independent_forward_train", "gm_graph_independent_backward",
+                 "gm_interaction_network_forward_train", "gm_interaction_network_backward"):
+        args = [None if t is C.c_void_p else 0 for t in _lib.PROTOTYPES[name][1]]
+        assert getattr(L, name)(*args) == -1, name   # GM_ERR_INVALID_ARGUMENT
+        assert L.gm_last_error() == f"{name}: null model".encode()
