@@ -1,14 +1,18 @@
 #!/usr/bin/env python3
 """Rollout-throughput bench for the MI355X rollout engine (contract: see DESIGN.md "Measurement").
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload target|c2|c3|c4|c5] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload target|c2|c3|c4|c5] [--dump-outputs DIR] [--full]
 
 A "step" is one full rollout step of the hot path (state update -> node features -> radius graph -> destination sort
 -> edge features -> encode / 10x process / decode -> Euler integration), the loop body of compute_rollout
 (gnn_manip/utils/rollout_utils.py:38-61), on a seeded synthetic dense granular scene resident in HBM.  The K timed steps
 run inside ONE library call (gm_rollout).  Default workload = the north_star target line (N = 100k, hidden 128, 10
-message-passing steps); at N = 1 the other single-GPU configurations of BASELINE.json (C2, C3, C4) are measured in the
-same process and reported as sub-records under "extra", each with its own roofline.
+message-passing steps).
+
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps, --dump-outputs, the JSON line.  --full adds
+what takes runs of its own: the roofline and per-kernel breakdown from a separate instrumented pass and, at N = 1, the CPU
+baseline and sub-records under "extra": the other single-GPU configurations of BASELINE.json (C2, C3, C4, each with its own
+roofline; C5) and a few training steps.
 
 N > 1 = candidate-parallel (weak scaling): every rank rolls out its own candidates of the same scene; the scripted
 trajectories are broadcast before and the per-candidate results all-gathered after the loop, over RCCL.
@@ -261,9 +265,10 @@ def roofline_record(model, ek, hidden, edges, n_nodes, workload_key):
     return rec, k_ms
 
 
-def measure(wl_key, dev, rank, world, dist, cdev, args, steps, warmup, candidates=1, outputs=None):
+def measure(wl_key, dev, rank, world, dist, cdev, args, steps, warmup, candidates=1, outputs=None, profile=False):
     """outputs: a dict that receives, after the timed region, what its rollout handed back: `state`, the [k, N, D] window run()
-    leaves in place, and with collectives `gathered_results`, the [world, 3] per-rank results of the all-gather."""
+    leaves in place, and with collectives `gathered_results`, the [world, 3] per-rank results of the all-gather.
+    profile: rank 0 adds `roofline` and `breakdown` from an instrumented pass after the timed region (--full)."""
     from gnn_manip_amd import _lib
     wl = WORKLOADS[wl_key]
     total = steps + warmup
@@ -318,8 +323,16 @@ def measure(wl_key, dev, rank, world, dist, cdev, args, steps, warmup, candidate
         outputs["state"] = obs.cpu().numpy()
         if dist:
             outputs["gathered_results"] = torch.stack(gathered).cpu().numpy()
-    rec = None
-    if rank == 0:
+    if rank != 0:
+        return None, (model, obs_np, stats, scene, ek)
+    rec = {"value": world * candidates * steps / el, "unit": "rollout steps/s", "steps": steps, "warmup": warmup,
+           "ms_per_step": el / steps * 1e3,
+           "config": {"workload": wl["name"], "n_particles": wl["n"], "hidden": wl["hidden"], "edges_last_step": edges, "k_steps": 6,
+                      "candidates_per_gpu": candidates, "parallelism": f"candidate-parallel x{world}",
+                      "particle_ids": "random (scene.make_scene); the engine renumbers its working copy in grid-cell order per run() call, "
+                                      "inside the timed region" if eng.renumber else "random (scene.make_scene), used as given"},
+           "collective_ms": coll * 1e3}
+    if profile:
         # Kernel timings: the same K steps once more, untimed, with HIP events (on the launch stream) around every model kernel
         # of this handle -- the dominant kernel's average launch duration for the roofline, the others for the breakdown.
         # A kind records at most 4096 scopes (gm_model_profile): the pass is bounded so that none fills up (a step opens ~31 node-side
@@ -344,13 +357,7 @@ def measure(wl_key, dev, rank, world, dist, cdev, args, steps, warmup, candidate
         # the parts are kernel time (HIP events of a separate, instrumented pass); ms_per_step is the wall time of the uninstrumented
         # timed region: their ratio says how much of the step is launch gaps / unattributed work
         br["sum_of_parts_ms_per_step"] = None if any(p is None for p in parts) else sum(parts)
-        rec = {"value": world * candidates * steps / el, "unit": "rollout steps/s", "steps": steps, "warmup": warmup,
-               "ms_per_step": el / steps * 1e3,
-               "config": {"workload": wl["name"], "n_particles": wl["n"], "hidden": wl["hidden"], "edges_last_step": edges, "k_steps": 6,
-                          "candidates_per_gpu": candidates, "parallelism": f"candidate-parallel x{world}",
-                          "particle_ids": "random (scene.make_scene); the engine renumbers its working copy in grid-cell order per run() call, "
-                                          "inside the timed region" if eng.renumber else "random (scene.make_scene), used as given"},
-               "roofline": roof, "breakdown": br, "collective_ms": coll * 1e3}
+        rec["roofline"], rec["breakdown"] = roof, br
         if br["sum_of_parts_ms_per_step"] is not None:
             br["sum_of_parts_over_step"] = br["sum_of_parts_ms_per_step"] / rec["ms_per_step"]
     return rec, (model, obs_np, stats, scene, ek)
@@ -590,8 +597,11 @@ def main():
                     help="seconds after which a multi-rank run that has not finished is ended with a non-zero exit (the launcher "
                          "terminates the ranks it started; a rank started by torch.distributed.run gives up its rendezvous / "
                          "collectives after the same time)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the C2 / C3 / C4 sub-records")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the roofline and per-kernel breakdown (an instrumented pass "
+                         "after the timed steps), and at one GPU the C2 / C3 / C4 / C5 / training sub-records and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the C2 / C3 / C4 / C5 / training sub-records")
     ap.add_argument("--edge-kernel", default="auto", choices=["auto", "sys", "sys_all", "hm"],
                     help="processor edge kernel (per-model option): auto = systolic fp16 x 3 kernel for hidden 128 (DESIGN.md 5.1)")
     ap.add_argument("--dump-outputs", metavar="DIR",
@@ -648,7 +658,7 @@ def main():
         steps = args.steps if args.steps > 0 else wl["steps"]
         warmup = args.warmup if args.warmup >= 0 else wl["warmup"]
         rec, (model, obs_np, stats, scene, ek) = measure(args.workload, dev, rank, world, dist, cdev, args, steps, warmup, args.candidates,
-                                                         outputs)
+                                                         outputs, profile=args.full)
         if outputs is not None:
             dump_outputs(args.dump_outputs, outputs)
         if rank == 0:
@@ -661,11 +671,13 @@ def main():
                                  "MFMA pipe, fp32 accumulation (1e-6 vs float64 through the model, like plain fp32)",
                    "data": "synthetic (seeded dense scene; random-init weights, decoder output layer scaled 1e-5 so the pile stays dense "
                            "over the rollout)",
-                   "config": rec["config"], "roofline": rec["roofline"], "breakdown": rec["breakdown"]}
+                   "config": rec["config"]}
+            if args.full:
+                out["roofline"], out["breakdown"] = rec["roofline"], rec["breakdown"]
             if dist:
                 out["collective_ms"] = rec["collective_ms"]   # rank 0: broadcast + all-gather (incl. waiting for the slowest rank)
                 out["collective_backend"] = dist.get_backend()
-            if world == 1 and not args.no_extra and args.workload == "target" and args.candidates == 1:
+            if args.full and world == 1 and not args.no_extra and args.workload == "target" and args.candidates == 1:
                 extra = {}
 
                 def sub(key, fn):   # a sub-record that fails is reported as such; the headline above stands on its own
@@ -677,11 +689,11 @@ def main():
 
                 for key in ("c2", "c3", "c4"):
                     w2 = WORKLOADS[key]
-                    sub(key, lambda: measure(key, dev, rank, world, None, cdev, args, w2["steps"], w2["warmup"], 1)[0])
+                    sub(key, lambda: measure(key, dev, rank, world, None, cdev, args, w2["steps"], w2["warmup"], 1, profile=True)[0])
                 sub("c5_1gpu", lambda: extra_c5_1gpu(dev, args))
                 sub("train", lambda: extra_train(dev))
                 out["extra"] = extra
-            if world == 1 and not args.no_cpu_baseline:
+            if args.full and world == 1 and not args.no_cpu_baseline:
                 out["cpu_baseline"] = cpu_baseline(obs_np, model, stats, scene, hidden)
             print(json.dumps(out))
     if dist:

@@ -75,3 +75,29 @@ def test_bench_dumps_the_state_its_timed_steps_computed(tmp_path):
     # Particles move ~1e-6 per step and the kernels sum in a fixed order: a bound of 1e-7 tells one step more or less apart.
     assert np.abs(state - after_warmup).max() > 1e-7
     np.testing.assert_allclose(state, obs.cpu().numpy(), rtol=0, atol=1e-7)
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_is_lean_and_full_adds_the_rest(tmp_path):
+    """A plain run prints the headline alone; `--full` adds the roofline and breakdown of the instrumented pass after the timed
+    steps.  Both at the C2 size as fresh child processes, without the CPU baseline (which only `--full` would run anyway)."""
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "GM_BENCH_REHEARSE"):
+        env.pop(k, None)
+    recs = {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline"])):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c2", "--steps", "3", "--warmup", "1"] + extra,
+                           env=env, capture_output=True, timeout=600)
+        assert r.returncode == 0, r.stdout.decode(errors="replace") + r.stderr.decode(errors="replace")
+        lines = [l for l in r.stdout.decode().splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        recs[mode] = json.loads(lines[0])
+    for rec in recs.values():
+        assert rec["unit"] == "rollout steps/s" and rec["higher_is_better"] is True and rec["dtype"] == "f32"
+        assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["value"] > 0 and rec["ms_per_step"] > 0
+        assert rec["metric"] == "rollout steps/sec (N particles, 10 MP steps, hidden=128)"
+    assert not {"roofline", "breakdown", "extra", "cpu_baseline"} & set(recs["plain"])
+    full = recs["full"]
+    assert full["roofline"]["kernel"].startswith("sys_edge_kernel") and full["roofline"]["avg_launch_ms"] > 0
+    assert full["breakdown"]["profiled_steps"] == 3 and full["breakdown"]["edge_kernel_ms_per_step"] > 0
+    assert "extra" not in full and "cpu_baseline" not in full   # sub-records: target workload only; baseline: skipped

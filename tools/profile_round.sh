@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/prof_$TAG
 mkdir -p $O
-B="--no-cpu-baseline --no-extra"
+B="--full --no-cpu-baseline --no-extra"
 for wl in target c2 c4; do
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/$wl -- python3 $R/bench.py --workload $wl $B > $O/$wl.log 2>&1
 done
