@@ -4,6 +4,8 @@
 #include <vector>
 #include "common.h"
 #include "hmlp.h"
+#include "mlp.h"
+#include "train.h"
 
 namespace gm {
 // choices of gm_model_set_edge_kernel (ABI values; 1 .. 4 were the round-1 fp32 / bf16 x 6 kernels, removed in round 5)
@@ -13,6 +15,12 @@ enum EdgeKernel : int {
     EK_HM = 6,        // the streamed kernels everywhere
     EK_SYS_ALL = 7,   // as EK_SYS, and the systolic node path at any graph size
 };
+
+// One MLP of the state_dict (epd_gnn.py:63-84): tensors [base, end) = W_0, b_0, .., W_NL, b_NL [, gamma, beta]; `in` inputs of
+// Linear 0, `out` outputs of Linear NL, hidden_size between them; normed: ends in a LayerNorm (all but the decoder)
+struct MlpSpec { int base, end, in, out; bool normed; };
+// the model's MLPs in state_dict order: edge encoder, node encoder, the edge and node MLP of each step, the decoder
+std::vector<MlpSpec> model_mlps(const gm_model_desc& d);
 }  // namespace gm
 
 struct gm_model {
@@ -21,38 +29,41 @@ struct gm_model {
     int Hp = 0;                   // the width the inference kernels run at: H zero-padded to 64 / 128 / 256 (hm_padded_hidden)
     int ci = 0, cj = 1, ce = 2;   // column block of phi_e's first Linear that multiplies h_i, h_j, e (gm_model_desc.col_*)
     int ch = 0, ca = 1;           // column block of phi_v's first Linear for h, agg (gm_model_desc.node_agg_first)
-    float* packed_h3 = nullptr;  // fp16 hi / lo images of the systolic kernels (hedge.h), h3_image_floats() each: the M processor edge MLPs, the
-                                 // edge encoder, then the M processor node MLPs (agg block of Linear 1 | Linear 2 | Linear 3)
-    float* packed_hm = nullptr;  // fp16 hi / lo image of every Linear (hmlp.h)
-    std::vector<gm::PackHmJob> hm_jobs;   // the pack job list of the last weight load (host copy of hm_jobs_dev)
-    void* hm_jobs_dev = nullptr;
-    float* hm_stats = nullptr;
-    size_t hm_jobs_cap = 0;
-    size_t hm_floats = 0, hm_enc_edge = 0, hm_enc_node = 0, hm_enc_node_tail = 0;
-    std::vector<size_t> hm_edge, hm_node, hm_node_tail;
-    std::vector<size_t> hm_node_q;   // Linear image of Q = h W_h^T + b1 of node step k (systolic node path: hedge.h)
-    bool has_train_streams = false;   // hidden 64 / 128 / 256: the bf16 x 3 streams (packed_t3) of the training kernels exist
-    gm::ProfState* prof = nullptr;  // gm_model_profile
-    int edge_kernel = gm::EK_AUTO;   // gm_model_set_edge_kernel: which kernels the forwards of this model may take (gm::EdgeKernel)
-    float* vec = nullptr;     // per-MLP contiguous [bias_0..bias_NL, ln_gamma, ln_beta]
-    size_t vec_floats = 0;
-    // vec offsets (floats): start of MLP block
-    size_t v_enc_edge, v_enc_node, v_dec;
-    std::vector<size_t> v_edge, v_node;
-    // bf16 x 3 weight streams of the training kernels (train.hip): MLP after MLP, stages of kStageFloatsB3
-    float* packed_t3 = nullptr;
-    size_t packed_t3_floats = 0;
-    size_t t_enc_edge = 0, t_enc_node = 0, t_dec = 0;
-    std::vector<size_t> t_edge, t_node;
-    std::vector<size_t> t_proj;   // [W_i | W_j] images of step k: the tail of the node encoder (k = 0) or of node step k - 1
+    std::vector<gm::MlpSpec> mlp;   // gm::model_mlps(d)
+    const gm::MlpSpec& edge_mlp(int k) const { return mlp[2 + 2 * k]; }
+    const gm::MlpSpec& node_mlp(int k) const { return mlp[3 + 2 * k]; }
+    // Every buffer below is laid out, and every job that fills it planned, once by gm_model_create (plan_weights); a load
+    // launches the jobs.  Offsets are in floats from the buffer's base.
     // The model's own copy of the raw tensors (device).  A weight update refreshes it and the cheap images (vec, the training
     // streams); the inference images (packed_hm, packed_h3) are re-packed from it by the first inference call that follows
     // (ensure_inference_images): a training loop, which updates the weights every step, never pays for them.
     float* raw = nullptr;
-    std::vector<size_t> raw_off;
-    size_t raw_floats = 0;
+    std::vector<gm::VecJob> raw_jobs;   // one per tensor: where it goes (each load supplies the source)
+    float* vec = nullptr;     // per-MLP contiguous [bias_0..bias_NL, ln_gamma, ln_beta]
+    std::vector<gm::VecJob> vec_jobs;
+    size_t v_enc_edge, v_enc_node, v_dec;   // start of each MLP's block
+    std::vector<size_t> v_edge, v_node;
+    // bf16 x 3 weight streams of the training kernels (train.hip), hidden 64 / 128 / 256 only: MLP after MLP, stages of kStageFloatsB3
+    float* packed_t3 = nullptr;
+    std::vector<gm::PackTJob> t_jobs;
+    size_t t_enc_edge = 0, t_enc_node = 0, t_dec = 0;
+    std::vector<size_t> t_edge, t_node, t_proj;   // t_proj: [W_i | W_j] of step k, the tail of the node encoder (k = 0) or node step k - 1
+    float* packed_hm = nullptr;  // fp16 hi / lo image of every Linear (hmlp.h)
+    std::vector<gm::PackHmJob> hm_jobs;   // host copy of hm_jobs_dev
+    gm::PackHmJob* hm_jobs_dev = nullptr;
+    float* hm_stats = nullptr;
+    size_t hm_enc_edge = 0, hm_enc_node = 0, hm_enc_node_tail = 0;
+    std::vector<size_t> hm_edge, hm_node, hm_node_tail, hm_node_q;   // hm_node_q: Q = h W_h^T + b1 of node step k (hedge.h)
+    // fp16 hi / lo images of the systolic kernels (hedge.h), hidden 128 / num_layers 2 only: the M processor edge MLPs, the edge
+    // encoder, then the M processor node MLPs (agg block of Linear 1 | Linear 2 | Linear 3)
+    float* packed_h3 = nullptr;
+    std::vector<gm::PackH3Job> h3_jobs;
+    size_t h3_enc = 0;
+    std::vector<size_t> h3_edge, h3_node;
     bool infer_stale = true;
     std::mutex lazy_mu;
+    gm::ProfState* prof = nullptr;  // gm_model_profile
+    int edge_kernel = gm::EK_AUTO;   // gm_model_set_edge_kernel: which kernels the forwards of this model may take (gm::EdgeKernel)
     // Every copy / pack of the weights is queued on the stream of the call that triggered it; `ready` is recorded behind the last
     // one.  An entry point that runs on ANOTHER stream waits for it there (weights_ready_on), so a model may be loaded on one
     // stream and used on others.  (The other direction -- a weight update while a forward on another stream still reads the old
@@ -63,6 +74,3 @@ struct gm_model {
 int ensure_inference_images(const gm_model* m, hipStream_t s);   // model.hip; called by every inference entry point
 int weights_ready_on(const gm_model* m, hipStream_t s);          // model.hip; called by every entry point that reads the packed weights
 
-namespace gm {
-inline int tensors_per_normed_mlp(int NL) { return 2 * (NL + 1) + 2; }
-}  // namespace gm

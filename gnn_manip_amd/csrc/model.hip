@@ -1,5 +1,6 @@
 // Model handle (packed weight image), forward orchestration and the device-resident rollout step.
-// Host-side C++ only: every kernel lives in graph.hip / features.hip / mlp.hip.
+// Host-side C++ only: the kernels it launches live in the other .hip files.
+#include <algorithm>
 #include <vector>
 #include "common.h"
 #include "mlp.h"
@@ -10,6 +11,22 @@
 
 using namespace gm;
 
+std::vector<MlpSpec> gm::model_mlps(const gm_model_desc& d) {
+    const int H = d.hidden_size, NL = d.num_layers;
+    std::vector<MlpSpec> mlp;
+    auto add = [&](int in, int out, bool normed) {
+        const int base = mlp.empty() ? 0 : mlp.back().end;
+        mlp.push_back({base, base + 2 * (NL + 1) + (normed ? 2 : 0), in, out, normed});
+    };
+    add(d.edge_dim, H, true);
+    add(d.node_dim, H, true);
+    for (int k = 0; k < d.m_steps; ++k) {
+        add(3 * H, H, true);
+        add(2 * H, H, true);
+    }
+    add(H, d.out_dim, false);
+    return mlp;
+}
 
 namespace {
 
@@ -55,200 +72,197 @@ FwdWs carve_fwd(void* ws, int H, int64_t n, int64_t cap_e, int64_t cap_side) {
     return f;
 }
 
-// element count of tensor ti in the state_dict order (epd_gnn.py:63-84: per MLP  W_0, b_0, .., W_NL, b_NL [, gamma, beta])
-size_t tensor_floats(const gm_model* m, int ti) {
-    const int H = m->H, NL = m->NL, M = m->M;
-    const int PM = tensors_per_normed_mlp(NL);
-    const int n_normed = 2 + 2 * M;
-    int mlp = ti / PM, r = ti % PM;
-    int in_dim, out_last = H;
-    if (mlp >= n_normed) { mlp = n_normed; r = ti - n_normed * PM; in_dim = H; out_last = m->d.out_dim; }
-    else if (mlp == 0) in_dim = m->d.edge_dim;
-    else if (mlp == 1) in_dim = m->d.node_dim;
-    else in_dim = (mlp % 2 == 0) ? 3 * H : 2 * H;
-    if (r >= 2 * (NL + 1)) return (size_t)H;   // LayerNorm gamma / beta
-    const int l = r / 2;
-    const int out = l == NL ? out_last : H, in = l == 0 ? in_dim : H;
-    return (r % 2) ? (size_t)out : (size_t)out * in;
-}
+struct WeightSizes { size_t raw, vec, t3, hm, h3; };   // floats of each buffer plan_weights lays out
 
-// (re)build the operand images + vec from the caller's tensors (device pointers)
-constexpr int kPackCommon = 1;      // vec + the training streams
-constexpr int kPackInference = 2;   // packed_hm, packed_h3
-int load_weights_device(gm_model* m, const float* const* T, hipStream_t s, int what) {
+// The one walk over the model's weights: where each raw tensor goes, then the layout of every image, the jobs that pack it from
+// the raw copy and the offsets the forward and training code read.  Called with the buffers still null it only sizes them;
+// gm_model_create calls it again once they are allocated, and every load launches the jobs it planned.
+WeightSizes plan_weights(gm_model* m) {
     // H: the width the kernels run at (hidden_size zero-padded to 64 / 128 / 256: strides, image sizes); Hv: the model's hidden_size
     const int H = m->Hp, Hv = m->H, NL = m->NL, M = m->M;
-    const int PM = tensors_per_normed_mlp(NL);
-    int rc = GM_OK;
-    const int b_enc_edge = 0, b_enc_node = PM, b_dec = (2 + 2 * M) * PM;
-    auto b_edge = [&](int k) { return (2 + 2 * k) * PM; };
-    auto b_node = [&](int k) { return (3 + 2 * k) * PM; };
-
-    if (m->packed_hm && (what & kPackInference)) {   // fp16 hi / lo images of every Linear (hmlp.h); consecutive Linears of an MLP form a scale chain
-        std::vector<PackHmJob>& jobs = m->hm_jobs;
-        jobs.clear();
-        int prev = -1;   // job whose output feeds the next lin() (-1: the next one heads a chain)
-        float head_rms = 1.f;
-        auto lin = [&](int ti, int ld, int col0a, int col0b, int out_valid, int out_pad, int out_seg, int k_valid, int k_pad, int k_seg,
-                       bool with_bias, int bias_n, size_t& off, int gain_col0 = 0, int gain_cols = 0) {
-            PackHmJob j{};
-            j.W = T[ti]; j.ld = ld; j.bias = with_bias ? T[ti + 1] : nullptr; j.bias_n = bias_n;
-            j.out_valid = out_valid; j.out_pad = out_pad; j.out_seg = out_seg;
-            j.k_valid = k_valid; j.k_pad = k_pad; j.k_seg = k_seg; j.col0[0] = col0a; j.col0[1] = col0b;
-            j.pred = prev; j.in_rms = head_rms; j.gain_col0 = gain_col0; j.gain_cols = gain_cols;
-            j.dst = m->packed_hm + off;
-            off += hm_lin_floats(out_pad, k_pad);
-            prev = (int)jobs.size();
-            jobs.push_back(j);
+    const MlpSpec &enc_edge = m->mlp[0], &enc_node = m->mlp[1], &dec = m->mlp.back();
+    WeightSizes z{};
+    for (auto* v : {&m->v_edge, &m->v_node, &m->t_proj, &m->t_edge, &m->t_node, &m->hm_edge, &m->hm_node, &m->hm_node_tail,
+                    &m->hm_node_q, &m->h3_edge, &m->h3_node})
+        v->assign(M, 0);
+    std::vector<const float*> T;   // the raw copy of each tensor
+    m->raw_jobs.clear();
+    for (const MlpSpec& p : m->mlp) {
+        auto put = [&](int count) {
+            m->raw_jobs.push_back({nullptr, z.raw, count, 0});
+            T.push_back(m->raw + z.raw);
+            z.raw += ((size_t)count + 3) & ~(size_t)3;
         };
-        auto head = [&](float rms) { prev = -1; head_rms = rms; };
-        auto hh = [&](int ti, size_t& off) { lin(ti, Hv, 0, 0, Hv, H, H, Hv, H, H, true, Hv, off); };
-        // Linears 1 .. NL of an MLP that ends in a LayerNorm (the decoder's are queued one by one): the last one is packed centred
-        auto hidden = [&](int base, size_t& off) {
-            for (int l = 1; l <= NL; ++l) hh(base + 2 * l, off);
-            jobs.back().center = 1;
-        };
-        auto proj = [&](int k, size_t& off) {   // P = h [W_i | W_j]^T + [b1 | 0] of processor step k: a chain of its own (input h)
-            head(1.f);
-            lin(b_edge(k), 3 * Hv, m->ci * Hv, m->cj * Hv, Hv, 2 * H, H, Hv, H, H, true, Hv, off);
-        };
-        size_t off = m->hm_enc_edge;
-        head(kHmRawInputRms);   // raw edge features: per-row power-of-two scale in the kernel
-        lin(b_enc_edge, m->d.edge_dim, 0, 0, Hv, H, H, m->d.edge_dim, 16, 16, true, Hv, off);
-        hidden(b_enc_edge, off);
-        off = m->hm_enc_node;
-        head(kHmRawInputRms);
-        lin(b_enc_node, m->d.node_dim, 0, 0, Hv, H, H, m->d.node_dim, 32, 32, true, Hv, off);
-        hidden(b_enc_node, off);
-        proj(0, off);
-        for (int k = 0; k < M; ++k) {
-            off = m->hm_edge[k];
-            head(1.f);
-            // the e block; b1 lives in P_i.  Its pre-activation also takes h_i and h_j: the gain is that of the whole [H x 3H] Linear
-            lin(b_edge(k), 3 * Hv, m->ce * Hv, 0, Hv, H, H, Hv, H, H, false, 0, off, 0, 3 * Hv);
-            hidden(b_edge(k), off);
-            off = m->hm_node[k];
-            head(1.f);
-            lin(b_node(k), 2 * Hv, m->ch * Hv, m->ca * Hv, Hv, H, H, Hv, 2 * H, H, true, Hv, off);
-            hidden(b_node(k), off);
-            if (k + 1 < M) proj(k + 1, off);
-            else {
-                head(1.f);
-                for (int l = 0; l < NL; ++l) hh(b_dec + 2 * l, off);
-                lin(b_dec + 2 * NL, Hv, 0, 0, m->d.out_dim, 32, 32, Hv, H, H, true, m->d.out_dim, off);
-            }
-        }
-        for (int k = 0; k < M; ++k) {   // Q = h W_h^T + b1 of node step k (systolic node path): a chain of its own, input h
-            off = m->hm_node_q[k];
-            head(1.f);
-            lin(b_node(k), 2 * Hv, m->ch * Hv, 0, Hv, H, H, Hv, H, H, true, Hv, off);
-        }
-        GM_REQUIRE(jobs.size() <= m->hm_jobs_cap, GM_ERR_INVALID_ARGUMENT, "model: %zu pack jobs, room for %zu", jobs.size(), m->hm_jobs_cap);
-        rc = pack_hm(jobs.data(), (int)jobs.size(), static_cast<PackHmJob*>(m->hm_jobs_dev), m->hm_stats, s);
-        if (rc != GM_OK) return rc;
-    }
-
-    if (what & kPackCommon) {
-    // biases + LayerNorm vectors (training, LayerNorm of every kernel)
-    VecJobs vj;
-    vj.n = 0;
-    auto flush_vec = [&]() {
-        if (rc == GM_OK && vj.n > 0) rc = launch_vec_batch(vj, m->vec, s);
-        vj.n = 0;
-    };
-    auto queue_vec = [&](const float* src, size_t off, int count, int zero_to) {
-        if (vj.n == kVecJobsMax) flush_vec();
-        VecJob& j = vj.job[vj.n++];
-        j.src = src; j.dst_off = off; j.count = count; j.zero_to = zero_to;
-    };
-    auto vecs = [&](int base, bool normed, size_t voff) {  // biases (+ LN) of the MLP whose first tensor is `base`
         for (int l = 0; l <= NL; ++l) {
-            const bool dec_out = !normed && l == NL;
-            if (dec_out) queue_vec(T[base + 2 * l + 1], voff + (size_t)NL * H, m->d.out_dim, 32);
-            else queue_vec(T[base + 2 * l + 1], voff + (size_t)l * H, Hv, Hv < H ? H : 0);
+            const int out = l == NL ? p.out : Hv, in = l == 0 ? p.in : Hv;
+            put(out * in);
+            put(out);
         }
-        if (normed) {   // LayerNorm gamma / beta: zero on the padded features, which therefore stay exactly zero
-            queue_vec(T[base + 2 * (NL + 1)], voff + (size_t)(NL + 1) * H, Hv, Hv < H ? H : 0);
-            queue_vec(T[base + 2 * (NL + 1) + 1], voff + (size_t)(NL + 2) * H, Hv, Hv < H ? H : 0);
-        }
-    };
-    vecs(b_enc_edge, true, m->v_enc_edge);
-    vecs(b_enc_node, true, m->v_enc_node);
-    for (int k = 0; k < M; ++k) {
-        vecs(b_edge(k), true, m->v_edge[k]);
-        vecs(b_node(k), true, m->v_node[k]);
+        if (p.normed) { put(Hv); put(Hv); }
     }
-    vecs(b_dec, false, m->v_dec);
-    flush_vec();
-    if (rc != GM_OK) return rc;
-    if (m->packed_t3) {   // bf16 x 3 streams of the training kernels: the forward Linears in the order the chains consume them
-        PackTJobs tj;
-        tj.n = 0;
-        auto flush_t = [&]() {
-            if (rc == GM_OK && tj.n > 0) rc = launch_pack_b3_batch(tj, m->packed_t3, s);
-            tj.n = 0;
+
+    // biases + LayerNorm vectors (training, LayerNorm of every kernel), zero on the padded features, which therefore stay exactly zero
+    m->vec_jobs.clear();
+    auto vecs = [&](const MlpSpec& p) {
+        const size_t start = z.vec;
+        auto put = [&](int ti, int count, int width) {
+            m->vec_jobs.push_back({T[ti], z.vec, count, count < width ? width : 0});
+            z.vec += width;
         };
-        auto pack3 = [&](int ti, int out_rows, int ld, int col0, int k, size_t& off) {
-            if (tj.n == kPackTJobsMax) flush_t();
-            PackTJob& j = tj.job[tj.n++];
-            j.W = T[ti]; j.w_rows = k; j.ld = ld; j.col0 = col0; j.ksub = out_rows; j.fwd = 1; j.dst_off = off;
-            off += (size_t)layer_stages_b3(k, out_rows) * kStageFloatsB3;
+        for (int l = 0; l <= NL; ++l) put(p.base + 2 * l + 1, l == NL ? p.out : Hv, p.normed || l < NL ? H : 32);
+        if (p.normed) { put(p.base + 2 * NL + 2, Hv, H); put(p.base + 2 * NL + 3, Hv, H); }
+        return start;
+    };
+    m->v_enc_edge = vecs(enc_edge);
+    m->v_enc_node = vecs(enc_node);
+    for (int k = 0; k < M; ++k) {
+        m->v_edge[k] = vecs(m->edge_mlp(k));
+        m->v_node[k] = vecs(m->node_mlp(k));
+    }
+    m->v_dec = vecs(dec);
+
+    // bf16 x 3 streams of the training kernels, for the widths they exist for: the forward Linears in the order the chains consume them
+    m->t_jobs.clear();
+    if (Hv == 64 || Hv == 128 || Hv == 256) {
+        auto t3 = [&](int ti, int out_rows, int ld, int col0, int k) {
+            m->t_jobs.push_back({T[ti], k, ld, col0, out_rows, 1, z.t3});
+            z.t3 += (size_t)layer_stages_b3(k, out_rows) * kStageFloatsB3;
         };
-        auto hidden3 = [&](int base, size_t& off) { for (int l = 1; l <= NL; ++l) pack3(base + 2 * l, H, H, 0, H, off); };
-        size_t off = m->t_enc_edge;
-        pack3(b_enc_edge, H, m->d.edge_dim, 0, m->d.edge_dim, off);
-        hidden3(b_enc_edge, off);
-        off = m->t_enc_node;
-        pack3(b_enc_node, H, m->d.node_dim, 0, m->d.node_dim, off);
-        hidden3(b_enc_node, off);
-        // the node encoder's stream and each node step's go on into the next step's W_i, W_j and the last one's into the decoder:
-        // the training entry points read those images where gm_model_create recorded them
+        auto hidden3 = [&](const MlpSpec& p) { for (int l = 1; l <= NL; ++l) t3(p.base + 2 * l, l == NL ? p.out : H, H, 0, H); };
+        auto whole3 = [&](const MlpSpec& p) { t3(p.base, H, p.in, 0, p.in); hidden3(p); };   // Linear 0 in one block: encoders, decoder
+        m->t_enc_edge = z.t3;
+        whole3(enc_edge);
+        m->t_enc_node = z.t3;
+        whole3(enc_node);
+        // the node encoder's stream and each node step's go on into the next step's W_i, W_j and the last one's into the decoder
         for (int k = 0; k < M; ++k) {
-            GM_REQUIRE(off == m->t_proj[k], GM_ERR_INVALID_ARGUMENT, "model: training stream of step %d's W_i, W_j at %zu, recorded at %zu", k,
-                       off, m->t_proj[k]);
-            pack3(b_edge(k), H, 3 * H, m->ci * H, H, off);  // W_i
-            pack3(b_edge(k), H, 3 * H, m->cj * H, H, off);  // W_j
-            off = m->t_edge[k];
-            pack3(b_edge(k), H, 3 * H, m->ce * H, H, off);  // W_e
-            hidden3(b_edge(k), off);
-            off = m->t_node[k];
-            pack3(b_node(k), H, 2 * H, m->ch * H, H, off);  // W_h
-            pack3(b_node(k), H, 2 * H, m->ca * H, H, off);  // W_agg
-            hidden3(b_node(k), off);
+            const MlpSpec &e = m->edge_mlp(k), &n = m->node_mlp(k);
+            m->t_proj[k] = z.t3;
+            t3(e.base, H, 3 * H, m->ci * H, H);   // W_i
+            t3(e.base, H, 3 * H, m->cj * H, H);   // W_j
+            m->t_edge[k] = z.t3;
+            t3(e.base, H, 3 * H, m->ce * H, H);   // W_e
+            hidden3(e);
+            m->t_node[k] = z.t3;
+            t3(n.base, H, 2 * H, m->ch * H, H);   // W_h
+            t3(n.base, H, 2 * H, m->ca * H, H);   // W_agg
+            hidden3(n);
         }
-        GM_REQUIRE(off == m->t_dec, GM_ERR_INVALID_ARGUMENT, "model: training stream of the decoder at %zu, recorded at %zu", off, m->t_dec);
-        for (int l = 0; l < NL; ++l) pack3(b_dec + 2 * l, H, H, 0, H, off);
-        pack3(b_dec + 2 * NL, m->d.out_dim, H, 0, H, off);
-        flush_t();
+        m->t_dec = z.t3;
+        whole3(dec);
+    }
+
+    // fp16 hi / lo images of every Linear (hmlp.h); consecutive Linears of an MLP form a scale chain
+    std::vector<PackHmJob>& jobs = m->hm_jobs;
+    jobs.clear();
+    int prev = -1;   // job whose output feeds the next lin() (-1: the next one heads a chain)
+    float head_rms = 1.f;
+    auto lin = [&](int ti, int ld, int col0a, int col0b, int out_valid, int out_pad, int out_seg, int k_valid, int k_pad, int k_seg,
+                   bool with_bias, int bias_n, int gain_col0 = 0, int gain_cols = 0) {
+        PackHmJob j{};
+        j.W = T[ti]; j.ld = ld; j.bias = with_bias ? T[ti + 1] : nullptr; j.bias_n = bias_n;
+        j.out_valid = out_valid; j.out_pad = out_pad; j.out_seg = out_seg;
+        j.k_valid = k_valid; j.k_pad = k_pad; j.k_seg = k_seg; j.col0[0] = col0a; j.col0[1] = col0b;
+        j.pred = prev; j.in_rms = head_rms; j.gain_col0 = gain_col0; j.gain_cols = gain_cols;
+        j.dst = m->packed_hm + z.hm;
+        z.hm += hm_lin_floats(out_pad, k_pad);
+        prev = (int)jobs.size();
+        jobs.push_back(j);
+    };
+    auto head = [&](float rms) { prev = -1; head_rms = rms; };
+    auto hh = [&](int ti) { lin(ti, Hv, 0, 0, Hv, H, H, Hv, H, H, true, Hv); };
+    // Linears 1 .. NL of an MLP that ends in a LayerNorm (the decoder's are queued one by one): the last one is packed centred
+    auto hidden = [&](const MlpSpec& p) {
+        for (int l = 1; l <= NL; ++l) hh(p.base + 2 * l);
+        jobs.back().center = 1;
+    };
+    auto proj = [&](int k) {   // P = h [W_i | W_j]^T + [b1 | 0] of processor step k: a chain of its own (input h)
+        head(1.f);
+        lin(m->edge_mlp(k).base, 3 * Hv, m->ci * Hv, m->cj * Hv, Hv, 2 * H, H, Hv, H, H, true, Hv);
+    };
+    m->hm_enc_edge = z.hm;
+    head(kHmRawInputRms);   // raw edge features: per-row power-of-two scale in the kernel
+    lin(enc_edge.base, enc_edge.in, 0, 0, Hv, H, H, enc_edge.in, 16, 16, true, Hv);
+    hidden(enc_edge);
+    m->hm_enc_node = z.hm;
+    head(kHmRawInputRms);
+    lin(enc_node.base, enc_node.in, 0, 0, Hv, H, H, enc_node.in, 32, 32, true, Hv);
+    hidden(enc_node);
+    m->hm_enc_node_tail = z.hm;
+    proj(0);
+    for (int k = 0; k < M; ++k) {
+        const MlpSpec &e = m->edge_mlp(k), &n = m->node_mlp(k);
+        m->hm_edge[k] = z.hm;
+        head(1.f);
+        // the e block; b1 lives in P_i.  Its pre-activation also takes h_i and h_j: the gain is that of the whole [H x 3H] Linear
+        lin(e.base, 3 * Hv, m->ce * Hv, 0, Hv, H, H, Hv, H, H, false, 0, 0, 3 * Hv);
+        hidden(e);
+        m->hm_node[k] = z.hm;
+        head(1.f);
+        lin(n.base, 2 * Hv, m->ch * Hv, m->ca * Hv, Hv, H, H, Hv, 2 * H, H, true, Hv);
+        hidden(n);
+        m->hm_node_tail[k] = z.hm;
+        if (k + 1 < M) proj(k + 1);
+        else {
+            head(1.f);
+            for (int l = 0; l < NL; ++l) hh(dec.base + 2 * l);
+            lin(dec.base + 2 * NL, Hv, 0, 0, dec.out, 32, 32, Hv, H, H, true, dec.out);
+        }
+    }
+    for (int k = 0; k < M; ++k) {   // Q = h W_h^T + b1 of node step k (systolic node path): a chain of its own, input h
+        m->hm_node_q[k] = z.hm;
+        head(1.f);
+        lin(m->node_mlp(k).base, 2 * Hv, m->ch * Hv, 0, Hv, H, H, Hv, H, H, true, Hv);
+    }
+
+    // fp16 hi / lo images of the systolic kernels (hidden 128, num_layers 2): the M processor edge MLPs, the edge encoder, then
+    // the node MLPs (the agg block of Linear 1, whose h block is Q; Linear 2; Linear 3)
+    m->h3_jobs.clear();
+    if (Hv == 128 && NL == 2) {
+        auto h3 = [&](size_t& slot, const MlpSpec& p, int W1_col0, int W1_ld, int enc_k1) {
+            const float* const* W = &T[p.base];   // W_0, b_0, W_1, b_1, W_2, b_2, gamma, beta
+            PackH3Job j{};
+            j.W1 = W[0]; j.b1 = W[1]; j.W2 = W[2]; j.b2 = W[3]; j.W3 = W[4]; j.b3 = W[5]; j.gamma = W[6]; j.beta = W[7];
+            j.W1_col0 = W1_col0; j.W1_ld = W1_ld; j.enc_k1 = enc_k1; j.dst = m->packed_h3 + z.h3;
+            m->h3_jobs.push_back(j);
+            slot = z.h3;
+            z.h3 += h3_image_floats();
+        };
+        for (int k = 0; k < M; ++k) h3(m->h3_edge[k], m->edge_mlp(k), m->ce * H, 0, 0);
+        h3(m->h3_enc, enc_edge, 0, 0, enc_edge.in);
+        for (int k = 0; k < M; ++k) h3(m->h3_node[k], m->node_mlp(k), m->ca * H, 2 * H, 0);
+    }
+    return z;
+}
+
+// Runs the jobs a batch (Batch::job) at a time, in order
+template <class Batch, class Job>
+int launch_batches(const std::vector<Job>& jobs, int (*launch)(const Batch&, float*, hipStream_t), float* base, hipStream_t s) {
+    Batch b;
+    const size_t cap = sizeof(b.job) / sizeof(b.job[0]);
+    for (size_t i = 0; i < jobs.size(); i += cap) {
+        b.n = (int)std::min(cap, jobs.size() - i);
+        std::copy_n(jobs.begin() + i, b.n, b.job);
+        const int rc = launch(b, base, s);
         if (rc != GM_OK) return rc;
     }
-    }   // kPackCommon
-    if (!(what & kPackInference)) return rc;
-    if (m->packed_h3 && rc == GM_OK) {  // fp16 hi / lo images of the systolic kernels: the M processor edge MLPs, then the edge encoder
-        std::vector<PackH3Job> jobs((size_t)M + 1);
-        for (int k = 0; k <= M; ++k) {
-            PackH3Job& j = jobs[(size_t)k];
-            const bool encj = k == M;
-            const int b = encj ? b_enc_edge : b_edge(k);
-            j.W1 = T[b]; j.W1_col0 = encj ? 0 : m->ce * H; j.W2 = T[b + 2]; j.W3 = T[b + 4];
-            j.b1 = T[b + 1]; j.b2 = T[b + 3]; j.b3 = T[b + 5];
-            j.gamma = T[b + 6]; j.beta = T[b + 7];
-            j.enc_k1 = encj ? m->d.edge_dim : 0;
-            j.dst = m->packed_h3 + (size_t)k * h3_image_floats();
-        }
-        rc = pack_h3(jobs.data(), m->d.edge_dim <= 16 ? M + 1 : M, s);
-        std::vector<PackH3Job> nj((size_t)M);
-        for (int k = 0; k < M; ++k) {   // node MLPs: the agg block of Linear 1 (its h block is Q), Linear 2, Linear 3
-            PackH3Job& j = nj[(size_t)k];
-            const int b = b_node(k);
-            j.W1 = T[b]; j.W1_col0 = m->ca * H; j.W1_ld = 2 * H; j.W2 = T[b + 2]; j.W3 = T[b + 4];
-            j.b1 = T[b + 1]; j.b2 = T[b + 3]; j.b3 = T[b + 5];
-            j.gamma = T[b + 6]; j.beta = T[b + 7];
-            j.enc_k1 = 0;
-            j.dst = m->packed_h3 + (size_t)(M + 1 + k) * h3_image_floats();
-        }
-        if (rc == GM_OK) rc = pack_h3(nj.data(), M, s);
-    }
+    return GM_OK;
+}
+
+// vec and the training streams: every load packs them from the raw copy
+int pack_common(const gm_model* m, hipStream_t s) {
+    int rc = launch_batches(m->vec_jobs, launch_vec_batch, m->vec, s);
+    if (rc == GM_OK && m->packed_t3) rc = launch_batches(m->t_jobs, launch_pack_b3_batch, m->packed_t3, s);
+    return rc;
+}
+
+// packed_hm and packed_h3: the first inference call after a load packs them (ensure_inference_images)
+int pack_inference(const gm_model* m, hipStream_t s) {
+    int rc = pack_hm(m->hm_jobs.data(), (int)m->hm_jobs.size(), m->hm_jobs_dev, m->hm_stats, s);
+    if (rc != GM_OK || !m->packed_h3) return rc;
+    const int n_edge = m->M + 1;   // the edge images (the steps', the encoder's), then the node images
+    rc = pack_h3(m->h3_jobs.data(), n_edge, s);
+    if (rc == GM_OK) rc = pack_h3(m->h3_jobs.data() + n_edge, m->M, s);
     return rc;
 }
 
@@ -263,30 +277,18 @@ int mark_ready(gm_model* m, hipStream_t s) {
 // The raw tensors are first copied into the model's own device buffer (host- or device-resident callers alike), then the cheap
 // images are packed from that copy; the inference images follow on first use (ensure_inference_images).
 int load_weights(gm_model* m, const float* const* T, int nt, bool on_device, hipStream_t s) {
-    GM_REQUIRE(nt == gm_model_num_tensors(&m->d), GM_ERR_INVALID_ARGUMENT, "model: expected %d tensors, got %d",
-               gm_model_num_tensors(&m->d), nt);
+    GM_REQUIRE(nt == (int)m->raw_jobs.size(), GM_ERR_INVALID_ARGUMENT, "model: expected %zu tensors, got %d", m->raw_jobs.size(), nt);
     for (int i = 0; i < nt; ++i) GM_REQUIRE(T[i] != nullptr, GM_ERR_INVALID_ARGUMENT, "model: tensor %d is null", i);
     std::lock_guard<std::mutex> guard(m->lazy_mu);
-    if (!m->raw) {
-        m->raw_off.resize((size_t)nt);
-        size_t total = 0;
-        for (int i = 0; i < nt; ++i) { m->raw_off[(size_t)i] = total; total += (tensor_floats(m, i) + 3) & ~(size_t)3; }
-        m->raw_floats = total;
-        GM_HIP_CHECK(hipMalloc(&m->raw, total * sizeof(float)));
-    }
     int rc = GM_OK;
     if (on_device) {
-        VecJobs vj;
-        vj.n = 0;
-        for (int i = 0; i < nt && rc == GM_OK; ++i) {
-            if (vj.n == kVecJobsMax) { rc = launch_vec_batch(vj, m->raw, s); vj.n = 0; }
-            VecJob& j = vj.job[vj.n++];
-            j.src = T[i]; j.dst_off = m->raw_off[(size_t)i]; j.count = (int)tensor_floats(m, i); j.zero_to = 0;
-        }
-        if (rc == GM_OK && vj.n > 0) rc = launch_vec_batch(vj, m->raw, s);
+        std::vector<VecJob> jobs = m->raw_jobs;
+        for (int i = 0; i < nt; ++i) jobs[(size_t)i].src = T[i];
+        rc = launch_batches(jobs, launch_vec_batch, m->raw, s);
     } else {
         for (int i = 0; i < nt && rc == GM_OK; ++i) {
-            if (hipMemcpyAsync(m->raw + m->raw_off[(size_t)i], T[i], tensor_floats(m, i) * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess) {
+            const VecJob& j = m->raw_jobs[(size_t)i];
+            if (hipMemcpyAsync(m->raw + j.dst_off, T[i], (size_t)j.count * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess) {
                 gm::set_error("model: copy of tensor %d to the device failed", i);
                 rc = GM_ERR_HIP;
             }
@@ -294,10 +296,8 @@ int load_weights(gm_model* m, const float* const* T, int nt, bool on_device, hip
         if (rc == GM_OK) (void)hipStreamSynchronize(s);   // the caller's host buffers may go away when this returns
     }
     if (rc != GM_OK) return rc;
-    std::vector<const float*> D((size_t)nt);
-    for (int i = 0; i < nt; ++i) D[(size_t)i] = m->raw + m->raw_off[(size_t)i];
     m->infer_stale = true;
-    rc = load_weights_device(m, D.data(), s, kPackCommon);
+    rc = pack_common(m, s);
     if (rc == GM_OK) rc = mark_ready(m, s);
     return rc;
 }
@@ -310,11 +310,7 @@ int ensure_inference_images(const gm_model* cm, hipStream_t s) {
     // the copy / common pack (and an earlier inference pack) may have been queued on another stream: this one waits for them
     if (m->ready && s != m->ready_stream) GM_HIP_CHECK(hipStreamWaitEvent(s, m->ready, 0));
     if (!m->infer_stale) return GM_OK;
-    GM_REQUIRE(m->raw, GM_ERR_INVALID_ARGUMENT, "model: no weights loaded");
-    const size_t nt = m->raw_off.size();
-    std::vector<const float*> D(nt);
-    for (size_t i = 0; i < nt; ++i) D[i] = m->raw + m->raw_off[i];
-    int rc = load_weights_device(m, D.data(), s, kPackInference);
+    int rc = pack_inference(m, s);
     if (rc == GM_OK) rc = mark_ready(m, s);   // the images are complete once THIS lands: other streams wait for it
     if (rc == GM_OK) m->infer_stale = false;
     return rc;
@@ -333,7 +329,7 @@ int gm_padded_hidden_size(int hidden_size) { return hm_padded_hidden(hidden_size
 
 int gm_model_num_tensors(const gm_model_desc* d) {
     if (!d) return 0;
-    return (2 + 2 * d->m_steps) * tensors_per_normed_mlp(d->num_layers) + 2 * (d->num_layers + 1);
+    return gm::model_mlps(*d).back().end;
 }
 
 int gm_model_create(const gm_model_desc* desc, const float* const* tensors, int n_tensors, int on_device, void* stream,
@@ -345,77 +341,20 @@ int gm_model_create(const gm_model_desc* desc, const float* const* tensors, int 
     gm_model* m = new gm_model();
     m->d = *desc;
     m->H = desc->hidden_size;
-    const int H = m->Hp = hm_padded_hidden(desc->hidden_size);   // width the kernels run at (buffers, images); m->H: the model's
-    const int NL = m->NL = desc->num_layers, M = m->M = desc->m_steps;
+    m->Hp = hm_padded_hidden(desc->hidden_size);   // width the kernels run at (buffers, images); m->H: the model's
+    m->NL = desc->num_layers; m->M = desc->m_steps;
     if (desc->col_i || desc->col_j || desc->col_e) { m->ci = desc->col_i; m->cj = desc->col_j; m->ce = desc->col_e; }
     if (desc->node_agg_first) { m->ch = 1; m->ca = 0; }
-    m->has_train_streams = m->H == 64 || m->H == 128 || m->H == 256;   // widths the training kernels (and their bf16 x 3 streams) exist for
-    {   // bf16 x 3 streams of the training kernels, one MLP after the other (stages)
-        const size_t T_HH = layer_stages_b3(H, H);
-        size_t t = 0;
-        m->t_enc_edge = t * kStageFloatsB3; t += layer_stages_b3(desc->edge_dim, H) + NL * T_HH;
-        m->t_enc_node = t * kStageFloatsB3; t += layer_stages_b3(desc->node_dim, H) + NL * T_HH;
-        m->t_proj.resize(M);
-        m->t_edge.resize(M);
-        m->t_node.resize(M);
-        for (int k = 0; k < M; ++k) {   // the [W_i | W_j] images of step k follow the node MLP before it
-            m->t_proj[k] = t * kStageFloatsB3; t += 2 * T_HH;
-            m->t_edge[k] = t * kStageFloatsB3; t += (NL + 1) * T_HH;
-            m->t_node[k] = t * kStageFloatsB3; t += (NL + 2) * T_HH;
-        }
-        m->t_dec = t * kStageFloatsB3; t += NL * T_HH + layer_stages_b3(H, desc->out_dim);
-        m->packed_t3_floats = t * kStageFloatsB3;
-    }
-    size_t v = 0;
-    const size_t VM = (size_t)(NL + 3) * H;
-    m->v_enc_edge = v; v += VM;
-    m->v_enc_node = v; v += VM;
-    m->v_edge.resize(M);
-    m->v_node.resize(M);
-    for (int k = 0; k < M; ++k) {
-        m->v_edge[k] = v; v += VM;
-        m->v_node[k] = v; v += VM;
-    }
-    m->v_dec = v; v += (size_t)NL * H + 32;
-    m->vec_floats = v;
-    {   // fp16 hi / lo images (hmlp.h): every MLP, any supported size
-        const size_t hh = hm_lin_floats(H, H), pj = hm_lin_floats(2 * H, H);
-        size_t o = 0;
-        m->hm_enc_edge = o; o += hm_lin_floats(H, 16) + NL * hh;
-        m->hm_enc_node = o; o += hm_lin_floats(H, 32) + NL * hh;
-        m->hm_enc_node_tail = o; o += pj;
-        m->hm_edge.resize(M);
-        m->hm_node.resize(M);
-        m->hm_node_tail.resize(M);
-        for (int k = 0; k < M; ++k) {
-            m->hm_edge[k] = o; o += (NL + 1) * hh;
-            m->hm_node[k] = o; o += hm_lin_floats(H, 2 * H) + NL * hh;
-            m->hm_node_tail[k] = o; o += k + 1 < M ? pj : NL * hh + hm_lin_floats(32, H);
-        }
-        m->hm_node_q.resize(M);
-        for (int k = 0; k < M; ++k) { m->hm_node_q[k] = o; o += hh; }
-        m->hm_floats = o;
-        m->hm_jobs_cap = (size_t)(2 + 2 * M) * (NL + 1) + 2 * M + NL + 1 + 4;
-        if (hipMalloc(&m->packed_hm, m->hm_floats * sizeof(float)) != hipSuccess ||
-            hipMalloc(&m->hm_jobs_dev, m->hm_jobs_cap * sizeof(PackHmJob)) != hipSuccess ||
-            hipMalloc(&m->hm_stats, m->hm_jobs_cap * 4 * sizeof(float)) != hipSuccess) {
-            gm::set_error("gm_model_create: hipMalloc failed");
-            gm_model_destroy(m);
-            return GM_ERR_HIP;
-        }
-    }
-    if (m->H == 128 && NL == 2 && hipMalloc(&m->packed_h3, (size_t)(2 * M + 1) * h3_image_floats() * sizeof(float)) != hipSuccess) {
+    m->mlp = model_mlps(*desc);
+    const WeightSizes z = plan_weights(m);
+    auto alloc = [](auto** p, size_t count) { return count == 0 || hipMalloc(p, count * sizeof(**p)) == hipSuccess; };
+    if (!alloc(&m->raw, z.raw) || !alloc(&m->vec, z.vec) || !alloc(&m->packed_t3, z.t3) || !alloc(&m->packed_hm, z.hm) ||
+        !alloc(&m->packed_h3, z.h3) || !alloc(&m->hm_jobs_dev, m->hm_jobs.size()) || !alloc(&m->hm_stats, 4 * m->hm_jobs.size())) {
         gm::set_error("gm_model_create: hipMalloc failed");
         gm_model_destroy(m);
         return GM_ERR_HIP;
     }
-    m->edge_kernel = EK_AUTO;   // gm_model_set_edge_kernel changes it per handle (no process-wide switch)
-    if ((m->has_train_streams && hipMalloc(&m->packed_t3, m->packed_t3_floats * sizeof(float)) != hipSuccess) ||
-        hipMalloc(&m->vec, m->vec_floats * sizeof(float)) != hipSuccess) {
-        gm::set_error("gm_model_create: hipMalloc failed");
-        gm_model_destroy(m);
-        return GM_ERR_HIP;
-    }
+    plan_weights(m);   // now with the buffers: the job lists point into them
     rc = load_weights(m, tensors, n_tensors, on_device != 0, (hipStream_t)stream);
     if (rc != GM_OK) {
         gm_model_destroy(m);
@@ -433,13 +372,8 @@ int gm_model_update(gm_model* m, const float* const* tensors, int n_tensors, int
 
 void gm_model_destroy(gm_model* m) {
     if (!m) return;
-    if (m->packed_t3) hipFree(m->packed_t3);
-    if (m->packed_h3) hipFree(m->packed_h3);
-    if (m->packed_hm) hipFree(m->packed_hm);
-    if (m->hm_jobs_dev) hipFree(m->hm_jobs_dev);
-    if (m->hm_stats) hipFree(m->hm_stats);
-    if (m->vec) hipFree(m->vec);
-    if (m->raw) hipFree(m->raw);
+    for (void* p : std::initializer_list<void*>{m->raw, m->vec, m->packed_t3, m->packed_hm, m->packed_h3, m->hm_jobs_dev, m->hm_stats})
+        (void)hipFree(p);
     if (m->ready) (void)hipEventDestroy(m->ready);
     delete m->prof;
     delete m;
@@ -492,7 +426,7 @@ EdgeArgs enc_edge_args(const gm_model* m, const float* edge_attr, const int* eid
     a.hdr = hdr; a.n_edges_host = e_host; a.eid = eid;
     a.e_in = edge_attr; a.e_out = e_out; a.k1 = m->d.edge_dim;
     a.wstream_hm = m->packed_hm + m->hm_enc_edge;
-    a.wstream_h3 = m->packed_h3 ? m->packed_h3 + (size_t)m->M * h3_image_floats() : nullptr;   // the encoder's image follows the steps'
+    a.wstream_h3 = m->packed_h3 ? m->packed_h3 + m->h3_enc : nullptr;
     a.prof = m->prof;
     set_ln(m, a, m->v_enc_edge);
     a.h_valid = m->H;
@@ -504,7 +438,7 @@ EdgeArgs proc_edge_args(const gm_model* m, int k, const CsrWs& c, int64_t n, con
     a.hdr = c.hdr; a.dst = c.dst; a.src = c.src; a.eid = eid; a.eid_out = eid;
     a.P = P; a.e_in = e_in; a.e_out = e_out; a.agg = agg; a.side = side; a.residual = residual;
     a.wstream_hm = m->packed_hm + m->hm_edge[k];
-    a.wstream_h3 = m->packed_h3 ? m->packed_h3 + (size_t)k * h3_image_floats() : nullptr;
+    a.wstream_h3 = m->packed_h3 ? m->packed_h3 + m->h3_edge[k] : nullptr;
     a.edge_blocks = c.blocks;
     a.n_nodes_tab = n;
     a.prof = m->prof;
@@ -544,7 +478,7 @@ void set_tail(const gm_model* m, HmNodeArgs& a, int next, float* P, float* out, 
     if (next < m->M) {
         a.tail = 1;
         a.P_out = P;
-        a.p_scale = p_scaled ? edge_sys_p_scale(m->packed_h3 + (size_t)next * h3_image_floats()) : nullptr;
+        a.p_scale = p_scaled ? edge_sys_p_scale(m->packed_h3 + m->h3_edge[next]) : nullptr;
     } else {
         a.tail = 2;
         a.dec_out = out;
@@ -589,14 +523,13 @@ int epd_forward_impl(const gm_model* m, const float* nodes, int64_t n, const flo
     }
     // The systolic node path (hedge.h) takes the h half of its node MLP's first Linear as Q, written with P by the projection kernel
     // behind every step.
-    const size_t h3f = h3_image_floats();
     auto project = [&](int k) {   // h -> P of edge step k, Q of node step k
         ProjSysArgs pa{};
         pa.h = f.h; pa.P = f.P; pa.Q = f.Q; pa.n = (int)n; pa.flags = flags; pa.prof = m->prof;
         pa.img_p = m->packed_hm + (k == 0 ? m->hm_enc_node_tail : m->hm_node_tail[k - 1]);
         pa.img_q = m->packed_hm + m->hm_node_q[k];
-        pa.scale_p = edge_sys_p_scale(m->packed_h3 + (size_t)k * h3f);
-        pa.scale_q = edge_sys_p_scale(m->packed_h3 + (size_t)(M + 1 + k) * h3f);
+        pa.scale_p = edge_sys_p_scale(m->packed_h3 + m->h3_edge[k]);
+        pa.scale_q = edge_sys_p_scale(m->packed_h3 + m->h3_node[k]);
         return launch_proj_sys(pa, s);
     };
     {
@@ -621,7 +554,7 @@ int epd_forward_impl(const gm_model* m, const float* nodes, int64_t n, const flo
             // head partials of the scatter-add into agg, the node MLP (h in place), then the next step's projections -- or the decoder
             rc = launch_agg_stitch(f.agg, f.side, carve_edge_blocks(c.blocks, n, cap), n, m->prof, s);
             NodeSysArgs ns{};
-            ns.h = f.h; ns.agg = f.agg; ns.Q = f.Q; ns.h_out = f.h; ns.image = m->packed_h3 + (size_t)(M + 1 + k) * h3f;
+            ns.h = f.h; ns.agg = f.agg; ns.Q = f.Q; ns.h_out = f.h; ns.image = m->packed_h3 + m->h3_node[k];
             ns.n = (int)n; ns.flags = flags; ns.eps = m->d.ln_eps; ns.prof = m->prof;
             if (rc == GM_OK) rc = launch_node_sys(ns, s);
             if (rc == GM_OK && k + 1 < M) rc = project(k + 1);

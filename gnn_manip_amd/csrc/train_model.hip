@@ -12,11 +12,6 @@ using namespace gm;
 
 namespace {
 
-// first state_dict tensor of an MLP (epd_gnn.py:63-84): edge encoder 0, node encoder PM, step k's edge and node MLPs, decoder
-int base_edge(const gm_model* m, int k) { return (2 + 2 * k) * tensors_per_normed_mlp(m->NL); }
-int base_node(const gm_model* m, int k) { return (3 + 2 * k) * tensors_per_normed_mlp(m->NL); }
-int base_dec(const gm_model* m) { return base_edge(m, m->M); }
-
 // The destination-sorted edges (aggregation index i = edge_index[1]) and the source-grouped view of the sorted list.  It starts
 // every tape that has one: epd_gnn.py (_HeaderWatch) reads the edge_index verdict from the destination sort's header at byte 0.
 struct TrainCsr {
@@ -200,8 +195,8 @@ struct PackBwd {
     // the hidden Linears NL + 1 .. 2 of the MLP whose first tensor is `base`
     void hidden(int base, size_t& off) { for (int l = m->NL; l >= 1; --l) job(T[base + 2 * l], m->H, m->H, 0, m->H, off); }
     void ij(int k, size_t& off) {   // W_i, W_j: the column blocks of step k's first edge Linear that multiply h_i, h_j
-        job(T[base_edge(m, k)], m->H, 3 * m->H, m->ci * m->H, m->H, off);
-        job(T[base_edge(m, k)], m->H, 3 * m->H, m->cj * m->H, m->H, off);
+        job(T[m->edge_mlp(k).base], m->H, 3 * m->H, m->ci * m->H, m->H, off);
+        job(T[m->edge_mlp(k).base], m->H, 3 * m->H, m->cj * m->H, m->H, off);
     }
     // input: W_1^T as well, for the gradient w.r.t. the raw features (block API)
     void enc(int base, size_t off, int k1, bool input) {
@@ -209,26 +204,26 @@ struct PackBwd {
         if (input) job(T[base], m->H, k1, 0, k1, off);
     }
     void dec() {
-        const int H = m->H, bd = base_dec(m);
+        const int H = m->H, bd = m->mlp.back().base;
         size_t off = b.off_dec;
         job(T[bd + 2 * m->NL], m->d.out_dim, H, 0, H, off);
         for (int l = m->NL - 1; l >= 0; --l) job(T[bd + 2 * l], H, H, 0, H, off);
     }
     void edge(int k, int j) {
         size_t off = b.off_edge[j];
-        hidden(base_edge(m, k), off);
-        job(T[base_edge(m, k)], m->H, 3 * m->H, m->ce * m->H, m->H, off);
+        hidden(m->edge_mlp(k).base, off);
+        job(T[m->edge_mlp(k).base], m->H, 3 * m->H, m->ce * m->H, m->H, off);
     }
     void node(int k, int j) {
         size_t off = b.off_node[j];
         if (j + 1 < (int)b.off_node.size()) ij(k + 1, off);   // a step with a next one: its chain also takes that step's Gi / Gj
-        hidden(base_node(m, k), off);
-        job(T[base_node(m, k)], m->H, 2 * m->H, m->ch * m->H, m->H, off);
-        job(T[base_node(m, k)], m->H, 2 * m->H, m->ca * m->H, m->H, off);
+        hidden(m->node_mlp(k).base, off);
+        job(T[m->node_mlp(k).base], m->H, 2 * m->H, m->ch * m->H, m->H, off);
+        job(T[m->node_mlp(k).base], m->H, 2 * m->H, m->ca * m->H, m->H, off);
     }
     void proj(int k) { size_t off = b.off_proj; ij(k, off); }
-    void enc_node(bool input) { enc(tensors_per_normed_mlp(m->NL), b.off_enc_node, m->d.node_dim, input); }
-    void enc_edge(bool input) { enc(0, b.off_enc_edge, m->d.edge_dim, input); }
+    void enc_node(bool input) { enc(m->mlp[1].base, b.off_enc_node, m->d.node_dim, input); }
+    void enc_edge(bool input) { enc(m->mlp[0].base, b.off_enc_edge, m->d.edge_dim, input); }
 };
 
 // The launches of one backward call after its images are packed.  Every call does nothing once rc holds an error.
@@ -306,7 +301,7 @@ unsigned small_grid(size_t count) {
 
 // The checks every training entry point starts with, before any device call.
 int check_model(const gm_model* m, int64_t n, int64_t e, const char* who) {
-    GM_REQUIRE(!m || m->has_train_streams, GM_ERR_UNSUPPORTED, "%s: the training kernels are instantiated for hidden_size 64 / 128 / 256", who);
+    GM_REQUIRE(!m || m->packed_t3, GM_ERR_UNSUPPORTED, "%s: the training kernels are instantiated for hidden_size 64 / 128 / 256", who);
     GM_REQUIRE(m, GM_ERR_INVALID_ARGUMENT, "%s: null model", who);
     GM_REQUIRE(n >= 1 && e >= 0 && n < ((int64_t)1 << 31) && e < ((int64_t)1 << 31) / m->H, GM_ERR_INVALID_ARGUMENT,
                "%s: sizes out of range (n=%lld, e=%lld)", who, (long long)n, (long long)e);
@@ -431,7 +426,7 @@ int gm_epd_backward(const gm_model* m, const float* const* T, int n_tensors, con
     if (rc != GM_OK) return rc;
     gm::DevGuard dev_guard(nodes);
     hipStream_t s = (hipStream_t)stream;
-    const int H = m->H, NL = m->NL, M = m->M, OD = m->d.out_dim, PM = tensors_per_normed_mlp(NL);
+    const int H = m->H, NL = m->NL, M = m->M, OD = m->d.out_dim;
     Tape t = carve_tape(tape, &m->d, n, e);
     BwdWs b = carve_bwd(ws, &m->d, n, e);
     rc = ready_to_launch(m, tape_bytes, t.bytes, ws_bytes, b.bytes, s, __func__);
@@ -460,7 +455,7 @@ int gm_epd_backward(const gm_model* m, const float* const* T, int n_tensors, con
     }
     // ---- decoder
     {
-        const int bd = base_dec(m);
+        const int bd = m->mlp.back().base;
         TrainBwdArgs a{};
         a.rows = (int)n; a.dY = b.go; a.out_dim = OD; a.tape = t.dec; a.wstream = b.packT + b.off_dec;
         a.dz = b.dz; a.dz_stride = b.dz_stride; a.nl = NL; a.dx = b.dh;
@@ -472,7 +467,7 @@ int gm_epd_backward(const gm_model* m, const float* const* T, int n_tensors, con
     // ---- processor blocks, last to first
     for (int k = M - 1; k >= 0; --k) {
         const bool has_next = k + 1 < M;
-        const int be = base_edge(m, k), bn = base_node(m, k);
+        const int be = m->edge_mlp(k).base, bn = m->node_mlp(k).base;
         {
             TrainBwdArgs a{};
             a.rows = (int)n; a.dY = b.dh; a.Gi = has_next ? b.Gi : nullptr; a.Gj = has_next ? b.Gj : nullptr; a.tape = t.step[k].tn;
@@ -495,14 +490,16 @@ int gm_epd_backward(const gm_model* m, const float* const* T, int n_tensors, con
     {
         TrainBwdArgs a{};
         a.rows = (int)n; a.dY = b.dh; a.Gi = b.Gi; a.Gj = b.Gj; a.tape = t.enc.en; a.wstream = b.packT + b.off_proj;
-        bw.chain(TB_ENC, a, PM, m->v_enc_node, true);   // as the node MLPs
-        bw.wgrad(b.dznl(1), H, H, nodes, m->d.node_dim, m->d.node_dim, nullptr, n, grads[PM], m->d.node_dim, 0, grads[PM + 1]);
+        const int bn = m->mlp[1].base;
+        bw.chain(TB_ENC, a, bn, m->v_enc_node, true);   // as the node MLPs
+        bw.wgrad(b.dznl(1), H, H, nodes, m->d.node_dim, m->d.node_dim, nullptr, n, grads[bn], m->d.node_dim, 0, grads[bn + 1]);
     }
     if (e > 0) {
         TrainBwdArgs a{};
         a.rows = (int)e; a.dY = b.de; a.tape = t.enc.ee; a.wstream = b.packT + b.off_enc_edge;
-        bw.chain(TB_ENC, a, 0, m->v_enc_edge, false);
-        bw.wgrad(b.dzl(1), H, H, edge_attr, m->d.edge_dim, m->d.edge_dim, c.eid, e, grads[0], m->d.edge_dim, 0, grads[1]);
+        const int be = m->mlp[0].base;
+        bw.chain(TB_ENC, a, be, m->v_enc_edge, false);
+        bw.wgrad(b.dzl(1), H, H, edge_attr, m->d.edge_dim, m->d.edge_dim, c.eid, e, grads[be], m->d.edge_dim, 0, grads[be + 1]);
     }
     return bw.finish();
 }
@@ -540,8 +537,9 @@ int gm_graph_independent_backward(const gm_model* m, const float* const* T, int 
     int rc = check_model(m, n, e, __func__);
     if (rc != GM_OK) return rc;
     GM_REQUIRE(T && grads && x && dh && tape && ws && (e == 0 || (edge_attr && de)), GM_ERR_INVALID_ARGUMENT, "%s: null pointer", __func__);
-    const int H = m->H, NL = m->NL, PM = tensors_per_normed_mlp(NL);
-    rc = check_tensors(m, T, grads, n_tensors, 0, 2 * PM, __func__);
+    const int H = m->H, NL = m->NL;
+    const MlpSpec &ee = m->mlp[0], &en = m->mlp[1];
+    rc = check_tensors(m, T, grads, n_tensors, ee.base, en.end, __func__);
     if (rc != GM_OK) return rc;
     gm::DevGuard dev_guard(x ? (const void*)x : (const void*)edge_attr);
     hipStream_t s = (hipStream_t)stream;
@@ -562,8 +560,8 @@ int gm_graph_independent_backward(const gm_model* m, const float* const* T, int 
         bw.chain(TB_ENC, a, base, voff, false);
         bw.wgrad(b.dzl(1), H, H, X, k1, k1, nullptr, rows, grads[base], k1, 0, grads[base + 1]);
     };
-    run(PM, t.enc.en, n, dh, m->v_enc_node, b.off_enc_node, x, m->d.node_dim, dx);
-    run(0, t.enc.ee, e, de, m->v_enc_edge, b.off_enc_edge, edge_attr, m->d.edge_dim, dedge_attr);
+    run(en.base, t.enc.en, n, dh, m->v_enc_node, b.off_enc_node, x, m->d.node_dim, dx);
+    run(ee.base, t.enc.ee, e, de, m->v_enc_edge, b.off_enc_edge, edge_attr, m->d.edge_dim, dedge_attr);
     return bw.finish();
 }
 
@@ -597,8 +595,8 @@ int gm_interaction_network_backward(const gm_model* m, int k, const float* const
     GM_REQUIRE(k >= 0 && k < m->M, GM_ERR_INVALID_ARGUMENT, "%s: block %d out of range", __func__, k);
     GM_REQUIRE(T && grads && h && dh_out && dh_in && tape && ws && (e == 0 || (e_in && de_out && de_in)), GM_ERR_INVALID_ARGUMENT,
                "%s: null pointer", __func__);
-    const int H = m->H, be = base_edge(m, k), bn = base_node(m, k);
-    rc = check_tensors(m, T, grads, n_tensors, be, bn + tensors_per_normed_mlp(m->NL), __func__);
+    const int H = m->H, be = m->edge_mlp(k).base, bn = m->node_mlp(k).base;
+    rc = check_tensors(m, T, grads, n_tensors, be, m->node_mlp(k).end, __func__);
     if (rc != GM_OK) return rc;
     gm::DevGuard dev_guard(h);
     hipStream_t s = (hipStream_t)stream;
