@@ -10,6 +10,18 @@
 // No N x M matrix is ever stored: every softmin recomputes the distances it needs from the coordinates
 // ("online" reduction): 6 flops + one exp per pair, two passes (max, then sum) -- exp-throughput bound,
 // the clouds and potentials live in L2.
+//
+// Gradient (gm_sinkhorn_divergence_batched_backward): geomloss's convention for the tensorized backend, read from its published
+// code and -- like the forward -- UNPINNED against geomloss itself.  The potentials are detached and only the last
+// extrapolation is differentiated, with the right-hand cloud of every cost matrix detached (C_xy = cost(x, y.detach()),
+// C_xx = cost(x, x.detach()), ...).  With a_i = 1/N, b_j = 1/M, eps = blur^2 and o[k] the input of the last extrapolation:
+//     dS/dx_i = a_i (T_xx(x_i) - T_xy(x_i)),   T_xy(x_i) = sum_j softmax_j(log b_j + o[2]_j / eps - C(x_i, y_j) / eps) y_j
+//                                              T_xx(x_i) = sum_k softmax_k(log a_k + o[0]_k / eps - C(x_i, x_k) / eps) x_k
+//     dS/dy_j = b_j (T_yy(y_j) - T_yx(y_j))    (o[1] over y, o[3] over x)
+// The output q[k] of the last extrapolation is each row's log-normaliser, so one pass suffices (sinkhorn_grad_kernel): the
+// weights exp(h_j - C_ij / eps + q_i / eps) are near 1 without a running max, and dividing by their sum at the end makes the
+// result independent of the rounding of q_i.  Again no N x M matrix: one exp and ~14 flops per pair, the cross and the self
+// barycentre of a row in one launch.
 #include <math.h>
 #include <vector>
 #include "common.h"
@@ -186,9 +198,104 @@ __global__ void __launch_bounds__(256) sinkhorn_cost_kernel(const float* __restr
     if (tid == 0) loss[b] = plan[b].n_eps > 0 ? (float)red[0] : (plan[b].n_eps == 0 ? 0.f : NAN);
 }
 
+// Gradient of pair b = blockIdx.y on one row set P (R rows of weight 1/R) from the other cloud Q (S points) and from P itself:
+//   out[i] = grad[b] * ((1/R) * (D_c[i] / W_c[i] - D_s[i] / W_s[i])) = grad[b] * (1/R) * (T_s(p_i) - T_c(p_i))
+//   W[i] = sum_j w_ij,  D[i] = sum_j w_ij (p_i - q_j),  w_ij = exp(logw + f_j / eps - |p_i - q_j|^2 / (2 eps) + g_i / eps)
+// at the final eps = blur^2, with (f, g, logw) = (o[kfc], q[kgc], logw_c) over Q and (o[kfs], q[kgs], logw_s) over P, where
+// o = pot[*sel] is the input of the forward's last extrapolation and q = pot[*sel ^ 1] its output.  n_eps == 0: 0; n_eps < 0: NaN.
+struct SkGradPots {
+    const float* p[2][4];   // the forward's two ping-pong sets (SinkhornWs::pot)
+};
+
+// W and D of the wave's SK_RB rows over the S points of Q (lanes strided over Q; wave-reduced, every lane holds the sums)
+__device__ __forceinline__ void sk_grad_sums(const float* px, const float* py, const float* pz, const float* gn, const float* __restrict__ Q,
+                                             int S, const float* __restrict__ f, float logw, float inv_eps, float* W, float (*D)[3]) {
+    const float hc = 0.5f * inv_eps;
+#pragma unroll
+    for (int r = 0; r < SK_RB; ++r) W[r] = D[r][0] = D[r][1] = D[r][2] = 0.f;
+    for (int j = threadIdx.x & 63; j < S; j += 64) {
+        const float qx = Q[3 * j], qy = Q[3 * j + 1], qz = Q[3 * j + 2];
+        const float h = logw + f[j] * inv_eps;
+#pragma unroll
+        for (int r = 0; r < SK_RB; ++r) {
+            const float dx = px[r] - qx, dy = py[r] - qy, dz = pz[r] - qz;
+            const float w = __expf(h - (dx * dx + dy * dy + dz * dz) * hc + gn[r]);
+            W[r] += w;
+            D[r][0] += w * dx;
+            D[r][1] += w * dy;
+            D[r][2] += w * dz;
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < SK_RB; ++r)
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) {
+            W[r] += __shfl_xor(W[r], o, 64);
+            D[r][0] += __shfl_xor(D[r][0], o, 64);
+            D[r][1] += __shfl_xor(D[r][1], o, 64);
+            D[r][2] += __shfl_xor(D[r][2], o, 64);
+        }
+}
+
+__global__ void __launch_bounds__(256) sinkhorn_grad_kernel(const float* __restrict__ P_all, int R, size_t p_stride, float logw_s,
+                                                             const float* __restrict__ Q_all, int S, size_t q_stride, float logw_c,
+                                                             SkGradPots pots, const int* __restrict__ sel, int kfc, int kgc, int kfs, int kgs,
+                                                             const SkPlan* __restrict__ plan, float blur, float scaling,
+                                                             const float* __restrict__ grad, float* __restrict__ out_all, size_t out_stride) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int b = blockIdx.y;
+    const int r0 = (blockIdx.x * 4 + wave) * SK_RB;
+    if (r0 >= R) return;
+    const SkPlan pl = plan[b];
+    float* out = out_all + (size_t)b * out_stride;
+    if (pl.n_eps <= 0) {   // one point against itself (loss 0 by definition) or non-finite input (loss NaN)
+        if (lane < 3 * SK_RB && r0 + lane / 3 < R) out[3 * r0 + lane] = pl.n_eps == 0 ? 0.f : NAN;
+        return;
+    }
+    const int o = *sel, q = o ^ 1;
+    const float* P = P_all + (size_t)b * p_stride;
+    const float* Q = Q_all + (size_t)b * q_stride;
+    const float* fc = pots.p[o][kfc] + (size_t)b * S;
+    const float* fs = pots.p[o][kfs] + (size_t)b * R;
+    const float* gc = pots.p[q][kgc] + (size_t)b * R;
+    const float* gs = pots.p[q][kgs] + (size_t)b * R;
+    const float inv_eps = (float)(1.0 / sk_eps(pl, pl.n_eps - 1, (double)blur, (double)scaling));
+    float px[SK_RB], py[SK_RB], pz[SK_RB], gcn[SK_RB], gsn[SK_RB];
+#pragma unroll
+    for (int r = 0; r < SK_RB; ++r) {
+        const int rr = min(r0 + r, R - 1);
+        px[r] = P[3 * rr];
+        py[r] = P[3 * rr + 1];
+        pz[r] = P[3 * rr + 2];
+        gcn[r] = gc[rr] * inv_eps;
+        gsn[r] = gs[rr] * inv_eps;
+    }
+    float Wc[SK_RB], Dc[SK_RB][3], Ws[SK_RB], Ds[SK_RB][3];
+    sk_grad_sums(px, py, pz, gcn, Q, S, fc, logw_c, inv_eps, Wc, Dc);
+    sk_grad_sums(px, py, pz, gsn, P, R, fs, logw_s, inv_eps, Ws, Ds);
+    if (lane < 3 * SK_RB && r0 + lane / 3 < R) {
+        float v = 0.f;
+#pragma unroll
+        for (int r = 0; r < SK_RB; ++r)
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+                if (lane == 3 * r + c) v = Dc[r][c] / Wc[r] - Ds[r][c] / Ws[r];
+        out[3 * r0 + lane] = grad[b] * ((1.f / (float)R) * v);
+    }
+}
+
+// dy of a cloud shared by the batch: the per-pair gradients summed in pair order, in double (deterministic, no atomics)
+__global__ void __launch_bounds__(256) sinkhorn_grad_sum_kernel(const float* __restrict__ part, int B, size_t len, float* __restrict__ out) {
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= len) return;
+    double s = 0.0;
+    for (int b = 0; b < B; ++b) s += (double)part[(size_t)b * len + e];
+    out[e] = (float)s;
+}
+
 struct SinkhornWs {
     SkPlan* plan;       // [B]
-    int* max_eps;       // 2
+    int* max_eps;       // [0] longest schedule, [1] non-finite input, [2] which pot set is the input of the last extrapolation
     float* pot[2][4];   // ping-pong sets of (a_x[B][n], b_y[B][m], a_y[B][m], b_x[B][n])
     size_t bytes;
 };
@@ -252,6 +359,8 @@ int gm_sinkhorn_divergence_batched(const float* x, int64_t batch, int64_t n, con
         GM_REQUIRE(back[1] == 0, GM_ERR_DATA, "gm_sinkhorn_divergence: non-finite coordinate");
         n_eps = back[0];
     }
+    // the set the last extrapolation reads after n_eps swaps, for the backward (which then needs no host round trip)
+    GM_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)(w.max_eps + 2), n_eps & 1, 1, s));
     const float logwa = -logf((float)n), logwb = -logf((float)m);
     const dim3 gx((unsigned)cdiv(n, 4 * SK_RB), (unsigned)batch), gy((unsigned)cdiv(m, 4 * SK_RB), (unsigned)batch);
     const size_t xs = (size_t)n * 3;
@@ -287,6 +396,50 @@ int gm_sinkhorn_divergence_batched(const float* x, int64_t batch, int64_t n, con
     }
     float** p = w.pot[cur];
     hipLaunchKernelGGL(sinkhorn_cost_kernel, dim3((unsigned)batch), dim3(256), 0, s, p[0], p[3], (int)n, p[2], p[1], (int)m, w.plan, loss_device);
+    GM_LAUNCH_CHECK();
+    return GM_OK;
+}
+
+size_t gm_sinkhorn_batched_backward_workspace_bytes(int64_t batch, int64_t n, int64_t m, int y_shared) {
+    if (batch < 0 || n < 0 || m < 0) return 0;
+    Carver c(nullptr);
+    if (y_shared) c.take<float>((size_t)(batch * m * 3));   // per-pair dy, summed over the batch in a second launch
+    return c.used();
+}
+
+int gm_sinkhorn_divergence_batched_backward(const float* x, int64_t batch, int64_t n, const float* y, int64_t m, int y_shared, float blur,
+                                            float scaling, const float* grad_loss, float* dx, float* dy, const void* fwd_ws, size_t fwd_ws_bytes,
+                                            void* bwd_ws, size_t bwd_ws_bytes, void* stream) {
+    gm::DevGuard dev_guard(x);
+    GM_REQUIRE(x && y && grad_loss && fwd_ws, GM_ERR_INVALID_ARGUMENT, "gm_sinkhorn_divergence_batched_backward: null pointer");
+    GM_REQUIRE(batch >= 1 && batch < 65536, GM_ERR_INVALID_ARGUMENT, "gm_sinkhorn_divergence_batched_backward: batch %lld out of range (1 .. 65535)",
+               (long long)batch);
+    GM_REQUIRE(n >= 1 && m >= 1 && n < ((int64_t)1 << 30) && m < ((int64_t)1 << 30), GM_ERR_INVALID_ARGUMENT,
+               "gm_sinkhorn_divergence_batched_backward: cloud sizes out of range (%lld, %lld)", (long long)n, (long long)m);
+    GM_REQUIRE(blur > 0.f && scaling > 0.f && scaling < 1.f, GM_ERR_INVALID_ARGUMENT,
+               "gm_sinkhorn_divergence_batched_backward: need blur > 0 and 0 < scaling < 1");
+    SinkhornWs w = carve_sinkhorn(const_cast<void*>(fwd_ws), batch, n, m);
+    GM_REQUIRE(fwd_ws_bytes >= w.bytes, GM_ERR_WORKSPACE, "gm_sinkhorn_divergence_batched_backward: forward workspace %zu < %zu", fwd_ws_bytes, w.bytes);
+    const size_t need = gm_sinkhorn_batched_backward_workspace_bytes(batch, n, m, y_shared && dy);
+    GM_REQUIRE(need == 0 || (bwd_ws && bwd_ws_bytes >= need), GM_ERR_WORKSPACE, "gm_sinkhorn_divergence_batched_backward: workspace %zu < %zu",
+               bwd_ws ? bwd_ws_bytes : 0, need);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t xs = (size_t)n * 3, y_stride = y_shared ? 0 : (size_t)m * 3;
+    const float logwa = -logf((float)n), logwb = -logf((float)m);
+    SkGradPots pots;
+    for (int st = 0; st < 2; ++st)
+        for (int k = 0; k < 4; ++k) pots.p[st][k] = w.pot[st][k];
+    const int* sel = w.max_eps + 2;
+    if (dx)   // x rows: across y with (o[2] = a_y, q[3] = b_x), within x with (o[0], q[0]) = a_x
+        hipLaunchKernelGGL(sinkhorn_grad_kernel, dim3((unsigned)cdiv(n, 4 * SK_RB), (unsigned)batch), dim3(256), 0, s, x, (int)n, xs, logwa, y,
+                           (int)m, y_stride, logwb, pots, sel, 2, 3, 0, 0, w.plan, blur, scaling, grad_loss, dx, xs);
+    if (dy) {   // y rows: across x with (o[3] = b_x, q[2] = a_y), within y with (o[1], q[1]) = b_y
+        float* part = y_shared ? Carver(bwd_ws).take<float>((size_t)(batch * m * 3)) : dy;
+        hipLaunchKernelGGL(sinkhorn_grad_kernel, dim3((unsigned)cdiv(m, 4 * SK_RB), (unsigned)batch), dim3(256), 0, s, y, (int)m, y_stride, logwb,
+                           x, (int)n, xs, logwa, pots, sel, 3, 2, 1, 1, w.plan, blur, scaling, grad_loss, part, (size_t)m * 3);
+        if (y_shared)
+            hipLaunchKernelGGL(sinkhorn_grad_sum_kernel, dim3((unsigned)cdiv(m * 3, 256)), dim3(256), 0, s, part, (int)batch, (size_t)m * 3, dy);
+    }
     GM_LAUNCH_CHECK();
     return GM_OK;
 }

@@ -1,13 +1,60 @@
 """Planner loss on the device: the ``geomloss.SamplesLoss(loss="sinkhorn", p=2, blur=.05)`` the reference builds at
 gnn_manip/utils/traj_utils.py:69 and calls at :279.  geomloss is an un-vendored pip dependency of the reference
 (environment.yml:25, version not pinned): csrc/sinkhorn.hip restates its published algorithm; see the header there.
-"""
-import ctypes as C
 
+The loss is differentiable like geomloss's: ``loss(x, y).backward()`` fills ``x.grad`` / ``y.grad`` through HIP kernels
+(gm_sinkhorn_divergence_batched_backward).  The gradient follows geomloss's convention for its tensorized backend, read from
+its published code and -- like the forward -- unpinned against geomloss itself: the potentials are detached and only the last
+extrapolation at eps = blur^2 is differentiated, with the right-hand cloud of every cost matrix detached; dS/dx_i is
+(1/N) (T_xx(x_i) - T_xy(x_i)), the difference of the softmax barycentres of x_i over x and over y.  Double backward is not
+supported.
+"""
 import torch
+from torch.autograd.function import once_differentiable
 
 from ._lib import check, current_stream, lib, ptr
 from .graph import _need_cuda, _ws
+
+
+def _forward(loss, x, y, ws):
+    """Launch the batched divergence of x [B, N, 3] against y ([M, 3] or [B, M, 3]) with workspace ws -> [B] device tensor."""
+    out = torch.empty((x.shape[0],), dtype=torch.float32, device=x.device)
+    check(lib().gm_sinkhorn_divergence_batched(ptr(x), x.shape[0], x.shape[1], ptr(y), y.shape[-2], 1 if y.dim() == 2 else 0, loss.blur,
+                                               loss.scaling, loss.diameter, ptr(out), ptr(ws), ws.numel(), current_stream()))
+    return out
+
+
+class _SinkhornFunction(torch.autograd.Function):
+    """SamplesLoss.batched under autograd: the forward runs in a workspace of the call's own (the backward reads its plan and
+    potentials, which the next call would overwrite in the loss's shared one); the backward is
+    gm_sinkhorn_divergence_batched_backward."""
+
+    @staticmethod
+    def forward(ctx, loss, x, y):
+        ws = _ws(lib().gm_sinkhorn_batched_workspace_bytes(x.shape[0], x.shape[1], y.shape[-2]), x.device)
+        out = _forward(loss, x, y, ws)
+        ctx.loss, ctx.ws = loss, ws
+        ctx.save_for_backward(x, y)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_loss):
+        if ctx.ws is None:
+            raise RuntimeError("SamplesLoss: a call's backward runs once (its workspace is released after it)")
+        L = lib()
+        x, y = ctx.saved_tensors
+        bsz, n, m, shared = x.shape[0], x.shape[1], y.shape[-2], 1 if y.dim() == 2 else 0
+        need_x, need_y = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        dx = torch.empty_like(x) if need_x else None
+        dy = torch.empty_like(y) if need_y else None
+        grad_loss = grad_loss.contiguous().float()
+        ws = _ws(L.gm_sinkhorn_batched_backward_workspace_bytes(bsz, n, m, shared if need_y else 0), x.device)
+        check(L.gm_sinkhorn_divergence_batched_backward(ptr(x), bsz, n, ptr(y), m, shared, ctx.loss.blur, ctx.loss.scaling,
+                                                        ptr(grad_loss), ptr(dx), ptr(dy), ptr(ctx.ws), ctx.ws.numel(), ptr(ws),
+                                                        ws.numel(), current_stream()))
+        ctx.ws = None
+        return None, dx, dy
 
 
 class SamplesLoss:
@@ -17,7 +64,11 @@ class SamplesLoss:
     final clouds of a whole block of candidates, X [B, N, 3], against the desired cloud y [M, 3] (or one per candidate,
     [B, M, 3]) in ONE launch sequence and returns the B losses as a device tensor -- element b bit-equal to ``loss(X[b], y)``.
     ``diameter`` (geomloss keyword, default None = bounding box of each pair): given, no host synchronisation happens at all;
-    otherwise one per call (the launch count is the longest epsilon schedule of the batch)."""
+    otherwise one per call (the launch count is the longest epsilon schedule of the batch).
+
+    Both calls are differentiable with respect to x and y (see the module docstring for the convention); with y shared by the
+    batch, its gradient is the sum over the pairs.  Under grad (grad mode on and x or y requiring grad) a call runs in a
+    workspace of its own, kept until its backward; otherwise calls reuse one workspace per SamplesLoss, as the planner's do."""
 
     def __init__(self, loss="sinkhorn", p=2, blur=0.05, scaling=0.5, debias=True, diameter=None, **unsupported):
         if loss != "sinkhorn" or p != 2 or not debias or unsupported:
@@ -35,15 +86,12 @@ class SamplesLoss:
         y = y.contiguous().float()
         if x.dim() != 3 or x.shape[2] != 3 or y.shape[-1] != 3 or y.dim() not in (2, 3) or (y.dim() == 3 and y.shape[0] != x.shape[0]):
             raise ValueError("SamplesLoss.batched: point clouds must be [B, N, 3] and [M, 3] or [B, M, 3]")
-        bsz, n, m = x.shape[0], x.shape[1], y.shape[-2]
-        L = lib()
-        need = L.gm_sinkhorn_batched_workspace_bytes(bsz, n, m)
+        if torch.is_grad_enabled() and (x.requires_grad or y.requires_grad):
+            return _SinkhornFunction.apply(self, x, y)
+        need = lib().gm_sinkhorn_batched_workspace_bytes(x.shape[0], x.shape[1], y.shape[-2])
         if self._ws is None or self._ws.numel() < need or self._ws.device != x.device:
             self._ws = _ws(need, x.device)
-        out = torch.empty((bsz,), dtype=torch.float32, device=x.device)
-        check(L.gm_sinkhorn_divergence_batched(ptr(x), bsz, n, ptr(y), m, 1 if y.dim() == 2 else 0, self.blur, self.scaling,
-                                               self.diameter, ptr(out), ptr(self._ws), self._ws.numel(), current_stream()))
-        return out
+        return _forward(self, x, y, self._ws)
 
     def __call__(self, x, y):
         """x [N, 3], y [M, 3] float32 CUDA tensors with uniform weights -> 0-dim float32 tensor on the device."""

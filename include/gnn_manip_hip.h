@@ -307,6 +307,22 @@ size_t gm_sinkhorn_batched_workspace_bytes(int64_t batch, int64_t n, int64_t m);
 int gm_sinkhorn_divergence_batched(const float* x, int64_t batch, int64_t n, const float* y, int64_t m, int y_shared,
                                    float blur, float scaling, float diameter, float* loss_device /*[batch]*/, void* ws,
                                    size_t ws_bytes, void* stream);
+/* Gradient of gm_sinkhorn_divergence_batched (differentiable SamplesLoss): dx [batch, N, 3] and dy ([batch, M, 3], or [M, 3]
+ * when y_shared: the sum over the pairs, in pair order) of sum_b grad_loss[b] * loss_b.  Either output may be NULL; both are
+ * written, not accumulated.  fwd_ws is the workspace of the gm_sinkhorn_divergence_batched call with the same arguments,
+ * untouched since: its plan and potentials are the backward's input (no host synchronisation, no float atomics).
+ * Convention: geomloss's tensorized backend, read from its published code and UNPINNED against geomloss itself (absent), like
+ * the forward.  Potentials are detached; only the last extrapolation at eps = blur^2 is differentiated, with the right-hand
+ * cloud of every cost matrix detached:  dS/dx_i = (1/N) (T_xx(x_i) - T_xy(x_i)),  dS/dy_j = (1/M) (T_yy(y_j) - T_yx(y_j)),
+ * T the softmax barycentres of the last extrapolation's rows.  A pair whose clouds are one point gets 0 (its loss is 0 by
+ * definition), a pair with a non-finite coordinate NaN.  bwd_ws: gm_sinkhorn_batched_backward_workspace_bytes bytes
+ * (0 unless y_shared, with dy requested). */
+size_t gm_sinkhorn_batched_backward_workspace_bytes(int64_t batch, int64_t n, int64_t m, int y_shared);
+int gm_sinkhorn_divergence_batched_backward(const float* x, int64_t batch, int64_t n, const float* y, int64_t m, int y_shared,
+                                            float blur, float scaling, const float* grad_loss /*[batch], device*/,
+                                            float* dx /*[batch,n,3] or NULL*/,
+                                            float* dy /*[batch,m,3]; [m,3] if y_shared; or NULL*/, const void* fwd_ws,
+                                            size_t fwd_ws_bytes, void* bwd_ws, size_t bwd_ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * One device-resident rollout step = compute_rollout's loop body, rollout_utils.py:38-61 ==
