@@ -101,7 +101,7 @@ __device__ __forceinline__ T* uniform_ptr(T* p) {
 // that overwrites a piece it has just read.  A lane's own read and write addresses therefore do alias, no proof to the contrary
 // exists, and the single-thread memory model itself keeps each such pair in program order -- for the whole wave, since all lanes
 // execute one instruction stream.  tests/test_turn_tiles.py checks that property of the index maps (here and in hmlp.hip's
-// HM_LINES turn).  Explicit fences were measured instead (round 6, tools/ab_train.sh): any form -- all address spaces, LDS-only
+// whole-line turn).  Explicit fences were measured instead (round 6, tools/ab_train.sh): any form -- all address spaces, LDS-only
 // at wavefront scope, volatile tile accesses -- costs the training step 2.8 % (the chains' global prefetches no longer cross a turn).
 constexpr int TURN_LD = 36;
 constexpr int TURN_FLOATS = 32 * TURN_LD;

@@ -436,10 +436,8 @@ __global__ void __launch_bounds__(256) cell_order_kernel(const float4* __restric
 // order (d2, index) is total so the result is order-independent) and emit the first K.  Queries
 // with more than NB_CAP in-radius candidates are marked (cnt = -1) for the general kernel below.
 // ------------------------------------------------------------------------------------------
-#ifndef NB_LPQ
-#define NB_LPQ 16                      // lanes per query.  Round 6, same box: 4 lanes graph scope 77 us at C2 / 238 us at the target, 8 lanes
-#endif                                 // (rounds 2 - 5) 55 / 170, 16 lanes 40 / 133: an x-run of three cells holds ~14 candidates, one step of 16 lanes
-static_assert(NB_LPQ == 4 || NB_LPQ == 8 || NB_LPQ == 16, "lanes per query: a power of two that divides a wave, below 32 (the ballot mask)");
+constexpr int NB_LPQ = 16;             // lanes per query.  Round 6, same box: 4 lanes graph scope 77 us at C2 / 238 us at the target, 8 lanes
+                                       // (rounds 2 - 5) 55 / 170, 16 lanes 40 / 133: an x-run of three cells holds ~14 candidates, one step of 16 lanes
 constexpr int NB_CAP = 96;
 constexpr int NB_STRIDE = NB_CAP + 1;  // doubles per list: odd stride keeps the groups of a wave on distinct banks
 constexpr int NB_QPB = 256 / NB_LPQ;   // queries per 256-thread block
@@ -701,9 +699,7 @@ __global__ void __launch_bounds__(256) fill_ei_kernel(const int64_t* __restrict_
 // 8 lanes per segment: the segment is staged in LDS, every element is ranked against the others
 // (ids are unique) and written back in place.  Segments longer than SEG_CAP (in-degree > 96) are rank-sorted by the
 // whole workgroup through a copy in the workspace.
-#ifndef SEG_LPS
-#define SEG_LPS 8                  // lanes per segment (A/B builds)
-#endif
+constexpr int SEG_LPS = 8;                  // lanes per segment
 constexpr int SEG_PER_WG = 256 / SEG_LPS;   // segments per workgroup
 constexpr int SEG_CAP = 96;
 constexpr int SEG_STRIDE = SEG_CAP + 1;

@@ -17,7 +17,7 @@
 //   role 0: all the tick's requests at its top (P rows and indices of block x+1, e rows of block x+2: unconditional,
 //           clamped); P_i[dst] + P_j[src] of block x -> accumulators; e of block x+1 -> operand image E (between the
 //           MFMAs); Linear 1 on E, ReLU, image X1; destinations of the block into a small LDS ring for role 2;
-//   role 1: Linear 2 of block x-1 (X1 -> X2); LayerNorm + e_out = e + e' of the first EPI_SPLIT row groups of block x-3
+//   role 1: Linear 2 of block x-1 (X1 -> X2); LayerNorm + e_out = e + e' of row group 0 of block x-3
 //           (row-major, 8 lanes per row; unconditional stores: rows that do not exist lie beyond the store's buffer bound);
 //   role 2: Linear 3 of block x-2 (X2 -> Z + LayerNorm partial statistics); the other row groups of that epilogue;
 //           aggregation of block x-3 on a TRANSPOSED view (lane = feature, 16 rows of a half block in registers): the
@@ -55,9 +55,6 @@ constexpr int H = 128;
 constexpr int BE = 32;             // edges per block
 constexpr int SYS_THREADS = 768;
 static_assert(BE == kBlockEdges, "block tables and the systolic kernels agree on the block size");
-#ifndef SIDE_STRIDE
-#define SIDE_STRIDE 6   // MFMA slots per row group of role 1's e_out epilogue (24 slots per tick, 4 row groups)
-#endif
 #ifdef HEDGE_STAMPS
 // development build only: s_memtime stamps of the three roles (workgroup 0, waves jb = 0, lane 0) at the phase boundaries of
 // ticks 16..47; read back with gm_debug_sys_stamps (tools/sys_stamps.py)
@@ -72,17 +69,6 @@ __device__ unsigned long long g_sys_stamps[3 * 32 * 8 + 32];   // + the 100 MHz 
 #else
 #define SYS_STAMP(tick, slot) do { } while (0)
 #endif
-#ifndef HEDGE_PRIO0
-#define HEDGE_PRIO0 1
-#define HEDGE_PRIO1 1
-#define HEDGE_PRIO2 3
-#endif
-#ifndef EPI_SPLIT
-#define EPI_SPLIT 1   // row groups (of 8 rows) of a block's LayerNorm + e_out epilogue that role 1 keeps; role 2 takes the others
-#endif
-#ifndef HEDGE_XCD
-#define HEDGE_XCD 1
-#endif
 // Cache policy of a launch's row stores (aux bits of the buffer instructions: 2 = nt, 16 = sc1).  STREAM launches write e + e' with
 // sc1 | nt -- written through and kept out of L2 / the Infinity Cache, which then hold h, P and agg for the kernels that follow -- and
 // agg with sc1: right when the rows a launch writes cannot stay resident until the next launch reads them (target: 1 GB per launch,
@@ -90,9 +76,8 @@ __device__ unsigned long long g_sys_stamps[3 * 32 * 8 + 32];   // + the 100 MHz 
 // launch, and writing them through costs every launch an HBM round trip (round 5 shipped the streaming policy at every size: C2 - 8 %).
 // The launcher chooses (launch_edge_sys: kStreamStoreBytes).
 constexpr int ST_STREAM_E = 2 | 16, ST_STREAM_AGG = 16;
-#ifndef HENC_ST_AUX
-#define HENC_ST_AUX 0    // cache policy of the edge encoder's e stores (2 = nt, 16 = sc1)
-#endif
+constexpr int ST_ENC_E = 0;     // the edge encoder's e stores: default policy
+constexpr int ST_PROJ_Q = 16;   // the projection kernel's Q stores: sc1 (read once, by the node kernel behind the next edge launch)
 constexpr int HW_HEADER_FLOATS = 4;            // T1, 1/T3, cap of the per-row input scale (encoder image), pad
 constexpr int HW_VEC_FLOATS = 5 * H;           // b2*T2 | b3*T3 | gamma | beta | b1*T1 (the encoder's; a processor step has b1 in P)
 constexpr int HW_IMAGE_HALF8 = 3 * 4 * 8 * 2 * 64;   // [layer][jb][ks][part][lane]
@@ -144,7 +129,7 @@ __device__ __forceinline__ void bst1s(srd_t r, unsigned voff, unsigned soff, flo
 // gather the same neighbouring P rows at the same time (ranges one layer of cells apart advance in step) share an L2.
 __device__ __forceinline__ int xcd_major_wg() {
     const int g = (int)gridDim.x, i = (int)blockIdx.x;
-    return (HEDGE_XCD && (g & 7) == 0) ? (i & 7) * (g >> 3) + (i >> 3) : i;
+    return (g & 7) == 0 ? (i & 7) * (g >> 3) + (i >> 3) : i;
 }
 
 __device__ __forceinline__ int s_clamp0(int v, int hi) {
@@ -293,9 +278,8 @@ __device__ __forceinline__ void sys_prologue(half8 (&wh)[8], half8 (&wl)[8], con
 // Instruction arbitration: role 2 (Linear 3 + statistics, and the edge kernel's scatter-add scan) is the longest instruction
 // stream of a tick and role 0 feeds the pipeline.
 __device__ __forceinline__ void set_role_prio(int role) {
-    if (role == 2) __builtin_amdgcn_s_setprio(HEDGE_PRIO2);        // the builtin takes an immediate
-    else if (role == 0) __builtin_amdgcn_s_setprio(HEDGE_PRIO0);
-    else __builtin_amdgcn_s_setprio(HEDGE_PRIO1);
+    if (role == 2) __builtin_amdgcn_s_setprio(3);        // the builtin takes an immediate
+    else __builtin_amdgcn_s_setprio(1);
 }
 
 // 32 floats of a bias (this wave's output block jb) in accumulator layout, from the LDS vec block (vec_b: its byte address,
@@ -509,7 +493,7 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_edge_kernel(const CsrHeade
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = 0.f;
         int rng = 0;
-        floatx4 er[EPI_SPLIT + 1];          // e rows (row-major quads, rows 8 j + rr) of block x-3 for the residual
+        floatx4 er = floatx4{0.f, 0.f, 0.f, 0.f};   // e rows (row-major quads, row rr) of block x-3 for the residual
         int st_a = e0, cnt_a = 0, st_b = e0, cnt_b = 0;  // blocks x-3, x-2
         int2 bi_c = a_blk[b0];                          // raw table entry of block x-1 (decoded a tick after its load)
         const float res_w = a_residual ? 1.f : 0.f;
@@ -522,8 +506,6 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_edge_kernel(const CsrHeade
         const unsigned z_r = opaque(L_Z + jb * TILE_B + rr * TILE_ROW_B + cq * 16);
         const unsigned x_in = opaque(L_X1 + lane0 * 16), x_out = opaque(L_X2 + 4 * jb * 1024 + lane0 * 16);
         float* const e_out_wg = a_e_out + (size_t)e0 * H;
-#pragma unroll
-        for (int j = 0; j < EPI_SPLIT; ++j) er[j] = floatx4{0.f, 0.f, 0.f, 0.f};
         auto tick = [&](auto par_c, int t) {
             constexpr int PAR = decltype(par_c)::value, P1 = 1 - PAR, P3 = 1 - PAR;   // parities of blocks x, x-1 (this Linear's), x-3
             const int x = b0 + t;
@@ -535,12 +517,11 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_edge_kernel(const CsrHeade
                                                         // scalar-memory counter then finds it done
             const unsigned rel_a = (unsigned)(st_a - e0), rel_b = (unsigned)(st_b - e0);
             LnGroup lg;
-            auto side = [&](int slot) {   // LayerNorm + e_out of block x-3, row group slot / SIDE_STRIDE
-                if (!WRITE_E || slot >= EPI_SPLIT * SIDE_STRIDE) return;   // the other row groups are role 2's (balance of the roles' ticks)
-                const int j = slot / SIDE_STRIDE;
-                if (slot % SIDE_STRIDE == 0) lg.load(km_r + j * 32, z_r + P3 * 4 * TILE_B + j * 8 * TILE_ROW_B);
-                else if (slot % SIDE_STRIDE == 2)   // then the residual rows of block x-2
-                    lg.store<STREAM ? ST_STREAM_E : 0>(e_out_wg, rel_a, j, cnt_st, v_eoff, gm, bt, er[j], res_w, srd_ein, rel_b);
+            auto side = [&](int slot) {   // LayerNorm + e_out of block x-3, row group 0 (groups 1 .. 3 are role 2's: balance of the roles' ticks)
+                if (!WRITE_E) return;
+                if (slot == 0) lg.load(km_r, z_r + P3 * 4 * TILE_B);
+                else if (slot == 2)   // then the residual rows of block x-2
+                    lg.store<STREAM ? ST_STREAM_E : 0>(e_out_wg, rel_a, 0, cnt_st, v_eoff, gm, bt, er, res_w, srd_ein, rel_b);
             };
             SYS_STAMP(t, 1);
             SYS_STAMP(t, 2);
@@ -574,11 +555,11 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_edge_kernel(const CsrHeade
         int head_a = -1, head_b = -1;   // destination whose segment began in an earlier group (its sum over this group goes to the side buffer)
         int2 bn = a_blk[b0], sn = make_int2(0, 0);      // table entries of the block the next fetch() handles
         const float gam = LDS(float, L_VEC + (2 * H + 32 * jb + n) * 4), bet = LDS(float, L_VEC + (3 * H + 32 * jb + n) * 4);
-        // its share of the LayerNorm + e_out epilogue (row groups EPI_SPLIT .. 3 of block x-3, row-major: 8 lanes per row)
+        // its share of the LayerNorm + e_out epilogue (row groups 1 .. 3 of block x-3, row-major: 8 lanes per row)
         const float res_w = a_residual ? 1.f : 0.f;
-        floatx4 er[4 - EPI_SPLIT + 1];  // e rows of block x-3 for the residual (the groups of this role)
+        floatx4 er[3];                  // e rows of block x-3 for the residual (the groups of this role)
 #pragma unroll
-        for (int j = 0; j < 4 - EPI_SPLIT; ++j) er[j] = floatx4{0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < 3; ++j) er[j] = floatx4{0.f, 0.f, 0.f, 0.f};
         int st_a = e0, st_b = e0;       // first edge of blocks x-3, x-2
         const unsigned km_re = opaque(L_KM2 + jb * 128 + rr * 4);                          // + 32 j
         const unsigned z_e = opaque(L_Z + jb * TILE_B + rr * TILE_ROW_B + cq * 16);         // + 8 j rows
@@ -649,15 +630,15 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_edge_kernel(const CsrHeade
                     const float from0 = lower_half_to_both(open0);
                     const float c1v = (cont & 0x10000u) ? from0 : 0.f;
                     cpend = hi ? c1v : c0v;
-                } else if (WRITE_E && EPI_SPLIT < 4 && slot >= 14 && slot < 14 + 2 * (4 - EPI_SPLIT)) {
+                } else if (WRITE_E && slot >= 14 && slot < 20) {
                     // this role's share of the e_out epilogue: row group j, loads at an even slot, arithmetic + store at the next
-                    const int j = EPI_SPLIT + ((slot - 14) >> 1);
+                    const int j = 1 + ((slot - 14) >> 1);
                     if (!((slot - 14) & 1)) {
                         lg.load(km_re + j * 32, z_e + P3 * 4 * TILE_B + j * 8 * TILE_ROW_B);
                     } else {
                         const floatx4 gmq = LDS(floatx4, L_VEC + (2 * H + 32 * jb + 4 * cq) * 4);   // read per use: registers are scarcer than LDS slots here
                         const floatx4 btq = LDS(floatx4, L_VEC + (3 * H + 32 * jb + 4 * cq) * 4);
-                        lg.store<STREAM ? ST_STREAM_E : 0>(e_out_wg, rel_a, j, cnt_st, v_eoff, gmq, btq, er[j - EPI_SPLIT], res_w, srd_ein, rel_b);
+                        lg.store<STREAM ? ST_STREAM_E : 0>(e_out_wg, rel_a, j, cnt_st, v_eoff, gmq, btq, er[j - 1], res_w, srd_ein, rel_b);
                     }
                 }
             };
@@ -840,7 +821,7 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_enc_kernel(const CsrHeader
                     floatx4 o;
 #pragma unroll
                     for (int tt = 0; tt < 4; ++tt) o[tt] = fmaf(zq[tt] * kr, gm[tt], bt[tt]);
-                    bst4s<HENC_ST_AUX>(make_srd(e_out_wg + (size_t)((xb - b0) * BE + 8 * j) * H, (unsigned)s_clamp0(cnt - 8 * j, 8) * 512u), v_eoff, 0, o);
+                    bst4s<ST_ENC_E>(make_srd(e_out_wg + (size_t)((xb - b0) * BE + 8 * j) * H, (unsigned)s_clamp0(cnt - 8 * j, 8) * 512u), v_eoff, 0, o);
                 }
             }
             rng |= __any(acc[0] != acc[0]) ? 1 : 0;
@@ -1047,9 +1028,6 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_node_kernel(const float* a
 // block of 32 rows per tick and ONE barrier: rows of block x+2 requested, rows of block x+1 -> operand image (waves 0 .. 7, two
 // (row group, slab) units each), 24 MFMAs on the image of block x, accumulators -> the wave's own tile -> whole 128-byte lines.
 // ------------------------------------------------------------------------------------------
-#ifndef HPROJ_Q_AUX
-#define HPROJ_Q_AUX 16   // cache policy of the Q stores (16 = sc1)
-#endif
 constexpr int LP_E = 0;                             // [2] images of h rows
 constexpr int LP_T = LP_E + 2 * IMG_B;              // [12 waves] output tiles
 constexpr size_t PROJ_LDS_BYTES = LP_T + 12 * TILE_B;
@@ -1140,7 +1118,7 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_proj_kernel(const float* _
             const floatx4 o = LDS(floatx4, t_r + j * 8 * TILE_ROW_B);
             // Q is read once, by the node kernel behind the next edge launch (2 GB of streaming later): written through, not kept in L2;
             // P is gathered by that edge launch: default policy
-            if (isq) bst4s<HPROJ_Q_AUX>(make_srd(out_wg + (size_t)(rowx + 8 * j) * (out_row_b / 4), (unsigned)s_clamp0(cnt - 8 * j, 8) * out_row_b), v_out, 0, o);
+            if (isq) bst4s<ST_PROJ_Q>(make_srd(out_wg + (size_t)(rowx + 8 * j) * (out_row_b / 4), (unsigned)s_clamp0(cnt - 8 * j, 8) * out_row_b), v_out, 0, o);
             else bst4(make_srd(out_wg + (size_t)(rowx + 8 * j) * (out_row_b / 4), (unsigned)s_clamp0(cnt - 8 * j, 8) * out_row_b), v_out, 0, o);
         }
         lds_barrier();
@@ -1397,10 +1375,8 @@ bool edge_sys_fits(int64_t n_nodes, int64_t edge_capacity) {
     return (uint64_t)n_nodes * 2 * H * 4 < (1ull << 32) && agg_rows * H * 4 < (1ull << 32);
 }
 
-#ifndef HEDGE_STREAM_MB
-#define HEDGE_STREAM_MB 128   // A/B builds move it; 0 = always stream (round 5's policy), a huge value = never
-#endif
-constexpr uint64_t kStreamStoreBytes = (uint64_t)HEDGE_STREAM_MB << 20;
+// launches that write more edge rows than this stream their row stores (measured: right from a few hundred MB, wrong at 49 MB)
+constexpr uint64_t kStreamStoreBytes = 128ull << 20;
 
 // One launch of a systolic kernel: one workgroup per CU, SYS_THREADS threads, `lds` bytes of dynamic LDS (the attribute is set
 // once per device and kernel), timed under the profiler kind `kind`.

@@ -55,12 +55,9 @@ __device__ unsigned long long g_hm_stamps[4 * 4 * 16];
 #else
 #define HM_STAMP_E(tile_i, slot) do { } while (0)
 #endif
-// HM_LINES: the edge kernel's e + e' rows (and the residual rows they are added to) move as whole 128-byte lines: a wave's
+// Whole lines: the edge kernel's e + e' rows (and the residual rows they are added to) move as whole 128-byte lines: a wave's
 // 32 rows x 32 features take a turn through a wave-private tile in the (then idle) image region, after which an instruction
 // covers 8 rows x 128 bytes instead of 32 rows x 32 bytes.  Rows in the caller's order (eid_out) keep the piece form.
-#ifndef HM_LINES
-#define HM_LINES 1
-#endif
 constexpr int HM_TURN_LD = 36;                       // floats per row of the turn tile
 constexpr int HM_TURN_FLOATS = 32 * HM_TURN_LD;
 constexpr int HM_THREADS = 512;
@@ -159,12 +156,6 @@ __device__ __forceinline__ void report_range(int bad, int* flags) {
 //   im : image of the wave's first row block at k-group 0, + lane  (row-block stride img_ksn * 128, k-group stride 128)
 // nrb: row blocks of this wave that hold rows (the others' MFMAs are skipped: the last tile of a workgroup's range may be partial;
 // a branch-free copy of the loop for full tiles was measured: -4 %, it costs registers the kernels do not have)
-#ifndef HM_SHORT_TILE_ROWS
-#define HM_SHORT_TILE_ROWS 1
-#endif
-#ifndef HM_RING4
-#define HM_RING4(RBW) ((RBW) == 1)
-#endif
 // One k-group: the three partial products of every row block (lo.hi + hi.lo + hi.hi).
 template <int RBW>
 __device__ __forceinline__ void mfma3(floatx16 (&acc)[RBW], const half8& ah, const half8& al, const half8 (&bh)[RBW], const half8 (&bl)[RBW], int nrb) {
@@ -191,7 +182,7 @@ __device__ __forceinline__ void gemm(floatx16 (&acc)[RBW], const half8* __restri
 #pragma unroll
         for (int rb = 0; rb < RBW; ++rb) { h[rb] = im[(rb * img_ksn + kg) * 128]; l[rb] = im[(rb * img_ksn + kg) * 128 + 64]; }
     };
-    if (HM_RING4(RBW) && nks >= 4 && (nks & 3) == 0) {
+    if (RBW == 1 && nks >= 4 && (nks & 3) == 0) {
         half8 ah[4], al[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) { ah[q] = wf[q * 128]; al[q] = wf[q * 128 + 64]; }
@@ -533,7 +524,7 @@ __global__ void __launch_bounds__(HM_THREADS, 1) hm_edge_kernel(HmEdgeArgs A) {
         for (int r = 0; r < 16; ++r) carry[r] = 0.f;
         int prev_last = -3, head = -1;
         // the image is idle from here to the next tile's barrier: wave-private turn tiles at its start
-        const bool lines = HM_LINES && !ENC && !A.eid_out && !A.discard_e_out;
+        const bool lines = !ENC && !A.eid_out && !A.discard_e_out;
         float* turn = reinterpret_cast<float*>(smem) + wave * HM_TURN_FLOATS;
         float* t_acc = turn + n * HM_TURN_LD + 4 * hi;                       // this lane's pieces of row n: + 8 g
         float* t_row = turn + (lane >> 3) * HM_TURN_LD + 4 * (lane & 7);      // row-major: row (lane >> 3) + 8 j: + 8 j HM_TURN_LD
@@ -703,7 +694,7 @@ __global__ void __launch_bounds__(HM_THREADS, 1) hm_node_kernel(HmNodeArgs A) {
         // rows nobody uses -- the last, short tile of a workgroup then costs what its blocks cost
         auto row_of = [&](int rbg, int nn) -> long long {
             const int j = (rbg % RBW) * C::NRG + rbg / RBW;
-            const int r = (HM_SHORT_TILE_ROWS && j >= nbt ? 32 * bt : slot_row0(rbg)) + nn;
+            const int r = (j >= nbt ? 32 * bt : slot_row0(rbg)) + nn;
             return r < N ? r : N - 1;
         };
         __syncthreads();   // the previous tile's readers of the image are done
@@ -1075,27 +1066,18 @@ int launch_node_hr(int mode, const HmNodeArgs& a, hipStream_t s) {
     else hipLaunchKernelGGL((hm_node_kernel<H, 2, RBW>), dim3(grid), dim3(HM_THREADS), LDS, s, a);
     return GM_OK;
 }
-// small graphs: one 32-row block per wave, so that the tiles cover the CUs.  HM_NODE_SMALL_ROUNDS: the 4-block form is used
-// once its tiles fill the CUs that many times over.  1 is the measured choice: at N = 100k / hidden 128 (391 tiles of 256
-// rows on 256 CUs, a half-empty second round) the small form is still 16 % slower (1.80 vs 1.55 ms of node kernels per
-// step, A/B on one box) -- it streams the weights four times as often.
+// small graphs: one 32-row block per wave, so that the tiles cover the CUs.  The 4-block form is used once its tiles fill the
+// CUs: at N = 100k / hidden 128 (391 tiles of 256 rows on 256 CUs, a half-empty second round) the small form is still 16 %
+// slower (1.80 vs 1.55 ms of node kernels per step, A/B on one box) -- it streams the weights four times as often.
 // Round 6, hidden 128: the kernel deals 32-row BLOCKS evenly to the workgroups whatever the form, so what counts is blocks per
-// workgroup, not whole tiles -- measured on one box (bench.py, -DHM_NODE_SMALL_BLOCKS): 1.2 blocks per workgroup (2 x 5k nodes)
-// one-block form 1924 vs four-block form 1503 steps/s; 2.4 (4 x 5k) 2091 vs 2021; 4.9 (a C5 batch, 8 x 5k) 2304 vs 2355 - 2360.
+// workgroup, not whole tiles -- measured on one box (bench.py): 1.2 blocks per workgroup (2 x 5k nodes) one-block form 1924
+// vs four-block form 1503 steps/s; 2.4 (4 x 5k) 2091 vs 2021; 4.9 (a C5 batch, 8 x 5k) 2304 vs 2355 - 2360.
 // The four-block form takes over from 4 blocks per workgroup (round 5: from 8).  Results do not depend on the form.
-#ifndef HM_NODE_SMALL_ROUNDS
-#define HM_NODE_SMALL_ROUNDS 1
-#endif
-#ifndef HM_NODE_RBW
-#define HM_NODE_RBW 4
-#endif
 template <int H>
 int launch_node_h(int mode, const HmNodeArgs& a, hipStream_t s) {
-#ifndef HM_NODE_SMALL_BLOCKS
-#define HM_NODE_SMALL_BLOCKS (H == 128 ? 4 : HM_NODE_SMALL_ROUNDS * Cfg<H, 4>::NRB)   // 32-row blocks per workgroup below which the one-block form runs
-#endif
-    if (cdiv(a.n_nodes, 32) < (int64_t)(HM_NODE_SMALL_BLOCKS) * device_cus()) return launch_node_hr<H, 1>(mode, a, s);
-    return launch_node_hr<H, HM_NODE_RBW>(mode, a, s);
+    constexpr int small_blocks = H == 128 ? 4 : Cfg<H, 4>::NRB;   // 32-row blocks per workgroup below which the one-block form runs
+    if (cdiv(a.n_nodes, 32) < (int64_t)small_blocks * device_cus()) return launch_node_hr<H, 1>(mode, a, s);
+    return launch_node_hr<H, 4>(mode, a, s);
 }
 
 }  // namespace

@@ -310,12 +310,9 @@ __device__ __forceinline__ void ln_param_sums(const floatx16 (&g)[NJB], const fl
     }
 }
 
-// Which of the chains' row-major arrays move as whole 128-byte lines through a wave-private LDS turn (store_feat_lines /
-// load_feat_lines) instead of accumulator-layout pieces (32 rows x 32 bytes per instruction).  Forward: 1 tape stores, 2 output
-// stores.  Backward: 8 dz stores, 16 input-gradient stores, 32 dY / G / xhat loads.
-#ifndef TRAIN_LINES
-#define TRAIN_LINES 63
-#endif
+// The chains' row-major arrays move as whole 128-byte lines through a wave-private LDS turn (store_feat_lines /
+// load_feat_lines) instead of accumulator-layout pieces (32 rows x 32 bytes per instruction).  Forward: tape and output
+// stores.  Backward: dz and input-gradient stores, dY / G / xhat loads.  Rows in the caller's order keep the piece form.
 
 // ------------------------------------------------------------------------------------------
 // forward with tape
@@ -372,12 +369,10 @@ __global__ void __launch_bounds__(THREADS, H <= 128 ? 2 : 1) train_fwd_kernel(Tr
             load_feat(act, A.x_in + pc * H, hi);
             load_feat(acc, A.bias, hi);
             run_layer_b3<H / 16, NJB, NJB>(acc, act, ws, more);
-            if (TRAIN_LINES & 2) store_feat_lines(acc, A.out + (size_t)row0 * (2 * H), 2 * H, R - row0, turn, lane);
-            else store_feat(acc, A.out + pc * (2 * H), hi);
+            store_feat_lines(acc, A.out + (size_t)row0 * (2 * H), 2 * H, R - row0, turn, lane);
             zero_feat(acc);
             run_layer_b3<H / 16, NJB, NJB>(acc, act, ws, more);
-            if (TRAIN_LINES & 2) store_feat_lines(acc, A.out + (size_t)row0 * (2 * H) + H, 2 * H, R - row0, turn, lane);
-            else store_feat(acc, A.out + pc * (2 * H) + H, hi);
+            store_feat_lines(acc, A.out + (size_t)row0 * (2 * H) + H, 2 * H, R - row0, turn, lane);
             continue;
         } else if (KIND == TK_PROC_NODE) {
             load_feat(act, A.x_in + pc * H, hi);
@@ -399,15 +394,13 @@ __global__ void __launch_bounds__(THREADS, H <= 128 ? 2 : 1) train_fwd_kernel(Tr
         for (int l = 1; l < NL; ++l) {   // Linear l + 1 (hidden)
             relu_to(act, acc);
             load_feat(acc, A.bias_tail + (size_t)(l - 1) * H, hi);
-            if (TRAIN_LINES & 1) store_feat_lines(act, A.tape.a + (size_t)(l - 1) * tstride + (size_t)row0 * H, H, R - row0, turn, lane);
-            else store_feat(act, A.tape.a + (size_t)(l - 1) * tstride + pc * H, hi);
+            store_feat_lines(act, A.tape.a + (size_t)(l - 1) * tstride + (size_t)row0 * H, H, R - row0, turn, lane);
             relu_mask_store(act, A.tape.mask + ((size_t)(l - 1) * R + pc) * NJB + hi * (NJB / 2));
             run_layer_b3<H / 16, NJB, NJB, NST + 1>(acc, act, ws, more);
         }
         relu_to(act, acc);
         if (KIND != TK_DEC) load_feat(acc, A.bias_tail + (size_t)(NL - 1) * H, hi);
-        if (TRAIN_LINES & 1) store_feat_lines(act, A.tape.a + (size_t)(NL - 1) * tstride + (size_t)row0 * H, H, R - row0, turn, lane);
-        else store_feat(act, A.tape.a + (size_t)(NL - 1) * tstride + pc * H, hi);
+        store_feat_lines(act, A.tape.a + (size_t)(NL - 1) * tstride + (size_t)row0 * H, H, R - row0, turn, lane);
         relu_mask_store(act, A.tape.mask + ((size_t)(NL - 1) * R + pc) * NJB + hi * (NJB / 2));
         if (KIND == TK_DEC) {
             floatx16 o[1];
@@ -421,8 +414,7 @@ __global__ void __launch_bounds__(THREADS, H <= 128 ? 2 : 1) train_fwd_kernel(Tr
         } else {
             run_layer_b3<H / 16, NJB, NJB, NST + 1>(acc, act, ws, more);
             const float rstd = layer_norm_tape(acc, act, A.ln_g, A.ln_b, A.eps, hi);
-            if (TRAIN_LINES & 1) store_feat_lines(act, A.tape.xhat + (size_t)row0 * H, H, R - row0, turn, lane);
-            else store_feat(act, A.tape.xhat + pc * H, hi);
+            store_feat_lines(act, A.tape.xhat + (size_t)row0 * H, H, R - row0, turn, lane);
             if (valid && hi == 0) A.tape.rstd[pc] = rstd;
             if (KIND == TK_PROC_EDGE && A.rowidx) {   // the single-block entry point: e rows in the caller's order
                 const int64_t orow = A.rowidx[pc];
@@ -430,8 +422,7 @@ __global__ void __launch_bounds__(THREADS, H <= 128 ? 2 : 1) train_fwd_kernel(Tr
                 if (valid) store_feat(acc, A.out + orow * H, hi);
             } else {
                 if ((KIND == TK_PROC_EDGE || KIND == TK_PROC_NODE) && A.residual) add_feat(acc, A.x_in + pc * H, hi);
-                if (TRAIN_LINES & 2) store_feat_lines(acc, A.out + (size_t)row0 * H, H, R - row0, turn, lane);
-                else store_feat(acc, A.out + pc * H, hi);
+                store_feat_lines(acc, A.out + (size_t)row0 * H, H, R - row0, turn, lane);
             }
             if ((KIND == TK_ENC_NODE || KIND == TK_PROC_NODE) && proj_tail) {
                 // the next edge step's factorised layer 1 on the rows still in registers: P = [h W_i^T + b1 | h W_j^T]
@@ -440,12 +431,10 @@ __global__ void __launch_bounds__(THREADS, H <= 128 ? 2 : 1) train_fwd_kernel(Tr
                 for (int jb = 0; jb < NJB; ++jb) act[jb] = acc[jb];
                 load_feat(acc, A.proj_bias, hi);
                 run_layer_b3<H / 16, NJB, NJB>(acc, act, ws, more);
-                if (TRAIN_LINES & 2) store_feat_lines(acc, A.P_out + (size_t)row0 * (2 * H), 2 * H, R - row0, turn, lane);
-                else store_feat(acc, A.P_out + pc * (2 * H), hi);
+                store_feat_lines(acc, A.P_out + (size_t)row0 * (2 * H), 2 * H, R - row0, turn, lane);
                 zero_feat(acc);
                 run_layer_b3<H / 16, NJB, NJB>(acc, act, ws, more);
-                if (TRAIN_LINES & 2) store_feat_lines(acc, A.P_out + (size_t)row0 * (2 * H) + H, 2 * H, R - row0, turn, lane);
-                else store_feat(acc, A.P_out + pc * (2 * H) + H, hi);
+                store_feat_lines(acc, A.P_out + (size_t)row0 * (2 * H) + H, 2 * H, R - row0, turn, lane);
             }
         }
     }
@@ -503,49 +492,42 @@ __global__ void __launch_bounds__(THREADS, H <= 128 ? 2 : 1) train_bwd_kernel(Tr
         } else {
             // total upstream gradient of the MLP output row
             if (A.dY) {
-                if (A.dyidx || !(TRAIN_LINES & 32)) load_feat(acc, A.dY + (A.dyidx ? (int64_t)A.dyidx[pc] : pc) * H, hi);
+                if (A.dyidx) load_feat(acc, A.dY + (A.dyidx ? (int64_t)A.dyidx[pc] : pc) * H, hi);
                 else load_feat_lines<0>(acc, A.dY + (size_t)row0 * H, H, R - row0, turn, lane);
             } else {
                 zero_feat(acc);
             }
             if (KIND == TB_EDGE && A.dagg) add_feat(acc, A.dagg + (int64_t)A.dst[pc] * H, hi);
             if (has_g) {  // + W_i^T G_i + W_j^T G_j : input gradient of the NEXT edge step's factorised layer 1
-                if (TRAIN_LINES & 32) load_feat_lines<0>(act, A.Gi + (size_t)row0 * H, H, R - row0, turn, lane);
-                else load_feat(act, A.Gi + pc * H, hi);
+                load_feat_lines<0>(act, A.Gi + (size_t)row0 * H, H, R - row0, turn, lane);
                 run_layer_b3<H / 16, NJB, NJB>(acc, act, ws, more);
-                if (TRAIN_LINES & 32) load_feat_lines<0>(act, A.Gj + (size_t)row0 * H, H, R - row0, turn, lane);
-                else load_feat(act, A.Gj + pc * H, hi);
+                load_feat_lines<0>(act, A.Gj + (size_t)row0 * H, H, R - row0, turn, lane);
                 run_layer_b3<H / 16, NJB, NJB>(acc, act, ws, more);
             }
             if (KIND == TB_PROJ) {
-                if (TRAIN_LINES & 16) store_feat_lines(acc, A.dx + (size_t)row0 * H, H, R - row0, turn, lane);
-                else store_feat(acc, A.dx + pc * H, hi);
+                store_feat_lines(acc, A.dx + (size_t)row0 * H, H, R - row0, turn, lane);
                 continue;
             }
             if (valid && KIND == TB_NODE && A.dx_resid) store_feat(acc, A.dx_resid + pc * H, hi);  // residual path: dh_in starts as dY
-            if (TRAIN_LINES & 32) load_feat_lines<0>(act, A.tape.xhat + (size_t)row0 * H, H, R - row0, turn, lane);
-            else load_feat(act, A.tape.xhat + pc * H, hi);
+            load_feat_lines<0>(act, A.tape.xhat + (size_t)row0 * H, H, R - row0, turn, lane);
             if (NORMED && A.ln_part) ln_param_sums(acc, act, valid, lnacc + wave * 2 * H, n, hi);
             layer_norm_bwd(acc, act, A.ln_g, A.tape.rstd[pc], hi);
             // dz stores: every lane (duplicates of the last row past the end), counted by run_layer_b3<.., PEND>
-            if (TRAIN_LINES & 8) store_feat_lines(act, A.dz + (size_t)NL * A.dz_stride + (size_t)row0 * H, H, R - row0, turn, lane);
-            else store_feat(act, A.dz + (size_t)NL * A.dz_stride + pc * H, hi);
+            store_feat_lines(act, A.dz + (size_t)NL * A.dz_stride + (size_t)row0 * H, H, R - row0, turn, lane);
             zero_feat(acc);
             run_layer_b3<H / 16, NJB, NJB, H / 8>(acc, act, ws, more);  // W_(NL+1)^T dz_(NL+1)
         }
 #pragma unroll 1
         for (int l = NL; l >= 2; --l) {   // dz_l = (W_(l+1)^T dz_(l+1)) [a_l > 0], then on through W_l^T
             mask_bits(acc, A.tape.mask + ((size_t)(l - 1) * R + pc) * NJB + hi * (NJB / 2));
-            if (TRAIN_LINES & 8) store_feat_lines(acc, A.dz + (size_t)(l - 1) * A.dz_stride + (size_t)row0 * H, H, R - row0, turn, lane);
-            else store_feat(acc, A.dz + (size_t)(l - 1) * A.dz_stride + pc * H, hi);
+            store_feat_lines(acc, A.dz + (size_t)(l - 1) * A.dz_stride + (size_t)row0 * H, H, R - row0, turn, lane);
 #pragma unroll
             for (int jb = 0; jb < NJB; ++jb) act[jb] = acc[jb];
             zero_feat(acc);
             run_layer_b3<H / 16, NJB, NJB, H / 8>(acc, act, ws, more);
         }
         mask_bits(acc, A.tape.mask + (size_t)pc * NJB + hi * (NJB / 2));
-        if (TRAIN_LINES & 8) store_feat_lines(acc, A.dz + (size_t)row0 * H, H, R - row0, turn, lane);
-        else store_feat(acc, A.dz + pc * H, hi);
+        store_feat_lines(acc, A.dz + (size_t)row0 * H, H, R - row0, turn, lane);
         if (KIND == TB_ENC) {
             if (A.dx_in) {  // gradient w.r.t. the raw input features: dX = dz1 . W1  (k1 <= 32 columns)
 #pragma unroll
@@ -570,26 +552,22 @@ __global__ void __launch_bounds__(THREADS, H <= 128 ? 2 : 1) train_bwd_kernel(Tr
         if (KIND == TB_EDGE) {
             // de_in = W_e^T dz1 (+ de_out through the residual), written over the row it came from
             if (A.residual && A.dY) {
-                if (A.dyidx || !(TRAIN_LINES & 32)) add_feat(acc, A.dY + (A.dyidx ? (int64_t)A.dyidx[pc] : pc) * H, hi);
+                if (A.dyidx) add_feat(acc, A.dY + (A.dyidx ? (int64_t)A.dyidx[pc] : pc) * H, hi);
                 else load_feat_lines<1>(acc, A.dY + (size_t)row0 * H, H, R - row0, turn, lane);
             }
             if (A.dxidx) {
                 if (valid) store_feat(acc, A.dx + (int64_t)A.dxidx[pc] * H, hi);
             } else {
-                if (TRAIN_LINES & 16) store_feat_lines(acc, A.dx + (size_t)row0 * H, H, R - row0, turn, lane);
-                else store_feat(acc, A.dx + pc * H, hi);
+                store_feat_lines(acc, A.dx + (size_t)row0 * H, H, R - row0, turn, lane);
             }
         } else if (KIND == TB_NODE) {
             if (A.dx_resid) add_feat(acc, A.dx_resid + pc * H, hi);  // same thread wrote this row above
-            if (TRAIN_LINES & 16) store_feat_lines(acc, A.dx + (size_t)row0 * H, H, R - row0, turn, lane);
-            else store_feat(acc, A.dx + pc * H, hi);
+            store_feat_lines(acc, A.dx + (size_t)row0 * H, H, R - row0, turn, lane);
             zero_feat(acc);
             run_layer_b3<H / 16, NJB, NJB>(acc, act, ws, more);  // W_agg^T dz1
-            if (TRAIN_LINES & 16) store_feat_lines(acc, A.dagg_out + (size_t)row0 * H, H, R - row0, turn, lane);
-            else store_feat(acc, A.dagg_out + pc * H, hi);
+            store_feat_lines(acc, A.dagg_out + (size_t)row0 * H, H, R - row0, turn, lane);
         } else {
-            if (TRAIN_LINES & 16) store_feat_lines(acc, A.dx + (size_t)row0 * H, H, R - row0, turn, lane);
-            else store_feat(acc, A.dx + pc * H, hi);
+            store_feat_lines(acc, A.dx + (size_t)row0 * H, H, R - row0, turn, lane);
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

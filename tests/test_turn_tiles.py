@@ -1,5 +1,5 @@
 """The wave-private LDS transposes of the training chains (csrc/fchain.h: store_feat_lines / turn_in) and of the streamed edge
-kernel's whole-line epilogue (csrc/hmlp.hip: HM_LINES) write a 32 x 32 tile in one layout and read it back in the other with no
+kernel's whole-line epilogue (csrc/hmlp.hip: hm_edge_kernel) write a 32 x 32 tile in one layout and read it back in the other with no
 barrier or fence in between.  Hardware: one wave's LDS instructions execute in order.  Compiler: it may reorder a read above a write
 only if it can prove that the two addresses never coincide for a thread -- so the property that keeps the order is that EVERY
 read instruction of a turn has a lane that reads a 16-byte piece that same lane wrote, and every write instruction of the next turn a
@@ -34,11 +34,11 @@ def check(write_piece, read_piece):
 
 
 def test_store_feat_lines_turn_keeps_program_order():
-    check(acc_piece, row_piece)     # accumulator layout in, whole lines out (store_feat_lines; HM_LINES e + e' stores)
+    check(acc_piece, row_piece)     # accumulator layout in, whole lines out (store_feat_lines; hm_edge_kernel's e + e' stores)
 
 
 def test_turn_in_keeps_program_order():
-    check(row_piece, acc_piece)     # whole lines in, accumulator layout out (turn_in / load_feat_lines; HM_LINES residual rows)
+    check(row_piece, acc_piece)     # whole lines in, accumulator layout out (turn_in / load_feat_lines; hm_edge_kernel's residual rows)
 
 
 def test_the_kernels_use_these_index_maps():
