@@ -5,7 +5,11 @@ Tolerances (floating point, stated here): forward 1e-5 relative (north_star).  G
 max(2e-4, 4 x the error of the SAME plain-PyTorch model run in float32) x max |g64| per tensor, g64 = float64
 oracle.  The second term exists because the gradient of a ReLU network with an L1 loss is discontinuous:
 one pre-activation whose sign differs between float32 and float64 arithmetic moves a whole row's contribution
-(~1e-3 of a tensor at these sizes) -- plain PyTorch float32 shows exactly the same deviations on the same tensors."""
+(~1e-3 of a tensor at these sizes) -- plain PyTorch float32 shows exactly the same deviations on the same tensors.
+
+Every graph here is small enough that a training workgroup runs ONE 128-row tile (at most 377 edge tiles, 20 node tiles) and is a
+radius graph of a scene.  Sizes past one tile per workgroup, hub / multigraph edge lists and the standalone InteractionNetwork's
+input gradients are in tests/test_gpu_train_regimes.py, held to the yardstick of this file."""
 import numpy as np
 import pytest
 import torch
@@ -54,14 +58,15 @@ def _check(m, params, nodes, ea, ei, dims, dev, seed):
     _, _, g32 = torch_epd.loss_and_grads(params, nodes, ea, ei, target, dims[4], dims[5], torch.float32)
     assert np.abs(out.detach().cpu().numpy() - ref_out).max() <= 1e-5 * max(np.abs(ref_out).max(), 1e-3)
     assert abs(float(loss.detach()) - ref_loss) <= 1e-5 * abs(ref_loss)
-    _compare_gradients(m, params, nodes, ea, ei, target, dims[4], dims[5], ref_g, g32)
+    return _compare_gradients(m, params, nodes, ea, ei, target, dims[4], dims[5], ref_g, g32)
 
 
 def _compare_gradients(m, params, nodes, ea, ei, target, num_layers, m_steps, ref_g, g32):
     """Every parameter gradient against float64: within max(GRAD_TOL, 4 x PyTorch float32's own error on this tensor) of the
     tensor's maximum.  A tensor beyond that is allowed only what the ReLU units of THIS input whose float64 pre-activation lies
     within 1e-5 of its Linear's rms of zero can explain (oracle/torch_epd.py: relu_flip_allowance -- two float32-accurate
-    evaluations may disagree on the sign of exactly those units): the bound is computed, not assumed, and no seed is exempt."""
+    evaluations may disagree on the sign of exactly those units): the bound is computed, not assumed, and no seed is exempt.
+    Returns (worst (name, err / tol, err, tol) without the allowance, the same with it -- or None where it was not needed)."""
     def worst_of(allow):
         worst = ("", 0.0)
         for name, p in m.named_parameters():
@@ -79,6 +84,8 @@ def _compare_gradients(m, params, nodes, ea, ei, target, num_layers, m_steps, re
         allow, n_units = torch_epd.relu_flip_allowance(params, nodes, ea, ei, target, num_layers, m_steps)
         worst2 = worst_of(allow)
         assert worst2[1] <= 1.0, (worst, worst2, n_units)
+        return worst, worst2
+    return worst, None
 
 
 @pytest.mark.parametrize("n,side,seed,m_steps", [(900, 0.075, 91, 3), (130, 0.3, 92, 2), (2500, 0.1, 93, 10)])
