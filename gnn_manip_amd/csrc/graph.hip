@@ -351,7 +351,10 @@ __device__ void grid_params(GraphHeader* hdr, double r, int max_cells, int64_t n
     double h = r * (1.0 + 1.0 / 1024.0);
     if (!(h > 0.0)) h = 1.0;
     int d[3];
-    for (int it = 0; it < 256; ++it) {
+    // The loop ends by itself: h grows without bound (to +inf at the latest, where every axis has one cell), so the cell count
+    // reaches 1 <= max_cells.  A fixed number of rounds does not: an extent of 1e30 at r = 0.015 needs 272 doublings of the
+    // volume, and a grid left larger than max_cells sends cell_assign_kernel past the end of cell_start.
+    for (;;) {
         double prod = 1.0;
         for (int a = 0; a < 3; ++a) {
             double c = floor(ext[a] / h) + 1.0;

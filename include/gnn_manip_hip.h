@@ -50,6 +50,8 @@ int gm_abi_version(void);
  *                 gnn_manip/utils/utils.py:64-93  (sklearn KDTree.query_radius semantics:
  *                 float64 squared distance, d2 <= r*r, ascending distance, first max_nb kept,
  *                 ties broken on the smaller index).
+ *                 max_neighbours: 1 .. 160 (the general kernel's candidate lists live in LDS), else GM_ERR_UNSUPPORTED;
+ *                 a batch whose n_nodes is not a multiple of nodes_per_graph: GM_ERR_INVALID_ARGUMENT.
  * ------------------------------------------------------------------------------------------ */
 size_t gm_graph_workspace_bytes(int64_t n_nodes, int max_neighbours);
 

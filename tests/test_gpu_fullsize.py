@@ -47,7 +47,7 @@ def test_radius_graph_full_size_bit_exact(dev, n, seed):
     same = s_np[1:] == s_np[:-1]
     p64 = pos.astype(np.float64)
     d2 = ((p64[s_np] - p64[r_np]) ** 2).sum(axis=1)
-    assert (d2[1:][same] > d2[:-1][same]).all()  # strictly ascending: no tie among the kept neighbours (tie order is undefined)
+    assert (d2[1:][same] > d2[:-1][same]).all()  # strictly ascending: no tie among the kept neighbours of this random scene (ties go to the smaller index: test_gpu_graph_edges.py)
 
 
 def test_csr_full_size_is_a_stable_sort(dev, scene100k):
