@@ -19,6 +19,9 @@ enum EdgeKernel : int {
 // One MLP of the state_dict (epd_gnn.py:63-84): tensors [base, end) = W_0, b_0, .., W_NL, b_NL [, gamma, beta]; `in` inputs of
 // Linear 0, `out` outputs of Linear NL, hidden_size between them; normed: ends in a LayerNorm (all but the decoder)
 struct MlpSpec { int base, end, in, out; bool normed; };
+// One chain's forward weight stream in packed_t3: where it starts and how many stages the chain walks -- `stages` on its own,
+// `stages_tail` with the next step's [W_i | W_j] that follow it (node streams whose kernel may run the projection tail; else 0)
+struct TStream { size_t off = 0; int stages = 0, stages_tail = 0; };
 // the model's MLPs in state_dict order: edge encoder, node encoder, the edge and node MLP of each step, the decoder
 std::vector<MlpSpec> model_mlps(const gm_model_desc& d);
 }  // namespace gm
@@ -46,8 +49,8 @@ struct gm_model {
     // bf16 x 3 weight streams of the training kernels (train.hip), hidden 64 / 128 / 256 only: MLP after MLP, stages of kStageFloatsB3
     float* packed_t3 = nullptr;
     std::vector<gm::PackTJob> t_jobs;
-    size_t t_enc_edge = 0, t_enc_node = 0, t_dec = 0;
-    std::vector<size_t> t_edge, t_node, t_proj;   // t_proj: [W_i | W_j] of step k, the tail of the node encoder (k = 0) or node step k - 1
+    gm::TStream t_enc_edge, t_enc_node, t_dec;
+    std::vector<gm::TStream> t_edge, t_node, t_proj;   // t_proj: [W_i | W_j] of step k, the tail of the node encoder (k = 0) or node step k - 1
     float* packed_hm = nullptr;  // fp16 hi / lo image of every Linear (hmlp.h)
     std::vector<gm::PackHmJob> hm_jobs;   // host copy of hm_jobs_dev
     gm::PackHmJob* hm_jobs_dev = nullptr;

@@ -82,7 +82,8 @@ WeightSizes plan_weights(gm_model* m) {
     const int H = m->Hp, Hv = m->H, NL = m->NL, M = m->M;
     const MlpSpec &enc_edge = m->mlp[0], &enc_node = m->mlp[1], &dec = m->mlp.back();
     WeightSizes z{};
-    for (auto* v : {&m->v_edge, &m->v_node, &m->t_proj, &m->t_edge, &m->t_node, &m->hm_edge, &m->hm_node, &m->hm_node_tail,
+    for (auto* v : {&m->t_proj, &m->t_edge, &m->t_node}) v->assign(M, TStream{});
+    for (auto* v : {&m->v_edge, &m->v_node, &m->hm_edge, &m->hm_node, &m->hm_node_tail,
                     &m->hm_node_q, &m->h3_edge, &m->h3_node})
         v->assign(M, 0);
     std::vector<const float*> T;   // the raw copy of each tensor
@@ -124,31 +125,35 @@ WeightSizes plan_weights(gm_model* m) {
     // bf16 x 3 streams of the training kernels, for the widths they exist for: the forward Linears in the order the chains consume them
     m->t_jobs.clear();
     if (Hv == 64 || Hv == 128 || Hv == 256) {
+        TStream* cur = nullptr;   // the stream being laid out: begin() opens it, every Linear packed from there on counts into it
+        auto begin = [&](TStream& t) { t = {z.t3, 0, 0}; cur = &t; };
         auto t3 = [&](int ti, int out_rows, int ld, int col0, int k) {
             m->t_jobs.push_back({T[ti], k, ld, col0, out_rows, 1, z.t3});
+            cur->stages += layer_stages_b3(k, out_rows);
             z.t3 += (size_t)layer_stages_b3(k, out_rows) * kStageFloatsB3;
         };
         auto hidden3 = [&](const MlpSpec& p) { for (int l = 1; l <= NL; ++l) t3(p.base + 2 * l, l == NL ? p.out : H, H, 0, H); };
         auto whole3 = [&](const MlpSpec& p) { t3(p.base, H, p.in, 0, p.in); hidden3(p); };   // Linear 0 in one block: encoders, decoder
-        m->t_enc_edge = z.t3;
+        begin(m->t_enc_edge);
         whole3(enc_edge);
-        m->t_enc_node = z.t3;
+        begin(m->t_enc_node);
         whole3(enc_node);
-        // the node encoder's stream and each node step's go on into the next step's W_i, W_j and the last one's into the decoder
         for (int k = 0; k < M; ++k) {
             const MlpSpec &e = m->edge_mlp(k), &n = m->node_mlp(k);
-            m->t_proj[k] = z.t3;
+            TStream& before = k == 0 ? m->t_enc_node : m->t_node[k - 1];   // ends where [W_i | W_j] begin: its projection tail runs on into them
+            begin(m->t_proj[k]);
             t3(e.base, H, 3 * H, m->ci * H, H);   // W_i
             t3(e.base, H, 3 * H, m->cj * H, H);   // W_j
-            m->t_edge[k] = z.t3;
+            before.stages_tail = before.stages + m->t_proj[k].stages;
+            begin(m->t_edge[k]);
             t3(e.base, H, 3 * H, m->ce * H, H);   // W_e
             hidden3(e);
-            m->t_node[k] = z.t3;
+            begin(m->t_node[k]);
             t3(n.base, H, 2 * H, m->ch * H, H);   // W_h
             t3(n.base, H, 2 * H, m->ca * H, H);   // W_agg
             hidden3(n);
         }
-        m->t_dec = z.t3;
+        begin(m->t_dec);
         whole3(dec);
     }
 

@@ -23,6 +23,7 @@ struct TrainFwdArgs {
     const int* src;
     const float* P;        // processor edge: [N][2H] = P_i (+ b1) | P_j
     const float* wstream;  // packed forward stream of this MLP
+    int wstages;           // its length in stages, the projection tail's images included when P_out is set (model.h: TStream)
     const float* bias;     // bias of Linear 1 (unused by the processor edge MLP: it sits in P_i)
     const float* bias_tail;  // biases of Linear 2 .. num_layers + 1, H apart (decoder: the last one padded to 32)
     int nl;                // num_layers: the MLP has nl + 1 Linears
@@ -50,12 +51,13 @@ struct TrainBwdArgs {
     TapePtr tape;
     const float* ln_g;
     const float* wstream;  // packed TRANSPOSED stream: [W_i^T, W_j^T (if Gi)] W_(nl+1)^T .. W_2^T [W_1^T ...]
+    int wstages;           // its length in stages, as the pack that filled it counted them (train_model.hip: PackBwd)
     float* dz;             // [nl + 1][dz_stride]: pre-activation gradients dz_l = dz + (l - 1) dz_stride of Linear l = 1 .. nl + 1, rows of H
     size_t dz_stride;      //   (the decoder's dz_(nl+1) is dY itself and is not written)
     int nl;
-    float* ln_part;        // normed MLPs: scratch [workgroups][2H] for the LayerNorm parameter gradients (column sums of gy xhat | gy)
-    float* dgamma;         //   ... which launch_train_bwd then adds, in workgroup order, to dgamma / dbeta  (nullptr: not computed)
+    float* dgamma;         // normed MLPs: the LayerNorm parameter gradients (column sums of gy xhat | gy) are added here  (nullptr: not computed)
     float* dbeta;
+    float* ln_part;        //   set by launch_train_bwd, not the caller: the batch's region [workgroups][2H] of their per-workgroup sums
     float* dx_resid;       // node: residual path; receives dY before dx adds the MLP's input gradient to it (may alias dY / dx)
     float* dx;             // edge: de_in; node: dh_in; decoder: dh; projection: dh_in
     const int* dxidx;      // edge: row of dx for row p (block API: the caller's edge order), or nullptr
@@ -84,9 +86,10 @@ int layer_stages_b3(int k, int out);      // stages of a Linear with k inputs an
 int train_kernels_init();
 int launch_train_fwd(int H, int kind, const TrainFwdArgs& a, hipStream_t s);
 struct WgradBatch;
-// wb != nullptr: the LayerNorm partial sums go to one of the batch's own regions and are reduced by its next flush (one launch with
-// the weight-gradient reductions) instead of a launch of their own -- at most kWgLnMax chains between two flushes.
-int launch_train_bwd(int H, int kind, const TrainBwdArgs& a, hipStream_t s, WgradBatch* wb = nullptr);
+// A chain with dgamma / dbeta set (normed kinds only) needs wb: its LayerNorm partial sums go to one of the batch's own regions and
+// are reduced by the batch's next flush, in one launch with the weight-gradient reductions -- at most kWgLnMax chains between two
+// flushes.  wb may be nullptr otherwise.
+int launch_train_bwd(int H, int kind, const TrainBwdArgs& a, hipStream_t s, WgradBatch* wb);
 // Weight gradients: jobs are collected and run a batch per launch pair (GEMM over row chunks + fixed-order reduction).
 //   out[m][col0 + k] += sum_r dz[r][m] * X[xidx ? xidx[r] : r][k];  db[m] += sum_r dz[r][m] (db may be nullptr)
 // A job reads its operands when the batch is FLUSHED: flush before anything overwrites them.
@@ -101,7 +104,7 @@ struct WgJob {
     size_t part_off;   // floats from the partial buffer: [G][Mp][Kp] tiles, then [G][Mp] bias partials
 };
 constexpr int kWgJobsMax = 12;
-constexpr int kWgLnMax = 2;   // backward chains whose LayerNorm partials may wait for one flush (a node chain and the edge chain after it)
+constexpr int kWgLnMax = 2;   // LayerNorm regions of a batch = normed chains between two flushes (a node chain and the edge chain after it)
 struct WgLnJob {              // dgamma[c] += sum_g part[g][c], dbeta[c] += sum_g part[g][H + c]
     const float* part;
     int G, H;
@@ -127,16 +130,14 @@ size_t wgrad_partial_floats(int H);
 int wgrad_enqueue(WgradBatch& b, const float* dz, int ldz, int M, const float* X, int ldx, int K, const int* xidx, int64_t rows, float* out,
                   int ldw, int col0, float* db);
 int wgrad_flush(WgradBatch& b);
-size_t train_bwd_ln_part_floats(int H);   // size of TrainBwdArgs.ln_part
+size_t train_bwd_ln_part_floats(int H);   // floats of one LayerNorm region
 int launch_pack_b3_batch(const PackTJobs& jobs, float* base, hipStream_t s);
-int launch_segment_sum(int H, const int* ptr, const int* perm, const float* rows, const float* scale, const float* shift, float* out,
-                       int64_t n, hipStream_t s);
-// two segment sums over the same rows in one launch (out2 = sums over ptr2 / perm2; scale / shift apply to both)
+// out = segment sums of `rows` over ptr / perm; with out2, a second set over ptr2 / perm2 in the same launch (scale / shift apply to both)
 int launch_segment_sum_pair(int H, const int* ptr, const int* perm, const int* ptr2, const int* perm2, const float* rows, const float* scale,
                             const float* shift, float* out, float* out2, int64_t n, hipStream_t s);
 int launch_swap_index(const int* src_sorted, int64_t e, int64_t* ei2, hipStream_t s);
 
-enum : int { TK_ENC_EDGE = 0, TK_ENC_NODE = 1, TK_PROC_EDGE = 2, TK_PROC_NODE = 3, TK_DEC = 4, TK_PROJ = 5 };   // TK_PROJ: out [N][2H] = h [W_i | W_j]^T + [b1 | 0]
-enum : int { TB_ENC = 0, TB_EDGE = 1, TB_NODE = 2, TB_DEC = 3, TB_PROJ = 4 };  // TB_PROJ: dx = dY + W_i^T Gi + W_j^T Gj only
+enum : int { TK_ENC_EDGE = 0, TK_ENC_NODE = 1, TK_PROC_EDGE = 2, TK_PROC_NODE = 3, TK_DEC = 4, TK_PROJ = 5, TK_KINDS = 6 };   // TK_PROJ: out [N][2H] = h [W_i | W_j]^T + [b1 | 0]
+enum : int { TB_ENC = 0, TB_EDGE = 1, TB_NODE = 2, TB_DEC = 3, TB_PROJ = 4, TB_KINDS = 5 };  // TB_PROJ: dx = dY + W_i^T Gi + W_j^T Gj only
 
 }  // namespace gm

@@ -18,7 +18,6 @@
 //
 // Tape (saved by the forward, one set per MLP): post-ReLU activations a_1 .. a_L, the normalised
 // pre-affine LayerNorm output xhat and 1/std per row; plus the block inputs h_k, e_k, agg_k.
-#include <vector>
 #include "common.h"
 #include "mlp.h"
 #include "fchain.h"
@@ -318,10 +317,22 @@ __device__ __forceinline__ void ln_param_sums(const floatx16 (&g)[NJB], const fl
 // forward with tape
 // ------------------------------------------------------------------------------------------
 
+// The next edge step's factorised layer 1 on the rows in `act`: P = [h W_i^T + b1 | h W_j^T] per node (what the inference node
+// kernels' tail does), rows row0 .. of `out` [.][ld].  acc: scratch.
+template <int H, int NJB>
+__device__ __forceinline__ void project_ij(floatx16 (&acc)[NJB], const floatx16 (&act)[NJB], const float* bias, float* out, int ld, int rows_left,
+                                           float* turn, WStream& ws, bool more, int lane, int hi) {
+    load_feat(acc, bias, hi);
+    run_layer_b3<H / 16, NJB, NJB>(acc, act, ws, more);
+    store_feat_lines(acc, out, ld, rows_left, turn, lane);
+    zero_feat(acc);
+    run_layer_b3<H / 16, NJB, NJB>(acc, act, ws, more);
+    store_feat_lines(acc, out + H, ld, rows_left, turn, lane);
+}
+
 template <int H, int KIND>
 __global__ void __launch_bounds__(THREADS, H <= 128 ? 2 : 1) train_fwd_kernel(TrainFwdArgs A) {
     constexpr int NJB = H / 32;
-    constexpr int SL = ((H / 16) * NJB + B3_STAGE_GROUPS - 1) / B3_STAGE_GROUPS;   // stages of one H x H Linear
     const int NL = A.nl;   // any num_layers >= 2 (epd_gnn.py:72-84): the hidden Linears are a run-time loop
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* ring = reinterpret_cast<float*>(smem);
@@ -333,12 +344,7 @@ __global__ void __launch_bounds__(THREADS, H <= 128 ? 2 : 1) train_fwd_kernel(Tr
     ws.base = A.wstream;
     ws.ring = ring;
     const bool proj_tail = (KIND == TK_ENC_NODE || KIND == TK_PROC_NODE) && A.P_out != nullptr;
-    ws.total = KIND == TK_ENC_EDGE ? 1 + NL * SL
-             : KIND == TK_ENC_NODE ? (2 * NJB + B3_STAGE_GROUPS - 1) / B3_STAGE_GROUPS + NL * SL + (proj_tail ? 2 * SL : 0)
-             : KIND == TK_PROC_EDGE ? (NL + 1) * SL
-             : KIND == TK_PROC_NODE ? (NL + 2) * SL + (proj_tail ? 2 * SL : 0)
-             : KIND == TK_PROJ ? 2 * SL
-                                   : NL * SL + (H / 16 + B3_STAGE_GROUPS - 1) / B3_STAGE_GROUPS;
+    ws.total = A.wstages;   // counted by the host that laid the stream out: a tile consumes exactly this many and wraps to stage 0
     ws.cur = 0;
     ws.parity = 0;
     ws.lane = lane;
@@ -365,14 +371,8 @@ __global__ void __launch_bounds__(THREADS, H <= 128 ? 2 : 1) train_fwd_kernel(Tr
             load_feat(act, A.x_in + (A.rowidx ? (int64_t)A.rowidx[pc] : pc) * H, hi);
             run_layer_b3<H / 16, NJB, NJB>(acc, act, ws, more);
         } else if (KIND == TK_PROJ) {
-            // the next edge step's factorised layer 1: P = [h W_i^T + b1 | h W_j^T] per node (what the inference node kernels' tail does)
             load_feat(act, A.x_in + pc * H, hi);
-            load_feat(acc, A.bias, hi);
-            run_layer_b3<H / 16, NJB, NJB>(acc, act, ws, more);
-            store_feat_lines(acc, A.out + (size_t)row0 * (2 * H), 2 * H, R - row0, turn, lane);
-            zero_feat(acc);
-            run_layer_b3<H / 16, NJB, NJB>(acc, act, ws, more);
-            store_feat_lines(acc, A.out + (size_t)row0 * (2 * H) + H, 2 * H, R - row0, turn, lane);
+            project_ij<H>(acc, act, A.bias, A.out + (size_t)row0 * (2 * H), 2 * H, R - row0, turn, ws, more, lane, hi);
             continue;
         } else if (KIND == TK_PROC_NODE) {
             load_feat(act, A.x_in + pc * H, hi);
@@ -425,16 +425,10 @@ __global__ void __launch_bounds__(THREADS, H <= 128 ? 2 : 1) train_fwd_kernel(Tr
                 store_feat_lines(acc, A.out + (size_t)row0 * H, H, R - row0, turn, lane);
             }
             if ((KIND == TK_ENC_NODE || KIND == TK_PROC_NODE) && proj_tail) {
-                // the next edge step's factorised layer 1 on the rows still in registers: P = [h W_i^T + b1 | h W_j^T]
-                // (what the inference node kernels' tail does; it was a launch of its own that re-read h)
+                // on the rows still in registers (it was a launch of its own that re-read h)
 #pragma unroll
                 for (int jb = 0; jb < NJB; ++jb) act[jb] = acc[jb];
-                load_feat(acc, A.proj_bias, hi);
-                run_layer_b3<H / 16, NJB, NJB>(acc, act, ws, more);
-                store_feat_lines(acc, A.P_out + (size_t)row0 * (2 * H), 2 * H, R - row0, turn, lane);
-                zero_feat(acc);
-                run_layer_b3<H / 16, NJB, NJB>(acc, act, ws, more);
-                store_feat_lines(acc, A.P_out + (size_t)row0 * (2 * H) + H, 2 * H, R - row0, turn, lane);
+                project_ij<H>(acc, act, A.proj_bias, A.P_out + (size_t)row0 * (2 * H), 2 * H, R - row0, turn, ws, more, lane, hi);
             }
         }
     }
@@ -448,7 +442,6 @@ __global__ void __launch_bounds__(THREADS, H <= 128 ? 2 : 1) train_fwd_kernel(Tr
 template <int H, int KIND>
 __global__ void __launch_bounds__(THREADS, H <= 128 ? 2 : 1) train_bwd_kernel(TrainBwdArgs A) {
     constexpr int NJB = H / 32;
-    constexpr int SL = ((H / 16) * NJB + B3_STAGE_GROUPS - 1) / B3_STAGE_GROUPS;   // stages of one H x H Linear
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* ring = reinterpret_cast<float*>(smem);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = lane & 31, hi = lane >> 5;
@@ -466,10 +459,7 @@ __global__ void __launch_bounds__(THREADS, H <= 128 ? 2 : 1) train_bwd_kernel(Tr
     WStream ws;
     ws.base = A.wstream;
     ws.ring = ring;
-    constexpr int S_IN = (H / 16 + B3_STAGE_GROUPS - 1) / B3_STAGE_GROUPS;  // W1^T of an encoder: one 32-row block of outputs
-    ws.total = (has_g ? 2 * SL : 0) +
-               (KIND == TB_ENC ? NL * SL + (A.dx_in ? S_IN : 0) : KIND == TB_EDGE ? (NL + 1) * SL : KIND == TB_NODE ? (NL + 2) * SL
-                : KIND == TB_PROJ ? 0 : 1 + NL * SL);
+    ws.total = A.wstages;   // counted by the pack that filled the slot
     ws.cur = 0;
     ws.parity = 0;
     ws.lane = lane;
@@ -779,26 +769,6 @@ __global__ void __launch_bounds__(256) wgrad_reduce_kernel(WgJobs Js, const floa
     }
 }
 
-// ------------------------------------------------------------------------------------------
-// LayerNorm parameter gradients, second stage: dgamma[c] += sum_g part[g][c], dbeta[c] += sum_g part[g][H + c]  (fixed order: deterministic)
-__global__ void __launch_bounds__(256) ln_grads_reduce_kernel(const float* __restrict__ part, int G, int H, float* __restrict__ dgamma,
-                                                               float* __restrict__ dbeta) {
-    __shared__ float red[8][33];
-    const int tid = threadIdx.x, i = tid & 31, gg = tid >> 5;
-    const int o = blockIdx.x * 32 + i;  // < 2H
-    float s = 0.f;
-    for (int g = gg; g < G; g += 8) s += part[(size_t)g * 2 * H + o];
-    red[gg][i] = s;
-    __syncthreads();
-    if (gg == 0) {
-        float t = 0.f;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) t += red[q][i];
-        if (o < H) dgamma[o] += t;
-        else dbeta[o - H] += t;
-    }
-}
-
 // bf16 x 3 operand images of many Linears in one launch (blockIdx.y = job).  A job describes a Linear with `ksub` outputs and
 // `w_rows` inputs: element (o, k) = W[o][col0 + k] (fwd) or W[k][col0 + o] (the transposed block: the weight of the backward,
 // input-gradient product dX = dZ . W).
@@ -899,70 +869,70 @@ static int grid_tiles(int64_t rows) {
     return (int)(t < 2048 ? t : 2048);
 }
 
-template <typename Kern>
-static int set_dyn_lds(Kern k, size_t bytes) {
-    GM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    return GM_OK;
-}
-
+// Every instantiation of the chain kernels, per hidden size and indexed by kind: the launchers pick from it, train_kernels_init
+// walks it.
+using FwdKern = void (*)(TrainFwdArgs);
+using BwdKern = void (*)(TrainBwdArgs);
+struct ChainKernels {
+    int H;
+    FwdKern fwd[TK_KINDS];
+    BwdKern bwd[TB_KINDS];
+};
 template <int H>
-static int launch_train_fwd_h(int kind, const TrainFwdArgs& a, hipStream_t s) {
-    const size_t lds = (size_t)2 * B3_STAGE_FLOATS * 4 + (size_t)4 * TURN_FLOATS * 4;
-    const int grid = grid_tiles(a.rows);
-    switch (kind) {
-        case TK_ENC_EDGE: hipLaunchKernelGGL((train_fwd_kernel<H, TK_ENC_EDGE>), dim3(grid), dim3(THREADS), lds, s, a); break;
-        case TK_ENC_NODE: hipLaunchKernelGGL((train_fwd_kernel<H, TK_ENC_NODE>), dim3(grid), dim3(THREADS), lds, s, a); break;
-        case TK_PROC_EDGE: hipLaunchKernelGGL((train_fwd_kernel<H, TK_PROC_EDGE>), dim3(grid), dim3(THREADS), lds, s, a); break;
-        case TK_PROC_NODE: hipLaunchKernelGGL((train_fwd_kernel<H, TK_PROC_NODE>), dim3(grid), dim3(THREADS), lds, s, a); break;
-        case TK_PROJ: hipLaunchKernelGGL((train_fwd_kernel<H, TK_PROJ>), dim3(grid), dim3(THREADS), lds, s, a); break;
-        default: hipLaunchKernelGGL((train_fwd_kernel<H, TK_DEC>), dim3(grid), dim3(THREADS), lds, s, a); break;
-    }
+static ChainKernels chain_kernels() {   // in the order of the TK_ / TB_ kinds
+    return {H,
+            {train_fwd_kernel<H, TK_ENC_EDGE>, train_fwd_kernel<H, TK_ENC_NODE>, train_fwd_kernel<H, TK_PROC_EDGE>,
+             train_fwd_kernel<H, TK_PROC_NODE>, train_fwd_kernel<H, TK_DEC>, train_fwd_kernel<H, TK_PROJ>},
+            {train_bwd_kernel<H, TB_ENC>, train_bwd_kernel<H, TB_EDGE>, train_bwd_kernel<H, TB_NODE>, train_bwd_kernel<H, TB_DEC>,
+             train_bwd_kernel<H, TB_PROJ>}};
+}
+static const ChainKernels kChainKernels[] = {chain_kernels<64>(), chain_kernels<128>(), chain_kernels<256>()};
+static const ChainKernels* chain_kernels_of(int H) {
+    for (const ChainKernels& t : kChainKernels)
+        if (t.H == H) return &t;
+    return nullptr;
+}
+// dynamic LDS: the weight ring and the line stores' turn tiles; the backward kernels' LayerNorm sums [4 waves][2 H] between them
+static size_t train_fwd_lds_bytes() { return ((size_t)2 * B3_STAGE_FLOATS + 4 * TURN_FLOATS) * 4; }
+static size_t train_bwd_lds_bytes(int H) { return train_fwd_lds_bytes() + (size_t)4 * 2 * H * 4; }
+
+int launch_train_fwd(int H, int kind, const TrainFwdArgs& a, hipStream_t s) {
+    const ChainKernels* t = chain_kernels_of(H);
+    GM_REQUIRE(t && kind >= 0 && kind < TK_KINDS, GM_ERR_INVALID_ARGUMENT, "launch_train_fwd: no kernel of kind %d at hidden %d", kind, H);
+    if (a.rows <= 0) return GM_OK;
+    GM_REQUIRE(a.wstages > 0, GM_ERR_INVALID_ARGUMENT, "launch_train_fwd: kind %d: a weight stream of %d stages", kind, a.wstages);
+    hipLaunchKernelGGL(t->fwd[kind], dim3(grid_tiles(a.rows)), dim3(THREADS), train_fwd_lds_bytes(), s, a);
     GM_LAUNCH_CHECK();
     return GM_OK;
-}
-int launch_train_fwd(int H, int kind, const TrainFwdArgs& a, hipStream_t s) {
-    if (a.rows <= 0) return GM_OK;
-    return H == 64 ? launch_train_fwd_h<64>(kind, a, s) : H == 128 ? launch_train_fwd_h<128>(kind, a, s) : launch_train_fwd_h<256>(kind, a, s);
 }
 
 size_t train_bwd_ln_part_floats(int H) { return (size_t)2 * 1024 * 2 * H; }   // workgroups of a backward launch: <= 2 per CU
 
-template <int H>
-static int launch_train_bwd_h(int kind, const TrainBwdArgs& a_in, hipStream_t s, WgradBatch* wb) {
-    const size_t lds = (size_t)2 * B3_STAGE_FLOATS * 4 + (size_t)4 * 2 * H * 4 + (size_t)4 * TURN_FLOATS * 4;
+int launch_train_bwd(int H, int kind, const TrainBwdArgs& a_in, hipStream_t s, WgradBatch* wb) {
+    const ChainKernels* t = chain_kernels_of(H);
+    GM_REQUIRE(t && kind >= 0 && kind < TB_KINDS, GM_ERR_INVALID_ARGUMENT, "launch_train_bwd: no kernel of kind %d at hidden %d", kind, H);
+    if (a_in.rows <= 0) return GM_OK;
+    GM_REQUIRE(a_in.wstages > 0, GM_ERR_INVALID_ARGUMENT, "launch_train_bwd: kind %d: a weight stream of %d stages", kind, a_in.wstages);
     int grid = grid_tiles(a_in.rows);
     TrainBwdArgs a = a_in;
-    const bool batched = wb && a.ln_part && a.dgamma && a.dbeta;
-    if (batched) {
+    a.ln_part = nullptr;
+    if (a.dgamma && a.dbeta) {   // the LayerNorm parameter gradients: summed per workgroup by the chain, reduced by the batch's next flush
+        GM_REQUIRE(wb && (kind == TB_ENC || kind == TB_EDGE || kind == TB_NODE), GM_ERR_INVALID_ARGUMENT,
+                   "launch_train_bwd: kind %d: LayerNorm parameter gradients need a normed kind and a weight-gradient batch", kind);
         GM_REQUIRE(wb->jobs.n_ln < kWgLnMax, GM_ERR_INVALID_ARGUMENT, "launch_train_bwd: flush the weight-gradient batch first");
-        a.ln_part = wb->ln_region(wb->jobs.n_ln);
-    }
-    const bool ln = a.ln_part && (kind == TB_ENC || kind == TB_EDGE || kind == TB_NODE);
-    if (ln) {
         // as many workgroups as are resident at once, each walking its tiles: one partial row of the LayerNorm parameter sums each
         const int resident = device_cus() * (H <= 128 ? 2 : 1);
         if (grid > resident) grid = resident;
         GM_REQUIRE((size_t)grid * 2 * H <= train_bwd_ln_part_floats(H), GM_ERR_WORKSPACE, "launch_train_bwd: %d workgroups", grid);
+        a.ln_part = wb->ln_region(wb->jobs.n_ln);
     }
-    switch (kind) {
-        case TB_ENC: hipLaunchKernelGGL((train_bwd_kernel<H, TB_ENC>), dim3(grid), dim3(THREADS), lds, s, a); break;
-        case TB_EDGE: hipLaunchKernelGGL((train_bwd_kernel<H, TB_EDGE>), dim3(grid), dim3(THREADS), lds, s, a); break;
-        case TB_NODE: hipLaunchKernelGGL((train_bwd_kernel<H, TB_NODE>), dim3(grid), dim3(THREADS), lds, s, a); break;
-        case TB_PROJ: hipLaunchKernelGGL((train_bwd_kernel<H, TB_PROJ>), dim3(grid), dim3(THREADS), lds, s, a); break;
-        default: hipLaunchKernelGGL((train_bwd_kernel<H, TB_DEC>), dim3(grid), dim3(THREADS), lds, s, a); break;
-    }
-    if (ln && batched) {
+    hipLaunchKernelGGL(t->bwd[kind], dim3(grid), dim3(THREADS), train_bwd_lds_bytes(H), s, a);
+    if (a.ln_part) {
         WgLnJob& Lj = wb->jobs.ln[wb->jobs.n_ln++];
         Lj.part = a.ln_part; Lj.G = grid; Lj.H = H; Lj.dgamma = a.dgamma; Lj.dbeta = a.dbeta;
-    } else if (ln && a.dgamma && a.dbeta) {
-        hipLaunchKernelGGL(ln_grads_reduce_kernel, dim3(2 * H / 32), dim3(256), 0, s, a.ln_part, grid, H, a.dgamma, a.dbeta);
     }
     GM_LAUNCH_CHECK();
     return GM_OK;
-}
-int launch_train_bwd(int H, int kind, const TrainBwdArgs& a, hipStream_t s, WgradBatch* wb) {
-    if (a.rows <= 0) return GM_OK;
-    return H == 64 ? launch_train_bwd_h<64>(kind, a, s, wb) : H == 128 ? launch_train_bwd_h<128>(kind, a, s, wb) : launch_train_bwd_h<256>(kind, a, s, wb);
 }
 
 // Row chunks of a batch.  All jobs of a flush share one chunk length, chosen so that the whole batch is two rounds of resident
@@ -1065,10 +1035,6 @@ int launch_segment_sum_pair(int H, const int* ptr, const int* perm, const int* p
     GM_LAUNCH_CHECK();
     return GM_OK;
 }
-int launch_segment_sum(int H, const int* ptr, const int* perm, const float* rows, const float* scale, const float* shift, float* out,
-                       int64_t n, hipStream_t s) {
-    return launch_segment_sum_pair(H, ptr, perm, nullptr, nullptr, rows, scale, shift, out, nullptr, n, s);
-}
 
 int launch_swap_index(const int* src_sorted, int64_t e, int64_t* ei2, hipStream_t s) {
     if (e <= 0) return GM_OK;
@@ -1080,23 +1046,13 @@ int launch_swap_index(const int* src_sorted, int64_t e, int64_t* ei2, hipStream_
 int train_kernels_init() {
     static PerDeviceOnce done_dev;
     return done_dev.run([]() -> int {
-    const size_t lds = (size_t)2 * B3_STAGE_FLOATS * 4 + (size_t)4 * 2 * 256 * 4 + (size_t)4 * TURN_FLOATS * 4;   // weight ring + the backward kernels' LayerNorm sums + the line stores' turn tiles
-    int rc = GM_OK;
-#define GM_SET(k) if (rc == GM_OK) rc = set_dyn_lds(k, lds)
-    GM_SET((train_fwd_kernel<64, TK_ENC_EDGE>)); GM_SET((train_fwd_kernel<64, TK_ENC_NODE>)); GM_SET((train_fwd_kernel<64, TK_PROC_EDGE>));
-    GM_SET((train_fwd_kernel<64, TK_PROC_NODE>)); GM_SET((train_fwd_kernel<64, TK_DEC>)); GM_SET((train_fwd_kernel<64, TK_PROJ>));
-    GM_SET((train_fwd_kernel<128, TK_PROJ>)); GM_SET((train_fwd_kernel<256, TK_PROJ>));
-    GM_SET((train_bwd_kernel<64, TB_ENC>)); GM_SET((train_bwd_kernel<64, TB_EDGE>)); GM_SET((train_bwd_kernel<64, TB_NODE>)); GM_SET((train_bwd_kernel<64, TB_DEC>));
-    GM_SET((train_bwd_kernel<64, TB_PROJ>));
-    GM_SET((train_fwd_kernel<128, TK_ENC_EDGE>)); GM_SET((train_fwd_kernel<128, TK_ENC_NODE>)); GM_SET((train_fwd_kernel<128, TK_PROC_EDGE>));
-    GM_SET((train_fwd_kernel<128, TK_PROC_NODE>)); GM_SET((train_fwd_kernel<128, TK_DEC>));
-    GM_SET((train_fwd_kernel<256, TK_ENC_EDGE>)); GM_SET((train_fwd_kernel<256, TK_ENC_NODE>)); GM_SET((train_fwd_kernel<256, TK_PROC_EDGE>));
-    GM_SET((train_fwd_kernel<256, TK_PROC_NODE>)); GM_SET((train_fwd_kernel<256, TK_DEC>));
-    GM_SET((train_bwd_kernel<128, TB_ENC>)); GM_SET((train_bwd_kernel<128, TB_EDGE>)); GM_SET((train_bwd_kernel<128, TB_NODE>)); GM_SET((train_bwd_kernel<128, TB_DEC>));
-    GM_SET((train_bwd_kernel<128, TB_PROJ>)); GM_SET((train_bwd_kernel<256, TB_PROJ>));
-    GM_SET((train_bwd_kernel<256, TB_ENC>)); GM_SET((train_bwd_kernel<256, TB_EDGE>)); GM_SET((train_bwd_kernel<256, TB_NODE>)); GM_SET((train_bwd_kernel<256, TB_DEC>));
-#undef GM_SET
-    return rc;
+        for (const ChainKernels& t : kChainKernels) {
+            for (FwdKern k : t.fwd)
+                GM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)train_fwd_lds_bytes()));
+            for (BwdKern k : t.bwd)
+                GM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)train_bwd_lds_bytes(t.H)));
+        }
+        return GM_OK;
     });
 }
 

@@ -116,6 +116,10 @@ InTape carve_in_tape(void* ws, int H, int NL, int64_t n, int64_t e) {
     return t;
 }
 
+// One backward chain's slot of BwdWs::packT: where its transposed stream starts, the stages the sizing walk reserved for it and
+// the stages the last pack put there -- which is what the chain launched on it walks (0: nothing packed, the launch refuses)
+struct Slot { size_t off = 0; int cap = 0, stages = 0; };
+
 struct BwdWs {
     float *packT, *dz, *dzn, *de, *dh, *dagg, *Gi, *Gj, *part;
     float* go;          // the upstream gradient as the chains read it: zero when the forward's edge_index was flagged (gate_grad_out_kernel)
@@ -125,31 +129,102 @@ struct BwdWs {
     // weight-gradient jobs over an edge chain's dz and those over the node chain's that follows run as ONE batch
     size_t dzn_stride;
     float* dznl(int l) const { return dzn + (size_t)(l - 1) * dzn_stride; }
-    // slots of packT, one per backward chain's transposed stream (filled by PackBwd); off_proj: W_i^T, W_j^T of one step, which the
-    // node encoder's chain reads in front of its own images (off_enc_node) and a block's projection backward alone
-    size_t off_dec, off_proj, off_enc_edge, off_enc_node;
-    std::vector<size_t> off_edge, off_node;
+    // slots of packT, one per backward chain (PackBwd)
+    Slot dec, enc_edge, enc_node;
+    std::vector<Slot> edge, node;
     size_t bytes;
+};
+
+// The transposed images of the backward chains, each MLP's Linears in the order its chain consumes them: the one place that knows
+// what a slot of BwdWs::packT holds.  With a model (m, T) it queues the pack jobs of the slots it is asked for and counts the
+// stages it puts in each.  Without one (carve_bwd, which asks for every optional part) the same walk only lays the slots out, back
+// to back.  k: the step whose tensors are packed; j: its slot (a block's is 0).
+struct PackBwd {
+    const gm_model_desc& d;
+    BwdWs& b;
+    const gm_model* m;   // nullptr: the sizing walk
+    const float* const* T;
+    hipStream_t s;
+    const int H = d.hidden_size, NL = d.num_layers;
+    PackTJobs jobs{};
+    int rc = GM_OK;
+    size_t laid = 0;     // sizing walk: floats of packT laid out so far
+    int flush() {   // also when a batch is full
+        if (rc == GM_OK && jobs.n > 0) rc = launch_pack_b3_batch(jobs, b.packT, s);
+        jobs.n = 0;
+        return rc;
+    }
+    // what only the real pack looks up: Linear l of MLP i (gm_model::mlp), the first column of block c (gm_model::ci ..) of a Linear 1
+    const float* W(int i, int l) const { return m ? T[m->mlp[i].base + 2 * l] : nullptr; }
+    int col(int gm_model::*c) const { return m ? m->*c * H : 0; }
+    Slot& begin(Slot& sl) { if (m) sl.stages = 0; else sl = {laid, 0, 0}; return sl; }
+    void job(Slot& sl, const float* W, int w_rows, int ld, int col0, int ksub) {
+        const int st = layer_stages_b3(w_rows, ksub);
+        if (!m) { sl.cap += st; laid = sl.off + (size_t)sl.cap * kStageFloatsB3; return; }
+        if (rc == GM_OK) rc = [&]() -> int {
+            GM_REQUIRE(sl.stages + st <= sl.cap, GM_ERR_WORKSPACE, "backward pack: %d stages into a slot laid out for %d", sl.stages + st, sl.cap);
+            return GM_OK;
+        }();
+        if (rc != GM_OK) return;
+        if (jobs.n == kPackTJobsMax) flush();
+        PackTJob& j = jobs.job[jobs.n++];
+        j.W = W; j.w_rows = w_rows; j.ld = ld; j.col0 = col0; j.ksub = ksub; j.fwd = 0;
+        j.dst_off = sl.off + (size_t)sl.stages * kStageFloatsB3;
+        sl.stages += st;
+    }
+    // the hidden Linears NL + 1 .. 2 of MLP i
+    void hidden(Slot& sl, int i) { for (int l = NL; l >= 1; --l) job(sl, W(i, l), H, H, 0, H); }
+    void ij(Slot& sl, int k) {   // W_i, W_j: the column blocks of step k's first edge Linear that multiply h_i, h_j
+        job(sl, W(2 + 2 * k, 0), H, 3 * H, col(&gm_model::ci), H);
+        job(sl, W(2 + 2 * k, 0), H, 3 * H, col(&gm_model::cj), H);
+    }
+    // an encoder (MLP i).  ij: in front, step 0's W_i^T, W_j^T (the model's node encoder: its chain also takes that step's Gi / Gj);
+    // input: behind, W_1^T for the gradient w.r.t. the raw features (block API)
+    void enc(Slot& slot, int i, int k1, bool with_ij, bool input) {
+        Slot& sl = begin(slot);
+        if (with_ij) ij(sl, 0);
+        hidden(sl, i);
+        if (input) job(sl, W(i, 0), H, k1, 0, k1);
+    }
+    void dec() {
+        const int i = 2 + 2 * d.m_steps;
+        Slot& sl = begin(b.dec);
+        job(sl, W(i, NL), d.out_dim, H, 0, H);
+        for (int l = NL - 1; l >= 0; --l) job(sl, W(i, l), H, H, 0, H);
+    }
+    void edge(int k, int j) {
+        Slot& sl = begin(b.edge[j]);
+        hidden(sl, 2 + 2 * k);
+        job(sl, W(2 + 2 * k, 0), H, 3 * H, col(&gm_model::ce), H);
+    }
+    void node(int k, int j) {
+        Slot& sl = begin(b.node[j]);
+        if (j + 1 < (int)b.node.size()) ij(sl, k + 1);   // a step with a next one: its chain also takes that step's Gi / Gj
+        hidden(sl, 3 + 2 * k);
+        job(sl, W(3 + 2 * k, 0), H, 2 * H, col(&gm_model::ch), H);
+        job(sl, W(3 + 2 * k, 0), H, 2 * H, col(&gm_model::ca), H);
+    }
+    // a block's projection backward: step k's W_i^T, W_j^T alone, in the node encoder's slot (which a block's backward does not use)
+    void proj(int k) { ij(begin(b.enc_node), k); }
+    void enc_node(bool with_ij, bool input) { enc(b.enc_node, 1, d.node_dim, with_ij, input); }
+    void enc_edge(bool input) { enc(b.enc_edge, 0, d.edge_dim, false, input); }
 };
 
 BwdWs carve_bwd(void* ws, const gm_model_desc* d, int64_t n, int64_t e) {
     BwdWs b;
     const int H = d->hidden_size, M = d->m_steps, NL = d->num_layers;
-    const size_t U = (size_t)layer_stages_b3(H, H) * kStageFloatsB3;  // one HxH unit
-    size_t off = 0;
-    b.off_dec = off; off += (size_t)layer_stages_b3(d->out_dim, H) * kStageFloatsB3 + (size_t)NL * U;
-    b.off_edge.resize(M);
-    b.off_node.resize(M);
+    b.edge.resize(M);
+    b.node.resize(M);
+    PackBwd lay{*d, b, nullptr, nullptr, nullptr};
+    lay.dec();
     for (int k = 0; k < M; ++k) {
-        b.off_node[k] = off; off += (k + 1 < M ? 2 * U : 0) + (size_t)(NL + 2) * U;
-        b.off_edge[k] = off; off += (size_t)(NL + 1) * U;
+        lay.node(k, k);
+        lay.edge(k, k);
     }
-    const size_t UIN = (size_t)layer_stages_b3(H, 32) * kStageFloatsB3;  // W1^T of an encoder (input gradient, block API)
-    b.off_proj = off; off += 2 * U;
-    b.off_enc_node = off; off += (size_t)NL * U + UIN;
-    b.off_enc_edge = off; off += (size_t)NL * U + UIN;
+    lay.enc_node(true, true);
+    lay.enc_edge(true);
     Carver c(ws);
-    b.packT = c.take<float>(off);
+    b.packT = c.take<float>(lay.laid);
     const int64_t R = n > e ? n : e;
     b.dz_stride = align_up((size_t)R * H, 64);
     b.dz = c.take<float>((size_t)(NL + 1) * b.dz_stride);
@@ -172,60 +247,6 @@ BwdWs carve_block_bwd(void* ws, const gm_model_desc* d, int64_t n, int64_t e) {
     return carve_bwd(ws, &d1, n, e);
 }
 
-// Queues the transposed images of the backward chains into the slots of BwdWs::packT, each MLP's Linears in the order its chain
-// consumes them: the one place that knows what a slot holds.  k: the step whose tensors are packed; j: its slot (a block's is 0).
-struct PackBwd {
-    const gm_model* m;
-    const float* const* T;
-    const BwdWs& b;
-    hipStream_t s;
-    PackTJobs jobs{};
-    int rc = GM_OK;
-    int flush() {   // also when a batch is full
-        if (rc == GM_OK && jobs.n > 0) rc = launch_pack_b3_batch(jobs, b.packT, s);
-        jobs.n = 0;
-        return rc;
-    }
-    void job(const float* W, int w_rows, int ld, int col0, int ksub, size_t& off) {
-        if (jobs.n == kPackTJobsMax) flush();
-        PackTJob& j = jobs.job[jobs.n++];
-        j.W = W; j.w_rows = w_rows; j.ld = ld; j.col0 = col0; j.ksub = ksub; j.fwd = 0; j.dst_off = off;
-        off += (size_t)layer_stages_b3(w_rows, ksub) * kStageFloatsB3;
-    }
-    // the hidden Linears NL + 1 .. 2 of the MLP whose first tensor is `base`
-    void hidden(int base, size_t& off) { for (int l = m->NL; l >= 1; --l) job(T[base + 2 * l], m->H, m->H, 0, m->H, off); }
-    void ij(int k, size_t& off) {   // W_i, W_j: the column blocks of step k's first edge Linear that multiply h_i, h_j
-        job(T[m->edge_mlp(k).base], m->H, 3 * m->H, m->ci * m->H, m->H, off);
-        job(T[m->edge_mlp(k).base], m->H, 3 * m->H, m->cj * m->H, m->H, off);
-    }
-    // input: W_1^T as well, for the gradient w.r.t. the raw features (block API)
-    void enc(int base, size_t off, int k1, bool input) {
-        hidden(base, off);
-        if (input) job(T[base], m->H, k1, 0, k1, off);
-    }
-    void dec() {
-        const int H = m->H, bd = m->mlp.back().base;
-        size_t off = b.off_dec;
-        job(T[bd + 2 * m->NL], m->d.out_dim, H, 0, H, off);
-        for (int l = m->NL - 1; l >= 0; --l) job(T[bd + 2 * l], H, H, 0, H, off);
-    }
-    void edge(int k, int j) {
-        size_t off = b.off_edge[j];
-        hidden(m->edge_mlp(k).base, off);
-        job(T[m->edge_mlp(k).base], m->H, 3 * m->H, m->ce * m->H, m->H, off);
-    }
-    void node(int k, int j) {
-        size_t off = b.off_node[j];
-        if (j + 1 < (int)b.off_node.size()) ij(k + 1, off);   // a step with a next one: its chain also takes that step's Gi / Gj
-        hidden(m->node_mlp(k).base, off);
-        job(T[m->node_mlp(k).base], m->H, 2 * m->H, m->ch * m->H, m->H, off);
-        job(T[m->node_mlp(k).base], m->H, 2 * m->H, m->ca * m->H, m->H, off);
-    }
-    void proj(int k) { size_t off = b.off_proj; ij(k, off); }
-    void enc_node(bool input) { enc(m->mlp[1].base, b.off_enc_node, m->d.node_dim, input); }
-    void enc_edge(bool input) { enc(m->mlp[0].base, b.off_enc_edge, m->d.edge_dim, input); }
-};
-
 // The launches of one backward call after its images are packed.  Every call does nothing once rc holds an error.
 struct BwdRun {
     const gm_model* m;
@@ -241,10 +262,11 @@ struct BwdRun {
                int col0, float* db) {
         if (rc == GM_OK) rc = wgrad_enqueue(wb, dz, ldz, Mo, X, ldx, K, xidx, rows, out, ldw, col0, db);
     }
-    // flush: the chain overwrites operands of the waiting jobs.  w: the batch that takes the chain's LayerNorm partials (or none)
-    void launch(int kind, const TrainBwdArgs& a, bool flush, WgradBatch* w) {
+    // sl: the slot the chain's stream was packed into.  flush: the chain overwrites operands of the waiting jobs
+    void launch(int kind, TrainBwdArgs a, const Slot& sl, bool flush) {
+        a.wstream = b.packT + sl.off; a.wstages = sl.stages;
         if (rc == GM_OK && flush) rc = wgrad_flush(wb);
-        if (rc == GM_OK) rc = launch_train_bwd(m->H, kind, a, s, w);
+        if (rc == GM_OK) rc = launch_train_bwd(m->H, kind, a, s, &wb);
     }
     // dW = dz_(l+1)^T a_l (+ the bias) of Linears l + 1 = top + 1 .. 2 of the MLP whose chain `a` just ran
     void tail(const TrainBwdArgs& a, int base, int top) {
@@ -252,19 +274,19 @@ struct BwdRun {
             wgrad(a.dz + (size_t)l * a.dz_stride, m->H, m->H, a.tape.a + (size_t)(l - 1) * a.rows * m->H, m->H, m->H, nullptr, a.rows,
                   grads[base + 2 * l], m->H, 0, grads[base + 2 * l + 1]);
     }
-    // the LayerNorm and dz fields of a normed MLP's chain: its LayerNorm parameter gradients are summed inside the chain kernel;
-    // node_set: dz goes to the node-sized set (BwdWs::dzn), which no waiting job reads
+    // the LayerNorm and dz fields of a normed MLP's chain: its LayerNorm parameter gradients are summed inside the chain kernel and
+    // reduced by wb's next flush; node_set: dz goes to the node-sized set (BwdWs::dzn), which no waiting job reads
     void set_normed(TrainBwdArgs& a, int base, size_t voff, bool node_set) const {
         const int NL = m->NL;
         a.ln_g = m->vec + voff + (size_t)(NL + 1) * m->H;
-        a.ln_part = b.part; a.dgamma = grads[base + 2 * (NL + 1)]; a.dbeta = grads[base + 2 * (NL + 1) + 1];
+        a.dgamma = grads[base + 2 * (NL + 1)]; a.dbeta = grads[base + 2 * (NL + 1) + 1];
         a.dz = node_set ? b.dzn : b.dz; a.dz_stride = node_set ? b.dzn_stride : b.dz_stride; a.nl = NL;
     }
     // a normed MLP's chain and the weight gradients of its Linears 2 .. NL + 1 (Linear 1's differ at every call site).  A chain
     // that writes the edge-sized dz set flushes first; one that writes the node-sized set adds its jobs to the waiting ones.
-    void chain(int kind, TrainBwdArgs a, int base, size_t voff, bool node_set) {
+    void chain(int kind, TrainBwdArgs a, const Slot& sl, int base, size_t voff, bool node_set) {
         set_normed(a, base, voff, node_set);
-        launch(kind, a, !node_set, &wb);
+        launch(kind, a, sl, !node_set);
         tail(a, base, m->NL);
     }
     // node-level sums of an edge chain's dz_1 (G_i over each edge's destination, G_j over its source): everything the factorised
@@ -323,6 +345,10 @@ int ready_to_launch(const gm_model* m, size_t tape_bytes, size_t tape_need, size
     return weights_ready_on(m, s);   // the weight streams may have been packed on another stream (model.h)
 }
 
+// the MLP's forward stream; tail: the chain runs on into the next step's [W_i | W_j] behind it (TrainFwdArgs::P_out)
+void set_stream(const gm_model* m, TrainFwdArgs& a, const TStream& t, bool tail) {
+    a.wstream = m->packed_t3 + t.off; a.wstages = tail ? t.stages_tail : t.stages;
+}
 void set_normed(const gm_model* m, TrainFwdArgs& a, size_t voff) {
     const float* v = m->vec + voff;
     const int H = m->H, NL = m->NL;
@@ -334,12 +360,12 @@ void set_normed(const gm_model* m, TrainFwdArgs& a, size_t voff) {
 int fwd_encoders(const gm_model* m, int64_t n, int64_t e, const float* x, const float* edge_attr, const int* rowidx, const EncTape& t,
                  float* h_out, float* e_out, float* P, hipStream_t s) {
     TrainFwdArgs ea{};
-    ea.rows = (int)e; ea.x_in = edge_attr; ea.rowidx = rowidx; ea.k1 = m->d.edge_dim; ea.wstream = m->packed_t3 + m->t_enc_edge;
-    set_normed(m, ea, m->v_enc_edge);
+    ea.rows = (int)e; ea.x_in = edge_attr; ea.rowidx = rowidx; ea.k1 = m->d.edge_dim;
+    set_stream(m, ea, m->t_enc_edge, false); set_normed(m, ea, m->v_enc_edge);
     ea.tape = t.ee; ea.out = e_out;
     TrainFwdArgs na{};
-    na.rows = (int)n; na.x_in = x; na.k1 = m->d.node_dim; na.wstream = m->packed_t3 + m->t_enc_node;
-    set_normed(m, na, m->v_enc_node);
+    na.rows = (int)n; na.x_in = x; na.k1 = m->d.node_dim;
+    set_stream(m, na, m->t_enc_node, P != nullptr); set_normed(m, na, m->v_enc_node);
     na.tape = t.en; na.out = h_out;
     if (P) { na.P_out = P; na.proj_bias = m->vec + m->v_edge[0]; }
     int rc = launch_train_fwd(m->H, TK_ENC_EDGE, ea, s);
@@ -352,17 +378,17 @@ int fwd_encoders(const gm_model* m, int64_t n, int64_t e, const float* x, const 
 int fwd_step(const gm_model* m, int k, const CsrWs& c, int64_t n, int64_t e, const float* h, const float* e_in, float* P,
              const StepTape& st, float* h_out, float* e_out, const int* rowidx, int residual, bool tail, hipStream_t s) {
     TrainFwdArgs ea{};
-    ea.rows = (int)e; ea.x_in = e_in; ea.rowidx = rowidx; ea.dst = c.dst; ea.src = c.src; ea.P = P; ea.wstream = m->packed_t3 + m->t_edge[k];
-    set_normed(m, ea, m->v_edge[k]);
+    ea.rows = (int)e; ea.x_in = e_in; ea.rowidx = rowidx; ea.dst = c.dst; ea.src = c.src; ea.P = P;
+    set_stream(m, ea, m->t_edge[k], false); set_normed(m, ea, m->v_edge[k]);
     ea.tape = st.te; ea.out = e_out; ea.residual = residual;
     TrainFwdArgs na{};
-    na.rows = (int)n; na.x_in = h; na.agg = st.agg; na.wstream = m->packed_t3 + m->t_node[k];
-    set_normed(m, na, m->v_node[k]);
+    na.rows = (int)n; na.x_in = h; na.agg = st.agg;
+    set_stream(m, na, m->t_node[k], tail); set_normed(m, na, m->v_node[k]);
     na.tape = st.tn; na.out = h_out; na.residual = residual;
     if (tail) { na.P_out = P; na.proj_bias = m->vec + m->v_edge[k + 1]; }
     int rc = launch_train_fwd(m->H, TK_PROC_EDGE, ea, s);
     // agg_i = sum over edges into i of e' = gamma * sum xhat + deg * beta
-    if (rc == GM_OK) rc = launch_segment_sum(m->H, c.in_ptr, nullptr, st.te.xhat, ea.ln_g, ea.ln_b, st.agg, n, s);
+    if (rc == GM_OK) rc = launch_segment_sum_pair(m->H, c.in_ptr, nullptr, nullptr, nullptr, st.te.xhat, ea.ln_g, ea.ln_b, st.agg, nullptr, n, s);
     if (rc == GM_OK) rc = launch_train_fwd(m->H, TK_PROC_NODE, na, s);
     return rc;
 }
@@ -402,7 +428,7 @@ int gm_epd_forward_train(const gm_model* m, const float* nodes, int64_t n, const
     }
     {
         TrainFwdArgs a{};
-        a.rows = (int)n; a.x_in = t.h[M]; a.wstream = m->packed_t3 + m->t_dec;
+        a.rows = (int)n; a.x_in = t.h[M]; set_stream(m, a, m->t_dec, false);
         a.bias = m->vec + m->v_dec; a.bias_tail = a.bias + m->H; a.nl = m->NL;
         a.tape = t.dec; a.out = out; a.out_dim = m->d.out_dim;
         rc = launch_train_fwd(m->H, TK_DEC, a, s);
@@ -435,14 +461,13 @@ int gm_epd_backward(const gm_model* m, const float* const* T, int n_tensors, con
     const CsrWs& c = t.csr.dst;
 
     // ---- transposed operand images of every Linear on the backward path (batched: a few launches)
-    PackBwd pk{m, T, b, s};
+    PackBwd pk{m->d, b, m, T, s};
     pk.dec();
     for (int k = 0; k < M; ++k) {
         pk.node(k, k);
         pk.edge(k, k);
     }
-    pk.proj(0);
-    pk.enc_node(false);
+    pk.enc_node(true, false);
     pk.enc_edge(false);
     rc = pk.flush();
     if (rc != GM_OK) return rc;
@@ -457,9 +482,9 @@ int gm_epd_backward(const gm_model* m, const float* const* T, int n_tensors, con
     {
         const int bd = m->mlp.back().base;
         TrainBwdArgs a{};
-        a.rows = (int)n; a.dY = b.go; a.out_dim = OD; a.tape = t.dec; a.wstream = b.packT + b.off_dec;
+        a.rows = (int)n; a.dY = b.go; a.out_dim = OD; a.tape = t.dec;
         a.dz = b.dz; a.dz_stride = b.dz_stride; a.nl = NL; a.dx = b.dh;
-        bw.launch(TB_DEC, a, true, nullptr);
+        bw.launch(TB_DEC, a, b.dec, true);
         bw.wgrad(b.go, OD, OD, t.dec.a + (size_t)(NL - 1) * n * H, H, H, nullptr, n, grads[bd + 2 * NL], H, 0, grads[bd + 2 * NL + 1]);
         bw.tail(a, bd, NL - 1);
         bw.wgrad(b.dzl(1), H, H, t.h[M], H, H, nullptr, n, grads[bd], H, 0, grads[bd + 1]);
@@ -471,17 +496,17 @@ int gm_epd_backward(const gm_model* m, const float* const* T, int n_tensors, con
         {
             TrainBwdArgs a{};
             a.rows = (int)n; a.dY = b.dh; a.Gi = has_next ? b.Gi : nullptr; a.Gj = has_next ? b.Gj : nullptr; a.tape = t.step[k].tn;
-            a.wstream = b.packT + b.off_node[k]; a.dx_resid = b.dh; a.dx = b.dh; a.dagg_out = b.dagg;
+            a.dx_resid = b.dh; a.dx = b.dh; a.dagg_out = b.dagg;
             // node-sized dz set: the waiting jobs read the edge-sized one, Gi / Gj and tapes -- nothing this chain writes
-            bw.chain(TB_NODE, a, bn, m->v_node[k], true);
+            bw.chain(TB_NODE, a, b.node[k], bn, m->v_node[k], true);
             bw.wgrad(b.dznl(1), H, H, t.h[k], H, H, nullptr, n, grads[bn], 2 * H, m->ch * H, grads[bn + 1]);
             bw.wgrad(b.dznl(1), H, H, t.step[k].agg, H, H, nullptr, n, grads[bn], 2 * H, m->ca * H, nullptr);
         }
         {
             TrainBwdArgs a{};
             a.rows = (int)e; a.dY = has_next ? b.de : nullptr; a.dagg = b.dagg; a.dst = c.dst; a.tape = t.step[k].te;
-            a.wstream = b.packT + b.off_edge[k]; a.dx = b.de; a.residual = 1;
-            bw.chain(TB_EDGE, a, be, m->v_edge[k], false);
+            a.dx = b.de; a.residual = 1;
+            bw.chain(TB_EDGE, a, b.edge[k], be, m->v_edge[k], false);
             bw.wgrad(b.dzl(1), H, H, t.e[k], H, H, nullptr, e, grads[be], 3 * H, m->ce * H, grads[be + 1]);
             bw.ij_grads(t.csr, t.h[k], be, n);
         }
@@ -489,16 +514,16 @@ int gm_epd_backward(const gm_model* m, const float* const* T, int n_tensors, con
     // ---- encoders
     {
         TrainBwdArgs a{};
-        a.rows = (int)n; a.dY = b.dh; a.Gi = b.Gi; a.Gj = b.Gj; a.tape = t.enc.en; a.wstream = b.packT + b.off_proj;
+        a.rows = (int)n; a.dY = b.dh; a.Gi = b.Gi; a.Gj = b.Gj; a.tape = t.enc.en;
         const int bn = m->mlp[1].base;
-        bw.chain(TB_ENC, a, bn, m->v_enc_node, true);   // as the node MLPs
+        bw.chain(TB_ENC, a, b.enc_node, bn, m->v_enc_node, true);   // as the node MLPs
         bw.wgrad(b.dznl(1), H, H, nodes, m->d.node_dim, m->d.node_dim, nullptr, n, grads[bn], m->d.node_dim, 0, grads[bn + 1]);
     }
     if (e > 0) {
         TrainBwdArgs a{};
-        a.rows = (int)e; a.dY = b.de; a.tape = t.enc.ee; a.wstream = b.packT + b.off_enc_edge;
+        a.rows = (int)e; a.dY = b.de; a.tape = t.enc.ee;
         const int be = m->mlp[0].base;
-        bw.chain(TB_ENC, a, be, m->v_enc_edge, false);
+        bw.chain(TB_ENC, a, b.enc_edge, be, m->v_enc_edge, false);
         bw.wgrad(b.dzl(1), H, H, edge_attr, m->d.edge_dim, m->d.edge_dim, c.eid, e, grads[be], m->d.edge_dim, 0, grads[be + 1]);
     }
     return bw.finish();
@@ -548,20 +573,20 @@ int gm_graph_independent_backward(const gm_model* m, const float* const* T, int 
     rc = ready_to_launch(m, tape_bytes, t.bytes, ws_bytes, b.bytes, s, __func__);
     if (rc != GM_OK) return rc;
     BwdRun bw(m, grads, b, s);
-    PackBwd pk{m, T, b, s};
-    pk.enc_node(dx != nullptr);
+    PackBwd pk{m->d, b, m, T, s};
+    pk.enc_node(false, dx != nullptr);
     pk.enc_edge(dedge_attr != nullptr);
     rc = pk.flush();
     if (rc != GM_OK) return rc;
-    auto run = [&](int base, const TapePtr& tp, int64_t rows, const float* dY, size_t voff, size_t woff, const float* X, int k1, float* dxin) {
+    auto run = [&](int base, const TapePtr& tp, int64_t rows, const float* dY, size_t voff, const Slot& sl, const float* X, int k1, float* dxin) {
         if (rows <= 0) return;
         TrainBwdArgs a{};
-        a.rows = (int)rows; a.dY = dY; a.tape = tp; a.wstream = b.packT + woff; a.dx_in = dxin; a.k1 = k1;
-        bw.chain(TB_ENC, a, base, voff, false);
+        a.rows = (int)rows; a.dY = dY; a.tape = tp; a.dx_in = dxin; a.k1 = k1;
+        bw.chain(TB_ENC, a, sl, base, voff, false);
         bw.wgrad(b.dzl(1), H, H, X, k1, k1, nullptr, rows, grads[base], k1, 0, grads[base + 1]);
     };
-    run(en.base, t.enc.en, n, dh, m->v_enc_node, b.off_enc_node, x, m->d.node_dim, dx);
-    run(ee.base, t.enc.ee, e, de, m->v_enc_edge, b.off_enc_edge, edge_attr, m->d.edge_dim, dedge_attr);
+    run(en.base, t.enc.en, n, dh, m->v_enc_node, b.enc_node, x, m->d.node_dim, dx);
+    run(ee.base, t.enc.ee, e, de, m->v_enc_edge, b.enc_edge, edge_attr, m->d.edge_dim, dedge_attr);
     return bw.finish();
 }
 
@@ -580,7 +605,7 @@ int gm_interaction_network_forward_train(const gm_model* m, int k, const float* 
     if (rc != GM_OK) return rc;
     {
         TrainFwdArgs pa{};   // P = [h W_i^T + b1 | h W_j^T] of this block's edge MLP
-        pa.rows = (int)n; pa.x_in = h; pa.bias = m->vec + m->v_edge[k]; pa.out = t.P; pa.nl = m->NL; pa.wstream = m->packed_t3 + m->t_proj[k];
+        pa.rows = (int)n; pa.x_in = h; pa.bias = m->vec + m->v_edge[k]; pa.out = t.P; pa.nl = m->NL; set_stream(m, pa, m->t_proj[k], false);
         rc = launch_train_fwd(m->H, TK_PROJ, pa, s);
         if (rc != GM_OK) return rc;
     }
@@ -606,7 +631,7 @@ int gm_interaction_network_backward(const gm_model* m, int k, const float* const
     if (rc != GM_OK) return rc;
     BwdRun bw(m, grads, b, s);
     const CsrWs& c = t.csr.dst;
-    PackBwd pk{m, T, b, s};
+    PackBwd pk{m->d, b, m, T, s};
     pk.node(k, 0);
     pk.edge(k, 0);
     pk.proj(k);
@@ -615,23 +640,23 @@ int gm_interaction_network_backward(const gm_model* m, int k, const float* const
     // node MLP: dY = dh_out (no residual inside the block); dx = W_h^T dz1 -> b.dh, dagg -> b.dagg
     {
         TrainBwdArgs a{};
-        a.rows = (int)n; a.dY = dh_out; a.tape = t.st.tn; a.wstream = b.packT + b.off_node[0]; a.dx = b.dh; a.dagg_out = b.dagg;
-        bw.chain(TB_NODE, a, bn, m->v_node[k], false);
+        a.rows = (int)n; a.dY = dh_out; a.tape = t.st.tn; a.dx = b.dh; a.dagg_out = b.dagg;
+        bw.chain(TB_NODE, a, b.node[0], bn, m->v_node[k], false);
         bw.wgrad(b.dzl(1), H, H, h, H, H, nullptr, n, grads[bn], 2 * H, m->ch * H, grads[bn + 1]);
         bw.wgrad(b.dzl(1), H, H, t.st.agg, H, H, nullptr, n, grads[bn], 2 * H, m->ca * H, nullptr);
     }
     if (e > 0) {
         TrainBwdArgs a{};
-        a.rows = (int)e; a.dY = de_out; a.dyidx = c.eid; a.dagg = b.dagg; a.dst = c.dst; a.tape = t.st.te; a.wstream = b.packT + b.off_edge[0];
+        a.rows = (int)e; a.dY = de_out; a.dyidx = c.eid; a.dagg = b.dagg; a.dst = c.dst; a.tape = t.st.te;
         a.dx = de_in; a.dxidx = c.eid;
-        bw.chain(TB_EDGE, a, be, m->v_edge[k], false);
+        bw.chain(TB_EDGE, a, b.edge[0], be, m->v_edge[k], false);
         bw.wgrad(b.dzl(1), H, H, e_in, H, H, c.eid, e, grads[be], 3 * H, m->ce * H, grads[be + 1]);
     }
     bw.ij_grads(t.csr, h, be, n);
     // dh_in = W_h^T dz1 (node MLP) + W_i^T G_i + W_j^T G_j (edge MLP, factorised layer 1)
     TrainBwdArgs a{};
-    a.rows = (int)n; a.dY = b.dh; a.Gi = b.Gi; a.Gj = b.Gj; a.wstream = b.packT + b.off_proj; a.dx = dh_in;
-    bw.launch(TB_PROJ, a, true, nullptr);
+    a.rows = (int)n; a.dY = b.dh; a.Gi = b.Gi; a.Gj = b.Gj; a.dx = dh_in;
+    bw.launch(TB_PROJ, a, b.enc_node, true);
     return bw.rc;
 }
 

@@ -3,7 +3,7 @@ forward and loss 1e-5; every parameter gradient within max(GRAD_TOL, 4 x PyTorch
 oracle/torch_epd.py relative to the tensor's maximum, relu_flip_allowance as the only fallback).
 
 A. More than one tile per workgroup.  train_bwd_kernel with a LayerNorm is launched with at most CUs x (2 at hidden <= 128, else 1)
-   workgroups of 128 rows (csrc/train.hip: launch_train_bwd_h); train_fwd_kernel and the other backward kinds with at most 2048
+   workgroups of 128 rows (csrc/train.hip: launch_train_bwd); train_fwd_kernel and the other backward kinds with at most 2048
    (grid_tiles).  Past that a workgroup walks several tiles: it restarts the weight-stream ring, re-uses its LDS turn and keeps
    adding into its LayerNorm parameter sums.  Every case asserts from the device's CU count that it is past the limit it is there
    for, so it cannot pass without entering its regime.  At these sizes the weight-gradient chunk length (wgrad_flush) is hundreds
