@@ -823,7 +823,8 @@ int gm_rollout(const gm_model* m, float* obs, int64_t n, const gm_feature_desc* 
         // traj_utils.py:126-134: steps past the scripted trajectory keep the rigid body where it is (control = 0 displacement)
         const float* target = i < n_targets ? rigid_targets + (size_t)i * n_rigid * 3 : nullptr;
         if (record_last) {  // the reference records the last frame after the control overwrite (rollout_utils.py:49, traj_utils.py:137)
-            int rc = gm_state_pre(state, n, fd, rank, target, stream);
+            // a descriptor without control columns has nothing to overwrite: the record is the last frame as it stands
+            int rc = fd->control_col >= 0 ? gm_state_pre(state, n, fd, rank, target, stream) : GM_OK;
             if (rc != GM_OK) return rc;
             if (total) rc = gm::renumber_scatter(last, record_last + (size_t)i * frame, 1, n, fd->data_dim, total, hs);
             else GM_HIP_CHECK(hipMemcpyAsync(record_last + (size_t)i * frame, last, frame * sizeof(float), hipMemcpyDeviceToDevice, hs));

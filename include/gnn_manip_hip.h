@@ -134,6 +134,10 @@ int gm_node_features(const float* obs, int64_t n_nodes, const gm_feature_desc* d
  * gm_integrate     replaces get_position_from_prediction  gnn_manip/utils/rollout_utils.py:145-158
  * gm_state_pre     replaces rollout_utils.py:40-47 == traj_utils.py:126-134: control columns of the
  *                  rigid rows (material == 1) of the last frame <- rigid_target - current xyz.
+ *                  A descriptor without control columns (control_col < 0) has nothing to overwrite:
+ *                  called on its own, gm_state_pre rejects it (GM_ERR_INVALID_ARGUMENT); gm_rollout_step
+ *                  and gm_rollout skip the overwrite, and gm_rollout's record is then the last frame
+ *                  as it stands.
  * gm_state_post    replaces rollout_utils.py:53-61 == traj_utils.py:146-152: window shift, write
  *                  p_{t+1}, overwrite rigid rows' xyz with the scripted pose.
  * rigid_target: [N_rigid,3] poses in rigid-row order; rigid_rank: int32[N] = rank of row among

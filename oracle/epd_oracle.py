@@ -473,6 +473,8 @@ def rollout(params, obs0, trajectory, horizon, stats, bounds, conn_r, cartesian_
             forward_fn=None):
     """cma_objective's loop (traj_utils.py:119-152).  obs0: [k, N, D] float32.
 
+    control_idx=None: a state without control columns (GraphBoundedMultimaterial) -- no control overwrite, the record is the last
+    frame as it stands; rigid rows still take the scripted pose.
     Returns the final state [k, N, D] (and per-step last-frame records if asked).
     ``forward_fn(nodes, edge_attr, edge_index)`` defaults to the oracle's epd_forward.
     """
@@ -480,7 +482,7 @@ def rollout(params, obs0, trajectory, horizon, stats, bounds, conn_r, cartesian_
     mat_col = material_idx[0]
     rigid = obs[-1][:, mat_col] == 1
     ci = list(cartesian_idx)
-    ui = list(control_idx)
+    ui = None if control_idx is None else list(control_idx)   # None: no control columns (GraphBoundedMultimaterial)
     recs = []
     if forward_fn is None:
         def forward_fn(n, ea, ei):
@@ -488,7 +490,9 @@ def rollout(params, obs0, trajectory, horizon, stats, bounds, conn_r, cartesian_
     for i in range(horizon):
         new_rigid = obs[-1][rigid].copy()
         cur = obs[-1][rigid][:, ci]
-        if i >= trajectory.shape[0]:
+        if ui is None:
+            pass  # nothing to overwrite; rigid rows still take the scripted pose below
+        elif i >= trajectory.shape[0]:
             new_rigid[:, ui] = cur  # traj_utils.py:130-131
         else:
             new_rigid[:, ui] = trajectory[i] - cur  # traj_utils.py:133

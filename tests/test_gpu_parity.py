@@ -2,6 +2,11 @@
 
 Integer / index results are compared bit-exactly.  Float32 tolerances are written at each check:
 the north_star bar is 1e-5 relative on the predicted accelerations.
+
+Every model here is (node_dim, edge_dim, out_dim) = (25, 4, 3) and every feature descriptor the default one (k_steps 6, data_dim 8,
+positions 2..4, material 1, control 5..7).  Other widths and layouts -- and the stand-alone gm_state_pre / gm_state_post,
+gm_radius_graph_build and gm_csr_from_graph entry points -- are in tests/test_gpu_widths.py (cases: tests/width_cases.py, their CPU
+side: tests/test_width_cases.py), at the bars of this file.
 """
 import numpy as np
 import pytest

@@ -48,7 +48,9 @@ def _graph(n, side, seed):
     return nodes, ea, np.stack((s, r))
 
 
-def _check(m, params, nodes, ea, ei, dims, dev, seed):
+def _check(m, params, nodes, ea, ei, dims, dev, seed, ref=None):
+    """ref: a dict that receives the target and the float64 / float32 reference gradients (target, ref_g, g32), for a caller that
+    looks at single tensors afterwards."""
     rng = np.random.default_rng(seed)
     target = rng.standard_normal((nodes.shape[0], dims[2])).astype(np.float32)
     out = m.forward(_t(nodes, dev), _t(ea, dev), _t(ei, dev))
@@ -58,6 +60,8 @@ def _check(m, params, nodes, ea, ei, dims, dev, seed):
     _, _, g32 = torch_epd.loss_and_grads(params, nodes, ea, ei, target, dims[4], dims[5], torch.float32)
     assert np.abs(out.detach().cpu().numpy() - ref_out).max() <= 1e-5 * max(np.abs(ref_out).max(), 1e-3)
     assert abs(float(loss.detach()) - ref_loss) <= 1e-5 * abs(ref_loss)
+    if ref is not None:
+        ref.update(target=target, ref_g=ref_g, g32=g32)
     return _compare_gradients(m, params, nodes, ea, ei, target, dims[4], dims[5], ref_g, g32)
 
 
