@@ -61,6 +61,10 @@ PROTOTYPES = {
     "gm_edge_features_csr": (_i32, [_vp, _i64, _vp, _i64, _i64, _f32, _vp, _vp]),
     "gm_node_features": (_i32, [_vp, _i64, _FD, _vp, _vp]),
     "gm_integrate": (_i32, [_vp, _vp, _i64, _FD, _vp, _vp]),
+    "gm_edge_features_backward_workspace_bytes": (_sz, [_i64, _i64]),
+    "gm_edge_features_backward": (_i32, [_vp, _i64, _vp, _vp, _i64, _i64, _f32, _vp, _vp, _vp, _sz, _vp]),
+    "gm_node_features_backward": (_i32, [_vp, _i64, _FD, _vp, _vp, _vp]),
+    "gm_integrate_backward": (_i32, [_vp, _i64, _FD, _vp, _vp, _vp]),
     "gm_rigid_rank": (_i32, [_vp, _i64, _FD, _vp, _vp, _vp]),
     "gm_state_pre": (_i32, [_vp, _i64, _FD, _vp, _vp, _vp]),
     "gm_state_post": (_i32, [_vp, _i64, _FD, _vp, _vp, _vp, _vp]),
@@ -78,6 +82,8 @@ PROTOTYPES = {
     "gm_train_backward_workspace_bytes": (_sz, [_MD, _i64, _i64]),
     "gm_epd_forward_train": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _sz, _vp]),
     "gm_epd_backward": (_i32, [_vp, _vp, _i32, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "gm_train_backward_inputs_workspace_bytes": (_sz, [_MD, _i64, _i64]),
+    "gm_epd_backward_inputs": (_i32, [_vp, _vp, _i32, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
     "gm_block_tape_bytes": (_sz, [_MD, _i32, _i64, _i64]),
     "gm_block_backward_workspace_bytes": (_sz, [_MD, _i64, _i64]),
     "gm_graph_independent_forward_train": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),

@@ -344,6 +344,152 @@ int rollout_integrate_post(float* obs, int64_t n, const gm_feature_desc* d, cons
     return GM_OK;
 }
 
+
+// ---- backward of the per-step functions (differentiable rollout step).  Each output is written in full, by one thread per row:
+// no atomics, the same bits every time.
+
+// transpose of node_features_kernel: d_obs[k][n][D] from d_out[n][F]
+__global__ void __launch_bounds__(256) node_features_bwd_kernel(const float* __restrict__ obs, int64_t n, FeatParams P,
+                                                                 const float* __restrict__ g, float* __restrict__ d_obs) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int F = 3 * (P.k - 1) + 7 + (P.ctrl >= 0 ? 3 : 0);
+    const float* gi = g + i * F;
+    const int64_t fs = n * P.D;
+    float* row = d_obs + i * P.D;
+    for (int t = 0; t < P.k; ++t)
+        for (int d = 0; d < P.D; ++d) row[t * fs + d] = 0.f;
+    // velocity t (frames t, t + 1): +g / vel_std on frame t + 1, -g / vel_std on frame t
+    for (int t = 0; t < P.k; ++t) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            float v = 0.f;
+            if (t >= 1) v = __fdiv_rn(gi[(t - 1) * 3 + a], P.vs[a]);
+            if (t + 1 < P.k) v = __fsub_rn(v, __fdiv_rn(gi[t * 3 + a], P.vs[a]));
+            row[t * fs + P.cart + a] = v;
+        }
+    }
+    const float* b = gi + 3 * (P.k - 1);
+    const float* last_in = obs + (int64_t)(P.k - 1) * fs + i * P.D;
+    float* last = row + (int64_t)(P.k - 1) * fs;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        // the forward's own unclamped values; the gradient passes where they lie in [-1, 1] (torch.clamp's rule)
+        const float cur = last_in[P.cart + a];
+        const float l = __fdiv_rn(__fsub_rn(cur, P.lo[a]), P.r);
+        const float u = __fdiv_rn(__fsub_rn(P.hi[a], cur), P.r);
+        float v = last[P.cart + a];
+        if (l >= -1.f && l <= 1.f) v = __fadd_rn(v, __fdiv_rn(b[a], P.r));
+        if (u >= -1.f && u <= 1.f) v = __fsub_rn(v, __fdiv_rn(b[3 + a], P.r));
+        last[P.cart + a] = v;
+    }
+    if (P.ctrl >= 0) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) last[P.ctrl + a] = __fdiv_rn(b[7 + a], P.vs[a]);
+    }
+}
+
+// transpose of integrate_kernel: next = 2 l1 - l2 + pred * acc_std + acc_mean
+__global__ void __launch_bounds__(256) integrate_bwd_kernel(const float* __restrict__ g, int64_t n, FeatParams P,
+                                                             float* __restrict__ d_pred, float* __restrict__ d_obs) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int64_t fs = n * P.D;
+    float* row = d_obs + i * P.D;
+    for (int t = 0; t < P.k; ++t)
+        for (int d = 0; d < P.D; ++d) row[t * fs + d] = 0.f;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float ga = g[i * 3 + a];
+        d_pred[i * 3 + a] = __fmul_rn(ga, P.as[a]);
+        row[(int64_t)(P.k - 1) * fs + P.cart + a] = __fmul_rn(2.f, ga);
+        row[(int64_t)(P.k - 2) * fs + P.cart + a] = -ga;
+    }
+}
+
+// edge_index [2][e] of the two sorts from the caller's separate rows
+__global__ void __launch_bounds__(256) edge_pair_kernel(const int64_t* __restrict__ snd, const int64_t* __restrict__ rcv, int64_t e,
+                                                         int64_t* __restrict__ ei) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= e) return;
+    ei[i] = snd[i];
+    ei[e + i] = rcv[i];
+}
+
+// per edge, in the caller's order: the gradient on p_s, (g[0:3] + g[3] d / |d|) / r with d = (p_s - p_r) / r; 0 for the norm's
+// term where |d| = 0 (torch.norm's subgradient).  An edge with an index out of range contributes nothing (the sorts leave it out).
+__global__ void __launch_bounds__(256) edge_features_bwd_edge_kernel(const float* __restrict__ pos, int64_t stride,
+                                                                      const int64_t* __restrict__ snd, const int64_t* __restrict__ rcv,
+                                                                      int64_t n, int64_t e, float cr, const float* __restrict__ g,
+                                                                      float* __restrict__ ge) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= e) return;
+    const int64_t s = snd[i], r = rcv[i];
+    float o[3] = {0.f, 0.f, 0.f};
+    if (s >= 0 && s < n && r >= 0 && r < n) {
+        float d[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) d[a] = __fdiv_rn(__fsub_rn(pos[s * stride + a], pos[r * stride + a]), cr);
+        float q = __fmul_rn(d[0], d[0]);
+        q = __fadd_rn(q, __fmul_rn(d[1], d[1]));
+        q = __fadd_rn(q, __fmul_rn(d[2], d[2]));
+        const float nrm = __fsqrt_rn(q);
+        const float4 gv = *reinterpret_cast<const float4*>(g + i * 4);
+        const float gg[3] = {gv.x, gv.y, gv.z};
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            float v = gg[a];
+            if (nrm > 0.f) v = __fadd_rn(v, __fdiv_rn(__fmul_rn(gv.w, d[a]), nrm));
+            o[a] = __fdiv_rn(v, cr);
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) ge[i * 3 + a] = o[a];
+}
+
+// per node: + the edges it sends (segments of the sort by sender), - the edges it receives (segments of the sort by receiver),
+// each segment in ascending edge id (the sorts' own order): fixed order, no atomics
+__global__ void __launch_bounds__(256) edge_features_bwd_node_kernel(const int* __restrict__ snd_ptr, const int* __restrict__ snd_eid,
+                                                                      const int* __restrict__ rcv_ptr, const int* __restrict__ rcv_eid,
+                                                                      const float* __restrict__ ge, int64_t n, float* __restrict__ d_pos) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float acc[3] = {0.f, 0.f, 0.f};
+    for (int p = snd_ptr[i], p1 = snd_ptr[i + 1]; p < p1; ++p) {
+        const float* v = ge + (int64_t)snd_eid[p] * 3;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) acc[a] = __fadd_rn(acc[a], v[a]);
+    }
+    for (int p = rcv_ptr[i], p1 = rcv_ptr[i + 1]; p < p1; ++p) {
+        const float* v = ge + (int64_t)rcv_eid[p] * 3;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) acc[a] = __fsub_rn(acc[a], v[a]);
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) d_pos[i * 3 + a] = acc[a];
+}
+
+// workspace of gm_edge_features_backward: the [2][e] index the sorts read, the sort by receiver (flow 0) and by sender (flow 1),
+// the per-edge gradients
+struct EdgeBwdWs {
+    int64_t* ei;
+    char *csr_rcv, *csr_snd;
+    size_t csr_bytes;
+    float* ge;
+    size_t bytes;
+};
+static EdgeBwdWs carve_edge_bwd(void* ws, int64_t n, int64_t e) {
+    EdgeBwdWs w;
+    Carver c(ws);
+    w.ei = c.take<int64_t>((size_t)2 * e);
+    w.csr_bytes = gm_csr_workspace_bytes(n, e);
+    w.csr_rcv = c.take<char>(w.csr_bytes);
+    w.csr_snd = c.take<char>(w.csr_bytes);
+    w.ge = c.take<float>((size_t)3 * e);
+    w.bytes = c.used();
+    return w;
+}
+
 }  // namespace gm
 
 using namespace gm;
@@ -450,6 +596,67 @@ int gm_rigid_transform(const float* rigid_init, int64_t nr, const float* cst, in
     GM_REQUIRE(rigid_init && cst && out, GM_ERR_INVALID_ARGUMENT, "gm_rigid_transform: null pointer");
     hipLaunchKernelGGL(rigid_transform_kernel, dim3((unsigned)cdiv(nr * steps, 256)), dim3(256), 0, (hipStream_t)stream,
                        rigid_init, nr, cst, steps, ty_init[0], ty_init[1], ty_init[2], out);
+    GM_LAUNCH_CHECK();
+    return GM_OK;
+}
+
+
+size_t gm_edge_features_backward_workspace_bytes(int64_t n, int64_t e) {
+    if (n < 0 || e < 0) return 0;
+    return carve_edge_bwd(nullptr, n, e).bytes;
+}
+
+int gm_edge_features_backward(const float* pos, int64_t pos_stride, const int64_t* senders, const int64_t* receivers, int64_t n,
+                              int64_t e, float conn_r, const float* d_out, float* d_pos, void* ws, size_t ws_bytes, void* stream) {
+    gm::DevGuard dev_guard(d_pos);
+    GM_REQUIRE(n >= 0 && e >= 0 && n < ((int64_t)1 << 31) && e < ((int64_t)1 << 31) / 4, GM_ERR_INVALID_ARGUMENT,
+               "gm_edge_features_backward: sizes out of range");
+    GM_REQUIRE(n == 0 || d_pos, GM_ERR_INVALID_ARGUMENT, "gm_edge_features_backward: null pointer");
+    GM_REQUIRE(e == 0 || (pos && senders && receivers && d_out && ws), GM_ERR_INVALID_ARGUMENT, "gm_edge_features_backward: null pointer");
+    GM_REQUIRE(conn_r > 0.f && pos_stride >= 3, GM_ERR_INVALID_ARGUMENT, "gm_edge_features_backward: bad conn_r / stride");
+    if (n == 0) return GM_OK;
+    hipStream_t s = (hipStream_t)stream;
+    if (e == 0) {
+        GM_HIP_CHECK(hipMemsetAsync(d_pos, 0, (size_t)n * 3 * sizeof(float), s));
+        return GM_OK;
+    }
+    EdgeBwdWs w = carve_edge_bwd(ws, n, e);
+    GM_REQUIRE(ws_bytes >= w.bytes, GM_ERR_WORKSPACE, "gm_edge_features_backward: workspace %zu < %zu", ws_bytes, w.bytes);
+    const unsigned eb = (unsigned)cdiv(e, 256);
+    hipLaunchKernelGGL(edge_pair_kernel, dim3(eb), dim3(256), 0, s, senders, receivers, e, w.ei);
+    hipLaunchKernelGGL(edge_features_bwd_edge_kernel, dim3(eb), dim3(256), 0, s, pos, pos_stride, senders, receivers, n, e, conn_r, d_out,
+                       w.ge);
+    GM_LAUNCH_CHECK();
+    int rc = gm::csr_from_edge_index(w.ei, n, e, 0, w.csr_rcv, w.csr_bytes, false, s);
+    if (rc == GM_OK) rc = gm::csr_from_edge_index(w.ei, n, e, 1, w.csr_snd, w.csr_bytes, false, s);
+    if (rc != GM_OK) return rc;
+    const CsrWs cr = carve_csr(w.csr_rcv, n, e), cs = carve_csr(w.csr_snd, n, e);
+    hipLaunchKernelGGL(edge_features_bwd_node_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, s, cs.in_ptr, cs.eid, cr.in_ptr, cr.eid,
+                       w.ge, n, d_pos);
+    GM_LAUNCH_CHECK();
+    return GM_OK;
+}
+
+int gm_node_features_backward(const float* obs, int64_t n, const gm_feature_desc* desc, const float* d_out, float* d_obs, void* stream) {
+    gm::DevGuard dev_guard(obs);
+    FeatParams P;
+    int rc = to_params(desc, &P, "gm_node_features_backward");
+    if (rc != GM_OK) return rc;
+    GM_REQUIRE(n >= 0 && (n == 0 || (obs && d_out && d_obs)), GM_ERR_INVALID_ARGUMENT, "gm_node_features_backward: null pointer");
+    if (n == 0) return GM_OK;
+    hipLaunchKernelGGL(node_features_bwd_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, obs, n, P, d_out, d_obs);
+    GM_LAUNCH_CHECK();
+    return GM_OK;
+}
+
+int gm_integrate_backward(const float* d_next_pos, int64_t n, const gm_feature_desc* desc, float* d_pred, float* d_obs, void* stream) {
+    gm::DevGuard dev_guard(d_next_pos);
+    FeatParams P;
+    int rc = to_params(desc, &P, "gm_integrate_backward");
+    if (rc != GM_OK) return rc;
+    GM_REQUIRE(n >= 0 && (n == 0 || (d_next_pos && d_pred && d_obs)), GM_ERR_INVALID_ARGUMENT, "gm_integrate_backward: null pointer");
+    if (n == 0) return GM_OK;
+    hipLaunchKernelGGL(integrate_bwd_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, d_next_pos, n, P, d_pred, d_obs);
     GM_LAUNCH_CHECK();
     return GM_OK;
 }

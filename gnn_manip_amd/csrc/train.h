@@ -60,7 +60,7 @@ struct TrainBwdArgs {
     float* ln_part;        //   set by launch_train_bwd, not the caller: the batch's region [workgroups][2H] of their per-workgroup sums
     float* dx_resid;       // node: residual path; receives dY before dx adds the MLP's input gradient to it (may alias dY / dx)
     float* dx;             // edge: de_in; node: dh_in; decoder: dh; projection: dh_in
-    const int* dxidx;      // edge: row of dx for row p (block API: the caller's edge order), or nullptr
+    const int* dxidx;      // edge: row of dx for row p (block API: the caller's edge order), or nullptr; encoders: row of dx_in for row p
     float* dx_in;          // encoders: gradient w.r.t. the raw input rows [rows][k1], or nullptr (then the chain stops at dz1)
     int k1;
     float* dagg_out;       // node: [rows][H]

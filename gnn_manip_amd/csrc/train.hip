@@ -526,10 +526,12 @@ __global__ void __launch_bounds__(THREADS, H <= 128 ? 2 : 1) train_bwd_kernel(Tr
                 zero_feat(o);
                 run_layer_b3<H / 16, 1, NJB, H / 8>(o, act, ws, more);
                 if (valid) {
+                    // dxidx: the input row of row pc (the fused model's edge encoder walks destination-sorted rows: a permutation)
+                    float* xr = A.dx_in + (A.dxidx ? (int64_t)A.dxidx[pc] : pc) * A.k1;
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         const int f = 8 * (r >> 2) + 4 * hi + (r & 3);
-                        if (f < A.k1) A.dx_in[pc * A.k1 + f] = o[0][r];
+                        if (f < A.k1) xr[f] = o[0][r];
                     }
                 }
             }

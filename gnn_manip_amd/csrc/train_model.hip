@@ -442,20 +442,22 @@ int gm_epd_forward_train(const gm_model* m, const float* nodes, int64_t n, const
     return GM_OK;
 }
 
-int gm_epd_backward(const gm_model* m, const float* const* T, int n_tensors, const float* nodes, const float* edge_attr, int64_t n,
-                    int64_t e, const float* grad_out, float* const* grads, void* tape, size_t tape_bytes, void* ws, size_t ws_bytes,
-                    void* stream) {
-    int rc = check_model(m, n, e, __func__);
+// The whole model's backward.  d_nodes / d_edge_attr (either may be null): the encoders' chains run on through W_1^T into the raw
+// input rows (TrainBwdArgs::dx_in); the parameter gradients are the same launches on the same operands either way.
+static int epd_backward(const gm_model* m, const float* const* T, int n_tensors, const float* nodes, const float* edge_attr, int64_t n,
+                        int64_t e, const float* grad_out, float* const* grads, float* d_nodes, float* d_edge_attr, void* tape,
+                        size_t tape_bytes, void* ws, size_t ws_bytes, void* stream, const char* who) {
+    int rc = check_model(m, n, e, who);
     if (rc != GM_OK) return rc;
-    GM_REQUIRE(T && grads && nodes && grad_out && tape && ws && (e == 0 || edge_attr), GM_ERR_INVALID_ARGUMENT, "%s: null pointer", __func__);
-    rc = check_tensors(m, T, grads, n_tensors, 0, n_tensors, __func__);
+    GM_REQUIRE(T && grads && nodes && grad_out && tape && ws && (e == 0 || edge_attr), GM_ERR_INVALID_ARGUMENT, "%s: null pointer", who);
+    rc = check_tensors(m, T, grads, n_tensors, 0, n_tensors, who);
     if (rc != GM_OK) return rc;
     gm::DevGuard dev_guard(nodes);
     hipStream_t s = (hipStream_t)stream;
     const int H = m->H, NL = m->NL, M = m->M, OD = m->d.out_dim;
     Tape t = carve_tape(tape, &m->d, n, e);
     BwdWs b = carve_bwd(ws, &m->d, n, e);
-    rc = ready_to_launch(m, tape_bytes, t.bytes, ws_bytes, b.bytes, s, __func__);
+    rc = ready_to_launch(m, tape_bytes, t.bytes, ws_bytes, b.bytes, s, who);
     if (rc != GM_OK) return rc;
     BwdRun bw(m, grads, b, s);
     const CsrWs& c = t.csr.dst;
@@ -467,8 +469,8 @@ int gm_epd_backward(const gm_model* m, const float* const* T, int n_tensors, con
         pk.node(k, k);
         pk.edge(k, k);
     }
-    pk.enc_node(true, false);
-    pk.enc_edge(false);
+    pk.enc_node(true, d_nodes != nullptr);
+    pk.enc_edge(d_edge_attr != nullptr);
     rc = pk.flush();
     if (rc != GM_OK) return rc;
 
@@ -515,6 +517,7 @@ int gm_epd_backward(const gm_model* m, const float* const* T, int n_tensors, con
     {
         TrainBwdArgs a{};
         a.rows = (int)n; a.dY = b.dh; a.Gi = b.Gi; a.Gj = b.Gj; a.tape = t.enc.en;
+        a.dx_in = d_nodes; a.k1 = m->d.node_dim;
         const int bn = m->mlp[1].base;
         bw.chain(TB_ENC, a, b.enc_node, bn, m->v_enc_node, true);   // as the node MLPs
         bw.wgrad(b.dznl(1), H, H, nodes, m->d.node_dim, m->d.node_dim, nullptr, n, grads[bn], m->d.node_dim, 0, grads[bn + 1]);
@@ -522,11 +525,32 @@ int gm_epd_backward(const gm_model* m, const float* const* T, int n_tensors, con
     if (e > 0) {
         TrainBwdArgs a{};
         a.rows = (int)e; a.dY = b.de; a.tape = t.enc.ee;
+        a.dx_in = d_edge_attr; a.k1 = m->d.edge_dim; a.dxidx = c.eid;   // sorted row p came from the caller's row eid[p]: a permutation
         const int be = m->mlp[0].base;
         bw.chain(TB_ENC, a, b.enc_edge, be, m->v_enc_edge, false);
         bw.wgrad(b.dzl(1), H, H, edge_attr, m->d.edge_dim, m->d.edge_dim, c.eid, e, grads[be], m->d.edge_dim, 0, grads[be + 1]);
     }
     return bw.finish();
+}
+
+int gm_epd_backward(const gm_model* m, const float* const* T, int n_tensors, const float* nodes, const float* edge_attr, int64_t n,
+                    int64_t e, const float* grad_out, float* const* grads, void* tape, size_t tape_bytes, void* ws, size_t ws_bytes,
+                    void* stream) {
+    return epd_backward(m, T, n_tensors, nodes, edge_attr, n, e, grad_out, grads, nullptr, nullptr, tape, tape_bytes, ws, ws_bytes, stream,
+                        __func__);
+}
+
+// carve_bwd lays every slot out with its optional parts, the encoders' transposed W_1 images among them: the same carve serves
+size_t gm_train_backward_inputs_workspace_bytes(const gm_model_desc* desc, int64_t n, int64_t e) {
+    if (!desc || n < 0 || e < 0) return 0;
+    return carve_bwd(nullptr, desc, n, e).bytes;
+}
+
+int gm_epd_backward_inputs(const gm_model* m, const float* const* T, int n_tensors, const float* nodes, const float* edge_attr, int64_t n,
+                           int64_t e, const float* grad_out, float* const* grads, float* d_nodes, float* d_edge_attr, void* tape,
+                           size_t tape_bytes, void* ws, size_t ws_bytes, void* stream) {
+    return epd_backward(m, T, n_tensors, nodes, edge_attr, n, e, grad_out, grads, d_nodes, d_edge_attr, tape, tape_bytes, ws, ws_bytes,
+                        stream, __func__);
 }
 
 

@@ -10,7 +10,7 @@ operand image of them (re-packed when a parameter changes) and runs the fused HI
 Block semantics (the torch_graphnet source is absent from the reference tree; fixed by
 BASELINE.json north_star, see DESIGN.md): j = edge_index[0] (source), i = edge_index[1] (target);
 e' = phi_e(cat[h_i, h_j, e]); agg_i = sum_{e -> i} e'; h' = phi_v(cat[h, agg]); no residual inside
-the block.  ``EncProcDecGNN.forward`` is differentiable w.r.t. every parameter (``train_dyn.py``:
+the block.  ``EncProcDecGNN.forward`` is differentiable w.r.t. every parameter and both inputs (``train_dyn.py``:
 forward with an activation tape + hand-written HIP backward, see csrc/train.hip), and so are the two
 standalone blocks (parameters and inputs), so the reference's own
 ``EncProcDecGNN`` wiring trains with them as well.
@@ -421,8 +421,9 @@ def _run_block(handle, desc, k, x, edge_attr, edge_index, csr=None):
 
 class _EpdTrainFunction(torch.autograd.Function):
     """``EncProcDecGNN.forward`` under autograd (examples/train_dyn.py:45-72): the forward records the
-    activation tape in one device buffer, the backward is gm_epd_backward.  Gradients are produced for the
-    parameters only; nodes / edge_attr / edge_index are data.  `spec` = (model descriptor tuple, _Handle): the module's own, or
+    activation tape in one device buffer, the backward is gm_epd_backward -- or, when nodes / edge_attr require grad (a
+    differentiable rollout step, a frozen model in a planning loop), gm_epd_backward_inputs, which runs the same launches and lets
+    the encoders' chains go on into d_nodes / d_edge_attr.  edge_index is data.  `spec` = (model descriptor tuple, _Handle): the module's own, or
     -- for a hidden size between the training kernels' widths -- the zero-padded model's (EncProcDecGNN._padded_training), with
     the module's own parameters as the third element: the tensors whose versions say when the padded copies are stale."""
 
@@ -454,11 +455,20 @@ class _EpdTrainFunction(torch.autograd.Function):
         dev = nodes.device
         grad_out = grad_out.contiguous().float()
         tensors, views, t_arr, g_arr = _grad_arrays(params, dev)
-        ws = _ws(L.gm_train_backward_workspace_bytes(C.byref(ctx.desc), n, e), dev)
-        check(L.gm_epd_backward(ctx.handle, t_arr, len(tensors), ptr(nodes), ptr(edge_attr), n, e, ptr(grad_out), g_arr,
-                                ptr(ctx.tape), ctx.tape.numel(), ptr(ws), ws.numel(), current_stream()))
+        d_nodes = d_edge_attr = None
+        if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
+            d_nodes = torch.empty_like(nodes) if ctx.needs_input_grad[2] else None
+            d_edge_attr = torch.empty_like(edge_attr) if ctx.needs_input_grad[3] else None
+            ws = _ws(L.gm_train_backward_inputs_workspace_bytes(C.byref(ctx.desc), n, e), dev)
+            check(L.gm_epd_backward_inputs(ctx.handle, t_arr, len(tensors), ptr(nodes), ptr(edge_attr), n, e, ptr(grad_out), g_arr,
+                                           ptr(d_nodes), ptr(d_edge_attr), ptr(ctx.tape), ctx.tape.numel(), ptr(ws), ws.numel(),
+                                           current_stream()))
+        else:
+            ws = _ws(L.gm_train_backward_workspace_bytes(C.byref(ctx.desc), n, e), dev)
+            check(L.gm_epd_backward(ctx.handle, t_arr, len(tensors), ptr(nodes), ptr(edge_attr), n, e, ptr(grad_out), g_arr,
+                                    ptr(ctx.tape), ctx.tape.numel(), ptr(ws), ws.numel(), current_stream()))
         ctx.tape = None
-        return (None, None, None, None, None) + tuple(views)
+        return (None, None, d_nodes, d_edge_attr, None) + tuple(views)
 
 
 TRAIN_WIDTHS = (64, 128, 256)   # hidden sizes the training kernels are instantiated for (csrc/train.hip)
@@ -609,11 +619,10 @@ class EncProcDecGNN(nn.Module):
         if edge_index.shape[1] != e:
             raise ValueError("edge_index and edge_attr disagree on the number of edges")
         params = list(self.parameters())
-        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
-            # training (examples/train_dyn.py:45-72): forward with tape, HIP backward
-            if nodes.requires_grad or edge_attr.requires_grad:
-                raise NotImplementedError("EncProcDecGNN: gradients w.r.t. nodes / edge_attr are not produced "
-                                          "(they are data in train_dyn.py); detach them")
+        if _wants_grad(params, nodes, edge_attr):
+            # training (examples/train_dyn.py:45-72): forward with tape, HIP backward.  Inputs that require grad get their gradient
+            # too (gm_epd_backward_inputs) -- also with every parameter frozen, a planning loop on a trained model: the result then
+            # still carries grad_fn (the parameter gradients are computed and dropped).
             # edge_index entries outside [0, n) are flagged on the device by the forward's destination sort (and left out; the
             # kernels stay inside their arrays): no blocking range check here -- a training loop queues its steps ahead of the GPU.
             # The flag surfaces as GMError at a later forward (auto_status) or at status(), like the inference path's.  Until it

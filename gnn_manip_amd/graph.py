@@ -72,9 +72,40 @@ def get_connectivity(pos_nodes, conn_r, max_neighbours=20, nodes_per_graph=None)
     return RadiusGraph(pos_nodes, conn_r, max_neighbours, nodes_per_graph).edges()
 
 
+class _EdgeFeaturesFunction(torch.autograd.Function):
+    """get_edges_displacement under autograd: d last_pos through gm_edge_features_backward (segmented sums, no atomics)."""
+
+    @staticmethod
+    def forward(ctx, last_pos, senders, receivers, conn_r):
+        ctx.conn_r = float(conn_r)
+        ctx.save_for_backward(last_pos, senders, receivers)
+        return _edge_features(last_pos, senders, receivers, conn_r)
+
+    @staticmethod
+    def backward(ctx, d_out):
+        last_pos, senders, receivers = ctx.saved_tensors
+        pos, stride = _pos_view(last_pos)
+        n, e = int(pos.shape[0]), int(senders.numel())
+        d_out = d_out.contiguous().float()
+        d_pos = torch.empty((n, 3), dtype=torch.float32, device=pos.device)
+        L = lib()
+        ws = _ws(L.gm_edge_features_backward_workspace_bytes(n, e), pos.device)
+        check(L.gm_edge_features_backward(C.c_void_p(pos.data_ptr()), stride, ptr(senders), ptr(receivers), n, e, ctx.conn_r,
+                                          ptr(d_out), ptr(d_pos), ptr(ws), ws.numel(), current_stream(pos.device)))
+        return d_pos, None, None, None
+
+
 def get_edges_displacement(last_pos, senders, receivers, conn_r):
-    """Reference ``get_edges_displacement`` (utils.py:43-61): [(p_s - p_r)/conn_r, ||.||]."""
+    """Reference ``get_edges_displacement`` (utils.py:43-61): [(p_s - p_r)/conn_r, ||.||].  Differentiable in ``last_pos`` (any view
+    the forward takes): where p_s = p_r -- the self edge every node has -- the norm's gradient is 0, as torch.norm's."""
     _need_cuda(last_pos, "last_pos")
+    if torch.is_grad_enabled() and last_pos.requires_grad:
+        _pos_view(last_pos)   # shape / dtype errors before autograd records anything
+        return _EdgeFeaturesFunction.apply(last_pos, senders.contiguous().long(), receivers.contiguous().long(), conn_r)
+    return _edge_features(last_pos, senders, receivers, conn_r)
+
+
+def _edge_features(last_pos, senders, receivers, conn_r):
     pos, stride = _pos_view(last_pos)
     senders = senders.contiguous().long()
     receivers = receivers.contiguous().long()
@@ -137,6 +168,33 @@ def make_feature_desc(conn_r, stats, bounds, cartesian_idx, material_idx, contro
     return d
 
 
+def _node_features(obs, d):
+    k, n, _ = obs.shape
+    f = 3 * (k - 1) + 7 + (3 if d.control_col >= 0 else 0)
+    out = torch.empty((n, f), dtype=torch.float32, device=obs.device)
+    check(lib().gm_node_features(ptr(obs), n, C.byref(d), ptr(out), current_stream()))
+    return out
+
+
+class _NodeFeaturesFunction(torch.autograd.Function):
+    """compute_nodes under autograd; obs: contiguous float32 [k, N, D], d: its gm_feature_desc."""
+
+    @staticmethod
+    def forward(ctx, obs, d):
+        ctx.desc = d
+        ctx.save_for_backward(obs)
+        return _node_features(obs, d)
+
+    @staticmethod
+    def backward(ctx, d_out):
+        obs, = ctx.saved_tensors
+        d_out = d_out.contiguous().float()
+        d_obs = torch.empty_like(obs)
+        check(lib().gm_node_features_backward(ptr(obs), int(obs.shape[1]), C.byref(ctx.desc), ptr(d_out), ptr(d_obs),
+                                              current_stream()))
+        return d_obs, None
+
+
 class GraphBoundedMultimaterial:
     """Mirror of the reference class of the same name (collate_utils.py:162-209)."""
 
@@ -163,14 +221,13 @@ class GraphBoundedMultimaterial:
 
     # -- reference surface
     def compute_nodes(self, obs):
+        """Differentiable in ``obs``: velocity, boundary (torch.clamp's rule) and control columns; gm_node_features_backward."""
         _need_cuda(obs, "obs")
         obs = obs.contiguous().float()
-        k, n, _ = obs.shape
         d = self.feature_desc(obs)
-        f = 3 * (k - 1) + 7 + (3 if d.control_col >= 0 else 0)
-        out = torch.empty((n, f), dtype=torch.float32, device=obs.device)
-        check(lib().gm_node_features(ptr(obs), n, C.byref(d), ptr(out), current_stream()))
-        return out
+        if torch.is_grad_enabled() and obs.requires_grad:
+            return _NodeFeaturesFunction.apply(obs, d)
+        return _node_features(obs, d)
 
     def compute_edges(self, obs, senders, receivers):
         last_pos = obs[-1][:, self.cartesian_idx[0]:self.cartesian_idx[0] + 3]

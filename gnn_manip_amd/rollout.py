@@ -13,11 +13,12 @@ import os
 import torch
 
 from ._lib import ModelDesc, check, current_stream, lib, ptr
-from .graph import _need_cuda, _ws, make_feature_desc
+from .graph import _NodeFeaturesFunction, _need_cuda, _node_features, _ws, get_connectivity, get_edges_displacement, make_feature_desc
 
 
 def get_position_from_prediction(stats, cartesian_idx, pred_acc, obs_seq, _desc=None):
-    """Reference ``get_position_from_prediction`` (rollout_utils.py:145-158) on the device."""
+    """Reference ``get_position_from_prediction`` (rollout_utils.py:145-158) on the device.  Differentiable in ``pred_acc`` and
+    ``obs_seq``."""
     _need_cuda(pred_acc, "pred_acc")
     obs = obs_seq.contiguous().float()
     pred = pred_acc.contiguous().float()
@@ -28,9 +29,34 @@ def get_position_from_prediction(stats, cartesian_idx, pred_acc, obs_seq, _desc=
         full.update(stats)
         _desc = make_feature_desc(1.0, full, dict(lower_bounds=[0.0] * 3, upper_bounds=one), cartesian_idx,
                                   [0], None, k, dd)
+    if torch.is_grad_enabled() and (pred.requires_grad or obs.requires_grad):
+        return _IntegrateFunction.apply(pred, obs, _desc)
+    return _integrate(pred, obs, _desc)
+
+
+def _integrate(pred, obs, desc):
+    n = int(obs.shape[1])
     out = torch.empty((n, 3), dtype=torch.float32, device=obs.device)
-    check(lib().gm_integrate(ptr(pred), ptr(obs), n, C.byref(_desc), ptr(out), current_stream()))
+    check(lib().gm_integrate(ptr(pred), ptr(obs), n, C.byref(desc), ptr(out), current_stream()))
     return out
+
+
+class _IntegrateFunction(torch.autograd.Function):
+    """get_position_from_prediction under autograd (it is linear): gm_integrate_backward."""
+
+    @staticmethod
+    def forward(ctx, pred, obs, desc):
+        ctx.desc, ctx.shape = desc, tuple(obs.shape)
+        return _integrate(pred, obs, desc)
+
+    @staticmethod
+    def backward(ctx, d_next):
+        d_next = d_next.contiguous().float()
+        n = ctx.shape[1]
+        d_pred = torch.empty((n, 3), dtype=torch.float32, device=d_next.device)
+        d_obs = torch.empty(ctx.shape, dtype=torch.float32, device=d_next.device)
+        check(lib().gm_integrate_backward(ptr(d_next), n, C.byref(ctx.desc), ptr(d_pred), ptr(d_obs), current_stream()))
+        return (d_pred if ctx.needs_input_grad[0] else None), (d_obs if ctx.needs_input_grad[1] else None), None
 
 
 class RolloutEngine:
@@ -76,6 +102,7 @@ class RolloutEngine:
         L = lib()
         self.ws = _ws(L.gm_rollout_workspace_bytes(C.byref(self.mdesc), self.n, self.max_neighbours), self.device)
         self.rigid_rank = None
+        self.rigid_rows = None   # int64 indices of the rigid rows, ascending (differentiable_step)
         self.n_rigid = 0
         if renumber == "auto" and os.environ.get("GM_RENUMBER") in ("0", "1"):   # A/B runs of the benchmark
             renumber = os.environ["GM_RENUMBER"] == "1"
@@ -94,6 +121,7 @@ class RolloutEngine:
         assert obs.shape == (self.k, self.n, self.data_dim) and obs.dtype == torch.float32 and obs.is_contiguous()
         self.rigid_rank, cnt = self._rank_rigid(obs)
         self.n_rigid = int(cnt.item())
+        self.rigid_rows = torch.nonzero(self.rigid_rank >= 0).flatten()   # ascending: row j of a rigid_target belongs to rigid_rows[j]
         return self.n_rigid
 
     def _check_state(self, obs, rigid_target, pred_out, use_rigid):
@@ -122,6 +150,50 @@ class RolloutEngine:
         rr = self.rigid_rank if use_rigid else None
         check(lib().gm_rollout_step(handle, ptr(obs), self.n, C.byref(self.fdesc), self.max_neighbours, ptr(rr),
                                     ptr(rigid_target), ptr(pred_out), ptr(self.ws), self.ws.numel(), current_stream()))
+
+    def differentiable_step(self, obs, rigid_target=None):
+        """One rollout step OUT of place, under autograd: returns (next_obs [k, N, D], pred [N, 3], edge_index [2, E]); ``obs`` is
+        untouched.  The chain is ``step``'s: state_pre -> node features -> radius graph -> edge features -> ``model.forward`` ->
+        integrate -> state_post.  Gradients flow to ``obs`` (position and control columns) and to ``rigid_target``, through the
+        model (gm_epd_backward_inputs) and the HIP backward of each feature function.
+
+        The radius graph is a constant of the step: connectivity is piecewise constant in the positions, so its gradient is
+        zero wherever it exists; the graph is built on the detached last frame and returned so that a caller (or a test) can
+        hold a reference computation to the same edges.  The two state updates -- control columns and scripted pose of the rigid
+        rows (``rigid_rows``, set_scene), the window shift -- are torch indexing operations on the device.  ``candidates`` > 1:
+        the batched radius graph, as in ``step``.  The forward reads ONE number back from the device, the edge count that sizes
+        ``edge_index`` / ``edge_attr``; nothing else in the forward and nothing in the backward synchronises with the host."""
+        self._check_state(obs, rigid_target, None, True)
+        ga = self.graph_attr
+        c0 = ga.cartesian_idx[0]
+        rows = self.rigid_rows
+        last = obs[-1]
+        if ga.control_idx is not None:   # state_pre: control of the rigid rows <- scripted pose - current xyz (no pose: current xyz)
+            u0 = ga.control_idx[0]
+            cur = last[rows, c0:c0 + 3]
+            last = last.clone()
+            last[rows, u0:u0 + 3] = cur if rigid_target is None else rigid_target - cur
+        obs_pre = torch.cat((obs[:-1], last.unsqueeze(0)))
+        if torch.is_grad_enabled() and obs_pre.requires_grad:
+            nodes = _NodeFeaturesFunction.apply(obs_pre, self.fdesc)
+        else:
+            nodes = _node_features(obs_pre, self.fdesc)
+        pos = obs_pre[-1][:, c0:c0 + 3]
+        senders, receivers = get_connectivity(pos.detach(), ga.conn_r, self.max_neighbours,
+                                              self.n_per if self.candidates > 1 else None)
+        edge_attr = get_edges_displacement(pos, senders, receivers, ga.conn_r)
+        edge_index = torch.stack((senders, receivers))
+        pred = self.model.forward(nodes, edge_attr, edge_index)
+        next_pos = get_position_from_prediction(ga.stats, ga.cartesian_idx, pred, obs_pre, _desc=self.fdesc)
+        # state_post: window shift; p_{t+1} into the last frame; a rigid row keeps its pre-step row, with the scripted pose if given
+        new_last = obs_pre[-1].clone()
+        new_last[:, c0:c0 + 3] = next_pos
+        keep = obs_pre[-1][rows]
+        if rigid_target is not None:
+            keep = keep.clone()
+            keep[:, c0:c0 + 3] = rigid_target
+        new_last[rows] = keep
+        return torch.cat((obs_pre[1:], new_last.unsqueeze(0))), pred, edge_index
 
     def status(self):
         """Synchronises; raises on a device-side data error; returns the last step's edge count."""

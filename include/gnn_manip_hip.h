@@ -157,6 +157,29 @@ int gm_rigid_transform(const float* rigid_init /*[Nr,3]*/, int64_t n_rigid, cons
                        /* [T,3] host-computed (cos, sin, ty_init[1]+translation) float32 */,
                        int64_t n_steps, const float ty_init[3], float* out /*[T,Nr,3]*/, void* stream);
 
+/* Backward of the per-step functions (a differentiable rollout step).  Every output is WRITTEN IN FULL, not accumulated, by one
+ * thread per row in a fixed order: no float atomics, the same call twice gives the same bits; no host synchronisation.
+ * nodes_per_graph of the descriptor plays no part.
+ * gm_edge_features_backward: d_pos [N,3] (dense rows) from d_out [E,4].  With d = (p_s - p_r) / r and g = d_out[e] the edge gives
+ *   (g[0:3] + g[3] d / |d|) / r to its sender and the negative to its receiver; where |d| = 0 (the self edge every node has) the
+ *   norm's term is 0, the subgradient torch.norm uses.  A node sums the edges it sends, then subtracts the edges it receives, each
+ *   group in ascending edge id (segmented sums over the destination sorts with flow 1 and flow 0, built in `ws`).  Any edge list
+ *   works: hubs, duplicates, isolated nodes (zero rows), any order; an edge with an index outside [0, N) contributes nothing.
+ * gm_node_features_backward: d_obs [k,N,D] from d_out [N,F], the transpose of gm_node_features.  Velocity columns give
+ *   +-1/vel_std to the two frames of their difference; the six boundary columns give +-1/conn_r to the last frame where the
+ *   UNCLAMPED value lies in [-1, 1] (torch.clamp's rule: the ends included) and nothing elsewhere; the material column gives
+ *   nothing; control columns give 1/vel_std to the last frame's control columns.  Columns no feature reads are zero.
+ * gm_integrate_backward: d_pred [N,3] = g acc_std and d_obs [k,N,D]: +2g on frame k-1, -g on frame k-2 in the position columns,
+ *   zero everywhere else, g = d_next_pos [N,3]. */
+size_t gm_edge_features_backward_workspace_bytes(int64_t n_nodes, int64_t n_edges);
+int gm_edge_features_backward(const float* pos, int64_t pos_stride, const int64_t* senders, const int64_t* receivers,
+                              int64_t n_nodes, int64_t n_edges, float conn_r, const float* d_out /*[E,4]*/,
+                              float* d_pos /*[N,3]*/, void* ws, size_t ws_bytes, void* stream);
+int gm_node_features_backward(const float* obs, int64_t n_nodes, const gm_feature_desc* desc,
+                              const float* d_out /*[N,F]*/, float* d_obs /*[k,N,D]*/, void* stream);
+int gm_integrate_backward(const float* d_next_pos /*[N,3]*/, int64_t n_nodes, const gm_feature_desc* desc,
+                          float* d_pred /*[N,3]*/, float* d_obs /*[k,N,D]*/, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Model.  Replaces EncProcDecGNN.__init__/_build_mlp + load_state_dict
  *         gnn_manip/models/epd_gnn.py:13-49,72-84 ; rollout_utils.py:137-139.
@@ -256,7 +279,7 @@ int gm_interaction_network_forward(const gm_model* m, int block, const float* h,
  * gradient of every parameter into grads[t] (same order and shapes as the `tensors` of
  * gm_model_create; the caller zeroes them), given grad_out = dLoss/d(out) [N, out_dim].  `tensors`
  * are the parameter values the forward ran with (device pointers).  Inputs x / edge_attr get no
- * gradient (they are data in train_dyn.py).  Weight gradients are reduced in a fixed order
+ * gradient here (they are data in train_dyn.py; gm_epd_backward_inputs returns them).  Weight gradients are reduced in a fixed order
  * (deterministic, like the bias and LayerNorm-parameter gradients: no atomics on the backward path). */
 size_t gm_train_tape_bytes(const gm_model_desc* desc, int64_t n_nodes, int64_t n_edges);
 size_t gm_train_backward_workspace_bytes(const gm_model_desc* desc, int64_t n_nodes, int64_t n_edges);
@@ -267,6 +290,20 @@ int gm_epd_backward(const gm_model* m, const float* const* tensors, int n_tensor
                     const float* edge_attr, int64_t n_nodes, int64_t n_edges, const float* grad_out,
                     float* const* grads, void* tape, size_t tape_bytes, void* ws, size_t ws_bytes,
                     void* stream);
+
+/* gm_epd_backward that also returns the gradient w.r.t. the model's inputs (a differentiable rollout step; a frozen model in a
+ * planning loop): d_nodes [N, node_dim] and d_edge_attr [E, edge_dim] in the CALLER's edge order, either may be NULL, both NULL
+ * is gm_epd_backward.  Both are written in full, not accumulated.  The parameter gradients are bit-equal to gm_epd_backward's:
+ * the encoders' chains only run one product further (dX = dz1 W1) and store.  A forward whose edge_index was flagged returns
+ * exactly zero input gradients, like its parameter gradients; the rows of edges the destination sort left out are zero.
+ * gm_train_backward_inputs_workspace_bytes is this entry point's workspace query (the transposed W1 images of the two encoders
+ * live in the encoders' slots of the backward workspace). */
+size_t gm_train_backward_inputs_workspace_bytes(const gm_model_desc* desc, int64_t n_nodes, int64_t n_edges);
+int gm_epd_backward_inputs(const gm_model* m, const float* const* tensors, int n_tensors, const float* nodes,
+                           const float* edge_attr, int64_t n_nodes, int64_t n_edges, const float* grad_out,
+                           float* const* grads, float* d_nodes /* [N, node_dim] or NULL */,
+                           float* d_edge_attr /* [E, edge_dim], caller's edge order, or NULL */, void* tape,
+                           size_t tape_bytes, void* ws, size_t ws_bytes, void* stream);
 
 /* The two standalone blocks under autograd -- the torch_graphnet surface the reference's own
  * EncProcDecGNN wiring calls (epd_gnn.py:30-33,42-45,88,101).  *_forward_train record a tape

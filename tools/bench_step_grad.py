@@ -1,0 +1,126 @@
+"""Input gradients of a rollout step, timed with HIP events.  Prints one JSON line per shape.
+
+    python tools/bench_step_grad.py [--reps 10] [--warmup 2] [--shapes train,100k]
+
+Shapes: `train` = the training benchmark's graph (two collated 5000-node scenes, hidden 128, 10 message-passing steps) and
+`100k` = one scene of N = 100k.  Per shape, interleaved call by call:
+  * `bwd` = gm_epd_backward and `bwd_inputs` = gm_epd_backward_inputs with both outputs, on the SAME tape of one training forward
+    (the backward reads the tape and writes its own workspace): what d_nodes / d_edge_attr cost on top of the parameter gradients;
+  * `step_fwd_bwd` = RolloutEngine.differentiable_step on the shape's state plus backward() of a seeded linear loss with respect to
+    obs and rigid_target (the forward's one host read of the edge count included); `step_fwd` = the same forward under no_grad;
+  * `tape_bytes` = gm_train_tape_bytes of the step's graph.
+Each time is one call between two events on the current stream; median and range over --reps calls.
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np
+import torch
+
+
+def _time(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b)
+
+
+def bench(name, scenes, reps, warmup, hidden=128, m_steps=10):
+    from gnn_manip_amd import EncProcDecGNN, GraphBoundedMultimaterialControl, RolloutEngine, scene
+    from gnn_manip_amd._lib import ModelDesc, check, current_stream, lib, ptr
+    from gnn_manip_amd.epd_gnn import _grad_arrays, _ws
+    dev = torch.device("cuda:0")
+    L = lib()
+    ga = GraphBoundedMultimaterialControl(0.015, scene.STATS, scene.CART, scene.MAT, scene.CTRL, scene.BOUNDS)
+    torch.manual_seed(0)
+    model = EncProcDecGNN(25, 4, 3, hidden, 2, m_steps).to(dev)
+    obs = torch.from_numpy(np.concatenate(scenes, axis=1)).to(dev).contiguous()
+    n_per = scenes[0].shape[1]
+    eng = RolloutEngine(model, ga, n_per, k_steps=obs.shape[0], data_dim=obs.shape[2], device=dev, candidates=len(scenes))
+    n_rigid = eng.set_scene(obs)
+    target = obs[-1][eng.rigid_rows][:, 2:5].contiguous() + 2e-4
+
+    # ---- the two backward entry points on one tape
+    with torch.no_grad():
+        _, _, ei = eng.differentiable_step(obs, target)
+        nodes = ga.compute_nodes(obs)
+        edge_attr = ga.compute_edges(obs, ei[0], ei[1]).contiguous()
+    n, e = int(nodes.shape[0]), int(edge_attr.shape[0])
+    d = ModelDesc(*model.model_desc())
+    h = model.device_handle(dev)
+    tape = _ws(L.gm_train_tape_bytes(C.byref(d), n, e), dev)
+    out = torch.empty((n, 3), device=dev)
+    check(L.gm_epd_forward_train(h, ptr(nodes), n, ptr(edge_attr), ptr(ei.contiguous()), e, ptr(out), ptr(tape), tape.numel(), current_stream()))
+    grad_out = torch.randn_like(out)
+    tensors, views, t_arr, g_arr = _grad_arrays(list(model.parameters()), dev)
+    ws = _ws(L.gm_train_backward_inputs_workspace_bytes(C.byref(d), n, e), dev)
+    d_nodes, d_edge_attr = torch.empty_like(nodes), torch.empty_like(edge_attr)
+
+    def bwd():
+        check(L.gm_epd_backward(h, t_arr, len(tensors), ptr(nodes), ptr(edge_attr), n, e, ptr(grad_out), g_arr, ptr(tape), tape.numel(),
+                                ptr(ws), ws.numel(), current_stream()))
+
+    def bwd_inputs():
+        check(L.gm_epd_backward_inputs(h, t_arr, len(tensors), ptr(nodes), ptr(edge_attr), n, e, ptr(grad_out), g_arr, ptr(d_nodes),
+                                       ptr(d_edge_attr), ptr(tape), tape.numel(), ptr(ws), ws.numel(), current_stream()))
+
+    w_o = torch.randn_like(obs)
+
+    def step_fwd():
+        with torch.no_grad():
+            eng.differentiable_step(obs, target)
+
+    def step_fwd_bwd():
+        o, t = obs.detach().requires_grad_(), target.detach().requires_grad_()
+        nxt, _, _ = eng.differentiable_step(o, t)
+        (nxt * w_o).sum().backward()
+
+    t = {}
+    for group in (dict(bwd=bwd, bwd_inputs=bwd_inputs), dict(step_fwd=step_fwd, step_fwd_bwd=step_fwd_bwd)):
+        for _ in range(warmup):
+            for fn in group.values():
+                fn()
+        torch.cuda.synchronize()
+        for k in group:
+            t[k] = []
+        for _ in range(reps):
+            for k, fn in group.items():
+                t[k].append(_time(fn))
+        if "bwd" in group:   # the tape and workspace of the first group are not needed by the second
+            tape = ws = None
+    med = {k: float(np.median(v)) for k, v in t.items()}
+    rec = dict(shape=name, nodes=n, edges=e, rigid=n_rigid, hidden=hidden, m_steps=m_steps, reps=reps,
+               tape_bytes=int(L.gm_train_tape_bytes(C.byref(d), n, e)))
+    for k, v in t.items():
+        rec[k + "_ms"] = round(med[k], 4)
+        rec[k + "_range_ms"] = [round(float(min(v)), 4), round(float(max(v)), 4)]
+    rec["inputs_over_bwd"] = round(med["bwd_inputs"] / med["bwd"], 4)
+    print(json.dumps(rec), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--shapes", default="train,100k")
+    args = ap.parse_args()
+    from gnn_manip_amd import scene
+    assert torch.cuda.is_available(), "bench_step_grad.py measures on the GPU"
+    for shape in args.shapes.split(","):
+        if shape == "train":      # bench.py extra_train's batch
+            bench("train_2x5000", [scene.make_scene(5000, seed=100 + b, side=0.152 * 0.8) for b in range(2)], args.reps, args.warmup)
+        elif shape == "100k":
+            bench("scene_100k", [scene.make_scene(100000, seed=1000)], args.reps, args.warmup)
+        else:
+            raise SystemExit(f"unknown shape {shape!r}")
+
+
+if __name__ == "__main__":
+    main()
