@@ -69,6 +69,7 @@ PROTOTYPES = {
     "gm_state_pre": (_i32, [_vp, _i64, _FD, _vp, _vp, _vp]),
     "gm_state_post": (_i32, [_vp, _i64, _FD, _vp, _vp, _vp, _vp]),
     "gm_rigid_transform": (_i32, [_vp, _i64, _vp, _i64, C.POINTER(_f32 * 3), _vp, _vp]),
+    "gm_rigid_transform_backward": (_i32, [_vp, _i64, _vp, _i64, C.POINTER(_f32 * 3), _vp, _vp, _vp]),
     "gm_model_num_tensors": (_i32, [_MD]),
     "gm_model_create": (_i32, [_MD, C.POINTER(_vp), _i32, _i32, _vp, C.POINTER(_vp)]),
     "gm_model_update": (_i32, [_vp, C.POINTER(_vp), _i32, _i32, _vp]),
@@ -84,6 +85,7 @@ PROTOTYPES = {
     "gm_epd_backward": (_i32, [_vp, _vp, _i32, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
     "gm_train_backward_inputs_workspace_bytes": (_sz, [_MD, _i64, _i64]),
     "gm_epd_backward_inputs": (_i32, [_vp, _vp, _i32, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "gm_epd_backward_inputs_only": (_i32, [_vp, _vp, _i32, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
     "gm_block_tape_bytes": (_sz, [_MD, _i32, _i64, _i64]),
     "gm_block_backward_workspace_bytes": (_sz, [_MD, _i64, _i64]),
     "gm_graph_independent_forward_train": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),

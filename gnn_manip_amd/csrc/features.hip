@@ -282,6 +282,37 @@ __global__ void __launch_bounds__(256) rigid_transform_kernel(const float* __res
     out[id * 3 + 1] = p2;
 }
 
+// transpose of rigid_transform_kernel w.r.t. its per-step row (cos, sin, ty_init[1] + translation): the map is linear in it, with
+// coefficients i1 = ty - init[i][2], i2 = tz - init[i][1].  One workgroup per step.  A thread walks its particles (tid, tid + 256,
+// ...) in order, the 256 partial sums go down a fixed tree in LDS: no atomics, the same bits every time.  The sums are carried in
+// float64 (the differences and products are then exact, the additions round at 2^-53) and rounded to float32 once at the end.
+__global__ void __launch_bounds__(256) rigid_transform_bwd_kernel(const float* __restrict__ init, int64_t nr, float ty, float tz,
+                                                                   const float* __restrict__ g, float* __restrict__ d_cst) {
+    __shared__ double red[3][256];
+    const int tid = threadIdx.x;
+    const int64_t t = blockIdx.x;
+    const float* gt = g + t * nr * 3;
+    double dc = 0.0, ds = 0.0, dt = 0.0;
+    for (int64_t i = tid; i < nr; i += 256) {
+        const double i1 = (double)ty - (double)init[i * 3 + 2];
+        const double i2 = (double)tz - (double)init[i * 3 + 1];
+        const double g1 = gt[i * 3 + 1], g2 = gt[i * 3 + 2];   // out[.][1] = p2, out[.][2] = p1
+        dc += g2 * i1 + g1 * i2;
+        ds += g1 * i1 - g2 * i2;
+        dt += g2;
+    }
+    red[0][tid] = dc; red[1][tid] = ds; red[2][tid] = dt;
+    __syncthreads();
+    for (int w = 128; w >= 1; w >>= 1) {
+        if (tid < w) {
+#pragma unroll
+            for (int a = 0; a < 3; ++a) red[a][tid] += red[a][tid + w];
+        }
+        __syncthreads();
+    }
+    if (tid < 3) d_cst[t * 3 + tid] = (float)red[tid][0];
+}
+
 // ---- renumbered rollout: rows of the [k, N, D] state move as whole rows (D floats), one thread per (frame, row)
 __global__ void __launch_bounds__(256) renumber_gather_kernel(const float* __restrict__ in, float* __restrict__ out, int k, int64_t n, int D,
                                                                const int* __restrict__ perm, const GraphHeader* __restrict__ ghdr,
@@ -596,6 +627,20 @@ int gm_rigid_transform(const float* rigid_init, int64_t nr, const float* cst, in
     GM_REQUIRE(rigid_init && cst && out, GM_ERR_INVALID_ARGUMENT, "gm_rigid_transform: null pointer");
     hipLaunchKernelGGL(rigid_transform_kernel, dim3((unsigned)cdiv(nr * steps, 256)), dim3(256), 0, (hipStream_t)stream,
                        rigid_init, nr, cst, steps, ty_init[0], ty_init[1], ty_init[2], out);
+    GM_LAUNCH_CHECK();
+    return GM_OK;
+}
+
+
+int gm_rigid_transform_backward(const float* rigid_init, int64_t nr, const float* cst, int64_t steps, const float ty_init[3],
+                                const float* d_out, float* d_cst, void* stream) {
+    (void)cst;   // the transform is linear in its (cos, sin, ty) rows: their values do not enter its transpose
+    GM_REQUIRE(nr >= 0 && steps >= 0 && steps < ((int64_t)1 << 31) && ty_init, GM_ERR_INVALID_ARGUMENT, "gm_rigid_transform_backward: bad sizes");
+    if (steps == 0) return GM_OK;
+    GM_REQUIRE(d_cst && (nr == 0 || (rigid_init && d_out)), GM_ERR_INVALID_ARGUMENT, "gm_rigid_transform_backward: null pointer");
+    gm::DevGuard dev_guard(d_cst);
+    hipLaunchKernelGGL(rigid_transform_bwd_kernel, dim3((unsigned)steps), dim3(256), 0, (hipStream_t)stream, rigid_init, nr, ty_init[1],
+                       ty_init[2], d_out, d_cst);
     GM_LAUNCH_CHECK();
     return GM_OK;
 }

@@ -248,6 +248,10 @@ BwdWs carve_block_bwd(void* ws, const gm_model_desc* d, int64_t n, int64_t e) {
 }
 
 // The launches of one backward call after its images are packed.  Every call does nothing once rc holds an error.
+// grads == nullptr: an inputs-only backward (gm_epd_backward_inputs_only).  No weight-gradient job is enqueued (so every flush is
+// empty and launches nothing), and the chains get no dgamma / dbeta, which is the launch argument that makes their epilogue skip
+// the LayerNorm parameter sums (train.hip: A.ln_part).  The dz chains, the segment sums and the dx tails are the same launches on
+// the same operands: a tile's results do not depend on which workgroup walks it.
 struct BwdRun {
     const gm_model* m;
     float* const* grads;
@@ -258,9 +262,10 @@ struct BwdRun {
     BwdRun(const gm_model* m_, float* const* grads_, const BwdWs& b_, hipStream_t s_) : m(m_), grads(grads_), b(b_), s(s_) {
         wgrad_batch_init(wb, b.part, m->H, s);
     }
+    float* g(int i) const { return grads ? grads[i] : nullptr; }   // gradient tensor i, or nullptr in an inputs-only backward
     void wgrad(const float* dz, int ldz, int Mo, const float* X, int ldx, int K, const int* xidx, int64_t rows, float* out, int ldw,
                int col0, float* db) {
-        if (rc == GM_OK) rc = wgrad_enqueue(wb, dz, ldz, Mo, X, ldx, K, xidx, rows, out, ldw, col0, db);
+        if (rc == GM_OK && grads) rc = wgrad_enqueue(wb, dz, ldz, Mo, X, ldx, K, xidx, rows, out, ldw, col0, db);
     }
     // sl: the slot the chain's stream was packed into.  flush: the chain overwrites operands of the waiting jobs
     void launch(int kind, TrainBwdArgs a, const Slot& sl, bool flush) {
@@ -272,14 +277,14 @@ struct BwdRun {
     void tail(const TrainBwdArgs& a, int base, int top) {
         for (int l = top; l >= 1; --l)
             wgrad(a.dz + (size_t)l * a.dz_stride, m->H, m->H, a.tape.a + (size_t)(l - 1) * a.rows * m->H, m->H, m->H, nullptr, a.rows,
-                  grads[base + 2 * l], m->H, 0, grads[base + 2 * l + 1]);
+                  g(base + 2 * l), m->H, 0, g(base + 2 * l + 1));
     }
     // the LayerNorm and dz fields of a normed MLP's chain: its LayerNorm parameter gradients are summed inside the chain kernel and
     // reduced by wb's next flush; node_set: dz goes to the node-sized set (BwdWs::dzn), which no waiting job reads
     void set_normed(TrainBwdArgs& a, int base, size_t voff, bool node_set) const {
         const int NL = m->NL;
         a.ln_g = m->vec + voff + (size_t)(NL + 1) * m->H;
-        a.dgamma = grads[base + 2 * (NL + 1)]; a.dbeta = grads[base + 2 * (NL + 1) + 1];
+        a.dgamma = g(base + 2 * (NL + 1)); a.dbeta = g(base + 2 * (NL + 1) + 1);
         a.dz = node_set ? b.dzn : b.dz; a.dz_stride = node_set ? b.dzn_stride : b.dz_stride; a.nl = NL;
     }
     // a normed MLP's chain and the weight gradients of its Linears 2 .. NL + 1 (Linear 1's differ at every call site).  A chain
@@ -295,8 +300,8 @@ struct BwdRun {
         if (rc == GM_OK)
             rc = launch_segment_sum_pair(m->H, csr.dst.in_ptr, nullptr, csr.src.in_ptr, csr.src.eid, b.dzl(1), nullptr, nullptr, b.Gi, b.Gj,
                                          n, s);
-        wgrad(b.Gi, m->H, m->H, h, m->H, m->H, nullptr, n, grads[be], 3 * m->H, m->ci * m->H, nullptr);
-        wgrad(b.Gj, m->H, m->H, h, m->H, m->H, nullptr, n, grads[be], 3 * m->H, m->cj * m->H, nullptr);
+        wgrad(b.Gi, m->H, m->H, h, m->H, m->H, nullptr, n, g(be), 3 * m->H, m->ci * m->H, nullptr);
+        wgrad(b.Gj, m->H, m->H, h, m->H, m->H, nullptr, n, g(be), 3 * m->H, m->cj * m->H, nullptr);
     }
     int finish() {
         if (rc == GM_OK) rc = wgrad_flush(wb);
@@ -329,11 +334,12 @@ int check_model(const gm_model* m, int64_t n, int64_t e, const char* who) {
                "%s: sizes out of range (n=%lld, e=%lld)", who, (long long)n, (long long)e);
     return GM_OK;
 }
-// a backward's state_dict: all of it, and the tensors and gradients [lo, hi) of the MLPs it reads non-null
+// a backward's state_dict: all of it, and the tensors and gradients [lo, hi) of the MLPs it reads non-null (grads == nullptr: an
+// inputs-only backward has none)
 int check_tensors(const gm_model* m, const float* const* T, float* const* grads, int n_tensors, int lo, int hi, const char* who) {
     const int nt = gm_model_num_tensors(&m->d);
     GM_REQUIRE(n_tensors == nt, GM_ERR_INVALID_ARGUMENT, "%s: expected %d tensors, got %d", who, nt, n_tensors);
-    for (int i = lo; i < hi; ++i) GM_REQUIRE(T[i] && grads[i], GM_ERR_INVALID_ARGUMENT, "%s: tensor / gradient %d is null", who, i);
+    for (int i = lo; i < hi; ++i) GM_REQUIRE(T[i] && (!grads || grads[i]), GM_ERR_INVALID_ARGUMENT, "%s: tensor / gradient %d is null", who, i);
     return GM_OK;
 }
 // after the entry point's own checks: the caller's buffers are large enough, the kernels set up, the weight streams ready on s
@@ -444,12 +450,15 @@ int gm_epd_forward_train(const gm_model* m, const float* nodes, int64_t n, const
 
 // The whole model's backward.  d_nodes / d_edge_attr (either may be null): the encoders' chains run on through W_1^T into the raw
 // input rows (TrainBwdArgs::dx_in); the parameter gradients are the same launches on the same operands either way.
+// grads == nullptr (inputs_only): the input gradients alone (BwdRun).
 static int epd_backward(const gm_model* m, const float* const* T, int n_tensors, const float* nodes, const float* edge_attr, int64_t n,
                         int64_t e, const float* grad_out, float* const* grads, float* d_nodes, float* d_edge_attr, void* tape,
-                        size_t tape_bytes, void* ws, size_t ws_bytes, void* stream, const char* who) {
+                        size_t tape_bytes, void* ws, size_t ws_bytes, void* stream, const char* who, bool inputs_only = false) {
+    GM_REQUIRE(!inputs_only || d_nodes || d_edge_attr, GM_ERR_INVALID_ARGUMENT, "%s: d_nodes and d_edge_attr are both null", who);
     int rc = check_model(m, n, e, who);
     if (rc != GM_OK) return rc;
-    GM_REQUIRE(T && grads && nodes && grad_out && tape && ws && (e == 0 || edge_attr), GM_ERR_INVALID_ARGUMENT, "%s: null pointer", who);
+    GM_REQUIRE(T && (grads || inputs_only) && nodes && grad_out && tape && ws && (e == 0 || edge_attr), GM_ERR_INVALID_ARGUMENT,
+               "%s: null pointer", who);
     rc = check_tensors(m, T, grads, n_tensors, 0, n_tensors, who);
     if (rc != GM_OK) return rc;
     gm::DevGuard dev_guard(nodes);
@@ -487,9 +496,9 @@ static int epd_backward(const gm_model* m, const float* const* T, int n_tensors,
         a.rows = (int)n; a.dY = b.go; a.out_dim = OD; a.tape = t.dec;
         a.dz = b.dz; a.dz_stride = b.dz_stride; a.nl = NL; a.dx = b.dh;
         bw.launch(TB_DEC, a, b.dec, true);
-        bw.wgrad(b.go, OD, OD, t.dec.a + (size_t)(NL - 1) * n * H, H, H, nullptr, n, grads[bd + 2 * NL], H, 0, grads[bd + 2 * NL + 1]);
+        bw.wgrad(b.go, OD, OD, t.dec.a + (size_t)(NL - 1) * n * H, H, H, nullptr, n, bw.g(bd + 2 * NL), H, 0, bw.g(bd + 2 * NL + 1));
         bw.tail(a, bd, NL - 1);
-        bw.wgrad(b.dzl(1), H, H, t.h[M], H, H, nullptr, n, grads[bd], H, 0, grads[bd + 1]);
+        bw.wgrad(b.dzl(1), H, H, t.h[M], H, H, nullptr, n, bw.g(bd), H, 0, bw.g(bd + 1));
     }
     // ---- processor blocks, last to first
     for (int k = M - 1; k >= 0; --k) {
@@ -501,15 +510,15 @@ static int epd_backward(const gm_model* m, const float* const* T, int n_tensors,
             a.dx_resid = b.dh; a.dx = b.dh; a.dagg_out = b.dagg;
             // node-sized dz set: the waiting jobs read the edge-sized one, Gi / Gj and tapes -- nothing this chain writes
             bw.chain(TB_NODE, a, b.node[k], bn, m->v_node[k], true);
-            bw.wgrad(b.dznl(1), H, H, t.h[k], H, H, nullptr, n, grads[bn], 2 * H, m->ch * H, grads[bn + 1]);
-            bw.wgrad(b.dznl(1), H, H, t.step[k].agg, H, H, nullptr, n, grads[bn], 2 * H, m->ca * H, nullptr);
+            bw.wgrad(b.dznl(1), H, H, t.h[k], H, H, nullptr, n, bw.g(bn), 2 * H, m->ch * H, bw.g(bn + 1));
+            bw.wgrad(b.dznl(1), H, H, t.step[k].agg, H, H, nullptr, n, bw.g(bn), 2 * H, m->ca * H, nullptr);
         }
         {
             TrainBwdArgs a{};
             a.rows = (int)e; a.dY = has_next ? b.de : nullptr; a.dagg = b.dagg; a.dst = c.dst; a.tape = t.step[k].te;
             a.dx = b.de; a.residual = 1;
             bw.chain(TB_EDGE, a, b.edge[k], be, m->v_edge[k], false);
-            bw.wgrad(b.dzl(1), H, H, t.e[k], H, H, nullptr, e, grads[be], 3 * H, m->ce * H, grads[be + 1]);
+            bw.wgrad(b.dzl(1), H, H, t.e[k], H, H, nullptr, e, bw.g(be), 3 * H, m->ce * H, bw.g(be + 1));
             bw.ij_grads(t.csr, t.h[k], be, n);
         }
     }
@@ -520,7 +529,7 @@ static int epd_backward(const gm_model* m, const float* const* T, int n_tensors,
         a.dx_in = d_nodes; a.k1 = m->d.node_dim;
         const int bn = m->mlp[1].base;
         bw.chain(TB_ENC, a, b.enc_node, bn, m->v_enc_node, true);   // as the node MLPs
-        bw.wgrad(b.dznl(1), H, H, nodes, m->d.node_dim, m->d.node_dim, nullptr, n, grads[bn], m->d.node_dim, 0, grads[bn + 1]);
+        bw.wgrad(b.dznl(1), H, H, nodes, m->d.node_dim, m->d.node_dim, nullptr, n, bw.g(bn), m->d.node_dim, 0, bw.g(bn + 1));
     }
     if (e > 0) {
         TrainBwdArgs a{};
@@ -528,7 +537,7 @@ static int epd_backward(const gm_model* m, const float* const* T, int n_tensors,
         a.dx_in = d_edge_attr; a.k1 = m->d.edge_dim; a.dxidx = c.eid;   // sorted row p came from the caller's row eid[p]: a permutation
         const int be = m->mlp[0].base;
         bw.chain(TB_ENC, a, b.enc_edge, be, m->v_enc_edge, false);
-        bw.wgrad(b.dzl(1), H, H, edge_attr, m->d.edge_dim, m->d.edge_dim, c.eid, e, grads[be], m->d.edge_dim, 0, grads[be + 1]);
+        bw.wgrad(b.dzl(1), H, H, edge_attr, m->d.edge_dim, m->d.edge_dim, c.eid, e, bw.g(be), m->d.edge_dim, 0, bw.g(be + 1));
     }
     return bw.finish();
 }
@@ -551,6 +560,13 @@ int gm_epd_backward_inputs(const gm_model* m, const float* const* T, int n_tenso
                            size_t tape_bytes, void* ws, size_t ws_bytes, void* stream) {
     return epd_backward(m, T, n_tensors, nodes, edge_attr, n, e, grad_out, grads, d_nodes, d_edge_attr, tape, tape_bytes, ws, ws_bytes,
                         stream, __func__);
+}
+
+int gm_epd_backward_inputs_only(const gm_model* m, const float* const* T, int n_tensors, const float* nodes, const float* edge_attr,
+                                int64_t n, int64_t e, const float* grad_out, float* d_nodes, float* d_edge_attr, void* tape,
+                                size_t tape_bytes, void* ws, size_t ws_bytes, void* stream) {
+    return epd_backward(m, T, n_tensors, nodes, edge_attr, n, e, grad_out, nullptr, d_nodes, d_edge_attr, tape, tape_bytes, ws, ws_bytes,
+                        stream, __func__, true);
 }
 
 
@@ -607,7 +623,7 @@ int gm_graph_independent_backward(const gm_model* m, const float* const* T, int 
         TrainBwdArgs a{};
         a.rows = (int)rows; a.dY = dY; a.tape = tp; a.dx_in = dxin; a.k1 = k1;
         bw.chain(TB_ENC, a, sl, base, voff, false);
-        bw.wgrad(b.dzl(1), H, H, X, k1, k1, nullptr, rows, grads[base], k1, 0, grads[base + 1]);
+        bw.wgrad(b.dzl(1), H, H, X, k1, k1, nullptr, rows, bw.g(base), k1, 0, bw.g(base + 1));
     };
     run(en.base, t.enc.en, n, dh, m->v_enc_node, b.enc_node, x, m->d.node_dim, dx);
     run(ee.base, t.enc.ee, e, de, m->v_enc_edge, b.enc_edge, edge_attr, m->d.edge_dim, dedge_attr);
@@ -666,15 +682,15 @@ int gm_interaction_network_backward(const gm_model* m, int k, const float* const
         TrainBwdArgs a{};
         a.rows = (int)n; a.dY = dh_out; a.tape = t.st.tn; a.dx = b.dh; a.dagg_out = b.dagg;
         bw.chain(TB_NODE, a, b.node[0], bn, m->v_node[k], false);
-        bw.wgrad(b.dzl(1), H, H, h, H, H, nullptr, n, grads[bn], 2 * H, m->ch * H, grads[bn + 1]);
-        bw.wgrad(b.dzl(1), H, H, t.st.agg, H, H, nullptr, n, grads[bn], 2 * H, m->ca * H, nullptr);
+        bw.wgrad(b.dzl(1), H, H, h, H, H, nullptr, n, bw.g(bn), 2 * H, m->ch * H, bw.g(bn + 1));
+        bw.wgrad(b.dzl(1), H, H, t.st.agg, H, H, nullptr, n, bw.g(bn), 2 * H, m->ca * H, nullptr);
     }
     if (e > 0) {
         TrainBwdArgs a{};
         a.rows = (int)e; a.dY = de_out; a.dyidx = c.eid; a.dagg = b.dagg; a.dst = c.dst; a.tape = t.st.te;
         a.dx = de_in; a.dxidx = c.eid;
         bw.chain(TB_EDGE, a, b.edge[0], be, m->v_edge[k], false);
-        bw.wgrad(b.dzl(1), H, H, e_in, H, H, c.eid, e, grads[be], 3 * H, m->ce * H, grads[be + 1]);
+        bw.wgrad(b.dzl(1), H, H, e_in, H, H, c.eid, e, bw.g(be), 3 * H, m->ce * H, bw.g(be + 1));
     }
     bw.ij_grads(t.csr, h, be, n);
     // dh_in = W_h^T dz1 (node MLP) + W_i^T G_i + W_j^T G_j (edge MLP, factorised layer 1)

@@ -425,13 +425,17 @@ class _EpdTrainFunction(torch.autograd.Function):
     differentiable rollout step, a frozen model in a planning loop), gm_epd_backward_inputs, which runs the same launches and lets
     the encoders' chains go on into d_nodes / d_edge_attr.  edge_index is data.  `spec` = (model descriptor tuple, _Handle): the module's own, or
     -- for a hidden size between the training kernels' widths -- the zero-padded model's (EncProcDecGNN._padded_training), with
-    the module's own parameters as the third element: the tensors whose versions say when the padded copies are stale."""
+    the module's own parameters as the third element: the tensors whose versions say when the padded copies are stale.  The fourth
+    element is the inputs-only switch: the parameters are constants of this call whatever their requires_grad flags say, and the
+    backward is gm_epd_backward_inputs_only -- none of the weight-gradient launches, no gradient buffers.  EncProcDecGNN.forward
+    sets it when no parameter requires grad; a caller that differentiates with respect to the inputs alone (a planner on a model
+    nobody froze) asks for it through ``EncProcDecGNN.forward_inputs_only``."""
 
     @staticmethod
     def forward(ctx, module, spec, nodes, edge_attr, edge_index, *params):
         L = lib()
         n, e = int(nodes.shape[0]), int(edge_attr.shape[0])
-        desc_tuple, handle, key_params = spec
+        desc_tuple, handle, key_params, ctx.inputs_only = spec
         h = handle.get(desc_tuple, list(params), nodes.device, key_params)
         d = ModelDesc(*desc_tuple)
         tape = _ws(L.gm_train_tape_bytes(C.byref(d), n, e), nodes.device)
@@ -454,8 +458,20 @@ class _EpdTrainFunction(torch.autograd.Function):
         n, e = ctx.sizes
         dev = nodes.device
         grad_out = grad_out.contiguous().float()
-        tensors, views, t_arr, g_arr = _grad_arrays(params, dev)
         d_nodes = d_edge_attr = None
+        if ctx.inputs_only:
+            d_nodes = torch.empty_like(nodes) if ctx.needs_input_grad[2] else None
+            d_edge_attr = torch.empty_like(edge_attr) if ctx.needs_input_grad[3] else None
+            if d_nodes is not None or (d_edge_attr is not None and e > 0):   # (an empty d_edge_attr has nothing to compute)
+                tensors = [p.detach().to(device=dev, dtype=torch.float32).contiguous() for p in params]
+                t_arr = (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+                ws = _ws(L.gm_train_backward_inputs_workspace_bytes(C.byref(ctx.desc), n, e), dev)
+                check(L.gm_epd_backward_inputs_only(ctx.handle, t_arr, len(tensors), ptr(nodes), ptr(edge_attr), n, e, ptr(grad_out),
+                                                    ptr(d_nodes), ptr(d_edge_attr), ptr(ctx.tape), ctx.tape.numel(), ptr(ws), ws.numel(),
+                                                    current_stream()))
+            ctx.tape = None
+            return (None, None, d_nodes, d_edge_attr, None) + (None,) * len(params)
+        tensors, views, t_arr, g_arr = _grad_arrays(params, dev)
         if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
             d_nodes = torch.empty_like(nodes) if ctx.needs_input_grad[2] else None
             d_edge_attr = torch.empty_like(edge_attr) if ctx.needs_input_grad[3] else None
@@ -608,7 +624,13 @@ class EncProcDecGNN(nn.Module):
         projection kernels whatever the graph's size: 'auto' takes them for graphs of 49152 nodes or more).  See include/gnn_manip_hip.h."""
         self._handle.set_edge_kernel(self.EDGE_KERNELS.get(choice, choice))
 
-    def forward(self, nodes, edge_attr, edge_index):
+    def forward_inputs_only(self, nodes, edge_attr, edge_index):
+        """``forward`` with the parameters as constants, whatever their requires_grad flags say: gradients flow to nodes /
+        edge_attr alone (gm_epd_backward_inputs_only) and no parameter's ``.grad`` is touched.  An ``nn.Module``'s parameters
+        require grad by default; a planner that differentiates through a trained model must not have to freeze them."""
+        return self.forward(nodes, edge_attr, edge_index, _inputs_only=True)
+
+    def forward(self, nodes, edge_attr, edge_index, _inputs_only=False):
         """epd_gnn.py:86-98: encoder -> m_steps x (InteractionNetwork + residuals) -> decoder, fused."""
         _need_cuda(nodes, "nodes")
         nodes = nodes.contiguous().float()
@@ -619,10 +641,12 @@ class EncProcDecGNN(nn.Module):
         if edge_index.shape[1] != e:
             raise ValueError("edge_index and edge_attr disagree on the number of edges")
         params = list(self.parameters())
-        if _wants_grad(params, nodes, edge_attr):
+        # inputs only: asked for (forward_inputs_only), or nothing else can want a gradient -- every parameter frozen, a planning loop
+        # on a trained model.  The backward is then gm_epd_backward_inputs_only: no weight-gradient launch, no gradient buffers.
+        inputs_only = _inputs_only or not any(p.requires_grad for p in params)
+        if _wants_grad([] if inputs_only else params, nodes, edge_attr):
             # training (examples/train_dyn.py:45-72): forward with tape, HIP backward.  Inputs that require grad get their gradient
-            # too (gm_epd_backward_inputs) -- also with every parameter frozen, a planning loop on a trained model: the result then
-            # still carries grad_fn (the parameter gradients are computed and dropped).
+            # too (gm_epd_backward_inputs).
             # edge_index entries outside [0, n) are flagged on the device by the forward's destination sort (and left out; the
             # kernels stay inside their arrays): no blocking range check here -- a training loop queues its steps ahead of the GPU.
             # The flag surfaces as GMError at a later forward (auto_status) or at status(), like the inference path's.  Until it
@@ -635,12 +659,15 @@ class EncProcDecGNN(nn.Module):
             if self.auto_status:
                 self._reap_watched(block=False)
             hidden = self.dims[3]
+            if inputs_only:
+                params = [p.detach() for p in params]   # constants: autograd records nothing for them (nor for the padded copies)
             if hidden in TRAIN_WIDTHS:
-                return _EpdTrainFunction.apply(self, (self.model_desc(), self._handle, None), nodes, edge_attr, edge_index, *params)
+                return _EpdTrainFunction.apply(self, (self.model_desc(), self._handle, None, inputs_only), nodes, edge_attr, edge_index,
+                                               *params)
             spec, padded = self._padded_training(params)
             # the padded tensors are rebuilt every step (version 0, recycled addresses): the handle is keyed on the parameters they
             # come from, so an optimiser step on ANY of them -- whatever is frozen -- re-packs the padded model's weight streams
-            return _EpdTrainFunction.apply(self, spec + (tuple(params),), nodes, edge_attr, edge_index, *padded)
+            return _EpdTrainFunction.apply(self, spec + (tuple(params), inputs_only), nodes, edge_attr, edge_index, *padded)
         if self.auto_status:
             # EARLIER inference forwards of this model: a device-side error (edge_index entry out of range, fp16 split range
             # exceeded) of one that has FINISHED surfaces here -- a reference-style caller never calls status() itself.

@@ -52,6 +52,55 @@ def get_rigid_body_trajectory(traj_rot, traj_ty, horizon, ty_init, rigid_particl
     return out
 
 
+def interpolate_trajectory_torch(x, n_points, rx_init, scale_rot, scale_ty, max_rot, max_ty):
+    """``interpolate_trajectory`` restated in float64 torch, differentiable in ``x`` (a 1-D float64 tensor): the clipped
+    increments (``clamp``: zero gradient beyond the limits) and their running sums, in the reference's order of additions.
+    Returns (rot, ty), each [n_points + 1]."""
+    inc_r = torch.clamp(torch.deg2rad(scale_rot * torch.rad2deg(x[:n_points])), -max_rot, max_rot)
+    inc_t = torch.clamp(scale_ty * x[n_points:2 * n_points], -max_ty, max_ty)
+    first = lambda v: torch.tensor([v], dtype=x.dtype, device=x.device)
+    return torch.cumsum(torch.cat((first(rx_init), inc_r)), 0), torch.cumsum(torch.cat((first(0.0), inc_t)), 0)
+
+
+class _RigidTransformFunction(torch.autograd.Function):
+    """gm_rigid_transform under autograd in its (cos, sin, ty) rows: the backward is gm_rigid_transform_backward."""
+
+    @staticmethod
+    def forward(ctx, rp, cst, ty_init):
+        steps = int(cst.shape[0])
+        out = torch.empty((steps, rp.shape[0], 3), dtype=torch.float32, device=rp.device)
+        t3 = (C.c_float * 3)(*[float(v) for v in ty_init])
+        check(lib().gm_rigid_transform(ptr(rp), rp.shape[0], ptr(cst), steps, C.byref(t3), ptr(out), current_stream(rp.device)))
+        ctx.t3 = t3
+        ctx.save_for_backward(rp, cst)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        rp, cst = ctx.saved_tensors
+        d_out = d_out.contiguous().float()
+        d_cst = torch.empty_like(cst)
+        check(lib().gm_rigid_transform_backward(ptr(rp), rp.shape[0], ptr(cst), int(cst.shape[0]), C.byref(ctx.t3), ptr(d_out),
+                                                ptr(d_cst), current_stream(rp.device)))
+        return None, d_cst, None
+
+
+def rigid_body_trajectory(rot, ty, horizon, ty_init, rigid_particles):
+    """``get_rigid_body_trajectory`` for tensors: rot, ty are float64 tensors (any device) of at least ``horizon`` entries, and
+    the [horizon, Nr, 3] poses are differentiable in both.  cos / sin are evaluated in float64 torch and rounded to float32, so
+    the poses are bit-equal to ``get_rigid_body_trajectory``'s for the same numbers; the transform is gm_rigid_transform, its
+    backward gm_rigid_transform_backward (a fixed-order sum over the rigid particles), the rest of the chain is autograd's."""
+    rp = rigid_particles.detach().contiguous().float()
+    assert rp.is_cuda
+    if rot.dtype != torch.float64 or ty.dtype != torch.float64 or rot.dim() != 1 or ty.dim() != 1:
+        raise ValueError("rot and ty must be 1-D float64 tensors")
+    if rot.shape[0] < horizon or ty.shape[0] < horizon:
+        raise IndexError(f"trajectory of {min(rot.shape[0], ty.shape[0])} poses is shorter than the horizon {horizon}")
+    rot, ty = rot[:horizon], ty[:horizon]
+    cst = torch.stack((torch.cos(rot), torch.sin(rot), float(ty_init[1]) + ty), dim=1).to(torch.float32).to(rp.device).contiguous()
+    return _RigidTransformFunction.apply(rp, cst, ty_init)
+
+
 def shard_range(n_items, world_size, rank):
     """Contiguous block [lo, hi) of `n_items` candidates owned by `rank` (blocks differ by at most one)."""
     base, rem = divmod(n_items, world_size)
@@ -290,6 +339,37 @@ class TrajectoryCMAsolver:
         w = self.loss.batched(torch.cat(ends), self.desired_pos).double().cpu().numpy()
         return [self._assemble_loss(float(w[i]), acts[i], X[i] if self._loss_takes_x else None)[0] for i in range(len(X))]
 
+    # ---- gradient of the objective
+    def loss_and_grad(self, x, edges=None):
+        """The objective of ``cma_objective(x)`` and its gradient with respect to the search vector: (loss: float, grad: array like
+        x).  The map from x to the poses is restated in float64 torch (``interpolate_trajectory_torch``: clip, running sums;
+        ``rigid_body_trajectory``), the rollout is ``RolloutEngine.differentiable_rollout`` (memory of one step's tape whatever the
+        horizon; the model's parameters are constants), the end cloud goes into the differentiable ``SamplesLoss``, and the
+        velocity / acceleration norms are float64 torch.  The boundary penalty is piecewise constant in x: it is added to the
+        value and contributes nothing to the gradient.  Which optimiser to drive with this gradient is left open.
+        edges: a list that receives the ``edge_index`` of every step of the backward's recomputation (diagnostics, tests)."""
+        x_np = np.asarray(x, dtype=np.float64)
+        xt = torch.tensor(x_np.reshape(-1), dtype=torch.float64, requires_grad=True)
+        rot, ty = interpolate_trajectory_torch(xt, self.sample_traj.shape[0], float(self.rx_init), self.scale_rot, self.scale_ty,
+                                               float(self.max_rot), self.max_ty)
+        h = self.horizon
+        traj = rigid_body_trajectory(rot, ty, h, self.ty_init, self.rigid_particles)
+        out = self._engine(1).differentiable_rollout(self.initial_state[0].contiguous(), traj, horizon=h, return_edges=edges is not None)
+        final, step_edges = out if edges is not None else (out, None)
+        c0 = self.graph_attr.cartesian_idx[0]
+        end = final[-1].index_select(0, self._coffee_rows)[:, c0:c0 + 3]
+        wasserstein = self.loss(end, self.desired_pos).double().cpu()
+        actions = torch.stack((rot[:h], ty[:h]), dim=1)
+        limits = torch.tensor([float(self.max_rot), float(self.max_ty)], dtype=torch.float64)
+        vel = actions[1:] - actions[:-1]
+        acc = actions[2:] - 2 * actions[1:-1] + actions[:-2]
+        loss = self.beta * wasserstein + self.alpha * torch.linalg.norm(vel / limits) + self.gamma * torch.linalg.norm(acc / limits)
+        loss.backward()
+        if edges is not None:
+            edges[:] = step_edges
+        bound_penalty = self.compute_boundaries_penalty(actions.detach().numpy())
+        return float(loss.detach()) + self.penalty * bound_penalty, xt.grad.numpy().reshape(x_np.shape)
+
     def _start_point(self):
         """The search starts at the sample trajectory: all rotation variables, then all translation variables."""
         return np.ascontiguousarray(self.sample_traj.T, dtype=np.float64).reshape(-1)
@@ -351,6 +431,9 @@ class InterpolatedCMAsolver(TrajectoryCMAsolver):
         vel, _ = self.compute_vel_acc(actions)
         upper = np.abs(vel) - np.array([self.max_rot * self.nr_traj_points, self.max_ty * self.nr_traj_points])
         return np.concatenate((upper[:, 0] / self.scale_rot, upper[:, 1] / self.scale_ty))
+
+    def loss_and_grad(self, x):
+        raise NotImplementedError("loss_and_grad: the PCHIP parametrisation (scipy, on the host) has no gradient")
 
     _loss_takes_x = True
 

@@ -11,6 +11,7 @@ import ctypes as C
 import os
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from ._lib import ModelDesc, check, current_stream, lib, ptr
 from .graph import _NodeFeaturesFunction, _need_cuda, _node_features, _ws, get_connectivity, get_edges_displacement, make_feature_desc
@@ -57,6 +58,50 @@ class _IntegrateFunction(torch.autograd.Function):
         d_obs = torch.empty(ctx.shape, dtype=torch.float32, device=d_next.device)
         check(lib().gm_integrate_backward(ptr(d_next), n, C.byref(ctx.desc), ptr(d_pred), ptr(d_obs), current_stream()))
         return (d_pred if ctx.needs_input_grad[0] else None), (d_obs if ctx.needs_input_grad[1] else None), None
+
+
+class _RolloutFunction(torch.autograd.Function):
+    """RolloutEngine.differentiable_rollout: the inference rollout forward, a reverse sweep of re-run differentiable steps backward."""
+
+    @staticmethod
+    def forward(ctx, engine, obs0, trajectory, steps, edges):
+        obs = obs0.detach().clone().contiguous()
+        traj = None if trajectory is None else trajectory.detach().contiguous().float()
+        engine.set_scene(obs)
+        windows = []
+        for t in range(steps):
+            windows.append(obs.clone())    # the pre-step window: all the backward needs of step t besides its pose
+            engine.step(obs, None if traj is None else traj[t])
+        engine.status()
+        ctx.engine, ctx.windows, ctx.traj, ctx.edges = engine, windows, traj, edges
+        ctx.scene = (engine.rigid_rank, engine.rigid_rows, engine.n_rigid)
+        return obs
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_window):
+        eng, traj = ctx.engine, ctx.traj
+        eng.rigid_rank, eng.rigid_rows, eng.n_rigid = ctx.scene   # the engine may have been given another scene since
+        need_traj = traj is not None and ctx.needs_input_grad[2]
+        d_traj = torch.zeros_like(traj) if need_traj else None
+        edges = [None] * len(ctx.windows)   # of the recomputed steps, for the caller's list (return_edges)
+        d_window = d_window.contiguous().float()
+        for t in range(len(ctx.windows) - 1, -1, -1):
+            with torch.enable_grad():
+                w = ctx.windows[t].requires_grad_(True)
+                pose = None if traj is None else traj[t].clone().requires_grad_(need_traj)
+                nxt, _, ei = eng.differentiable_step(w, pose, inputs_only=True)
+            # step t's tape lives from here to the end of this call to autograd, which frees it: one tape at a time
+            grads = torch.autograd.grad(nxt, [w, pose] if need_traj else [w], grad_outputs=d_window)
+            d_window = grads[0]
+            if need_traj:
+                d_traj[t] = grads[1]
+            ctx.windows[t] = None
+            edges[t] = ei if ctx.edges is not None else None
+            del nxt, w, pose, grads
+        if ctx.edges is not None:
+            ctx.edges[:] = edges
+        return None, (d_window if ctx.needs_input_grad[1] else None), d_traj, None, None
 
 
 class RolloutEngine:
@@ -151,7 +196,7 @@ class RolloutEngine:
         check(lib().gm_rollout_step(handle, ptr(obs), self.n, C.byref(self.fdesc), self.max_neighbours, ptr(rr),
                                     ptr(rigid_target), ptr(pred_out), ptr(self.ws), self.ws.numel(), current_stream()))
 
-    def differentiable_step(self, obs, rigid_target=None):
+    def differentiable_step(self, obs, rigid_target=None, inputs_only=False):
         """One rollout step OUT of place, under autograd: returns (next_obs [k, N, D], pred [N, 3], edge_index [2, E]); ``obs`` is
         untouched.  The chain is ``step``'s: state_pre -> node features -> radius graph -> edge features -> ``model.forward`` ->
         integrate -> state_post.  Gradients flow to ``obs`` (position and control columns) and to ``rigid_target``, through the
@@ -162,7 +207,10 @@ class RolloutEngine:
         hold a reference computation to the same edges.  The two state updates -- control columns and scripted pose of the rigid
         rows (``rigid_rows``, set_scene), the window shift -- are torch indexing operations on the device.  ``candidates`` > 1:
         the batched radius graph, as in ``step``.  The forward reads ONE number back from the device, the edge count that sizes
-        ``edge_index`` / ``edge_attr``; nothing else in the forward and nothing in the backward synchronises with the host."""
+        ``edge_index`` / ``edge_attr``; nothing else in the forward and nothing in the backward synchronises with the host.
+
+        inputs_only: the model's parameters are constants of the step whatever their requires_grad flags say
+        (``EncProcDecGNN.forward_inputs_only``: no weight-gradient work in the backward, no parameter's ``.grad`` touched)."""
         self._check_state(obs, rigid_target, None, True)
         ga = self.graph_attr
         c0 = ga.cartesian_idx[0]
@@ -183,7 +231,7 @@ class RolloutEngine:
                                               self.n_per if self.candidates > 1 else None)
         edge_attr = get_edges_displacement(pos, senders, receivers, ga.conn_r)
         edge_index = torch.stack((senders, receivers))
-        pred = self.model.forward(nodes, edge_attr, edge_index)
+        pred = (self.model.forward_inputs_only if inputs_only else self.model.forward)(nodes, edge_attr, edge_index)
         next_pos = get_position_from_prediction(ga.stats, ga.cartesian_idx, pred, obs_pre, _desc=self.fdesc)
         # state_post: window shift; p_{t+1} into the last frame; a rigid row keeps its pre-step row, with the scripted pose if given
         new_last = obs_pre[-1].clone()
@@ -194,6 +242,33 @@ class RolloutEngine:
             keep[:, c0:c0 + 3] = rigid_target
         new_last[rows] = keep
         return torch.cat((obs_pre[1:], new_last.unsqueeze(0))), pred, edge_index
+
+    def differentiable_rollout(self, obs0, trajectory=None, horizon=None, return_edges=False):
+        """``rollout(obs0, trajectory, horizon)`` under autograd: returns the final state [k, N, D], bit-equal to ``rollout``'s
+        (an engine that renumbers, see ``renumber``, sums a node's messages in another order inside ``rollout``: equal to
+        rounding there), with gradients to ``obs0`` (position and control columns) and to ``trajectory`` [T, N_rigid, 3].  The
+        model's parameters are CONSTANTS of this function: they get no gradient, whatever their requires_grad flags say, and
+        their ``.grad`` is not touched.
+
+        Memory does not grow with the horizon beyond one state window per step.  The forward is the inference rollout (``step``
+        in place on a clone, no tape) and keeps each step's pre-step window, k N D floats.  The backward walks the steps in
+        reverse: it re-runs ``differentiable_step`` on step t's saved window (inputs only: none of the weight-gradient work),
+        feeds it the gradient with respect to the window after step t, and takes the gradient with respect to the window before
+        it and to ``trajectory[t]``.  One step's tape is alive at a time.  Each recomputed step reads its edge count back from
+        the device (the limit of ``differentiable_step``); the forward synchronises once, at its end.
+
+        return_edges: the call returns (final state, edges), where ``edges`` is a list that the BACKWARD fills with the T
+        ``edge_index`` tensors [2, E_t] of its recomputation (empty until then), so that a reference computation can be held to
+        the same graphs.  ``candidates`` > 1 works as in ``differentiable_step``."""
+        steps = int(horizon) if horizon is not None else (int(trajectory.shape[0]) if trajectory is not None else 0)
+        self._check_state(obs0, None, None, False)
+        if trajectory is not None:
+            if (trajectory.device != self.device or trajectory.dim() != 3 or int(trajectory.shape[0]) < steps
+                    or int(trajectory.shape[2]) != 3):
+                raise ValueError(f"trajectory must be [T >= {steps}, N_rigid, 3] on {self.device}, got {tuple(trajectory.shape)}")
+        edges = [] if return_edges else None
+        out = _RolloutFunction.apply(self, obs0, trajectory, steps, edges)
+        return (out, edges) if return_edges else out
 
     def status(self):
         """Synchronises; raises on a device-side data error; returns the last step's edge count."""

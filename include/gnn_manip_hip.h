@@ -157,6 +157,16 @@ int gm_rigid_transform(const float* rigid_init /*[Nr,3]*/, int64_t n_rigid, cons
                        /* [T,3] host-computed (cos, sin, ty_init[1]+translation) float32 */,
                        int64_t n_steps, const float ty_init[3], float* out /*[T,Nr,3]*/, void* stream);
 
+/* Transpose of gm_rigid_transform with respect to its per-step rows: d_rot_cs_ty [T,3] from d_out [T,Nr,3].  With
+ * i1 = ty_init[1] - init[i][2], i2 = ty_init[2] - init[i][1] and g = d_out[t][i]:
+ *   d_cos = sum_i (g[2] i1 + g[1] i2),  d_sin = sum_i (g[1] i1 - g[2] i2),  d_ty = sum_i g[2].
+ * The transform is linear in its rows, so rot_cs_ty itself is not read (it may be NULL).  One workgroup per step, the sum over the
+ * rigid particles in a fixed order carried in float64 and rounded once: no float atomics, the same call twice gives the same bits.
+ * The output is written in full; n_rigid = 0 writes zeros. */
+int gm_rigid_transform_backward(const float* rigid_init /*[Nr,3]*/, int64_t n_rigid, const float* rot_cs_ty /*[T,3] or NULL*/,
+                                int64_t n_steps, const float ty_init[3], const float* d_out /*[T,Nr,3]*/,
+                                float* d_rot_cs_ty /*[T,3]*/, void* stream);
+
 /* Backward of the per-step functions (a differentiable rollout step).  Every output is WRITTEN IN FULL, not accumulated, by one
  * thread per row in a fixed order: no float atomics, the same call twice gives the same bits; no host synchronisation.
  * nodes_per_graph of the descriptor plays no part.
@@ -304,6 +314,19 @@ int gm_epd_backward_inputs(const gm_model* m, const float* const* tensors, int n
                            float* const* grads, float* d_nodes /* [N, node_dim] or NULL */,
                            float* d_edge_attr /* [E, edge_dim], caller's edge order, or NULL */, void* tape,
                            size_t tape_bytes, void* ws, size_t ws_bytes, void* stream);
+
+/* gm_epd_backward_inputs without the parameter gradients (weights are constants of a planning loop): no `grads` argument, and none
+ * of the weight-gradient work is enqueued -- no dW products (those of the factorised W_i / W_j among them), no bias sums, no
+ * LayerNorm-parameter partial sums or reductions (the chain kernels skip that part of their epilogue by a launch argument).  The dz
+ * chains, the segment sums they need and the input tails are the same launches on the same operands, so d_nodes / d_edge_attr are
+ * bit-equal to gm_epd_backward_inputs' for the same tape.  Workspace: gm_train_backward_inputs_workspace_bytes.  d_nodes and
+ * d_edge_attr both NULL is GM_ERR_INVALID_ARGUMENT (there would be nothing to compute).  A flagged edge_index gives exactly zero
+ * rows, as above. */
+int gm_epd_backward_inputs_only(const gm_model* m, const float* const* tensors, int n_tensors, const float* nodes,
+                                const float* edge_attr, int64_t n_nodes, int64_t n_edges, const float* grad_out,
+                                float* d_nodes /* [N, node_dim] or NULL */,
+                                float* d_edge_attr /* [E, edge_dim], caller's edge order, or NULL */, void* tape,
+                                size_t tape_bytes, void* ws, size_t ws_bytes, void* stream);
 
 /* The two standalone blocks under autograd -- the torch_graphnet surface the reference's own
  * EncProcDecGNN wiring calls (epd_gnn.py:30-33,42-45,88,101).  *_forward_train record a tape

@@ -1,14 +1,23 @@
 """Input gradients of a rollout step, timed with HIP events.  Prints one JSON line per shape.
 
-    python tools/bench_step_grad.py [--reps 10] [--warmup 2] [--shapes train,100k]
+    python tools/bench_step_grad.py [--reps 10] [--warmup 2] [--shapes train,100k] [--horizon 4] [--parent-lib PATH]
 
 Shapes: `train` = the training benchmark's graph (two collated 5000-node scenes, hidden 128, 10 message-passing steps) and
 `100k` = one scene of N = 100k.  Per shape, interleaved call by call:
   * `bwd` = gm_epd_backward and `bwd_inputs` = gm_epd_backward_inputs with both outputs, on the SAME tape of one training forward
     (the backward reads the tape and writes its own workspace): what d_nodes / d_edge_attr cost on top of the parameter gradients;
+    `bwd_inputs_only` = gm_epd_backward_inputs_only on that tape: what leaving the weight-gradient work out saves.  With
+    --parent-lib (a build of another commit's library, e.g. `python -m gnn_manip_amd.build --tag=parent` in a checkout of it),
+    `bwd_inputs_parent` = THAT library's gm_epd_backward_inputs, on a model handle and a tape of its own making, in the same
+    interleaving;
   * `step_fwd_bwd` = RolloutEngine.differentiable_step on the shape's state plus backward() of a seeded linear loss with respect to
     obs and rigid_target (the forward's one host read of the edge count included); `step_fwd` = the same forward under no_grad;
-  * `tape_bytes` = gm_train_tape_bytes of the step's graph.
+  * `tape_bytes` = gm_train_tape_bytes of the step's graph;
+  * `rollout_bwd_per_step` = the backward sweep of RolloutEngine.differentiable_rollout over --horizon steps (one re-run step and
+    its inputs-only backward per step), divided by the horizon; `rollout_fwd_per_step` its forward (the inference rollout plus one
+    window copy per step).  `rollout_peak_bytes` / `unrolled_peak_bytes`: torch.cuda.max_memory_allocated above the level before
+    the call, over forward + backward of that rollout and of the same horizon unrolled through differentiable_step (every
+    step's tape alive until backward()).
 Each time is one call between two events on the current stream; median and range over --reps calls.
 """
 import argparse
@@ -32,7 +41,27 @@ def _time(fn):
     return a.elapsed_time(b)
 
 
-def bench(name, scenes, reps, warmup, hidden=128, m_steps=10):
+def _load_parent(path):
+    """Another build of the library: only what the comparison calls, with this tree's prototypes (the ABI version is the same)."""
+    from gnn_manip_amd._lib import PROTOTYPES
+    P = C.CDLL(path)
+    for name in ("gm_model_create", "gm_model_destroy", "gm_train_tape_bytes", "gm_epd_forward_train",
+                 "gm_train_backward_inputs_workspace_bytes", "gm_epd_backward_inputs", "gm_last_error"):
+        fn = getattr(P, name)
+        fn.restype, fn.argtypes = PROTOTYPES[name]
+    return P
+
+
+def _peak(fn, dev):
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats(dev)
+    base = torch.cuda.memory_allocated(dev)
+    fn()
+    torch.cuda.synchronize()
+    return int(torch.cuda.max_memory_allocated(dev) - base)
+
+
+def bench(name, scenes, reps, warmup, hidden=128, m_steps=10, horizon=4, parent_lib=None):
     from gnn_manip_amd import EncProcDecGNN, GraphBoundedMultimaterialControl, RolloutEngine, scene
     from gnn_manip_amd._lib import ModelDesc, check, current_stream, lib, ptr
     from gnn_manip_amd.epd_gnn import _grad_arrays, _ws
@@ -71,7 +100,49 @@ def bench(name, scenes, reps, warmup, hidden=128, m_steps=10):
         check(L.gm_epd_backward_inputs(h, t_arr, len(tensors), ptr(nodes), ptr(edge_attr), n, e, ptr(grad_out), g_arr, ptr(d_nodes),
                                        ptr(d_edge_attr), ptr(tape), tape.numel(), ptr(ws), ws.numel(), current_stream()))
 
+    def bwd_inputs_only():
+        check(L.gm_epd_backward_inputs_only(h, t_arr, len(tensors), ptr(nodes), ptr(edge_attr), n, e, ptr(grad_out), ptr(d_nodes),
+                                            ptr(d_edge_attr), ptr(tape), tape.numel(), ptr(ws), ws.numel(), current_stream()))
+
+    model_calls = dict(bwd=bwd, bwd_inputs=bwd_inputs, bwd_inputs_only=bwd_inputs_only)
+    if parent_lib:
+        P = _load_parent(parent_lib)
+        hp = C.c_void_p()
+        assert P.gm_model_create(C.byref(d), t_arr, len(tensors), 1, current_stream(), C.byref(hp)) == 0, P.gm_last_error()
+        tape_p, ws_p, out_p = torch.empty_like(tape), torch.empty_like(ws), torch.empty_like(out)
+        assert P.gm_epd_forward_train(hp, ptr(nodes), n, ptr(edge_attr), ptr(ei.contiguous()), e, ptr(out_p), ptr(tape_p), tape_p.numel(),
+                                      current_stream()) == 0, P.gm_last_error()
+        dn_p, de_p = torch.empty_like(nodes), torch.empty_like(edge_attr)
+
+        def bwd_inputs_parent():
+            rc = P.gm_epd_backward_inputs(hp, t_arr, len(tensors), ptr(nodes), ptr(edge_attr), n, e, ptr(grad_out), g_arr, ptr(dn_p),
+                                          ptr(de_p), ptr(tape_p), tape_p.numel(), ptr(ws_p), ws_p.numel(), current_stream())
+            assert rc == 0, P.gm_last_error()
+        model_calls["bwd_inputs_parent"] = bwd_inputs_parent
+
     w_o = torch.randn_like(obs)
+    traj = torch.stack([target + 2e-4 * t for t in range(horizon)]).contiguous()
+    sweep = {}
+
+    def rollout_fwd_bwd():
+        o, tr = obs.detach().requires_grad_(), traj.detach().requires_grad_()
+        a, b, c = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+        a.record()
+        final = eng.differentiable_rollout(o, tr, horizon=horizon)
+        loss = (final * w_o).sum()
+        b.record()
+        loss.backward()
+        c.record()
+        c.synchronize()
+        sweep.setdefault("rollout_fwd_per_step", []).append(a.elapsed_time(b) / horizon)
+        sweep.setdefault("rollout_bwd_per_step", []).append(b.elapsed_time(c) / horizon)
+
+    def unrolled_fwd_bwd():
+        o, tr = obs.detach().requires_grad_(), traj.detach().requires_grad_()
+        cur = o
+        for t in range(horizon):
+            cur, _, _ = eng.differentiable_step(cur, tr[t], inputs_only=True)
+        (cur * w_o).sum().backward()
 
     def step_fwd():
         with torch.no_grad():
@@ -83,7 +154,7 @@ def bench(name, scenes, reps, warmup, hidden=128, m_steps=10):
         (nxt * w_o).sum().backward()
 
     t = {}
-    for group in (dict(bwd=bwd, bwd_inputs=bwd_inputs), dict(step_fwd=step_fwd, step_fwd_bwd=step_fwd_bwd)):
+    for group in (model_calls, dict(step_fwd=step_fwd, step_fwd_bwd=step_fwd_bwd)):
         for _ in range(warmup):
             for fn in group.values():
                 fn()
@@ -93,8 +164,17 @@ def bench(name, scenes, reps, warmup, hidden=128, m_steps=10):
         for _ in range(reps):
             for k, fn in group.items():
                 t[k].append(_time(fn))
-        if "bwd" in group:   # the tape and workspace of the first group are not needed by the second
+        if "bwd" in group:   # the tapes and workspaces of the first group are not needed by the second
             tape = ws = None
+            if parent_lib:
+                tape_p = ws_p = None
+                P.gm_model_destroy(hp)
+    rollout_fwd_bwd()                     # warm-up
+    sweep.clear()
+    for _ in range(max(1, reps // 2)):
+        rollout_fwd_bwd()
+    t.update(sweep)
+    peaks = dict(rollout_peak_bytes=_peak(rollout_fwd_bwd, dev), unrolled_peak_bytes=_peak(unrolled_fwd_bwd, dev))
     med = {k: float(np.median(v)) for k, v in t.items()}
     rec = dict(shape=name, nodes=n, edges=e, rigid=n_rigid, hidden=hidden, m_steps=m_steps, reps=reps,
                tape_bytes=int(L.gm_train_tape_bytes(C.byref(d), n, e)))
@@ -102,6 +182,10 @@ def bench(name, scenes, reps, warmup, hidden=128, m_steps=10):
         rec[k + "_ms"] = round(med[k], 4)
         rec[k + "_range_ms"] = [round(float(min(v)), 4), round(float(max(v)), 4)]
     rec["inputs_over_bwd"] = round(med["bwd_inputs"] / med["bwd"], 4)
+    rec["inputs_only_over_inputs"] = round(med["bwd_inputs_only"] / med["bwd_inputs"], 4)
+    if parent_lib:
+        rec["inputs_only_over_parent_inputs"] = round(med["bwd_inputs_only"] / med["bwd_inputs_parent"], 4)
+    rec.update(horizon=horizon, **peaks)
     print(json.dumps(rec), flush=True)
 
 
@@ -110,14 +194,18 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--shapes", default="train,100k")
+    ap.add_argument("--horizon", type=int, default=4)
+    ap.add_argument("--parent-lib", default=None)
     args = ap.parse_args()
     from gnn_manip_amd import scene
     assert torch.cuda.is_available(), "bench_step_grad.py measures on the GPU"
     for shape in args.shapes.split(","):
         if shape == "train":      # bench.py extra_train's batch
-            bench("train_2x5000", [scene.make_scene(5000, seed=100 + b, side=0.152 * 0.8) for b in range(2)], args.reps, args.warmup)
+            bench("train_2x5000", [scene.make_scene(5000, seed=100 + b, side=0.152 * 0.8) for b in range(2)], args.reps, args.warmup,
+                  horizon=args.horizon, parent_lib=args.parent_lib)
         elif shape == "100k":
-            bench("scene_100k", [scene.make_scene(100000, seed=1000)], args.reps, args.warmup)
+            bench("scene_100k", [scene.make_scene(100000, seed=1000)], args.reps, args.warmup, horizon=args.horizon,
+                  parent_lib=args.parent_lib)
         else:
             raise SystemExit(f"unknown shape {shape!r}")
 
