@@ -68,6 +68,8 @@ PROTOTYPES = {
     "gm_rigid_rank": (_i32, [_vp, _i64, _FD, _vp, _vp, _vp]),
     "gm_state_pre": (_i32, [_vp, _i64, _FD, _vp, _vp, _vp]),
     "gm_state_post": (_i32, [_vp, _i64, _FD, _vp, _vp, _vp, _vp]),
+    "gm_state_pre_backward": (_i32, [_vp, _i64, _FD, _vp, _i32, _vp, _vp, _vp]),
+    "gm_state_post_backward": (_i32, [_vp, _i64, _FD, _vp, _i32, _vp, _vp, _vp, _vp]),
     "gm_rigid_transform": (_i32, [_vp, _i64, _vp, _i64, C.POINTER(_f32 * 3), _vp, _vp]),
     "gm_rigid_transform_backward": (_i32, [_vp, _i64, _vp, _i64, C.POINTER(_f32 * 3), _vp, _vp, _vp]),
     "gm_model_num_tensors": (_i32, [_MD]),
@@ -103,6 +105,10 @@ PROTOTYPES = {
     "gm_rollout_renumber_workspace_bytes": (_sz, [_FD, _i64]),
     "gm_rollout": (_i32, [_vp, _vp, _i64, _FD, _i32, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _sz, _vp, _sz, _vp]),
     "gm_rollout_status": (_i32, [_vp, _MD, _i64, _i32, C.POINTER(_i64), _vp]),
+    "gm_rollout_step_backward_workspace_bytes": (_sz, [_MD, _FD, _i64, _i32]),
+    "gm_rollout_step_backward": (_i32, [_vp, _vp, _i32, _vp, _i64, _FD, _i32, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64), _vp, _sz, _vp]),
+    "gm_rollout_backward_workspace_bytes": (_sz, [_MD, _FD, _i64, _i32]),
+    "gm_rollout_backward": (_i32, [_vp, _vp, _i32, _vp, _i64, _FD, _i32, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "gm_model_profile": (_i32, [_vp, _i32]),
     "gm_model_set_edge_kernel": (_i32, [_vp, _i32]),
     "gm_model_profile_query": (_i32, [_vp, _i32, C.POINTER(_i64), C.POINTER(_f64)]),

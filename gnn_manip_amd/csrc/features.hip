@@ -438,6 +438,98 @@ __global__ void __launch_bounds__(256) integrate_bwd_kernel(const float* __restr
     }
 }
 
+// transpose of state_pre_kernel on one particle row, in place on `last` = that row of the last frame of the gradient: a rigid row's
+// control columns were overwritten by (target - xyz), or by xyz without a target, so their old values get nothing and xyz gets
+// -+ the control gradient on top of its own; gt (or nullptr) = the row of d_rigid_target the particle owns, written in full
+// (zeros without a target).  post_t (or nullptr): what state_post's transpose gave the same row of d_rigid_target, added first.
+__device__ __forceinline__ void state_pre_bwd_row(float* __restrict__ last, const FeatParams& P, bool has_target, float* __restrict__ gt,
+                                                  const float* __restrict__ post_t) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float gc = last[P.ctrl + a];
+        const float gx = last[P.cart + a];
+        last[P.cart + a] = has_target ? __fsub_rn(gx, gc) : __fadd_rn(gx, gc);
+        last[P.ctrl + a] = 0.f;
+        if (gt) gt[a] = has_target ? (post_t ? __fadd_rn(post_t[a], gc) : gc) : 0.f;
+    }
+}
+
+// transpose of state_pre_kernel: d_before[k][n][D] from d_after[k][n][D]; one thread owns row i of every frame
+__global__ void __launch_bounds__(256) state_pre_bwd_kernel(const float* __restrict__ d_after, int64_t n, FeatParams P,
+                                                             const int* __restrict__ rank, int has_target, float* __restrict__ d_before,
+                                                             float* __restrict__ d_target) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int64_t fs = n * P.D;
+    const float* in = d_after + i * P.D;
+    float* row = d_before + i * P.D;
+    for (int t = 0; t < P.k; ++t)
+        for (int d = 0; d < P.D; ++d) row[t * fs + d] = in[t * fs + d];
+    const int rk = rank[i];
+    if (rk >= 0) state_pre_bwd_row(row + (int64_t)(P.k - 1) * fs, P, has_target != 0, d_target ? d_target + (int64_t)rk * 3 : nullptr, nullptr);
+}
+
+// transpose of state_post_kernel: frame t of the window before the update is frame t - 1 after it (frame 0 fell out: zero); the
+// last frame before it also fed the last frame after it -- every column but xyz for a non-rigid row (xyz came from next_pos), the
+// whole row for a rigid one, less xyz where a scripted pose replaced it -- so its gradient is the sum of those two terms
+__global__ void __launch_bounds__(256) state_post_bwd_kernel(const float* __restrict__ d_after, int64_t n, FeatParams P,
+                                                              const int* __restrict__ rank, int has_target, float* __restrict__ d_before,
+                                                              float* __restrict__ d_next, float* __restrict__ d_target) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int64_t fs = n * P.D;
+    const float* in = d_after + i * P.D;
+    float* row = d_before + i * P.D;
+    for (int d = 0; d < P.D; ++d) row[d] = 0.f;
+    for (int t = 1; t + 1 < P.k; ++t)
+        for (int d = 0; d < P.D; ++d) row[t * fs + d] = in[(t - 1) * fs + d];
+    const int rk = rank ? rank[i] : -1;
+    const float* g_last = in + (int64_t)(P.k - 1) * fs;
+    const float* g_prev = in + (int64_t)(P.k - 2) * fs;
+    float* last = row + (int64_t)(P.k - 1) * fs;
+    const bool xyz_replaced = rk < 0 || has_target;
+    for (int d = 0; d < P.D; ++d) {
+        const bool xyz = d >= P.cart && d < P.cart + 3;
+        last[d] = (xyz && xyz_replaced) ? g_prev[d] : __fadd_rn(g_prev[d], g_last[d]);
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        d_next[i * 3 + a] = rk < 0 ? g_last[P.cart + a] : 0.f;
+        if (rk >= 0 && d_target) d_target[(int64_t)rk * 3 + a] = has_target ? g_last[P.cart + a] : 0.f;
+    }
+}
+
+// the gradient of a rollout step with respect to its pre-step window, assembled: one thread owns row i of every frame and adds,
+// in this order, state_post's transpose, the integrator's, the node features' and -- xyz of the last frame -- the edge features';
+// then the transpose of state_pre on that sum (pre != 0: the step ran the overwrite) and the row of d_rigid_target it owns:
+// state_post's share, then state_pre's
+__global__ void __launch_bounds__(256) step_assemble_bwd_kernel(const float* __restrict__ g_post, const float* __restrict__ g_int,
+                                                                 const float* __restrict__ g_nodes, const float* __restrict__ g_pos,
+                                                                 const float* __restrict__ t_post, int64_t n, FeatParams P,
+                                                                 const int* __restrict__ rank, int has_target, int pre,
+                                                                 float* __restrict__ d_before, float* __restrict__ d_target) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int64_t fs = n * P.D;
+    float* row = d_before + i * P.D;
+    for (int t = 0; t < P.k; ++t)
+        for (int d = 0; d < P.D; ++d) {
+            const int64_t at = i * P.D + t * fs + d;
+            float v = __fadd_rn(__fadd_rn(g_post[at], g_int[at]), g_nodes[at]);
+            if (t == P.k - 1 && d >= P.cart && d < P.cart + 3) v = __fadd_rn(v, g_pos[i * 3 + (d - P.cart)]);
+            row[t * fs + d] = v;
+        }
+    const int rk = rank ? rank[i] : -1;
+    if (rk < 0) return;
+    float* gt = d_target ? d_target + (int64_t)rk * 3 : nullptr;
+    if (pre) {
+        state_pre_bwd_row(row + (int64_t)(P.k - 1) * fs, P, has_target != 0, gt, t_post + (int64_t)rk * 3);
+    } else if (gt) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) gt[a] = has_target ? t_post[(int64_t)rk * 3 + a] : 0.f;
+    }
+}
+
 // edge_index [2][e] of the two sorts from the caller's separate rows
 __global__ void __launch_bounds__(256) edge_pair_kernel(const int64_t* __restrict__ snd, const int64_t* __restrict__ rcv, int64_t e,
                                                          int64_t* __restrict__ ei) {
@@ -519,6 +611,18 @@ static EdgeBwdWs carve_edge_bwd(void* ws, int64_t n, int64_t e) {
     w.ge = c.take<float>((size_t)3 * e);
     w.bytes = c.used();
     return w;
+}
+
+int rollout_assemble_backward(const float* g_post, const float* g_int, const float* g_nodes, const float* g_pos, const float* t_post,
+                              int64_t n, const gm_feature_desc* d, const int* rank, bool has_target, float* d_before, float* d_target,
+                              hipStream_t s) {
+    FeatParams P;
+    int rc = to_params(d, &P, "gm_rollout_step_backward");
+    if (rc != GM_OK) return rc;
+    hipLaunchKernelGGL(step_assemble_bwd_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, s, g_post, g_int, g_nodes, g_pos, t_post, n, P,
+                       rank, has_target ? 1 : 0, (rank && P.ctrl >= 0) ? 1 : 0, d_before, d_target);
+    GM_LAUNCH_CHECK();
+    return GM_OK;
 }
 
 }  // namespace gm
@@ -615,6 +719,38 @@ int gm_state_post(float* obs, int64_t n, const gm_feature_desc* desc, const floa
     if (n == 0) return GM_OK;
     hipLaunchKernelGGL(state_post_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, obs, n, P,
                        next_pos, rank, target);
+    GM_LAUNCH_CHECK();
+    return GM_OK;
+}
+
+int gm_state_pre_backward(const float* d_obs_after, int64_t n, const gm_feature_desc* desc, const int32_t* rank, int has_target,
+                          float* d_obs_before, float* d_rigid_target, void* stream) {
+    gm::DevGuard dev_guard(d_obs_after);
+    FeatParams P;
+    int rc = to_params(desc, &P, "gm_state_pre_backward");
+    if (rc != GM_OK) return rc;
+    GM_REQUIRE(P.ctrl >= 0, GM_ERR_INVALID_ARGUMENT, "gm_state_pre_backward: descriptor has no control columns");
+    GM_REQUIRE(n >= 0 && (n == 0 || (d_obs_after && d_obs_before && rank)), GM_ERR_INVALID_ARGUMENT, "gm_state_pre_backward: null pointer");
+    GM_REQUIRE(d_obs_after != d_obs_before || n == 0, GM_ERR_INVALID_ARGUMENT, "gm_state_pre_backward: d_obs_before must not be d_obs_after");
+    if (n == 0) return GM_OK;
+    hipLaunchKernelGGL(state_pre_bwd_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, d_obs_after, n, P, rank,
+                       has_target ? 1 : 0, d_obs_before, d_rigid_target);
+    GM_LAUNCH_CHECK();
+    return GM_OK;
+}
+
+int gm_state_post_backward(const float* d_obs_after, int64_t n, const gm_feature_desc* desc, const int32_t* rank, int has_target,
+                           float* d_obs_before, float* d_next_pos, float* d_rigid_target, void* stream) {
+    gm::DevGuard dev_guard(d_obs_after);
+    FeatParams P;
+    int rc = to_params(desc, &P, "gm_state_post_backward");
+    if (rc != GM_OK) return rc;
+    GM_REQUIRE(n >= 0 && (n == 0 || (d_obs_after && d_obs_before && d_next_pos)), GM_ERR_INVALID_ARGUMENT,
+               "gm_state_post_backward: null pointer");
+    GM_REQUIRE(d_obs_after != d_obs_before || n == 0, GM_ERR_INVALID_ARGUMENT, "gm_state_post_backward: d_obs_before must not be d_obs_after");
+    if (n == 0) return GM_OK;
+    hipLaunchKernelGGL(state_post_bwd_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, d_obs_after, n, P, rank,
+                       has_target ? 1 : 0, d_obs_before, d_next_pos, d_rigid_target);
     GM_LAUNCH_CHECK();
     return GM_OK;
 }

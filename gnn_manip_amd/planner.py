@@ -340,21 +340,24 @@ class TrajectoryCMAsolver:
         return [self._assemble_loss(float(w[i]), acts[i], X[i] if self._loss_takes_x else None)[0] for i in range(len(X))]
 
     # ---- gradient of the objective
-    def loss_and_grad(self, x, edges=None):
+    def loss_and_grad(self, x, edges=None, sweep="autograd"):
         """The objective of ``cma_objective(x)`` and its gradient with respect to the search vector: (loss: float, grad: array like
         x).  The map from x to the poses is restated in float64 torch (``interpolate_trajectory_torch``: clip, running sums;
         ``rigid_body_trajectory``), the rollout is ``RolloutEngine.differentiable_rollout`` (memory of one step's tape whatever the
         horizon; the model's parameters are constants), the end cloud goes into the differentiable ``SamplesLoss``, and the
         velocity / acceleration norms are float64 torch.  The boundary penalty is piecewise constant in x: it is added to the
         value and contributes nothing to the gradient.  Which optimiser to drive with this gradient is left open.
-        edges: a list that receives the ``edge_index`` of every step of the backward's recomputation (diagnostics, tests)."""
+        edges: a list that receives the ``edge_index`` of every step of the backward's recomputation (diagnostics, tests).
+        sweep: ``differentiable_rollout``'s keyword -- "library" runs the rollout's reverse sweep as one library call (and hands out no
+        edge lists: ``edges`` must then be None)."""
         x_np = np.asarray(x, dtype=np.float64)
         xt = torch.tensor(x_np.reshape(-1), dtype=torch.float64, requires_grad=True)
         rot, ty = interpolate_trajectory_torch(xt, self.sample_traj.shape[0], float(self.rx_init), self.scale_rot, self.scale_ty,
                                                float(self.max_rot), self.max_ty)
         h = self.horizon
         traj = rigid_body_trajectory(rot, ty, h, self.ty_init, self.rigid_particles)
-        out = self._engine(1).differentiable_rollout(self.initial_state[0].contiguous(), traj, horizon=h, return_edges=edges is not None)
+        out = self._engine(1).differentiable_rollout(self.initial_state[0].contiguous(), traj, horizon=h, return_edges=edges is not None,
+                                                     sweep=sweep)
         final, step_edges = out if edges is not None else (out, None)
         c0 = self.graph_attr.cartesian_idx[0]
         end = final[-1].index_select(0, self._coffee_rows)[:, c0:c0 + 3]

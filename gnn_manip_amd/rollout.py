@@ -104,6 +104,33 @@ class _RolloutFunction(torch.autograd.Function):
         return None, (d_window if ctx.needs_input_grad[1] else None), d_traj, None, None
 
 
+class _RolloutLibraryFunction(torch.autograd.Function):
+    """RolloutEngine.differentiable_rollout(sweep="library"): _RolloutFunction's forward with the windows kept in one [T, k, N, D]
+    array, and the whole reverse sweep as one gm_rollout_backward call."""
+
+    @staticmethod
+    def forward(ctx, engine, obs0, trajectory, steps):
+        obs = obs0.detach().clone().contiguous()
+        traj = None if trajectory is None else trajectory.detach().contiguous().float()
+        engine.set_scene(obs)
+        windows = torch.empty((steps,) + tuple(obs.shape), dtype=torch.float32, device=obs.device)
+        for t in range(steps):
+            windows[t].copy_(obs)          # the pre-step window of step t
+            engine.step(obs, None if traj is None else traj[t])
+        engine.status()
+        ctx.engine, ctx.windows, ctx.traj, ctx.steps = engine, windows, traj, steps
+        ctx.scene = (engine.rigid_rank, engine.n_rigid)
+        return obs
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_final):
+        need_traj = ctx.traj is not None and ctx.needs_input_grad[2]
+        d_obs0, d_traj = ctx.engine._sweep_backward(ctx.windows, ctx.traj, ctx.steps, d_final.contiguous().float(), ctx.scene, need_traj)
+        ctx.windows = None
+        return None, (d_obs0 if ctx.needs_input_grad[1] else None), d_traj, None
+
+
 class RolloutEngine:
     """Runs rollouts of an ``EncProcDecGNN`` for scenes of ``n_nodes`` particles.
 
@@ -243,7 +270,73 @@ class RolloutEngine:
         new_last[rows] = keep
         return torch.cat((obs_pre[1:], new_last.unsqueeze(0))), pred, edge_index
 
-    def differentiable_rollout(self, obs0, trajectory=None, horizon=None, return_edges=False):
+    def _training_model(self):
+        """(gm_model handle, its parameter tensors, their pointer array, descriptor) of the model as the training entry points run
+        it: the module's own at a hidden size of 64 / 128 / 256, the zero-padded one otherwise (EncProcDecGNN._padded_training).
+        The parameters are constants here."""
+        from .epd_gnn import TRAIN_WIDTHS
+        m = self.model
+        params = [p.detach() for p in m.parameters()]
+        if m.dims[3] in TRAIN_WIDTHS:
+            desc_t, tensors, h = m.model_desc(), params, m.device_handle(self.device)
+        else:
+            with torch.no_grad():
+                (desc_t, handle), tensors = m._padded_training(params)
+            h = handle.get(desc_t, tensors, self.device, tuple(params))
+        tensors = [t.to(device=self.device, dtype=torch.float32).contiguous() for t in tensors]
+        t_arr = (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+        return h, tensors, t_arr, ModelDesc(*desc_t)
+
+    def _backward_ws(self, mdesc):
+        """The reverse sweep's workspace (the step's is its head): sized by n and max_neighbours, allocated at first use."""
+        need = lib().gm_rollout_backward_workspace_bytes(C.byref(mdesc), C.byref(self.fdesc), self.n, self.max_neighbours)
+        if need == 0:
+            raise ValueError("RolloutEngine: no backward workspace for these sizes")
+        if getattr(self, "_bwd_ws", None) is None or self._bwd_ws.numel() < need:
+            self._bwd_ws = _ws(need, self.device)
+        return self._bwd_ws
+
+    def _check_grad(self, g, name):
+        if not (isinstance(g, torch.Tensor) and g.device == self.device and g.dtype == torch.float32 and g.is_contiguous()
+                and tuple(g.shape) == (self.k, self.n, self.data_dim)):
+            raise ValueError(f"{name} must be contiguous float32 [{self.k}, {self.n}, {self.data_dim}] on {self.device}")
+
+    def step_backward(self, obs_before, rigid_target, d_obs_after, return_edge_count=False):
+        """The vector-Jacobian product of one ``step`` inside the library (gm_rollout_step_backward): (d_obs_before [k, N, D],
+        d_rigid_target [N_rigid, 3] or None without a target) from the pre-step window, the step's scripted pose and the gradient
+        with respect to the window the step left.  The model's parameters are constants.  ``set_scene`` must have been called;
+        ``obs_before`` is not written.  One host synchronisation (the edge count, returned third when asked for)."""
+        self._check_state(obs_before, rigid_target, None, True)
+        self._check_grad(d_obs_after, "d_obs_after")
+        h, tensors, t_arr, mdesc = self._training_model()
+        ws = self._backward_ws(mdesc)
+        d_obs = torch.empty_like(obs_before)
+        d_tgt = None if rigid_target is None else torch.empty_like(rigid_target)
+        e = C.c_int64(0)
+        check(lib().gm_rollout_step_backward(h, t_arr, len(tensors), ptr(obs_before), self.n, C.byref(self.fdesc), self.max_neighbours,
+                                             ptr(self.rigid_rank), ptr(rigid_target), ptr(d_obs_after), ptr(d_obs), ptr(d_tgt), C.byref(e),
+                                             ptr(ws), ws.numel(), current_stream()))
+        return (d_obs, d_tgt, int(e.value)) if return_edge_count else (d_obs, d_tgt)
+
+    def _sweep_backward(self, windows, traj, steps, d_final, scene, need_traj):
+        """gm_rollout_backward on the windows a forward kept: (d_obs0, d_trajectory or None)."""
+        rank, n_rigid = scene
+        self._check_grad(d_final, "d_final")
+        if traj is not None and (tuple(traj.shape[1:]) != (n_rigid, 3) or traj.dtype != torch.float32 or not traj.is_contiguous()):
+            raise ValueError(f"trajectory must be contiguous float32 [T, {n_rigid}, 3], got {tuple(traj.shape)}")
+        if tuple(windows.shape) != (steps, self.k, self.n, self.data_dim) or not windows.is_contiguous():
+            raise ValueError(f"windows must be contiguous [{steps}, {self.k}, {self.n}, {self.data_dim}], got {tuple(windows.shape)}")
+        h, tensors, t_arr, mdesc = self._training_model()
+        ws = self._backward_ws(mdesc)
+        d_obs0 = torch.empty_like(d_final)
+        d_traj = torch.empty_like(traj) if need_traj else None
+        n_targets = 0 if traj is None else int(traj.shape[0])
+        check(lib().gm_rollout_backward(h, t_arr, len(tensors), ptr(windows), self.n, C.byref(self.fdesc), self.max_neighbours, ptr(rank),
+                                        ptr(traj), n_targets, n_rigid, steps, ptr(d_final), ptr(d_obs0), ptr(d_traj), ptr(ws), ws.numel(),
+                                        current_stream()))
+        return d_obs0, d_traj
+
+    def differentiable_rollout(self, obs0, trajectory=None, horizon=None, return_edges=False, sweep="autograd"):
         """``rollout(obs0, trajectory, horizon)`` under autograd: returns the final state [k, N, D], bit-equal to ``rollout``'s
         (an engine that renumbers, see ``renumber``, sums a node's messages in another order inside ``rollout``: equal to
         rounding there), with gradients to ``obs0`` (position and control columns) and to ``trajectory`` [T, N_rigid, 3].  The
@@ -259,13 +352,24 @@ class RolloutEngine:
 
         return_edges: the call returns (final state, edges), where ``edges`` is a list that the BACKWARD fills with the T
         ``edge_index`` tensors [2, E_t] of its recomputation (empty until then), so that a reference computation can be held to
-        the same graphs.  ``candidates`` > 1 works as in ``differentiable_step``."""
+        the same graphs.  ``candidates`` > 1 works as in ``differentiable_step``.
+
+        sweep: "autograd" (the default) is the backward described above.  "library" keeps the windows in one [T, k, N, D] array and
+        runs the whole reverse sweep as ONE library call (gm_rollout_backward: per step the same forward and backward entry
+        points, the state updates' transposes and the sum of the contributions as HIP kernels, no autograd node and no Python
+        between steps; still one edge-count read per step).  It hands out no edge lists: ``return_edges`` raises ValueError."""
+        if sweep not in ("autograd", "library"):
+            raise ValueError(f"sweep must be 'autograd' or 'library', got {sweep!r}")
+        if sweep == "library" and return_edges:
+            raise ValueError("sweep='library' hands out no edge lists: return_edges needs sweep='autograd'")
         steps = int(horizon) if horizon is not None else (int(trajectory.shape[0]) if trajectory is not None else 0)
         self._check_state(obs0, None, None, False)
         if trajectory is not None:
             if (trajectory.device != self.device or trajectory.dim() != 3 or int(trajectory.shape[0]) < steps
                     or int(trajectory.shape[2]) != 3):
                 raise ValueError(f"trajectory must be [T >= {steps}, N_rigid, 3] on {self.device}, got {tuple(trajectory.shape)}")
+        if sweep == "library":
+            return _RolloutLibraryFunction.apply(self, obs0, trajectory, steps)
         edges = [] if return_edges else None
         out = _RolloutFunction.apply(self, obs0, trajectory, steps, edges)
         return (out, edges) if return_edges else out

@@ -190,6 +190,25 @@ int gm_node_features_backward(const float* obs, int64_t n_nodes, const gm_featur
 int gm_integrate_backward(const float* d_next_pos /*[N,3]*/, int64_t n_nodes, const gm_feature_desc* desc,
                           float* d_pred /*[N,3]*/, float* d_obs /*[k,N,D]*/, void* stream);
 
+/* Transposes of the two state updates (the reverse sweep of a rollout): the gradient with respect to the window BEFORE the update,
+ * d_obs_before [k,N,D], from the gradient with respect to the window after it, d_obs_after [k,N,D] (another buffer).  Both are
+ * linear maps of the window, so no state is read: has_target says whether the update was given a rigid_target.  Outputs are
+ * written in full by one thread per particle row; d_rigid_target [N_rigid,3] may be NULL, and without a target it is written as
+ * zeros.  Every element is a copy, a negation or a sum of two float32 terms: no float atomics, the same bits every time.
+ * gm_state_pre_backward: a rigid row's control columns were overwritten with (target - xyz), or xyz without a target: their old
+ *   values get zero, xyz gets its own gradient MINUS (with a target) or PLUS (without) the control columns' gradient, and
+ *   d_rigid_target gets the control columns' gradient.  Every other element is copied.  A descriptor without control columns is
+ *   refused, as by gm_state_pre.
+ * gm_state_post_backward: frame 0 gets zero (it fell out of the window), frame t gets frame t - 1 of d_obs_after, and the last
+ *   frame gets frame k - 2 PLUS frame k - 1 of d_obs_after in the columns it passed on: every column but xyz for a non-rigid row,
+ *   whose xyz gradient is d_next_pos [N,3]; the whole row for a rigid row without a target (zero d_next_pos); every column but
+ *   xyz for a rigid row with one, whose xyz gradient is d_rigid_target.  rigid_rank NULL: no rigid rows, d_rigid_target untouched. */
+int gm_state_pre_backward(const float* d_obs_after, int64_t n_nodes, const gm_feature_desc* desc, const int32_t* rigid_rank,
+                          int has_target, float* d_obs_before, float* d_rigid_target /* [N_rigid,3] or NULL */, void* stream);
+int gm_state_post_backward(const float* d_obs_after, int64_t n_nodes, const gm_feature_desc* desc,
+                           const int32_t* rigid_rank /* or NULL */, int has_target, float* d_obs_before, float* d_next_pos /*[N,3]*/,
+                           float* d_rigid_target /* [N_rigid,3] or NULL */, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Model.  Replaces EncProcDecGNN.__init__/_build_mlp + load_state_dict
  *         gnn_manip/models/epd_gnn.py:13-49,72-84 ; rollout_utils.py:137-139.
@@ -425,6 +444,53 @@ int gm_rollout(const gm_model* m, float* obs /*[k,N,D] in/out*/, int64_t n_nodes
 /* Error flags / edge count of the last step (synchronises). */
 int gm_rollout_status(const void* rollout_ws, const gm_model_desc* desc, int64_t n_nodes,
                       int max_neighbours, int64_t* n_edges_host, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The reverse sweep of a rollout (no reference counterpart: the reference's planner is derivative-free, traj_utils.py:247-259).
+ * gm_rollout_step_backward is the vector-Jacobian product of ONE gm_rollout_step with the model's parameters as constants:
+ * d_obs_before [k,N,D] and d_rigid_target [N_rigid,3] (may be NULL; zeros without a rigid_target) from d_obs_after [k,N,D], the
+ * gradient with respect to the window the step left.  obs_before is the window the step started from and is not written.
+ *
+ * The call re-runs the step's forward out of place on a copy of obs_before in the workspace, with a tape -- gm_state_pre,
+ * gm_node_features, gm_radius_graph_build_batched (nodes_per_graph of the descriptor: a block-diagonal batch), gm_radius_graph_edges,
+ * gm_edge_features, gm_epd_forward_train (whose destination sort opens its tape) -- and then runs, in this order,
+ * gm_state_post_backward, gm_integrate_backward, gm_epd_backward_inputs_only, gm_node_features_backward and
+ * gm_edge_features_backward.  The radius graph is a constant of the step (connectivity is piecewise constant in the positions).
+ * Those transposes write window-sized or [N,3] contributions of their own; ONE last launch, one thread per particle row owning
+ * that row in every frame, adds them in a fixed order,
+ *     ((state_post's + integrator's) + node features') + edge features' (xyz of the last frame),
+ * applies gm_state_pre_backward's rule to the sum where the step ran the overwrite (rigid_rank given, control columns exist) and
+ * writes the row of d_rigid_target it owns as state_post's share + state_pre's share.  No float atomics: the same call twice
+ * gives the same bits, and a scene of a batch gets the bits it gets alone.
+ *
+ * `tensors` / n_tensors: the parameter values the handle was created from (device pointers, gm_epd_backward_inputs_only's
+ * argument).  Hidden sizes 64 / 128 / 256 (the training entry points).  HOST SYNCHRONISATION: the training forward takes the
+ * edge count on the host, so the call reads that one number back (gm_radius_graph_num_edges) per step; n_edges_host (may be NULL)
+ * returns it.  A non-finite position is reported there (GM_ERR_DATA).  The workspace depends on n_nodes and max_neighbours alone
+ * (edge capacity n_nodes * max_neighbours), never on a horizon; nothing in it needs initialising.
+ *
+ * gm_rollout_backward is the whole sweep: windows [steps,k,N,D] are the pre-step windows a forward kept (window t = the state
+ * before step t), trajectory [n_targets,N_rigid,3] or NULL the scripted poses with gm_rollout's rule (step t uses pose t, steps
+ * past n_targets have none), d_final [k,N,D] the gradient with respect to the final state.  Outputs: d_obs0 [k,N,D] and
+ * d_trajectory [n_targets,N_rigid,3] (may be NULL), whose rows of steps at or past `steps` are written as zeros.  steps == 0 copies
+ * d_final to d_obs0.  It is a loop of gm_rollout_step_backward from the last step to the first; two [k,N,D] gradient windows take
+ * turns behind the step's workspace, so the workspace is the step's plus those two, whatever `steps` is.  One host
+ * synchronisation per step, as above.
+ * ------------------------------------------------------------------------------------------ */
+size_t gm_rollout_step_backward_workspace_bytes(const gm_model_desc* desc, const gm_feature_desc* fdesc, int64_t n_nodes,
+                                                int max_neighbours);
+int gm_rollout_step_backward(const gm_model* m, const float* const* tensors, int n_tensors, const float* obs_before /*[k,N,D]*/,
+                             int64_t n_nodes, const gm_feature_desc* fdesc, int max_neighbours, const int32_t* rigid_rank,
+                             const float* rigid_target /*[Nr,3] or NULL*/, const float* d_obs_after /*[k,N,D]*/,
+                             float* d_obs_before /*[k,N,D]*/, float* d_rigid_target /*[Nr,3] or NULL*/,
+                             int64_t* n_edges_host /* or NULL */, void* ws, size_t ws_bytes, void* stream);
+size_t gm_rollout_backward_workspace_bytes(const gm_model_desc* desc, const gm_feature_desc* fdesc, int64_t n_nodes,
+                                           int max_neighbours);
+int gm_rollout_backward(const gm_model* m, const float* const* tensors, int n_tensors, const float* windows /*[steps,k,N,D]*/,
+                        int64_t n_nodes, const gm_feature_desc* fdesc, int max_neighbours, const int32_t* rigid_rank,
+                        const float* trajectory /*[n_targets,Nr,3] or NULL*/, int64_t n_targets, int64_t n_rigid, int64_t steps,
+                        const float* d_final /*[k,N,D]*/, float* d_obs0 /*[k,N,D]*/, float* d_trajectory /*[n_targets,Nr,3] or NULL*/,
+                        void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Measurement hooks (no reference counterpart; the reference only wraps model.forward in

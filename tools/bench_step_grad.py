@@ -18,6 +18,14 @@ Shapes: `train` = the training benchmark's graph (two collated 5000-node scenes,
     window copy per step).  `rollout_peak_bytes` / `unrolled_peak_bytes`: torch.cuda.max_memory_allocated above the level before
     the call, over forward + backward of that rollout and of the same horizon unrolled through differentiable_step (every
     step's tape alive until backward()).
+  * the reverse sweep inside the library, against the autograd one, in the same run: `lib_step_bwd` = one
+    RolloutEngine.step_backward (gm_rollout_step_backward: the step's forward with a tape and every transpose, one library call)
+    and `autograd_step_bwd` = one step of the autograd sweep, the body of the loop in _RolloutFunction.backward (differentiable_step
+    with inputs_only on the window under enable_grad, then torch.autograd.grad), both on the same window, pose and upstream
+    gradient, interleaved call by call; `rollout_lib_bwd_per_step` / `rollout_lib_fwd_per_step` / `rollout_lib_peak_bytes` = the
+    rollout figures above with differentiable_rollout(sweep="library").  `sweep_ws_bytes` = gm_rollout_backward_workspace_bytes
+    (sized for N x max_neighbours edges whatever the graph holds; the engine keeps it once allocated, so the peak of a later call
+    does not count it: it is reported next to the peaks).
 Each time is one call between two events on the current stream; median and range over --reps calls.
 """
 import argparse
@@ -124,18 +132,31 @@ def bench(name, scenes, reps, warmup, hidden=128, m_steps=10, horizon=4, parent_
     traj = torch.stack([target + 2e-4 * t for t in range(horizon)]).contiguous()
     sweep = {}
 
-    def rollout_fwd_bwd():
+    def rollout_fwd_bwd(which="autograd", key="rollout"):
         o, tr = obs.detach().requires_grad_(), traj.detach().requires_grad_()
         a, b, c = (torch.cuda.Event(enable_timing=True) for _ in range(3))
         a.record()
-        final = eng.differentiable_rollout(o, tr, horizon=horizon)
+        final = eng.differentiable_rollout(o, tr, horizon=horizon, sweep=which)
         loss = (final * w_o).sum()
         b.record()
         loss.backward()
         c.record()
         c.synchronize()
-        sweep.setdefault("rollout_fwd_per_step", []).append(a.elapsed_time(b) / horizon)
-        sweep.setdefault("rollout_bwd_per_step", []).append(b.elapsed_time(c) / horizon)
+        sweep.setdefault(key + "_fwd_per_step", []).append(a.elapsed_time(b) / horizon)
+        sweep.setdefault(key + "_bwd_per_step", []).append(b.elapsed_time(c) / horizon)
+
+    def rollout_lib_fwd_bwd():
+        rollout_fwd_bwd("library", "rollout_lib")
+
+    def lib_step_bwd():
+        eng.step_backward(obs, target, w_o)
+
+    def autograd_step_bwd():      # the body of the loop in _RolloutFunction.backward
+        with torch.enable_grad():
+            w = obs.detach().requires_grad_(True)
+            pose = target.detach().clone().requires_grad_(True)
+            nxt, _, _ = eng.differentiable_step(w, pose, inputs_only=True)
+        torch.autograd.grad(nxt, [w, pose], grad_outputs=w_o)
 
     def unrolled_fwd_bwd():
         o, tr = obs.detach().requires_grad_(), traj.detach().requires_grad_()
@@ -154,7 +175,8 @@ def bench(name, scenes, reps, warmup, hidden=128, m_steps=10, horizon=4, parent_
         (nxt * w_o).sum().backward()
 
     t = {}
-    for group in (model_calls, dict(step_fwd=step_fwd, step_fwd_bwd=step_fwd_bwd)):
+    for group in (model_calls, dict(step_fwd=step_fwd, step_fwd_bwd=step_fwd_bwd),
+                  dict(lib_step_bwd=lib_step_bwd, autograd_step_bwd=autograd_step_bwd)):
         for _ in range(warmup):
             for fn in group.values():
                 fn()
@@ -170,11 +192,15 @@ def bench(name, scenes, reps, warmup, hidden=128, m_steps=10, horizon=4, parent_
                 tape_p = ws_p = None
                 P.gm_model_destroy(hp)
     rollout_fwd_bwd()                     # warm-up
+    rollout_lib_fwd_bwd()
     sweep.clear()
-    for _ in range(max(1, reps // 2)):
+    for _ in range(max(1, reps // 2)):    # the two sweeps interleaved
         rollout_fwd_bwd()
+        rollout_lib_fwd_bwd()
     t.update(sweep)
-    peaks = dict(rollout_peak_bytes=_peak(rollout_fwd_bwd, dev), unrolled_peak_bytes=_peak(unrolled_fwd_bwd, dev))
+    peaks = dict(rollout_peak_bytes=_peak(rollout_fwd_bwd, dev), rollout_lib_peak_bytes=_peak(rollout_lib_fwd_bwd, dev),
+                 unrolled_peak_bytes=_peak(unrolled_fwd_bwd, dev),
+                 sweep_ws_bytes=int(L.gm_rollout_backward_workspace_bytes(C.byref(d), C.byref(eng.fdesc), eng.n, eng.max_neighbours)))
     med = {k: float(np.median(v)) for k, v in t.items()}
     rec = dict(shape=name, nodes=n, edges=e, rigid=n_rigid, hidden=hidden, m_steps=m_steps, reps=reps,
                tape_bytes=int(L.gm_train_tape_bytes(C.byref(d), n, e)))
@@ -185,6 +211,8 @@ def bench(name, scenes, reps, warmup, hidden=128, m_steps=10, horizon=4, parent_
     rec["inputs_only_over_inputs"] = round(med["bwd_inputs_only"] / med["bwd_inputs"], 4)
     if parent_lib:
         rec["inputs_only_over_parent_inputs"] = round(med["bwd_inputs_only"] / med["bwd_inputs_parent"], 4)
+    rec["lib_over_autograd_step"] = round(med["lib_step_bwd"] / med["autograd_step_bwd"], 4)
+    rec["lib_over_autograd_sweep"] = round(med["rollout_lib_bwd_per_step"] / med["rollout_bwd_per_step"], 4)
     rec.update(horizon=horizon, **peaks)
     print(json.dumps(rec), flush=True)
 
