@@ -111,6 +111,7 @@ PROTOTYPES = {
     "gm_rollout_backward": (_i32, [_vp, _vp, _i32, _vp, _i64, _FD, _i32, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "gm_model_profile": (_i32, [_vp, _i32]),
     "gm_model_set_edge_kernel": (_i32, [_vp, _i32]),
+    "gm_model_set_node_fusion": (_i32, [_vp, _i32]),
     "gm_model_profile_query": (_i32, [_vp, _i32, C.POINTER(_i64), C.POINTER(_f64)]),
 }
 

@@ -90,6 +90,9 @@ struct ProjSysArgs {
     ProfState* prof;
 };
 int launch_proj_sys(const ProjSysArgs& a, hipStream_t s);
+// launch_node_sys(a) and launch_proj_sys(p) as one launch (sys_node_proj_kernel): p.h = a.h_out, p.Q = a.Q, the same n and flags.
+// Every workgroup projects the rows it has just written; the results are those of the two launches, bit for bit.
+int launch_node_proj_sys(const NodeSysArgs& a, const ProjSysArgs& p, hipStream_t s);
 int launch_agg_stitch(float* agg, const float* side, const EdgeBlocks& t, int64_t n, ProfState* prof, hipStream_t s);
 // Graphs from this size take the systolic node path (a workgroup needs blocks to pipeline).  The size that counts is ONE GRAPH's
 // (the rollout step passes nodes_per_graph of a block-diagonal batch): the systolic and the streamed node kernels add a row's terms in

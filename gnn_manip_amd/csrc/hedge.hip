@@ -78,6 +78,7 @@ __device__ unsigned long long g_sys_stamps[3 * 32 * 8 + 32];   // + the 100 MHz 
 constexpr int ST_STREAM_E = 2 | 16, ST_STREAM_AGG = 16;
 constexpr int ST_ENC_E = 0;     // the edge encoder's e stores: default policy
 constexpr int ST_PROJ_Q = 16;   // the projection kernel's Q stores: sc1 (read once, by the node kernel behind the next edge launch)
+constexpr int LD_SC1 = 16;      // loads served by L2, past the CU's L1 (sys_node_proj_kernel's h' rows)
 constexpr int HW_HEADER_FLOATS = 4;            // T1, 1/T3, cap of the per-row input scale (encoder image), pad
 constexpr int HW_VEC_FLOATS = 5 * H;           // b2*T2 | b3*T3 | gamma | beta | b1*T1 (the encoder's; a processor step has b1 in P)
 constexpr int HW_IMAGE_HALF8 = 3 * 4 * 8 * 2 * 64;   // [layer][jb][ks][part][lane]
@@ -342,6 +343,29 @@ struct LnGroup {
     _Pragma("unroll 1") for (int t_ = (FIRST); t_ <= (last); t_ += 2) {                \
         tick(std::integral_constant<int, (FIRST) & 1>{}, t_);                          \
         tick(std::integral_constant<int, 1 - ((FIRST) & 1)>{}, t_ + 1);                \
+    }
+
+// Kinds of tick of the node and projection kernels.  A pipeline's first tick has no block to multiply yet and its last one
+// none any more: run as full ticks they would spend a whole MFMA chain per wave on buffers nobody reads.  TICK_FILL / TICK_DRAIN
+// are those ticks with the work that later ticks or the results need -- requests, rows -> image, the last block's epilogue --
+// and nothing else.
+constexpr int TICK_FULL = 0, TICK_FILL = 1, TICK_DRAIN = 2;
+template <int V>
+using int_c = std::integral_constant<int, V>;
+
+// The node kernel's ticks -1 .. nb + 2 (tick t: Linear 1 of block t, Linear 2 of block t - 1, Linear 3 of block t - 2, epilogue of
+// block t - 3): a fill tick, the full ticks 0 .. nb + 1 in pairs (and one alone when nb is odd), a drain tick.
+#define NODE_TICKS(tick_as)                                                                          \
+    {                                                                                                \
+        auto tick = [&](auto par_c, int t) { tick_as(par_c, int_c<TICK_FULL>{}, t); };               \
+        tick_as(int_c<1>{}, int_c<TICK_FILL>{}, -1);                                                 \
+        RUN_TICKS(0, nb, tick);                                                                      \
+        if (nb & 1) {                                                                                \
+            tick(int_c<0>{}, nb + 1);                                                                \
+            tick_as(int_c<1>{}, int_c<TICK_DRAIN>{}, nb + 2);                                        \
+        } else {                                                                                     \
+            tick_as(int_c<0>{}, int_c<TICK_DRAIN>{}, nb + 2);                                        \
+        }                                                                                            \
     }
 
 // range check of the fp16 split (rng: set once an accumulator row turned NaN): one report per wave.  flags may be null, except
@@ -889,8 +913,9 @@ constexpr int LN_VEC = LN_ZERO_END;                // 4 x 128 floats: b2 T2 | b3
 constexpr size_t NODE_LDS_BYTES = LN_VEC + 4 * H * 4;
 static_assert(NODE_LDS_BYTES <= 160 * 1024, "LDS budget");
 
-__global__ void __launch_bounds__(SYS_THREADS, 1) sys_node_kernel(const float* a_h, const float* __restrict__ a_agg, const float* __restrict__ a_Q,
-                                                                       float* a_h_out, const float* __restrict__ a_hw, int a_n, int* a_flags, float a_eps) {
+// The kernel's body as a function: sys_node_kernel is this alone, sys_node_proj_kernel runs the projections behind it.
+__device__ __forceinline__ void sys_node_body(const float* a_h, const float* __restrict__ a_agg, const float* __restrict__ a_Q,
+                                              float* a_h_out, const float* __restrict__ a_hw, int a_n, int* a_flags, float a_eps) {
     const int tid = threadIdx.x, lane0 = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int role = wave >> 2, jb = wave & 3;
@@ -927,8 +952,12 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_node_kernel(const float* a
 #pragma unroll
         for (int r = 0; r < 16; ++r) c0v[r] = 0.f;
         auto clampb = [&](int x) { return x < b0 ? b0 : (x < b1 ? x : b1 - 1); };
-        auto tick = [&](auto par_c, int t) {
-            constexpr int PAR = decltype(par_c)::value;
+        auto tick_as = [&](auto par_c, auto kind_c, int t) {
+            constexpr int PAR = decltype(par_c)::value, KIND = decltype(kind_c)::value;
+            if constexpr (KIND == TICK_DRAIN) {   // Linear 1 has no block left and nothing to prepare
+                lds_barrier();
+                return;
+            }
             const int x = b0 + t;
             const unsigned rel1 = (unsigned)(clampb(x + 1) - b0) * (BE * 512u), rel2 = (unsigned)(clampb(x + 2) - b0) * (BE * 512u);
 #pragma unroll
@@ -945,10 +974,15 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_node_kernel(const float* a
                     for (int j = 0; j < 4; ++j) eq[j] = bld4(srd_a, v_eoff, rel2 + j * 4096);
                 }
             };
-            mlp_layer(acc, c0v, wh, wl, smem, e_r0 + PAR * IMG_B, e_r1 + PAR * IMG_B, side);
-            rng |= __any(acc[0] != acc[0]) ? 1 : 0;
-            GM_SB;
-            acc_to_image(acc, smem, x1_w + PAR * IMG_B);
+            if constexpr (KIND == TICK_FULL) {
+                mlp_layer(acc, c0v, wh, wl, smem, e_r0 + PAR * IMG_B, e_r1 + PAR * IMG_B, side);
+                rng |= __any(acc[0] != acc[0]) ? 1 : 0;
+                GM_SB;
+                acc_to_image(acc, smem, x1_w + PAR * IMG_B);
+            } else {   // the fill tick: the first block's rows -> image E, the requests behind it
+#pragma unroll
+                for (int slot = 0; slot <= 8; ++slot) side(slot);
+            }
             // initial accumulators of block x+1: Q rows (already at this kernel's weight scale) row-major -> tile -> accumulator layout
 #pragma unroll
             for (int j = 0; j < 4; ++j) LDS(floatx4, ps_w + j * TILE_ROW_B) = qv[j];
@@ -960,7 +994,7 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_node_kernel(const float* a
             }
             lds_barrier();
         };
-        RUN_TICKS(-1, nb + 2, tick);   // one tick of fill, nb blocks, three (four when nb is odd) that drain the pipeline
+        NODE_TICKS(tick_as);
     } else {
         // roles 1 / 2: Linear 2 of block x-1 / Linear 3 of block x-2; each runs two row groups of the epilogue of block x-3
         const bool r2 = role == 2;
@@ -979,8 +1013,13 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_node_kernel(const float* a
         floatx4 er[2];   // residual rows (h, row-major quads) of block x-3, this role's two row groups
         er[0] = er[1] = floatx4{0.f, 0.f, 0.f, 0.f};
         floatx16 acc;
-        auto tick = [&](auto par_c, int t) {
+        auto tick_as = [&](auto par_c, auto kind_c, int t) {
             constexpr int PAR = decltype(par_c)::value, PIN = 1 - PAR, P3 = 1 - PAR;   // role 1: X1 of block x-1; role 2: X2 of block x-2 (PAR)
+            constexpr int KIND = decltype(kind_c)::value;
+            if constexpr (KIND == TICK_FILL) {   // no block has reached Linear 2 / 3 or the epilogue yet
+                lds_barrier();
+                return;
+            }
             const int x = b0 + t;
             LDS(float, km_w) = ln_k(smem, st_r + P3 * 512, inv_T, a_eps);   // 1 / (T sigma) of the rows of block x-3
             const int xb = x - 3;
@@ -1004,7 +1043,10 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_node_kernel(const float* a
                     er[jj] = bld4(srd_h, v_eoff, rel_b + j * 4096);   // residual rows of block x-2: a whole tick to arrive
                 }
             };
-            if (!r2) {
+            if constexpr (KIND == TICK_DRAIN) {   // the last block's epilogue alone
+#pragma unroll
+                for (int slot = 0; slot <= 8; ++slot) side(slot);
+            } else if (!r2) {
                 mlp_layer(acc, bv, wh, wl, smem, x_in + PIN * IMG_B, x_in + PIN * IMG_B, side);
                 rng |= __any(acc[0] != acc[0]) ? 1 : 0;
                 GM_SB;
@@ -1016,9 +1058,14 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_node_kernel(const float* a
             }
             lds_barrier();
         };
-        RUN_TICKS(-1, nb + 2, tick);
+        NODE_TICKS(tick_as);
     }
     report_split_range(rng, lane0, a_flags);
+}
+
+__global__ void __launch_bounds__(SYS_THREADS, 1) sys_node_kernel(const float* a_h, const float* __restrict__ a_agg, const float* __restrict__ a_Q,
+                                                                       float* a_h_out, const float* __restrict__ a_hw, int a_n, int* a_flags, float a_eps) {
+    sys_node_body(a_h, a_agg, a_Q, a_h_out, a_hw, a_n, a_flags, a_eps);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1032,9 +1079,12 @@ constexpr int LP_E = 0;                             // [2] images of h rows
 constexpr int LP_T = LP_E + 2 * IMG_B;              // [12 waves] output tiles
 constexpr size_t PROJ_LDS_BYTES = LP_T + 12 * TILE_B;
 
-__global__ void __launch_bounds__(SYS_THREADS, 1) sys_proj_kernel(const float* __restrict__ a_h, float* __restrict__ a_P, float* __restrict__ a_Q,
-                                                                       const float* __restrict__ a_wp, const float* __restrict__ a_wq,
-                                                                       const float* __restrict__ a_sp, const float* __restrict__ a_sq, int a_n, int* a_flags) {
+// The kernel's body as a function (sys_proj_kernel, and the second phase of sys_node_proj_kernel).  LD_H: cache-policy bits of the
+// loads of h rows.
+template <int LD_H>
+__device__ __forceinline__ void sys_proj_body(const float* __restrict__ a_h, float* __restrict__ a_P, float* __restrict__ a_Q,
+                                              const float* __restrict__ a_wp, const float* __restrict__ a_wq,
+                                              const float* __restrict__ a_sp, const float* __restrict__ a_sq, int a_n, int* a_flags) {
     const int tid = threadIdx.x, lane0 = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int N = a_n;
@@ -1081,11 +1131,11 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_proj_kernel(const float* _
     auto clampb = [&](int x) { return x < b0 ? b0 : (x < b1 ? x : b1 - 1); };
     floatx4 hq[2];
 #pragma unroll
-    for (int i = 0; i < 2; ++i) hq[i] = producer ? bld4(srd_h, v_in[i], 0) : floatx4{0.f, 0.f, 0.f, 0.f};   // rows of block b0 ("x+1" of the fill tick)
+    for (int i = 0; i < 2; ++i) hq[i] = producer ? bld4s<LD_H>(srd_h, v_in[i], 0) : floatx4{0.f, 0.f, 0.f, 0.f};   // rows of block b0 ("x+1" of the fill tick)
     int rng = 0;
     floatx16 acc;
-    auto tick = [&](auto par_c, int t) {
-        constexpr int PAR = decltype(par_c)::value;
+    auto tick_as = [&](auto par_c, auto kind_c, int t) {
+        constexpr int PAR = decltype(par_c)::value, KIND = decltype(kind_c)::value;
         const int x = b0 + t;
         const unsigned rel2 = (unsigned)(clampb(x + 2) - b0) * (BE * 512u);
         const int cnt = (x >= b0 && x < b1) ? min(BE, N - x * BE) : 0;
@@ -1098,9 +1148,15 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_proj_kernel(const float* _
                 LDS(uintx2, e_w[i] + (1 - PAR) * IMG_B + 1024) = l;
             } else if (producer && slot == 4) {
 #pragma unroll
-                for (int i = 0; i < 2; ++i) hq[i] = bld4(srd_h, v_in[i], rel2);
+                for (int i = 0; i < 2; ++i) hq[i] = bld4s<LD_H>(srd_h, v_in[i], rel2);
             }
         };
+        if constexpr (KIND == TICK_FILL) {   // rows of the first block -> image, the second block's requested: nothing to multiply yet
+#pragma unroll
+            for (int slot = 0; slot <= 4; ++slot) side(slot);
+            lds_barrier();
+            return;
+        }
         mlp_layer(acc, bv, wh, wl, smem, e_r0 + PAR * IMG_B, e_r1 + PAR * IMG_B, side);
         rng |= __any(acc[0] != acc[0]) ? 1 : 0;
         // outputs of block x: accumulator layout -> the wave's own tile -> row-major, whole 128-byte lines (rows that do not exist
@@ -1123,8 +1179,43 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_proj_kernel(const float* _
         }
         lds_barrier();
     };
-    RUN_TICKS(-1, nb, tick);   // one tick of fill, nb blocks (one more when nb is even: it recomputes the last block, stores nothing)
+    // a fill tick, then the nb blocks in pairs (and the last one alone when nb is odd)
+    auto tick = [&](auto par_c, int t) { tick_as(par_c, int_c<TICK_FULL>{}, t); };
+    tick_as(int_c<1>{}, int_c<TICK_FILL>{}, -1);
+    RUN_TICKS(0, nb - 2, tick);
+    if (nb & 1) tick(int_c<0>{}, nb - 1);
     report_split_range(rng, lane0, a_flags);
+}
+
+__global__ void __launch_bounds__(SYS_THREADS, 1) sys_proj_kernel(const float* __restrict__ a_h, float* __restrict__ a_P, float* __restrict__ a_Q,
+                                                                       const float* __restrict__ a_wp, const float* __restrict__ a_wq,
+                                                                       const float* __restrict__ a_sp, const float* __restrict__ a_sq, int a_n, int* a_flags) {
+    sys_proj_body<0>(a_h, a_P, a_Q, a_wp, a_wq, a_sp, a_sq, a_n, a_flags);
+}
+
+// ------------------------------------------------------------------------------------------
+// A processor step's node MLP and the next step's projections as ONE launch: the projection of block b needs h' of block b only,
+// and both kernels deal the blocks to the workgroups in the same way, so the workgroup that wrote those rows is the one that
+// reads them -- no grid-wide boundary lies between the two.  Phase A is sys_node_body over the workgroup's blocks, phase B
+// sys_proj_body over the same blocks (a workgroup without blocks leaves both at once).
+// Hand-over: phase A's last tick ends in a workgroup barrier behind which no wave touches phase A's LDS regions again, so phase B's
+// prologue overlays its map at once: it requests the projection weights (into the registers phase A's weights have left: they
+// travel while the last h' stores drain and the images are re-zeroed), zeroes the two operand images, waits vmcnt(0) -- every wave's
+// h' stores have then been acknowledged by this XCD's L2, the gfx950 vector L1 being write-through -- and joins a barrier.  Phase
+// B then loads h' with sc1: served by L2, past this CU's L1, which may still hold lines of h from phase A's residual reads of
+// the same addresses (where h is updated in place).  No invalidate (an agent-scope acquire costs more than a microsecond per CU and phase),
+// no flag, no atomic: nothing crosses a workgroup.  Q is read by phase A and written by phase B, each workgroup its own rows.
+// ------------------------------------------------------------------------------------------
+constexpr size_t NODE_PROJ_LDS_BYTES = NODE_LDS_BYTES > PROJ_LDS_BYTES ? NODE_LDS_BYTES : PROJ_LDS_BYTES;
+static_assert(NODE_PROJ_LDS_BYTES <= 160 * 1024, "LDS budget");
+
+__global__ void __launch_bounds__(SYS_THREADS, 1) sys_node_proj_kernel(const float* a_h, float* a_h_out, const float* __restrict__ a_agg, float* a_Q, const float* __restrict__ a_hw,
+                                                                            float* __restrict__ a_P, const float* __restrict__ a_wp, const float* __restrict__ a_wq,
+                                                                            const float* __restrict__ a_sp, const float* __restrict__ a_sq, int a_n, int* a_flags,
+                                                                            float a_eps) {
+    sys_node_body(a_h, a_agg, a_Q, a_h_out, a_hw, a_n, a_flags, a_eps);
+    __builtin_amdgcn_s_setprio(0);   // phase A's roles are gone: twelve equal waves
+    sys_proj_body<LD_SC1>(a_h_out, a_P, a_Q, a_wp, a_wq, a_sp, a_sq, a_n, a_flags);
 }
 
 // agg rows of the nodes whose in-edge segment crosses groups of the scatter-add: + the head partials the later groups hold, in
@@ -1434,6 +1525,16 @@ int launch_node_sys(const NodeSysArgs& a, hipStream_t s) {
 int launch_proj_sys(const ProjSysArgs& a, hipStream_t s) {
     GM_REQUIRE(a.h && a.P && a.Q && a.img_p && a.img_q && a.n > 0, GM_ERR_INVALID_ARGUMENT, "launch_proj_sys: bad argument");
     return launch_sys<sys_proj_kernel>(PROJ_LDS_BYTES, a.prof, PROF_NODE, s, a.h, a.P, a.Q, a.img_p, a.img_q, a.scale_p, a.scale_q, a.n, a.flags);
+}
+
+int launch_node_proj_sys(const NodeSysArgs& a, const ProjSysArgs& p, hipStream_t s) {
+    GM_REQUIRE(a.h && a.agg && a.Q && a.h_out && a.image && a.n > 0, GM_ERR_INVALID_ARGUMENT, "launch_node_proj_sys: bad argument");
+    GM_REQUIRE(p.P && p.img_p && p.img_q, GM_ERR_INVALID_ARGUMENT, "launch_node_proj_sys: bad argument");
+    // one workgroup reads back what it wrote, and overwrites the Q rows it has consumed: the two halves must name the same arrays
+    GM_REQUIRE(p.h == a.h_out && p.Q == a.Q && p.n == a.n && p.flags == a.flags, GM_ERR_INVALID_ARGUMENT,
+               "launch_node_proj_sys: the projection must read the node MLP's h_out and write its Q, over the same rows");
+    return launch_sys<sys_node_proj_kernel>(NODE_PROJ_LDS_BYTES, a.prof, PROF_NODE, s, a.h, a.h_out, a.agg, p.Q, a.image, p.P, p.img_p, p.img_q, p.scale_p,
+                                            p.scale_q, a.n, a.flags, a.eps);
 }
 
 int launch_agg_stitch(float* agg, const float* side, const EdgeBlocks& t, int64_t n, ProfState* prof_state, hipStream_t s) {

@@ -528,21 +528,21 @@ int epd_forward_impl(const gm_model* m, const float* nodes, int64_t n, const flo
     }
     // The systolic node path (hedge.h) takes the h half of its node MLP's first Linear as Q, written with P by the projection kernel
     // behind every step.
-    auto project = [&](int k) {   // h -> P of edge step k, Q of node step k
+    auto proj_args = [&](int k) {   // h -> P of edge step k, Q of node step k
         ProjSysArgs pa{};
         pa.h = f.h; pa.P = f.P; pa.Q = f.Q; pa.n = (int)n; pa.flags = flags; pa.prof = m->prof;
         pa.img_p = m->packed_hm + (k == 0 ? m->hm_enc_node_tail : m->hm_node_tail[k - 1]);
         pa.img_q = m->packed_hm + m->hm_node_q[k];
         pa.scale_p = edge_sys_p_scale(m->packed_h3 + m->h3_edge[k]);
         pa.scale_q = edge_sys_p_scale(m->packed_h3 + m->h3_node[k]);
-        return launch_proj_sys(pa, s);
+        return pa;
     };
     {
         HmNodeArgs na = enc_node_args(m, n, nodes, f.h, flags);
         if (!route.sys_node) set_tail(m, na, 0, f.P, out, route.sys_edge);
         rc = launch_node_hm(H, 0, na, s);
     }
-    if (rc == GM_OK && route.sys_node) rc = project(0);
+    if (rc == GM_OK && route.sys_node) rc = launch_proj_sys(proj_args(0), s);
     if (rc != GM_OK) return rc;
     // agg is zeroed once (nodes without in-edges read zeros; rows with in-edges are stored whole by every edge launch)
     if (!agg_cleared) {
@@ -556,13 +556,15 @@ int epd_forward_impl(const gm_model* m, const float* nodes, int64_t n, const flo
         rc = launch_edge(H, NL, false, route.sys_edge, ea, cap, s);
         if (rc != GM_OK) return rc;
         if (route.sys_node) {
-            // head partials of the scatter-add into agg, the node MLP (h in place), then the next step's projections -- or the decoder
+            // head partials of the scatter-add into agg, the node MLP (h in place), then the next step's projections (one launch with the
+            // node MLP, or two: gm_model_set_node_fusion) -- or the decoder
             rc = launch_agg_stitch(f.agg, f.side, carve_edge_blocks(c.blocks, n, cap), n, m->prof, s);
             NodeSysArgs ns{};
             ns.h = f.h; ns.agg = f.agg; ns.Q = f.Q; ns.h_out = f.h; ns.image = m->packed_h3 + m->h3_node[k];
             ns.n = (int)n; ns.flags = flags; ns.eps = m->d.ln_eps; ns.prof = m->prof;
-            if (rc == GM_OK) rc = launch_node_sys(ns, s);
-            if (rc == GM_OK && k + 1 < M) rc = project(k + 1);
+            const bool fused = k + 1 < M && m->node_fusion;
+            if (rc == GM_OK) rc = fused ? launch_node_proj_sys(ns, proj_args(k + 1), s) : launch_node_sys(ns, s);
+            if (rc == GM_OK && k + 1 < M && !fused) rc = launch_proj_sys(proj_args(k + 1), s);
             if (rc == GM_OK && k + 1 == M) rc = launch_node_hm(H, 2, tail_args(m, M, n, f.h, f.P, out, flags), s);
         } else {
             HmNodeArgs a = proc_node_args(m, k, c, n, cap, f.h, f.agg, f.side, f.h, 1);
@@ -682,6 +684,12 @@ int gm_model_set_edge_kernel(gm_model* m, int choice) {
                "gm_model_set_edge_kernel: choices 1..4 (the round-1 fp32 / bf16 x 6 kernels) were removed from the library (round 5)");
     GM_REQUIRE((choice != EK_SYS && choice != EK_SYS_ALL) || m->packed_h3, GM_ERR_UNSUPPORTED, "gm_model_set_edge_kernel: the systolic kernel is for hidden_size 128, num_layers 2");
     m->edge_kernel = choice;
+    return GM_OK;
+}
+
+int gm_model_set_node_fusion(gm_model* m, int on) {
+    GM_REQUIRE(m, GM_ERR_INVALID_ARGUMENT, "gm_model_set_node_fusion: null model");
+    m->node_fusion = on != 0;
     return GM_OK;
 }
 

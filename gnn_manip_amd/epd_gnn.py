@@ -74,6 +74,7 @@ class _Handle:
         self.built_for = None
         self.desc = None
         self.edge_kernel = 0
+        self.node_fusion = 1
         self.prof_mask = 0
 
     def get(self, desc_tuple, params, device, key_params=None):
@@ -96,6 +97,8 @@ class _Handle:
             self.h = _Model(out)
             if self.edge_kernel:
                 check(L.gm_model_set_edge_kernel(self.h, self.edge_kernel))
+            if not self.node_fusion:
+                check(L.gm_model_set_node_fusion(self.h, 0))
             if self.prof_mask:
                 check(L.gm_model_profile(self.h, self.prof_mask))
         # no synchronisation: the pack kernels are queued on torch's current stream, and the caching allocator hands the
@@ -109,6 +112,11 @@ class _Handle:
         self.edge_kernel = int(choice)
         if self.h is not None:
             check(lib().gm_model_set_edge_kernel(self.h, self.edge_kernel))
+
+    def set_node_fusion(self, on):
+        self.node_fusion = int(bool(on))
+        if self.h is not None:
+            check(lib().gm_model_set_node_fusion(self.h, self.node_fusion))
 
     def profile(self, kind_mask):
         self.prof_mask = int(kind_mask)
@@ -623,6 +631,12 @@ class EncProcDecGNN(nn.Module):
         (systolic fp16 x 3, hidden 128 / num_layers 2), 'hm' (streamed fp16 x 3), 'sys_all' (as 'sys', and the systolic node /
         projection kernels whatever the graph's size: 'auto' takes them for graphs of 49152 nodes or more).  See include/gnn_manip_hip.h."""
         self._handle.set_edge_kernel(self.EDGE_KERNELS.get(choice, choice))
+
+    def set_node_fusion(self, on):
+        """The systolic node path of this model (diagnostics / A-B measurements): True (the default) runs a processor step's node
+        MLP and the next step's projections as one launch, False as the two launches it is made of; the results are the same bit
+        for bit.  See include/gnn_manip_hip.h."""
+        self._handle.set_node_fusion(on)
 
     def forward_inputs_only(self, nodes, edge_attr, edge_index):
         """``forward`` with the parameters as constants, whatever their requires_grad flags say: gradients flow to nodes /

@@ -270,6 +270,10 @@ void gm_model_destroy(gm_model* m);
  * hedge.hip) whatever the graph's size -- 0 takes those for graphs of 49152 nodes or more (one graph of a batch counts, not the batch), where a workgroup has blocks enough to pipeline.  1..4 were round 1's fp32 / bf16 x 6 kernels: removed from the library in round 5
  * (GM_ERR_UNSUPPORTED).  No environment variable is read: the choice belongs to the handle. */
 int gm_model_set_edge_kernel(gm_model* m, int choice);
+/* The systolic node path of THIS model (diagnostics / A-B measurements, like the choice above): on != 0 (the default) runs a
+ * processor step's node MLP and the next step's projections as one launch (sys_node_proj_kernel), 0 as the two launches it is
+ * made of.  The results are the same bit for bit. */
+int gm_model_set_node_fusion(gm_model* m, int on);
 
 size_t gm_forward_workspace_bytes(const gm_model_desc* desc, int64_t n_nodes, int64_t edge_capacity);
 /* workspace of gm_interaction_network_forward (the latent edge arrays are the caller's) */
