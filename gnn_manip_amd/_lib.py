@@ -109,6 +109,10 @@ PROTOTYPES = {
     "gm_rollout_step_backward": (_i32, [_vp, _vp, _i32, _vp, _i64, _FD, _i32, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64), _vp, _sz, _vp]),
     "gm_rollout_backward_workspace_bytes": (_sz, [_MD, _FD, _i64, _i32]),
     "gm_rollout_backward": (_i32, [_vp, _vp, _i32, _vp, _i64, _FD, _i32, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "gm_rollout_step_backward_train": (_i32, [_vp, _vp, _i32, _vp, _i64, _FD, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64), _vp, _sz,
+                                              _vp]),
+    "gm_rollout_backward_train": (_i32, [_vp, _vp, _i32, _vp, _i64, _FD, _i32, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
+                                         _vp]),
     "gm_model_profile": (_i32, [_vp, _i32]),
     "gm_model_set_edge_kernel": (_i32, [_vp, _i32]),
     "gm_model_set_node_fusion": (_i32, [_vp, _i32]),

@@ -500,13 +500,14 @@ __global__ void __launch_bounds__(256) state_post_bwd_kernel(const float* __rest
 }
 
 // the gradient of a rollout step with respect to its pre-step window, assembled: one thread owns row i of every frame and adds,
-// in this order, state_post's transpose, the integrator's, the node features' and -- xyz of the last frame -- the edge features';
-// then the transpose of state_pre on that sum (pre != 0: the step ran the overwrite) and the row of d_rigid_target it owns:
-// state_post's share, then state_pre's
+// in this order, state_post's transpose, the integrator's, the node features' and -- xyz of the last frame -- the edge features',
+// and last -- every column of the last frame, g_rec given -- the caller's gradient on the step's record (the last frame after
+// state_pre's overwrite, which is where this sum lives); then the transpose of state_pre on that sum (pre != 0: the step ran the
+// overwrite) and the row of d_rigid_target it owns: state_post's share, then state_pre's
 __global__ void __launch_bounds__(256) step_assemble_bwd_kernel(const float* __restrict__ g_post, const float* __restrict__ g_int,
                                                                  const float* __restrict__ g_nodes, const float* __restrict__ g_pos,
-                                                                 const float* __restrict__ t_post, int64_t n, FeatParams P,
-                                                                 const int* __restrict__ rank, int has_target, int pre,
+                                                                 const float* __restrict__ t_post, const float* __restrict__ g_rec,
+                                                                 int64_t n, FeatParams P, const int* __restrict__ rank, int has_target, int pre,
                                                                  float* __restrict__ d_before, float* __restrict__ d_target) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -517,6 +518,7 @@ __global__ void __launch_bounds__(256) step_assemble_bwd_kernel(const float* __r
             const int64_t at = i * P.D + t * fs + d;
             float v = __fadd_rn(__fadd_rn(g_post[at], g_int[at]), g_nodes[at]);
             if (t == P.k - 1 && d >= P.cart && d < P.cart + 3) v = __fadd_rn(v, g_pos[i * 3 + (d - P.cart)]);
+            if (t == P.k - 1 && g_rec) v = __fadd_rn(v, g_rec[i * P.D + d]);
             row[t * fs + d] = v;
         }
     const int rk = rank ? rank[i] : -1;
@@ -614,13 +616,13 @@ static EdgeBwdWs carve_edge_bwd(void* ws, int64_t n, int64_t e) {
 }
 
 int rollout_assemble_backward(const float* g_post, const float* g_int, const float* g_nodes, const float* g_pos, const float* t_post,
-                              int64_t n, const gm_feature_desc* d, const int* rank, bool has_target, float* d_before, float* d_target,
-                              hipStream_t s) {
+                              const float* g_rec, int64_t n, const gm_feature_desc* d, const int* rank, bool has_target, float* d_before,
+                              float* d_target, hipStream_t s) {
     FeatParams P;
     int rc = to_params(d, &P, "gm_rollout_step_backward");
     if (rc != GM_OK) return rc;
-    hipLaunchKernelGGL(step_assemble_bwd_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, s, g_post, g_int, g_nodes, g_pos, t_post, n, P,
-                       rank, has_target ? 1 : 0, (rank && P.ctrl >= 0) ? 1 : 0, d_before, d_target);
+    hipLaunchKernelGGL(step_assemble_bwd_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, s, g_post, g_int, g_nodes, g_pos, t_post, g_rec, n,
+                       P, rank, has_target ? 1 : 0, (rank && P.ctrl >= 0) ? 1 : 0, d_before, d_target);
     GM_LAUNCH_CHECK();
     return GM_OK;
 }

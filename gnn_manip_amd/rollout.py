@@ -131,6 +131,58 @@ class _RolloutLibraryFunction(torch.autograd.Function):
         return None, (d_obs0 if ctx.needs_input_grad[1] else None), d_traj, None
 
 
+class _RolloutTrainFunction(torch.autograd.Function):
+    """RolloutEngine.differentiable_rollout(sweep="library", record=..., params=...): _RolloutLibraryFunction with the per-step
+    records as a second output and the model's (training) tensors as inputs; the reverse sweep is one gm_rollout_backward_train
+    call.  `model`: None (the parameters are constants, no tensors follow) or the (gm_model handle, descriptor) the tensors that
+    follow belong to -- the module's parameters, or the padded tensors EncProcDecGNN._padded_training built from them under
+    autograd, which then carries their gradients back into the checkpoint's shapes."""
+
+    @staticmethod
+    def forward(ctx, engine, obs0, trajectory, steps, record, model, *tensors):
+        obs = obs0.detach().clone().contiguous()
+        traj = None if trajectory is None else trajectory.detach().contiguous().float()
+        engine.set_scene(obs)
+        windows = torch.empty((steps,) + tuple(obs.shape), dtype=torch.float32, device=obs.device)
+        records = torch.empty((steps,) + tuple(obs.shape[1:]), dtype=torch.float32, device=obs.device) if record else None
+        for t in range(steps):
+            windows[t].copy_(obs)          # the pre-step window of step t
+            engine.step(obs, None if traj is None else traj[t])
+            if record:
+                # the last frame after step t's control overwrite is frame k-2 of the window the step left (the shift moved it there)
+                records[t].copy_(obs[-2])
+        engine.status()
+        ctx.engine, ctx.windows, ctx.traj, ctx.steps, ctx.model, ctx.record = engine, windows, traj, steps, model, record
+        ctx.scene = (engine.rigid_rank, engine.n_rigid)
+        ctx.save_for_backward(*tensors)
+        ctx.set_materialize_grads(False)   # an output the loss does not touch: no gradient array is made up (or read) for it
+        return (obs, records) if record else obs
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_final, d_records=None):
+        eng = ctx.engine
+        if d_final is None:
+            d_final = torch.zeros((eng.k, eng.n, eng.data_dim), dtype=torch.float32, device=eng.device)
+        need_traj = ctx.traj is not None and ctx.needs_input_grad[2]
+        tensors = ctx.saved_tensors
+        model = grads = None
+        if ctx.model is not None:
+            model = ctx.model + ([t.detach().to(device=eng.device, dtype=torch.float32).contiguous() for t in tensors],)
+            if any(ctx.needs_input_grad[6:]):
+                flat = torch.zeros(sum(t.numel() for t in model[2]), dtype=torch.float32, device=eng.device)   # ONE set, whatever T
+                grads, off = [], 0
+                for t in model[2]:
+                    grads.append(flat[off:off + t.numel()].view_as(t))
+                    off += t.numel()
+        d_obs0, d_traj = eng._sweep_backward(ctx.windows, ctx.traj, ctx.steps, d_final.contiguous().float(), ctx.scene, need_traj,
+                                             d_records=None if d_records is None else d_records.contiguous().float(), model=model,
+                                             grads=grads)
+        ctx.windows = None
+        d_tensors = tuple(g if ctx.needs_input_grad[6 + i] else None for i, g in enumerate(grads)) if grads else (None,) * len(tensors)
+        return (None, (d_obs0 if ctx.needs_input_grad[1] else None), d_traj, None, None, None) + d_tensors
+
+
 class RolloutEngine:
     """Runs rollouts of an ``EncProcDecGNN`` for scenes of ``n_nodes`` particles.
 
@@ -301,42 +353,69 @@ class RolloutEngine:
                 and tuple(g.shape) == (self.k, self.n, self.data_dim)):
             raise ValueError(f"{name} must be contiguous float32 [{self.k}, {self.n}, {self.data_dim}] on {self.device}")
 
-    def step_backward(self, obs_before, rigid_target, d_obs_after, return_edge_count=False):
-        """The vector-Jacobian product of one ``step`` inside the library (gm_rollout_step_backward): (d_obs_before [k, N, D],
+    def _check_param_grads(self, grads, tensors):
+        if len(grads) != len(tensors) or any(not (isinstance(g, torch.Tensor) and g.device == self.device and g.dtype == torch.float32
+                                                  and g.is_contiguous() and g.shape == t.shape) for g, t in zip(grads, tensors)):
+            raise ValueError(f"grads must be {len(tensors)} contiguous float32 tensors on {self.device} shaped like the training model's")
+        return (C.c_void_p * len(grads))(*[g.data_ptr() for g in grads])
+
+    def step_backward(self, obs_before, rigid_target, d_obs_after, return_edge_count=False, d_record=None, grads=None):
+        """The vector-Jacobian product of one ``step`` inside the library (gm_rollout_step_backward_train): (d_obs_before [k, N, D],
         d_rigid_target [N_rigid, 3] or None without a target) from the pre-step window, the step's scripted pose and the gradient
-        with respect to the window the step left.  The model's parameters are constants.  ``set_scene`` must have been called;
-        ``obs_before`` is not written.  One host synchronisation (the edge count, returned third when asked for)."""
+        with respect to the window the step left.  ``set_scene`` must have been called; ``obs_before`` is not written.  One host
+        synchronisation (the edge count, returned third when asked for).
+
+        d_record: [N, D] or None, the gradient with respect to the step's record (the last frame after the control overwrite,
+        what ``run(record=True)`` keeps of this step); it is added inside the same launch that sums the step's contributions.
+        grads: None -- the model's parameters are constants -- or a list of float32 tensors shaped like the model's parameters
+        (hidden sizes 64 / 128 / 256; like ``_training_model``'s padded tensors otherwise), which the parameter gradients are
+        ACCUMULATED into: the caller zeroes them.  The two returned gradients have the same bits with and without ``grads``."""
         self._check_state(obs_before, rigid_target, None, True)
         self._check_grad(d_obs_after, "d_obs_after")
+        if d_record is not None and not (isinstance(d_record, torch.Tensor) and d_record.device == self.device and d_record.dtype == torch.float32
+                                         and d_record.is_contiguous() and tuple(d_record.shape) == (self.n, self.data_dim)):
+            raise ValueError(f"d_record must be contiguous float32 [{self.n}, {self.data_dim}] on {self.device}")
         h, tensors, t_arr, mdesc = self._training_model()
+        g_arr = None if grads is None else self._check_param_grads(grads, tensors)
         ws = self._backward_ws(mdesc)
         d_obs = torch.empty_like(obs_before)
         d_tgt = None if rigid_target is None else torch.empty_like(rigid_target)
         e = C.c_int64(0)
-        check(lib().gm_rollout_step_backward(h, t_arr, len(tensors), ptr(obs_before), self.n, C.byref(self.fdesc), self.max_neighbours,
-                                             ptr(self.rigid_rank), ptr(rigid_target), ptr(d_obs_after), ptr(d_obs), ptr(d_tgt), C.byref(e),
-                                             ptr(ws), ws.numel(), current_stream()))
+        check(lib().gm_rollout_step_backward_train(h, t_arr, len(tensors), ptr(obs_before), self.n, C.byref(self.fdesc), self.max_neighbours,
+                                                   ptr(self.rigid_rank), ptr(rigid_target), ptr(d_obs_after), ptr(d_record), g_arr,
+                                                   ptr(d_obs), ptr(d_tgt), C.byref(e), ptr(ws), ws.numel(), current_stream()))
         return (d_obs, d_tgt, int(e.value)) if return_edge_count else (d_obs, d_tgt)
 
-    def _sweep_backward(self, windows, traj, steps, d_final, scene, need_traj):
-        """gm_rollout_backward on the windows a forward kept: (d_obs0, d_trajectory or None)."""
+    def _sweep_backward(self, windows, traj, steps, d_final, scene, need_traj, d_records=None, model=None, grads=None):
+        """gm_rollout_backward_train on the windows a forward kept: (d_obs0, d_trajectory or None).  d_records: [steps, N, D] or
+        None.  model: (handle, descriptor, tensors) of the training model the sweep runs, None for ``_training_model()``'s; grads:
+        tensors shaped like its tensors that the parameter gradients are accumulated into, or None."""
         rank, n_rigid = scene
         self._check_grad(d_final, "d_final")
         if traj is not None and (tuple(traj.shape[1:]) != (n_rigid, 3) or traj.dtype != torch.float32 or not traj.is_contiguous()):
             raise ValueError(f"trajectory must be contiguous float32 [T, {n_rigid}, 3], got {tuple(traj.shape)}")
         if tuple(windows.shape) != (steps, self.k, self.n, self.data_dim) or not windows.is_contiguous():
             raise ValueError(f"windows must be contiguous [{steps}, {self.k}, {self.n}, {self.data_dim}], got {tuple(windows.shape)}")
-        h, tensors, t_arr, mdesc = self._training_model()
+        if d_records is not None and (tuple(d_records.shape) != (steps, self.n, self.data_dim) or d_records.dtype != torch.float32
+                                      or d_records.device != self.device or not d_records.is_contiguous()):
+            raise ValueError(f"d_records must be contiguous float32 [{steps}, {self.n}, {self.data_dim}], got {tuple(d_records.shape)}")
+        if model is None:
+            h, tensors, t_arr, mdesc = self._training_model()
+        else:
+            h, mdesc, tensors = model
+            t_arr = (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+        g_arr = None if grads is None else self._check_param_grads(grads, tensors)
         ws = self._backward_ws(mdesc)
         d_obs0 = torch.empty_like(d_final)
         d_traj = torch.empty_like(traj) if need_traj else None
         n_targets = 0 if traj is None else int(traj.shape[0])
-        check(lib().gm_rollout_backward(h, t_arr, len(tensors), ptr(windows), self.n, C.byref(self.fdesc), self.max_neighbours, ptr(rank),
-                                        ptr(traj), n_targets, n_rigid, steps, ptr(d_final), ptr(d_obs0), ptr(d_traj), ptr(ws), ws.numel(),
-                                        current_stream()))
+        check(lib().gm_rollout_backward_train(h, t_arr, len(tensors), ptr(windows), self.n, C.byref(self.fdesc), self.max_neighbours,
+                                              ptr(rank), ptr(traj), n_targets, n_rigid, steps, ptr(d_final), ptr(d_records), g_arr,
+                                              ptr(d_obs0), ptr(d_traj), ptr(ws), ws.numel(), current_stream()))
         return d_obs0, d_traj
 
-    def differentiable_rollout(self, obs0, trajectory=None, horizon=None, return_edges=False, sweep="autograd"):
+    def differentiable_rollout(self, obs0, trajectory=None, horizon=None, return_edges=False, sweep="autograd", record=False,
+                               params=False):
         """``rollout(obs0, trajectory, horizon)`` under autograd: returns the final state [k, N, D], bit-equal to ``rollout``'s
         (an engine that renumbers, see ``renumber``, sums a node's messages in another order inside ``rollout``: equal to
         rounding there), with gradients to ``obs0`` (position and control columns) and to ``trajectory`` [T, N_rigid, 3].  The
@@ -357,17 +436,42 @@ class RolloutEngine:
         sweep: "autograd" (the default) is the backward described above.  "library" keeps the windows in one [T, k, N, D] array and
         runs the whole reverse sweep as ONE library call (gm_rollout_backward: per step the same forward and backward entry
         points, the state updates' transposes and the sum of the contributions as HIP kernels, no autograd node and no Python
-        between steps; still one edge-count read per step).  It hands out no edge lists: ``return_edges`` raises ValueError."""
+        between steps; still one edge-count read per step).  It hands out no edge lists: ``return_edges`` raises ValueError.
+
+        record, params (sweep="library" only; ValueError otherwise): what a multi-step TRAINING loss needs.  record=True returns
+        (final state, records [T, N, D]), both differentiable: ``rollout(..., record=True)``'s records (bit-equal on an engine
+        that does not renumber), read off the windows the forward passes through anyway -- record t is frame k-2 of the state
+        after step t.  params=True makes the model's parameters inputs of the rollout: the sweep accumulates their gradients
+        over the steps (gm_rollout_backward_train, step T-1 first, step 0 last, no atomics) and they arrive in ``.grad`` like any
+        other tensor's -- in the checkpoint's own shapes at a hidden size between 64 / 128 / 256 too, where the zero-padded tensors
+        are built under autograd as in ``EncProcDecGNN.forward``; ``obs0`` need not require grad.  Peak memory still grows with
+        the horizon only by the windows (and the records asked for): one tape and one set of parameter gradients are alive."""
         if sweep not in ("autograd", "library"):
             raise ValueError(f"sweep must be 'autograd' or 'library', got {sweep!r}")
         if sweep == "library" and return_edges:
             raise ValueError("sweep='library' hands out no edge lists: return_edges needs sweep='autograd'")
+        if sweep != "library" and (record or params):
+            raise ValueError("record=True / params=True need sweep='library' (the autograd sweep returns the final state alone, "
+                             "with the parameters as constants)")
         steps = int(horizon) if horizon is not None else (int(trajectory.shape[0]) if trajectory is not None else 0)
         self._check_state(obs0, None, None, False)
         if trajectory is not None:
             if (trajectory.device != self.device or trajectory.dim() != 3 or int(trajectory.shape[0]) < steps
                     or int(trajectory.shape[2]) != 3):
                 raise ValueError(f"trajectory must be [T >= {steps}, N_rigid, 3] on {self.device}, got {tuple(trajectory.shape)}")
+        if sweep == "library" and (record or params):
+            model, tensors = None, ()
+            if params:
+                from .epd_gnn import TRAIN_WIDTHS
+                m = self.model
+                own = list(m.parameters())
+                if m.dims[3] in TRAIN_WIDTHS:
+                    desc_t, tensors, h = m.model_desc(), own, m.device_handle(self.device)
+                else:   # the padded tensors are functions of the parameters: autograd takes the gradients back through them
+                    (desc_t, handle), tensors = m._padded_training(own)
+                    h = handle.get(desc_t, tensors, self.device, tuple(own))
+                model = (h, ModelDesc(*desc_t))
+            return _RolloutTrainFunction.apply(self, obs0, trajectory, steps, bool(record), model, *tensors)
         if sweep == "library":
             return _RolloutLibraryFunction.apply(self, obs0, trajectory, steps)
         edges = [] if return_edges else None

@@ -480,6 +480,26 @@ int gm_rollout_status(const void* rollout_ws, const gm_model_desc* desc, int64_t
  * d_final to d_obs0.  It is a loop of gm_rollout_step_backward from the last step to the first; two [k,N,D] gradient windows take
  * turns behind the step's workspace, so the workspace is the step's plus those two, whatever `steps` is.  One host
  * synchronisation per step, as above.
+ *
+ * gm_rollout_step_backward_train / gm_rollout_backward_train are the same two calls with two more inputs, for a loss that trains the
+ * model through the rollout and has a term on every step (both NULL: gm_rollout_step_backward / gm_rollout_backward, bit for bit --
+ * those two ARE these with both NULL).
+ *   grads: gm_epd_backward's argument -- one float buffer per parameter tensor, same order and shapes as `tensors` -- ACCUMULATED into
+ * (the caller zeroes them); everything else these calls return is WRITTEN in full.  With grads the step's model backward is
+ * gm_epd_backward_inputs, without it gm_epd_backward_inputs_only; their input gradients are bit-equal (see there), so d_obs_before,
+ * d_rigid_target, d_obs0 and d_trajectory have the same bits with and without grads.  Across a sweep every step adds into the same
+ * buffers, step steps-1 first and step 0 last; within a step the order is gm_epd_backward's.  No float atomics: the same call from
+ * zeroed grads gives the same bits twice.  steps == 0 leaves grads untouched.
+ *   d_record [N,D] / d_records [steps,N,D]: the gradient with respect to record_last[t] of gm_rollout, the last frame of window t
+ * after the control overwrite of gm_state_pre -- d_records is the transpose of the record the forward offers.  It joins the last
+ * frame's sum inside the one assembly launch, as the last term of the fixed order,
+ *     (((state_post's + integrator's) + node features') + edge features') + record's,
+ * before gm_state_pre_backward's rule is applied to that sum: no extra launch, no extra pass over a window.  Rows of d_records at or
+ * past `steps` are not read; steps == 0 ignores it.  (record_last[t] is also frame k-2 of the window after step t: the window shift
+ * moves it there unchanged, so a forward that keeps its windows has its records already.)
+ *   Workspace: gm_train_backward_inputs_workspace_bytes is the query of both model backwards, so
+ * gm_rollout_step_backward_workspace_bytes and gm_rollout_backward_workspace_bytes serve these two unchanged; one tape and one
+ * backward workspace are alive whatever `steps` is.
  * ------------------------------------------------------------------------------------------ */
 size_t gm_rollout_step_backward_workspace_bytes(const gm_model_desc* desc, const gm_feature_desc* fdesc, int64_t n_nodes,
                                                 int max_neighbours);
@@ -495,6 +515,18 @@ int gm_rollout_backward(const gm_model* m, const float* const* tensors, int n_te
                         const float* trajectory /*[n_targets,Nr,3] or NULL*/, int64_t n_targets, int64_t n_rigid, int64_t steps,
                         const float* d_final /*[k,N,D]*/, float* d_obs0 /*[k,N,D]*/, float* d_trajectory /*[n_targets,Nr,3] or NULL*/,
                         void* ws, size_t ws_bytes, void* stream);
+int gm_rollout_step_backward_train(const gm_model* m, const float* const* tensors, int n_tensors, const float* obs_before /*[k,N,D]*/,
+                                   int64_t n_nodes, const gm_feature_desc* fdesc, int max_neighbours, const int32_t* rigid_rank,
+                                   const float* rigid_target /*[Nr,3] or NULL*/, const float* d_obs_after /*[k,N,D]*/,
+                                   const float* d_record /*[N,D] or NULL*/, float* const* grads /* or NULL */,
+                                   float* d_obs_before /*[k,N,D]*/, float* d_rigid_target /*[Nr,3] or NULL*/,
+                                   int64_t* n_edges_host /* or NULL */, void* ws, size_t ws_bytes, void* stream);
+int gm_rollout_backward_train(const gm_model* m, const float* const* tensors, int n_tensors, const float* windows /*[steps,k,N,D]*/,
+                              int64_t n_nodes, const gm_feature_desc* fdesc, int max_neighbours, const int32_t* rigid_rank,
+                              const float* trajectory /*[n_targets,Nr,3] or NULL*/, int64_t n_targets, int64_t n_rigid, int64_t steps,
+                              const float* d_final /*[k,N,D]*/, const float* d_records /*[steps,N,D] or NULL*/,
+                              float* const* grads /* or NULL */, float* d_obs0 /*[k,N,D]*/,
+                              float* d_trajectory /*[n_targets,Nr,3] or NULL*/, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Measurement hooks (no reference counterpart; the reference only wraps model.forward in

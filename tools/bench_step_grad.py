@@ -26,6 +26,10 @@ Shapes: `train` = the training benchmark's graph (two collated 5000-node scenes,
     rollout figures above with differentiable_rollout(sweep="library").  `sweep_ws_bytes` = gm_rollout_backward_workspace_bytes
     (sized for N x max_neighbours edges whatever the graph holds; the engine keeps it once allocated, so the peak of a later call
     does not count it: it is reported next to the peaks).
+  * training through the rollout: `sweep_lib_bwd_per_step` / `sweep_train_bwd_per_step` = ONE reverse sweep of --horizon steps
+    (RolloutEngine._sweep_backward: gm_rollout_backward_train) on the windows of one forward, without and with `grads` (zeroed
+    outside the timed window) and a gradient on every record, interleaved call by call, divided by the horizon: what the
+    weight-gradient launches add to a step of the sweep, to be read against `bwd_inputs` - `bwd_inputs_only` of the same run.
 Each time is one call between two events on the current stream; median and range over --reps calls.
 """
 import argparse
@@ -198,6 +202,38 @@ def bench(name, scenes, reps, warmup, hidden=128, m_steps=10, horizon=4, parent_
         rollout_fwd_bwd()
         rollout_lib_fwd_bwd()
     t.update(sweep)
+
+    # ---- the library sweep without and with parameter gradients, on the windows of one forward
+    windows = torch.empty((horizon,) + tuple(obs.shape), device=dev)
+    cur = obs.clone()
+    eng.set_scene(cur)
+    for i in range(horizon):
+        windows[i].copy_(cur)
+        eng.step(cur, traj[i])
+    eng.status()
+    scene_key = (eng.rigid_rank, eng.n_rigid)
+    _, tr_tensors, _, tr_desc = eng._training_model()
+    p_grads = [torch.zeros_like(x) for x in tr_tensors]
+    d_records = torch.randn((horizon,) + tuple(obs.shape[1:]), device=dev)
+
+    def sweep_lib():
+        eng._sweep_backward(windows, traj, horizon, w_o, scene_key, True)
+
+    def sweep_train():
+        eng._sweep_backward(windows, traj, horizon, w_o, scene_key, True, d_records=d_records, grads=p_grads)
+
+    for _ in range(warmup):
+        sweep_lib()
+        sweep_train()
+    torch.cuda.synchronize()
+    t["sweep_lib_bwd_per_step"], t["sweep_train_bwd_per_step"] = [], []
+    for _ in range(reps):
+        t["sweep_lib_bwd_per_step"].append(_time(sweep_lib) / horizon)
+        for x in p_grads:
+            x.zero_()
+        torch.cuda.synchronize()
+        t["sweep_train_bwd_per_step"].append(_time(sweep_train) / horizon)
+    windows = d_records = None
     peaks = dict(rollout_peak_bytes=_peak(rollout_fwd_bwd, dev), rollout_lib_peak_bytes=_peak(rollout_lib_fwd_bwd, dev),
                  unrolled_peak_bytes=_peak(unrolled_fwd_bwd, dev),
                  sweep_ws_bytes=int(L.gm_rollout_backward_workspace_bytes(C.byref(d), C.byref(eng.fdesc), eng.n, eng.max_neighbours)))
@@ -212,6 +248,8 @@ def bench(name, scenes, reps, warmup, hidden=128, m_steps=10, horizon=4, parent_
     if parent_lib:
         rec["inputs_only_over_parent_inputs"] = round(med["bwd_inputs_only"] / med["bwd_inputs_parent"], 4)
     rec["lib_over_autograd_step"] = round(med["lib_step_bwd"] / med["autograd_step_bwd"], 4)
+    rec["train_minus_lib_sweep_per_step_ms"] = round(med["sweep_train_bwd_per_step"] - med["sweep_lib_bwd_per_step"], 4)
+    rec["bwd_inputs_minus_inputs_only_ms"] = round(med["bwd_inputs"] - med["bwd_inputs_only"], 4)
     rec["lib_over_autograd_sweep"] = round(med["rollout_lib_bwd_per_step"] / med["rollout_bwd_per_step"], 4)
     rec.update(horizon=horizon, **peaks)
     print(json.dumps(rec), flush=True)
