@@ -193,12 +193,17 @@ __device__ __forceinline__ void load_feat_lines(floatx16 (&v)[NKB], const float*
         }
     }
 }
+// ReLU that passes a NaN on, as the float32 reference's does: fmaxf(z, 0) is 0 for a NaN, so a non-finite feature or weight left
+// the chain as finite, wrong numbers.  !(z <= 0) holds for z > 0 and for NaN; everything else (-0, -inf) gives +0: the bits
+// fmaxf gave for every finite z.  |z| clears a NaN's sign so that relu_mask_store records the unit as active and the backward
+// lets its gradient through (threshold_backward does).  A compare and a select for fmaxf's two instructions: no measurable
+// cost ("Numeric domain").
 template <int NKB>
 __device__ __forceinline__ void relu_to(floatx16 (&dst)[NKB], const floatx16 (&src)[NKB]) {
 #pragma unroll
     for (int kb = 0; kb < NKB; ++kb)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) dst[kb][r] = fmaxf(src[kb][r], 0.f);
+        for (int r = 0; r < 16; ++r) dst[kb][r] = !(src[kb][r] <= 0.f) ? __builtin_fabsf(src[kb][r]) : 0.f;
 }
 
 }  // namespace gm

@@ -228,6 +228,18 @@ int gm_state_post_backward(const float* d_obs_after, int64_t n_nodes, const gm_f
  * kernel that meets it sets a flag in the CSR header of that forward and gm_csr_num_edges / gm_rollout_status return
  * GM_ERR_DATA ("fp16 split range exceeded"); the outputs of that forward are then invalid.  A float32 evaluation would
  * also stay finite for magnitudes up to 3.4e38: that part of its domain is not covered.
+ *
+ * Numeric domain of the training entry points (gm_epd_forward_train / gm_epd_backward*, the *_forward_train / *_backward block
+ * entry points).  They form the float32 products on the bf16 matrix pipe: every operand -- weight, activation, gradient -- is
+ * split into three bf16 parts, which keep float32's whole exponent range, and accumulated in float32.  No operand is scaled and
+ * no range is searched, so ANY finite float32 magnitude is supported, in the forward and in the backward (gradients of 1e-9 and
+ * 1e+5 in one array included), and nothing is flagged or clamped.  A rescaling by a power of two is bit-exact: grad_out * 2^k
+ * gives every gradient * 2^k; (W_l, b_l) * s with W_(l+1) / s, or features * c with the encoders' first weights / c, give the
+ * same prediction bit for bit and the gradients of the rescaled tensors times the inverse factor (as long as no value leaves
+ * float32's normal range).  A non-finite input feature or parameter gives NaN rows exactly where a float32 evaluation has them
+ * -- the row itself, and the rows its edges carry it to -- and leaves every other row's bits alone (the chains' ReLU passes a
+ * NaN on and records the unit as active, as relu / threshold_backward do); the loss and the parameter gradients of such a step
+ * are non-finite as in float32.  tests/test_gpu_train_domain.py holds the kernels to this.
  * ------------------------------------------------------------------------------------------ */
 typedef struct gm_model_desc {
     int32_t node_dim, edge_dim, out_dim;

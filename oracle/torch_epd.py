@@ -59,6 +59,20 @@ def _mlp_taped(p, prefix, x, num_layers, norm, tape):
     return x
 
 
+def epd_forward_taped(p, nodes, edge_attr, edge_index, num_layers, m_steps, tape):
+    """epd_forward that appends (z, a) of every hidden Linear to `tape`, in evaluation order: node encoder, edge encoder, per
+    step edge then node MLP, decoder -- num_layers entries each."""
+    j, i = edge_index[0], edge_index[1]
+    h = _mlp_taped(p, "encoder.phi_node", nodes, num_layers, True, tape)
+    e = _mlp_taped(p, "encoder.phi_edge", edge_attr, num_layers, True, tape)
+    for k in range(m_steps):
+        e_new = _mlp_taped(p, f"processor.{k}.phi_edge", torch.cat((h[i], h[j], e), dim=1), num_layers, True, tape)
+        agg = torch.zeros_like(h).index_add_(0, i, e_new)
+        h_new = _mlp_taped(p, f"processor.{k}.phi_node", torch.cat((h, agg), dim=1), num_layers, True, tape)
+        h, e = h + h_new, e + e_new
+    return _mlp_taped(p, "decoder", h, num_layers, False, tape)
+
+
 def relu_flip_allowance(params_np, nodes, edge_attr, edge_index, target, num_layers, m_steps, tau=1e-5, max_units=256):
     """The gradient of a ReLU network is discontinuous where a pre-activation crosses zero: two evaluations that are both accurate to
     float32 rounding can disagree on the sign of a pre-activation that lies within rounding distance of zero, and then their
@@ -69,16 +83,8 @@ def relu_flip_allowance(params_np, nodes, edge_attr, edge_index, target, num_lay
     dtype = torch.float64
     p = {k: torch.tensor(v, dtype=dtype, requires_grad=True) for k, v in params_np.items()}
     tape = []
-    idx = torch.tensor(edge_index, dtype=torch.int64)
-    j, i = idx[0], idx[1]
-    h = _mlp_taped(p, "encoder.phi_node", torch.tensor(nodes, dtype=dtype), num_layers, True, tape)
-    e = _mlp_taped(p, "encoder.phi_edge", torch.tensor(edge_attr, dtype=dtype), num_layers, True, tape)
-    for k in range(m_steps):
-        e_new = _mlp_taped(p, f"processor.{k}.phi_edge", torch.cat((h[i], h[j], e), dim=1), num_layers, True, tape)
-        agg = torch.zeros_like(h).index_add_(0, i, e_new)
-        h_new = _mlp_taped(p, f"processor.{k}.phi_node", torch.cat((h, agg), dim=1), num_layers, True, tape)
-        h, e = h + h_new, e + e_new
-    out = _mlp_taped(p, "decoder", h, num_layers, False, tape)
+    out = epd_forward_taped(p, torch.tensor(nodes, dtype=dtype), torch.tensor(edge_attr, dtype=dtype),
+                            torch.tensor(edge_index, dtype=torch.int64), num_layers, m_steps, tape)
     loss = F.l1_loss(out, torch.tensor(target, dtype=dtype), reduction="sum") / out.shape[0]
     loss.backward(retain_graph=True)
     units = []   # (|z| / rms, tape entry, flat index)
