@@ -26,6 +26,11 @@
 //           down the registers; one 128-byte store per finished segment and half wave -- to its agg row, or, for the piece
 //           of a segment that began in an earlier group of 4 blocks, to that group's row of the side buffer, which the
 //           node kernel adds in group order: no atomics.  Roles run at different s_setprio levels (role 2 first).
+// A workgroup with nb blocks runs ticks -1 .. nb + 2, and every wave one barrier in each.  A role runs its chain only in the nb ticks in
+// which its Linear has a block (role 0: ticks 0 .. nb - 1, role 1: 1 .. nb, role 2: 2 .. nb + 1); in its other ticks it runs what
+// later ticks or the results need and nothing else (TICK_FILL / TICK_IDLE / TICK_LAST / TICK_DRAIN): the first block's requests
+// and image, the table rotation, the last blocks' epilogue and scatter-add.  The light ticks are straight-line code of their own
+// outside the pair loops, which keep the full tick's body.
 // The cache policy of the row stores is chosen per launch by size (STREAM, below).
 // hipcc's counted vmcnt waits assume the path with the fewest younger operations and share one in-order counter between
 // loads and stores: every global access of the tick loops is therefore branch-free, the weights are waited for before the
@@ -148,6 +153,9 @@ extern __shared__ __attribute__((aligned(16))) char smem[];
 // A lane-constant LDS / buffer base: made opaque so that hipcc addresses "base register + 16-bit immediate" instead of folding
 // every region offset into a register of its own (the DS immediate reaches 64 KiB, the regions lie further apart than that).
 __device__ __forceinline__ unsigned opaque(unsigned v) { asm volatile("" : "+v"(v)); return v; }
+// The number of a tick that runs outside the pair loop: made opaque so that hipcc compiles the tick as it compiles the loop's -- from a
+// run-time tick number -- and does not fold "this block does not exist" into constant operands of the scan's inline assembly.
+__device__ __forceinline__ int tick_no(int t) { asm volatile("" : "+s"(t)); return t; }
 #define GM_SB __builtin_amdgcn_sched_barrier(0)
 
 // accumulator registers 8q..8q+7 of a wave's 32-feature block are the elements of B fragment ks = 2 jb + q (same lane):
@@ -350,6 +358,9 @@ struct LnGroup {
 // are those ticks with the work that later ticks or the results need -- requests, rows -> image, the last block's epilogue --
 // and nothing else.
 constexpr int TICK_FULL = 0, TICK_FILL = 1, TICK_DRAIN = 2;
+// The edge kernel's roles are a tick apart, so each has ticks of its own without a block: TICK_IDLE is the barrier and whatever
+// scalar state later ticks depend on; TICK_LAST is role 0's tick of the last block: its chain, and no requests for blocks beyond.
+constexpr int TICK_IDLE = 3, TICK_LAST = 4;
 template <int V>
 using int_c = std::integral_constant<int, V>;
 
@@ -440,8 +451,22 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_edge_kernel(const CsrHeade
         for (int r = 0; r < 16; ++r) { c0v[r] = 0.f; acc[r] = 0.f; }
         intx4 di = bldi4(srd_dst, v_ioff, 0), si = bldi4(srd_src, v_ioff, 0);   // indices of the rows of block b0 ( = "x+1" of the first tick's requests)
         int2 be = a_blk[clampb(b0 + 1)];   // table entry of block x+2 (its .x = first edge): the rows and indices requested this tick
-        auto tick = [&](auto par_c, int t) {
+        auto tick_as = [&](auto par_c, auto kind_c, int t) __attribute__((always_inline)) {
             constexpr int PAR = decltype(par_c)::value;   // parity of x: the images' double buffers are compile-time offsets
+            constexpr int KIND = decltype(kind_c)::value;
+            if constexpr (KIND == TICK_IDLE) {   // ticks nb .. nb + 2: Linear 1 has no block left
+                lds_barrier();
+                return;
+            }
+            if constexpr (KIND == TICK_LAST) {   // tick nb - 1: the last block's chain; there is no block x+1 to request, image or prepare
+                auto nothing = [](int) {};
+                mlp_layer(acc, c0v, wh, wl, smem, e_r0 + PAR * IMG_B, e_r1 + PAR * IMG_B, nothing);
+                rng |= __any(acc[0] != acc[0]) ? 1 : 0;
+                GM_SB;
+                acc_to_image(acc, smem, x1_w + PAR * IMG_B);
+                lds_barrier();
+                return;
+            }
             const int x = b0 + t;
             SYS_STAMP(t, 0);
             auto prepare = [&]() {   // accumulator = (P_i[dst] + P_j[src]) * T1: row-major sum -> tile -> accumulator layout
@@ -489,13 +514,18 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_edge_kernel(const CsrHeade
                 }
             };
             SYS_STAMP(t, 2);
-            mlp_layer(acc, c0v, wh, wl, smem, e_r0 + PAR * IMG_B, e_r1 + PAR * IMG_B, side);
-            SYS_STAMP(t, 3);
-            // range check of the fp16 split: a value that does not fit an operand image is (inf, -inf) as a pair and turns every
-            // accumulator of its row into NaN (hmlp.hip: check_rows) -- one comparison per tick, wave-uniform verdict
-            rng |= __any(acc[0] != acc[0]) ? 1 : 0;
-            GM_SB;
-            acc_to_image(acc, smem, x1_w + PAR * IMG_B);
+            if constexpr (KIND == TICK_FULL) {
+                mlp_layer(acc, c0v, wh, wl, smem, e_r0 + PAR * IMG_B, e_r1 + PAR * IMG_B, side);
+                SYS_STAMP(t, 3);
+                // range check of the fp16 split: a value that does not fit an operand image is (inf, -inf) as a pair and turns every
+                // accumulator of its row into NaN (hmlp.hip: check_rows) -- one comparison per tick, wave-uniform verdict
+                rng |= __any(acc[0] != acc[0]) ? 1 : 0;
+                GM_SB;
+                acc_to_image(acc, smem, x1_w + PAR * IMG_B);
+            } else {   // the fill tick: the first block's rows -> image E, the second block's requested; nothing to multiply yet
+#pragma unroll
+                for (int slot = 0; slot <= 8; ++slot) side(slot);
+            }
             SYS_STAMP(t, 4);
             // Rotated tick: this wave's MFMAs open the tick -- while roles 1 and 2 merge statistics -- and the accumulators of
             // block x+1 (rows requested at the top of this tick) are prepared here, behind them, and cross the barrier in
@@ -505,10 +535,17 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_edge_kernel(const CsrHeade
             lds_barrier();
             SYS_STAMP(t, 6);
         };
-        // Ticks -1 .. nb + 2: one tick of fill (the e rows and indices of the first block come from the prologue), nb ticks in
-        // which blocks enter, three that drain the pipeline: an even count (nb is a multiple of 4), taken as (odd, even) pairs --
-        // at N = 5k a workgroup has 12 blocks, and every fill / drain tick counts.
-        RUN_TICKS(-1, nb + 1, tick);
+        // Ticks -1 .. nb + 2, nb a multiple of 4: one tick of fill (the e rows and indices of the first block come from the
+        // prologue), nb ticks in which blocks enter -- the middle ones as (odd, even) pairs --, three in which the other roles
+        // drain the pipeline.  At N = 5k a workgroup has 12 blocks: run as full ticks, fill and drain were a quarter of the launch.
+        auto tick = [&](auto par_c, int t) __attribute__((always_inline)) { tick_as(par_c, int_c<TICK_FULL>{}, t); };
+        tick_as(int_c<1>{}, int_c<TICK_FILL>{}, -1);
+        tick(int_c<0>{}, tick_no(0));
+        RUN_TICKS(1, nb - 3, tick);
+        tick_as(int_c<1>{}, int_c<TICK_LAST>{}, nb - 1);
+        tick_as(int_c<0>{}, int_c<TICK_IDLE>{}, nb);
+        tick_as(int_c<1>{}, int_c<TICK_IDLE>{}, nb + 1);
+        tick_as(int_c<0>{}, int_c<TICK_IDLE>{}, nb + 2);
         report_split_range<false>(rng, lane0, a_flags);
     } else if (role == 1) {
         // ------------------------------------------------------------------ role 1
@@ -530,9 +567,18 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_edge_kernel(const CsrHeade
         const unsigned z_r = opaque(L_Z + jb * TILE_B + rr * TILE_ROW_B + cq * 16);
         const unsigned x_in = opaque(L_X1 + lane0 * 16), x_out = opaque(L_X2 + 4 * jb * 1024 + lane0 * 16);
         float* const e_out_wg = a_e_out + (size_t)e0 * H;
-        auto tick = [&](auto par_c, int t) {
+        auto tick_as = [&](auto par_c, auto kind_c, int t) {
             constexpr int PAR = decltype(par_c)::value, P1 = 1 - PAR, P3 = 1 - PAR;   // parities of blocks x, x-1 (this Linear's), x-3
+            constexpr int KIND = decltype(kind_c)::value;
             const int x = b0 + t;
+            if constexpr (KIND == TICK_IDLE) {   // ticks -1, 0: no block has reached Linear 2 yet; the table entries rotate as always
+                const int2 bi_i = a_blk[clampb(x)];
+                st_a = st_b; cnt_a = cnt_b;
+                st_b = bi_c.x; cnt_b = bi_c.y & 0xff;
+                bi_c = bi_i;
+                lds_barrier();
+                return;
+            }
             SYS_STAMP(t, 0);
             // 1 / (T sigma) of the rows of block x-3: lane n (both halves) -> this wave's table
             if (WRITE_E) LDS(float, km_w) = ln_k(smem, st_r + P3 * 512, inv_T, a_eps);
@@ -549,10 +595,15 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_edge_kernel(const CsrHeade
             };
             SYS_STAMP(t, 1);
             SYS_STAMP(t, 2);
-            mlp_layer(acc, b2v, wh, wl, smem, x_in + P1 * IMG_B, x_in + P1 * IMG_B, side);
-            rng |= __any(acc[0] != acc[0]) ? 1 : 0;
-            GM_SB;
-            acc_to_image(acc, smem, x_out + P1 * IMG_B);
+            if constexpr (KIND == TICK_FULL) {
+                mlp_layer(acc, b2v, wh, wl, smem, x_in + P1 * IMG_B, x_in + P1 * IMG_B, side);
+                rng |= __any(acc[0] != acc[0]) ? 1 : 0;
+                GM_SB;
+                acc_to_image(acc, smem, x_out + P1 * IMG_B);
+            } else {   // ticks nb + 1, nb + 2: the epilogue of the last two blocks alone
+#pragma unroll
+                for (int slot = 0; slot <= 2; ++slot) side(slot);
+            }
             SYS_STAMP(t, 3);
             SYS_STAMP(t, 4);
             st_a = st_b; cnt_a = cnt_b;
@@ -562,7 +613,12 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_edge_kernel(const CsrHeade
             lds_barrier();
             SYS_STAMP(t, 6);
         };
-        RUN_TICKS(-1, nb + 1, tick);
+        auto tick = [&](auto par_c, int t) { tick_as(par_c, int_c<TICK_FULL>{}, t); };
+        tick_as(int_c<1>{}, int_c<TICK_IDLE>{}, -1);
+        tick_as(int_c<0>{}, int_c<TICK_IDLE>{}, 0);
+        RUN_TICKS(1, nb - 1, tick);   // Linear 2 of blocks b0 .. b1 - 1: ticks 1 .. nb
+        tick_as(int_c<1>{}, int_c<TICK_DRAIN>{}, nb + 1);
+        tick_as(int_c<0>{}, int_c<TICK_DRAIN>{}, nb + 2);
         report_split_range<false>(rng, lane0, a_flags);
     } else {
         // ------------------------------------------------------------------ role 2
@@ -608,12 +664,26 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_edge_kernel(const CsrHeade
             last = (unsigned)si.y;
             if (fl & 1) head = hd;
         };
-        auto tick = [&](auto par_c, int t) {
+        auto tick_as = [&](auto par_c, auto kind_c, int t) __attribute__((always_inline)) {
             constexpr int PAR = decltype(par_c)::value, P2 = PAR, P3 = 1 - PAR;   // parities of blocks x-2, x-3
+            constexpr int KIND = decltype(kind_c)::value;
             const int x = b0 + t;
             // table entries of block x (decoded next tick): requested at the top, so that the barrier's scalar-memory wait finds them done
             const int2 bn_n = a_blk[clampb(x)], sn_n = a_seg[clampb(x)];
             const int hd_n = a_head[clampb(x - 1) >> 2];   // head of block x-1's group (used if that block opens its group)
+            if constexpr (KIND == TICK_IDLE) {
+                // ticks -1 .. 1: no block has reached Linear 3 yet, none the scatter-add (carry stays 0, nothing is stored); the
+                // table entries advance as always.  Z and ST keep the prologue's zeros until tick 2: what ticks 1 and 2 make of
+                // them (blocks before b0: cnt = 0, no segment bits) is dropped by the stores' bounds.
+                cnt_a = cnt_b; fl_a = fl_b; cont_a = cont_b; last_a = last_b;
+                if (fl_b & 1) head_a = head_b;
+                st_a = st_b;
+                fetch(x - 1, bn, sn, hd_n, st_b, cnt_b, fl_b, cont_b, last_b, head_b);
+                bn = bn_n;
+                sn = sn_n;
+                lds_barrier();
+                return;
+            }
             b3v = vec_to_acc(smem, L_VEC, H, jb, hi);  // b3' T3 -> the first MFMA's C operand (lands under the statistics merge)
             const bool agg_on = ok(x - 3);
             SYS_STAMP(t, 0);
@@ -690,6 +760,10 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_edge_kernel(const CsrHeade
                 const float nc = upper_half_to_both(y[15] + cpend);
                 carry = (((last >> 31) & 1u) || !agg_on || cnt_a < BE) ? 0.f : nc;
             };
+            if constexpr (KIND == TICK_DRAIN) {   // tick nb + 2: the last block's scatter-add and epilogue, no Linear 3
+#pragma unroll
+                for (int slot = 0; slot < 20; ++slot) side(slot);
+            } else {
             mlp_layer(acc, b3v, wh, wl, smem, x_in + P2 * IMG_B, x_in + P2 * IMG_B, side);
             SYS_STAMP(t, 3);   // 24 MFMAs with the scatter-add between them
             rng |= __any(acc[0] != acc[0]) ? 1 : 0;
@@ -710,6 +784,7 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_edge_kernel(const CsrHeade
                     LDS(floatx4, z_w + P2 * 4 * TILE_B + 32 * g) = z;
                 }
             }
+            }
             SYS_STAMP(t, 4);   // statistics + Z written
             stores();
             cnt_a = cnt_b; fl_a = fl_b; cont_a = cont_b; last_a = last_b;
@@ -722,7 +797,14 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_edge_kernel(const CsrHeade
             lds_barrier();
             SYS_STAMP(t, 6);   // every wave of the workgroup has finished the tick
         };
-        RUN_TICKS(-1, nb + 1, tick);
+        auto tick = [&](auto par_c, int t) __attribute__((always_inline)) { tick_as(par_c, int_c<TICK_FULL>{}, t); };
+        tick_as(int_c<1>{}, int_c<TICK_IDLE>{}, -1);
+        tick_as(int_c<0>{}, int_c<TICK_IDLE>{}, 0);
+        tick_as(int_c<1>{}, int_c<TICK_IDLE>{}, 1);
+        tick(int_c<0>{}, tick_no(2));
+        RUN_TICKS(3, nb - 1, tick);   // with ticks 2 and nb + 1: Linear 3 of blocks b0 .. b1 - 1
+        tick(int_c<1>{}, nb + 1);
+        tick_as(int_c<0>{}, int_c<TICK_DRAIN>{}, nb + 2);
         report_split_range<false>(rng, lane0, a_flags);
     }
 }
