@@ -116,6 +116,7 @@ PROTOTYPES = {
     "gm_model_profile": (_i32, [_vp, _i32]),
     "gm_model_set_edge_kernel": (_i32, [_vp, _i32]),
     "gm_model_set_node_fusion": (_i32, [_vp, _i32]),
+    "gm_model_set_precision": (_i32, [_vp, _i32]),
     "gm_model_profile_query": (_i32, [_vp, _i32, C.POINTER(_i64), C.POINTER(_f64)]),
 }
 

@@ -75,6 +75,7 @@ struct NodeSysArgs {
     int* flags;
     float eps;
     ProfState* prof;
+    int precision;         // kPrecisionF32 / kPrecisionF16 (mlp.h)
 };
 int launch_node_sys(const NodeSysArgs& a, hipStream_t s);
 struct ProjSysArgs {
@@ -88,6 +89,7 @@ struct ProjSysArgs {
     int n;
     int* flags;
     ProfState* prof;
+    int precision;         // kPrecisionF32 / kPrecisionF16 (mlp.h)
 };
 int launch_proj_sys(const ProjSysArgs& a, hipStream_t s);
 // launch_node_sys(a) and launch_proj_sys(p) as one launch (sys_node_proj_kernel): p.h = a.h_out, p.Q = a.Q, the same n and flags.

@@ -161,6 +161,7 @@ __device__ __forceinline__ int tick_no(int t) { asm volatile("" : "+s"(t)); retu
 // accumulator registers 8q..8q+7 of a wave's 32-feature block are the elements of B fragment ks = 2 jb + q (same lane):
 // K slot (lane >> 5, j) of k-group ks carries feature 16 ks + 8 (j >> 2) + 4 (lane >> 5) + (j & 3) in both operands.
 // a: byte address of this lane's slot in fragment (ks = 2 jb, hi part) of the image.
+template <int NP>
 __device__ __forceinline__ void acc_to_image(const floatx16& a, char* smem, unsigned addr) {
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
@@ -168,10 +169,15 @@ __device__ __forceinline__ void acc_to_image(const floatx16& a, char* smem, unsi
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] = relu(a[8 * q + j]);
         uintx2 h0, l0, h1, l1;
-        split4(v[0], v[1], v[2], v[3], h0, l0);
-        split4(v[4], v[5], v[6], v[7], h1, l1);
+        if constexpr (NP == 3) {
+            split4(v[0], v[1], v[2], v[3], h0, l0);
+            split4(v[4], v[5], v[6], v[7], h1, l1);
+        } else {
+            hi4(v[0], v[1], v[2], v[3], h0);
+            hi4(v[4], v[5], v[6], v[7], h1);
+        }
         LDS(uintx4, addr + (q * 2 + 0) * 1024) = uintx4{h0[0], h0[1], h1[0], h1[1]};
-        LDS(uintx4, addr + (q * 2 + 1) * 1024) = uintx4{l0[0], l0[1], l1[0], l1[1]};
+        if constexpr (NP == 3) LDS(uintx4, addr + (q * 2 + 1) * 1024) = uintx4{l0[0], l0[1], l1[0], l1[1]};
     }
 }
 
@@ -179,8 +185,30 @@ __device__ __forceinline__ void acc_to_image(const floatx16& a, char* smem, unsi
 // after each MFMA with the instruction order pinned.  B fragments are fetched one k-group (hi part) / two MFMAs (lo part) ahead.  a0 / a1: byte address of this
 // lane's slot in fragment (0, hi part) for the even / odd k-groups (they differ in the swizzled image E only); c0: initial
 // accumulators (the first MFMA's C operand).
-template <class F>
+// NP = 1 (the fp16 mode): 8 k-groups x 1 MFMA (hi*hi); the 24 side slots keep their numbers and their order, three behind each MFMA,
+// so what a role places in them does not move between roles or ticks.  The lo fragments (wl, the images' lo parts) are not read.
+template <int NP, class F>
 __device__ __forceinline__ void mlp_layer(floatx16& acc, const floatx16& c0, const half8 (&wh)[8], const half8 (&wl)[8], char* smem, unsigned a0, unsigned a1, F&& side) {
+    if constexpr (NP == 1) {
+        half8 bh = LDS(half8, a0);
+#pragma unroll
+        for (int ks = 0; ks < 8; ++ks) {
+            half8 nh = bh;
+            const unsigned an = (((ks + 1) & 1) ? a1 : a0) + (ks + 1) * 2048;
+            GM_SB;
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[ks], bh, ks == 0 ? c0 : acc, 0, 0, 0);
+            GM_SB;
+            if (ks + 1 < 8) nh = LDS(half8, an);
+            side(3 * ks);
+            GM_SB;
+            side(3 * ks + 1);
+            GM_SB;
+            side(3 * ks + 2);
+            bh = nh;
+        }
+        GM_SB;
+        return;
+    }
     half8 bh = LDS(half8, a0), bl = LDS(half8, a0 + 1024);
 #pragma unroll
     for (int ks = 0; ks < 8; ++ks) {
@@ -266,14 +294,15 @@ __device__ __forceinline__ int2 wg_range(int units, bool xcd_major) {
 // multiplies k-group 0 only (its image holds zeros beyond) and loads that one --, LDS [0, zero_end) zeroed, n_vec floats of
 // vec to vec_b, and a workgroup barrier.  I: type of the fragment index (sys_proj_kernel's images, hmlp.h, are addressed with
 // size_t; the kernel reads its bias from global memory before the prologue).
-template <class I = int>
+// NP = 1: the lo fragments are not loaded (wl stays unset and unread).
+template <int NP, class I = int>
 __device__ __forceinline__ void sys_prologue(half8 (&wh)[8], half8 (&wl)[8], const half8* frag, int slice, bool one_kgroup, int zero_end, int vec_b, const float* vec, int n_vec) {
     const int tid = threadIdx.x, lane0 = tid & 63;
 #pragma unroll
     for (int ks = 0; ks < 8; ++ks) {
         const int kq = one_kgroup ? 0 : ks;
         wh[ks] = frag[(((I)slice * 8 + kq) * 2 + 0) * 64 + lane0];
-        wl[ks] = frag[(((I)slice * 8 + kq) * 2 + 1) * 64 + lane0];
+        if constexpr (NP == 3) wl[ks] = frag[(((I)slice * 8 + kq) * 2 + 1) * 64 + lane0];
     }
     // every buffer starts finite: the pipeline's fill / drain ticks compute on them
     for (int i = tid; i < zero_end / 16; i += SYS_THREADS) LDS(uintx4, i * 16) = uintx4{0u, 0u, 0u, 0u};
@@ -391,7 +420,8 @@ __device__ __forceinline__ void report_split_range(int rng, int lane0, int* flag
 // epd_gnn.py:96) -- LayerNorm statistics and the scatter-add run as always, the row-major epilogue (residual read, e + e', store)
 // does not exist: 1 GB less written and 1 GB less re-read at the target.
 // STREAM: the cache policy of the row stores (ST_STREAM_* above).
-template <bool WRITE_E, bool STREAM>
+// NP: partial products per multiply (hmma_dev.h: 3, or 1 in the fp16 mode).
+template <bool WRITE_E, bool STREAM, int NP>
 __global__ void __launch_bounds__(SYS_THREADS, 1) sys_edge_kernel(const CsrHeader* a_hdr, const int* __restrict__ a_dst, const int* __restrict__ a_src, const float* __restrict__ a_P,
                                                                        const float* a_e_in, float* a_e_out, float* __restrict__ a_agg, const float* __restrict__ a_hw,
                                                                        const int2* __restrict__ a_blk, const int2* __restrict__ a_seg, const int* __restrict__ a_head,
@@ -412,7 +442,7 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_edge_kernel(const CsrHeade
     if (nb <= 0) return;
     const float inv_T = a_hw[1];
     half8 wh[8], wl[8];
-    sys_prologue(wh, wl, reinterpret_cast<const half8*>(a_hw + HW_HEADER_FLOATS + HW_VEC_FLOATS), role * 4 + jb, false, L_ZERO_END, L_VEC,
+    sys_prologue<NP>(wh, wl, reinterpret_cast<const half8*>(a_hw + HW_HEADER_FLOATS + HW_VEC_FLOATS), role * 4 + jb, false, L_ZERO_END, L_VEC,
                       a_hw + HW_HEADER_FLOATS, 4 * H);
     auto ok = [&](int x) { return x >= b0 && x < b1; };
     auto clampb = [&](int x) { return x < b0 ? b0 : (x < b1 ? x : b1 - 1); };
@@ -460,10 +490,10 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_edge_kernel(const CsrHeade
             }
             if constexpr (KIND == TICK_LAST) {   // tick nb - 1: the last block's chain; there is no block x+1 to request, image or prepare
                 auto nothing = [](int) {};
-                mlp_layer(acc, c0v, wh, wl, smem, e_r0 + PAR * IMG_B, e_r1 + PAR * IMG_B, nothing);
-                rng |= __any(acc[0] != acc[0]) ? 1 : 0;
+                mlp_layer<NP>(acc, c0v, wh, wl, smem, e_r0 + PAR * IMG_B, e_r1 + PAR * IMG_B, nothing);
+                rng |= __any(row_bad<NP>(acc[0])) ? 1 : 0;
                 GM_SB;
-                acc_to_image(acc, smem, x1_w + PAR * IMG_B);
+                acc_to_image<NP>(acc, smem, x1_w + PAR * IMG_B);
                 lds_barrier();
                 return;
             }
@@ -504,9 +534,10 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_edge_kernel(const CsrHeade
                 if (slot < 8 && !(slot & 1)) {
                     const int j = slot >> 1;
                     uintx2 h, l;
-                    split4(eq[j][0], eq[j][1], eq[j][2], eq[j][3], h, l);
+                    if constexpr (NP == 3) split4(eq[j][0], eq[j][1], eq[j][2], eq[j][3], h, l);
+                    else hi4(eq[j][0], eq[j][1], eq[j][2], eq[j][3], h);
                     LDS(uintx2, e_w + (1 - PAR) * IMG_B + j * 128) = h;
-                    LDS(uintx2, e_w + (1 - PAR) * IMG_B + j * 128 + 1024) = l;
+                    if constexpr (NP == 3) LDS(uintx2, e_w + (1 - PAR) * IMG_B + j * 128 + 1024) = l;
                 } else if (slot == 8) {
 #pragma unroll
                     for (int j = 0; j < 4; ++j) eq[j] = bld4(srd_ein, v_eoff, rel * 512 + j * 4096);
@@ -515,13 +546,13 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_edge_kernel(const CsrHeade
             };
             SYS_STAMP(t, 2);
             if constexpr (KIND == TICK_FULL) {
-                mlp_layer(acc, c0v, wh, wl, smem, e_r0 + PAR * IMG_B, e_r1 + PAR * IMG_B, side);
+                mlp_layer<NP>(acc, c0v, wh, wl, smem, e_r0 + PAR * IMG_B, e_r1 + PAR * IMG_B, side);
                 SYS_STAMP(t, 3);
                 // range check of the fp16 split: a value that does not fit an operand image is (inf, -inf) as a pair and turns every
                 // accumulator of its row into NaN (hmlp.hip: check_rows) -- one comparison per tick, wave-uniform verdict
-                rng |= __any(acc[0] != acc[0]) ? 1 : 0;
+                rng |= __any(row_bad<NP>(acc[0])) ? 1 : 0;
                 GM_SB;
-                acc_to_image(acc, smem, x1_w + PAR * IMG_B);
+                acc_to_image<NP>(acc, smem, x1_w + PAR * IMG_B);
             } else {   // the fill tick: the first block's rows -> image E, the second block's requested; nothing to multiply yet
 #pragma unroll
                 for (int slot = 0; slot <= 8; ++slot) side(slot);
@@ -596,10 +627,10 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_edge_kernel(const CsrHeade
             SYS_STAMP(t, 1);
             SYS_STAMP(t, 2);
             if constexpr (KIND == TICK_FULL) {
-                mlp_layer(acc, b2v, wh, wl, smem, x_in + P1 * IMG_B, x_in + P1 * IMG_B, side);
-                rng |= __any(acc[0] != acc[0]) ? 1 : 0;
+                mlp_layer<NP>(acc, b2v, wh, wl, smem, x_in + P1 * IMG_B, x_in + P1 * IMG_B, side);
+                rng |= __any(row_bad<NP>(acc[0])) ? 1 : 0;
                 GM_SB;
-                acc_to_image(acc, smem, x_out + P1 * IMG_B);
+                acc_to_image<NP>(acc, smem, x_out + P1 * IMG_B);
             } else {   // ticks nb + 1, nb + 2: the epilogue of the last two blocks alone
 #pragma unroll
                 for (int slot = 0; slot <= 2; ++slot) side(slot);
@@ -764,9 +795,9 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_edge_kernel(const CsrHeade
 #pragma unroll
                 for (int slot = 0; slot < 20; ++slot) side(slot);
             } else {
-            mlp_layer(acc, b3v, wh, wl, smem, x_in + P2 * IMG_B, x_in + P2 * IMG_B, side);
+            mlp_layer<NP>(acc, b3v, wh, wl, smem, x_in + P2 * IMG_B, x_in + P2 * IMG_B, side);
             SYS_STAMP(t, 3);   // 24 MFMAs with the scatter-add between them
-            rng |= __any(acc[0] != acc[0]) ? 1 : 0;
+            rng |= __any(row_bad<NP>(acc[0])) ? 1 : 0;
             {
                 // (publish_ln_stats written out: through the helper hipcc moves slot 13's carry selects behind the statistics)
                 // LayerNorm statistics of the scaled accumulators: the image's W3 / b3 are centred over the output features, so a
@@ -828,6 +859,7 @@ constexpr int LE_ZERO_END = LE_RS + RS_SLOTS * 32 * 4;
 constexpr int LE_VEC = LE_ZERO_END;                // 5 x 128 floats
 constexpr size_t ENC_LDS_BYTES = LE_VEC + 5 * H * 4;
 
+template <int NP>
 __global__ void __launch_bounds__(SYS_THREADS, 1) sys_enc_kernel(const CsrHeader* a_hdr, const float* __restrict__ a_x, float* __restrict__ a_e_out,
                                                                       const float* __restrict__ a_hw, int* a_flags, float a_eps, int a_pad_rows) {
     const int tid = threadIdx.x, lane0 = tid & 63;
@@ -845,7 +877,7 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_enc_kernel(const CsrHeader
     if (nb <= 0) return;
     const float inv_T = a_hw[1], cap = a_hw[2];
     half8 wh[8], wl[8];
-    sys_prologue(wh, wl, reinterpret_cast<const half8*>(a_hw + HW_HEADER_FLOATS + HW_VEC_FLOATS), role * 4 + jb, role == 0, LE_ZERO_END, LE_VEC,
+    sys_prologue<NP>(wh, wl, reinterpret_cast<const half8*>(a_hw + HW_HEADER_FLOATS + HW_VEC_FLOATS), role * 4 + jb, role == 0, LE_ZERO_END, LE_VEC,
                       a_hw + HW_HEADER_FLOATS, 5 * H);
     const int n = lane0 & 31, hi = lane0 >> 5, rr = lane0 >> 3, cq = lane0 & 7;
     const int e0 = b0 * BE;                               // first row of the workgroup
@@ -898,17 +930,23 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_enc_kernel(const CsrHeader
             sc = lower_half_to_both(sc);           // both halves of the wave hold row n's scale
             if (jb == 0 && hi == 0) LDS(float, rs_l + (x & (RS_SLOTS - 1)) * 128) = sc;
             uintx2 h, l;
-            split4(xq[0] * sc, xq[1] * sc, xq[2] * sc, xq[3] * sc, h, l);   // upper half: zeros (features 4 .. 7 do not exist)
-            const half8 bh = __builtin_bit_cast(half8, uintx4{h[0], h[1], 0u, 0u}), bl = __builtin_bit_cast(half8, uintx4{l[0], l[1], 0u, 0u});
+            if constexpr (NP == 3) split4(xq[0] * sc, xq[1] * sc, xq[2] * sc, xq[3] * sc, h, l);   // upper half: zeros (features 4 .. 7 do not exist)
+            else hi4(xq[0] * sc, xq[1] * sc, xq[2] * sc, xq[3] * sc, h);
+            const half8 bh = __builtin_bit_cast(half8, uintx4{h[0], h[1], 0u, 0u});
             const floatx16 c0v = scaled_bias(sc);
             // rows of the next block (clamped to the workgroup's range: the fill / drain ticks recompute a block, nothing is stored)
             {
                 const int xn = x + 1 < b0 ? b0 : (x + 1 < b1 ? x + 1 : b1 - 1);
                 xq = bld4(srd_x, v_xoff, (unsigned)(xn - b0) * 512u);
             }
+            if constexpr (NP == 3) {
+            const half8 bl = __builtin_bit_cast(half8, uintx4{l[0], l[1], 0u, 0u});
             acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl[0], bh, c0v, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[0], bl, acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[0], bh, acc, 0, 0, 0);
+            } else {
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[0], bh, c0v, 0, 0, 0);
+            }
             // ---- LayerNorm + store of block x-3 (its statistics and tiles were written a tick ago)
             {
                 const float rs3 = LDS(float, rs_l + ((x - 3) & (RS_SLOTS - 1)) * 128);
@@ -930,9 +968,9 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_enc_kernel(const CsrHeader
                     bst4s<ST_ENC_E>(make_srd(e_out_wg + (size_t)((xb - b0) * BE + 8 * j) * H, (unsigned)s_clamp0(cnt - 8 * j, 8) * 512u), v_eoff, 0, o);
                 }
             }
-            rng |= __any(acc[0] != acc[0]) ? 1 : 0;
+            rng |= __any(row_bad<NP>(acc[0])) ? 1 : 0;
             GM_SB;
-            acc_to_image(acc, smem, x1_w + PAR * IMG_B);
+            acc_to_image<NP>(acc, smem, x1_w + PAR * IMG_B);
             lds_barrier();
         };
         RUN_TICKS(0, nb + 2, tick);   // ticks 0 .. nb + 2 (one more when nb is even: it drains like the one before it)
@@ -943,10 +981,10 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_enc_kernel(const CsrHeader
             constexpr int PAR = decltype(par_c)::value, P1 = 1 - PAR;
             const int x = b0 + t;
             const floatx16 c0v = scaled_bias(LDS(float, rs_l + ((x - 1) & (RS_SLOTS - 1)) * 128));
-            mlp_layer(acc, c0v, wh, wl, smem, x_in + P1 * IMG_B, x_in + P1 * IMG_B, nothing);
-            rng |= __any(acc[0] != acc[0]) ? 1 : 0;
+            mlp_layer<NP>(acc, c0v, wh, wl, smem, x_in + P1 * IMG_B, x_in + P1 * IMG_B, nothing);
+            rng |= __any(row_bad<NP>(acc[0])) ? 1 : 0;
             GM_SB;
-            acc_to_image(acc, smem, x_out + P1 * IMG_B);
+            acc_to_image<NP>(acc, smem, x_out + P1 * IMG_B);
             lds_barrier();
         };
         RUN_TICKS(0, nb + 2, tick);   // ticks 0 .. nb + 2 (one more when nb is even: it drains like the one before it)
@@ -959,8 +997,8 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_enc_kernel(const CsrHeader
             constexpr int PAR = decltype(par_c)::value, P2 = PAR;
             const int x = b0 + t;
             const floatx16 c0v = scaled_bias(LDS(float, rs_l + ((x - 2) & (RS_SLOTS - 1)) * 128));
-            mlp_layer(acc, c0v, wh, wl, smem, x_in + P2 * IMG_B, x_in + P2 * IMG_B, nothing);
-            rng |= __any(acc[0] != acc[0]) ? 1 : 0;
+            mlp_layer<NP>(acc, c0v, wh, wl, smem, x_in + P2 * IMG_B, x_in + P2 * IMG_B, nothing);
+            rng |= __any(row_bad<NP>(acc[0])) ? 1 : 0;
             publish_ln_stats(acc, st_w + P2 * 512, z_w + P2 * 4 * TILE_B);
             lds_barrier();
         };
@@ -996,6 +1034,7 @@ constexpr size_t NODE_LDS_BYTES = LN_VEC + 4 * H * 4;
 static_assert(NODE_LDS_BYTES <= 160 * 1024, "LDS budget");
 
 // The kernel's body as a function: sys_node_kernel is this alone, sys_node_proj_kernel runs the projections behind it.
+template <int NP>
 __device__ __forceinline__ void sys_node_body(const float* a_h, const float* __restrict__ a_agg, const float* __restrict__ a_Q,
                                               float* a_h_out, const float* __restrict__ a_hw, int a_n, int* a_flags, float a_eps) {
     const int tid = threadIdx.x, lane0 = tid & 63;
@@ -1009,7 +1048,7 @@ __device__ __forceinline__ void sys_node_body(const float* a_h, const float* __r
     if (nb <= 0) return;
     const float inv_T = a_hw[1];
     half8 wh[8], wl[8];
-    sys_prologue(wh, wl, reinterpret_cast<const half8*>(a_hw + HW_HEADER_FLOATS + HW_VEC_FLOATS), role * 4 + jb, false, LN_ZERO_END, LN_VEC,
+    sys_prologue<NP>(wh, wl, reinterpret_cast<const half8*>(a_hw + HW_HEADER_FLOATS + HW_VEC_FLOATS), role * 4 + jb, false, LN_ZERO_END, LN_VEC,
                  a_hw + HW_HEADER_FLOATS, 4 * H);
     const int n = lane0 & 31, hi = lane0 >> 5, rr = lane0 >> 3, cq = lane0 & 7;
     const int r0 = b0 * BE;                                 // first row of the workgroup
@@ -1048,19 +1087,20 @@ __device__ __forceinline__ void sys_node_body(const float* a_h, const float* __r
                 if (slot < 8 && !(slot & 1)) {
                     const int j = slot >> 1;
                     uintx2 h, l;
-                    split4(eq[j][0], eq[j][1], eq[j][2], eq[j][3], h, l);
+                    if constexpr (NP == 3) split4(eq[j][0], eq[j][1], eq[j][2], eq[j][3], h, l);
+                    else hi4(eq[j][0], eq[j][1], eq[j][2], eq[j][3], h);
                     LDS(uintx2, e_w + (1 - PAR) * IMG_B + j * 128) = h;
-                    LDS(uintx2, e_w + (1 - PAR) * IMG_B + j * 128 + 1024) = l;
+                    if constexpr (NP == 3) LDS(uintx2, e_w + (1 - PAR) * IMG_B + j * 128 + 1024) = l;
                 } else if (slot == 8) {
 #pragma unroll
                     for (int j = 0; j < 4; ++j) eq[j] = bld4(srd_a, v_eoff, rel2 + j * 4096);
                 }
             };
             if constexpr (KIND == TICK_FULL) {
-                mlp_layer(acc, c0v, wh, wl, smem, e_r0 + PAR * IMG_B, e_r1 + PAR * IMG_B, side);
-                rng |= __any(acc[0] != acc[0]) ? 1 : 0;
+                mlp_layer<NP>(acc, c0v, wh, wl, smem, e_r0 + PAR * IMG_B, e_r1 + PAR * IMG_B, side);
+                rng |= __any(row_bad<NP>(acc[0])) ? 1 : 0;
                 GM_SB;
-                acc_to_image(acc, smem, x1_w + PAR * IMG_B);
+                acc_to_image<NP>(acc, smem, x1_w + PAR * IMG_B);
             } else {   // the fill tick: the first block's rows -> image E, the requests behind it
 #pragma unroll
                 for (int slot = 0; slot <= 8; ++slot) side(slot);
@@ -1129,13 +1169,13 @@ __device__ __forceinline__ void sys_node_body(const float* a_h, const float* __r
 #pragma unroll
                 for (int slot = 0; slot <= 8; ++slot) side(slot);
             } else if (!r2) {
-                mlp_layer(acc, bv, wh, wl, smem, x_in + PIN * IMG_B, x_in + PIN * IMG_B, side);
-                rng |= __any(acc[0] != acc[0]) ? 1 : 0;
+                mlp_layer<NP>(acc, bv, wh, wl, smem, x_in + PIN * IMG_B, x_in + PIN * IMG_B, side);
+                rng |= __any(row_bad<NP>(acc[0])) ? 1 : 0;
                 GM_SB;
-                acc_to_image(acc, smem, x_out + PIN * IMG_B);
+                acc_to_image<NP>(acc, smem, x_out + PIN * IMG_B);
             } else {
-                mlp_layer(acc, bv, wh, wl, smem, x_in + PAR * IMG_B, x_in + PAR * IMG_B, side);
-                rng |= __any(acc[0] != acc[0]) ? 1 : 0;
+                mlp_layer<NP>(acc, bv, wh, wl, smem, x_in + PAR * IMG_B, x_in + PAR * IMG_B, side);
+                rng |= __any(row_bad<NP>(acc[0])) ? 1 : 0;
                 publish_ln_stats(acc, st_w + PAR * 512, z_w + PAR * 4 * TILE_B);
             }
             lds_barrier();
@@ -1145,9 +1185,10 @@ __device__ __forceinline__ void sys_node_body(const float* a_h, const float* __r
     report_split_range(rng, lane0, a_flags);
 }
 
+template <int NP>
 __global__ void __launch_bounds__(SYS_THREADS, 1) sys_node_kernel(const float* a_h, const float* __restrict__ a_agg, const float* __restrict__ a_Q,
                                                                        float* a_h_out, const float* __restrict__ a_hw, int a_n, int* a_flags, float a_eps) {
-    sys_node_body(a_h, a_agg, a_Q, a_h_out, a_hw, a_n, a_flags, a_eps);
+    sys_node_body<NP>(a_h, a_agg, a_Q, a_h_out, a_hw, a_n, a_flags, a_eps);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1163,7 +1204,7 @@ constexpr size_t PROJ_LDS_BYTES = LP_T + 12 * TILE_B;
 
 // The kernel's body as a function (sys_proj_kernel, and the second phase of sys_node_proj_kernel).  LD_H: cache-policy bits of the
 // loads of h rows.
-template <int LD_H>
+template <int LD_H, int NP>
 __device__ __forceinline__ void sys_proj_body(const float* __restrict__ a_h, float* __restrict__ a_P, float* __restrict__ a_Q,
                                               const float* __restrict__ a_wp, const float* __restrict__ a_wq,
                                               const float* __restrict__ a_sp, const float* __restrict__ a_sq, int a_n, int* a_flags) {
@@ -1189,7 +1230,7 @@ __device__ __forceinline__ void sys_proj_body(const float* __restrict__ a_h, flo
         for (int tt = 0; tt < 4; ++tt) bv[4 * g + tt] = v[tt];
     }
     half8 wh[8], wl[8];
-    sys_prologue<size_t>(wh, wl, reinterpret_cast<const half8*>(img + 4 + out_pad), ob, false, LP_E + 2 * IMG_B, 0, nullptr, 0);
+    sys_prologue<NP, size_t>(wh, wl, reinterpret_cast<const half8*>(img + 4 + out_pad), ob, false, LP_E + 2 * IMG_B, 0, nullptr, 0);
     const int r0 = b0 * BE;
     const int rows_wg = (b1 * BE < N ? b1 * BE : N) - r0;
     const unsigned wg_bytes = (unsigned)(rows_wg > 0 ? rows_wg : 0) * 512u;
@@ -1225,9 +1266,10 @@ __device__ __forceinline__ void sys_proj_body(const float* __restrict__ a_h, flo
             if (producer && (slot == 0 || slot == 2)) {   // rows of block x+1 -> image
                 const int i = slot >> 1;
                 uintx2 h, l;
-                split4(hq[i][0], hq[i][1], hq[i][2], hq[i][3], h, l);
+                if constexpr (NP == 3) split4(hq[i][0], hq[i][1], hq[i][2], hq[i][3], h, l);
+                else hi4(hq[i][0], hq[i][1], hq[i][2], hq[i][3], h);
                 LDS(uintx2, e_w[i] + (1 - PAR) * IMG_B) = h;
-                LDS(uintx2, e_w[i] + (1 - PAR) * IMG_B + 1024) = l;
+                if constexpr (NP == 3) LDS(uintx2, e_w[i] + (1 - PAR) * IMG_B + 1024) = l;
             } else if (producer && slot == 4) {
 #pragma unroll
                 for (int i = 0; i < 2; ++i) hq[i] = bld4s<LD_H>(srd_h, v_in[i], rel2);
@@ -1239,8 +1281,8 @@ __device__ __forceinline__ void sys_proj_body(const float* __restrict__ a_h, flo
             lds_barrier();
             return;
         }
-        mlp_layer(acc, bv, wh, wl, smem, e_r0 + PAR * IMG_B, e_r1 + PAR * IMG_B, side);
-        rng |= __any(acc[0] != acc[0]) ? 1 : 0;
+        mlp_layer<NP>(acc, bv, wh, wl, smem, e_r0 + PAR * IMG_B, e_r1 + PAR * IMG_B, side);
+        rng |= __any(row_bad<NP>(acc[0])) ? 1 : 0;
         // outputs of block x: accumulator layout -> the wave's own tile -> row-major, whole 128-byte lines (rows that do not exist
         // lie beyond the resource's byte count)
 #pragma unroll
@@ -1269,10 +1311,11 @@ __device__ __forceinline__ void sys_proj_body(const float* __restrict__ a_h, flo
     report_split_range(rng, lane0, a_flags);
 }
 
+template <int NP>
 __global__ void __launch_bounds__(SYS_THREADS, 1) sys_proj_kernel(const float* __restrict__ a_h, float* __restrict__ a_P, float* __restrict__ a_Q,
                                                                        const float* __restrict__ a_wp, const float* __restrict__ a_wq,
                                                                        const float* __restrict__ a_sp, const float* __restrict__ a_sq, int a_n, int* a_flags) {
-    sys_proj_body<0>(a_h, a_P, a_Q, a_wp, a_wq, a_sp, a_sq, a_n, a_flags);
+    sys_proj_body<0, NP>(a_h, a_P, a_Q, a_wp, a_wq, a_sp, a_sq, a_n, a_flags);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1291,13 +1334,14 @@ __global__ void __launch_bounds__(SYS_THREADS, 1) sys_proj_kernel(const float* _
 constexpr size_t NODE_PROJ_LDS_BYTES = NODE_LDS_BYTES > PROJ_LDS_BYTES ? NODE_LDS_BYTES : PROJ_LDS_BYTES;
 static_assert(NODE_PROJ_LDS_BYTES <= 160 * 1024, "LDS budget");
 
+template <int NP>
 __global__ void __launch_bounds__(SYS_THREADS, 1) sys_node_proj_kernel(const float* a_h, float* a_h_out, const float* __restrict__ a_agg, float* a_Q, const float* __restrict__ a_hw,
                                                                             float* __restrict__ a_P, const float* __restrict__ a_wp, const float* __restrict__ a_wq,
                                                                             const float* __restrict__ a_sp, const float* __restrict__ a_sq, int a_n, int* a_flags,
                                                                             float a_eps) {
-    sys_node_body(a_h, a_agg, a_Q, a_h_out, a_hw, a_n, a_flags, a_eps);
+    sys_node_body<NP>(a_h, a_agg, a_Q, a_h_out, a_hw, a_n, a_flags, a_eps);
     __builtin_amdgcn_s_setprio(0);   // phase A's roles are gone: twelve equal waves
-    sys_proj_body<LD_SC1>(a_h_out, a_P, a_Q, a_wp, a_wq, a_sp, a_sq, a_n, a_flags);
+    sys_proj_body<LD_SC1, NP>(a_h_out, a_P, a_Q, a_wp, a_wq, a_sp, a_sq, a_n, a_flags);
 }
 
 // agg rows of the nodes whose in-edge segment crosses groups of the scatter-add: + the head partials the later groups hold, in
@@ -1588,25 +1632,38 @@ int launch_edge_sys(const EdgeArgs& a, const EdgeBlocks& t, int64_t edge_capacit
                                                  t.blk, t.seg, t.head, t.hdr, (unsigned)(a.side - a.agg), (unsigned)agg_bytes,
                                                  (unsigned)((uint64_t)a.n_nodes_tab * 2 * H * 4), const_cast<int*>(&a.hdr->error_flags), a.eps, a.residual);
     };
-    if (a.discard_e_out) return stream ? go(kernel_c<sys_edge_kernel<false, true>>{}) : go(kernel_c<sys_edge_kernel<false, false>>{});
-    return stream ? go(kernel_c<sys_edge_kernel<true, true>>{}) : go(kernel_c<sys_edge_kernel<true, false>>{});
+    auto pick = [&](auto np_c) {
+        constexpr int NP = decltype(np_c)::value;
+        if (a.discard_e_out) return stream ? go(kernel_c<sys_edge_kernel<false, true, NP>>{}) : go(kernel_c<sys_edge_kernel<false, false, NP>>{});
+        return stream ? go(kernel_c<sys_edge_kernel<true, true, NP>>{}) : go(kernel_c<sys_edge_kernel<true, false, NP>>{});
+    };
+    return a.precision == kPrecisionF16 ? pick(int_c<NP_F16>{}) : pick(int_c<NP_F32>{});
 }
 
 int launch_edge_sys_enc(const EdgeArgs& a, hipStream_t s) {
     GM_REQUIRE(a.hdr && a.wstream_h3 && a.e_in && a.e_out && !a.eid && !a.eid_out && a.k1 == 4, GM_ERR_INVALID_ARGUMENT,
                "launch_edge_sys_enc: unsupported argument combination");
-    return launch_sys<sys_enc_kernel>(ENC_LDS_BYTES, a.prof, PROF_ENC, s, a.hdr, a.e_in, a.e_out, a.wstream_h3, const_cast<int*>(&a.hdr->error_flags), a.eps,
-                                      a.zero_pad_rows ? 1 : 0);
+    auto go = [&](auto kern) {
+        return launch_sys<decltype(kern)::value>(ENC_LDS_BYTES, a.prof, PROF_ENC, s, a.hdr, a.e_in, a.e_out, a.wstream_h3, const_cast<int*>(&a.hdr->error_flags),
+                                                 a.eps, a.zero_pad_rows ? 1 : 0);
+    };
+    return a.precision == kPrecisionF16 ? go(kernel_c<sys_enc_kernel<NP_F16>>{}) : go(kernel_c<sys_enc_kernel<NP_F32>>{});
 }
 
 int launch_node_sys(const NodeSysArgs& a, hipStream_t s) {
     GM_REQUIRE(a.h && a.agg && a.Q && a.h_out && a.image && a.n > 0, GM_ERR_INVALID_ARGUMENT, "launch_node_sys: bad argument");
-    return launch_sys<sys_node_kernel>(NODE_LDS_BYTES, a.prof, PROF_NODE, s, a.h, a.agg, a.Q, a.h_out, a.image, a.n, a.flags, a.eps);
+    auto go = [&](auto kern) {
+        return launch_sys<decltype(kern)::value>(NODE_LDS_BYTES, a.prof, PROF_NODE, s, a.h, a.agg, a.Q, a.h_out, a.image, a.n, a.flags, a.eps);
+    };
+    return a.precision == kPrecisionF16 ? go(kernel_c<sys_node_kernel<NP_F16>>{}) : go(kernel_c<sys_node_kernel<NP_F32>>{});
 }
 
 int launch_proj_sys(const ProjSysArgs& a, hipStream_t s) {
     GM_REQUIRE(a.h && a.P && a.Q && a.img_p && a.img_q && a.n > 0, GM_ERR_INVALID_ARGUMENT, "launch_proj_sys: bad argument");
-    return launch_sys<sys_proj_kernel>(PROJ_LDS_BYTES, a.prof, PROF_NODE, s, a.h, a.P, a.Q, a.img_p, a.img_q, a.scale_p, a.scale_q, a.n, a.flags);
+    auto go = [&](auto kern) {
+        return launch_sys<decltype(kern)::value>(PROJ_LDS_BYTES, a.prof, PROF_NODE, s, a.h, a.P, a.Q, a.img_p, a.img_q, a.scale_p, a.scale_q, a.n, a.flags);
+    };
+    return a.precision == kPrecisionF16 ? go(kernel_c<sys_proj_kernel<NP_F16>>{}) : go(kernel_c<sys_proj_kernel<NP_F32>>{});
 }
 
 int launch_node_proj_sys(const NodeSysArgs& a, const ProjSysArgs& p, hipStream_t s) {
@@ -1615,8 +1672,12 @@ int launch_node_proj_sys(const NodeSysArgs& a, const ProjSysArgs& p, hipStream_t
     // one workgroup reads back what it wrote, and overwrites the Q rows it has consumed: the two halves must name the same arrays
     GM_REQUIRE(p.h == a.h_out && p.Q == a.Q && p.n == a.n && p.flags == a.flags, GM_ERR_INVALID_ARGUMENT,
                "launch_node_proj_sys: the projection must read the node MLP's h_out and write its Q, over the same rows");
-    return launch_sys<sys_node_proj_kernel>(NODE_PROJ_LDS_BYTES, a.prof, PROF_NODE, s, a.h, a.h_out, a.agg, p.Q, a.image, p.P, p.img_p, p.img_q, p.scale_p,
-                                            p.scale_q, a.n, a.flags, a.eps);
+    GM_REQUIRE(p.precision == a.precision, GM_ERR_INVALID_ARGUMENT, "launch_node_proj_sys: the two halves disagree on the precision");
+    auto go = [&](auto kern) {
+        return launch_sys<decltype(kern)::value>(NODE_PROJ_LDS_BYTES, a.prof, PROF_NODE, s, a.h, a.h_out, a.agg, p.Q, a.image, p.P, p.img_p, p.img_q,
+                                                 p.scale_p, p.scale_q, a.n, a.flags, a.eps);
+    };
+    return a.precision == kPrecisionF16 ? go(kernel_c<sys_node_proj_kernel<NP_F16>>{}) : go(kernel_c<sys_node_proj_kernel<NP_F32>>{});
 }
 
 int launch_agg_stitch(float* agg, const float* side, const EdgeBlocks& t, int64_t n, ProfState* prof_state, hipStream_t s) {

@@ -50,6 +50,8 @@ constexpr float kHmRawInputRms = 32.0f;     // encoders: raw feature rows are sc
 struct HmEdgeArgs {
     const CsrHeader* hdr;
     int n_edges_host;
+    int precision;        // kPrecisionF32 / kPrecisionF16 (mlp.h): read by the launcher, which picks the instantiation (the kernels do not
+                          // read it; it sits in what was alignment padding, so the kernels' argument layout is the one it was)
     const int* dst;
     const int* src;
     const int* eid;       // row of the input for sorted position p, or nullptr
@@ -77,6 +79,7 @@ struct HmEdgeArgs {
 
 struct HmNodeArgs {
     int n_nodes;
+    int precision;        // kPrecisionF32 / kPrecisionF16 (mlp.h): read by the launcher (in what was alignment padding, as in HmEdgeArgs)
     const float* x_in;    // mode 0: [N][k1]; mode 1 / 2: h [N][H]
     int k1;
     const float* agg;

@@ -131,11 +131,12 @@ __device__ __forceinline__ void init_bias_rows(floatx16 (&acc)[RBW], const float
 // its row that sums over it becomes NaN (inf - inf) -- the whole row, all output features.  So one accumulator per row and
 // Linear tells: a comparison per row block instead of a maximum over every value written.  The verdict is wave-uniform and
 // lives in a scalar register.  (A non-finite input of the caller's raises the same flag.)
-template <int RBW>
+// One product (NP = 1, the fp16 mode): the value is a lone +-inf and the row's accumulators are +-inf or NaN -- row_bad<1> takes both.
+template <int NP, int RBW>
 __device__ __forceinline__ void check_rows(int& bad, const floatx16 (&acc)[RBW]) {
     bool nan = false;
 #pragma unroll
-    for (int rb = 0; rb < RBW; ++rb) nan |= acc[rb][0] != acc[rb][0];
+    for (int rb = 0; rb < RBW; ++rb) nan |= row_bad<NP>(acc[rb][0]);
     bad |= __any(nan) ? 1 : 0;
 }
 // Encoder forms (raw feature rows in; the standalone GraphIndependent entry point has no header to flag): a row whose accumulators
@@ -157,12 +158,15 @@ __device__ __forceinline__ void report_range(int bad, int* flags) {
 // nrb: row blocks of this wave that hold rows (the others' MFMAs are skipped: the last tile of a workgroup's range may be partial;
 // a branch-free copy of the loop for full tiles was measured: -4 %, it costs registers the kernels do not have)
 // One k-group: the three partial products of every row block (lo.hi + hi.lo + hi.hi).
-template <int RBW>
+// NP = 1: hi.hi alone (al, bl are never loaded).
+template <int NP, int RBW>
 __device__ __forceinline__ void mfma3(floatx16 (&acc)[RBW], const half8& ah, const half8& al, const half8 (&bh)[RBW], const half8 (&bl)[RBW], int nrb) {
+    if constexpr (NP == 3) {
 #pragma unroll
     for (int rb = 0; rb < RBW; ++rb) if (rb < nrb) acc[rb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh[rb], acc[rb], 0, 0, 0);
 #pragma unroll
     for (int rb = 0; rb < RBW; ++rb) if (rb < nrb) acc[rb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl[rb], acc[rb], 0, 0, 0);
+    }
 #pragma unroll
     for (int rb = 0; rb < RBW; ++rb) if (rb < nrb) acc[rb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh[rb], acc[rb], 0, 0, 0);
 }
@@ -174,32 +178,39 @@ __device__ __forceinline__ void mfma3(floatx16 (&acc)[RBW], const half8& ah, con
 // register pressure the scheduler otherwise sinks every load to its first use.  The weights come from L2 (~1 us under
 // load), so the A fragments run a ring of 4 k-groups: a k-group is requested one and a half trips (36 MFMAs of this wave,
 // as many of the SIMD's other wave) before its use.  The redundant loads of the last trips re-read the last k-group.
-template <int RBW>
+template <int NP, int RBW>
 __device__ __forceinline__ void gemm(floatx16 (&acc)[RBW], const half8* __restrict__ wf, const half8* im, int img_ksn, int nks, int nrb = RBW) {
     const int last = nks - 1;
     half8 bh[RBW], bl[RBW], ch[RBW], cl[RBW];
     auto load_b = [&](half8 (&h)[RBW], half8 (&l)[RBW], int kg) {
 #pragma unroll
-        for (int rb = 0; rb < RBW; ++rb) { h[rb] = im[(rb * img_ksn + kg) * 128]; l[rb] = im[(rb * img_ksn + kg) * 128 + 64]; }
+        for (int rb = 0; rb < RBW; ++rb) {
+            h[rb] = im[(rb * img_ksn + kg) * 128];
+            if constexpr (NP == 3) l[rb] = im[(rb * img_ksn + kg) * 128 + 64];
+        }
+    };
+    // the lo fragment of the weights' k-group kg (NP = 1: not loaded)
+    auto load_al = [&](half8& l, int kg) {
+        if constexpr (NP == 3) l = wf[kg * 128 + 64];
     };
     if (RBW == 1 && nks >= 4 && (nks & 3) == 0) {
         half8 ah[4], al[4];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) { ah[q] = wf[q * 128]; al[q] = wf[q * 128 + 64]; }
+        for (int q = 0; q < 4; ++q) { ah[q] = wf[q * 128]; load_al(al[q], q); }
         load_b(bh, bl, 0);
         load_b(ch, cl, 1);
 #pragma unroll 1
         for (int ks = 0; ks < nks; ks += 4) {
 #pragma unroll
             for (int u = 0; u < 4; u += 2) {
-                mfma3(acc, ah[u], al[u], bh, bl, nrb);
+                mfma3<NP>(acc, ah[u], al[u], bh, bl, nrb);
                 __builtin_amdgcn_sched_barrier(0);
-                { const int ka = min(ks + u + 4, last); ah[u] = wf[ka * 128]; al[u] = wf[ka * 128 + 64]; }
+                { const int ka = min(ks + u + 4, last); ah[u] = wf[ka * 128]; load_al(al[u], ka); }
                 load_b(bh, bl, min(ks + u + 2, last));
                 __builtin_amdgcn_sched_barrier(0);
-                mfma3(acc, ah[u + 1], al[u + 1], ch, cl, nrb);
+                mfma3<NP>(acc, ah[u + 1], al[u + 1], ch, cl, nrb);
                 __builtin_amdgcn_sched_barrier(0);
-                { const int ka = min(ks + u + 5, last); ah[u + 1] = wf[ka * 128]; al[u + 1] = wf[ka * 128 + 64]; }
+                { const int ka = min(ks + u + 5, last); ah[u + 1] = wf[ka * 128]; load_al(al[u + 1], ka); }
                 load_b(ch, cl, min(ks + u + 3, last));
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -207,21 +218,23 @@ __device__ __forceinline__ void gemm(floatx16 (&acc)[RBW], const half8* __restri
         return;
     }
     // short inputs (the encoders' first Linear: 1 or 2 k-groups)
-    half8 ah0 = wf[0], al0 = wf[64];
-    half8 ah1 = wf[min(1, last) * 128], al1 = wf[min(1, last) * 128 + 64];
+    half8 ah0 = wf[0], al0, ah1, al1;
+    load_al(al0, 0);
+    ah1 = wf[min(1, last) * 128];
+    load_al(al1, min(1, last));
     load_b(bh, bl, 0);
     load_b(ch, cl, min(1, last));
 #pragma unroll 1
     for (int ks = 0; ks < nks; ks += 2) {
         const int k2 = min(ks + 2, last), k3 = min(ks + 3, last);
-        mfma3(acc, ah0, al0, bh, bl, nrb);
+        mfma3<NP>(acc, ah0, al0, bh, bl, nrb);
         __builtin_amdgcn_sched_barrier(0);
-        ah0 = wf[k2 * 128]; al0 = wf[k2 * 128 + 64];
+        ah0 = wf[k2 * 128]; load_al(al0, k2);
         load_b(bh, bl, k2);
         __builtin_amdgcn_sched_barrier(0);
-        if (ks + 1 < nks) mfma3(acc, ah1, al1, ch, cl, nrb);   // MFMAs only inside the branch (odd nks: the 16-wide edge features)
+        if (ks + 1 < nks) mfma3<NP>(acc, ah1, al1, ch, cl, nrb);   // MFMAs only inside the branch (odd nks: the 16-wide edge features)
         __builtin_amdgcn_sched_barrier(0);
-        ah1 = wf[k3 * 128]; al1 = wf[k3 * 128 + 64];
+        ah1 = wf[k3 * 128]; load_al(al1, k3);
         load_b(ch, cl, k3);
         __builtin_amdgcn_sched_barrier(0);
     }
@@ -229,7 +242,7 @@ __device__ __forceinline__ void gemm(floatx16 (&acc)[RBW], const half8* __restri
 
 // accumulators -> [ReLU] -> fp16 hi / lo -> the wave's two k-groups of the image of row block rb.  The ReLU form passes the
 // accumulators' scale on (no multiply); the other form (a LayerNorm output entering a tail) writes the values as they are.
-template <bool RELU>
+template <bool RELU, int NP>
 __device__ __forceinline__ void acc_to_img(const floatx16& a, uintx4* img_rb, int jb, int lane) {
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
@@ -237,16 +250,21 @@ __device__ __forceinline__ void acc_to_img(const floatx16& a, uintx4* img_rb, in
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] = RELU ? relu(a[8 * q + j]) : a[8 * q + j];
         uintx2 h0, l0, h1, l1;
-        split4(v[0], v[1], v[2], v[3], h0, l0);
-        split4(v[4], v[5], v[6], v[7], h1, l1);
+        if constexpr (NP == 3) {
+            split4(v[0], v[1], v[2], v[3], h0, l0);
+            split4(v[4], v[5], v[6], v[7], h1, l1);
+        } else {
+            hi4(v[0], v[1], v[2], v[3], h0);
+            hi4(v[4], v[5], v[6], v[7], h1);
+        }
         img_rb[((2 * jb + q) * 2 + 0) * 64 + lane] = uintx4{h0[0], h0[1], h1[0], h1[1]};
-        img_rb[((2 * jb + q) * 2 + 1) * 64 + lane] = uintx4{l0[0], l0[1], l1[0], l1[1]};
+        if constexpr (NP == 3) img_rb[((2 * jb + q) * 2 + 1) * 64 + lane] = uintx4{l0[0], l0[1], l1[0], l1[1]};
     }
 }
 
 // rows of H floats -> image (k-group count KS).  16 RBW units of (16 rows, 2 k-groups) per tile, 2 RBW per wave; lane = (row, k-group
 // parity, kg) reads the two 16-byte pieces that make its 8 K slots.  row_of(rbg, n) returns the source row (or -1: zeros).
-template <int H, int RBW, int UNR, class R, class Z>
+template <int H, int RBW, int UNR, int NP, class R, class Z>
 __device__ __forceinline__ void rows_to_image(const float* __restrict__ src, uintx4* img, int wave, int lane, R&& row_of, Z&& adjust) {
     using C = Cfg<H, RBW>;
 #pragma unroll UNR
@@ -260,10 +278,15 @@ __device__ __forceinline__ void rows_to_image(const float* __restrict__ src, uin
         floatx4 v1 = *reinterpret_cast<const floatx4*>(p + 8);
         adjust(row, 16 * ks + 4 * kg, v0, v1);
         uintx2 h0, l0, h1, l1;
-        split4(v0[0], v0[1], v0[2], v0[3], h0, l0);
-        split4(v1[0], v1[1], v1[2], v1[3], h1, l1);
+        if constexpr (NP == 3) {
+            split4(v0[0], v0[1], v0[2], v0[3], h0, l0);
+            split4(v1[0], v1[1], v1[2], v1[3], h1, l1);
+        } else {
+            hi4(v0[0], v0[1], v0[2], v0[3], h0);
+            hi4(v1[0], v1[1], v1[2], v1[3], h1);
+        }
         img[((rbg * C::KS + ks) * 2 + 0) * 64 + nn + 32 * kg] = uintx4{h0[0], h0[1], h1[0], h1[1]};
-        img[((rbg * C::KS + ks) * 2 + 1) * 64 + nn + 32 * kg] = uintx4{l0[0], l0[1], l1[0], l1[1]};
+        if constexpr (NP == 3) img[((rbg * C::KS + ks) * 2 + 1) * 64 + nn + 32 * kg] = uintx4{l0[0], l0[1], l1[0], l1[1]};
     }
 }
 
@@ -273,7 +296,7 @@ __device__ __forceinline__ void rows_to_image(const float* __restrict__ src, uin
 // a cache hit, and drop it); then the pieces are combined, in group order, and split into the image.  `more` (the next
 // group holds a partial of the same row too: in-degree beyond a group's 128 edges) takes the loop.
 // (The first form waited for a stitch[] and a head[] look-up per piece, two pieces at a time: a third of the tile's time.)
-template <int H, int RBW, class R>
+template <int H, int RBW, int NP, class R>
 __device__ __forceinline__ void agg_rows_to_image(const float* __restrict__ agg, uintx4* img, int wave, int lane, R&& row_of, const int* SC,
                                                   const float* __restrict__ side, const int* __restrict__ head, int ng) {
     using C = Cfg<H, RBW>;
@@ -328,10 +351,15 @@ __device__ __forceinline__ void agg_rows_to_image(const float* __restrict__ agg,
                 }
             }
             uintx2 h0, l0, h1, l1;
-            split4(v0[q][0], v0[q][1], v0[q][2], v0[q][3], h0, l0);
-            split4(v1[q][0], v1[q][1], v1[q][2], v1[q][3], h1, l1);
+            if constexpr (NP == 3) {
+                split4(v0[q][0], v0[q][1], v0[q][2], v0[q][3], h0, l0);
+                split4(v1[q][0], v1[q][1], v1[q][2], v1[q][3], h1, l1);
+            } else {
+                hi4(v0[q][0], v0[q][1], v0[q][2], v0[q][3], h0);
+                hi4(v1[q][0], v1[q][1], v1[q][2], v1[q][3], h1);
+            }
             img[((rbg * C::KS + ks) * 2 + 0) * 64 + nn + 32 * kg] = uintx4{h0[0], h0[1], h1[0], h1[1]};
-            img[((rbg * C::KS + ks) * 2 + 1) * 64 + nn + 32 * kg] = uintx4{l0[0], l0[1], l1[0], l1[1]};
+            if constexpr (NP == 3) img[((rbg * C::KS + ks) * 2 + 1) * 64 + nn + 32 * kg] = uintx4{l0[0], l0[1], l1[0], l1[1]};
         }
     }
 }
@@ -339,7 +367,7 @@ __device__ __forceinline__ void agg_rows_to_image(const float* __restrict__ agg,
 // rows of k1 <= 16 KSN raw features -> image with KSN k-groups (zero-padded), every row scaled by its own power of two so that
 // its largest magnitude lands in [2^6, 2^7), but by no more than `cap` (pack_hm_kernel: what keeps the bias in range; an
 // all-zero row takes the cap).  RS[rbg * 32 + n] receives the scale.
-template <int H, int RBW, int KSN, class R>
+template <int H, int RBW, int KSN, int NP, class R>
 __device__ __forceinline__ void narrow_rows_to_image(const float* __restrict__ src, int k1, uintx4* img, float* RS, float cap, int tid, R&& row_of) {
     using C = Cfg<H, RBW>;
     for (int i = tid; i < C::NRB * KSN * 64; i += HM_THREADS) {
@@ -362,10 +390,15 @@ __device__ __forceinline__ void narrow_rows_to_image(const float* __restrict__ s
             v[j] = f < k1 ? p[f] * sc : 0.f;
         }
         uintx2 h0, l0, h1, l1;
-        split4(v[0], v[1], v[2], v[3], h0, l0);
-        split4(v[4], v[5], v[6], v[7], h1, l1);
+        if constexpr (NP == 3) {
+            split4(v[0], v[1], v[2], v[3], h0, l0);
+            split4(v[4], v[5], v[6], v[7], h1, l1);
+        } else {
+            hi4(v[0], v[1], v[2], v[3], h0);
+            hi4(v[4], v[5], v[6], v[7], h1);
+        }
         img[((rbg * KSN + ks) * 2 + 0) * 64 + l] = uintx4{h0[0], h0[1], h1[0], h1[1]};
-        img[((rbg * KSN + ks) * 2 + 1) * 64 + l] = uintx4{l0[0], l0[1], l1[0], l1[1]};
+        if constexpr (NP == 3) img[((rbg * KSN + ks) * 2 + 1) * 64 + l] = uintx4{l0[0], l0[1], l1[0], l1[1]};
     }
 }
 
@@ -407,7 +440,7 @@ __device__ __forceinline__ void ln_merge(const float* ST, int rbg, int n, float 
 // ------------------------------------------------------------------------------------------
 // edge kernel
 // ------------------------------------------------------------------------------------------
-template <int H, bool ENC>
+template <int H, bool ENC, int NP>
 __global__ void __launch_bounds__(HM_THREADS, 1) hm_edge_kernel(HmEdgeArgs A) {
     using C = Cfg<H>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -458,8 +491,8 @@ __global__ void __launch_bounds__(HM_THREADS, 1) hm_edge_kernel(HmEdgeArgs A) {
             const int p = pos_of(rbg, nn);
             return A.eid ? A.eid[p] : p;
         };
-        if (ENC) narrow_rows_to_image<H, 4, 1>(A.e_in, A.k1, img, RS, A.w[3], tid, in_row);
-        else rows_to_image<H, 4, 8>(A.e_in, img, wave, lane, in_row, [](long long, int, floatx4&, floatx4&) {});
+        if (ENC) narrow_rows_to_image<H, 4, 1, NP>(A.e_in, A.k1, img, RS, A.w[3], tid, in_row);
+        else rows_to_image<H, 4, 8, NP>(A.e_in, img, wave, lane, in_row, [](long long, int, floatx4&, floatx4&) {});
         __syncthreads();
         HM_STAMP_E(iter, 1);   // e rows in the image
 
@@ -494,8 +527,8 @@ __global__ void __launch_bounds__(HM_THREADS, 1) hm_edge_kernel(HmEdgeArgs A) {
             }
         }
         HM_STAMP_E(iter, 2);   // P gather issued (accumulators initialised: waits land in the GEMM)
-        gemm(acc, L.frag + (size_t)jb * KS0 * 128 + lane, imgh + (size_t)(4 * rg) * KS0 * 128 + lane, KS0, KS0);
-        check_rows(rng, acc);
+        gemm<NP>(acc, L.frag + (size_t)jb * KS0 * 128 + lane, imgh + (size_t)(4 * rg) * KS0 * 128 + lane, KS0, KS0);
+        check_rows<NP>(rng, acc);
         float pois[4] = {0.f, 0.f, 0.f, 0.f};
         if (ENC) mark_rows(pois, acc);
         wp += lin0;
@@ -504,13 +537,13 @@ __global__ void __launch_bounds__(HM_THREADS, 1) hm_edge_kernel(HmEdgeArgs A) {
         for (int l = 1; l <= A.nl; ++l) {
             __syncthreads();
 #pragma unroll
-            for (int rb = 0; rb < 4; ++rb) acc_to_img<true>(acc[rb], img + (size_t)(4 * rg + rb) * C::KS * 128, jb, lane);
+            for (int rb = 0; rb < 4; ++rb) acc_to_img<true, NP>(acc[rb], img + (size_t)(4 * rg + rb) * C::KS * 128, jb, lane);
             __syncthreads();
             L = lin_at(wp, H);
             if (ENC) init_bias_rows(acc, L.bias, jb, hi, rs);
             else init_bias(acc, L.bias, jb, hi);
-            gemm(acc, L.frag + (size_t)jb * C::KS * 128 + lane, imgh + (size_t)(4 * rg) * C::KS * 128 + lane, C::KS, C::KS);
-            check_rows(rng, acc);
+            gemm<NP>(acc, L.frag + (size_t)jb * C::KS * 128 + lane, imgh + (size_t)(4 * rg) * C::KS * 128 + lane, C::KS, C::KS);
+            check_rows<NP>(rng, acc);
             if (ENC) mark_rows(pois, acc);
             wp += linh;
         }
@@ -647,7 +680,7 @@ __global__ void __launch_bounds__(HM_THREADS, 1) hm_edge_kernel(HmEdgeArgs A) {
 // ------------------------------------------------------------------------------------------
 // node kernel
 // ------------------------------------------------------------------------------------------
-template <int H, int MODE, int RBW>
+template <int H, int MODE, int RBW, int NP>
 __global__ void __launch_bounds__(HM_THREADS, 1) hm_node_kernel(HmNodeArgs A) {
     using C = Cfg<H, RBW>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -711,8 +744,8 @@ __global__ void __launch_bounds__(HM_THREADS, 1) hm_node_kernel(HmNodeArgs A) {
         float rs[RBW], pois[RBW];   // pois: MODE 0 only (mark_rows)
 #pragma unroll
         for (int rb = 0; rb < RBW; ++rb) { rs[rb] = 1.f; pois[rb] = 0.f; }
-        if (MODE == 0) narrow_rows_to_image<H, RBW, 2>(A.x_in, A.k1, img, RS, A.w[3], tid, row_of);
-        else rows_to_image<H, RBW, 2 * RBW>(A.x_in, img, wave, lane, row_of, [](long long, int, floatx4&, floatx4&) {});
+        if (MODE == 0) narrow_rows_to_image<H, RBW, 2, NP>(A.x_in, A.k1, img, RS, A.w[3], tid, row_of);
+        else rows_to_image<H, RBW, 2 * RBW, NP>(A.x_in, img, wave, lane, row_of, [](long long, int, floatx4&, floatx4&) {});
         __syncthreads();
         HM_STAMP(tile_i, 1);   // h rows in the image
         if (MODE != 2) {
@@ -726,8 +759,8 @@ __global__ void __launch_bounds__(HM_THREADS, 1) hm_node_kernel(HmNodeArgs A) {
                 init_bias(acc, L.bias, jb, hi);
             }
             if (MODE == 0) {
-                gemm(acc, L.frag + (size_t)jb * 2 * 128 + lane, imgh + (size_t)(RBW * rg) * 2 * 128 + lane, 2, 2, nrb);
-                check_rows(rng, acc);
+                gemm<NP>(acc, L.frag + (size_t)jb * 2 * 128 + lane, imgh + (size_t)(RBW * rg) * 2 * 128 + lane, 2, 2, nrb);
+                check_rows<NP>(rng, acc);
                 mark_rows(pois, acc);
             } else {
                 int sc_head = -2;
@@ -737,17 +770,17 @@ __global__ void __launch_bounds__(HM_THREADS, 1) hm_node_kernel(HmNodeArgs A) {
                     sc_head = A.head[sc_c];
                     if (sc_c + 1 < ng) sc_head1 = A.head[sc_c + 1];
                 }
-                gemm(acc, L.frag + (size_t)jb * 2 * C::KS * 128 + lane, imgh + (size_t)(RBW * rg) * C::KS * 128 + lane, C::KS, C::KS, nrb);
-                check_rows(rng, acc);
+                gemm<NP>(acc, L.frag + (size_t)jb * 2 * C::KS * 128 + lane, imgh + (size_t)(RBW * rg) * C::KS * 128 + lane, C::KS, C::KS, nrb);
+                check_rows<NP>(rng, acc);
                 if (stitched && tid < C::NRB * 32) SC[tid] = sc_head == sc_row ? 2 * sc_c + (sc_head1 == sc_row ? 1 : 0) : -1;
                 __syncthreads();
                 HM_STAMP(tile_i, 2);   // GEMM 1a (h part)
                 // agg row + the head partials other groups hold of its segment, in group order (hedge.h)
-                agg_rows_to_image<H, RBW>(A.agg, img, wave, lane, row_of, stitched ? SC : nullptr, A.side, A.head, ng);
+                agg_rows_to_image<H, RBW, NP>(A.agg, img, wave, lane, row_of, stitched ? SC : nullptr, A.side, A.head, ng);
                 __syncthreads();
                 HM_STAMP(tile_i, 3);   // agg rows (+ head partials) in the image
-                gemm(acc, L.frag + ((size_t)jb * 2 * C::KS + C::KS) * 128 + lane, imgh + (size_t)(RBW * rg) * C::KS * 128 + lane, C::KS, C::KS, nrb);
-                check_rows(rng, acc);
+                gemm<NP>(acc, L.frag + ((size_t)jb * 2 * C::KS + C::KS) * 128 + lane, imgh + (size_t)(RBW * rg) * C::KS * 128 + lane, C::KS, C::KS, nrb);
+                check_rows<NP>(rng, acc);
             }
             wp += lin0;
             HM_STAMP(tile_i, 4);   // GEMM 1b (agg part)
@@ -755,13 +788,13 @@ __global__ void __launch_bounds__(HM_THREADS, 1) hm_node_kernel(HmNodeArgs A) {
             for (int l = 1; l <= A.nl; ++l) {
                 __syncthreads();
 #pragma unroll
-                for (int rb = 0; rb < RBW; ++rb) if (rb < nrb) acc_to_img<true>(acc[rb], img + (size_t)(RBW * rg + rb) * C::KS * 128, jb, lane);
+                for (int rb = 0; rb < RBW; ++rb) if (rb < nrb) acc_to_img<true, NP>(acc[rb], img + (size_t)(RBW * rg + rb) * C::KS * 128, jb, lane);
                 __syncthreads();
                 L = lin_at(wp, H);
                 if (MODE == 0) init_bias_rows(acc, L.bias, jb, hi, rs);
                 else init_bias(acc, L.bias, jb, hi);
-                gemm(acc, L.frag + (size_t)jb * C::KS * 128 + lane, imgh + (size_t)(RBW * rg) * C::KS * 128 + lane, C::KS, C::KS, nrb);
-                check_rows(rng, acc);
+                gemm<NP>(acc, L.frag + (size_t)jb * C::KS * 128 + lane, imgh + (size_t)(RBW * rg) * C::KS * 128 + lane, C::KS, C::KS, nrb);
+                check_rows<NP>(rng, acc);
                 if (MODE == 0) mark_rows(pois, acc);
                 wp += linh;
             }
@@ -801,7 +834,7 @@ __global__ void __launch_bounds__(HM_THREADS, 1) hm_node_kernel(HmNodeArgs A) {
             if (A.tail == 0) continue;
             // the new h becomes the tail's input image (every wave has passed the barrier after the last Linear)
 #pragma unroll
-            for (int rb = 0; rb < RBW; ++rb) if (rb < nrb) acc_to_img<false>(acc[rb], img + (size_t)(RBW * rg + rb) * C::KS * 128, jb, lane);
+            for (int rb = 0; rb < RBW; ++rb) if (rb < nrb) acc_to_img<false, NP>(acc[rb], img + (size_t)(RBW * rg + rb) * C::KS * 128, jb, lane);
             __syncthreads();
             HM_STAMP(tile_i, 8);   // h in the image
         }
@@ -814,8 +847,8 @@ __global__ void __launch_bounds__(HM_THREADS, 1) hm_node_kernel(HmNodeArgs A) {
             for (int half = 0; half < 2; ++half) {
                 const int jbv = jb + half * C::NJB;
                 init_bias(acc, LP.bias, jbv, hi);
-                gemm(acc, LP.frag + (size_t)jbv * C::KS * 128 + lane, imgh + (size_t)(RBW * rg) * C::KS * 128 + lane, C::KS, C::KS, nrb);
-                check_rows(rng, acc);
+                gemm<NP>(acc, LP.frag + (size_t)jbv * C::KS * 128 + lane, imgh + (size_t)(RBW * rg) * C::KS * 128 + lane, C::KS, C::KS, nrb);
+                check_rows<NP>(rng, acc);
 #pragma unroll
                 for (int rb = 0; rb < RBW; ++rb) {
                     const int r = slot_row0(RBW * rg + rb) + n;
@@ -838,19 +871,19 @@ __global__ void __launch_bounds__(HM_THREADS, 1) hm_node_kernel(HmNodeArgs A) {
             for (int l = 0; l < A.nl; ++l) {
                 const Lin LD = lin_at(wp, H);
                 init_bias(acc, LD.bias, jb, hi);
-                gemm(acc, LD.frag + (size_t)jb * C::KS * 128 + lane, imgh + (size_t)(RBW * rg) * C::KS * 128 + lane, C::KS, C::KS, nrb);
-                check_rows(rng, acc);
+                gemm<NP>(acc, LD.frag + (size_t)jb * C::KS * 128 + lane, imgh + (size_t)(RBW * rg) * C::KS * 128 + lane, C::KS, C::KS, nrb);
+                check_rows<NP>(rng, acc);
                 __syncthreads();
 #pragma unroll
-                for (int rb = 0; rb < RBW; ++rb) if (rb < nrb) acc_to_img<true>(acc[rb], img + (size_t)(RBW * rg + rb) * C::KS * 128, jb, lane);
+                for (int rb = 0; rb < RBW; ++rb) if (rb < nrb) acc_to_img<true, NP>(acc[rb], img + (size_t)(RBW * rg + rb) * C::KS * 128, jb, lane);
                 __syncthreads();
                 wp += linh;
             }
             if (jb == 0) {
                 const Lin LO = lin_at(wp, 32);
                 init_bias(acc, LO.bias, 0, hi);
-                gemm(acc, LO.frag + lane, imgh + (size_t)(RBW * rg) * C::KS * 128 + lane, C::KS, C::KS, nrb);
-                check_rows(rng, acc);
+                gemm<NP>(acc, LO.frag + lane, imgh + (size_t)(RBW * rg) * C::KS * 128 + lane, C::KS, C::KS, nrb);
+                check_rows<NP>(rng, acc);
                 if (hi == 0) {
 #pragma unroll
                     for (int rb = 0; rb < RBW; ++rb) {
@@ -1031,29 +1064,34 @@ int set_lds_attr(K kernel, size_t bytes = HM_LDS_BYTES) {
     return GM_OK;
 }
 
-template <int H>
-int launch_edge_h(bool enc, const HmEdgeArgs& a, hipStream_t s) {
+// NP: partial products per multiply (hmma_dev.h), chosen by the model's precision (HmEdgeArgs / HmNodeArgs::precision)
+template <int H, int NP>
+int launch_edge_hp(bool enc, const HmEdgeArgs& a, hipStream_t s) {
     static PerDeviceOnce once;
     const int rc_attr = once.run([]() -> int {
-        int rc = set_lds_attr(hm_edge_kernel<H, true>);
-        if (rc == GM_OK) rc = set_lds_attr(hm_edge_kernel<H, false>);
+        int rc = set_lds_attr(hm_edge_kernel<H, true, NP>);
+        if (rc == GM_OK) rc = set_lds_attr(hm_edge_kernel<H, false, NP>);
         return rc;
     });
     if (rc_attr != GM_OK) return rc_attr;
     ProfScope prof(a.prof, enc ? PROF_ENC : PROF_EDGE, s);
-    if (enc) hipLaunchKernelGGL((hm_edge_kernel<H, true>), dim3(device_cus()), dim3(HM_THREADS), HM_LDS_BYTES, s, a);
-    else hipLaunchKernelGGL((hm_edge_kernel<H, false>), dim3(device_cus()), dim3(HM_THREADS), HM_LDS_BYTES, s, a);
+    if (enc) hipLaunchKernelGGL((hm_edge_kernel<H, true, NP>), dim3(device_cus()), dim3(HM_THREADS), HM_LDS_BYTES, s, a);
+    else hipLaunchKernelGGL((hm_edge_kernel<H, false, NP>), dim3(device_cus()), dim3(HM_THREADS), HM_LDS_BYTES, s, a);
     return GM_OK;
 }
+template <int H>
+int launch_edge_h(bool enc, const HmEdgeArgs& a, hipStream_t s) {
+    return a.precision == kPrecisionF16 ? launch_edge_hp<H, NP_F16>(enc, a, s) : launch_edge_hp<H, NP_F32>(enc, a, s);
+}
 
-template <int H, int RBW>
+template <int H, int RBW, int NP>
 int launch_node_hr(int mode, const HmNodeArgs& a, hipStream_t s) {
     constexpr size_t LDS = hm_node_lds_bytes(RBW);
     static PerDeviceOnce once;
     const int rc_attr = once.run([]() -> int {
-        int rc = set_lds_attr(hm_node_kernel<H, 0, RBW>, LDS);
-        if (rc == GM_OK) rc = set_lds_attr(hm_node_kernel<H, 1, RBW>, LDS);
-        if (rc == GM_OK) rc = set_lds_attr(hm_node_kernel<H, 2, RBW>, LDS);
+        int rc = set_lds_attr(hm_node_kernel<H, 0, RBW, NP>, LDS);
+        if (rc == GM_OK) rc = set_lds_attr(hm_node_kernel<H, 1, RBW, NP>, LDS);
+        if (rc == GM_OK) rc = set_lds_attr(hm_node_kernel<H, 2, RBW, NP>, LDS);
         return rc;
     });
     if (rc_attr != GM_OK) return rc_attr;
@@ -1061,9 +1099,9 @@ int launch_node_hr(int mode, const HmNodeArgs& a, hipStream_t s) {
     int grid = device_cus();
     if (tiles < grid) grid = tiles < 1 ? 1 : tiles;
     ProfScope prof(a.prof, mode == 0 ? PROF_ENC : PROF_NODE, s);
-    if (mode == 0) hipLaunchKernelGGL((hm_node_kernel<H, 0, RBW>), dim3(grid), dim3(HM_THREADS), LDS, s, a);
-    else if (mode == 1) hipLaunchKernelGGL((hm_node_kernel<H, 1, RBW>), dim3(grid), dim3(HM_THREADS), LDS, s, a);
-    else hipLaunchKernelGGL((hm_node_kernel<H, 2, RBW>), dim3(grid), dim3(HM_THREADS), LDS, s, a);
+    if (mode == 0) hipLaunchKernelGGL((hm_node_kernel<H, 0, RBW, NP>), dim3(grid), dim3(HM_THREADS), LDS, s, a);
+    else if (mode == 1) hipLaunchKernelGGL((hm_node_kernel<H, 1, RBW, NP>), dim3(grid), dim3(HM_THREADS), LDS, s, a);
+    else hipLaunchKernelGGL((hm_node_kernel<H, 2, RBW, NP>), dim3(grid), dim3(HM_THREADS), LDS, s, a);
     return GM_OK;
 }
 // small graphs: one 32-row block per wave, so that the tiles cover the CUs.  The 4-block form is used once its tiles fill the
@@ -1076,8 +1114,10 @@ int launch_node_hr(int mode, const HmNodeArgs& a, hipStream_t s) {
 template <int H>
 int launch_node_h(int mode, const HmNodeArgs& a, hipStream_t s) {
     constexpr int small_blocks = H == 128 ? 4 : Cfg<H, 4>::NRB;   // 32-row blocks per workgroup below which the one-block form runs
-    if (cdiv(a.n_nodes, 32) < (int64_t)small_blocks * device_cus()) return launch_node_hr<H, 1>(mode, a, s);
-    return launch_node_hr<H, 4>(mode, a, s);
+    const bool f16 = a.precision == kPrecisionF16;
+    if (cdiv(a.n_nodes, 32) < (int64_t)small_blocks * device_cus())
+        return f16 ? launch_node_hr<H, 1, NP_F16>(mode, a, s) : launch_node_hr<H, 1, NP_F32>(mode, a, s);
+    return f16 ? launch_node_hr<H, 4, NP_F16>(mode, a, s) : launch_node_hr<H, 4, NP_F32>(mode, a, s);
 }
 
 }  // namespace

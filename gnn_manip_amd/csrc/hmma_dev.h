@@ -62,6 +62,27 @@ __device__ __forceinline__ void split4(float a, float b, float c, float d, uintx
     lo[1] = lo_pair(hi[1], c, d);
 }
 
+// Partial products per multiply, a compile-time parameter NP of every inference kernel: 3 is the scheme above; 1 is the fp16 mode
+// (gm_model_set_precision): hi * hi alone, fp32 accumulation -- every Linear multiplies its weights and its inputs rounded to fp16
+// (round to nearest even: cvt_pk), everything else stays fp32.  The one-product instantiations read and write the hi halves of the
+// same weight and operand images and leave the lo halves alone: no low-part splits, image stores or fragment loads.
+constexpr int NP_F32 = 3, NP_F16 = 1;
+
+// the hi parts alone (NP = 1)
+__device__ __forceinline__ void hi4(float a, float b, float c, float d, uintx2& hi) {
+    hi[0] = cvt_pk(a, b);
+    hi[1] = cvt_pk(c, d);
+}
+
+// Row check of a Linear's accumulators (one value per row tells, hmlp.hip: check_rows).  Three products: a value beyond the fp16
+// range is (inf, -inf) as a pair and its row's accumulators are NaN.  One product: it is a lone +-inf, and the row's accumulators are
+// +-inf or NaN (inf * 0, inf - inf) -- anything that is not finite counts.
+template <int NP>
+__device__ __forceinline__ bool row_bad(float a) {
+    if constexpr (NP == 3) return a != a;
+    else return !(__builtin_fabsf(a) <= 3.4028235e38f);
+}
+
 // x += lanes(x shifted) * f.  The value is produced by compiler code just before: the VALU -> DPP hazard (2 wait states) of
 // the first reader is padded by hand, hipcc pads nothing inside asm.
 #define DPP_FMAC(x, f, ctrl) asm volatile("v_fmac_f32_dpp %0, %0, %1 " ctrl : "+v"(x) : "v"(f))

@@ -4,6 +4,11 @@
 
 namespace gm {
 
+// gm_model_set_precision (ABI values): how the inference kernels form a Linear's products on the fp16 matrix pipe (hmma_dev.h).
+// Every launcher picks its kernel's instantiation from the `precision` of its argument block; nothing else depends on it.
+constexpr int kPrecisionF32 = 0;   // three partial products per multiply: fp32 accuracy
+constexpr int kPrecisionF16 = 1;   // one: weights and inputs of every Linear rounded to fp16, fp32 accumulation
+
 // What the edge kernels read: launch_edge_sys / launch_edge_sys_enc (hedge.h) take it as is, the streamed path copies it into an
 // HmEdgeArgs (hmlp.h).
 struct EdgeArgs {
@@ -32,6 +37,7 @@ struct EdgeArgs {
     int k1;                // encoder: edge_dim
     int h_valid;           // the model's hidden_size (<= the width H the kernel runs at; LayerNorm statistics are over these features)
     int zero_pad_rows;     // systolic encoder: e_out is a forward's latent array -- keep kEdgePadRows zero rows behind row n_edges (hedge.h)
+    int precision;         // kPrecisionF32 / kPrecisionF16 (the model's)
 };
 
 struct VecJob {

@@ -40,6 +40,7 @@ int launch_edge(int H, int NL, bool enc, bool sys, const EdgeArgs& a, int64_t ed
     h.P = a.P; h.e_in = a.e_in; h.e_out = a.e_out; h.agg = a.agg; h.w = a.wstream_hm; h.ln_g = a.ln_g; h.ln_b = a.ln_b;
     h.eps = a.eps; h.residual = a.residual; h.discard_e_out = a.discard_e_out; h.k1 = a.k1; h.nl = NL; h.prof = a.prof;
     h.h_valid = a.h_valid;
+    h.precision = a.precision;
     h.flags = a.hdr ? const_cast<int*>(&a.hdr->error_flags) : nullptr;
     if (!enc) {
         const EdgeBlocks t = carve_edge_blocks(const_cast<int*>(a.edge_blocks), a.n_nodes_tab, edge_capacity);

@@ -68,6 +68,7 @@ struct gm_model {
     gm::ProfState* prof = nullptr;  // gm_model_profile
     int edge_kernel = gm::EK_AUTO;   // gm_model_set_edge_kernel: which kernels the forwards of this model may take (gm::EdgeKernel)
     bool node_fusion = true;         // gm_model_set_node_fusion: the systolic node path runs a step's node MLP and projections as one launch
+    int precision = gm::kPrecisionF32;   // gm_model_set_precision: partial products of the inference kernels (training never reads it)
     // Every copy / pack of the weights is queued on the stream of the call that triggered it; `ready` is recorded behind the last
     // one.  An entry point that runs on ANOTHER stream waits for it there (weights_ready_on), so a model may be loaded on one
     // stream and used on others.  (The other direction -- a weight update while a forward on another stream still reads the old

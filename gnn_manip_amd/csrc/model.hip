@@ -433,6 +433,7 @@ EdgeArgs enc_edge_args(const gm_model* m, const float* edge_attr, const int* eid
     a.wstream_hm = m->packed_hm + m->hm_enc_edge;
     a.wstream_h3 = m->packed_h3 ? m->packed_h3 + m->h3_enc : nullptr;
     a.prof = m->prof;
+    a.precision = m->precision;
     set_ln(m, a, m->v_enc_edge);
     a.h_valid = m->H;
     return a;
@@ -447,6 +448,7 @@ EdgeArgs proc_edge_args(const gm_model* m, int k, const CsrWs& c, int64_t n, con
     a.edge_blocks = c.blocks;
     a.n_nodes_tab = n;
     a.prof = m->prof;
+    a.precision = m->precision;
     set_ln(m, a, m->v_edge[k]);
     a.h_valid = m->H;
     return a;
@@ -456,6 +458,7 @@ EdgeArgs proc_edge_args(const gm_model* m, int k, const CsrWs& c, int64_t n, con
 HmNodeArgs node_args(const gm_model* m, int64_t n, const float* x_in, int* flags) {
     HmNodeArgs a{};
     a.n_nodes = (int)n; a.x_in = x_in; a.nl = m->NL; a.h_valid = m->H; a.flags = flags; a.prof = m->prof;
+    a.precision = m->precision;
     return a;
 }
 HmNodeArgs enc_node_args(const gm_model* m, int64_t n, const float* x, float* h_out, int* flags) {
@@ -531,6 +534,7 @@ int epd_forward_impl(const gm_model* m, const float* nodes, int64_t n, const flo
     auto proj_args = [&](int k) {   // h -> P of edge step k, Q of node step k
         ProjSysArgs pa{};
         pa.h = f.h; pa.P = f.P; pa.Q = f.Q; pa.n = (int)n; pa.flags = flags; pa.prof = m->prof;
+        pa.precision = m->precision;
         pa.img_p = m->packed_hm + (k == 0 ? m->hm_enc_node_tail : m->hm_node_tail[k - 1]);
         pa.img_q = m->packed_hm + m->hm_node_q[k];
         pa.scale_p = edge_sys_p_scale(m->packed_h3 + m->h3_edge[k]);
@@ -562,6 +566,7 @@ int epd_forward_impl(const gm_model* m, const float* nodes, int64_t n, const flo
             NodeSysArgs ns{};
             ns.h = f.h; ns.agg = f.agg; ns.Q = f.Q; ns.h_out = f.h; ns.image = m->packed_h3 + m->h3_node[k];
             ns.n = (int)n; ns.flags = flags; ns.eps = m->d.ln_eps; ns.prof = m->prof;
+            ns.precision = m->precision;
             const bool fused = k + 1 < M && m->node_fusion;
             if (rc == GM_OK) rc = fused ? launch_node_proj_sys(ns, proj_args(k + 1), s) : launch_node_sys(ns, s);
             if (rc == GM_OK && k + 1 < M && !fused) rc = launch_proj_sys(proj_args(k + 1), s);
@@ -690,6 +695,14 @@ int gm_model_set_edge_kernel(gm_model* m, int choice) {
 int gm_model_set_node_fusion(gm_model* m, int on) {
     GM_REQUIRE(m, GM_ERR_INVALID_ARGUMENT, "gm_model_set_node_fusion: null model");
     m->node_fusion = on != 0;
+    return GM_OK;
+}
+
+int gm_model_set_precision(gm_model* m, int precision) {
+    GM_REQUIRE(m, GM_ERR_INVALID_ARGUMENT, "gm_model_set_precision: null model");
+    GM_REQUIRE(precision == GM_PRECISION_F32 || precision == GM_PRECISION_F16, GM_ERR_INVALID_ARGUMENT,
+               "gm_model_set_precision: precision %d (GM_PRECISION_F32 = 0, GM_PRECISION_F16 = 1)", precision);
+    m->precision = precision;
     return GM_OK;
 }
 

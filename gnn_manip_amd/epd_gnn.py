@@ -25,6 +25,17 @@ from .graph import _need_cuda, _ws
 
 
 FLOWS = {"source_to_target": 0, "target_to_source": 1}
+PRECISIONS = {"f32": 0, "f16": 1}   # GM_PRECISION_F32 / GM_PRECISION_F16 (include/gnn_manip_hip.h)
+
+
+def _precision_code(name):
+    if name not in PRECISIONS:
+        raise ValueError(f"precision must be one of {sorted(PRECISIONS)}, not {name!r}")
+    return PRECISIONS[name]
+
+
+def _precision_name(code):
+    return next(k for k, v in PRECISIONS.items() if v == code)
 
 
 def _convention(flow, concat, node_concat):
@@ -75,6 +86,7 @@ class _Handle:
         self.desc = None
         self.edge_kernel = 0
         self.node_fusion = 1
+        self.precision = 0
         self.prof_mask = 0
 
     def get(self, desc_tuple, params, device, key_params=None):
@@ -99,6 +111,8 @@ class _Handle:
                 check(L.gm_model_set_edge_kernel(self.h, self.edge_kernel))
             if not self.node_fusion:
                 check(L.gm_model_set_node_fusion(self.h, 0))
+            if self.precision:
+                check(L.gm_model_set_precision(self.h, self.precision))
             if self.prof_mask:
                 check(L.gm_model_profile(self.h, self.prof_mask))
         # no synchronisation: the pack kernels are queued on torch's current stream, and the caching allocator hands the
@@ -117,6 +131,11 @@ class _Handle:
         self.node_fusion = int(bool(on))
         if self.h is not None:
             check(lib().gm_model_set_node_fusion(self.h, self.node_fusion))
+
+    def set_precision(self, code):
+        self.precision = int(code)
+        if self.h is not None:
+            check(lib().gm_model_set_precision(self.h, self.precision))
 
     def profile(self, kind_mask):
         self.prof_mask = int(kind_mask)
@@ -342,6 +361,16 @@ class GraphIndependent(nn.Module):
         params = _mlp_params(self.phi_edge) + _mlp_params(self.phi_node) + self._pad[str(device)]
         return desc, params
 
+    def set_precision(self, precision):
+        """Arithmetic of this block's stand-alone inference forward: 'f32' (the default, float32 accuracy) or 'f16' (weights and
+        inputs of every Linear rounded to fp16, float32 accumulation; see ``EncProcDecGNN.set_precision``).  ``forward`` under
+        autograd ignores it."""
+        self._handle.set_precision(_precision_code(precision))
+
+    @property
+    def precision(self):
+        return _precision_name(self._handle.precision)
+
     def forward(self, x, edge_attr, edge_index=None):
         _need_cuda(x, "x")
         desc, params = self._standalone(x.device)
@@ -392,6 +421,16 @@ class InteractionNetwork(nn.Module):
         pre, post = self._pad[str(device)]
         params = pre + _mlp_params(self.phi_edge) + _mlp_params(self.phi_node) + post
         return desc, params
+
+    def set_precision(self, precision):
+        """Arithmetic of this block's stand-alone inference forward: 'f32' (the default, float32 accuracy) or 'f16' (weights and
+        inputs of every Linear rounded to fp16, float32 accumulation; see ``EncProcDecGNN.set_precision``).  ``forward`` under
+        autograd ignores it."""
+        self._handle.set_precision(_precision_code(precision))
+
+    @property
+    def precision(self):
+        return _precision_name(self._handle.precision)
 
     def forward(self, x, edge_attr, edge_index):
         _need_cuda(x, "x")
@@ -638,6 +677,30 @@ class EncProcDecGNN(nn.Module):
         for bit.  See include/gnn_manip_hip.h."""
         self._handle.set_node_fusion(on)
 
+    def set_precision(self, precision):
+        """Arithmetic of this model's INFERENCE kernels (gm_model_set_precision; no reference counterpart).  'f32', the default: every
+        Linear forms float32-accurate products on the fp16 matrix pipe (three partial products per multiply), the 1e-5 parity path.
+        'f16': every Linear multiplies its weights and its inputs rounded to fp16 and accumulates in float32 -- one matrix
+        instruction per multiply; biases, LayerNorm, residuals, the scatter-add and the latents stay float32.  After 10
+        message-passing steps the prediction is about 1e-3 of its largest element away from float64 (float32: 1e-6): enough to rank
+        the candidates of a planner, not for parity.  The range is the same: a latent beyond fp16 raises the same error at
+        ``status()`` and the prediction of that forward is NaN.
+
+        It covers ``forward`` without autograd, ``RolloutEngine`` and the planner built on this model, and -- set here for
+        convenience -- the stand-alone forwards of ``self.encoder`` and the ``self.processor`` blocks.  ``forward`` under autograd
+        (training, input gradients) ignores it: the training kernels have one arithmetic.  A differentiable rollout on an 'f16'
+        model visits the fp16 forward's states and differentiates the float32 step at them.  The switch needs no re-pack, may change
+        between any two calls and survives a weight update."""
+        code = _precision_code(precision)
+        self._handle.set_precision(code)
+        for block in [self.encoder] + list(self.processor):
+            block._handle.set_precision(code)
+
+    @property
+    def precision(self):
+        """'f32' or 'f16': what ``set_precision`` chose."""
+        return _precision_name(self._handle.precision)
+
     def forward_inputs_only(self, nodes, edge_attr, edge_index):
         """``forward`` with the parameters as constants, whatever their requires_grad flags say: gradients flow to nodes /
         edge_attr alone (gm_epd_backward_inputs_only) and no parameter's ``.grad`` is touched.  An ``nn.Module``'s parameters
@@ -645,7 +708,8 @@ class EncProcDecGNN(nn.Module):
         return self.forward(nodes, edge_attr, edge_index, _inputs_only=True)
 
     def forward(self, nodes, edge_attr, edge_index, _inputs_only=False):
-        """epd_gnn.py:86-98: encoder -> m_steps x (InteractionNetwork + residuals) -> decoder, fused."""
+        """epd_gnn.py:86-98: encoder -> m_steps x (InteractionNetwork + residuals) -> decoder, fused.  Under autograd (a parameter or an
+        input requires grad) this is the training forward, which ignores ``set_precision``."""
         _need_cuda(nodes, "nodes")
         nodes = nodes.contiguous().float()
         edge_attr = edge_attr.contiguous().float()

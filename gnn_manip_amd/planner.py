@@ -194,6 +194,8 @@ class TrajectoryCMAsolver:
     * ``optimize_trajectory(desired_position)``: ``cmaes.fmin2`` over that (the reference: ``cma.fmin2``, :257).
 
     Same constructor arguments as the reference (``state_init`` = (obs [k, N, D], next positions) on the device).
+    The rollouts follow the model's ``set_precision``: ``model.set_precision('f16')`` before planning ranks the candidates with the
+    fp16 single-product kernels (what that costs in accuracy and buys in time: DESIGN.md section 6.1).
     """
 
     def __init__(self, model, graph_attr, state_init, rx_init, ty_init, scale_rot, scale_ty, alpha, beta, gamma, penalty,

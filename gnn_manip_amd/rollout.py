@@ -188,6 +188,7 @@ class RolloutEngine:
 
     graph_attr: a ``GraphBoundedMultimaterial(Control)`` (gnn_manip_amd.graph) carrying conn_r,
     stats, bounds and the column indices, exactly like ``dataset.graph_attr`` in the reference.
+    The engine follows the model's ``set_precision``: every step it runs is in the arithmetic the model has at that call.
     """
 
     # run() renumbers the particles of scenes at least this large in grid-cell order, again every RENUMBER_EVERY steps
@@ -420,7 +421,9 @@ class RolloutEngine:
         (an engine that renumbers, see ``renumber``, sums a node's messages in another order inside ``rollout``: equal to
         rounding there), with gradients to ``obs0`` (position and control columns) and to ``trajectory`` [T, N_rigid, 3].  The
         model's parameters are CONSTANTS of this function: they get no gradient, whatever their requires_grad flags say, and
-        their ``.grad`` is not touched.
+        their ``.grad`` is not touched.  On a model switched to ``set_precision('f16')`` the forward visits the fp16 mode's windows and
+        the backward differentiates the FLOAT32 step at them (the training kernels have one arithmetic): the gradients are those of
+        the float32 model along the fp16 trajectory, and do not depend on the switch for given windows.
 
         Memory does not grow with the horizon beyond one state window per step.  The forward is the inference rollout (``step``
         in place on a clone, no tape) and keeps each step's pre-step window, k N D floats.  The backward walks the steps in

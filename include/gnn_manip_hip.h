@@ -229,6 +229,17 @@ int gm_state_post_backward(const float* d_obs_after, int64_t n_nodes, const gm_f
  * GM_ERR_DATA ("fp16 split range exceeded"); the outputs of that forward are then invalid.  A float32 evaluation would
  * also stay finite for magnitudes up to 3.4e38: that part of its domain is not covered.
  *
+ * Numeric domain of the fp16 mode (gm_model_set_precision(m, GM_PRECISION_F16); inference entry points only).  Every Linear
+ * multiplies its weights and its inputs ROUNDED TO fp16 (round to nearest even; 11 significant bits) and accumulates the exact
+ * products in float32: one matrix instruction per multiply instead of three.  Everything else is as above and stays float32: the
+ * power-of-two scales (which commute with the rounding), the biases, P and Q as initial accumulators, LayerNorm, residuals, the
+ * scatter-add and its summation order, the latents in memory.  The weight images are the same (the mode reads their hi halves), so the
+ * switch needs no re-pack.  Expect a decoder output about 1e-3 of its largest element away from float64 after 10 message-passing
+ * steps (float32: 1e-6): enough to rank rollout candidates, not for parity.  The range is the same: a value of magnitude >= 65520 in an
+ * operand image becomes +-inf, the row check of every kernel counts +-inf like NaN, the same flag is raised (GM_ERR_DATA, "fp16 split
+ * range exceeded") and the prediction of that forward comes out NaN, never a plausible finite number; a non-finite input row of
+ * gm_graph_independent_forward comes out as a NaN row and leaves the other rows' bits alone.
+ *
  * Numeric domain of the training entry points (gm_epd_forward_train / gm_epd_backward*, the *_forward_train / *_backward block
  * entry points).  They form the float32 products on the bf16 matrix pipe: every operand -- weight, activation, gradient -- is
  * split into three bf16 parts, which keep float32's whole exponent range, and accumulated in float32.  No operand is scaled and
@@ -286,6 +297,17 @@ int gm_model_set_edge_kernel(gm_model* m, int choice);
  * processor step's node MLP and the next step's projections as one launch (sys_node_proj_kernel), 0 as the two launches it is
  * made of.  The results are the same bit for bit. */
 int gm_model_set_node_fusion(gm_model* m, int on);
+/* Arithmetic of the INFERENCE kernels of THIS model (see "Numeric domain" above): GM_PRECISION_F32 (the default: three partial
+ * products per multiply, float32 accuracy) or GM_PRECISION_F16 (one: weights and inputs of every Linear rounded to fp16, float32
+ * accumulation).  It covers gm_epd_forward, gm_graph_independent_forward, gm_interaction_network_forward, gm_rollout_step and
+ * gm_rollout; which kernels a forward takes (gm_model_set_edge_kernel) does not depend on it.  It does NOT touch the training
+ * entry points (*_train, every backward), the Sinkhorn loss or the graph build: gm_rollout_step_backward / gm_rollout_backward of a
+ * GM_PRECISION_F16 model re-run and differentiate the FLOAT32 step at the states the fp16 forward visited.  The choice belongs to the
+ * handle (no process-global state, no environment variable), takes effect at the next call and may change between any two calls
+ * (the caller orders it against calls in flight on other threads, like a weight update).  A null model or any other value:
+ * GM_ERR_INVALID_ARGUMENT. */
+enum { GM_PRECISION_F32 = 0, GM_PRECISION_F16 = 1 };
+int gm_model_set_precision(gm_model* m, int precision);
 
 size_t gm_forward_workspace_bytes(const gm_model_desc* desc, int64_t n_nodes, int64_t edge_capacity);
 /* workspace of gm_interaction_network_forward (the latent edge arrays are the caller's) */
