@@ -24,6 +24,12 @@ struct MlpSpec { int base, end, in, out; bool normed; };
 struct TStream { size_t off = 0; int stages = 0, stages_tail = 0; };
 // the model's MLPs in state_dict order: edge encoder, node encoder, the edge and node MLP of each step, the decoder
 std::vector<MlpSpec> model_mlps(const gm_model_desc& d);
+
+// Two facts a rollout step (model.hip) and its backward (rollout_grad.hip) must agree on.
+// Width of a scene's node features (features.hip): 3 (k_steps - 1) + 7, and 3 more with control columns
+inline int node_feature_dim(const gm_feature_desc* fd) { return 3 * (fd->k_steps - 1) + 7 + (fd->control_col >= 0 ? 3 : 0); }
+// Nodes of one graph of a batch of equal-sized scenes stored back to back (nodes_per_graph == 0: one scene of n nodes)
+inline int64_t graph_nodes(const gm_feature_desc* fd, int64_t n) { return fd->nodes_per_graph > 0 ? fd->nodes_per_graph : n; }
 }  // namespace gm
 
 struct gm_model {

@@ -745,7 +745,7 @@ int gm_rollout_step(const gm_model* m, float* obs, int64_t n, const gm_feature_d
                     const float* rigid_target, float* pred_acc_out, void* ws, size_t ws_bytes, void* stream) {
     gm::DevGuard dev_guard(obs);
     GM_REQUIRE(m && obs && fd && ws, GM_ERR_INVALID_ARGUMENT, "gm_rollout_step: null pointer");
-    const int F = 3 * (fd->k_steps - 1) + 7 + (fd->control_col >= 0 ? 3 : 0);
+    const int F = gm::node_feature_dim(fd);
     GM_REQUIRE(m->d.node_dim == F, GM_ERR_INVALID_ARGUMENT, "gm_rollout_step: model node_dim=%d but features give %d", m->d.node_dim, F);
     GM_REQUIRE(m->d.edge_dim == 4 && m->d.out_dim == 3, GM_ERR_INVALID_ARGUMENT, "gm_rollout_step: needs edge_dim=4, out_dim=3 (3-D scene)");
     GM_REQUIRE(n < ((int64_t)1 << 31) / (K > 0 ? K : 1), GM_ERR_UNSUPPORTED, "gm_rollout_step: n*max_neighbours overflows int32");
@@ -771,7 +771,7 @@ int gm_rollout_step(const gm_model* m, float* obs, int64_t n, const gm_feature_d
     const float* last_pos = obs + (size_t)(fd->k_steps - 1) * n * fd->data_dim + fd->cart_col;
     {   // the in-degree count of the destination sort rides in the neighbour search
         ProfScope prof(m->prof, PROF_GRAPH, hs);
-        rc = gm::radius_graph_build_fused(last_pos, fd->data_dim, n, fd->nodes_per_graph > 0 ? fd->nodes_per_graph : n, fd->conn_r, K,
+        rc = gm::radius_graph_build_fused(last_pos, fd->data_dim, n, gm::graph_nodes(fd, n), fd->conn_r, K,
                                           r.graph, r.graph_bytes, r.csr, r.csr_bytes, m->d.flow, hs);
     }
     if (rc != GM_OK) return rc;
@@ -782,8 +782,7 @@ int gm_rollout_step(const gm_model* m, float* obs, int64_t n, const gm_feature_d
                                       m->d.flow, hs);
     }
     if (rc != GM_OK) return rc;
-    rc = epd_forward_impl(m, r.x, n, r.edge_attr, 1, r.csr, cap, r.pred, r.fwd, r.fwd_bytes, stream, true,
-                          fd->nodes_per_graph > 0 ? fd->nodes_per_graph : n);
+    rc = epd_forward_impl(m, r.x, n, r.edge_attr, 1, r.csr, cap, r.pred, r.fwd, r.fwd_bytes, stream, true, gm::graph_nodes(fd, n));
     if (rc != GM_OK) return rc;
     // integrator + window shift + write-back (+ copy of the prediction) in one launch
     ProfScope prof(m->prof, PROF_REST, hs);
@@ -829,7 +828,7 @@ int gm_rollout(const gm_model* m, float* obs, int64_t n, const gm_feature_desc* 
     for (int64_t i = 0; i < steps; ++i) {
         if (renum && i % renumber_every == 0) {
             const float* last_pos = state + (size_t)(fd->k_steps - 1) * frame + fd->cart_col;
-            int rc = gm::cell_order(last_pos, fd->data_dim, n, fd->nodes_per_graph > 0 ? fd->nodes_per_graph : n, fd->conn_r, K, r.graph,
+            int rc = gm::cell_order(last_pos, fd->data_dim, n, gm::graph_nodes(fd, n), fd->conn_r, K, r.graph,
                                     r.graph_bytes, rw.perm, hs);
             if (rc != GM_OK) return rc;
             rc = gm::renumber_gather(state, rw.state[flip], fd->k_steps, n, fd->data_dim, rw.perm, r.graph, total, rw.total[flip],

@@ -25,13 +25,11 @@ struct StepBwdWs {
     size_t bytes;
 };
 
-int node_dim_of(const gm_feature_desc* fd) { return 3 * (fd->k_steps - 1) + 7 + (fd->control_col >= 0 ? 3 : 0); }
-
 StepBwdWs carve_step_bwd(void* ws, const gm_model_desc* d, const gm_feature_desc* fd, int64_t n, int K) {
     StepBwdWs w;
     const int64_t cap = n * K;
     const size_t window = (size_t)fd->k_steps * n * fd->data_dim;
-    const size_t F = (size_t)node_dim_of(fd);
+    const size_t F = (size_t)gm::node_feature_dim(fd);
     gm::Carver c(ws);
     w.pre = c.take<float>(window);
     w.nodes = c.take<float>((size_t)n * F);
@@ -101,7 +99,7 @@ static int step_backward(const gm_model* m, const float* const* tensors, int n_t
     GM_REQUIRE(sizes_ok(&m->d, fd, n, K), GM_ERR_INVALID_ARGUMENT, "%s: sizes out of range", who);
     GM_REQUIRE(n == 0 || (obs_before && d_obs_after && d_obs_before), GM_ERR_INVALID_ARGUMENT, "%s: null pointer", who);
     GM_REQUIRE(!rigid_target || rigid_rank, GM_ERR_INVALID_ARGUMENT, "%s: rigid_target needs rigid_rank", who);
-    const int F = node_dim_of(fd);
+    const int F = gm::node_feature_dim(fd);
     GM_REQUIRE(m->d.node_dim == F, GM_ERR_INVALID_ARGUMENT, "%s: model node_dim=%d but features give %d", who, m->d.node_dim, F);
     GM_REQUIRE(m->d.edge_dim == 4 && m->d.out_dim == 3, GM_ERR_INVALID_ARGUMENT,
                "%s: needs edge_dim=4, out_dim=3 (3-D scene)", who);
@@ -125,7 +123,7 @@ static int step_backward(const gm_model* m, const float* const* tensors, int n_t
     rc = gm_node_features(w.pre, n, fd, w.nodes, stream);
     if (rc != GM_OK) return rc;
     const float* last_pos = w.pre + (size_t)(fd->k_steps - 1) * n * fd->data_dim + fd->cart_col;
-    rc = gm_radius_graph_build_batched(last_pos, fd->data_dim, n, fd->nodes_per_graph > 0 ? fd->nodes_per_graph : n, fd->conn_r, K, w.graph,
+    rc = gm_radius_graph_build_batched(last_pos, fd->data_dim, n, gm::graph_nodes(fd, n), fd->conn_r, K, w.graph,
                                        w.graph_bytes, stream);
     if (rc != GM_OK) return rc;
     int64_t e = 0;

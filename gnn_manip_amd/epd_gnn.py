@@ -62,6 +62,34 @@ def _mlp_dims(seq):
     return lin, norm
 
 
+def _pointers(tensors):
+    """The void* array a library call takes for a list of contiguous tensors."""
+    return (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def _device_arrays(params, device):
+    """(contiguous float32 copies of `params` on `device`, detached; their pointer array): a model's tensors as the library reads them."""
+    tensors = [p.detach().to(device=device, dtype=torch.float32).contiguous() for p in params]
+    return tensors, _pointers(tensors)
+
+
+def _zeroed_like(tensors):
+    """One view per tensor, shaped like it, into ONE flat zeroed float32 buffer: a set of parameter gradients for a backward call."""
+    flat = torch.zeros(sum(t.numel() for t in tensors), dtype=torch.float32, device=tensors[0].device)
+    views, off = [], 0
+    for t in tensors:
+        views.append(flat[off:off + t.numel()].view_as(t))
+        off += t.numel()
+    return views
+
+
+def _grad_arrays(params, device):
+    """(tensors, per-tensor views of a flat zeroed gradient buffer, ctypes arrays of both) for a backward call."""
+    tensors, t_arr = _device_arrays(params, device)
+    views = _zeroed_like(tensors)
+    return tensors, views, t_arr, _pointers(views)
+
+
 class _Model:
     """A gm_model* that lives as long as anything refers to it (the owning _Handle, or the ctx of a pending backward):
     ctypes passes `_as_parameter_`; the library object is destroyed when the last reference goes."""
@@ -97,15 +125,15 @@ class _Handle:
         if self.h is not None and key == self.key:
             return self.h
         L = lib()
-        tensors = [p.detach().to(device=device, dtype=torch.float32).contiguous() for p in params]
-        arr = (C.c_void_p * len(tensors))(*[ptr(t).value for t in tensors])
+        tensors, arr = _device_arrays(params, device)
+        stream = current_stream(tensors[0])
         d = ModelDesc(*desc_tuple)
         if self.h is not None and self.built_for == (desc_tuple, str(device)):   # (not self.key: invalidate() clears that)
-            check(L.gm_model_update(self.h, arr, len(tensors), 1, current_stream()))
+            check(L.gm_model_update(self.h, arr, len(tensors), 1, stream))
         else:
             self.close()
             out = C.c_void_p()
-            check(L.gm_model_create(C.byref(d), arr, len(tensors), 1, current_stream(), C.byref(out)))
+            check(L.gm_model_create(C.byref(d), arr, len(tensors), 1, stream, C.byref(out)))
             self.h = _Model(out)
             if self.edge_kernel:
                 check(L.gm_model_set_edge_kernel(self.h, self.edge_kernel))
@@ -163,26 +191,14 @@ class _Handle:
             pass
 
 
-def _grad_arrays(params, device):
-    """(tensors, flat gradient buffer, per-tensor views, ctypes arrays) for a backward call."""
-    tensors = [p.detach().to(device=device, dtype=torch.float32).contiguous() for p in params]
-    flat = torch.zeros(sum(t.numel() for t in tensors), dtype=torch.float32, device=device)
-    views, off = [], 0
-    for t in tensors:
-        views.append(flat[off:off + t.numel()].view_as(t))
-        off += t.numel()
-    t_arr = (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
-    g_arr = (C.c_void_p * len(views))(*[v.data_ptr() for v in views])
-    return tensors, views, t_arr, g_arr
-
-
 def _wants_grad(params, *inputs):
     return torch.is_grad_enabled() and (any(p.requires_grad for p in params) or any(t.requires_grad for t in inputs))
 
 
-def _check_edge_index(edge_index, n, e, ranges=True):
+def _check_edge_index(edge_index, n, e=None, ranges=True):
+    """e: the number of edges the caller's other arrays have, None when there is nothing to agree with."""
     _need_cuda(edge_index, "edge_index")
-    if edge_index.dtype != torch.int64 or edge_index.dim() != 2 or edge_index.shape[0] != 2 or edge_index.shape[1] != e:
+    if edge_index.dtype != torch.int64 or edge_index.dim() != 2 or edge_index.shape[0] != 2 or e not in (None, edge_index.shape[1]):
         raise ValueError("edge_index must be int64 [2, E]")
     if ranges and e and (int(edge_index.min()) < 0 or int(edge_index.max()) >= n):   # two blocking reductions
         raise ValueError("edge_index entry out of range [0, n_nodes)")
@@ -268,9 +284,7 @@ class DstCsr:
     """Destination-sorted edge structure of an edge_index [2, E] (int64) on the device."""
 
     def __init__(self, edge_index, n_nodes, flow=0):
-        _need_cuda(edge_index, "edge_index")
-        if edge_index.dtype != torch.int64 or edge_index.dim() != 2 or edge_index.shape[0] != 2:
-            raise ValueError("edge_index must be int64 [2, E]")
+        _check_edge_index(edge_index, n_nodes, ranges=False)
         ei = edge_index.contiguous()
         self.n = int(n_nodes)
         self.e = int(ei.shape[1])
@@ -337,29 +351,20 @@ def _zeros_mlp(fin, hidden, fout, num_layers, norm, device):
     return t
 
 
-class GraphIndependent(nn.Module):
-    """``torch_graphnet.GraphIndependent(phi_edge=, phi_node=)``: (x, e, idx) -> (phi_node(x), phi_edge(e), None)."""
+class _StandaloneBlock(nn.Module):
+    """What the two blocks share when they run on their own: a standalone block runs through a one-step model handle whose other
+    MLPs are zero placeholders, built once per device.  Nothing here is a parameter, a buffer or a sub-module: a block's
+    ``state_dict()`` is its phi_edge / phi_node alone."""
 
-    def __init__(self, phi_edge, phi_node):
+    def __init__(self):
         super().__init__()
-        self.phi_edge = phi_edge
-        self.phi_node = phi_node
         self._handle = _Handle()
         self._pad = {}
 
-    def _standalone(self, device):
-        # a standalone block runs through a one-step model handle whose other MLPs are zero placeholders
-        le, ne = _mlp_dims(self.phi_edge)
-        ln, nn_ = _mlp_dims(self.phi_node)
-        hidden, nl = le[-1].out_features, len(le) - 1
-        eps = ne[0].eps if ne else 1e-5
-        desc = (ln[0].in_features, le[0].in_features, 1, hidden, nl, 1, float(eps))
+    def _placeholders(self, device, build):
         if str(device) not in self._pad:
-            self._pad[str(device)] = (_zeros_mlp(3 * hidden, hidden, hidden, nl, True, device)
-                                      + _zeros_mlp(2 * hidden, hidden, hidden, nl, True, device)
-                                      + _zeros_mlp(hidden, hidden, 1, nl, False, device))
-        params = _mlp_params(self.phi_edge) + _mlp_params(self.phi_node) + self._pad[str(device)]
-        return desc, params
+            self._pad[str(device)] = build()
+        return self._pad[str(device)]
 
     def set_precision(self, precision):
         """Arithmetic of this block's stand-alone inference forward: 'f32' (the default, float32 accuracy) or 'f16' (weights and
@@ -371,6 +376,35 @@ class GraphIndependent(nn.Module):
     def precision(self):
         return _precision_name(self._handle.precision)
 
+    @staticmethod
+    def _unpadded(hidden, h_out, e_out):
+        """(h', e', None) of an inference forward: the library's latents have the row stride padded_hidden(hidden), and the padded
+        columns, which come back as zeros, are sliced off again."""
+        if h_out.shape[1] != hidden:
+            h_out, e_out = h_out[:, :hidden].contiguous(), e_out[:, :hidden].contiguous()
+        return h_out, e_out, None
+
+
+class GraphIndependent(_StandaloneBlock):
+    """``torch_graphnet.GraphIndependent(phi_edge=, phi_node=)``: (x, e, idx) -> (phi_node(x), phi_edge(e), None)."""
+
+    def __init__(self, phi_edge, phi_node):
+        super().__init__()
+        self.phi_edge = phi_edge
+        self.phi_node = phi_node
+
+    def _standalone(self, device):
+        le, ne = _mlp_dims(self.phi_edge)
+        ln, nn_ = _mlp_dims(self.phi_node)
+        hidden, nl = le[-1].out_features, len(le) - 1
+        eps = ne[0].eps if ne else 1e-5
+        desc = (ln[0].in_features, le[0].in_features, 1, hidden, nl, 1, float(eps))
+        pad = self._placeholders(device, lambda: (_zeros_mlp(3 * hidden, hidden, hidden, nl, True, device)
+                                                  + _zeros_mlp(2 * hidden, hidden, hidden, nl, True, device)
+                                                  + _zeros_mlp(hidden, hidden, 1, nl, False, device)))
+        params = _mlp_params(self.phi_edge) + _mlp_params(self.phi_node) + pad
+        return desc, params
+
     def forward(self, x, edge_attr, edge_index=None):
         _need_cuda(x, "x")
         desc, params = self._standalone(x.device)
@@ -381,18 +415,15 @@ class GraphIndependent(nn.Module):
             h_out, e_out = _GraphIndependentFunction.apply(self, len(own), x, edge_attr, *params)
             return h_out, e_out, None
         h = self._handle.get(desc, params, x.device)
-        hidden = desc[3]
-        hp = padded_hidden(hidden)   # the library's row stride of latents; the padded columns come back as zeros
+        hp = padded_hidden(desc[3])   # the library's row stride of latents
         h_out = torch.empty((x.shape[0], hp), dtype=torch.float32, device=x.device)
         e_out = torch.empty((edge_attr.shape[0], hp), dtype=torch.float32, device=x.device)
         check(lib().gm_graph_independent_forward(h, ptr(x), x.shape[0], ptr(edge_attr), edge_attr.shape[0],
                                                  ptr(h_out), ptr(e_out), current_stream()))
-        if hp != hidden:
-            h_out, e_out = h_out[:, :hidden].contiguous(), e_out[:, :hidden].contiguous()
-        return h_out, e_out, None
+        return self._unpadded(desc[3], h_out, e_out)
 
 
-class InteractionNetwork(nn.Module):
+class InteractionNetwork(_StandaloneBlock):
     """``torch_graphnet.InteractionNetwork(phi_edge=, phi_node=)``: (h, e, idx) -> (h', e', None).
 
     The block's source is absent from the reference tree (.gitmodules:1-3); the defaults are the convention of DESIGN.md
@@ -405,8 +436,6 @@ class InteractionNetwork(nn.Module):
         self.phi_edge = phi_edge
         self.phi_node = phi_node
         self.convention = _convention(flow, concat, node_concat)
-        self._handle = _Handle()
-        self._pad = {}
 
     def _standalone(self, device):
         le, ne = _mlp_dims(self.phi_edge)
@@ -415,22 +444,12 @@ class InteractionNetwork(nn.Module):
             raise ValueError("InteractionNetwork.phi_edge must take 3*hidden inputs ([h_i, h_j, e])")
         eps = ne[0].eps if ne else 1e-5
         desc = (1, 1, 1, hidden, nl, 1, float(eps)) + self.convention
-        if str(device) not in self._pad:
-            self._pad[str(device)] = (_zeros_mlp(1, hidden, hidden, nl, True, device) + _zeros_mlp(1, hidden, hidden, nl, True, device),
-                                      _zeros_mlp(hidden, hidden, 1, nl, False, device))
-        pre, post = self._pad[str(device)]
+        # the placeholder encoders come before the block's own tensors, the placeholder decoder after them
+        pre, post = self._placeholders(device, lambda: (_zeros_mlp(1, hidden, hidden, nl, True, device)
+                                                        + _zeros_mlp(1, hidden, hidden, nl, True, device),
+                                                        _zeros_mlp(hidden, hidden, 1, nl, False, device)))
         params = pre + _mlp_params(self.phi_edge) + _mlp_params(self.phi_node) + post
         return desc, params
-
-    def set_precision(self, precision):
-        """Arithmetic of this block's stand-alone inference forward: 'f32' (the default, float32 accuracy) or 'f16' (weights and
-        inputs of every Linear rounded to fp16, float32 accumulation; see ``EncProcDecGNN.set_precision``).  ``forward`` under
-        autograd ignores it."""
-        self._handle.set_precision(_precision_code(precision))
-
-    @property
-    def precision(self):
-        return _precision_name(self._handle.precision)
 
     def forward(self, x, edge_attr, edge_index):
         _need_cuda(x, "x")
@@ -448,7 +467,7 @@ class InteractionNetwork(nn.Module):
 
 
 def _run_block(handle, desc, k, x, edge_attr, edge_index, csr=None):
-    hidden, hp = desc[3], padded_hidden(desc[3])
+    hp = padded_hidden(desc[3])
     x = _pad_cols(x.float(), hp).contiguous()            # library row stride (zero padding stays zero through the block)
     edge_attr = _pad_cols(edge_attr.float(), hp).contiguous()
     n, e = x.shape[0], edge_attr.shape[0]
@@ -461,19 +480,16 @@ def _run_block(handle, desc, k, x, edge_attr, edge_index, csr=None):
     e_out = torch.empty_like(edge_attr)
     check(L.gm_interaction_network_forward(handle, k, ptr(x), n, ptr(edge_attr), ptr(csr.ws), e, ptr(h_out),
                                            ptr(e_out), ptr(fwd), fwd.numel(), current_stream()))
-    if hp != hidden:
-        h_out, e_out = h_out[:, :hidden].contiguous(), e_out[:, :hidden].contiguous()
-    return h_out, e_out, None
+    return _StandaloneBlock._unpadded(desc[3], h_out, e_out)
 
 
 class _EpdTrainFunction(torch.autograd.Function):
     """``EncProcDecGNN.forward`` under autograd (examples/train_dyn.py:45-72): the forward records the
     activation tape in one device buffer, the backward is gm_epd_backward -- or, when nodes / edge_attr require grad (a
     differentiable rollout step, a frozen model in a planning loop), gm_epd_backward_inputs, which runs the same launches and lets
-    the encoders' chains go on into d_nodes / d_edge_attr.  edge_index is data.  `spec` = (model descriptor tuple, _Handle): the module's own, or
-    -- for a hidden size between the training kernels' widths -- the zero-padded model's (EncProcDecGNN._padded_training), with
-    the module's own parameters as the third element: the tensors whose versions say when the padded copies are stale.  The fourth
-    element is the inputs-only switch: the parameters are constants of this call whatever their requires_grad flags say, and the
+    the encoders' chains go on into d_nodes / d_edge_attr.  edge_index is data.  `spec` = (descriptor tuple, _Handle, key tensors) of the
+    model that `params` are the tensors of, as ``EncProcDecGNN._training_spec`` resolved it, and as the fourth element the
+    inputs-only switch: the parameters are constants of this call whatever their requires_grad flags say, and the
     backward is gm_epd_backward_inputs_only -- none of the weight-gradient launches, no gradient buffers.  EncProcDecGNN.forward
     sets it when no parameter requires grad; a caller that differentiates with respect to the inputs alone (a planner on a model
     nobody froze) asks for it through ``EncProcDecGNN.forward_inputs_only``."""
@@ -510,8 +526,7 @@ class _EpdTrainFunction(torch.autograd.Function):
             d_nodes = torch.empty_like(nodes) if ctx.needs_input_grad[2] else None
             d_edge_attr = torch.empty_like(edge_attr) if ctx.needs_input_grad[3] else None
             if d_nodes is not None or (d_edge_attr is not None and e > 0):   # (an empty d_edge_attr has nothing to compute)
-                tensors = [p.detach().to(device=dev, dtype=torch.float32).contiguous() for p in params]
-                t_arr = (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+                tensors, t_arr = _device_arrays(params, dev)
                 ws = _ws(L.gm_train_backward_inputs_workspace_bytes(C.byref(ctx.desc), n, e), dev)
                 check(L.gm_epd_backward_inputs_only(ctx.handle, t_arr, len(tensors), ptr(nodes), ptr(edge_attr), n, e, ptr(grad_out),
                                                     ptr(d_nodes), ptr(d_edge_attr), ptr(ctx.tape), ctx.tape.numel(), ptr(ws), ws.numel(),
@@ -604,8 +619,6 @@ class EncProcDecGNN(nn.Module):
         Returns ((descriptor tuple of the padded model, its handle), padded parameter tensors)."""
         node_dim, edge_dim, out_dim, hv, nl, m_steps = self.dims
         hp = padded_hidden(hv)
-        if hp not in TRAIN_WIDTHS:
-            raise NotImplementedError(f"training at hidden_size={hv}: supported are 1 .. {TRAIN_WIDTHS[-1]}")
         pad = torch.nn.functional.pad
         scale = (hv / hp) ** 0.5
         it = iter(params)
@@ -644,6 +657,22 @@ class EncProcDecGNN(nn.Module):
         if "_pad_handle" not in self.__dict__:
             self.__dict__["_pad_handle"] = _Handle()
         return (desc, self._pad_handle), padded
+
+    def _training_spec(self, params):
+        """The model the training entry points run for this module -- ``forward`` under autograd, the engine's ``step_backward`` and
+        library sweeps: (descriptor tuple, _Handle, tensors to hand the library, key tensors for ``_Handle.get``).  At a hidden
+        size of 64 / 128 / 256 that is the module's own descriptor and handle with `params` themselves (key tensors None);
+        otherwise the zero-padded model of ``_padded_training``, whose handle is keyed on `params`: the padded tensors are rebuilt
+        at every call (version 0, recycled addresses), so it is the tensors they come from whose versions say when the packed
+        weight streams are stale -- an optimiser step on ANY of them, whatever is frozen, re-packs.
+        `params`: ``self.parameters()``, live (gradients then flow back through the padded copies: the caller runs under autograd)
+        or detached (constants; a caller that wants no graph for the padded copies wraps the call in no_grad)."""
+        if self.dims[3] in TRAIN_WIDTHS:
+            return self.model_desc(), self._handle, params, None
+        if padded_hidden(self.dims[3]) not in TRAIN_WIDTHS:
+            raise NotImplementedError(f"training at hidden_size={self.dims[3]}: supported are 1 .. {TRAIN_WIDTHS[-1]}")
+        (desc, handle), padded = self._padded_training(params)
+        return desc, handle, padded, tuple(params)
 
     auto_status = True   # check the previous inference forward's device-side error flags at the start of the next one
 
@@ -736,16 +765,10 @@ class EncProcDecGNN(nn.Module):
             _check_edge_index(edge_index, n, e, ranges=False)
             if self.auto_status:
                 self._reap_watched(block=False)
-            hidden = self.dims[3]
             if inputs_only:
                 params = [p.detach() for p in params]   # constants: autograd records nothing for them (nor for the padded copies)
-            if hidden in TRAIN_WIDTHS:
-                return _EpdTrainFunction.apply(self, (self.model_desc(), self._handle, None, inputs_only), nodes, edge_attr, edge_index,
-                                               *params)
-            spec, padded = self._padded_training(params)
-            # the padded tensors are rebuilt every step (version 0, recycled addresses): the handle is keyed on the parameters they
-            # come from, so an optimiser step on ANY of them -- whatever is frozen -- re-packs the padded model's weight streams
-            return _EpdTrainFunction.apply(self, spec + (tuple(params), inputs_only), nodes, edge_attr, edge_index, *padded)
+            desc, handle, tensors, key = self._training_spec(params)
+            return _EpdTrainFunction.apply(self, (desc, handle, key, inputs_only), nodes, edge_attr, edge_index, *tensors)
         if self.auto_status:
             # EARLIER inference forwards of this model: a device-side error (edge_index entry out of range, fp16 split range
             # exceeded) of one that has FINISHED surfaces here -- a reference-style caller never calls status() itself.

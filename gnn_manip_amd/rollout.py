@@ -14,6 +14,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from ._lib import ModelDesc, check, current_stream, lib, ptr
+from .epd_gnn import _device_arrays, _pointers, _zeroed_like
 from .graph import _NodeFeaturesFunction, _need_cuda, _node_features, _ws, get_connectivity, get_edges_displacement, make_feature_desc
 
 
@@ -60,19 +61,31 @@ class _IntegrateFunction(torch.autograd.Function):
         return (d_pred if ctx.needs_input_grad[0] else None), (d_obs if ctx.needs_input_grad[1] else None), None
 
 
+def _roll_forward(engine, obs0, trajectory, steps, keep, records=None):
+    """The forward of both rollout Functions: the inference rollout -- ``step`` in place on a detached clone of ``obs0``, no tape,
+    one synchronisation at its end -- with ``keep(t, window)`` called on every pre-step window, all the backward needs of step t
+    besides its pose; how the windows are held is the caller's business.  records: None or [steps, N, D] to fill.  Returns the
+    final state and the trajectory as the steps read it (detached, contiguous float32)."""
+    obs = obs0.detach().clone().contiguous()
+    traj = None if trajectory is None else trajectory.detach().contiguous().float()
+    engine.set_scene(obs)
+    for t in range(steps):
+        keep(t, obs)
+        engine.step(obs, None if traj is None else traj[t])
+        if records is not None:
+            # the last frame after step t's control overwrite is frame k-2 of the window the step left (the shift moved it there)
+            records[t].copy_(obs[-2])
+    engine.status()
+    return obs, traj
+
+
 class _RolloutFunction(torch.autograd.Function):
     """RolloutEngine.differentiable_rollout: the inference rollout forward, a reverse sweep of re-run differentiable steps backward."""
 
     @staticmethod
     def forward(ctx, engine, obs0, trajectory, steps, edges):
-        obs = obs0.detach().clone().contiguous()
-        traj = None if trajectory is None else trajectory.detach().contiguous().float()
-        engine.set_scene(obs)
         windows = []
-        for t in range(steps):
-            windows.append(obs.clone())    # the pre-step window: all the backward needs of step t besides its pose
-            engine.step(obs, None if traj is None else traj[t])
-        engine.status()
+        obs, traj = _roll_forward(engine, obs0, trajectory, steps, lambda t, window: windows.append(window.clone()))
         ctx.engine, ctx.windows, ctx.traj, ctx.edges = engine, windows, traj, edges
         ctx.scene = (engine.rigid_rank, engine.rigid_rows, engine.n_rigid)
         return obs
@@ -104,54 +117,19 @@ class _RolloutFunction(torch.autograd.Function):
         return None, (d_window if ctx.needs_input_grad[1] else None), d_traj, None, None
 
 
-class _RolloutLibraryFunction(torch.autograd.Function):
-    """RolloutEngine.differentiable_rollout(sweep="library"): _RolloutFunction's forward with the windows kept in one [T, k, N, D]
-    array, and the whole reverse sweep as one gm_rollout_backward call."""
-
-    @staticmethod
-    def forward(ctx, engine, obs0, trajectory, steps):
-        obs = obs0.detach().clone().contiguous()
-        traj = None if trajectory is None else trajectory.detach().contiguous().float()
-        engine.set_scene(obs)
-        windows = torch.empty((steps,) + tuple(obs.shape), dtype=torch.float32, device=obs.device)
-        for t in range(steps):
-            windows[t].copy_(obs)          # the pre-step window of step t
-            engine.step(obs, None if traj is None else traj[t])
-        engine.status()
-        ctx.engine, ctx.windows, ctx.traj, ctx.steps = engine, windows, traj, steps
-        ctx.scene = (engine.rigid_rank, engine.n_rigid)
-        return obs
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, d_final):
-        need_traj = ctx.traj is not None and ctx.needs_input_grad[2]
-        d_obs0, d_traj = ctx.engine._sweep_backward(ctx.windows, ctx.traj, ctx.steps, d_final.contiguous().float(), ctx.scene, need_traj)
-        ctx.windows = None
-        return None, (d_obs0 if ctx.needs_input_grad[1] else None), d_traj, None
-
-
 class _RolloutTrainFunction(torch.autograd.Function):
-    """RolloutEngine.differentiable_rollout(sweep="library", record=..., params=...): _RolloutLibraryFunction with the per-step
-    records as a second output and the model's (training) tensors as inputs; the reverse sweep is one gm_rollout_backward_train
-    call.  `model`: None (the parameters are constants, no tensors follow) or the (gm_model handle, descriptor) the tensors that
-    follow belong to -- the module's parameters, or the padded tensors EncProcDecGNN._padded_training built from them under
-    autograd, which then carries their gradients back into the checkpoint's shapes."""
+    """RolloutEngine.differentiable_rollout(sweep="library"): _RolloutFunction's forward with the windows kept in one [T, k, N, D]
+    array, and the whole reverse sweep as one gm_rollout_backward_train call.  `record`: the per-step records are a second
+    output.  `model`: None (the parameters are constants, no tensors follow: the sweep is gm_rollout_backward's) or the (gm_model
+    handle, descriptor) the tensors that follow belong to, as EncProcDecGNN._training_spec resolved them from the LIVE
+    parameters -- the parameters themselves, or the padded tensors built from them under autograd, which then carries their
+    gradients back into the checkpoint's shapes."""
 
     @staticmethod
     def forward(ctx, engine, obs0, trajectory, steps, record, model, *tensors):
-        obs = obs0.detach().clone().contiguous()
-        traj = None if trajectory is None else trajectory.detach().contiguous().float()
-        engine.set_scene(obs)
-        windows = torch.empty((steps,) + tuple(obs.shape), dtype=torch.float32, device=obs.device)
-        records = torch.empty((steps,) + tuple(obs.shape[1:]), dtype=torch.float32, device=obs.device) if record else None
-        for t in range(steps):
-            windows[t].copy_(obs)          # the pre-step window of step t
-            engine.step(obs, None if traj is None else traj[t])
-            if record:
-                # the last frame after step t's control overwrite is frame k-2 of the window the step left (the shift moved it there)
-                records[t].copy_(obs[-2])
-        engine.status()
+        windows = torch.empty((steps,) + tuple(obs0.shape), dtype=torch.float32, device=obs0.device)
+        records = torch.empty((steps,) + tuple(obs0.shape[1:]), dtype=torch.float32, device=obs0.device) if record else None
+        obs, traj = _roll_forward(engine, obs0, trajectory, steps, lambda t, window: windows[t].copy_(window), records)
         ctx.engine, ctx.windows, ctx.traj, ctx.steps, ctx.model, ctx.record = engine, windows, traj, steps, model, record
         ctx.scene = (engine.rigid_rank, engine.n_rigid)
         ctx.save_for_backward(*tensors)
@@ -168,13 +146,10 @@ class _RolloutTrainFunction(torch.autograd.Function):
         tensors = ctx.saved_tensors
         model = grads = None
         if ctx.model is not None:
-            model = ctx.model + ([t.detach().to(device=eng.device, dtype=torch.float32).contiguous() for t in tensors],)
+            h, mdesc = ctx.model
+            model = (h,) + _device_arrays(tensors, eng.device) + (mdesc,)
             if any(ctx.needs_input_grad[6:]):
-                flat = torch.zeros(sum(t.numel() for t in model[2]), dtype=torch.float32, device=eng.device)   # ONE set, whatever T
-                grads, off = [], 0
-                for t in model[2]:
-                    grads.append(flat[off:off + t.numel()].view_as(t))
-                    off += t.numel()
+                grads = _zeroed_like(model[1])   # ONE set, whatever T
         d_obs0, d_traj = eng._sweep_backward(ctx.windows, ctx.traj, ctx.steps, d_final.contiguous().float(), ctx.scene, need_traj,
                                              d_records=None if d_records is None else d_records.contiguous().float(), model=model,
                                              grads=grads)
@@ -249,24 +224,32 @@ class RolloutEngine:
         self.rigid_rows = torch.nonzero(self.rigid_rank >= 0).flatten()   # ascending: row j of a rigid_target belongs to rigid_rows[j]
         return self.n_rigid
 
+    def _check_tensor(self, t, name, shape, converted=False, min_rows=0):
+        """The C entries take raw pointers: `t` must be a tensor on this engine's device, float32 and contiguous, of exactly `shape`,
+        else ValueError.  A string in `shape` names a dimension that is free (the first one from `min_rows` up); an int in place
+        of the tuple is an element count, whatever the dimensions.  converted: any dtype and layout pass (the caller makes the
+        contiguous float32 copy itself)."""
+        fits = isinstance(t, torch.Tensor) and t.device == self.device and (converted or (t.dtype == torch.float32 and t.is_contiguous()))
+        if fits and isinstance(shape, int):
+            fits = t.numel() == shape
+        elif fits and t.shape != shape:   # (equal: the common case, settled without looking at the entries)
+            fits = (t.dim() == len(shape) and all(isinstance(want, str) or want == got for want, got in zip(shape, t.shape))
+                    and t.shape[0] >= min_rows)
+        if not fits:
+            want = f"with {shape} elements" if isinstance(shape, int) else "[" + ", ".join(str(d) for d in shape) + "]"
+            given = f"{tuple(t.shape)} {t.dtype} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
+            raise ValueError(f"{name} must be {'a tensor' if converted else 'contiguous float32'} {want} on {self.device}, got {given}")
+
     def _check_state(self, obs, rigid_target, pred_out, use_rigid):
-        """The C entry takes raw pointers: shapes, dtypes and devices are checked here."""
-        if not (isinstance(obs, torch.Tensor) and obs.is_cuda and obs.device == self.device):
-            raise ValueError(f"obs must be a tensor on {self.device}")
-        if tuple(obs.shape) != (self.k, self.n, self.data_dim) or obs.dtype != torch.float32 or not obs.is_contiguous():
-            raise ValueError(f"obs must be contiguous float32 [{self.k}, {self.n}, {self.data_dim}], got {tuple(obs.shape)} {obs.dtype}")
+        self._check_tensor(obs, "obs", (self.k, self.n, self.data_dim))
         if use_rigid and self.rigid_rank is None:
             raise RuntimeError("RolloutEngine.set_scene(obs) must be called before step()")
         if rigid_target is not None:
             if not use_rigid:
                 raise ValueError("rigid_target needs use_rigid=True")
-            if (rigid_target.device != self.device or rigid_target.dtype != torch.float32 or not rigid_target.is_contiguous()
-                    or tuple(rigid_target.shape) != (self.n_rigid, 3)):
-                raise ValueError(f"rigid_target must be contiguous float32 [{self.n_rigid}, 3] on {self.device}, got {tuple(rigid_target.shape)}")
+            self._check_tensor(rigid_target, "rigid_target", (self.n_rigid, 3))
         if pred_out is not None:
-            if (pred_out.device != self.device or pred_out.dtype != torch.float32 or not pred_out.is_contiguous()
-                    or pred_out.numel() != self.n * 3):
-                raise ValueError(f"pred_out must be contiguous float32 with {self.n * 3} elements on {self.device}")
+            self._check_tensor(pred_out, "pred_out", self.n * 3)
 
     def step(self, obs, rigid_target=None, pred_out=None, use_rigid=True):
         """One rollout step in place on ``obs`` [k, N, D]; rigid_target: [N_rigid, 3] scripted pose or None."""
@@ -325,20 +308,11 @@ class RolloutEngine:
 
     def _training_model(self):
         """(gm_model handle, its parameter tensors, their pointer array, descriptor) of the model as the training entry points run
-        it: the module's own at a hidden size of 64 / 128 / 256, the zero-padded one otherwise (EncProcDecGNN._padded_training).
-        The parameters are constants here."""
-        from .epd_gnn import TRAIN_WIDTHS
-        m = self.model
-        params = [p.detach() for p in m.parameters()]
-        if m.dims[3] in TRAIN_WIDTHS:
-            desc_t, tensors, h = m.model_desc(), params, m.device_handle(self.device)
-        else:
-            with torch.no_grad():
-                (desc_t, handle), tensors = m._padded_training(params)
-            h = handle.get(desc_t, tensors, self.device, tuple(params))
-        tensors = [t.to(device=self.device, dtype=torch.float32).contiguous() for t in tensors]
-        t_arr = (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
-        return h, tensors, t_arr, ModelDesc(*desc_t)
+        it (``EncProcDecGNN._training_spec``).  The parameters are constants here."""
+        with torch.no_grad():
+            desc_t, handle, tensors, key = self.model._training_spec([p.detach() for p in self.model.parameters()])
+        h = handle.get(desc_t, tensors, self.device, key)
+        return (h,) + _device_arrays(tensors, self.device) + (ModelDesc(*desc_t),)
 
     def _backward_ws(self, mdesc):
         """The reverse sweep's workspace (the step's is its head): sized by n and max_neighbours, allocated at first use."""
@@ -349,16 +323,12 @@ class RolloutEngine:
             self._bwd_ws = _ws(need, self.device)
         return self._bwd_ws
 
-    def _check_grad(self, g, name):
-        if not (isinstance(g, torch.Tensor) and g.device == self.device and g.dtype == torch.float32 and g.is_contiguous()
-                and tuple(g.shape) == (self.k, self.n, self.data_dim)):
-            raise ValueError(f"{name} must be contiguous float32 [{self.k}, {self.n}, {self.data_dim}] on {self.device}")
-
     def _check_param_grads(self, grads, tensors):
-        if len(grads) != len(tensors) or any(not (isinstance(g, torch.Tensor) and g.device == self.device and g.dtype == torch.float32
-                                                  and g.is_contiguous() and g.shape == t.shape) for g, t in zip(grads, tensors)):
-            raise ValueError(f"grads must be {len(tensors)} contiguous float32 tensors on {self.device} shaped like the training model's")
-        return (C.c_void_p * len(grads))(*[g.data_ptr() for g in grads])
+        if len(grads) != len(tensors):
+            raise ValueError(f"grads must be {len(tensors)} tensors shaped like the training model's, got {len(grads)}")
+        for g, t in zip(grads, tensors):
+            self._check_tensor(g, "each of grads", t.shape)
+        return _pointers(grads)
 
     def step_backward(self, obs_before, rigid_target, d_obs_after, return_edge_count=False, d_record=None, grads=None):
         """The vector-Jacobian product of one ``step`` inside the library (gm_rollout_step_backward_train): (d_obs_before [k, N, D],
@@ -372,10 +342,9 @@ class RolloutEngine:
         (hidden sizes 64 / 128 / 256; like ``_training_model``'s padded tensors otherwise), which the parameter gradients are
         ACCUMULATED into: the caller zeroes them.  The two returned gradients have the same bits with and without ``grads``."""
         self._check_state(obs_before, rigid_target, None, True)
-        self._check_grad(d_obs_after, "d_obs_after")
-        if d_record is not None and not (isinstance(d_record, torch.Tensor) and d_record.device == self.device and d_record.dtype == torch.float32
-                                         and d_record.is_contiguous() and tuple(d_record.shape) == (self.n, self.data_dim)):
-            raise ValueError(f"d_record must be contiguous float32 [{self.n}, {self.data_dim}] on {self.device}")
+        self._check_tensor(d_obs_after, "d_obs_after", (self.k, self.n, self.data_dim))
+        if d_record is not None:
+            self._check_tensor(d_record, "d_record", (self.n, self.data_dim))
         h, tensors, t_arr, mdesc = self._training_model()
         g_arr = None if grads is None else self._check_param_grads(grads, tensors)
         ws = self._backward_ws(mdesc)
@@ -389,22 +358,16 @@ class RolloutEngine:
 
     def _sweep_backward(self, windows, traj, steps, d_final, scene, need_traj, d_records=None, model=None, grads=None):
         """gm_rollout_backward_train on the windows a forward kept: (d_obs0, d_trajectory or None).  d_records: [steps, N, D] or
-        None.  model: (handle, descriptor, tensors) of the training model the sweep runs, None for ``_training_model()``'s; grads:
-        tensors shaped like its tensors that the parameter gradients are accumulated into, or None."""
+        None.  model: the training model the sweep runs, as ``_training_model()`` returns it -- None for that one; grads: tensors
+        shaped like its tensors that the parameter gradients are accumulated into, or None."""
         rank, n_rigid = scene
-        self._check_grad(d_final, "d_final")
-        if traj is not None and (tuple(traj.shape[1:]) != (n_rigid, 3) or traj.dtype != torch.float32 or not traj.is_contiguous()):
-            raise ValueError(f"trajectory must be contiguous float32 [T, {n_rigid}, 3], got {tuple(traj.shape)}")
-        if tuple(windows.shape) != (steps, self.k, self.n, self.data_dim) or not windows.is_contiguous():
-            raise ValueError(f"windows must be contiguous [{steps}, {self.k}, {self.n}, {self.data_dim}], got {tuple(windows.shape)}")
-        if d_records is not None and (tuple(d_records.shape) != (steps, self.n, self.data_dim) or d_records.dtype != torch.float32
-                                      or d_records.device != self.device or not d_records.is_contiguous()):
-            raise ValueError(f"d_records must be contiguous float32 [{steps}, {self.n}, {self.data_dim}], got {tuple(d_records.shape)}")
-        if model is None:
-            h, tensors, t_arr, mdesc = self._training_model()
-        else:
-            h, mdesc, tensors = model
-            t_arr = (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+        self._check_tensor(d_final, "d_final", (self.k, self.n, self.data_dim))
+        if traj is not None:
+            self._check_tensor(traj, "trajectory", ("T", n_rigid, 3))
+        self._check_tensor(windows, "windows", (steps, self.k, self.n, self.data_dim))
+        if d_records is not None:
+            self._check_tensor(d_records, "d_records", (steps, self.n, self.data_dim))
+        h, tensors, t_arr, mdesc = self._training_model() if model is None else model
         g_arr = None if grads is None else self._check_param_grads(grads, tensors)
         ws = self._backward_ws(mdesc)
         d_obs0 = torch.empty_like(d_final)
@@ -459,24 +422,13 @@ class RolloutEngine:
         steps = int(horizon) if horizon is not None else (int(trajectory.shape[0]) if trajectory is not None else 0)
         self._check_state(obs0, None, None, False)
         if trajectory is not None:
-            if (trajectory.device != self.device or trajectory.dim() != 3 or int(trajectory.shape[0]) < steps
-                    or int(trajectory.shape[2]) != 3):
-                raise ValueError(f"trajectory must be [T >= {steps}, N_rigid, 3] on {self.device}, got {tuple(trajectory.shape)}")
-        if sweep == "library" and (record or params):
-            model, tensors = None, ()
-            if params:
-                from .epd_gnn import TRAIN_WIDTHS
-                m = self.model
-                own = list(m.parameters())
-                if m.dims[3] in TRAIN_WIDTHS:
-                    desc_t, tensors, h = m.model_desc(), own, m.device_handle(self.device)
-                else:   # the padded tensors are functions of the parameters: autograd takes the gradients back through them
-                    (desc_t, handle), tensors = m._padded_training(own)
-                    h = handle.get(desc_t, tensors, self.device, tuple(own))
-                model = (h, ModelDesc(*desc_t))
-            return _RolloutTrainFunction.apply(self, obs0, trajectory, steps, bool(record), model, *tensors)
+            self._check_tensor(trajectory, "trajectory", (f"T >= {steps}", "N_rigid", 3), converted=True, min_rows=steps)
         if sweep == "library":
-            return _RolloutLibraryFunction.apply(self, obs0, trajectory, steps)
+            model, tensors = None, ()
+            if params:   # the LIVE parameters: padded tensors are functions of them, and autograd takes the gradients back through those
+                desc_t, handle, tensors, key = self.model._training_spec(list(self.model.parameters()))
+                model = (handle.get(desc_t, tensors, self.device, key), ModelDesc(*desc_t))
+            return _RolloutTrainFunction.apply(self, obs0, trajectory, steps, bool(record), model, *tensors)
         edges = [] if return_edges else None
         out = _RolloutFunction.apply(self, obs0, trajectory, steps, edges)
         return (out, edges) if return_edges else out
@@ -495,9 +447,7 @@ class RolloutEngine:
         steps = T if steps is None else int(steps)
         self._check_state(obs, None, None, True)
         if trajectory is not None:
-            if (trajectory.device != self.device or trajectory.dtype != torch.float32 or not trajectory.is_contiguous()
-                    or tuple(trajectory.shape[1:]) != (self.n_rigid, 3)):
-                raise ValueError(f"trajectory must be contiguous float32 [T, {self.n_rigid}, 3] on {self.device}, got {tuple(trajectory.shape)}")
+            self._check_tensor(trajectory, "trajectory", ("T", self.n_rigid, 3))
         recs = torch.empty((steps, self.n, self.data_dim), dtype=torch.float32, device=self.device) if record else None
         handle = self.model.device_handle(self.device)  # resolved once per rollout
         L = lib()

@@ -96,16 +96,12 @@ def _both_backwards(m, nodes, ea, ei, w, dev):
     """gm_epd_forward_train once, then gm_epd_backward_inputs and gm_epd_backward_inputs_only on that tape (the second on a copy
     taken before the first ran, in a workspace filled with NaN bytes): ((d_nodes, d_edge_attr) of each, parameter gradient views)."""
     from gnn_manip_amd._lib import ModelDesc, check, current_stream, lib, ptr
-    from gnn_manip_amd.epd_gnn import TRAIN_WIDTHS, _grad_arrays
+    from gnn_manip_amd.epd_gnn import _grad_arrays
     from gnn_manip_amd.graph import _ws
     L = lib()
-    params = list(m.parameters())
     with torch.no_grad():
-        if m.dims[3] in TRAIN_WIDTHS:
-            desc_t, tensors, h = m.model_desc(), [p.detach() for p in params], m.device_handle(dev)
-        else:
-            (desc_t, handle), tensors = m._padded_training(params)
-            h = handle.get(desc_t, tensors, dev, tuple(params))
+        desc_t, handle, tensors, key = m._training_spec([p.detach() for p in m.parameters()])
+    h = handle.get(desc_t, tensors, dev, key)
     d = C.byref(ModelDesc(*desc_t))
     x, a, idx, go = _t(nodes, dev), _t(ea, dev), _t(ei, dev), _t(w, dev)
     n, e = x.shape[0], a.shape[0]
