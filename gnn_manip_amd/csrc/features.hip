@@ -1,16 +1,9 @@
-// Per-step featurisation, integrator, rollout state update and the scripted rigid-body pose.
-// All float32 element-wise work; operations are written with the _rn intrinsics so that no
-// multiply-add is contracted: the results are bit-identical to the reference's separate torch
-// ops wherever the reference's own op order is defined.
+// Per-step featurisation, integrator, rollout state update and the scripted rigid-body pose.  The formulas of one row are
+// step_rows.h's; the kernels here are their stand-alone and fused launches, the transposes and the host entry points.
 #include "common.h"
+#include "step_rows.h"
 
 namespace gm {
-
-struct FeatParams {
-    int k, D, cart, mat, ctrl;
-    float r;
-    float vm[3], vs[3], am[3], as[3], lo[3], hi[3];
-};
 
 static int to_params(const gm_feature_desc* d, FeatParams* p, const char* who) {
     GM_REQUIRE(d != nullptr, GM_ERR_INVALID_ARGUMENT, "%s: null feature descriptor", who);
@@ -30,61 +23,29 @@ static int to_params(const gm_feature_desc* d, FeatParams* p, const char* who) {
     return GM_OK;
 }
 
-// collate_utils.py:217-232 (control) / 195-208; velocities per utils.py:27-40
+// one thread per row, 256 per workgroup
+template <class Kernel, class... Args>
+static int launch_rows(Kernel kernel, int64_t rows, hipStream_t s, Args... args) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)cdiv(rows, 256)), dim3(256), 0, s, args...);
+    GM_LAUNCH_CHECK();
+    return GM_OK;
+}
+
 __global__ void __launch_bounds__(256) node_features_kernel(const float* __restrict__ obs, int64_t n, FeatParams P,
                                                              float* __restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const int F = 3 * (P.k - 1) + 7 + (P.ctrl >= 0 ? 3 : 0);
-    float* o = out + i * F;
-    const int64_t fs = n * P.D;  // frame stride
-    const float* row = obs + i * P.D;
-    float prev[3], cur[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) prev[a] = row[P.cart + a];
-    for (int t = 1; t < P.k; ++t) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            cur[a] = row[t * fs + P.cart + a];
-            o[(t - 1) * 3 + a] = __fdiv_rn(__fsub_rn(__fsub_rn(cur[a], prev[a]), P.vm[a]), P.vs[a]);
-            prev[a] = cur[a];
-        }
-    }
-    float* b = o + 3 * (P.k - 1);
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        float l = __fdiv_rn(__fsub_rn(cur[a], P.lo[a]), P.r);
-        float u = __fdiv_rn(__fsub_rn(P.hi[a], cur[a]), P.r);
-        b[a] = fminf(fmaxf(l, -1.f), 1.f);
-        b[3 + a] = fminf(fmaxf(u, -1.f), 1.f);
-    }
-    const float* last = row + (int64_t)(P.k - 1) * fs;
-    b[6] = last[P.mat];
-    if (P.ctrl >= 0) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) b[7 + a] = __fdiv_rn(__fsub_rn(last[P.ctrl + a], P.vm[a]), P.vs[a]);
-    }
+    node_features_row(obs + i * P.D, n * P.D, P, out + i * node_feature_dim(P.k, P.ctrl));
 }
 
-__device__ __forceinline__ void edge_feat(const float* __restrict__ pos, int64_t stride, int64_t s, int64_t r, float cr,
-                                          float* __restrict__ o) {
-    float d[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) d[a] = __fdiv_rn(__fsub_rn(pos[s * stride + a], pos[r * stride + a]), cr);
-    float q = __fmul_rn(d[0], d[0]);
-    q = __fadd_rn(q, __fmul_rn(d[1], d[1]));
-    q = __fadd_rn(q, __fmul_rn(d[2], d[2]));
-    *reinterpret_cast<float4*>(o) = make_float4(d[0], d[1], d[2], __fsqrt_rn(q));
-}
-
-// utils.py:43-61, reference edge order
+// reference edge order
 __global__ void __launch_bounds__(256) edge_features_kernel(const float* __restrict__ pos, int64_t stride,
                                                              const int64_t* __restrict__ snd,
                                                              const int64_t* __restrict__ rcv, int64_t e, float cr,
                                                              float* __restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= e) return;
-    edge_feat(pos, stride, snd[i], rcv[i], cr, out + i * 4);
+    *reinterpret_cast<float4*>(out + i * 4) = edge_feature(pos + snd[i] * stride, pos + rcv[i] * stride, cr);
 }
 
 // same values, destination-sorted order.  The feature is (p_sender - p_receiver) / r with sender = edge_index[0]: that is
@@ -95,25 +56,20 @@ __global__ void __launch_bounds__(256) edge_features_csr_kernel(const float* __r
                                                                  float cr, float* __restrict__ out) {
     const int e = hdr->n_edges;
     const bool swap = hdr->flow != 0;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < e; i += (int64_t)gridDim.x * blockDim.x)
-        edge_feat(pos, stride, swap ? dst[i] : src[i], swap ? src[i] : dst[i], cr, out + i * 4);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < e; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t s = swap ? dst[i] : src[i], r = swap ? src[i] : dst[i];
+        *reinterpret_cast<float4*>(out + i * 4) = edge_feature(pos + s * stride, pos + r * stride, cr);
+    }
 }
 
-// rollout_utils.py:145-158
 __global__ void __launch_bounds__(256) integrate_kernel(const float* __restrict__ pred, const float* __restrict__ obs,
                                                          int64_t n, FeatParams P, float* __restrict__ next_pos) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const int64_t fs = n * P.D;
     const float* l1 = obs + (int64_t)(P.k - 1) * fs + i * P.D + P.cart;
-    const float* l2 = obs + (int64_t)(P.k - 2) * fs + i * P.D + P.cart;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        float acc = __fadd_rn(__fmul_rn(pred[i * 3 + a], P.as[a]), P.am[a]);
-        float lv = __fsub_rn(l1[a], l2[a]);
-        float v = __fadd_rn(lv, acc);
-        next_pos[i * 3 + a] = __fadd_rn(l1[a], v);
-    }
+    const float3 nxt = integrate_row(l1, l1 - fs, pred + i * 3, P);
+    next_pos[i * 3] = nxt.x; next_pos[i * 3 + 1] = nxt.y; next_pos[i * 3 + 2] = nxt.z;
 }
 
 // rollout step, fused: state_pre + node features (one thread owns row i of every frame) -- and, as the step's first launch, the
@@ -126,43 +82,11 @@ __global__ void __launch_bounds__(256) pre_features_kernel(float* __restrict__ o
     if (i >= n) return;
     const int64_t fs = n * P.D;
     float* row = obs + i * P.D;
-    float* last = row + (int64_t)(P.k - 1) * fs;
     if (rank && P.ctrl >= 0) {
         const int rk = rank[i];
-        if (rk >= 0) {
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                const float cur = last[P.cart + a];
-                last[P.ctrl + a] = target ? __fsub_rn(target[(int64_t)rk * 3 + a], cur) : cur;
-            }
-        }
+        if (rk >= 0) control_overwrite_row(row + (int64_t)(P.k - 1) * fs, P, target ? target + (int64_t)rk * 3 : nullptr);
     }
-    const int F = 3 * (P.k - 1) + 7 + (P.ctrl >= 0 ? 3 : 0);
-    float* o = out + i * F;
-    float prev[3], cur[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) prev[a] = row[P.cart + a];
-    for (int t = 1; t < P.k; ++t) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            cur[a] = row[t * fs + P.cart + a];
-            o[(t - 1) * 3 + a] = __fdiv_rn(__fsub_rn(__fsub_rn(cur[a], prev[a]), P.vm[a]), P.vs[a]);
-            prev[a] = cur[a];
-        }
-    }
-    float* b = o + 3 * (P.k - 1);
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        float l = __fdiv_rn(__fsub_rn(cur[a], P.lo[a]), P.r);
-        float u = __fdiv_rn(__fsub_rn(P.hi[a], cur[a]), P.r);
-        b[a] = fminf(fmaxf(l, -1.f), 1.f);
-        b[3 + a] = fminf(fmaxf(u, -1.f), 1.f);
-    }
-    b[6] = last[P.mat];
-    if (P.ctrl >= 0) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) b[7 + a] = __fdiv_rn(__fsub_rn(last[P.ctrl + a], P.vm[a]), P.vs[a]);
-    }
+    node_features_row(row, fs, P, out + i * node_feature_dim(P.k, P.ctrl));
 }
 
 // rollout step, fused: integrator + window shift + write-back (+ optional copy of the prediction)
@@ -174,27 +98,13 @@ __global__ void __launch_bounds__(256) integrate_post_kernel(float* __restrict__
     const int64_t fs = n * P.D;
     float* row = obs + i * P.D;
     const float* l1 = row + (int64_t)(P.k - 1) * fs + P.cart;
-    const float* l2 = row + (int64_t)(P.k - 2) * fs + P.cart;
-    float nxt[3];
+    if (pred_out) {
 #pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float pa = pred[i * 3 + a];
-        if (pred_out) pred_out[i * 3 + a] = pa;
-        const float acc = __fadd_rn(__fmul_rn(pa, P.as[a]), P.am[a]);
-        const float lv = __fsub_rn(l1[a], l2[a]);
-        nxt[a] = __fadd_rn(l1[a], __fadd_rn(lv, acc));
+        for (int a = 0; a < 3; ++a) pred_out[i * 3 + a] = pred[i * 3 + a];
     }
-    for (int t = 0; t + 1 < P.k; ++t)
-        for (int d = 0; d < P.D; ++d) row[t * fs + d] = row[(t + 1) * fs + d];
-    float* last = row + (int64_t)(P.k - 1) * fs;
+    const float3 nxt = integrate_row(l1, l1 - fs, pred + i * 3, P);
     const int rk = rank ? rank[i] : -1;
-    if (rk < 0) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) last[P.cart + a] = nxt[a];
-    } else if (target) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) last[P.cart + a] = target[(int64_t)rk * 3 + a];
-    }
+    shift_write_row(row, fs, P, rk, nxt, (rk >= 0 && target) ? target + (int64_t)rk * 3 : nullptr);
 }
 
 // rank of each rigid row (material == 1) among the rigid rows; one block, running carry
@@ -227,40 +137,24 @@ __global__ void __launch_bounds__(1024) rigid_rank_kernel(const float* __restric
     if (threadIdx.x == 0 && n_rigid) *n_rigid = carry_s;
 }
 
-// rollout_utils.py:40-47 / traj_utils.py:126-134
 __global__ void __launch_bounds__(256) state_pre_kernel(float* __restrict__ obs, int64_t n, FeatParams P,
                                                          const int* __restrict__ rank, const float* __restrict__ target) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const int rk = rank[i];
     if (rk < 0) return;
-    float* last = obs + (int64_t)(P.k - 1) * n * P.D + i * P.D;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        float cur = last[P.cart + a];
-        last[P.ctrl + a] = target ? __fsub_rn(target[(int64_t)rk * 3 + a], cur) : cur;
-    }
+    control_overwrite_row(obs + (int64_t)(P.k - 1) * n * P.D + i * P.D, P, target ? target + (int64_t)rk * 3 : nullptr);
 }
 
-// rollout_utils.py:53-61 / traj_utils.py:146-152
 __global__ void __launch_bounds__(256) state_post_kernel(float* __restrict__ obs, int64_t n, FeatParams P,
                                                           const float* __restrict__ next_pos,
                                                           const int* __restrict__ rank, const float* __restrict__ target) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const int64_t fs = n * P.D;
-    float* row = obs + i * P.D;
-    for (int t = 0; t + 1 < P.k; ++t)
-        for (int d = 0; d < P.D; ++d) row[t * fs + d] = row[(t + 1) * fs + d];
-    float* last = row + (int64_t)(P.k - 1) * fs;
     const int rk = rank ? rank[i] : -1;
-    if (rk < 0) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) last[P.cart + a] = next_pos[i * 3 + a];
-    } else if (target) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) last[P.cart + a] = target[(int64_t)rk * 3 + a];
-    }  // rigid row without a scripted pose keeps its pre-step row (traj_utils.py:150-152)
+    const float* np = next_pos + i * 3;
+    const float3 nxt = rk < 0 ? make_float3(np[0], np[1], np[2]) : make_float3(0.f, 0.f, 0.f);   // read for the rows that take it only
+    shift_write_row(obs + i * P.D, n * P.D, P, rk, nxt, (rk >= 0 && target) ? target + (int64_t)rk * 3 : nullptr);
 }
 
 // traj_utils.py:167-194: rotation about X in the cup frame with the y/z axis swap
@@ -343,16 +237,12 @@ __global__ void __launch_bounds__(256) renumber_scatter_kernel(const float* __re
 int renumber_gather(const float* in, float* out, int k, int64_t n, int D, const int* perm, const void* graph_ws, const int* total_in,
                     int* total_out, const int* rank_caller, int* rank_out, hipStream_t s) {
     if (n <= 0 || k <= 0) return GM_OK;
-    hipLaunchKernelGGL(renumber_gather_kernel, dim3((unsigned)cdiv((int64_t)k * n, 256)), dim3(256), 0, s, in, out, k, n, D, perm,
-                       static_cast<const GraphHeader*>(graph_ws), total_in, total_out, rank_caller, rank_out);
-    GM_LAUNCH_CHECK();
-    return GM_OK;
+    return launch_rows(renumber_gather_kernel, (int64_t)k * n, s, in, out, k, n, D, perm, static_cast<const GraphHeader*>(graph_ws), total_in,
+                       total_out, rank_caller, rank_out);
 }
 int renumber_scatter(const float* in, float* out, int frames, int64_t n, int D, const int* total, hipStream_t s) {
     if (n <= 0 || frames <= 0) return GM_OK;
-    hipLaunchKernelGGL(renumber_scatter_kernel, dim3((unsigned)cdiv((int64_t)frames * n, 256)), dim3(256), 0, s, in, out, frames, n, D, total);
-    GM_LAUNCH_CHECK();
-    return GM_OK;
+    return launch_rows(renumber_scatter_kernel, (int64_t)frames * n, s, in, out, frames, n, D, total);
 }
 
 int rollout_pre_features(float* obs, int64_t n, const gm_feature_desc* d, const int* rank, const float* target, float* out,
@@ -360,9 +250,7 @@ int rollout_pre_features(float* obs, int64_t n, const gm_feature_desc* d, const 
     FeatParams P;
     int rc = to_params(d, &P, "gm_rollout_step");
     if (rc != GM_OK) return rc;
-    hipLaunchKernelGGL(pre_features_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, s, obs, n, P, rank, target, out, clear ? *clear : StepClear{});
-    GM_LAUNCH_CHECK();
-    return GM_OK;
+    return launch_rows(pre_features_kernel, n, s, obs, n, P, rank, target, out, clear ? *clear : StepClear{});
 }
 
 int rollout_integrate_post(float* obs, int64_t n, const gm_feature_desc* d, const float* pred, const int* rank,
@@ -370,26 +258,28 @@ int rollout_integrate_post(float* obs, int64_t n, const gm_feature_desc* d, cons
     FeatParams P;
     int rc = to_params(d, &P, "gm_rollout_step");
     if (rc != GM_OK) return rc;
-    hipLaunchKernelGGL(integrate_post_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, s, obs, n, P, pred, rank, target, pred_out);
-    GM_LAUNCH_CHECK();
-    return GM_OK;
+    return launch_rows(integrate_post_kernel, n, s, obs, n, P, pred, rank, target, pred_out);
 }
 
 
 // ---- backward of the per-step functions (differentiable rollout step).  Each output is written in full, by one thread per row:
 // no atomics, the same bits every time.
 
+// zeros in one particle's row of every frame of a gradient window (row = its row of frame 0)
+__device__ __forceinline__ void zero_window_row(float* __restrict__ row, int64_t fs, const FeatParams& P) {
+    for (int t = 0; t < P.k; ++t)
+        for (int d = 0; d < P.D; ++d) row[t * fs + d] = 0.f;
+}
+
 // transpose of node_features_kernel: d_obs[k][n][D] from d_out[n][F]
 __global__ void __launch_bounds__(256) node_features_bwd_kernel(const float* __restrict__ obs, int64_t n, FeatParams P,
                                                                  const float* __restrict__ g, float* __restrict__ d_obs) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const int F = 3 * (P.k - 1) + 7 + (P.ctrl >= 0 ? 3 : 0);
-    const float* gi = g + i * F;
+    const float* gi = g + i * node_feature_dim(P.k, P.ctrl);
     const int64_t fs = n * P.D;
     float* row = d_obs + i * P.D;
-    for (int t = 0; t < P.k; ++t)
-        for (int d = 0; d < P.D; ++d) row[t * fs + d] = 0.f;
+    zero_window_row(row, fs, P);
     // velocity t (frames t, t + 1): +g / vel_std on frame t + 1, -g / vel_std on frame t
     for (int t = 0; t < P.k; ++t) {
 #pragma unroll
@@ -406,12 +296,11 @@ __global__ void __launch_bounds__(256) node_features_bwd_kernel(const float* __r
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         // the forward's own unclamped values; the gradient passes where they lie in [-1, 1] (torch.clamp's rule)
-        const float cur = last_in[P.cart + a];
-        const float l = __fdiv_rn(__fsub_rn(cur, P.lo[a]), P.r);
-        const float u = __fdiv_rn(__fsub_rn(P.hi[a], cur), P.r);
+        float l, u;
+        boundary_terms(last_in[P.cart + a], P, a, l, u);
         float v = last[P.cart + a];
-        if (l >= -1.f && l <= 1.f) v = __fadd_rn(v, __fdiv_rn(b[a], P.r));
-        if (u >= -1.f && u <= 1.f) v = __fsub_rn(v, __fdiv_rn(b[3 + a], P.r));
+        if (in_unit(l)) v = __fadd_rn(v, __fdiv_rn(b[a], P.r));
+        if (in_unit(u)) v = __fsub_rn(v, __fdiv_rn(b[3 + a], P.r));
         last[P.cart + a] = v;
     }
     if (P.ctrl >= 0) {
@@ -427,8 +316,7 @@ __global__ void __launch_bounds__(256) integrate_bwd_kernel(const float* __restr
     if (i >= n) return;
     const int64_t fs = n * P.D;
     float* row = d_obs + i * P.D;
-    for (int t = 0; t < P.k; ++t)
-        for (int d = 0; d < P.D; ++d) row[t * fs + d] = 0.f;
+    zero_window_row(row, fs, P);
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         const float ga = g[i * 3 + a];
@@ -552,19 +440,14 @@ __global__ void __launch_bounds__(256) edge_features_bwd_edge_kernel(const float
     const int64_t s = snd[i], r = rcv[i];
     float o[3] = {0.f, 0.f, 0.f};
     if (s >= 0 && s < n && r >= 0 && r < n) {
-        float d[3];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) d[a] = __fdiv_rn(__fsub_rn(pos[s * stride + a], pos[r * stride + a]), cr);
-        float q = __fmul_rn(d[0], d[0]);
-        q = __fadd_rn(q, __fmul_rn(d[1], d[1]));
-        q = __fadd_rn(q, __fmul_rn(d[2], d[2]));
-        const float nrm = __fsqrt_rn(q);
+        const float4 f = edge_feature(pos + s * stride, pos + r * stride, cr);   // the forward's (d, |d|)
+        const float d[3] = {f.x, f.y, f.z};
         const float4 gv = *reinterpret_cast<const float4*>(g + i * 4);
         const float gg[3] = {gv.x, gv.y, gv.z};
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
             float v = gg[a];
-            if (nrm > 0.f) v = __fadd_rn(v, __fdiv_rn(__fmul_rn(gv.w, d[a]), nrm));
+            if (f.w > 0.f) v = __fadd_rn(v, __fdiv_rn(__fmul_rn(gv.w, d[a]), f.w));
             o[a] = __fdiv_rn(v, cr);
         }
     }
@@ -621,10 +504,8 @@ int rollout_assemble_backward(const float* g_post, const float* g_int, const flo
     FeatParams P;
     int rc = to_params(d, &P, "gm_rollout_step_backward");
     if (rc != GM_OK) return rc;
-    hipLaunchKernelGGL(step_assemble_bwd_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, s, g_post, g_int, g_nodes, g_pos, t_post, g_rec, n,
-                       P, rank, has_target ? 1 : 0, (rank && P.ctrl >= 0) ? 1 : 0, d_before, d_target);
-    GM_LAUNCH_CHECK();
-    return GM_OK;
+    return launch_rows(step_assemble_bwd_kernel, n, s, g_post, g_int, g_nodes, g_pos, t_post, g_rec, n, P, rank, has_target ? 1 : 0,
+                       (rank && P.ctrl >= 0) ? 1 : 0, d_before, d_target);
 }
 
 }  // namespace gm
@@ -640,9 +521,7 @@ int gm_node_features(const float* obs, int64_t n, const gm_feature_desc* desc, f
     if (rc != GM_OK) return rc;
     GM_REQUIRE(n >= 0 && (n == 0 || (obs && out)), GM_ERR_INVALID_ARGUMENT, "gm_node_features: null pointer");
     if (n == 0) return GM_OK;
-    hipLaunchKernelGGL(node_features_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, obs, n, P, out);
-    GM_LAUNCH_CHECK();
-    return GM_OK;
+    return launch_rows(node_features_kernel, n, (hipStream_t)stream, obs, n, P, out);
 }
 
 int gm_edge_features(const float* pos, int64_t pos_stride, const int64_t* senders, const int64_t* receivers,
@@ -651,10 +530,7 @@ int gm_edge_features(const float* pos, int64_t pos_stride, const int64_t* sender
     GM_REQUIRE(e >= 0 && (e == 0 || (pos && senders && receivers && out)), GM_ERR_INVALID_ARGUMENT, "gm_edge_features: null pointer");
     GM_REQUIRE(conn_r > 0.f && pos_stride >= 3, GM_ERR_INVALID_ARGUMENT, "gm_edge_features: bad conn_r / stride");
     if (e == 0) return GM_OK;
-    hipLaunchKernelGGL(edge_features_kernel, dim3((unsigned)cdiv(e, 256)), dim3(256), 0, (hipStream_t)stream, pos,
-                       pos_stride, senders, receivers, e, conn_r, out);
-    GM_LAUNCH_CHECK();
-    return GM_OK;
+    return launch_rows(edge_features_kernel, e, (hipStream_t)stream, pos, pos_stride, senders, receivers, e, conn_r, out);
 }
 
 int gm_edge_features_csr(const float* pos, int64_t pos_stride, const void* csr_ws, int64_t n, int64_t cap,
@@ -680,9 +556,7 @@ int gm_integrate(const float* pred, const float* obs, int64_t n, const gm_featur
     if (rc != GM_OK) return rc;
     GM_REQUIRE(n >= 0 && (n == 0 || (pred && obs && next_pos)), GM_ERR_INVALID_ARGUMENT, "gm_integrate: null pointer");
     if (n == 0) return GM_OK;
-    hipLaunchKernelGGL(integrate_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, pred, obs, n, P, next_pos);
-    GM_LAUNCH_CHECK();
-    return GM_OK;
+    return launch_rows(integrate_kernel, n, (hipStream_t)stream, pred, obs, n, P, next_pos);
 }
 
 int gm_rigid_rank(const float* obs, int64_t n, const gm_feature_desc* desc, int32_t* rank, int32_t* n_rigid_dev,
@@ -706,9 +580,7 @@ int gm_state_pre(float* obs, int64_t n, const gm_feature_desc* desc, const int32
     GM_REQUIRE(P.ctrl >= 0, GM_ERR_INVALID_ARGUMENT, "gm_state_pre: descriptor has no control columns");
     GM_REQUIRE(n >= 0 && (n == 0 || (obs && rank)), GM_ERR_INVALID_ARGUMENT, "gm_state_pre: null pointer");
     if (n == 0) return GM_OK;
-    hipLaunchKernelGGL(state_pre_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, obs, n, P, rank, target);
-    GM_LAUNCH_CHECK();
-    return GM_OK;
+    return launch_rows(state_pre_kernel, n, (hipStream_t)stream, obs, n, P, rank, target);
 }
 
 int gm_state_post(float* obs, int64_t n, const gm_feature_desc* desc, const float* next_pos, const int32_t* rank,
@@ -719,10 +591,7 @@ int gm_state_post(float* obs, int64_t n, const gm_feature_desc* desc, const floa
     if (rc != GM_OK) return rc;
     GM_REQUIRE(n >= 0 && (n == 0 || (obs && next_pos)), GM_ERR_INVALID_ARGUMENT, "gm_state_post: null pointer");
     if (n == 0) return GM_OK;
-    hipLaunchKernelGGL(state_post_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, obs, n, P,
-                       next_pos, rank, target);
-    GM_LAUNCH_CHECK();
-    return GM_OK;
+    return launch_rows(state_post_kernel, n, (hipStream_t)stream, obs, n, P, next_pos, rank, target);
 }
 
 int gm_state_pre_backward(const float* d_obs_after, int64_t n, const gm_feature_desc* desc, const int32_t* rank, int has_target,
@@ -735,10 +604,7 @@ int gm_state_pre_backward(const float* d_obs_after, int64_t n, const gm_feature_
     GM_REQUIRE(n >= 0 && (n == 0 || (d_obs_after && d_obs_before && rank)), GM_ERR_INVALID_ARGUMENT, "gm_state_pre_backward: null pointer");
     GM_REQUIRE(d_obs_after != d_obs_before || n == 0, GM_ERR_INVALID_ARGUMENT, "gm_state_pre_backward: d_obs_before must not be d_obs_after");
     if (n == 0) return GM_OK;
-    hipLaunchKernelGGL(state_pre_bwd_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, d_obs_after, n, P, rank,
-                       has_target ? 1 : 0, d_obs_before, d_rigid_target);
-    GM_LAUNCH_CHECK();
-    return GM_OK;
+    return launch_rows(state_pre_bwd_kernel, n, (hipStream_t)stream, d_obs_after, n, P, rank, has_target ? 1 : 0, d_obs_before, d_rigid_target);
 }
 
 int gm_state_post_backward(const float* d_obs_after, int64_t n, const gm_feature_desc* desc, const int32_t* rank, int has_target,
@@ -751,10 +617,8 @@ int gm_state_post_backward(const float* d_obs_after, int64_t n, const gm_feature
                "gm_state_post_backward: null pointer");
     GM_REQUIRE(d_obs_after != d_obs_before || n == 0, GM_ERR_INVALID_ARGUMENT, "gm_state_post_backward: d_obs_before must not be d_obs_after");
     if (n == 0) return GM_OK;
-    hipLaunchKernelGGL(state_post_bwd_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, d_obs_after, n, P, rank,
-                       has_target ? 1 : 0, d_obs_before, d_next_pos, d_rigid_target);
-    GM_LAUNCH_CHECK();
-    return GM_OK;
+    return launch_rows(state_post_bwd_kernel, n, (hipStream_t)stream, d_obs_after, n, P, rank, has_target ? 1 : 0, d_obs_before, d_next_pos,
+                       d_rigid_target);
 }
 
 int gm_rigid_transform(const float* rigid_init, int64_t nr, const float* cst, int64_t steps, const float ty_init[3],
@@ -763,10 +627,7 @@ int gm_rigid_transform(const float* rigid_init, int64_t nr, const float* cst, in
     GM_REQUIRE(nr >= 0 && steps >= 0 && ty_init, GM_ERR_INVALID_ARGUMENT, "gm_rigid_transform: bad sizes");
     if (nr == 0 || steps == 0) return GM_OK;
     GM_REQUIRE(rigid_init && cst && out, GM_ERR_INVALID_ARGUMENT, "gm_rigid_transform: null pointer");
-    hipLaunchKernelGGL(rigid_transform_kernel, dim3((unsigned)cdiv(nr * steps, 256)), dim3(256), 0, (hipStream_t)stream,
-                       rigid_init, nr, cst, steps, ty_init[0], ty_init[1], ty_init[2], out);
-    GM_LAUNCH_CHECK();
-    return GM_OK;
+    return launch_rows(rigid_transform_kernel, nr * steps, (hipStream_t)stream, rigid_init, nr, cst, steps, ty_init[0], ty_init[1], ty_init[2], out);
 }
 
 
@@ -814,10 +675,7 @@ int gm_edge_features_backward(const float* pos, int64_t pos_stride, const int64_
     if (rc == GM_OK) rc = gm::csr_from_edge_index(w.ei, n, e, 1, w.csr_snd, w.csr_bytes, false, s);
     if (rc != GM_OK) return rc;
     const CsrWs cr = carve_csr(w.csr_rcv, n, e), cs = carve_csr(w.csr_snd, n, e);
-    hipLaunchKernelGGL(edge_features_bwd_node_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, s, cs.in_ptr, cs.eid, cr.in_ptr, cr.eid,
-                       w.ge, n, d_pos);
-    GM_LAUNCH_CHECK();
-    return GM_OK;
+    return launch_rows(edge_features_bwd_node_kernel, n, s, cs.in_ptr, cs.eid, cr.in_ptr, cr.eid, w.ge, n, d_pos);
 }
 
 int gm_node_features_backward(const float* obs, int64_t n, const gm_feature_desc* desc, const float* d_out, float* d_obs, void* stream) {
@@ -827,9 +685,7 @@ int gm_node_features_backward(const float* obs, int64_t n, const gm_feature_desc
     if (rc != GM_OK) return rc;
     GM_REQUIRE(n >= 0 && (n == 0 || (obs && d_out && d_obs)), GM_ERR_INVALID_ARGUMENT, "gm_node_features_backward: null pointer");
     if (n == 0) return GM_OK;
-    hipLaunchKernelGGL(node_features_bwd_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, obs, n, P, d_out, d_obs);
-    GM_LAUNCH_CHECK();
-    return GM_OK;
+    return launch_rows(node_features_bwd_kernel, n, (hipStream_t)stream, obs, n, P, d_out, d_obs);
 }
 
 int gm_integrate_backward(const float* d_next_pos, int64_t n, const gm_feature_desc* desc, float* d_pred, float* d_obs, void* stream) {
@@ -839,9 +695,7 @@ int gm_integrate_backward(const float* d_next_pos, int64_t n, const gm_feature_d
     if (rc != GM_OK) return rc;
     GM_REQUIRE(n >= 0 && (n == 0 || (d_next_pos && d_pred && d_obs)), GM_ERR_INVALID_ARGUMENT, "gm_integrate_backward: null pointer");
     if (n == 0) return GM_OK;
-    hipLaunchKernelGGL(integrate_bwd_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, d_next_pos, n, P, d_pred, d_obs);
-    GM_LAUNCH_CHECK();
-    return GM_OK;
+    return launch_rows(integrate_bwd_kernel, n, (hipStream_t)stream, d_next_pos, n, P, d_pred, d_obs);
 }
 
 }  // extern "C"

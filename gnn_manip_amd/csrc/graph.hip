@@ -9,6 +9,7 @@
 #include "common.h"
 #include "hedge.h"
 #include "blocks_dev.h"
+#include "step_rows.h"
 
 namespace gm {
 
@@ -445,6 +446,48 @@ constexpr int NB_CAP = 96;
 constexpr int NB_STRIDE = NB_CAP + 1;  // doubles per list: odd stride keeps the groups of a wave on distinct banks
 constexpr int NB_QPB = 256 / NB_LPQ;   // queries per 256-thread block
 
+// A query of the neighbour search, from its entry of `sorted`: its index, its position in float64, and the cells its candidates lie
+// in -- the 3 x 3 rows (z0..z1, y0..y1) around its own cell, clamped to the grid of its graph (cells from cbase), each row one run
+// of cell_start from cell x0 to cell x1
+struct Query {
+    int qi;
+    double x, y, z;
+    int cbase, dx, dy, x0, x1, y0, y1, z0, z1;
+    __device__ __forceinline__ void row_range(const int* __restrict__ cell_start, int zc, int yc, int& b, int& e) const {
+        const int row = cbase + (zc * dy + yc) * dx;
+        b = cell_start[row + x0];
+        e = cell_start[row + x1 + 1];
+    }
+};
+__device__ __forceinline__ Query decode_query(const float4 q, const GraphHeader* __restrict__ hdr) {
+    Query Q;
+    Q.qi = __float_as_int(q.w);
+    Q.dx = hdr->dims[0];
+    Q.dy = hdr->dims[1];
+    const int dz = hdr->dims[2];
+    const double inv_h = hdr->inv_h;
+    const int cx = cell_coord(q.x, hdr->origin[0], inv_h, Q.dx);
+    const int cy = cell_coord(q.y, hdr->origin[1], inv_h, Q.dy);
+    const int cz = cell_coord(q.z, hdr->origin[2], inv_h, dz);
+    Q.x = (double)q.x; Q.y = (double)q.y; Q.z = (double)q.z;
+    Q.cbase = (Q.qi / hdr->n_per_graph) * hdr->ncells_local;  // this graph's block of cells
+    Q.x0 = max(cx - 1, 0); Q.x1 = min(cx + 1, Q.dx - 1);
+    Q.y0 = max(cy - 1, 0); Q.y1 = min(cy + 1, Q.dy - 1);
+    Q.z0 = max(cz - 1, 0); Q.z1 = min(cz + 1, dz - 1);
+    return Q;
+}
+// Squared distance of a candidate to the query: float64, accumulated x -> y -> z (utils.py:76-78 via sklearn rdist).  Every product
+// of float32-origin differences is exact in float64, the two additions round -- so the order is part of the result, and the
+// d2 <= r * r test and the (d2, index) ranking of both kernels must see the same one.
+__device__ __forceinline__ double query_dist2(const Query& Q, const float4 p) {
+    double d = Q.x - (double)p.x;
+    double d2 = __dmul_rn(d, d);
+    d = Q.y - (double)p.y;
+    d2 = __dadd_rn(d2, __dmul_rn(d, d));
+    d = Q.z - (double)p.z;
+    return __dadd_rn(d2, __dmul_rn(d, d));
+}
+
 // indeg / arrival (optional: the rollout step's fused path): the counting pass of the destination sort rides along -- every kept
 // neighbour takes its arrival number within its aggregation node's segment (flow 0: the neighbour, 1: the query) from an atomic on
 // indeg[], so that the fill pass places the edge with plain stores (see indeg_graph_kernel, the stand-alone form of the same count).
@@ -459,24 +502,16 @@ __global__ void __launch_bounds__(256) neighbor_fast_kernel(const float4* __rest
     const int grp_shift = (lane / NB_LPQ) * NB_LPQ;  // position of this group's bits in the wave ballot
     const int64_t slot = (int64_t)blockIdx.x * NB_QPB + ql;
     const bool active = slot < n;
-    const float4 q = sorted[active ? slot : 0];
-    const int qi = __float_as_int(q.w);
-    const int dx = hdr->dims[0], dy = hdr->dims[1], dz = hdr->dims[2];
-    const double inv_h = hdr->inv_h;
-    const int cx = cell_coord(q.x, hdr->origin[0], inv_h, dx);
-    const int cy = cell_coord(q.y, hdr->origin[1], inv_h, dy);
-    const int cz = cell_coord(q.z, hdr->origin[2], inv_h, dz);
-    const double qx = (double)q.x, qy = (double)q.y, qz = (double)q.z;
-    const int cbase = (qi / hdr->n_per_graph) * hdr->ncells_local;  // this graph's block of cells
+    const Query Q = decode_query(sorted[active ? slot : 0], hdr);
+    const int qi = Q.qi;
     double* ld = sd2 + ql * NB_STRIDE;
     int* lj = sj + ql * NB_STRIDE;
     int count = 0;  // group-uniform
-    const int x0 = max(cx - 1, 0), x1 = min(cx + 1, dx - 1);
     if (active) {
-        for (int z = max(cz - 1, 0); z <= min(cz + 1, dz - 1); ++z) {
-            for (int y = max(cy - 1, 0); y <= min(cy + 1, dy - 1); ++y) {
-                const int row = cbase + (z * dy + y) * dx;
-                const int b = cell_start[row + x0], e = cell_start[row + x1 + 1];
+        for (int z = Q.z0; z <= Q.z1; ++z) {
+            for (int y = Q.y0; y <= Q.y1; ++y) {
+                int b, e;
+                Q.row_range(cell_start, z, y, b, e);
                 for (int c0 = b; c0 < e; c0 += NB_LPQ) {
                     const int c = c0 + sub;
                     bool in = false;
@@ -484,12 +519,7 @@ __global__ void __launch_bounds__(256) neighbor_fast_kernel(const float4* __rest
                     int j = 0;
                     if (c < e) {
                         const float4 p = sorted[c];
-                        double d = qx - (double)p.x;
-                        d2 = __dmul_rn(d, d);
-                        d = qy - (double)p.y;
-                        d2 = __dadd_rn(d2, __dmul_rn(d, d));
-                        d = qz - (double)p.z;
-                        d2 = __dadd_rn(d2, __dmul_rn(d, d));
+                        d2 = query_dist2(Q, p);
                         in = d2 <= r2;
                         j = __float_as_int(p.w);
                     }
@@ -555,31 +585,17 @@ __global__ void __launch_bounds__(BS) neighbor_kernel(const float4* __restrict__
     const int64_t slot = (int64_t)blockIdx.x * BS + t;
     if (slot >= n) return;
     const float4 q = sorted[slot];
-    const int qi = __float_as_int(q.w);
-    if (cnt[qi] != -1) return;  // done by neighbor_fast_kernel
-    const int cbase = (qi / hdr->n_per_graph) * hdr->ncells_local;
-    const int dx = hdr->dims[0], dy = hdr->dims[1], dz = hdr->dims[2];
-    const double inv_h = hdr->inv_h;
-    const int cx = cell_coord(q.x, hdr->origin[0], inv_h, dx);
-    const int cy = cell_coord(q.y, hdr->origin[1], inv_h, dy);
-    const int cz = cell_coord(q.z, hdr->origin[2], inv_h, dz);
-    const double qx = (double)q.x, qy = (double)q.y, qz = (double)q.z;
+    if (cnt[__float_as_int(q.w)] != -1) return;  // done by neighbor_fast_kernel
+    const Query Q = decode_query(q, hdr);
+    const int qi = Q.qi;
     int kept = 0;
-    const int x0 = max(cx - 1, 0), x1 = min(cx + 1, dx - 1);
-    for (int z = max(cz - 1, 0); z <= min(cz + 1, dz - 1); ++z) {
-        for (int y = max(cy - 1, 0); y <= min(cy + 1, dy - 1); ++y) {
-            const int row = cbase + (z * dy + y) * dx;
-            const int b = cell_start[row + x0], e = cell_start[row + x1 + 1];
+    for (int z = Q.z0; z <= Q.z1; ++z) {
+        for (int y = Q.y0; y <= Q.y1; ++y) {
+            int b, e;
+            Q.row_range(cell_start, z, y, b, e);
             for (int c = b; c < e; ++c) {
                 const float4 p = sorted[c];
-                // float64, accumulated x -> y -> z (utils.py:76-78 via sklearn rdist); every
-                // product of float32-origin differences is exact in float64.
-                double d = qx - (double)p.x;
-                double d2 = __dmul_rn(d, d);
-                d = qy - (double)p.y;
-                d2 = __dadd_rn(d2, __dmul_rn(d, d));
-                d = qz - (double)p.z;
-                d2 = __dadd_rn(d2, __dmul_rn(d, d));
+                const double d2 = query_dist2(Q, p);
                 if (!(d2 <= r2)) continue;
                 const int j = __float_as_int(p.w);
                 int pos;
@@ -612,15 +628,21 @@ __global__ void __launch_bounds__(BS) neighbor_kernel(const float4* __restrict__
     }
 }
 
+// Slot `id` of the [n][K] neighbour table: its query i and its place s in the query's list; false past the table or past the list
+__device__ __forceinline__ bool decode_slot(int64_t id, int64_t n, int K, const int* __restrict__ cnt, int64_t& i, int& s) {
+    if (id >= n * K) return false;
+    i = id / K;
+    s = (int)(id - i * K);
+    return s < cnt[i];
+}
+
 __global__ void __launch_bounds__(256) emit_edges_kernel(const int* __restrict__ cnt, const int* __restrict__ out_ptr,
                                                           const int* __restrict__ nbr, int64_t n, int K,
                                                           int64_t capacity, int64_t* __restrict__ senders,
                                                           int64_t* __restrict__ receivers) {
-    int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (id >= n * K) return;
-    int64_t i = id / K;
-    int s = (int)(id - i * K);
-    if (s >= cnt[i]) return;
+    int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, i;
+    int s;
+    if (!decode_slot(id, n, K, cnt, i, s)) return;
     int64_t e = (int64_t)out_ptr[i] + s;
     if (e >= capacity) return;
     senders[e] = i;
@@ -636,10 +658,9 @@ __global__ void __launch_bounds__(256) emit_edges_kernel(const int* __restrict__
 // edge with plain stores: one atomic per edge instead of two.  (The arrival order is arbitrary; segment_sort_kernel fixes the order.)
 __global__ void __launch_bounds__(256) indeg_graph_kernel(const int* __restrict__ cnt, const int* __restrict__ nbr,
                                                            int64_t n, int K, int flow, int* __restrict__ indeg, int* __restrict__ slot) {
-    int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (id >= n * K) return;
-    int64_t i = id / K;
-    if ((int)(id - i * K) >= cnt[i]) return;
+    int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, i;
+    int s;
+    if (!decode_slot(id, n, K, cnt, i, s)) return;
     slot[id] = atomicAdd(&indeg[flow ? (int)i : nbr[id]], 1);
 }
 
@@ -651,12 +672,10 @@ __global__ void __launch_bounds__(256) fill_graph_kernel(const int* __restrict__
                                                           int64_t cap, int flow, int* __restrict__ dst, int* __restrict__ src,
                                                           int* __restrict__ eid, CsrHeader* hdr, const int* n_per_dev,
                                                           EdgeBlockHeader* tab, int* gblk) {
-    int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, i;
+    int s;
     if (id == 0 && tab) edge_blocks_plan(in_ptr, (int)n, n_per_dev, 0, tab, gblk, (int)n + 1);
-    if (id >= n * K) return;
-    int64_t i = id / K;
-    int s = (int)(id - i * K);
-    if (s >= cnt[i]) return;
+    if (!decode_slot(id, n, K, cnt, i, s)) return;
     const int d = flow ? (int)i : nbr[id];
     int p = in_ptr[d] + slot[id];
     if (p >= cap) { atomicOr(&hdr->error_flags, ERRF_CAPACITY); return; }
@@ -666,12 +685,19 @@ __global__ void __launch_bounds__(256) fill_graph_kernel(const int* __restrict__
 }
 
 // mode 1: caller-supplied edge_index [2, E] (int64)
+// Edge `id` of it at a flow: the row it is gathered from (s) and the one it aggregates at (d); false where either is out of [0, n)
+__device__ __forceinline__ bool decode_endpoints(const int64_t* __restrict__ ei, int64_t n, int64_t e, int64_t id, int flow, int64_t& s,
+                                                 int64_t& d) {
+    s = ei[flow ? e + id : id];
+    d = ei[flow ? id : e + id];
+    return s >= 0 && s < n && d >= 0 && d < n;
+}
+
 __global__ void __launch_bounds__(256) indeg_ei_kernel(const int64_t* __restrict__ ei, int64_t n, int64_t e, int flow,
                                                         int* __restrict__ indeg, CsrHeader* hdr) {
-    int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, s, d;
     if (id >= e) return;
-    int64_t s = ei[flow ? e + id : id], d = ei[flow ? id : e + id];
-    if (s < 0 || s >= n || d < 0 || d >= n) { atomicOr(&hdr->error_flags, ERRF_BAD_EDGE_INDEX); return; }
+    if (!decode_endpoints(ei, n, e, id, flow, s, d)) { atomicOr(&hdr->error_flags, ERRF_BAD_EDGE_INDEX); return; }
     atomicAdd(&indeg[d], 1);
 }
 
@@ -679,10 +705,9 @@ __global__ void __launch_bounds__(256) fill_ei_kernel(const int64_t* __restrict_
                                                        const int* __restrict__ in_ptr, int* __restrict__ cursor,
                                                        int* __restrict__ dst, int* __restrict__ src,
                                                        int* __restrict__ eid, CsrHeader* hdr) {
-    int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, s, d;
     if (id >= e) return;
-    int64_t s = ei[flow ? e + id : id], d = ei[flow ? id : e + id];
-    if (s < 0 || s >= n || d < 0 || d >= n) {
+    if (!decode_endpoints(ei, n, e, id, flow, s, d)) {
         // An edge with an index out of range is left out (flagged by the counting pass).  Its place is one of the slots past the
         // E valid edges: it gets VALID indices there (node 0, its own edge id), so that a caller that walks all `e` slots with its
         // host-side count -- the training kernels -- stays inside every array; what it computes for a flagged forward is not used.
@@ -750,16 +775,10 @@ __global__ void __launch_bounds__(256) segment_sort_kernel(const int* __restrict
         }
     if (sub == 0) s_long[sl] = (active && !small) ? 1 : 0;
     __syncthreads();
-    auto write_attr = [&](int64_t node, int srcv, int64_t at) {  // [(p_s - p_r)/r, |.|] of the edge at sorted position `at` (utils.py:43-61)
-        float d[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-            d[c] = flow ? __fdiv_rn(__fsub_rn(pos[node * pos_stride + c], pos[(int64_t)srcv * pos_stride + c]), conn_r)
-                        : __fdiv_rn(__fsub_rn(pos[(int64_t)srcv * pos_stride + c], pos[node * pos_stride + c]), conn_r);
-        float q = __fmul_rn(d[0], d[0]);
-        q = __fadd_rn(q, __fmul_rn(d[1], d[1]));
-        q = __fadd_rn(q, __fmul_rn(d[2], d[2]));
-        *reinterpret_cast<float4*>(edge_attr + at * 4) = make_float4(d[0], d[1], d[2], __fsqrt_rn(q));
+    // feature of the edge at sorted position `at`; the sender (edge_index[0]) is the segment's source at flow 0, its node at flow 1
+    auto write_attr = [&](int64_t node, int srcv, int64_t at) {
+        const int64_t s = flow ? node : (int64_t)srcv, r = flow ? (int64_t)srcv : node;
+        *reinterpret_cast<float4*>(edge_attr + at * 4) = edge_feature(pos + s * pos_stride, pos + r * pos_stride, conn_r);
     };
     if (active && small) {
         for (int a = sub; a < len; a += SEG_LPS) {
@@ -791,23 +810,31 @@ __global__ void __launch_bounds__(256) segment_sort_kernel(const int* __restrict
     }
 }
 
+// The grid phase of a build, behind its resets: bounding box + grid, cell assignment, ONE-launch scan of the cell counts, cell fill
+// (-> g.sorted: the rows grouped by cell, g.cell_start: where each cell's rows begin)
+static int grid_phase(const float* pos, int64_t pos_stride, int64_t n, int64_t n_per, double conn_r, const GraphWs& g, hipStream_t s) {
+    const int nb = (int)cdiv(n, 256);
+    hipLaunchKernelGGL(bbox_kernel, dim3(nb < 64 ? nb : 64), dim3(256), 0, s, pos, pos_stride, n, g.hdr, conn_r, g.max_cells, n_per);
+    hipLaunchKernelGGL(cell_assign_kernel, dim3(nb), dim3(256), 0, s, pos, pos_stride, n, g.hdr, g.cell_of, g.cell_start);
+    const ScanJob sj{g.cell_start, g.cell_start, (long long)g.max_cells + 1, nullptr, g.scan_cells};
+    const int rc = scan_lookback(&sj, 1, s);
+    if (rc != GM_OK) return rc;
+    hipLaunchKernelGGL(cell_fill_kernel, dim3(nb), dim3(256), 0, s, pos, pos_stride, n, g.cell_of, g.cell_start, g.cell_cursor, g.sorted);
+    GM_LAUNCH_CHECK();
+    return GM_OK;
+}
+
 int cell_order(const float* pos, int64_t pos_stride, int64_t n, int64_t n_per, double conn_r, int K, void* graph_ws, size_t graph_ws_bytes,
                int* perm, hipStream_t s) {
     GM_REQUIRE(pos && graph_ws && perm && n > 0 && pos_stride >= 3 && conn_r > 0.0, GM_ERR_INVALID_ARGUMENT, "cell_order: bad argument");
     GraphWs g = carve_graph(graph_ws, n, K);
     GM_REQUIRE(graph_ws_bytes >= g.bytes, GM_ERR_WORKSPACE, "cell_order: workspace %zu < %zu", graph_ws_bytes, g.bytes);
-    const int nb = (int)cdiv(n, 256);
     StepClear clr;
     int rc = graph_clear_jobs(clr, g, n);
     if (rc == GM_OK) rc = launch_step_clear(clr, s);
+    if (rc == GM_OK) rc = grid_phase(pos, pos_stride, n, n_per, conn_r, g, s);
     if (rc != GM_OK) return rc;
-    hipLaunchKernelGGL(bbox_kernel, dim3(nb < 64 ? nb : 64), dim3(256), 0, s, pos, pos_stride, n, g.hdr, conn_r, g.max_cells, n_per);
-    hipLaunchKernelGGL(cell_assign_kernel, dim3(nb), dim3(256), 0, s, pos, pos_stride, n, g.hdr, g.cell_of, g.cell_start);
-    const ScanJob sj{g.cell_start, g.cell_start, (long long)g.max_cells + 1, nullptr, g.scan_cells};
-    rc = scan_lookback(&sj, 1, s);
-    if (rc != GM_OK) return rc;
-    hipLaunchKernelGGL(cell_fill_kernel, dim3(nb), dim3(256), 0, s, pos, pos_stride, n, g.cell_of, g.cell_start, g.cell_cursor, g.sorted);
-    hipLaunchKernelGGL(cell_order_kernel, dim3(nb), dim3(256), 0, s, g.sorted, g.cell_of, g.cell_start, g.hdr, n, perm);
+    hipLaunchKernelGGL(cell_order_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, s, g.sorted, g.cell_of, g.cell_start, g.hdr, n, perm);
     GM_LAUNCH_CHECK();
     return GM_OK;
 }
@@ -847,55 +874,39 @@ int check_build_args(const float* pos, int64_t pos_stride, int64_t n, int64_t n_
     return GM_OK;
 }
 
+// The general neighbour kernel at BS queries per workgroup: K * BS (d2, index) entries of LDS, above 64 KiB behind the attribute
+// that allows it (raised once per device)
+template <int BS>
+int launch_neighbor(const GraphWs& g, int64_t n, double r2, int K, int* indeg, int* slot, int flow, hipStream_t s) {
+    const size_t lds = (size_t)K * BS * 12;
+    GM_REQUIRE(lds <= 160 * 1024, GM_ERR_UNSUPPORTED, "gm_radius_graph_build: max_neighbours=%d needs %zu bytes of LDS", K, lds);
+    if (lds > 64 * 1024) {
+        static PerDeviceOnce big_lds;
+        const int rc_attr = big_lds.run([]() -> int {
+            GM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(neighbor_kernel<BS>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            return GM_OK;
+        });
+        if (rc_attr != GM_OK) return rc_attr;
+    }
+    hipLaunchKernelGGL(neighbor_kernel<BS>, dim3((int)cdiv(n, BS)), dim3(BS), lds, s, g.sorted, g.cell_start, g.hdr, n, r2, K, g.cnt, g.nbr,
+                       indeg, slot, flow);
+    GM_LAUNCH_CHECK();
+    return GM_OK;
+}
+
 // The build behind its resets (StepClear: a launch of its own in the stand-alone entry point, part of the step's first launch in the
-// rollout): bounding box + grid, cell assignment, ONE-launch scan of the cell counts, cell fill, the two neighbour kernels.  The scan
-// of cnt (-> out_ptr, E) is the caller's: the rollout path runs it together with the in-degree scan of the destination sort.
+// rollout): the grid phase and the two neighbour kernels.  The scan of cnt (-> out_ptr, E) is the caller's: the rollout path runs it
+// together with the in-degree scan of the destination sort.
 // indeg / slot: the destination sort's counting pass rides in the neighbour kernels (nullptr: it does not).
 int radius_graph_build_core(const float* pos, int64_t pos_stride, int64_t n, int64_t n_per, double conn_r, int K, const GraphWs& g,
                             int* indeg, int* slot, int flow, hipStream_t s) {
     if (n <= 0) return GM_OK;
-    int nb = (int)cdiv(n, 256);
-    hipLaunchKernelGGL(bbox_kernel, dim3(nb < 64 ? nb : 64), dim3(256), 0, s, pos, pos_stride, n, g.hdr, conn_r,
-                       g.max_cells, n_per);
-    hipLaunchKernelGGL(cell_assign_kernel, dim3(nb), dim3(256), 0, s, pos, pos_stride, n, g.hdr, g.cell_of, g.cell_start);
-    const ScanJob sj{g.cell_start, g.cell_start, (long long)g.max_cells + 1, nullptr, g.scan_cells};
-    int rc = scan_lookback(&sj, 1, s);
+    const int rc = grid_phase(pos, pos_stride, n, n_per, conn_r, g, s);
     if (rc != GM_OK) return rc;
-    hipLaunchKernelGGL(cell_fill_kernel, dim3(nb), dim3(256), 0, s, pos, pos_stride, n, g.cell_of, g.cell_start,
-                       g.cell_cursor, g.sorted);
     const double r2 = conn_r * conn_r;  // KDTree compares rdist with r*r in float64
     hipLaunchKernelGGL(neighbor_fast_kernel, dim3((unsigned)cdiv(n, NB_QPB)), dim3(256), 0, s, g.sorted, g.cell_start,
                        g.hdr, n, r2, K, g.cnt, g.nbr, indeg, slot, flow);
-    if (K <= 64) {
-        constexpr int BS = 128;
-        size_t lds = (size_t)K * BS * 12;
-        if (lds > 64 * 1024) {
-            static PerDeviceOnce big_lds;
-            const int rc_attr = big_lds.run([]() -> int {
-                GM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(neighbor_kernel<BS>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                return GM_OK;
-            });
-            if (rc_attr != GM_OK) return rc_attr;
-        }
-        hipLaunchKernelGGL(neighbor_kernel<BS>, dim3((int)cdiv(n, BS)), dim3(BS), lds, s, g.sorted, g.cell_start,
-                           g.hdr, n, r2, K, g.cnt, g.nbr, indeg, slot, flow);
-    } else {
-        constexpr int BS = 64;
-        size_t lds = (size_t)K * BS * 12;
-        GM_REQUIRE(lds <= 160 * 1024, GM_ERR_UNSUPPORTED, "gm_radius_graph_build: max_neighbours=%d needs %zu bytes of LDS", K, lds);
-        if (lds > 64 * 1024) {
-            static PerDeviceOnce big_lds64;
-            const int rc_attr = big_lds64.run([]() -> int {
-                GM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(neighbor_kernel<BS>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                return GM_OK;
-            });
-            if (rc_attr != GM_OK) return rc_attr;
-        }
-        hipLaunchKernelGGL(neighbor_kernel<BS>, dim3((int)cdiv(n, BS)), dim3(BS), lds, s, g.sorted, g.cell_start,
-                           g.hdr, n, r2, K, g.cnt, g.nbr, indeg, slot, flow);
-    }
-    GM_LAUNCH_CHECK();
-    return GM_OK;
+    return K <= 64 ? launch_neighbor<128>(g, n, r2, K, indeg, slot, flow, s) : launch_neighbor<64>(g, n, r2, K, indeg, slot, flow, s);
 }
 }  // namespace
 

@@ -5,6 +5,7 @@
 #include "common.h"
 #include "hmlp.h"
 #include "mlp.h"
+#include "step_rows.h"
 #include "train.h"
 
 namespace gm {
@@ -25,11 +26,14 @@ struct TStream { size_t off = 0; int stages = 0, stages_tail = 0; };
 // the model's MLPs in state_dict order: edge encoder, node encoder, the edge and node MLP of each step, the decoder
 std::vector<MlpSpec> model_mlps(const gm_model_desc& d);
 
-// Two facts a rollout step (model.hip) and its backward (rollout_grad.hip) must agree on.
-// Width of a scene's node features (features.hip): 3 (k_steps - 1) + 7, and 3 more with control columns
-inline int node_feature_dim(const gm_feature_desc* fd) { return 3 * (fd->k_steps - 1) + 7 + (fd->control_col >= 0 ? 3 : 0); }
-// Nodes of one graph of a batch of equal-sized scenes stored back to back (nodes_per_graph == 0: one scene of n nodes)
-inline int64_t graph_nodes(const gm_feature_desc* fd, int64_t n) { return fd->nodes_per_graph > 0 ? fd->nodes_per_graph : n; }
+// What a rollout step (model.hip) and its backward (rollout_grad.hip) ask of a model for a scene: its node features' width
+// (step_rows.h) and a 3-D scene's edge features and accelerations; `who`: the entry point, for the message
+static inline int check_model_for_scene(const gm_model_desc& d, const gm_feature_desc* fd, const char* who) {
+    const int F = node_feature_dim(fd);
+    GM_REQUIRE(d.node_dim == F, GM_ERR_INVALID_ARGUMENT, "%s: model node_dim=%d but features give %d", who, d.node_dim, F);
+    GM_REQUIRE(d.edge_dim == 4 && d.out_dim == 3, GM_ERR_INVALID_ARGUMENT, "%s: needs edge_dim=4, out_dim=3 (3-D scene)", who);
+    return GM_OK;
+}
 }  // namespace gm
 
 struct gm_model {

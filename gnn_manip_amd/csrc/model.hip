@@ -745,15 +745,13 @@ int gm_rollout_step(const gm_model* m, float* obs, int64_t n, const gm_feature_d
                     const float* rigid_target, float* pred_acc_out, void* ws, size_t ws_bytes, void* stream) {
     gm::DevGuard dev_guard(obs);
     GM_REQUIRE(m && obs && fd && ws, GM_ERR_INVALID_ARGUMENT, "gm_rollout_step: null pointer");
-    const int F = gm::node_feature_dim(fd);
-    GM_REQUIRE(m->d.node_dim == F, GM_ERR_INVALID_ARGUMENT, "gm_rollout_step: model node_dim=%d but features give %d", m->d.node_dim, F);
-    GM_REQUIRE(m->d.edge_dim == 4 && m->d.out_dim == 3, GM_ERR_INVALID_ARGUMENT, "gm_rollout_step: needs edge_dim=4, out_dim=3 (3-D scene)");
+    int rc = gm::check_model_for_scene(m->d, fd, "gm_rollout_step");
+    if (rc != GM_OK) return rc;
     GM_REQUIRE(n < ((int64_t)1 << 31) / (K > 0 ? K : 1), GM_ERR_UNSUPPORTED, "gm_rollout_step: n*max_neighbours overflows int32");
     RolloutWs r = carve_rollout(ws, &m->d, n, K);
     GM_REQUIRE(ws_bytes >= r.bytes, GM_ERR_WORKSPACE, "gm_rollout_step: workspace %zu < %zu", ws_bytes, r.bytes);
     if (n == 0) return GM_OK;
     const int64_t cap = n * K;
-    int rc;
     hipStream_t hs = (hipStream_t)stream;
     // state_pre + node features in one launch -- which also resets what the step's later launches build on: the graph and
     // destination-sort workspaces (headers, cell counts, in-degrees, scan states, stitch table) and the forward's agg rows

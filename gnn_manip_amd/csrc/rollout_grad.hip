@@ -99,10 +99,8 @@ static int step_backward(const gm_model* m, const float* const* tensors, int n_t
     GM_REQUIRE(sizes_ok(&m->d, fd, n, K), GM_ERR_INVALID_ARGUMENT, "%s: sizes out of range", who);
     GM_REQUIRE(n == 0 || (obs_before && d_obs_after && d_obs_before), GM_ERR_INVALID_ARGUMENT, "%s: null pointer", who);
     GM_REQUIRE(!rigid_target || rigid_rank, GM_ERR_INVALID_ARGUMENT, "%s: rigid_target needs rigid_rank", who);
-    const int F = gm::node_feature_dim(fd);
-    GM_REQUIRE(m->d.node_dim == F, GM_ERR_INVALID_ARGUMENT, "%s: model node_dim=%d but features give %d", who, m->d.node_dim, F);
-    GM_REQUIRE(m->d.edge_dim == 4 && m->d.out_dim == 3, GM_ERR_INVALID_ARGUMENT,
-               "%s: needs edge_dim=4, out_dim=3 (3-D scene)", who);
+    int rc = gm::check_model_for_scene(m->d, fd, who);
+    if (rc != GM_OK) return rc;
     StepBwdWs w = carve_step_bwd(ws, &m->d, fd, n, K);
     GM_REQUIRE(ws_bytes >= w.bytes, GM_ERR_WORKSPACE, "%s: workspace %zu < %zu", who, ws_bytes, w.bytes);
     if (n_edges_host) *n_edges_host = 0;
@@ -112,7 +110,6 @@ static int step_backward(const gm_model* m, const float* const* tensors, int n_t
     const bool has_target = rigid_target != nullptr;
     const bool pre = rigid_rank && fd->control_col >= 0;   // gm_rollout_step's own condition for the overwrite
     const float conn_r = (float)fd->conn_r;
-    int rc;
 
     // ---- the step's forward again, out of place, with the training forward's tape
     GM_HIP_CHECK(hipMemcpyAsync(w.pre, obs_before, window * sizeof(float), hipMemcpyDeviceToDevice, hs));

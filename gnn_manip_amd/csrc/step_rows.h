@@ -1,0 +1,114 @@
+// The per-row formulas of a rollout step, each stated once: the stand-alone kernels (features.hip, graph.hip) call one of them, the
+// fused kernels of gm_rollout_step compose them -- which is why a fused step equals the chain of stand-alone entry points bit for bit.
+// All float32 element-wise work; operations are written with the _rn intrinsics so that no multiply-add is contracted: the results
+// are bit-identical to the reference's separate torch ops wherever the reference's own op order is defined.
+#pragma once
+#include "common.h"
+
+namespace gm {
+
+struct FeatParams {
+    int k, D, cart, mat, ctrl;
+    float r;
+    float vm[3], vs[3], am[3], as[3], lo[3], hi[3];
+};
+
+// Width of a scene's node features: 3 (k_steps - 1) velocities, 6 boundary terms, the material, and 3 more with control columns
+__host__ __device__ static inline int node_feature_dim(int k_steps, int control_col) { return 3 * (k_steps - 1) + 7 + (control_col >= 0 ? 3 : 0); }
+inline int node_feature_dim(const gm_feature_desc* fd) { return node_feature_dim(fd->k_steps, fd->control_col); }
+// Nodes of one graph of a batch of equal-sized scenes stored back to back (nodes_per_graph == 0: one scene of n nodes)
+inline int64_t graph_nodes(const gm_feature_desc* fd, int64_t n) { return fd->nodes_per_graph > 0 ? fd->nodes_per_graph : n; }
+
+#if defined(__HIPCC__)
+// [(p_s - p_r) / r, |.|] of one edge, ps / pr = the xyz of its sender (edge_index[0]) / receiver (utils.py:43-61)
+__device__ __forceinline__ float4 edge_feature(const float* __restrict__ ps, const float* __restrict__ pr, float cr) {
+    float d[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) d[a] = __fdiv_rn(__fsub_rn(ps[a], pr[a]), cr);
+    float q = __fmul_rn(d[0], d[0]);
+    q = __fadd_rn(q, __fmul_rn(d[1], d[1]));
+    q = __fadd_rn(q, __fmul_rn(d[2], d[2]));
+    return make_float4(d[0], d[1], d[2], __fsqrt_rn(q));
+}
+
+// Distance of x to the lower (l) and from the upper (u) bound of one axis in units of r, before the clamp: the forward clamps both
+// to [-1, 1] (unit_clamp), the backward passes a gradient where they lie inside (in_unit: torch.clamp's rule)
+__device__ __forceinline__ void boundary_terms(float x, const FeatParams& P, int a, float& l, float& u) {
+    l = __fdiv_rn(__fsub_rn(x, P.lo[a]), P.r);
+    u = __fdiv_rn(__fsub_rn(P.hi[a], x), P.r);
+}
+__device__ __forceinline__ float unit_clamp(float v) { return fminf(fmaxf(v, -1.f), 1.f); }
+__device__ __forceinline__ bool in_unit(float v) { return v >= -1.f && v <= 1.f; }
+
+// Node features of one particle, row = its row of frame 0, fs = the frame stride, o = its node_feature_dim floats: the k - 1
+// velocities (utils.py:27-40), the clamped boundary terms and the material (collate_utils.py:195-208), the control (217-232)
+__device__ __forceinline__ void node_features_row(const float* __restrict__ row, int64_t fs, const FeatParams& P, float* __restrict__ o) {
+    float prev[3], cur[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) prev[a] = row[P.cart + a];
+    for (int t = 1; t < P.k; ++t) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            cur[a] = row[t * fs + P.cart + a];
+            o[(t - 1) * 3 + a] = __fdiv_rn(__fsub_rn(__fsub_rn(cur[a], prev[a]), P.vm[a]), P.vs[a]);
+            prev[a] = cur[a];
+        }
+    }
+    float* b = o + 3 * (P.k - 1);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        float l, u;
+        boundary_terms(cur[a], P, a, l, u);
+        b[a] = unit_clamp(l);
+        b[3 + a] = unit_clamp(u);
+    }
+    const float* last = row + (int64_t)(P.k - 1) * fs;
+    b[6] = last[P.mat];
+    if (P.ctrl >= 0) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) b[7 + a] = __fdiv_rn(__fsub_rn(last[P.ctrl + a], P.vm[a]), P.vs[a]);
+    }
+}
+
+// Control of one rigid particle, last = its row of the last frame, tgt = its scripted xyz or nullptr: the way to the target, or
+// without one its current xyz (rollout_utils.py:40-47 / traj_utils.py:126-134)
+__device__ __forceinline__ void control_overwrite_row(float* __restrict__ last, const FeatParams& P, const float* __restrict__ tgt) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float cur = last[P.cart + a];
+        last[P.ctrl + a] = tgt ? __fsub_rn(tgt[a], cur) : cur;
+    }
+}
+
+// Next xyz of one particle from its xyz in the last two frames (l1, l2) and its predicted, normalised acceleration:
+// l1 + ((l1 - l2) + (pred * acc_std + acc_mean)) (rollout_utils.py:145-158)
+__device__ __forceinline__ float3 integrate_row(const float* __restrict__ l1, const float* __restrict__ l2, const float* __restrict__ pred,
+                                                const FeatParams& P) {
+    float nxt[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float acc = __fadd_rn(__fmul_rn(pred[a], P.as[a]), P.am[a]);
+        const float lv = __fsub_rn(l1[a], l2[a]);
+        nxt[a] = __fadd_rn(l1[a], __fadd_rn(lv, acc));
+    }
+    return make_float3(nxt[0], nxt[1], nxt[2]);
+}
+
+// Window shift and write-back of one particle, row = its row of frame 0: frame t takes frame t + 1, then the last frame's xyz takes
+// nxt (rk < 0: not rigid; by value, so that a fused caller's stays in registers) or the scripted tgt
+// (rollout_utils.py:53-61 / traj_utils.py:146-152)
+__device__ __forceinline__ void shift_write_row(float* __restrict__ row, int64_t fs, const FeatParams& P, int rk, float3 nxt,
+                                                const float* __restrict__ tgt) {
+    for (int t = 0; t + 1 < P.k; ++t)
+        for (int d = 0; d < P.D; ++d) row[t * fs + d] = row[(t + 1) * fs + d];
+    float* last = row + (int64_t)(P.k - 1) * fs + P.cart;
+    if (rk < 0) {
+        last[0] = nxt.x; last[1] = nxt.y; last[2] = nxt.z;
+    } else if (tgt) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) last[a] = tgt[a];
+    }  // rigid row without a scripted pose keeps its pre-step row (traj_utils.py:150-152)
+}
+#endif
+
+}  // namespace gm

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+import graph_cases as gc
 import width_cases as wc
 from conftest import BOUNDS, STATS, assert_forward_close
 from oracle import epd_oracle as orc
@@ -33,9 +34,9 @@ def _t(a, dev):
     return torch.from_numpy(np.array(a, order="C", copy=True)).to(dev)     # a copy: the cases' arrays are read-only
 
 
-def _model(params, dims, dev):
+def _model(params, dims, dev, **conv):
     from gnn_manip_amd import EncProcDecGNN
-    m = EncProcDecGNN(*dims)
+    m = EncProcDecGNN(*dims, **conv)
     m.load_state_dict({k: torch.from_numpy(v) for k, v in params.items()}, strict=True)
     return m.to(dev)
 
@@ -281,15 +282,17 @@ def test_rigid_rank_is_a_cumsum(dev, n):
             assert np.array_equal(rank.cpu().numpy(), np.where(rigid, np.cumsum(rigid) - 1, -1)), (lname, pattern)
 
 
-def _step_and_chain(dev, name, kernel):
+def _step_and_chain(dev, name, kernel, obs=None, K=20, flow=0):
+    """obs: a state in the layout `name` (default: wc.scene_in_layout's); flow 1: a model of the flow="target_to_source" convention,
+    the chain's sort through gm_csr_from_graph_flow.  Returns the longest segment of the destination sort, by the oracle's edges."""
     from gnn_manip_amd._lib import ModelDesc
     L = wc.LAYOUTS[name]
-    obs = wc.scene_in_layout(name)
-    n, K = obs.shape[1], 20
+    obs = wc.scene_in_layout(name) if obs is None else obs
+    n = obs.shape[1]
     cap = n * K
     dims = (L.node_dim, 4, 3, wc.HIDDEN, wc.NUM_LAYERS, wc.M_STEPS)
     params = orc.init_params(*dims, 810 + list(wc.LAYOUTS).index(name))
-    m = _model(params, dims, dev)
+    m = _model(params, dims, dev, **(dict(flow="target_to_source") if flow else {}))
     m.set_edge_kernel(kernel)
     handle = m.device_handle(dev)
     abi, fd, md = _Abi(dev), _fdesc(L), ModelDesc(*m.model_desc())
@@ -312,7 +315,10 @@ def _step_and_chain(dev, name, kernel):
     gws = abi.u8(lib.gm_graph_workspace_bytes(n, K))
     check(lib.gm_radius_graph_build(p(b, last), L.D, n, wc.R, K, p(gws), gws.numel(), abi.stream()))
     cws = abi.u8(lib.gm_csr_workspace_bytes(n, cap))
-    check(lib.gm_csr_from_graph(p(gws), n, K, p(cws), cws.numel(), abi.stream()))
+    if flow == 0:
+        check(lib.gm_csr_from_graph(p(gws), n, K, p(cws), cws.numel(), abi.stream()))
+    else:
+        check(lib.gm_csr_from_graph_flow(p(gws), n, K, flow, p(cws), cws.numel(), abi.stream()))
     ea = torch.zeros((cap, 4), dtype=torch.float32, device=dev)
     check(lib.gm_edge_features_csr(p(b, last), L.D, p(cws), n, cap, wc.R, p(ea), abi.stream()))
     fws = abi.u8(lib.gm_forward_workspace_bytes(C.byref(md), n, cap))
@@ -323,12 +329,13 @@ def _step_and_chain(dev, name, kernel):
     nxt = abi.integrate(pred_b, b, fd)
     abi.state_post(b, fd, nxt, rank, target)
     torch.cuda.synchronize()
-    e_ref = orc.get_connectivity(obs[-1][:, L.cart_idx], wc.R, K)[0].shape[0]
-    assert e_a.value == e_b.value == e_ref
+    snd_ref, rcv_ref = orc.get_connectivity(obs[-1][:, L.cart_idx], wc.R, K)
+    assert e_a.value == e_b.value == snd_ref.shape[0]
     assert torch.isfinite(pred_a).all() and float(pred_a.abs().max()) > 0
     assert torch.equal(pred_a, pred_b), float((pred_a - pred_b).abs().max())
     assert torch.equal(a, b), float((a - b).abs().max())
     assert not torch.equal(a, _t(obs, dev))
+    return int(np.bincount(snd_ref if flow else rcv_ref, minlength=n).max())   # a segment: the edges that aggregate at one node
 
 
 @pytest.mark.parametrize("name", list(wc.LAYOUTS))
@@ -342,6 +349,19 @@ def test_a_step_is_the_chain_it_documents(dev, name):
 
 def test_a_step_is_the_chain_it_documents_systolic(dev):
     _step_and_chain(dev, "default", "sys_all")
+
+
+def test_a_step_is_the_chain_it_documents_at_flow_1_with_long_segments(dev):
+    """The sort's own edge features at flow 1 on segments the whole workgroup sorts (more than 96 edges: segment_sort_kernel's long
+    path), which run inside gm_rollout_step only.  At flow 1 a query's own list is its segment, so K = 128 on graph_cases'
+    a3_cluster150 -- 151 rows on one point, nine more within conn_r of it, whose lists of 128 carry 127 non-zero features each --
+    gives 160 segments of 128.  Its positions are the last frame of a state in the default layout."""
+    geo = gc.geometry("a3_cluster150")
+    on_one_point = np.flatnonzero((geo.pos == geo.pos[17]).all(axis=1))
+    assert on_one_point.size >= 151 and geo.r == wc.R
+    obs = gc.scene_with_last_frame(geo.pos, on_one_point, seed=812)
+    assert obs.shape[::2] == (wc.LAYOUTS["default"].k, wc.LAYOUTS["default"].D)
+    assert _step_and_chain(dev, "default", "hm", obs=obs, K=128, flow=1) > 96
 
 
 def _rollout_model(name, dev):
