@@ -96,7 +96,7 @@ def flip_allowance(run, leaves, tau=1e-5, max_units=256):
         for acc, gk in zip(allow, g):
             if gk is not None:
                 acc += gk.abs()
-    return [v.numpy() for v in allow], len(units)
+    return [v.cpu().numpy() for v in allow], len(units)   # (the leaves may live on a device: tests/test_gpu_offsets.py)
 
 
 def _lazy(fn):
