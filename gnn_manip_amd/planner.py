@@ -183,6 +183,58 @@ class CandidateEvaluator:
         return out
 
 
+def projected_adam(objective, x0, half_widths, iters=20, lr=0.01, betas=(0.9, 0.999), eps=1e-8):
+    """Projected Adam on P starts at once, in float64 on the host.  objective(X [P, dim]) -> (values [P], gradients [P, dim]);
+    half_widths [dim] > 0: the box is |x_j| <= half_widths[j], and the iteration runs in z = x / half_widths, so that ``lr``
+    bounds a step by about that fraction of a half-width per coordinate.  The starts are clamped to the box (iterate 0), every
+    update is textbook Adam with bias correction followed by the clamp, and iterate k is evaluated by the k-th call of
+    ``objective``: ``iters + 1`` calls, the last one for its values alone.  Starts do not interact (the state is per row).
+    Returns (x_best [P, dim], f_best [P], info): per start the iterate of the lowest value, the earliest one among equals;
+    info["f"] [P, iters + 1] the values and info["x"] [P, iters + 1, dim] the iterates."""
+    hw = np.asarray(half_widths, dtype=np.float64).reshape(-1)
+    x0 = np.asarray(x0, dtype=np.float64)
+    if x0.ndim != 2 or x0.shape[1] != hw.shape[0] or not (hw > 0).all():
+        raise ValueError(f"projected_adam: starts [P, dim] and positive half-widths [dim], got {x0.shape} and {hw.shape}")
+    b1, b2 = float(betas[0]), float(betas[1])
+    z = np.clip(x0 / hw, -1.0, 1.0)
+    m, v = np.zeros_like(z), np.zeros_like(z)
+    xs = np.empty((z.shape[0], iters + 1, z.shape[1]))
+    fs = np.empty((z.shape[0], iters + 1))
+    for k in range(iters + 1):
+        xs[:, k] = z * hw
+        f, g = objective(xs[:, k].copy())
+        fs[:, k] = np.asarray(f, dtype=np.float64).reshape(-1)
+        if k == iters:
+            break
+        g = np.asarray(g, dtype=np.float64).reshape(z.shape) * hw
+        m = b1 * m + (1.0 - b1) * g
+        v = b2 * v + (1.0 - b2) * g * g
+        step = (m / (1.0 - b1 ** (k + 1))) / (np.sqrt(v / (1.0 - b2 ** (k + 1))) + eps)
+        z = np.clip(z - lr * step, -1.0, 1.0)
+    best = np.argmin(fs, axis=1)   # the first of equal minima
+    rows = np.arange(z.shape[0])
+    return xs[rows, best].copy(), fs[rows, best].copy(), {"f": fs, "x": xs}
+
+
+def refine_starts(block_objective, x0, half_widths, iters=20, lr=0.01, betas=(0.9, 0.999), eps=1e-8, collective_device=None):
+    """``projected_adam`` with the starts sharded over the ranks of torch.distributed (one process: the plain call).  Rank 0's
+    starts are broadcast, each rank refines its contiguous block for all iterations on its own -- block_objective sees that
+    block's rows only -- and one all-gather of [f_best, x_best..., f_0...f_iters] rows hands every rank the full result.
+    ``info`` then holds "f" alone."""
+    import torch.distributed as dist
+    kw = dict(iters=iters, lr=lr, betas=betas, eps=eps)
+    if not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+        return projected_adam(block_objective, x0, half_widths, **kw)
+    dim = int(np.asarray(half_widths).reshape(-1).shape[0])
+
+    def block(xs):
+        xb, fb, info = projected_adam(block_objective, np.stack(xs), half_widths, **kw)
+        return list(np.concatenate((fb[:, None], xb, info["f"]), axis=1))
+
+    rows = CandidateEvaluator(None, result_dim=1 + dim + iters + 1, device=collective_device).evaluate_blocks(x0, block)
+    return rows[:, 1:1 + dim].copy(), rows[:, 0].copy(), {"f": rows[:, 1 + dim:].copy()}
+
+
 class TrajectoryCMAsolver:
     """Mirror of the reference's ``TrajectoryCMAsolver`` (traj_utils.py:14-76,197-285) with the population of a
     CMA-ES generation evaluated TOGETHER on the device(s) instead of one ``cma_objective`` call per candidate:
@@ -191,7 +243,9 @@ class TrajectoryCMAsolver:
     * ``population_losses(X)``: the generation is cut into blocks of ``candidates_per_gpu`` block-diagonal
       batched rollouts (``RolloutEngine(candidates=B)``) and, under ``torch.distributed``, sharded over the ranks
       (``CandidateEvaluator``: one broadcast of X, one all-gather of the losses per generation);
-    * ``optimize_trajectory(desired_position)``: ``cmaes.fmin2`` over that (the reference: ``cma.fmin2``, :257).
+    * ``optimize_trajectory(desired_position)``: ``cmaes.fmin2`` over that (the reference: ``cma.fmin2``, :257);
+    * ``loss_and_grad(x)`` / ``population_loss_and_grad(X)`` / ``refine(X0)``: the objective's gradient with respect to the search
+      vector, for one candidate and for blocks of them, and the projected Adam that runs on it (not in the reference).
 
     Same constructor arguments as the reference (``state_init`` = (obs [k, N, D], next positions) on the device).
     The rollouts follow the model's ``set_precision``: ``model.set_precision('f16')`` before planning ranks the candidates with the
@@ -348,7 +402,8 @@ class TrajectoryCMAsolver:
         ``rigid_body_trajectory``), the rollout is ``RolloutEngine.differentiable_rollout`` (memory of one step's tape whatever the
         horizon; the model's parameters are constants), the end cloud goes into the differentiable ``SamplesLoss``, and the
         velocity / acceleration norms are float64 torch.  The boundary penalty is piecewise constant in x: it is added to the
-        value and contributes nothing to the gradient.  Which optimiser to drive with this gradient is left open.
+        value and contributes nothing to the gradient.  ``population_loss_and_grad`` is this call for a block of candidates at once,
+        ``refine`` the projected Adam that runs on it.
         edges: a list that receives the ``edge_index`` of every step of the backward's recomputation (diagnostics, tests).
         sweep: ``differentiable_rollout``'s keyword -- "library" runs the rollout's reverse sweep as one library call (and hands out no
         edge lists: ``edges`` must then be None)."""
@@ -375,17 +430,104 @@ class TrajectoryCMAsolver:
         bound_penalty = self.compute_boundaries_penalty(actions.detach().numpy())
         return float(loss.detach()) + self.penalty * bound_penalty, xt.grad.numpy().reshape(x_np.shape)
 
+    def _block_loss_and_grad(self, xs, sweep):
+        """``loss_and_grad`` of the candidates xs (at most a block) through ONE block-diagonal rollout: every candidate has its own
+        float64 leaf and pose chain, the poses are laid side by side along the rigid axis ([h, B Nr, 3], ``rollout_candidates``'
+        layout) and the initial state B times along the node axis; one ``differentiable_rollout`` on ``_engine(B)``, one batched
+        Sinkhorn call, one backward of the sum of the B objectives.  No term couples two candidates, so each leaf receives the
+        gradient of its own objective."""
+        b, h, n_points = len(xs), self.horizon, self.sample_traj.shape[0]
+        leaves = [torch.tensor(x.reshape(-1), dtype=torch.float64, requires_grad=True) for x in xs]
+        chains = [interpolate_trajectory_torch(xt, n_points, float(self.rx_init), self.scale_rot, self.scale_ty, float(self.max_rot),
+                                               self.max_ty) for xt in leaves]
+        traj = torch.cat([rigid_body_trajectory(rot, ty, h, self.ty_init, self.rigid_particles) for rot, ty in chains], dim=1)
+        eng = self._engine(b)
+        obs = self.initial_state[0]
+        obs = obs.unsqueeze(1).repeat(1, b, 1, 1).reshape(eng.k, b * eng.n_per, eng.data_dim).contiguous()
+        final = eng.differentiable_rollout(obs, traj, horizon=h, sweep=sweep)
+        c0 = self.graph_attr.cartesian_idx[0]
+        ends = final[-1].reshape(b, eng.n_per, eng.data_dim).index_select(1, self._coffee_rows)[:, :, c0:c0 + 3]
+        wasserstein = self.loss.batched(ends, self.desired_pos).double().cpu()
+        limits = torch.tensor([float(self.max_rot), float(self.max_ty)], dtype=torch.float64)
+        losses, penalties = [], []
+        for i, (rot, ty) in enumerate(chains):
+            actions = torch.stack((rot[:h], ty[:h]), dim=1)
+            vel = actions[1:] - actions[:-1]
+            acc = actions[2:] - 2 * actions[1:-1] + actions[:-2]
+            losses.append(self.beta * wasserstein[i] + self.alpha * torch.linalg.norm(vel / limits) + self.gamma * torch.linalg.norm(acc / limits))
+            penalties.append(self.compute_boundaries_penalty(actions.detach().numpy()))
+        torch.stack(losses).sum().backward()
+        return [float(l.detach()) + self.penalty * p for l, p in zip(losses, penalties)], [xt.grad.numpy() for xt in leaves]
+
+    def _local_loss_and_grad(self, X, sweep="library"):
+        """This rank's candidates in blocks of ``candidates_per_gpu`` (the last one may be shorter): (losses [P], grads [P, dim])."""
+        X = np.asarray(X, dtype=np.float64)
+        losses, grads = [], []
+        for b in range(0, len(X), self.candidates_per_gpu):
+            l, g = self._block_loss_and_grad(list(X[b:b + self.candidates_per_gpu]), sweep)
+            losses += l
+            grads += g
+        return np.asarray(losses, dtype=np.float64), np.asarray(grads, dtype=np.float64).reshape(X.shape)
+
+    def population_loss_and_grad(self, X, sweep="library"):
+        """``loss_and_grad`` of a whole population: (losses [P], grads [P, dim]) as float64 arrays, row p what
+        ``loss_and_grad(X[p], sweep=sweep)`` returns, from one block-diagonal rollout, one reverse sweep and one batched Sinkhorn
+        call per block of ``candidates_per_gpu`` candidates.  Under torch.distributed rank 0's X is broadcast, every rank takes
+        a contiguous block, and the [loss, grad...] rows are all-gathered (``population_losses``' pattern)."""
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            def rows_of(xs):
+                losses, grads = self._local_loss_and_grad(xs, sweep)
+                return list(np.concatenate((losses[:, None], grads), axis=1))
+
+            ev = CandidateEvaluator(None, result_dim=1 + 2 * self.sample_traj.shape[0], device=self.collective_device or self.device)
+            rows = ev.evaluate_blocks(X, rows_of)
+            return rows[:, 0].copy(), rows[:, 1:].copy()
+        return self._local_loss_and_grad(X, sweep)
+
+    def box_half_widths(self):
+        """Per search variable, the half-width of the box outside which ``interpolate_trajectory`` clips the increment (beyond it
+        the objective is flat in that variable): max_rot / scale_rot for the rotation entries, max_ty / scale_ty for the
+        translation entries, float64."""
+        n_points = self.sample_traj.shape[0]
+        return np.concatenate((np.full(n_points, abs(float(self.max_rot) / float(self.scale_rot))),
+                               np.full(n_points, abs(float(self.max_ty) / float(self.scale_ty)))))
+
+    def refine(self, X0, iters=20, lr=0.01, betas=(0.9, 0.999), eps=1e-8, sweep="library"):
+        """Gradient refinement of P trajectories at once: ``projected_adam`` on ``population_loss_and_grad``, in variables
+        normalised by ``box_half_widths()`` and clamped to that box after every update (and before the first evaluation: outside
+        it the gradient is zero and a start would never move).  ``lr`` is in those units: a step moves a variable by at most about
+        ``lr`` of its admissible increment.  Returns (x_best [P, dim], f_best [P], info): per start the best iterate by the full
+        objective, boundary penalty included, the start itself (clamped) being iterate 0; info["f"] [P, iters + 1] holds the
+        objective sequences.  The values are the sweep's forward, the inference rollout: ``cma_objective``'s.  ``iters + 1``
+        gradient evaluations; deterministic.  Under torch.distributed rank 0's starts are broadcast and each rank refines its
+        block on its own, with one all-gather at the end (``refine_starts``)."""
+        return refine_starts(lambda xs: self._local_loss_and_grad(xs, sweep), X0, self.box_half_widths(), iters=iters, lr=lr, betas=betas,
+                             eps=eps, collective_device=self.collective_device or self.device)
+
     def _start_point(self):
         """The search starts at the sample trajectory: all rotation variables, then all translation variables."""
         return np.ascontiguousarray(self.sample_traj.T, dtype=np.float64).reshape(-1)
 
-    def optimize_trajectory(self, desired_position):
-        """traj_utils.py:247-259."""
+    def optimize_trajectory(self, desired_position, refine=None):
+        """traj_utils.py:247-259.  refine: None, or the keywords of ``refine`` as a dict (``iters``, ``lr``, ``sweep``): after the
+        search, ``es.result.xbest`` and ``es.result.xfavorite`` are refined together, the refined points are ranked against
+        ``xbest`` by the search's own objective (one more ``population_losses`` call), and the best of the three is returned in
+        ``xbest``'s place -- a refined point only where its objective is strictly below ``es.result.fbest``.
+        ``es.refined = {"x", "f", "info"}`` keeps what ``refine`` returned."""
         from . import cmaes
         initial_traj = self._start_point()
         self.desired_pos = desired_position.clone()
-        return cmaes.fmin2(self.cma_objective, initial_traj.tolist(), self.cma_initial_var, options=self.cma_options,
-                           parallel_objective=self.population_losses)
+        xopt, es = cmaes.fmin2(self.cma_objective, initial_traj.tolist(), self.cma_initial_var, options=self.cma_options,
+                               parallel_objective=self.population_losses)
+        if refine is None:
+            return xopt, es
+        x, f, info = self.refine(np.stack((np.asarray(es.result.xbest, dtype=np.float64), np.asarray(es.result.xfavorite, dtype=np.float64))),
+                                 **refine)
+        es.refined = {"x": x, "f": f, "info": info}
+        ranked = self.population_losses(list(x))
+        best = int(np.argmin(ranked))
+        return (x[best].copy(), es) if ranked[best] < es.result.fbest else (xopt, es)
 
 
 class InterpolatedCMAsolver(TrajectoryCMAsolver):
@@ -439,6 +581,12 @@ class InterpolatedCMAsolver(TrajectoryCMAsolver):
 
     def loss_and_grad(self, x):
         raise NotImplementedError("loss_and_grad: the PCHIP parametrisation (scipy, on the host) has no gradient")
+
+    def population_loss_and_grad(self, X, sweep="library"):
+        raise NotImplementedError("population_loss_and_grad: the PCHIP parametrisation (scipy, on the host) has no gradient")
+
+    def refine(self, X0, **kwargs):
+        raise NotImplementedError("refine: the PCHIP parametrisation (scipy, on the host) has no gradient")
 
     _loss_takes_x = True
 

@@ -1,7 +1,10 @@
 """One CMA-ES generation of the planner on one GPU (BASELINE config C5's per-GPU share: 64 candidates over 8 GPUs =
 8 candidates x 200 rollout steps per GPU, then the Sinkhorn loss of every candidate).  Prints one JSON line.
 
-    python tools/bench_plan.py [--n 5000] [--candidates 8] [--horizon 200] [--generations 2]
+    python tools/bench_plan.py [--n 5000] [--candidates 8] [--horizon 200] [--generations 2] [--refine ITERS]
+
+--refine ITERS: then the gradient refinement of the same candidates on the same solver (TrajectoryCMAsolver.refine): time per
+iteration (host clock around a device synchronise), peak memory and the ratio to the generation time, under "refine" in the line.
 """
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -16,6 +19,8 @@ def main():
     ap.add_argument("--candidates", type=int, default=8)
     ap.add_argument("--horizon", type=int, default=200)
     ap.add_argument("--generations", type=int, default=2)
+    ap.add_argument("--refine", type=int, default=None, metavar="ITERS",
+                    help="after the generation timing, time TrajectoryCMAsolver.refine(iters=ITERS) from the same candidates")
     args = ap.parse_args()
     from gnn_manip_amd import EncProcDecGNN, GraphBoundedMultimaterialControl, scene
     from gnn_manip_amd.planner import TrajectoryCMAsolver
@@ -55,11 +60,25 @@ def main():
         s.loss(e.contiguous(), s.desired_pos).item()
     torch.cuda.synchronize()
     loss_t = time.perf_counter() - t1
-    print(json.dumps({"metric": "CMA-ES generation time per GPU", "value": gen, "unit": "s", "higher_is_better": False,
-                      "config": {"workload": f"{args.candidates} candidates x {args.horizon} steps, N={args.n}, hidden=128, 10 MP",
-                                 "coffee_particles": int(coffee.shape[0])},
-                      "rollout_steps_per_s": args.candidates * args.horizon / gen, "sinkhorn_losses_s": loss_t,
-                      "loss_example": float(losses[0])}))
+    result = {"metric": "CMA-ES generation time per GPU", "value": gen, "unit": "s", "higher_is_better": False,
+              "config": {"workload": f"{args.candidates} candidates x {args.horizon} steps, N={args.n}, hidden=128, 10 MP",
+                         "coffee_particles": int(coffee.shape[0])},
+              "rollout_steps_per_s": args.candidates * args.horizon / gen, "sinkhorn_losses_s": loss_t,
+              "loss_example": float(losses[0])}
+    if args.refine is not None:
+        # the same candidates as starts of the gradient refinement: `refine` iterations are refine + 1 evaluations of value and gradient
+        # (one block-diagonal rollout, one reverse sweep, one batched Sinkhorn backward each).  Random weights: what an iteration COSTS.
+        s.population_loss_and_grad(X)  # warm-up: the engine's backward workspace, the training model's weight images
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats(dev)
+        t2 = time.perf_counter()
+        _, f_best, info = s.refine(np.stack(X), iters=args.refine)
+        torch.cuda.synchronize()
+        per_iter = (time.perf_counter() - t2) / (args.refine + 1)
+        result["refine"] = {"iters": args.refine, "s_per_iteration": per_iter, "ratio_to_generation": per_iter / gen,
+                            "peak_memory_GB": torch.cuda.max_memory_allocated(dev) / 1e9,
+                            "f_start": info["f"][:, 0].tolist(), "f_best": f_best.tolist()}
+    print(json.dumps(result))
 
 
 if __name__ == "__main__":
