@@ -73,12 +73,47 @@ def epd_forward_taped(p, nodes, edge_attr, edge_index, num_layers, m_steps, tape
     return _mlp_taped(p, "decoder", h, num_layers, False, tape)
 
 
+def near_zero_units(tape, tau=1e-5, max_units=256):
+    """The hidden units of a tape with |z| < tau * rms(z of its Linear), as sorted (|z| / rms, tape entry, flat index): the closest
+    to zero first, at most max_units.  Empty entries and entries with rms == 0 have none."""
+    units = []
+    for t, (z, a) in enumerate(tape):
+        if z.numel() == 0:
+            continue
+        zz = z.detach().flatten()
+        rms = float(zz.pow(2).mean().sqrt())
+        if rms <= 0.0:
+            continue
+        for q in torch.nonzero(zz.abs() < tau * rms).flatten().tolist():
+            units.append((float(zz[q].abs()) / rms, t, q))
+    units.sort()
+    return units[:max_units]
+
+
+def flip_bounds(tape, units, leaves):
+    """Per element of every leaf, what toggling the ReLU derivative of each of `units` alone can change in d loss / d leaf (first
+    order), absolute values summed over the units.  The loss has been backpropagated through the tape's graph (retain_graph=True),
+    so a.grad is d loss / d a_u: what reaches a unit from above whether or not its derivative lets it through."""
+    bounds = [torch.zeros_like(v) for v in leaves]
+    for _, t, q in units:
+        z, a = tape[t]
+        ga = a.grad.flatten()[q]
+        if float(ga) == 0.0:
+            continue
+        seed = torch.zeros_like(z).flatten()
+        seed[q] = ga
+        g = torch.autograd.grad(z, leaves, grad_outputs=seed.view_as(z), retain_graph=True, allow_unused=True)
+        for acc, gk in zip(bounds, g):
+            if gk is not None:
+                acc += gk.abs()
+    return bounds
+
+
 def relu_flip_allowance(params_np, nodes, edge_attr, edge_index, target, num_layers, m_steps, tau=1e-5, max_units=256):
     """The gradient of a ReLU network is discontinuous where a pre-activation crosses zero: two evaluations that are both accurate to
     float32 rounding can disagree on the sign of a pre-activation that lies within rounding distance of zero, and then their
     gradients differ by what toggling that unit's ReLU derivative changes.  This returns, per parameter, an upper bound of that
-    effect for THIS input (float64, first order): for every hidden unit with |z| < tau * rms(z of its Linear) -- at most max_units,
-    the closest to zero first -- the gradient that flows back from toggling it alone, absolute values summed over the units.
+    effect for THIS input (float64, first order): near_zero_units of the model's tape, flip_bounds of them on the parameters.
     Returns ({name: max |allowed change|}, number of such units)."""
     dtype = torch.float64
     p = {k: torch.tensor(v, dtype=dtype, requires_grad=True) for k, v in params_np.items()}
@@ -87,30 +122,6 @@ def relu_flip_allowance(params_np, nodes, edge_attr, edge_index, target, num_lay
                             torch.tensor(edge_index, dtype=torch.int64), num_layers, m_steps, tape)
     loss = F.l1_loss(out, torch.tensor(target, dtype=dtype), reduction="sum") / out.shape[0]
     loss.backward(retain_graph=True)
-    units = []   # (|z| / rms, tape entry, flat index)
-    for t, (z, a) in enumerate(tape):
-        if z.numel() == 0:
-            continue
-        zz = z.detach()
-        rms = float(zz.pow(2).mean().sqrt())
-        if rms <= 0.0:
-            continue
-        near = torch.nonzero(zz.abs().flatten() < tau * rms).flatten()
-        for q in near.tolist():
-            units.append((float(zz.flatten()[q].abs()) / rms, t, q))
-    units.sort()
-    units = units[:max_units]
-    names = list(p.keys())
-    allow = {k: torch.zeros_like(v) for k, v in p.items()}
-    for _, t, q in units:
-        z, a = tape[t]
-        ga = a.grad.flatten()[q]   # d loss / d a_u: what reaches the unit from above whether or not its derivative lets it through
-        if float(ga) == 0.0:
-            continue
-        seed = torch.zeros_like(z).flatten()
-        seed[q] = ga
-        g = torch.autograd.grad(z, [p[k] for k in names], grad_outputs=seed.view_as(z), retain_graph=True, allow_unused=True)
-        for k, gk in zip(names, g):
-            if gk is not None:
-                allow[k] += gk.abs()
-    return {k: float(v.max()) for k, v in allow.items()}, len(units)
+    units = near_zero_units(tape, tau, max_units)
+    bounds = flip_bounds(tape, units, list(p.values()))
+    return {k: float(v.max()) for k, v in zip(p, bounds)}, len(units)

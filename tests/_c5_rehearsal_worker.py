@@ -20,8 +20,8 @@ def main():
     rank = dist.get_rank()
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
-    import test_gpu_planner as tp
-    s, _, _ = tp._solver(dev, cands=2)
+    from gpu_support import planner_solver
+    s, _, _ = planner_solver(dev, cands=2)
     s.collective_device = torch.device("cpu")   # collective payloads of the gloo rehearsal live on the host
     x0 = np.concatenate((s.sample_traj[:, 0], s.sample_traj[:, 1]))
     rng = np.random.default_rng(6)

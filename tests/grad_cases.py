@@ -17,7 +17,9 @@ import torch
 from conftest import BOUNDS, STATS
 from oracle import epd_oracle as orc
 from oracle import torch_epd
+import train_cases
 import width_cases as wc
+from yardstick import lazy, within
 
 F32 = np.float32
 R = wc.R
@@ -159,10 +161,9 @@ def radius_edges(name, layout=None, n=wc.SCENE_N, side=0.06):
 @functools.lru_cache(maxsize=None)
 def multigraph():
     """(pos [HUB_N, 3] float32, edge_index [2, HUB_E]): the seeded hub / duplicate / self-loop / isolated-node multigraph of
-    tests/test_gpu_train_regimes.py part B, in its random edge order, over seeded positions."""
-    import test_gpu_train_regimes as reg
-    ei = reg._hub_graph()
-    pos = (0.3 + 0.05 * np.random.Generator(np.random.PCG64(831)).random((reg.HUB_N, 3))).astype(F32)
+    tests/train_cases.py (hub_graph), in its random edge order, over seeded positions."""
+    ei = train_cases.hub_graph()
+    pos = (0.3 + 0.05 * np.random.Generator(np.random.PCG64(831)).random((train_cases.HUB_N, 3))).astype(F32)
     return pos, ei
 
 
@@ -200,3 +201,71 @@ def t64(a, grad=False, dtype=F64):
 def weights(shape, seed):
     """Seeded float32 weights w of a loss (out * w).sum()."""
     return np.random.default_rng(seed).standard_normal(shape).astype(F32)
+
+
+# ------------------------------------------------------------------------------------------ the ReLU flip allowance of input gradients
+def flip_allowance(run, leaves, tau=1e-5, max_units=256):
+    """oracle/torch_epd.relu_flip_allowance for INPUT gradients, per element instead of per tensor (an input gradient is not summed
+    over rows: one unit of one edge moves that edge's row and its two nodes' rows, and nothing else).  run(forward) evaluates the
+    float64 loss with `forward` as the model (torch_epd.epd_forward's signature; it records the hidden pre-activations).
+    Returns ([per-element bound of each leaf], number of near-zero units)."""
+    tape = []
+    run(lambda *args: torch_epd.epd_forward_taped(*args, tape)).backward(retain_graph=True)
+    units = torch_epd.near_zero_units(tape, tau, max_units)
+    bounds = torch_epd.flip_bounds(tape, units, leaves)
+    return [v.cpu().numpy() for v in bounds], len(units)   # (the leaves may live on a device: tests/test_gpu_offsets.py)
+
+
+# ------------------------------------------------------------------------------------------ the step scene: references and allowance
+L0 = wc.LAYOUTS["default"]
+
+
+def step_allowance(params, obs_np, targets, edge_lists, w_o, w_p, end_grad=None):
+    """flip_allowance of the unrolled restatement: ([bound for obs, bound for each target that is not None], units), evaluated once.
+    end_grad: the gradient w.r.t. the end state that stands for a loss behind it (first order)."""
+    def compute():
+        p = {k: torch.tensor(v, dtype=torch.float64) for k, v in params.items()}
+        rows = torch.tensor(rigid_rows(obs_np, L0))
+        obs = t64(obs_np, True)
+        tg = [None if t is None else t64(t, True) for t in targets]
+
+        def run(fwd):
+            cur = obs
+            for t, ei in zip(tg, edge_lists):
+                cur, pred = step(p, cur, L0, rows, t, torch.tensor(ei), STEP_DIMS[4], STEP_DIMS[5], forward=fwd)
+            if end_grad is not None:
+                return (cur * t64(end_grad)).sum()
+            return (cur * t64(w_o)).sum() + (pred * t64(w_p)).sum()
+        return flip_allowance(run, [obs] + [t for t in tg if t is not None])
+    return lazy(compute)
+
+
+def step_reference(params, obs_np, targets, edge_lists, w_o, w_p, dtype, end_loss=None):
+    """The unrolled restatement on the GPU's edge lists: gradients w.r.t. obs and every step's target of sum(next_obs * w_o) +
+    sum(pred * w_p) over the last step -- or of end_loss(next_obs) (a function returning the gradient w.r.t. next_obs)."""
+    p = {k: torch.tensor(v, dtype=dtype) for k, v in params.items()}
+    rows = torch.tensor(rigid_rows(obs_np, L0))
+    obs = t64(obs_np, True, dtype)
+    tg = [None if t is None else t64(t, True, dtype) for t in targets]
+    cur, preds = obs, []
+    for t, ei in zip(tg, edge_lists):
+        cur, pred = step(p, cur, L0, rows, t, torch.tensor(ei), STEP_DIMS[4], STEP_DIMS[5])
+        preds.append(pred.detach().numpy())
+    if end_loss is None:
+        ((cur * t64(w_o, dtype=dtype)).sum() + (pred * t64(w_p, dtype=dtype)).sum()).backward()
+    else:
+        cur.backward(gradient=torch.tensor(end_loss(cur.detach().numpy()), dtype=dtype))
+    return cur.detach().numpy(), preds, obs.grad.numpy(), [None if t is None else t.grad.numpy() for t in tg]
+
+
+def split(what, got, g64, g32, allow):
+    """d / d obs by the rule of tests/yardstick.py, position and control columns separately; the other columns -- zero (the
+    material label) or the loss's own weights passed through the window shift, at most one float32 addition -- to 1e-6 of their
+    maximum."""
+    c, u = slice(L0.cart, L0.cart + 3), slice(L0.ctrl, L0.ctrl + 3)
+    for name, cols in (("position", c), ("control", u)):
+        part = (slice(None), slice(None), cols)
+        within(f"{what} d_obs {name}", got[part], g64[part], g32[part], lambda: (allow()[0][0], allow()[1]), part)
+    rest = [i for i in range(L0.D) if not (c.start <= i < c.stop or u.start <= i < u.stop)]
+    err, bar = np.abs(got[:, :, rest] - g64[:, :, rest]).max(), 1e-6 * max(np.abs(g64[:, :, rest]).max(), 1e-30)
+    assert err <= bar, (what, "columns other than position and control", err, bar)

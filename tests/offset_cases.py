@@ -282,31 +282,6 @@ def input_grad_scale(t):
     return 1.0 / t
 
 
-def compare_gradients(got, ref_g, g32, grad_tol, allowance=None):
-    """tests/test_gpu_train.py's _compare_gradients rule on assembled references: every tensor within max(grad_tol, 4 x float32
-    torch's own error on it) of its float64 maximum; beyond that only what `allowance()` -- {name: max allowed change}, computed
-    on demand from oracle/torch_epd.py's relu_flip_allowance -- explains.  Returns the worst (name, err / tol, err, tol)."""
-    def worst_of(allow):
-        worst = ("", 0.0, 0.0, 0.0)
-        for name, r in ref_g.items():
-            g = np.asarray(got[name], np.float64)
-            assert g.shape == r.shape, name
-            scale = max(np.abs(r).max(), 1e-12)
-            err = np.abs(g - r).max() / scale
-            tol = max(grad_tol, 4.0 * np.abs(g32[name] - r).max() / scale) + (allow[name] / scale if allow else 0.0)
-            if err / tol > worst[1]:
-                worst = (name, err / tol, err, tol)
-        return worst
-    worst = worst_of(None)
-    if worst[1] > 1.0:
-        assert allowance is not None, worst
-        worst2 = worst_of(allowance())
-        print(f"[offsets] gradient {worst[0]}: err {worst[2]:.3e} of its maximum against tol {worst[3]:.3e}; with the ReLU flip allowance "
-              f"the worst is {worst2[0]}: err / (tol + allowance) {worst2[1]:.3f}")
-        assert worst2[1] <= 1.0, (worst, worst2)
-    return worst
-
-
 def assembled_flip_allowance(fam, params, targets, num_layers, m_steps, t):
     """relu_flip_allowance per class, assembled like the gradients (a sum of per-class bounds bounds the sum)."""
     from oracle import torch_epd

@@ -14,12 +14,12 @@ import torch
 
 from oracle import epd_oracle as orc
 import grad_cases as gc
-import width_cases as wc
+from sinkhorn_cases import sinkhorn_grad_ref
+from yardstick import GRAD_TOL  # noqa: F401  (the CPU regime test reads it from here)
 
-L0 = wc.LAYOUTS["default"]
+L0 = gc.L0
 T = 4
 MODEL_SEED = 841
-GRAD_TOL = 2e-4          # tests/test_gpu_train.py's, restated: the CPU regime test must not import a GPU test module
 TY_INIT = (0.5, 0.5, 0.4)
 F64 = torch.float64
 
@@ -165,3 +165,30 @@ def desired_cloud(obs_np):
     shift = np.array([0.03, -0.02, 0.05], np.float32)
     cloud = (obs_np[-1][fluid][:, L0.cart:L0.cart + 3] + shift + np.float32(0.004) * gc.weights((len(fluid), 3), 8)).astype(np.float32)
     return fluid, cloud
+
+
+# ------------------------------------------------------------------------------------------ the planner's objective
+def objective_reference(s, x, obs_np, init, fluid, cloud, eis, dtype, forward=None, end_grad=None):
+    """The objective assembled from the checked pieces, differentiated w.r.t. x (float64 leaf): torch interpolation and float64
+    rigid transform -> the restatement rollout in `dtype` on the device's edge lists -> sinkhorn_grad_ref at its end cloud -> the
+    float64 penalties.  forward / end_grad: flip_allowance's model and the first-order stand-in of the loss behind the end state.
+    Returns (value, gradient), or the scalar whose gradient the allowance needs."""
+    from gnn_manip_amd.planner import interpolate_trajectory_torch
+    xt = x if isinstance(x, torch.Tensor) else gc.t64(x, True)
+    rot, ty = interpolate_trajectory_torch(xt, s.sample_traj.shape[0], float(s.rx_init), s.scale_rot, s.scale_ty, float(s.max_rot), s.max_ty)
+    tr = poses(rot[:4], ty[:4], s.ty_init, gc.t64(init)).to(dtype)
+    p = p_of(dtype)
+    rows = torch.tensor(gc.rigid_rows(obs_np, L0))
+    cur = gc.t64(obs_np, dtype=dtype)
+    for t, ei in enumerate(eis):
+        kw = {} if forward is None else dict(forward=forward)
+        cur, _ = gc.step(p, cur, L0, rows, tr[t], torch.tensor(ei), gc.STEP_DIMS[4], gc.STEP_DIMS[5], **kw)
+    c = slice(L0.cart, L0.cart + 3)
+    if end_grad is not None:
+        return (cur[-1][fluid][:, c] * gc.t64(end_grad)).sum()
+    end = cur[-1][fluid][:, c]
+    w, dx, _ = sinkhorn_grad_ref(end.detach().numpy(), cloud)
+    v, a = velocity_acceleration_terms(torch.stack((rot[:4], ty[:4]), dim=1), float(s.max_rot), s.max_ty)
+    smooth = s.beta * (end.double() * gc.t64(dx)).sum() + s.alpha * v + s.gamma * a        # first order in the end cloud: its gradient is the loss's
+    smooth.backward()
+    return s.beta * w + s.alpha * float(v.detach()) + s.gamma * float(a.detach()), xt.grad.numpy().copy(), s.beta * dx

@@ -79,3 +79,19 @@ def state_post_transpose(g, L, rank, has_target):
     if has_target:
         d_target[rank[rigid]] = g[-1][rigid][:, c]
     return out, d_next, d_target
+
+
+def ctype(decl):
+    """The ctypes type _lib.py uses for a C parameter declaration."""
+    import ctypes as C
+    from gnn_manip_amd import _lib
+    decl = decl.strip()
+    if "*" in decl:
+        if decl.startswith("const gm_feature_desc"):
+            return _lib._FD
+        if decl.startswith("const gm_model_desc"):
+            return _lib._MD
+        if decl.startswith("int64_t*"):
+            return C.POINTER(C.c_int64)
+        return C.c_void_p
+    return {"int64_t": C.c_int64, "int": C.c_int, "size_t": C.c_size_t}[decl.rsplit(" ", 1)[0]]

@@ -9,14 +9,9 @@ import torch
 
 from conftest import BOUNDS, CART, CTRL, MAT, STATS
 from oracle import epd_oracle as orc
+from gpu_support import dev
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
 
 
 def _write_dataset(g, root):

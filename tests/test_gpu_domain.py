@@ -8,30 +8,12 @@ import torch
 
 from conftest import BOUNDS, CART, CTRL, MAT, STATS
 from oracle import epd_oracle as orc
+from gpu_support import dev, load_model as _model, poison_allocator as _poison, to_dev as _t
 
 pytestmark = pytest.mark.gpu
 
 KW = dict(stats=STATS, bounds=BOUNDS, conn_r=0.015, cartesian_idx=CART, material_idx=MAT)
 MLPS = ["encoder.phi_edge", "encoder.phi_node", "processor.0.phi_edge", "processor.1.phi_node", "decoder"]
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
-
-
-def _t(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
-
-def _model(params, dims, dev, kernel):
-    from gnn_manip_amd import EncProcDecGNN
-    m = EncProcDecGNN(*dims)
-    m.load_state_dict({k: torch.from_numpy(v) for k, v in params.items()}, strict=True)
-    m = m.to(dev)
-    m.set_edge_kernel(kernel)
-    return m
 
 
 @pytest.fixture(scope="module")
@@ -149,13 +131,6 @@ def test_deep_mlp_scales_stay_in_range(dev, graph):
         out = m.forward(_t(nodes, dev), _t(ea, dev), _t(ei, dev)).cpu().numpy()
     assert m.status() == ei.shape[1]
     assert _rel(out, ref) <= 2e-5, _rel(out, ref)
-
-
-def _poison(dev, pattern):
-    """Fill the caching allocator's free blocks: what torch.empty hands out next (the library's workspaces) holds `pattern`."""
-    junk = [torch.full((n,), pattern, device=dev) for n in (1 << 24, 1 << 22, 1 << 20, 3 << 18, 5 << 16, 7 << 12, 65536 * 3, 257)]
-    junk += [torch.full((n,), 0x7fc00000, dtype=torch.int32, device=dev) for n in (1 << 22, 1 << 20, 1 << 18, 4096)]
-    del junk
 
 
 @pytest.mark.parametrize("pattern", [float("nan"), float("inf"), 3e38])

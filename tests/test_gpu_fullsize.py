@@ -7,24 +7,15 @@ import torch
 
 from conftest import BOUNDS, CART, CTRL, MAT, STATS
 from oracle import epd_oracle as orc
+from gpu_support import dev, to_dev as _t
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
 
 
 @pytest.fixture(scope="module")
 def scene100k():
     from gnn_manip_amd import scene
     return scene.make_scene(100000, seed=5)
-
-
-def _t(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
 
 
 @pytest.mark.parametrize("n,seed", [(100000, 5), (50000, 6)])

@@ -14,32 +14,11 @@ import torch
 import graph_cases as gc
 from conftest import BOUNDS, CART, CTRL, MAT, STATS, assert_forward_close
 from oracle import epd_oracle as orc
+from gpu_support import dev, graph_attr, load_model as _model, to_dev as _t
 
 pytestmark = pytest.mark.gpu
 
 GM_ERR_INVALID_ARGUMENT, GM_ERR_UNSUPPORTED = -1, -2
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
-
-
-def _t(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
-
-def _model(params, dims, dev):
-    from gnn_manip_amd import EncProcDecGNN
-    m = EncProcDecGNN(*dims)
-    m.load_state_dict({k: torch.from_numpy(v) for k, v in params.items()}, strict=True)
-    return m.to(dev)
-
-
-def _ga():
-    from gnn_manip_amd import GraphBoundedMultimaterialControl
-    return GraphBoundedMultimaterialControl(0.015, STATS, CART, MAT, CTRL, BOUNDS)
 
 
 # ------------------------------------------------------------------ reading a csr workspace back
@@ -210,12 +189,12 @@ def test_one_rollout_step_on_ties_and_coincident_rows(dev, name):
     for kernel in ("auto", "hm", "sys_all"):
         m.set_edge_kernel(kernel)
         with torch.no_grad():
-            eng_1 = RolloutEngine(m, _ga(), n, device=dev)
+            eng_1 = RolloutEngine(m, graph_attr(0.015), n, device=dev)
             singles = []
             for k in range(3):
                 singles.append(eng_1.rollout(_t(obs, dev), _t(trajs[k], dev), horizon=1).cpu().numpy())
                 assert eng_1.status() == e_ref, (kernel, k)
-            eng_b = RolloutEngine(m, _ga(), n, device=dev, candidates=3)
+            eng_b = RolloutEngine(m, graph_attr(0.015), n, device=dev, candidates=3)
             out = eng_b.rollout_candidates(_t(obs, dev), _t(trajs, dev)).cpu().numpy()
             assert eng_b.status() == 3 * e_ref, kernel
         for k in range(3):
@@ -245,10 +224,10 @@ def test_renumbered_step_with_and_without_an_overfull_cell(dev, name):
             params[f"processor.{k}.phi_edge.5.{leaf}"] = params[f"processor.{k}.phi_edge.5.{leaf}"] * np.float32(1.0 / 32.0)
     m = _model(params, (25, 4, 3, 128, 2, 10), dev)
     with torch.no_grad():
-        plain = RolloutEngine(m, _ga(), n, device=dev, renumber=False)
+        plain = RolloutEngine(m, graph_attr(0.015), n, device=dev, renumber=False)
         f0, r0 = plain.rollout(_t(obs, dev), _t(trajs[0], dev), horizon=1, record=True)
         e0 = plain.status()
-        ren = RolloutEngine(m, _ga(), n, device=dev, renumber=True)
+        ren = RolloutEngine(m, graph_attr(0.015), n, device=dev, renumber=True)
         ren.RENUMBER_EVERY = 1
         f1, r1 = ren.rollout(_t(obs, dev), _t(trajs[0], dev), horizon=1, record=True)
         e1 = ren.status()

@@ -1,113 +1,25 @@
 """Input gradients on the MI355X: EncProcDecGNN's d_nodes / d_edge_attr (gm_epd_backward_inputs), the backward kernels of the
 per-step feature functions and the integrator, and RolloutEngine.differentiable_step, alone and unrolled into SamplesLoss.
 
-Yardstick: tests/test_gpu_train.py's, per tensor: max |g - g64| <= max(GRAD_TOL, 4 x the error of the same plain-PyTorch float32
-computation) x max |g64|, g64 the float64 reference (oracle/torch_epd.py for the model, tests/grad_cases.py for the step, both
-checked on the CPU).  Losses are (out * w).sum() with seeded w.  Forward values: conftest.assert_forward_close (1e-5).  Every
+Yardstick: the rule of tests/yardstick.py (`within`), the flip allowance per element; g64 the float64 reference (oracle/torch_epd.py
+for the model, tests/grad_cases.py for the step, both checked on the CPU).  Losses are (out * w).sum() with seeded w.  Forward values: conftest.assert_forward_close (1e-5).  Every
 figure is printed before it is asserted."""
 import numpy as np
 import pytest
 import torch
 
-from conftest import BOUNDS, STATS, assert_forward_close
+from conftest import STATS, assert_forward_close
 from oracle import epd_oracle as orc
 from oracle import torch_epd
 import grad_cases as gc
 import width_cases as wc
-from test_gpu_train import GRAD_TOL, _graph, _model, _t
-from test_gpu_train_regimes import HUB_E, HUB_N, _benchmark_graph, _cus, _hub_graph, _tiles
-from test_gpu_sinkhorn_grad import sinkhorn_grad_ref
+from gpu_support import cus as _cus, dev, graph_attr, load_model as _model, step_engine as _engine, tiles as _tiles, to_dev as _t
+from grad_cases import L0, flip_allowance, split as _split, step_allowance as _step_allowance, step_reference as _step_reference
+from sinkhorn_cases import sinkhorn_grad_ref
+from train_cases import HUB_E, HUB_N, benchmark_graph as _benchmark_graph, graph as _graph, hub_graph as _hub_graph
+from yardstick import lazy as _lazy, within as _within
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
-
-
-def _within(what, got, g64, g32, allow=None, part=None):
-    """The gradient yardstick on one tensor.  An element beyond it is allowed only what the ReLU units of THIS input whose float64
-    pre-activation lies within 1e-5 of its Linear's rms of zero can explain (flip_allowance below; allow: a function returning
-    that bound per element, part: the slice of it that `got` is): computed, not assumed, and only where the plain bound fails."""
-    got, g64, g32 = (np.asarray(a, np.float64) for a in (got, g64, g32))
-    assert got.shape == g64.shape and np.isfinite(got).all(), what
-    scale = max(np.abs(g64).max(), 1e-12)
-    err = np.abs(got - g64)
-    tol = max(GRAD_TOL, 4.0 * np.abs(g32 - g64).max() / scale)
-    print(f"\n[input grads] {what}: err {err.max() / scale:.3e} tol {tol:.3e} (float32 torch {np.abs(g32 - g64).max() / scale:.3e}), max |g64| {scale:.3e}")
-    if err.max() / scale <= tol:
-        return
-    assert allow is not None, (what, err.max() / scale, tol)
-    a, n_units = allow()
-    a = a if part is None else a[part]
-    over = err > tol * scale
-    worst = float((err / (tol * scale + a)).max())
-    print(f"[input grads] {what}: {int(over.sum())} elements in {int(over.reshape(len(over), -1).any(axis=1).sum())} rows beyond the plain bound; "
-          f"relu flip allowance over {n_units} units: worst err / (tol + allowance) {worst:.3e}")
-    assert worst <= 1.0, (what, err.max() / scale, tol, worst, n_units)
-
-
-def _epd_forward_taped(tape):
-    """oracle/torch_epd.epd_forward that records every hidden pre-activation and activation (torch_epd._mlp_taped)."""
-    def forward(p, nodes, edge_attr, edge_index, num_layers, m_steps):
-        j, i = edge_index[0], edge_index[1]
-        h = torch_epd._mlp_taped(p, "encoder.phi_node", nodes, num_layers, True, tape)
-        e = torch_epd._mlp_taped(p, "encoder.phi_edge", edge_attr, num_layers, True, tape)
-        for k in range(m_steps):
-            e_new = torch_epd._mlp_taped(p, f"processor.{k}.phi_edge", torch.cat((h[i], h[j], e), dim=1), num_layers, True, tape)
-            agg = torch.zeros_like(h).index_add_(0, i, e_new)
-            h_new = torch_epd._mlp_taped(p, f"processor.{k}.phi_node", torch.cat((h, agg), dim=1), num_layers, True, tape)
-            h, e = h + h_new, e + e_new
-        return torch_epd._mlp_taped(p, "decoder", h, num_layers, False, tape)
-    return forward
-
-
-def flip_allowance(run, leaves, tau=1e-5, max_units=256):
-    """oracle/torch_epd.relu_flip_allowance restated for INPUT gradients, per element instead of per tensor (an input gradient is
-    not summed over rows: one unit of one edge moves that edge's row and its two nodes' rows, and nothing else).  run(forward)
-    evaluates the float64 loss with `forward` as the model; for every hidden unit with |z| < tau rms(z of its Linear) -- at most
-    max_units, the closest to zero first -- the gradient that toggling it alone sends back to `leaves`, absolute values summed
-    over the units (first order).  Returns ([per-element bound of each leaf], number of such units)."""
-    tape = []
-    run(_epd_forward_taped(tape)).backward(retain_graph=True)
-    units = []
-    for t, (z, a) in enumerate(tape):
-        if z.numel() == 0:
-            continue
-        zz = z.detach()
-        rms = float(zz.pow(2).mean().sqrt())
-        if rms <= 0.0:
-            continue
-        for q in torch.nonzero(zz.abs().flatten() < tau * rms).flatten().tolist():
-            units.append((float(zz.flatten()[q].abs()) / rms, t, q))
-    units.sort()
-    units = units[:max_units]
-    allow = [torch.zeros_like(v) for v in leaves]
-    for _, t, q in units:
-        z, a = tape[t]
-        ga = a.grad.flatten()[q]
-        if float(ga) == 0.0:
-            continue
-        seed = torch.zeros_like(z).flatten()
-        seed[q] = ga
-        g = torch.autograd.grad(z, leaves, grad_outputs=seed.view_as(z), retain_graph=True, allow_unused=True)
-        for acc, gk in zip(allow, g):
-            if gk is not None:
-                acc += gk.abs()
-    return [v.cpu().numpy() for v in allow], len(units)   # (the leaves may live on a device: tests/test_gpu_offsets.py)
-
-
-def _lazy(fn):
-    """fn() evaluated at most once: the tensors of one run share one allowance."""
-    box = []
-
-    def get():
-        if not box:
-            box.append(fn())
-        return box[0]
-    return get
 
 
 # ------------------------------------------------------------------------------------------ the fused model
@@ -296,13 +208,6 @@ def test_edge_features_backward_without_edges(dev):
     assert pos.grad.shape == (10, 3) and float(pos.grad.abs().max()) == 0.0
 
 
-def _ga(L):
-    from gnn_manip_amd import GraphBoundedMultimaterial, GraphBoundedMultimaterialControl
-    if L.ctrl < 0:
-        return GraphBoundedMultimaterial(gc.R, STATS, L.cart_idx, [L.mat], BOUNDS)
-    return GraphBoundedMultimaterialControl(gc.R, STATS, L.cart_idx, [L.mat], L.ctrl_idx, BOUNDS)
-
-
 @pytest.mark.parametrize("name", list(wc.LAYOUTS))
 def test_node_features_and_integrator_backward(dev, name):
     """Piecewise-linear functions with coefficients 1 / vel_std, 1 / r, acc_std, 2 and 1: every gradient entry is one or two
@@ -320,7 +225,7 @@ def test_node_features_and_integrator_backward(dev, name):
     ref_next = gc.integrate(p64, o64, L)
     (ref_next * gc.t64(w_p)).sum().backward()
     obs = _t(obs_np, dev).requires_grad_(True)
-    nodes = _ga(L).compute_nodes(obs)
+    nodes = graph_attr(gc.R, L).compute_nodes(obs)
     assert nodes.grad_fn is not None
     (nodes * _t(w_n, dev)).sum().backward()
     assert_forward_close(nodes.detach().cpu().numpy(), ref_nodes.detach().numpy(), what=name)
@@ -341,63 +246,6 @@ def test_node_features_and_integrator_backward(dev, name):
 
 
 # ------------------------------------------------------------------------------------------ the step
-L0 = wc.LAYOUTS["default"]
-
-
-def _engine(m, dev, candidates=1):
-    from gnn_manip_amd import RolloutEngine
-    return RolloutEngine(m, _ga(L0), gc.STEP_N, k_steps=L0.k, data_dim=L0.D, device=dev, candidates=candidates)
-
-
-def _step_allowance(params, obs_np, targets, edge_lists, w_o, w_p, end_grad=None):
-    """flip_allowance of the unrolled restatement: ([bound for obs, bound for each target that is not None], units), evaluated once.
-    end_grad: the gradient w.r.t. the end state that stands for a loss behind it (first order)."""
-    def compute():
-        p = {k: torch.tensor(v, dtype=torch.float64) for k, v in params.items()}
-        rows = torch.tensor(gc.rigid_rows(obs_np, L0))
-        obs = gc.t64(obs_np, True)
-        tg = [None if t is None else gc.t64(t, True) for t in targets]
-
-        def run(fwd):
-            cur = obs
-            for t, ei in zip(tg, edge_lists):
-                cur, pred = gc.step(p, cur, L0, rows, t, torch.tensor(ei), gc.STEP_DIMS[4], gc.STEP_DIMS[5], forward=fwd)
-            if end_grad is not None:
-                return (cur * gc.t64(end_grad)).sum()
-            return (cur * gc.t64(w_o)).sum() + (pred * gc.t64(w_p)).sum()
-        return flip_allowance(run, [obs] + [t for t in tg if t is not None])
-    return _lazy(compute)
-
-
-def _step_reference(params, obs_np, targets, edge_lists, w_o, w_p, dtype, end_loss=None):
-    """The unrolled restatement on the GPU's edge lists: gradients w.r.t. obs and every step's target of sum(next_obs * w_o) +
-    sum(pred * w_p) over the last step -- or of end_loss(next_obs) (a function returning the gradient w.r.t. next_obs)."""
-    p = {k: torch.tensor(v, dtype=dtype) for k, v in params.items()}
-    rows = torch.tensor(gc.rigid_rows(obs_np, L0))
-    obs = gc.t64(obs_np, True, dtype)
-    tg = [None if t is None else gc.t64(t, True, dtype) for t in targets]
-    cur, preds = obs, []
-    for t, ei in zip(tg, edge_lists):
-        cur, pred = gc.step(p, cur, L0, rows, t, torch.tensor(ei), gc.STEP_DIMS[4], gc.STEP_DIMS[5])
-        preds.append(pred.detach().numpy())
-    if end_loss is None:
-        ((cur * gc.t64(w_o, dtype=dtype)).sum() + (pred * gc.t64(w_p, dtype=dtype)).sum()).backward()
-    else:
-        cur.backward(gradient=torch.tensor(end_loss(cur.detach().numpy()), dtype=dtype))
-    return cur.detach().numpy(), preds, obs.grad.numpy(), [None if t is None else t.grad.numpy() for t in tg]
-
-
-def _split(what, got, g64, g32, allow):
-    """d / d obs, position and control columns separately; the other columns -- zero (the material label) or the loss's own
-    weights passed through the window shift, at most one float32 addition -- to 1e-6 of their maximum."""
-    c, u = slice(L0.cart, L0.cart + 3), slice(L0.ctrl, L0.ctrl + 3)
-    for name, cols in (("position", c), ("control", u)):
-        part = (slice(None), slice(None), cols)
-        _within(f"{what} d_obs {name}", got[part], g64[part], g32[part], lambda: (allow()[0][0], allow()[1]), part)
-    rest = [i for i in range(L0.D) if not (c.start <= i < c.stop or u.start <= i < u.stop)]
-    assert np.abs(got[:, :, rest] - g64[:, :, rest]).max() <= 1e-6 * max(np.abs(g64[:, :, rest]).max(), 1e-30)
-
-
 @pytest.mark.parametrize("with_target", [True, False])
 def test_differentiable_step(dev, with_target):
     params = orc.init_params(*gc.STEP_DIMS, 841)
@@ -478,7 +326,7 @@ def test_differentiable_step_with_two_candidates(dev):
 
 def test_two_steps_unrolled_into_samples_loss(dev):
     """d SamplesLoss(end cloud, target cloud) / d (initial obs, both steps' rigid_target) through two differentiable steps,
-    against the float64 two-step restatement on the edge lists the GPU returned and test_gpu_sinkhorn_grad's float64 Sinkhorn
+    against the float64 two-step restatement on the edge lists the GPU returned and sinkhorn_cases' float64 Sinkhorn
     gradient at the restatement's own end cloud."""
     from gnn_manip_amd.losses import SamplesLoss
     params = orc.init_params(*gc.STEP_DIMS, 841)

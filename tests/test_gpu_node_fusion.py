@@ -10,17 +10,11 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import BOUNDS, CART, CTRL, MAT, STATS
+from gpu_support import dev, graph_attr, poison_allocator as _poison, torch_random_graph as _random_graph
 
 pytestmark = pytest.mark.gpu
 
 DIMS = (25, 4, 3, 128, 2, 3)
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
 
 
 @pytest.fixture(scope="module")
@@ -30,21 +24,6 @@ def model(dev):
     m = EncProcDecGNN(*DIMS).to(dev)
     m.set_edge_kernel("sys_all")
     return m
-
-
-def _ga():
-    from gnn_manip_amd import GraphBoundedMultimaterialControl
-    return GraphBoundedMultimaterialControl(0.015, STATS, CART, MAT, CTRL, BOUNDS)
-
-
-def _random_graph(n, e, seed, dev, hub=0):
-    """n nodes, e random edges; hub > 0: the first `hub` edges all arrive at node n // 2."""
-    g = torch.Generator().manual_seed(seed)
-    nodes = torch.randn(n, DIMS[0], generator=g)
-    ea = torch.randn(e, DIMS[1], generator=g)
-    ei = torch.randint(0, n, (2, e), generator=g)
-    ei[1, :hub] = n // 2
-    return nodes.to(dev), ea.to(dev), ei.to(dev)
 
 
 def _forward(m, nodes, ea, ei, fused):
@@ -121,9 +100,9 @@ def test_candidate_of_a_batch_equals_the_graph_alone(dev, model):
     trajs = np.stack([scene.rigid_drift_trajectory(obs, steps, seed=100 + c, step_size=3e-4) for c in range(b)])
     model.set_node_fusion(True)
     with torch.no_grad():
-        eng_b = RolloutEngine(model, _ga(), n, device=dev, candidates=b)
+        eng_b = RolloutEngine(model, graph_attr(0.015), n, device=dev, candidates=b)
         out = eng_b.rollout_candidates(torch.from_numpy(obs).to(dev), torch.from_numpy(trajs).to(dev))
-        eng_1 = RolloutEngine(model, _ga(), n, device=dev)
+        eng_1 = RolloutEngine(model, graph_attr(0.015), n, device=dev)
         one = eng_1.rollout(torch.from_numpy(obs).to(dev), torch.from_numpy(trajs[1]).to(dev), horizon=steps)
     assert torch.isfinite(one).all()
     assert torch.equal(out[1], one), float((out[1] - one).abs().max())
@@ -135,7 +114,7 @@ def test_rollout_states_do_not_depend_on_the_switch(dev, model):
     n, steps = 3000, 3
     obs = scene.make_scene(n, seed=41, side=0.12)
     traj = torch.from_numpy(scene.rigid_drift_trajectory(obs, steps)).to(dev)
-    eng = RolloutEngine(model, _ga(), n, device=dev)
+    eng = RolloutEngine(model, graph_attr(0.015), n, device=dev)
     got = {}
     for fused in (True, False):
         model.set_node_fusion(fused)
@@ -144,13 +123,6 @@ def test_rollout_states_do_not_depend_on_the_switch(dev, model):
     model.set_node_fusion(True)
     assert torch.isfinite(got[True]).all()
     assert torch.equal(got[True], got[False]), float((got[True] - got[False]).abs().max())
-
-
-def _poison(dev, pattern):
-    """Fill the caching allocator's free blocks: what torch.empty hands out next (the library's workspaces) holds `pattern`."""
-    junk = [torch.full((n,), pattern, device=dev) for n in (1 << 24, 1 << 22, 1 << 20, 3 << 18, 5 << 16, 7 << 12, 65536 * 3, 257)]
-    junk += [torch.full((n,), 0x7fc00000, dtype=torch.int32, device=dev) for n in (1 << 22, 1 << 20, 1 << 18, 4096)]
-    del junk
 
 
 def test_fused_forward_does_not_depend_on_what_the_workspaces_held(dev, model):
@@ -165,7 +137,7 @@ def test_fused_forward_does_not_depend_on_what_the_workspaces_held(dev, model):
     def runs():
         with torch.no_grad():
             out = model.forward(nodes, ea, ei).clone()
-            eng = RolloutEngine(model, _ga(), obs.shape[1], device=dev)
+            eng = RolloutEngine(model, graph_attr(0.015), obs.shape[1], device=dev)
             state = eng.rollout(torch.from_numpy(obs).to(dev), traj, horizon=2).clone()
         model.status()
         torch.cuda.synchronize()

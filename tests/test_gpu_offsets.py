@@ -4,7 +4,7 @@ every copy held to its class's float64 reference).
 Every model is num_layers = 2, m_steps = 1 (F1s2 / F3s2: 2) with oracle.init_params weights.  The bars are the project's own: the forward bar of
 conftest.assert_forward_close (1e-5: against the tensor's maximum and per element), applied to every copy against its class
 reference (`_assert_copies_close` is that rule on the device, one reshape per class instead of T calls; the first and the last
-copy also go through assert_forward_close itself), and tests/test_gpu_train.py's gradient rule (GRAD_TOL, 4 x float32 torch's own
+copy also go through assert_forward_close itself), and the gradient rule of tests/yardstick.py (GRAD_TOL, 4 x float32 torch's own
 error, the ReLU flip allowance as the only fallback).
 
   case  path                                   what crosses
@@ -49,18 +49,16 @@ import offset_cases as oc
 from conftest import BOUNDS, CART, CTRL, MAT, STATS, assert_forward_close
 from oracle import epd_oracle as orc
 from oracle import torch_epd
+import yardstick
+from gpu_support import dev, load_model
+from grad_cases import flip_allowance
+from yardstick import GRAD_TOL
 
 pytestmark = pytest.mark.gpu
 
 NL, MS = 2, 1
 SEEDS = {128: 6128, 256: 6256}
 GIB = float(1 << 30)
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
 
 
 @pytest.fixture(autouse=True)
@@ -84,10 +82,7 @@ def _family(name):
 
 
 def _model(hidden, dev, ms=MS):
-    from gnn_manip_amd import EncProcDecGNN
-    m = EncProcDecGNN(*_dims(hidden, ms))
-    m.load_state_dict({k: torch.from_numpy(v) for k, v in _params(hidden, ms).items()}, strict=True)
-    return m.to(dev)
+    return load_model(_params(hidden, ms), _dims(hidden, ms), dev)
 
 
 @functools.lru_cache(maxsize=None)
@@ -262,8 +257,7 @@ def test_block_forward_gathers_and_returns_rows_in_the_callers_order(dev):
 
 # ------------------------------------------------------------------------------------------ T0 .. T2: the training step
 def _input_grad_check(what, view, g64, g32, scale_to_tiled, allowance):
-    """tests/test_gpu_input_grads.py's _within on the worst copy of a class: view [copies, rows, w] on the device."""
-    from test_gpu_train import GRAD_TOL
+    """yardstick.within's rule on the worst copy of a class: view [copies, rows, w] on the device."""
     ref = torch.from_numpy(np.ascontiguousarray(g64 * scale_to_tiled, np.float64)).to(view.device)
     assert bool(torch.isfinite(view).all()), what
     err = (view.double() - ref[None]).abs().amax(dim=0).cpu().numpy()
@@ -283,10 +277,9 @@ def _input_grad_check(what, view, g64, g32, scale_to_tiled, allowance):
 
 @functools.lru_cache(maxsize=None)
 def _class_input_allowance(hidden, c, dev):
-    """test_gpu_input_grads.flip_allowance of class c's loss sum |out - target| / n0: per-element bounds for (d_nodes, d_edge_attr).
+    """grad_cases.flip_allowance of class c's loss sum |out - target| / n0: per-element bounds for (d_nodes, d_edge_attr).
     Plain torch in float64 ON THE DEVICE (up to 256 backward passes through a 20 k-edge graph: seconds there, most of a minute on
     the host), once per class and module."""
-    from test_gpu_input_grads import flip_allowance
     fam = oc.dense_family()
     p = {k: torch.tensor(v, dtype=torch.float64, device=dev) for k, v in _params(hidden).items()}
     x = torch.tensor(fam.nodes[c], dtype=torch.float64, device=dev, requires_grad=True)
@@ -298,7 +291,6 @@ def _class_input_allowance(hidden, c, dev):
 
 
 def _training_step(dev, name, inputs_grad):
-    from test_gpu_train import GRAD_TOL
     case = _case(name)
     fam, t, hidden = case.family, case.copies, case.hidden
     n, e = case.regime["n"], case.regime["e"]
@@ -324,8 +316,8 @@ def _training_step(dev, name, inputs_grad):
     assert abs(float(loss.detach()) - ref_loss) <= 1e-5 * abs(ref_loss), (name, float(loss.detach()), ref_loss)
     got = {k: p.grad.cpu().numpy() for k, p in m.named_parameters()}
     assert all(np.isfinite(g).all() for g in got.values())
-    wg = oc.compare_gradients(got, oc.assemble_param_grads(r64, t), oc.assemble_param_grads(r32, t), GRAD_TOL,
-                              allowance=lambda: oc.assembled_flip_allowance(fam, params, targets, NL, MS, t))
+    wg, _ = yardstick.compare(got, oc.assemble_param_grads(r64, t), oc.assemble_param_grads(r32, t), tag="[offsets]",
+                              allowance=lambda: (oc.assembled_flip_allowance(fam, params, targets, NL, MS, t), None))
     print(f"[offsets] {name}: forward worst copy error {wf[0]:.3e} (bar 1e-5), per-element ratio {wf[1]:.3f}; worst parameter gradient "
           f"{wg[0]}: err {wg[2]:.3e} of its maximum, tol {wg[3]:.3e} (err / tol {wg[1]:.3f})")
     if inputs_grad:
@@ -456,27 +448,8 @@ def _block_flip_allowance(hidden, c, dev):
     h_new = torch_epd._mlp_taped(p, "processor.0.phi_node", torch.cat((h, torch.zeros_like(h).index_add_(0, i, e_new)), dim=1), NL, True, tape)
     wh, we = _block_weights(hidden, c)
     ((h_new * t64(wh)).sum() + (e_new * t64(we)).sum()).backward(retain_graph=True)
-    units = []
-    for t, (z, a) in enumerate(tape):
-        zz = z.detach()
-        rms = float(zz.pow(2).mean().sqrt())
-        near = torch.nonzero(zz.abs().flatten() < 1e-5 * rms).flatten()
-        units += [(v / rms, t, q) for v, q in zip(zz.flatten()[near].abs().tolist(), near.tolist())]
-    units.sort()
-    names = list(p)
-    allow = {k: torch.zeros_like(v) for k, v in p.items()}
-    for _, t, q in units[:256]:
-        z, a = tape[t]
-        ga = a.grad.flatten()[q]
-        if float(ga) == 0.0:
-            continue
-        seed = torch.zeros_like(z).flatten()
-        seed[q] = ga
-        g = torch.autograd.grad(z, [p[k] for k in names], grad_outputs=seed.view_as(z), retain_graph=True, allow_unused=True)
-        for k, gk in zip(names, g):
-            if gk is not None:
-                allow[k] += gk.abs()
-    return {k[len("processor.0."):]: float(v.max()) for k, v in allow.items()}
+    bounds = torch_epd.flip_bounds(tape, torch_epd.near_zero_units(tape), list(p.values()))
+    return {k[len("processor.0."):]: float(v.max()) for k, v in zip(p, bounds)}
 
 
 def test_block_backward_just_under_the_guard(dev):
@@ -488,7 +461,6 @@ def test_block_backward_just_under_the_guard(dev):
     gradient does not depend on where the row lies (the batch invariant), and a stand-alone block's input gradients at ordinary
     sizes are tests/test_gpu_train_regimes.py's subject."""
     from gnn_manip_amd._lib import ModelDesc, lib
-    from test_gpu_train import GRAD_TOL
     case = _case("T1g")
     fam, t, hidden = case.family, case.copies, case.hidden
     n, e = case.regime["n"], case.regime["e"]
@@ -529,8 +501,8 @@ def test_block_backward_just_under_the_guard(dev):
     got = {k: q.grad.cpu().numpy() for k, q in blk.named_parameters()}
     def allowance():
         per_class = [_block_flip_allowance(hidden, c, dev) for c in range(oc.K)]
-        return {k: sum(mu * per_class[c][k] for c, mu in enumerate(mult)) for k in per_class[0]}
-    wg = oc.compare_gradients(got, g64, g32, GRAD_TOL, allowance=allowance)
+        return {k: sum(mu * per_class[c][k] for c, mu in enumerate(mult)) for k in per_class[0]}, None
+    wg, _ = yardstick.compare(got, g64, g32, allowance=allowance, tag="[offsets]")
     # input gradients: every copy is its class graph alone, bit for bit
     dhv = oc.copies_view(dh, fam, t)
     full, rem = divmod(t, oc.K)

@@ -14,32 +14,11 @@ import torch
 
 from conftest import BOUNDS, CART, CTRL, G1_CASES, MAT, STATS, assert_forward_close
 from oracle import epd_oracle as orc
+from gpu_support import dev, graph_attr, load_model as _model, to_dev as _t
 
 pytestmark = pytest.mark.gpu
 
 KW = dict(stats=STATS, bounds=BOUNDS, conn_r=0.015, cartesian_idx=CART, material_idx=MAT)
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
-
-
-def _t(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
-
-def _model(params, dims, dev):
-    from gnn_manip_amd import EncProcDecGNN
-    m = EncProcDecGNN(*dims)
-    m.load_state_dict({k: torch.from_numpy(v) for k, v in params.items()}, strict=True)
-    return m.to(dev)
-
-
-def _ga():
-    from gnn_manip_amd import GraphBoundedMultimaterialControl
-    return GraphBoundedMultimaterialControl(0.015, STATS, CART, MAT, CTRL, BOUNDS)
 
 
 # ------------------------------------------------------------------ K1 radius graph
@@ -100,7 +79,7 @@ def test_edge_features_golden(golden, dev, case):
 def test_node_features_process_collate_golden(golden, dev):
     from gnn_manip_amd import GraphBoundedMultimaterial
     g = golden("g4_features.npz")
-    ga = _ga()
+    ga = graph_attr(0.015)
     n1 = ga.compute_nodes(_t(g["obs_a"], dev))
     np.testing.assert_allclose(n1.cpu().numpy(), g["nodes_ctrl_a"], rtol=2e-7, atol=1e-7)
     gn = GraphBoundedMultimaterial(0.015, STATS, CART, MAT, BOUNDS)
@@ -348,7 +327,7 @@ def test_rollout_golden_g8(golden, dev):
     obs0 = g["obs0"]
     rigid = obs0[-1, :, 1] == 1
     traj = get_rigid_body_trajectory(g["traj_rot"], g["traj_ty"], horizon, [0.5, 0.5, 0.4], _t(obs0[-1][rigid][:, 2:5], dev))
-    eng = RolloutEngine(m, _ga(), obs0.shape[1], device=dev)
+    eng = RolloutEngine(m, graph_attr(0.015), obs0.shape[1], device=dev)
     with torch.no_grad():
         final, recs = eng.rollout(_t(obs0, dev), traj, horizon=horizon, record=True)
     final, recs = final.cpu().numpy(), recs.cpu().numpy()
@@ -364,7 +343,7 @@ def test_rollout_vs_oracle_whole_state(dev):
     traj = scene.rigid_drift_trajectory(obs, steps - 1)  # last step has no scripted pose (traj_utils.py:130-131)
     params = orc.init_params(25, 4, 3, 128, 2, 10, 92)
     m = _model(params, (25, 4, 3, 128, 2, 10), dev)
-    eng = RolloutEngine(m, _ga(), n, device=dev)
+    eng = RolloutEngine(m, graph_attr(0.015), n, device=dev)
     with torch.no_grad():
         final = eng.rollout(_t(obs, dev), _t(traj, dev), horizon=steps).cpu().numpy()
     ref = orc.rollout(params, obs, traj, steps, STATS, BOUNDS, 0.015, CART, MAT, CTRL)
@@ -384,7 +363,7 @@ def test_rollout_small_and_ragged_scenes(dev, n, side, seed):
     traj = scene.rigid_drift_trajectory(obs, 2)
     params = orc.init_params(25, 4, 3, 128, 2, 3, seed)
     m = _model(params, (25, 4, 3, 128, 2, 3), dev)
-    eng = RolloutEngine(m, _ga(), n, device=dev)
+    eng = RolloutEngine(m, graph_attr(0.015), n, device=dev)
     with torch.no_grad():
         final = eng.rollout(_t(obs, dev), _t(traj, dev), horizon=2).cpu().numpy()
     ref = orc.rollout(params, obs, traj, 2, STATS, BOUNDS, 0.015, CART, MAT, CTRL, 2, 3)
@@ -408,10 +387,10 @@ def test_renumbered_rollout_matches_the_plain_one_and_the_oracle(dev):
     params = orc.init_params(25, 4, 3, 128, 2, 10, 314)
     m = _model(params, (25, 4, 3, 128, 2, 10), dev)
     with torch.no_grad():
-        plain = RolloutEngine(m, _ga(), n, device=dev, renumber=False)
+        plain = RolloutEngine(m, graph_attr(0.015), n, device=dev, renumber=False)
         f0, r0 = plain.rollout(_t(obs, dev), _t(traj, dev), horizon=steps, record=True)
         e0 = plain.status()
-        ren = RolloutEngine(m, _ga(), n, device=dev, renumber=True)
+        ren = RolloutEngine(m, graph_attr(0.015), n, device=dev, renumber=True)
         ren.RENUMBER_EVERY = 2                                # three steps = a chunk of two and one of one: the re-sort path too
         f1, r1 = ren.rollout(_t(obs, dev), _t(traj, dev), horizon=steps, record=True)
         e1 = ren.status()
@@ -429,7 +408,7 @@ def test_renumbered_rollout_matches_the_plain_one_and_the_oracle(dev):
     np.testing.assert_allclose(f1[:, :, 2:8], ref[:, :, 2:8], rtol=0, atol=5e-6)
     trajs = np.stack([traj, scene.rigid_drift_trajectory(obs, steps, seed=315, step_size=3e-4)])
     with torch.no_grad():
-        eng_b = RolloutEngine(m, _ga(), n, device=dev, candidates=b, renumber=True)
+        eng_b = RolloutEngine(m, graph_attr(0.015), n, device=dev, candidates=b, renumber=True)
         eng_b.RENUMBER_EVERY = 2
         out = eng_b.rollout_candidates(_t(obs, dev), _t(trajs, dev)).cpu().numpy()
         one = ren.rollout(_t(obs, dev), _t(trajs[1], dev), horizon=steps).cpu().numpy()
@@ -438,7 +417,7 @@ def test_renumbered_rollout_matches_the_plain_one_and_the_oracle(dev):
         long_r = ren.rollout(_t(obs, dev), _t(traj[:1], dev), horizon=steps).cpu().numpy()
     np.testing.assert_allclose(long_r[:, :, 2:8], long_p[:, :, 2:8], rtol=0, atol=2e-6)
     assert np.array_equal(out[0], f1) and np.array_equal(out[1], one)
-    assert RolloutEngine(m, _ga(), RolloutEngine.RENUMBER_MIN_NODES, device=dev).renumber and not RolloutEngine(m, _ga(), 5000, device=dev).renumber
+    assert RolloutEngine(m, graph_attr(0.015), RolloutEngine.RENUMBER_MIN_NODES, device=dev).renumber and not RolloutEngine(m, graph_attr(0.015), 5000, device=dev).renumber
 
 
 def test_gm_rollout_renumbers_behind_the_c_abi(dev):
@@ -456,10 +435,10 @@ def test_gm_rollout_renumbers_behind_the_c_abi(dev):
     params = orc.init_params(25, 4, 3, 128, 2, 3, 324)
     m = _model(params, (25, 4, 3, 128, 2, 3), dev)
     with torch.no_grad():
-        ren = RolloutEngine(m, _ga(), n, device=dev, renumber=True)
+        ren = RolloutEngine(m, graph_attr(0.015), n, device=dev, renumber=True)
         ren.RENUMBER_EVERY = every
         want, want_rec = ren.rollout(_t(obs, dev), _t(traj, dev), horizon=steps, record=True)
-        plain = RolloutEngine(m, _ga(), n, device=dev, renumber=False)
+        plain = RolloutEngine(m, graph_attr(0.015), n, device=dev, renumber=False)
         want_plain = plain.rollout(_t(obs, dev), _t(traj, dev), horizon=steps)
     L = lib()
     fdesc, mdesc = ren.fdesc, ModelDesc(*m.model_desc())
@@ -522,9 +501,9 @@ def test_candidate_batched_rollout_matches_independent_rollouts(dev):
     for kernel in ("auto", "hm", "sys_all"):
         m.set_edge_kernel(kernel)
         with torch.no_grad():
-            eng_b = RolloutEngine(m, _ga(), n, device=dev, candidates=b)
+            eng_b = RolloutEngine(m, graph_attr(0.015), n, device=dev, candidates=b)
             out = eng_b.rollout_candidates(_t(obs, dev), _t(trajs, dev)).cpu().numpy()
-            eng_1 = RolloutEngine(m, _ga(), n, device=dev)
+            eng_1 = RolloutEngine(m, graph_attr(0.015), n, device=dev)
             for c in range(b):
                 one = eng_1.rollout(_t(obs, dev), _t(trajs[c], dev), horizon=steps).cpu().numpy()
                 assert np.array_equal(out[c], one), (kernel, c, np.abs(out[c] - one).max())
@@ -615,7 +594,7 @@ def test_block_convention_switch_forward_block_and_rollout(dev, conv):
     np.testing.assert_allclose(h1.cpu().numpy(), h1o, rtol=1e-5, atol=5e-6)
     # rollout: the destination sort of the radius graph follows the flow
     traj = scene.rigid_drift_trajectory(obs, 2)
-    eng = RolloutEngine(m, _ga(), n, device=dev)
+    eng = RolloutEngine(m, graph_attr(0.015), n, device=dev)
     with torch.no_grad():
         final = eng.rollout(_t(obs, dev), _t(traj, dev), horizon=2).cpu().numpy()
     fwd = lambda nn, ee, ii: orc.epd_forward(params, nn, ee, ii, 2, 3, **conv)
@@ -712,7 +691,7 @@ def test_epd_any_size_vs_oracle(dev, hid, nl, ms):
     n = 600
     obs = scene.make_scene(n, seed=85, side=0.07)
     traj = scene.rigid_drift_trajectory(obs, 1)
-    eng = RolloutEngine(m, _ga(), n, device=dev)
+    eng = RolloutEngine(m, graph_attr(0.015), n, device=dev)
     with torch.no_grad():
         final = eng.rollout(_t(obs, dev), _t(traj, dev), horizon=1).cpu().numpy()
     fwd = lambda nn, ee, ii: orc.epd_forward(params, nn, ee, ii, nl, ms)
@@ -783,7 +762,7 @@ def test_profile_kinds_cover_a_rollout_step_and_report_when_they_run_out(dev):
     n = 400
     obs = scene.make_scene(n, seed=71, side=0.06)
     m = _model(orc.init_params(25, 4, 3, 128, 2, 10, 72), (25, 4, 3, 128, 2, 10), dev)
-    eng = RolloutEngine(m, _ga(), n, device=dev)
+    eng = RolloutEngine(m, graph_attr(0.015), n, device=dev)
     state = _t(obs, dev)
     eng.set_scene(state)
     traj = _t(scene.rigid_drift_trajectory(obs, 8, seed=73, step_size=1e-5), dev)
@@ -880,7 +859,7 @@ def test_hidden_sizes_between_the_instantiated_widths(dev, hidden, nl, ms):
     np.testing.assert_allclose(e1.cpu().numpy(), e1o, rtol=1e-5, atol=1e-5)
     if hidden in (96, 100):
         traj = scene.rigid_drift_trajectory(obs, 2)
-        eng = RolloutEngine(m, _ga(), obs.shape[1], device=dev)
+        eng = RolloutEngine(m, graph_attr(0.015), obs.shape[1], device=dev)
         with torch.no_grad():
             final = eng.rollout(_t(obs, dev), _t(traj, dev), horizon=2).cpu().numpy()
         refr = orc.rollout(params, obs, traj, 2, STATS, BOUNDS, 0.015, CART, MAT, CTRL, nl, ms)

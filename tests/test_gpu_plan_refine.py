@@ -5,9 +5,8 @@ cma_objective's values) and optimize_trajectory(refine=...).  The scene is the s
 (tests/test_plan_refine_cases.py).  Every figure is printed before it is asserted."""
 import numpy as np
 import pytest
-import torch
 
-from test_gpu_rollout_grad import _solver
+from gpu_support import dev, step_solver as _solver
 
 pytestmark = pytest.mark.gpu
 
@@ -21,12 +20,6 @@ pytestmark = pytest.mark.gpu
 # 0.003 and 0.01 decrease at every iterate; 0.03 and 0.1 rise at the first one (Adam's first step is lr in EVERY variable, whatever
 # the size of its gradient entry) and 0.1 turns around after five.  All four end below the start.
 LR = 0.01
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
 
 
 def _x0(s):

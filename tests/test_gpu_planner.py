@@ -6,18 +6,9 @@ import torch
 
 from conftest import BOUNDS, CART, CTRL, MAT, STATS
 from oracle import epd_oracle as orc
+from gpu_support import dev, planner_solver as _solver, to_dev as _t
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
-
-
-def _t(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
 
 
 @pytest.mark.parametrize("n,m,seed", [(150, 130, 1), (1000, 777, 2), (3, 5, 3), (2500, 2500, 4)])
@@ -105,27 +96,6 @@ def test_sinkhorn_diameter_keyword_and_bad_input(dev):
     xb[17, 1] = np.nan
     with pytest.raises(GMError):
         SamplesLoss(loss="sinkhorn", p=2, blur=.05).batched(_t(np.stack((x, xb)), dev), _t(y, dev))
-
-
-def _solver(dev, n=400, horizon=5, cands=4):
-    from gnn_manip_amd import EncProcDecGNN, GraphBoundedMultimaterialControl, scene
-    from gnn_manip_amd.planner import TrajectoryCMAsolver
-    obs = scene.make_scene(n, seed=31, side=0.06)
-    params = orc.init_params(25, 4, 3, 128, 2, 2, 31)
-    params["decoder.4.weight"] = params["decoder.4.weight"] * 1e-3  # keep the random-weight scene from exploding
-    m = EncProcDecGNN(25, 4, 3, 128, 2, 2)
-    m.load_state_dict({k: torch.from_numpy(v) for k, v in params.items()})
-    m = m.to(dev)
-    ga = GraphBoundedMultimaterialControl(0.015, STATS, CART, MAT, CTRL, BOUNDS)
-    state = (_t(obs, dev), _t(obs[-1, :, 2:5], dev))
-    s = TrajectoryCMAsolver(m, ga, state, 180, [0.5, 0.5, 0.4], scale_rot=1.0, scale_ty=1.0, alpha=0.1, beta=1000.0, gamma=0.05,
-                            penalty=1.0, rho=0.0, device=dev, cma_iter=3, cma_popsize=6, total_steps=horizon,
-                            candidates_per_gpu=cands)
-    sample = np.stack((180.0 - 0.4 * np.arange(horizon + 1), 1e-4 * np.arange(horizon + 1)), axis=1)
-    s.set_sample_traj(sample)
-    coffee = obs[-1, obs[-1, :, 1] == 0][:, 2:5]
-    s.desired_pos = _t(coffee + np.float32(0.002), dev)
-    return s, params, obs
 
 
 def test_batched_population_equals_one_by_one(dev):

@@ -19,43 +19,11 @@ import torch
 
 import precision_cases as pc
 from conftest import BOUNDS, CART, CTRL, MAT, STATS, assert_forward_close
+from gpu_support import dev, graph_attr, load_model as _model, poison_allocator as _poison, to_dev as _t
 
 pytestmark = pytest.mark.gpu
 
 R, K = 0.015, 20
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
-
-
-def _t(a, dev):
-    return torch.from_numpy(np.array(a, order="C", copy=True)).to(dev)
-
-
-def _model(params, dims, dev, kernel="auto", precision="f32"):
-    from gnn_manip_amd import EncProcDecGNN
-    m = EncProcDecGNN(*dims)
-    m.load_state_dict({k: torch.from_numpy(v) for k, v in params.items()}, strict=True)
-    m = m.to(dev)
-    m.set_edge_kernel(kernel)
-    if precision != "f32":
-        m.set_precision(precision)
-    return m
-
-
-def _ga():
-    from gnn_manip_amd import GraphBoundedMultimaterialControl
-    return GraphBoundedMultimaterialControl(R, STATS, CART, MAT, CTRL, BOUNDS)
-
-
-def _poison(dev, pattern):
-    """Fill the caching allocator's free blocks: what torch.empty hands out next (the library's workspaces) holds `pattern`."""
-    junk = [torch.full((n,), pattern, device=dev) for n in (1 << 24, 1 << 22, 1 << 20, 3 << 18, 5 << 16, 7 << 12, 65536 * 3, 257)]
-    junk += [torch.full((n,), 0x7fc00000, dtype=torch.int32, device=dev) for n in (1 << 22, 1 << 20, 1 << 18, 4096)]
-    del junk
 
 
 # ================================================================== A: one MLP deep, tight
@@ -155,7 +123,7 @@ def _everything(m, dev):
         m.status()
         out["encoder_h"], out["encoder_e"], _ = m.encoder(nodes, ea)
         out["block_h"], out["block_e"], _ = m.processor[0](h, e, ei_a)
-        eng = RolloutEngine(m, _ga(), obs.shape[1], device=dev)
+        eng = RolloutEngine(m, graph_attr(R), obs.shape[1], device=dev)
         out["rollout"] = eng.rollout(_t(obs, dev), _t(trajs[0], dev), horizon=2).clone()
         eng.status()
     return out
@@ -190,8 +158,8 @@ def test_c_candidate_of_a_batch_equals_the_scene_alone(dev, kernel):
     obs, trajs = _scene(n, 95, steps, b)
     m = _model(_c_params(), C_DIMS, dev, kernel, "f16")
     with torch.no_grad():
-        out = RolloutEngine(m, _ga(), n, device=dev, candidates=b).rollout_candidates(_t(obs, dev), _t(trajs, dev))
-        one = RolloutEngine(m, _ga(), n, device=dev).rollout(_t(obs, dev), _t(trajs[1], dev), horizon=steps)
+        out = RolloutEngine(m, graph_attr(R), n, device=dev, candidates=b).rollout_candidates(_t(obs, dev), _t(trajs, dev))
+        one = RolloutEngine(m, graph_attr(R), n, device=dev).rollout(_t(obs, dev), _t(trajs[1], dev), horizon=steps)
     assert torch.isfinite(one).all()
     assert torch.equal(out[1], one), float((out[1] - one).abs().max())
 
@@ -208,7 +176,7 @@ def test_c_a_step_is_the_forward_on_its_own_features(dev, kernel):
     n, D, k = obs.shape[1], obs.shape[2], obs.shape[0]
     cap = n * K
     m = _model(_c_params(), C_DIMS, dev, kernel, "f16")
-    eng = RolloutEngine(m, _ga(), n, device=dev)
+    eng = RolloutEngine(m, graph_attr(R), n, device=dev)
     a, target = _t(obs, dev), _t(trajs[0][0], dev)
     assert eng.set_scene(a) == target.shape[0] > 0
     pred_step = torch.empty((n, 3), dtype=torch.float32, device=dev)
@@ -276,7 +244,7 @@ def test_c_autograd_paths_do_not_read_the_switch(dev):
         out.square().sum().backward()
         r = {"train_forward": out.detach().clone(), "d_nodes": x.grad.clone(),
              "d_weight": m.decoder[0].weight.grad.clone()}
-        eng = RolloutEngine(m, _ga(), obs.shape[1], device=dev)
+        eng = RolloutEngine(m, graph_attr(R), obs.shape[1], device=dev)
         o0 = _t(obs, dev).requires_grad_(True)
         tr = _t(trajs[0], dev).requires_grad_(True)
         for sweep in ("autograd", "library"):

@@ -2,9 +2,8 @@
 backward (gm_epd_backward_inputs_only), RolloutEngine.differentiable_rollout (values, gradients, constant memory) and
 TrajectoryCMAsolver.loss_and_grad.
 
-Yardstick of the gradients through the model: tests/test_gpu_input_grads.py's `_within` -- per tensor, max |g - g64| <=
-max(GRAD_TOL, 4 x the error of the same plain-PyTorch float32 computation) x max |g64|, the ReLU flip allowance only where that
-plain bound fails -- against the float64 restatement of tests/rollout_grad_cases.py (checked on the CPU) on the edge lists the
+Yardstick of the gradients through the model: the rule of tests/yardstick.py (`within`), the flip allowance per element, against
+the float64 restatement of tests/rollout_grad_cases.py (checked on the CPU) on the edge lists the
 device returned.  The rigid transform's transpose is a plain sum: its bar is the element-wise float32 summation bound
 Nr 2^-23 sum |terms|.  Every figure is printed before it is asserted."""
 import ctypes as C
@@ -16,20 +15,14 @@ import torch
 from oracle import epd_oracle as orc
 import grad_cases as gc
 import rollout_grad_cases as rc
-from test_gpu_train import GRAD_TOL, _graph, _model, _t
-from test_gpu_train_regimes import HUB_E, HUB_N, _hub_graph
-from test_gpu_sinkhorn_grad import sinkhorn_grad_ref
-from test_gpu_input_grads import L0, _engine, _ga, _lazy, _split, _step_allowance, _step_reference, _within, flip_allowance
+from gpu_support import dev, load_model as _model, step_engine as _engine, step_solver as _solver, to_dev as _t
+from grad_cases import L0, flip_allowance, split as _split, step_allowance as _step_allowance, step_reference as _step_reference
+from rollout_grad_cases import objective_reference as _objective_reference
+from sinkhorn_cases import sinkhorn_grad_ref
+from train_cases import HUB_E, HUB_N, graph as _graph, hub_graph as _hub_graph
+from yardstick import lazy as _lazy, within as _within
 
 pytestmark = pytest.mark.gpu
-
-assert GRAD_TOL == rc.GRAD_TOL
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
 
 
 # ------------------------------------------------------------------------------------------ 1. the rigid transform's transpose
@@ -340,56 +333,6 @@ def test_rollout_memory_does_not_grow_with_the_horizon(dev):
 
 
 # ------------------------------------------------------------------------------------------ 5. the planner's objective
-def _solver(dev, cls=None):
-    """A TrajectoryCMAsolver on the step scene, total_steps = 4, traj_points = 2.  The cup frame is centred on the rigid rows and
-    the solver's rigid particles are their mirror images in x, so that the pose at the initial rotation (180 degrees) and no
-    translation is where the rigid rows are: the scripted poses then move them by a fraction of a millimetre per step."""
-    from gnn_manip_amd.planner import TrajectoryCMAsolver
-    from conftest import BOUNDS, STATS
-    obs_np = gc.step_state("step_a")
-    m = _model(rc.params(), gc.STEP_DIMS, dev)
-    rigid = obs_np[-1][gc.rigid_rows(obs_np, L0)][:, L0.cart:L0.cart + 3]
-    cx, cy, cz = (float(np.float32(round(float(v), 3))) for v in rigid.mean(axis=0))
-    ty_init = [cx, cz, cy]
-    state = (_t(obs_np, dev), _t(obs_np[-1][:, L0.cart:L0.cart + 3], dev))
-    s = (cls or TrajectoryCMAsolver)(m, _ga(L0), state, 180, ty_init, scale_rot=1.0, scale_ty=1.0, alpha=0.1, beta=1000.0, gamma=0.05,
-                                     penalty=1.0, rho=0.0, device=dev, total_steps=4, traj_points=2, candidates_per_gpu=1)
-    mirrored = rigid.copy()
-    mirrored[:, 0] = np.float32(2.0) * np.float32(cx) - rigid[:, 0]
-    s.rigid_particles = _t(mirrored, dev)
-    s.set_sample_traj(np.stack((180.0 - 0.4 * np.arange(5), 1e-4 * np.arange(5)), axis=1))
-    fluid, cloud = rc.desired_cloud(obs_np)
-    assert np.array_equal(fluid, np.nonzero(s.coffee_particles_idx.cpu().numpy())[0])
-    s.desired_pos = _t(cloud, dev)
-    return s, obs_np, mirrored, fluid, cloud
-
-
-def _objective_reference(s, x, obs_np, init, fluid, cloud, eis, dtype, forward=None, end_grad=None):
-    """The objective assembled from the checked pieces, differentiated w.r.t. x (float64 leaf): torch interpolation and float64
-    rigid transform -> the restatement rollout in `dtype` on the device's edge lists -> sinkhorn_grad_ref at its end cloud -> the
-    float64 penalties.  forward / end_grad: flip_allowance's model and the first-order stand-in of the loss behind the end state.
-    Returns (value, gradient), or the scalar whose gradient the allowance needs."""
-    from gnn_manip_amd.planner import interpolate_trajectory_torch
-    xt = x if isinstance(x, torch.Tensor) else gc.t64(x, True)
-    rot, ty = interpolate_trajectory_torch(xt, s.sample_traj.shape[0], float(s.rx_init), s.scale_rot, s.scale_ty, float(s.max_rot), s.max_ty)
-    tr = rc.poses(rot[:4], ty[:4], s.ty_init, gc.t64(init)).to(dtype)
-    p = rc.p_of(dtype)
-    rows = torch.tensor(gc.rigid_rows(obs_np, L0))
-    cur = gc.t64(obs_np, dtype=dtype)
-    for t, ei in enumerate(eis):
-        kw = {} if forward is None else dict(forward=forward)
-        cur, _ = gc.step(p, cur, L0, rows, tr[t], torch.tensor(ei), gc.STEP_DIMS[4], gc.STEP_DIMS[5], **kw)
-    c = slice(L0.cart, L0.cart + 3)
-    if end_grad is not None:
-        return (cur[-1][fluid][:, c] * gc.t64(end_grad)).sum()
-    end = cur[-1][fluid][:, c]
-    w, dx, _ = sinkhorn_grad_ref(end.detach().numpy(), cloud)
-    v, a = rc.velocity_acceleration_terms(torch.stack((rot[:4], ty[:4]), dim=1), float(s.max_rot), s.max_ty)
-    smooth = s.beta * (end.double() * gc.t64(dx)).sum() + s.alpha * v + s.gamma * a        # first order in the end cloud: its gradient is the loss's
-    smooth.backward()
-    return s.beta * w + s.alpha * float(v.detach()) + s.gamma * float(a.detach()), xt.grad.numpy().copy(), s.beta * dx
-
-
 @pytest.mark.parametrize("what", ["inside the limits", "one rotation increment clipped"])
 def test_loss_and_grad(dev, what):
     s, obs_np, init, fluid, cloud = _solver(dev)

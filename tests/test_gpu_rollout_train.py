@@ -1,9 +1,8 @@
 """Training through a rollout on the MI355X: gm_rollout_step_backward_train, gm_rollout_backward_train and the Python layer on top
 (RolloutEngine.step_backward(d_record=, grads=), differentiable_rollout(sweep="library", record=, params=)).
 
-Yardstick: tests/test_gpu_input_grads.py's `_within` / `_split` -- per tensor, max |g - g64| <= max(GRAD_TOL = 2e-4, 4 x the error
-of the same plain-PyTorch float32 computation) x max |g64|, the ReLU flip allowance (computed for this input, parameters among the
-leaves) only where that plain bound fails -- against the float64 restatement of tests/rollout_train_cases.py (reverse_sweep, checked
+Yardstick: the rule of tests/yardstick.py (`within`; grad_cases.split for d_obs), the flip allowance per element (computed for this
+input, parameters among the leaves) -- against the float64 restatement of tests/rollout_train_cases.py (reverse_sweep, checked
 on the CPU) on the edge lists get_connectivity returns for each pre-step window: the same kernel on the same input as the library's
 own list.  Where two calls run the same launches on the same operands the comparison is bit for bit.  Every figure is printed
 before it is asserted.
@@ -21,19 +20,14 @@ import grad_cases as gc
 import rollout_grad_cases as rc
 import rollout_train_cases as tc
 from oracle import epd_oracle as orc
-from test_gpu_train import _model, _t
-from test_gpu_input_grads import L0, _engine, _lazy, _split, _within, flip_allowance
-from test_gpu_rollout_vjp import K_NB, _bits, _edges_of, _forward_windows, _same_bits, _step_call, _sweep_call
+from gpu_support import (K_NB, dev, edges_of as _edges_of, forward_windows as _forward_windows, load_model as _model,
+                         step_call as _step_call, step_engine as _engine, sweep_call as _sweep_call, to_dev as _t)
+from grad_cases import L0, flip_allowance, split as _split
+from yardstick import bits as _bits, lazy as _lazy, same_bits as _same_bits, within as _within
 
 pytestmark = pytest.mark.gpu
 
 NAMES = list(rc.params())        # the state_dict's order, which is the order of `tensors` and `grads`
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
 
 
 # ------------------------------------------------------------------------------------------ the calls

@@ -3,9 +3,8 @@ gm_rollout_step_backward, gm_rollout_backward, and the Python layer on top (Roll
 differentiable_rollout(sweep="library"), TrajectoryCMAsolver.loss_and_grad(sweep="library")).
 
 Yardsticks.  The state transposes copy, negate or add two float32 terms: the device result IS the float32 restatement of
-tests/rollout_vjp_cases.py (checked on the CPU), bit for bit.  Gradients through the model: tests/test_gpu_input_grads.py's
-`_within` -- per tensor, max |g - g64| <= max(GRAD_TOL, 4 x the error of the same plain-PyTorch float32 computation) x max |g64|,
-the ReLU flip allowance only where that plain bound fails -- against the float64 restatements of tests/grad_cases.py (one step) and
+tests/rollout_vjp_cases.py (checked on the CPU), bit for bit.  Gradients through the model: the rule of
+tests/yardstick.py (`within`), the flip allowance per element, against the float64 restatements of tests/grad_cases.py (one step) and
 tests/rollout_grad_cases.py (reverse_sweep), on the edge lists get_connectivity returns for the pre-step positions: the same kernel
 on the same input as the library's own list.  Every figure is printed before it is asserted."""
 import ctypes as C
@@ -19,40 +18,22 @@ from conftest import BOUNDS, STATS
 import grad_cases as gc
 import rollout_grad_cases as rc
 import rollout_vjp_cases as vc
-from test_gpu_train import _model, _t
-from test_gpu_input_grads import L0, _engine, _split, _step_allowance, _step_reference, _within
+from gpu_support import (K_NB, dev, edges_of as _edges_of, feature_desc, forward_windows as _forward_windows, load_model as _model,
+                         step_call as _step_call, step_engine as _engine, step_solver as _solver, sweep_call as _sweep_call, to_dev as _t)
+from grad_cases import L0, flip_allowance, split as _split, step_allowance as _step_allowance, step_reference as _step_reference
+from rollout_grad_cases import objective_reference as _objective_reference
+from yardstick import bits as _bits, lazy as _lazy, same_bits as _same_bits, within as _within
 
 pytestmark = pytest.mark.gpu
 
-K_NB = 20
 W_SEED = 6
 
 
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
-
-
-def _bits(a):
-    a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def _same_bits(a, b):
-    return np.array_equal(_bits(a), _bits(b))
-
-
 # ------------------------------------------------------------------------------------------ 1. the state transposes alone
-def _fdesc(L):
-    from gnn_manip_amd.graph import make_feature_desc
-    return make_feature_desc(gc.R, STATS, BOUNDS, L.cart_idx, [L.mat], L.ctrl_idx, L.k, L.D)
-
-
 def _state_transposes(g_np, L, rank_np, has_target, dev):
     """Both transposes on outputs pre-filled with NaN: (pre: d_obs, d_target), (post: d_obs, d_next, d_target)."""
     from gnn_manip_amd._lib import check, current_stream, lib, ptr
-    fd = _fdesc(L)
+    fd = feature_desc(gc.R, L)
     n = g_np.shape[1]
     nr = int((rank_np >= 0).sum())
     g, rank = _t(g_np, dev), _t(rank_np, dev)
@@ -90,7 +71,7 @@ def test_state_transposes_without_a_rank_or_a_target_buffer(dev):
     from gnn_manip_amd._lib import check, current_stream, lib, ptr
     L, n = vc.LAYOUTS[6], 257
     g_np = vc.gradient(n, 6, 5)
-    g, fd = _t(g_np, dev), _fdesc(L)
+    g, fd = _t(g_np, dev), feature_desc(gc.R, L)
     d_obs, d_next = torch.full_like(g, float("nan")), torch.full((n, 3), float("nan"), device=dev)
     check(lib().gm_state_post_backward(ptr(g), n, C.byref(fd), None, 1, ptr(d_obs), ptr(d_next), None, current_stream(dev)))
     want = vc.state_post_transpose(g_np, L, vc.rigid_rank(n, "none"), True)
@@ -114,7 +95,7 @@ def test_state_transposes_refuse_bad_arguments(dev):
     L = lib()
     assert L.gm_state_pre_backward(ptr(g), n, C.byref(fd_n), ptr(rank), 1, ptr(out), None, current_stream(dev)) == -1
     assert L.gm_last_error() == b"gm_state_pre_backward: descriptor has no control columns"
-    fd = _fdesc(vc.LAYOUTS[6])
+    fd = feature_desc(gc.R, vc.LAYOUTS[6])
     assert L.gm_state_pre_backward(ptr(g), n, C.byref(fd), None, 1, ptr(out), None, current_stream(dev)) == -1       # no rank
     assert L.gm_last_error() == b"gm_state_pre_backward: null pointer"
     assert L.gm_state_pre_backward(None, n, C.byref(fd), ptr(rank), 1, ptr(out), None, current_stream(dev)) == -1
@@ -135,33 +116,6 @@ def _weights():
 
 def _end_grad(final):
     return _weights()
-
-
-def _edges_of(window, eng):
-    """The radius graph of a pre-step window: get_connectivity on its last frame's positions (state_pre moves no position)."""
-    from gnn_manip_amd import get_connectivity
-    c0 = L0.cart
-    s, r = get_connectivity(window[-1][:, c0:c0 + 3], gc.R, K_NB, eng.n_per if eng.candidates > 1 else None)
-    return torch.stack((s, r)).cpu().numpy()
-
-
-def _step_call(eng, obs, tgt, g, dev, ws=None):
-    """gm_rollout_step_backward through ctypes, in a workspace of the queried size (or the caller's): (d_obs, d_target, edges)."""
-    from gnn_manip_amd._lib import check, current_stream, lib, ptr
-    from gnn_manip_amd.graph import _ws
-    L = lib()
-    h, tensors, t_arr, md = eng._training_model()
-    need = L.gm_rollout_step_backward_workspace_bytes(C.byref(md), C.byref(eng.fdesc), eng.n, K_NB)
-    assert need > 0
-    if ws is None:
-        ws = _ws(need, dev)
-    assert ws.numel() >= need
-    d_obs = torch.full_like(obs, float("nan"))
-    d_tgt = None if tgt is None else torch.full_like(tgt, float("nan"))
-    e = C.c_int64(-1)
-    check(L.gm_rollout_step_backward(h, t_arr, len(tensors), ptr(obs), eng.n, C.byref(eng.fdesc), K_NB, ptr(eng.rigid_rank), ptr(tgt),
-                                     ptr(g), ptr(d_obs), ptr(d_tgt), C.byref(e), ptr(ws), need, current_stream(dev)))
-    return d_obs, d_tgt, int(e.value)
 
 
 _STEP_REF = {}
@@ -255,36 +209,6 @@ def test_step_vjp_with_two_candidates(dev):
 
 
 # ------------------------------------------------------------------------------------------ 4. the whole sweep
-def _forward_windows(eng, obs_np, traj_np, steps, dev):
-    """The inference rollout keeping every pre-step window: (windows [steps, k, N, D], final state)."""
-    obs = _t(obs_np, dev).clone()
-    eng.set_scene(obs)
-    tr = None if traj_np is None else _t(traj_np, dev)
-    windows = torch.empty((steps,) + tuple(obs.shape), device=dev)
-    for t in range(steps):
-        windows[t].copy_(obs)
-        eng.step(obs, None if tr is None or t >= tr.shape[0] else tr[t])
-    eng.status()
-    return windows, obs
-
-
-def _sweep_call(eng, windows, traj, steps, d_final, dev, ws=None, want_traj=True):
-    from gnn_manip_amd._lib import check, current_stream, lib, ptr
-    from gnn_manip_amd.graph import _ws
-    L = lib()
-    h, tensors, t_arr, md = eng._training_model()
-    need = L.gm_rollout_backward_workspace_bytes(C.byref(md), C.byref(eng.fdesc), eng.n, K_NB)
-    if ws is None:
-        ws = _ws(need, dev)
-    assert ws.numel() >= need
-    d_obs0 = torch.full_like(d_final, float("nan"))
-    d_traj = torch.full_like(traj, float("nan")) if traj is not None and want_traj else None
-    check(L.gm_rollout_backward(h, t_arr, len(tensors), ptr(windows), eng.n, C.byref(eng.fdesc), K_NB, ptr(eng.rigid_rank), ptr(traj),
-                                0 if traj is None else traj.shape[0], eng.n_rigid, steps, ptr(d_final), ptr(d_obs0), ptr(d_traj), ptr(ws),
-                                need, current_stream(dev)))
-    return d_obs0, d_traj
-
-
 @pytest.mark.parametrize("with_trajectory", [True, False])
 def test_rollout_backward(dev, with_trajectory):
     m = _model(rc.params(), gc.STEP_DIMS, dev)
@@ -399,10 +323,8 @@ def test_differentiable_rollout_with_the_library_sweep(dev, with_trajectory):
 
 def test_loss_and_grad_with_the_library_sweep(dev):
     """test_gpu_rollout_grad.test_loss_and_grad's bars, with the reverse sweep in the library: the value is cma_objective's to 1e-5,
-    the gradient is within `_within` of the float64 objective on the edge lists of the default sweep's recomputation (the same
+    the gradient is within the rule (`_within`) of the float64 objective on the edge lists of the default sweep's recomputation (the same
     windows, hence the same graphs)."""
-    from test_gpu_input_grads import _lazy, flip_allowance
-    from test_gpu_rollout_grad import _objective_reference, _solver
     s, obs_np, init, fluid, cloud = _solver(dev)
     x = np.concatenate((s.sample_traj[:, 0], s.sample_traj[:, 1])) * 1.1
     eis = []

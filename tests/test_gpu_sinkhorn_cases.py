@@ -13,18 +13,9 @@ import pytest
 import torch
 
 import sinkhorn_cases as sc
+from gpu_support import dev, to_dev as _t
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
-
-
-def _t(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
 
 
 def _loss(c=None, **kw):

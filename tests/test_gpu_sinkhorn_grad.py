@@ -3,70 +3,17 @@
 against single calls, the unchanged forward, edge cases, and composition with EncProcDecGNN's autograd Function.
 
 The convention (geomloss tensorized backend, unpinned like the forward): the potentials are detached and only the last
-extrapolation is differentiated, with the right-hand cloud of every cost matrix detached.  sinkhorn_grad_ref restates it; its
+extrapolation is differentiated, with the right-hand cloud of every cost matrix detached.  sinkhorn_cases.sinkhorn_grad_ref restates it; its
 own check against finite differences of oracle.sinkhorn_divergence is tests/test_sinkhorn_grad_reference.py."""
 import numpy as np
 import pytest
 import torch
 
 from oracle import epd_oracle as orc
+from sinkhorn_cases import sinkhorn_grad_ref
+from gpu_support import dev, to_dev as _t
 
 pytestmark = pytest.mark.gpu
-
-
-def sinkhorn_grad_ref(x, y, blur=0.05, scaling=0.5, diameter=None):
-    """(S, dS/dx, dS/dy) in float64: oracle.sinkhorn_divergence's schedule (oracle/epd_oracle.py, sinkhorn_divergence) run
-    without autograd, then the last extrapolation at blur^2 differentiated with C_xx = cost(x, x.detach()),
-    C_yy = cost(y, y.detach()), C_xy = cost(x, y.detach()), C_yx = cost(y, x.detach())."""
-    x = torch.as_tensor(np.asarray(x), dtype=torch.float64)
-    y = torch.as_tensor(np.asarray(y), dtype=torch.float64)
-    n, m = x.shape[0], y.shape[0]
-    if diameter is None:   # as the oracle: the bounding box of both clouds in float32
-        both = np.concatenate((x.numpy(), y.numpy())).astype(np.float32)
-        diameter = float(np.sqrt(((both.max(0) - both.min(0)).astype(np.float32) ** 2).sum(dtype=np.float32)))
-    diameter = float(np.float32(diameter))
-    if diameter == 0.0:
-        return 0.0, np.zeros(tuple(x.shape)), np.zeros(tuple(y.shape))
-    eps_s = [diameter ** 2] + [float(np.exp(e)) for e in np.arange(2 * np.log(diameter), 2 * np.log(blur), 2 * np.log(scaling))] + [blur ** 2]
-
-    def cost(a, b):
-        return ((a[:, None, :] - b[None, :, :]) ** 2).sum(-1) / 2
-
-    def softmin(eps, C, h):
-        return -eps * torch.logsumexp(h[None, :] - C / eps, dim=1)
-
-    la = torch.full((n,), -np.log(n), dtype=torch.float64)
-    lb = torch.full((m,), -np.log(m), dtype=torch.float64)
-    with torch.no_grad():
-        C_xx, C_yy, C_xy, C_yx = cost(x, x), cost(y, y), cost(x, y), cost(y, x)
-        eps = eps_s[0]
-        a_x, b_y = softmin(eps, C_xx, la), softmin(eps, C_yy, lb)
-        a_y, b_x = softmin(eps, C_yx, la), softmin(eps, C_xy, lb)
-        for eps in eps_s:
-            at_x, bt_y = softmin(eps, C_xx, la + a_x / eps), softmin(eps, C_yy, lb + b_y / eps)
-            at_y, bt_x = softmin(eps, C_yx, la + b_x / eps), softmin(eps, C_xy, lb + a_y / eps)
-            a_x, b_y = 0.5 * (a_x + at_x), 0.5 * (b_y + bt_y)
-            a_y, b_x = 0.5 * (a_y + at_y), 0.5 * (b_x + bt_x)
-        del C_xx, C_yy, C_xy, C_yx
-    xg, yg = x.clone().requires_grad_(), y.clone().requires_grad_()
-    eps = blur ** 2
-    fa_x = softmin(eps, cost(xg, x), la + a_x / eps)
-    fb_y = softmin(eps, cost(yg, y), lb + b_y / eps)
-    fa_y = softmin(eps, cost(yg, x), la + b_x / eps)
-    fb_x = softmin(eps, cost(xg, y), lb + a_y / eps)
-    S = (fb_x - fa_x).mean() + (fa_y - fb_y).mean()
-    dx, dy = torch.autograd.grad(S, (xg, yg))
-    return float(S.detach()), dx.numpy(), dy.numpy()
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
-
-
-def _t(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
 
 
 def _clouds(n, m, seed):

@@ -1,95 +1,23 @@
 """Training path on the MI355X: forward with tape + HIP backward (csrc/train.hip) against the plain-PyTorch
 float64 CPU restatement oracle/torch_epd.py (reference call site examples/train_dyn.py:45-72).
 
-Tolerances (floating point, stated here): forward 1e-5 relative (north_star).  Gradients: max |g - g64| <=
-max(2e-4, 4 x the error of the SAME plain-PyTorch model run in float32) x max |g64| per tensor, g64 = float64
-oracle.  The second term exists because the gradient of a ReLU network with an L1 loss is discontinuous:
-one pre-activation whose sign differs between float32 and float64 arithmetic moves a whole row's contribution
-(~1e-3 of a tensor at these sizes) -- plain PyTorch float32 shows exactly the same deviations on the same tensors.
+Tolerances: forward 1e-5 relative (north_star); gradients by the rule of tests/yardstick.py, per tensor, with
+oracle/torch_epd.py's relu_flip_allowance as the only fallback (gpu_support.check_training_step).
 
 Every graph here is small enough that a training workgroup runs ONE 128-row tile (at most 377 edge tiles, 20 node tiles) and is a
 radius graph of a scene.  Sizes past one tile per workgroup, hub / multigraph edge lists and the standalone InteractionNetwork's
-input gradients are in tests/test_gpu_train_regimes.py, held to the yardstick of this file."""
+input gradients are in tests/test_gpu_train_regimes.py, held to the same yardstick."""
 import numpy as np
 import pytest
 import torch
 
-from conftest import BOUNDS, CART, CTRL, MAT, STATS
+from conftest import CTRL
 from oracle import epd_oracle as orc
 from oracle import torch_epd
+from gpu_support import check_training_step as _check, compare_parameter_gradients as _compare_gradients, dev, load_model as _model, to_dev as _t
+from train_cases import KW, graph as _graph
 
 pytestmark = pytest.mark.gpu
-
-KW = dict(stats=STATS, bounds=BOUNDS, conn_r=0.015, cartesian_idx=CART, material_idx=MAT)
-GRAD_TOL = 2e-4
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
-
-
-def _t(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
-
-def _model(params, dims, dev):
-    from gnn_manip_amd import EncProcDecGNN
-    m = EncProcDecGNN(*dims)
-    m.load_state_dict({k: torch.from_numpy(v) for k, v in params.items()}, strict=True)
-    return m.to(dev)
-
-
-def _graph(n, side, seed):
-    from gnn_manip_amd import scene
-    obs = scene.make_scene(n, seed=seed, side=side)
-    nodes, ea, s, r, _ = orc.process(obs, None, control_idx=CTRL, **KW)
-    return nodes, ea, np.stack((s, r))
-
-
-def _check(m, params, nodes, ea, ei, dims, dev, seed, ref=None):
-    """ref: a dict that receives the target and the float64 / float32 reference gradients (target, ref_g, g32), for a caller that
-    looks at single tensors afterwards."""
-    rng = np.random.default_rng(seed)
-    target = rng.standard_normal((nodes.shape[0], dims[2])).astype(np.float32)
-    out = m.forward(_t(nodes, dev), _t(ea, dev), _t(ei, dev))
-    loss = torch.nn.functional.l1_loss(out, _t(target, dev), reduction="sum") / out.shape[0]  # train_dyn.py:65
-    loss.backward()
-    ref_out, ref_loss, ref_g = torch_epd.loss_and_grads(params, nodes, ea, ei, target, dims[4], dims[5])
-    _, _, g32 = torch_epd.loss_and_grads(params, nodes, ea, ei, target, dims[4], dims[5], torch.float32)
-    assert np.abs(out.detach().cpu().numpy() - ref_out).max() <= 1e-5 * max(np.abs(ref_out).max(), 1e-3)
-    assert abs(float(loss.detach()) - ref_loss) <= 1e-5 * abs(ref_loss)
-    if ref is not None:
-        ref.update(target=target, ref_g=ref_g, g32=g32)
-    return _compare_gradients(m, params, nodes, ea, ei, target, dims[4], dims[5], ref_g, g32)
-
-
-def _compare_gradients(m, params, nodes, ea, ei, target, num_layers, m_steps, ref_g, g32):
-    """Every parameter gradient against float64: within max(GRAD_TOL, 4 x PyTorch float32's own error on this tensor) of the
-    tensor's maximum.  A tensor beyond that is allowed only what the ReLU units of THIS input whose float64 pre-activation lies
-    within 1e-5 of its Linear's rms of zero can explain (oracle/torch_epd.py: relu_flip_allowance -- two float32-accurate
-    evaluations may disagree on the sign of exactly those units): the bound is computed, not assumed, and no seed is exempt.
-    Returns (worst (name, err / tol, err, tol) without the allowance, the same with it -- or None where it was not needed)."""
-    def worst_of(allow):
-        worst = ("", 0.0)
-        for name, p in m.named_parameters():
-            assert p.grad is not None, name
-            g, r = p.grad.cpu().numpy(), ref_g[name]
-            assert g.shape == r.shape, name
-            scale = max(np.abs(r).max(), 1e-12)
-            err = np.abs(g - r).max() / scale
-            tol = max(GRAD_TOL, 4.0 * np.abs(g32[name] - r).max() / scale) + (allow[name] / scale if allow else 0.0)
-            if err / tol > worst[1]:
-                worst = (name, err / tol, err, tol)
-        return worst
-    worst = worst_of(None)
-    if worst[1] > 1.0:
-        allow, n_units = torch_epd.relu_flip_allowance(params, nodes, ea, ei, target, num_layers, m_steps)
-        worst2 = worst_of(allow)
-        assert worst2[1] <= 1.0, (worst, worst2, n_units)
-        return worst, worst2
-    return worst, None
 
 
 @pytest.mark.parametrize("n,side,seed,m_steps", [(900, 0.075, 91, 3), (130, 0.3, 92, 2), (2500, 0.1, 93, 10)])
@@ -200,7 +128,7 @@ def test_backward_over_many_seeds(dev):
     """The single-seed tests above use seeds on which no pre-activation sits within rounding distance of zero.  Over a run of
     seeds that cannot hold: a ReLU whose sign differs between two float32-accurate evaluations moves the gradients by ~1e-4 ..
     1e-3 of a tensor -- and plain PyTorch float32 shows the same deviation from float64 on the same seed.  So every seed is held
-    to the yardstick of _check(): each gradient within max(GRAD_TOL, 4 x the error of PyTorch's own float32 evaluation of that
+    to the yardstick of _check() (tests/yardstick.py): each gradient within max(GRAD_TOL, 4 x the error of PyTorch's own float32 evaluation of that
     tensor on that seed) of the float64 gradient -- plus, only where that fails, what toggling the units of that seed whose
     float64 pre-activation is within 1e-5 rms of zero explains (_compare_gradients) -- and forward 1e-5.  No seed is exempt and
     none is hand-picked."""

@@ -19,15 +19,9 @@ import torch
 
 from oracle import torch_epd
 import train_domain_cases as tc
-from test_gpu_train import _compare_gradients, _model, _t
+from gpu_support import compare_parameter_gradients as _compare_gradients, dev, load_model as _model, to_dev as _t
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
 
 
 def _step(params, dims, nodes, ea, ei, w, dev):
@@ -176,7 +170,7 @@ def test_gradients_are_float32_accurate_where_they_are_continuous(dev, name):
 def test_rows_of_very_different_feature_magnitude(dev, hidden):
     """The training forward's twin of test_gpu_domain.test_rows_of_very_different_magnitude: node and edge rows scaled by
     10^U(-6, 4) with one all-zero row each, an uncalibrated model.  Prediction within max(2.5 x float32's error, 2.5e-6) of float64;
-    the gradients of the L1 loss to test_gpu_train.py's yardstick (sign flips are possible for this model)."""
+    the gradients of the L1 loss to the rule of tests/yardstick.py (sign flips are possible for this model)."""
     dims, params, nodes, ea, ei, seed = tc.row_magnitude_case(hidden)
     target = np.random.default_rng(seed).standard_normal((nodes.shape[0], 3)).astype(np.float32)
     m = _model(params, dims, dev)

@@ -1,6 +1,6 @@
-"""Training path on the MI355X in the regimes tests/test_gpu_train.py does not reach (same yardstick, imported from there:
-forward and loss 1e-5; every parameter gradient within max(GRAD_TOL, 4 x PyTorch float32's own error) of the float64 gradient of
-oracle/torch_epd.py relative to the tensor's maximum, relu_flip_allowance as the only fallback).
+"""Training path on the MI355X in the regimes tests/test_gpu_train.py does not reach (same yardstick: forward and loss 1e-5; every
+parameter gradient by the rule of tests/yardstick.py against the float64 gradient of oracle/torch_epd.py, relu_flip_allowance as the
+only fallback).
 
 A. More than one tile per workgroup.  train_bwd_kernel with a LayerNorm is launched with at most CUs x (2 at hidden <= 128, else 1)
    workgroups of 128 rows (csrc/train.hip: launch_train_bwd); train_fwd_kernel and the other backward kinds with at most 2048
@@ -22,29 +22,15 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import CTRL
 from oracle import epd_oracle as orc
 from oracle import torch_epd
-from test_gpu_train import GRAD_TOL, KW, _check, _graph, _model, _t
+import yardstick
+from gpu_support import check_training_step as _check, cus as _cus, dev, l1_step, load_model as _model, tiles as _tiles, to_dev as _t
+from train_cases import HUB_E, HUB_N, benchmark_graph as _benchmark_graph, graph as _graph, hub_graph as _hub_graph
 
 pytestmark = pytest.mark.gpu
 
-TILE = 128            # rows of one training tile (csrc/train.h)
 FWD_GRID_TILES = 2048  # grid_tiles(): workgroups of train_fwd_kernel and of the backward kinds without a LayerNorm
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
-
-
-def _cus(dev):
-    return int(torch.cuda.get_device_properties(dev).multi_processor_count)
-
-
-def _tiles(rows):
-    return -(-rows // TILE)
 
 
 def _report(case, res):
@@ -55,7 +41,7 @@ def _report(case, res):
 
 
 def _assert_every_parameter_is_compared(m, params, num_layers):
-    """_compare_gradients walks m.named_parameters(): those are all of the oracle's tensors, the LayerNorm weight / bias of every
+    """gpu_support.compare_parameter_gradients walks m.named_parameters(): those are all of the oracle's tensors, the LayerNorm weight / bias of every
     normed MLP (the tensors that depend on a workgroup's sums surviving from tile to tile) among them, and each has a gradient."""
     names = [k for k, _ in m.named_parameters()]
     assert sorted(names) == sorted(params.keys())
@@ -65,23 +51,12 @@ def _assert_every_parameter_is_compared(m, params, num_layers):
     assert all(p.grad is not None and bool(torch.isfinite(p.grad).all()) for p in m.parameters())
 
 
-@functools.lru_cache(maxsize=1)
-def _benchmark_graph():
-    """bench.py extra_train's batch: two make_scene(5000, side=0.152 * 0.8) scenes, seeds 100 / 101, collated."""
-    from gnn_manip_amd import scene
-    batch = [(scene.make_scene(5000, seed=100 + b, side=0.152 * 0.8), None) for b in range(2)]
-    nodes, ea, ei, _ = orc.process_collate(batch, control_idx=CTRL, **KW)
-    return nodes, ea, ei
-
-
 def _grads(m):
     return {k: p.grad.detach().clone() for k, p in m.named_parameters()}
 
 
 def _step(m, nodes, ea, ei, target, dev):
-    out = m.forward(_t(nodes, dev), _t(ea, dev), _t(ei, dev))
-    loss = torch.nn.functional.l1_loss(out, _t(target, dev), reduction="sum") / out.shape[0]
-    loss.backward()
+    out, _ = l1_step(m, nodes, ea, ei, target, dev)
     return out.detach(), _grads(m)
 
 
@@ -168,48 +143,6 @@ def test_hidden_64_three_layers_backward_walks_tiles(dev):
 
 
 # ------------------------------------------------------------------ B: graphs that are not radius graphs
-HUB_N, HUB_E = 400, 9000
-HUB_DST, HUB_DST2, HUB_SRC2 = 17, 201, 333     # node 17 is a hub destination AND a hub source
-SEND_ONLY, RECV_ONLY, ISOLATED = (390, 391, 392), (393, 394, 395), (396, 397, 398, 399)
-
-
-def _hub_graph(seed=73):
-    """edge_index [2, HUB_E] of a random multigraph over the nodes 0 .. 389 (in the style of
-    test_scatter_add_is_deterministic_with_hub_nodes) with, all at once: destinations of in-degree >= 700 and >= 300, sources of
-    out-degree >= 700 (the first hub destination) and >= 300, a block of exact duplicates, a block of self loops, nodes that only
-    send, only receive, or are in no edge -- and the columns in random order.  Every one of these properties is asserted on the
-    graph that was built."""
-    rng = np.random.Generator(np.random.PCG64(seed))
-    ei = rng.integers(0, 390, size=(2, HUB_E)).astype(np.int64)
-    ei[1, :700] = HUB_DST
-    ei[1, 700:1000] = HUB_DST2
-    ei[0, 1000:1700] = HUB_DST
-    ei[0, 1700:2000] = HUB_SRC2
-    ei[:, 2000:2064] = ei[:, 2100:2164]                 # 64 edges twice
-    ei[:, 2064:2072] = ei[:, 2100:2101]                 # ... and one of them ten times in all
-    ei[0, 2200:2300] = ei[1, 2200:2300]                 # self loops
-    ei[0, 2300:2320] = np.resize(SEND_ONLY, 20)
-    ei[1, 2320:2340] = np.resize(RECV_ONLY, 20)
-    order = rng.permutation(HUB_E)
-    ei = np.ascontiguousarray(ei[:, order])
-    # the properties the cases below are there for, on the graph that was built
-    indeg, outdeg = np.bincount(ei[1], minlength=HUB_N), np.bincount(ei[0], minlength=HUB_N)
-    assert indeg[HUB_DST] >= 700 and indeg[HUB_DST2] >= 300 and outdeg[HUB_DST] >= 700 and outdeg[HUB_SRC2] >= 300
-    rest = np.ones(HUB_N, bool)
-    rest[[HUB_DST, HUB_DST2, HUB_SRC2]] = False
-    assert indeg[rest].max() < 100 and outdeg[rest].max() < 100
-    assert indeg[HUB_DST] != outdeg[HUB_DST] and indeg[HUB_SRC2] < 100 and outdeg[HUB_DST2] < 100
-    assert all(indeg[v] == 0 and outdeg[v] > 0 for v in SEND_ONLY)
-    assert all(outdeg[v] == 0 and indeg[v] > 0 for v in RECV_ONLY)
-    assert all(indeg[v] == 0 and outdeg[v] == 0 for v in ISOLATED)
-    _, counts = np.unique(ei.T, axis=0, return_counts=True)
-    assert (counts >= 2).sum() >= 64 and counts.max() >= 10
-    assert (ei[0] == ei[1]).sum() >= 100
-    dst_sorted = np.argsort(ei[1], kind="stable")
-    assert not np.array_equal(dst_sorted, np.arange(HUB_E))   # the destination sort has something to undo
-    return ei
-
-
 @pytest.mark.parametrize("hidden,seed", [(64, 160), (128, 161), (256, 162)])
 def test_hub_graph_full_model(dev, hidden, seed):
     """EncProcDecGNN under autograd on the hub graph: the source-sorted CSR, segment sums of 700 and 300 rows with and without
@@ -271,31 +204,10 @@ def _block_flip_allowance(params, h, e, ei, wh, we, conv, tau=1e-5, max_units=25
     h_new, e_new = _block_forward(p, h_t, e_t, torch.tensor(ei, dtype=torch.int64), conv,
                                   lambda pp, prefix, x, nl, norm: torch_epd._mlp_taped(pp, prefix, x, nl, norm, tape))
     ((h_new * torch.tensor(wh, dtype=dtype)).sum() + (e_new * torch.tensor(we, dtype=dtype)).sum()).backward(retain_graph=True)
-    units = []
-    for t, (z, a) in enumerate(tape):
-        zz = z.detach().flatten()
-        rms = float(zz.pow(2).mean().sqrt())
-        if rms <= 0.0:
-            continue
-        for q in torch.nonzero(zz.abs() < tau * rms).flatten().tolist():
-            units.append((float(zz[q].abs()) / rms, t, q))
-    units.sort()
-    units = units[:max_units]
+    units = torch_epd.near_zero_units(tape, tau, max_units)
     leaves = dict(p, dh_in=h_t, de_in=e_t)
-    names = list(leaves)
-    allow = {k: torch.zeros_like(v) for k, v in leaves.items()}
-    for _, t, q in units:
-        z, a = tape[t]
-        ga = a.grad.flatten()[q]
-        if float(ga) == 0.0:
-            continue
-        seed = torch.zeros_like(z).flatten()
-        seed[q] = ga
-        g = torch.autograd.grad(z, [leaves[k] for k in names], grad_outputs=seed.view_as(z), retain_graph=True, allow_unused=True)
-        for k, gk in zip(names, g):
-            if gk is not None:
-                allow[k] += gk.abs()
-    return {k: v.numpy() for k, v in allow.items()}, len(units)
+    bounds = torch_epd.flip_bounds(tape, units, list(leaves.values()))
+    return {k: v.numpy() for k, v in zip(leaves, bounds)}, len(units)
 
 
 def _block_step(blk, h, e, ei, wh, we, dev):
@@ -308,37 +220,11 @@ def _block_step(blk, h, e, ei, wh, we, dev):
     return dict({k: p.grad.detach().clone() for k, p in blk.named_parameters()}, dh_in=x.grad.detach().clone(), de_in=a.grad.detach().clone())
 
 
-def _tolerances(ref64, ref32):
-    """Per tensor: max(2e-4, 4 x float32's error) -- of the tensor's maximum (test_gpu_train.py's rule, no fallback)."""
-    tol = {}
-    for k, r in ref64.items():
-        scale = max(np.abs(r).max(), 1e-12)
-        tol[k] = max(GRAD_TOL, 4.0 * np.abs(ref32[k] - r).max() / scale) * scale
-    return tol
-
-
-def _assert_within(case, got, ref64, tol, allowance):
-    """Every tensor of `got` within tol of float64; one beyond it is allowed only what `allowance()` (the relu-flip bound of the
-    same inputs, computed when needed) adds, as in test_gpu_train.py's _compare_gradients."""
+def _assert_within(case, got, ref64, ref32, allowance):
+    """Every tensor of `got` within the rule of float64; one beyond it is allowed only what `allowance()` (the relu-flip bound of the
+    same inputs, per element, computed when needed) adds."""
     assert sorted(got) == sorted(ref64)
-
-    def worst_of(allow):
-        worst = ("", 0.0)
-        for k, r in ref64.items():
-            g = got[k].cpu().numpy()
-            assert g.shape == r.shape, k
-            err = np.abs(g - r).max()
-            ratio = (np.abs(g - r) / (tol[k] + (allow[k] if allow else 0.0))).max()
-            if ratio > worst[1]:
-                worst = (k, float(ratio), float(err), float(tol[k]))
-        return worst
-    worst = worst_of(None)
-    print(f"\n[regimes] {case}: worst err/tol {worst[1]:.3f} at {worst[0]!r}")
-    if worst[1] > 1.0:
-        allow, n_units = allowance()
-        worst2 = worst_of(allow)
-        print(f"[regimes] {case}: relu-flip fallback ran ({n_units} units): worst with allowance {worst2[1]:.3f} at {worst2[0]!r}")
-        assert worst2[1] <= 1.0, (case, worst, worst2, n_units)
+    yardstick.compare({k: v.cpu().numpy() for k, v in got.items()}, ref64, ref32, allowance, tag="[regimes]", what=case)
 
 
 @pytest.mark.parametrize("hidden,conv,seed", [(128, DEFAULT_CONV, 170), (64, DEFAULT_CONV, 171), (256, DEFAULT_CONV, 172), (128, OTHER_CONV, 173)])
@@ -365,11 +251,10 @@ def test_hub_graph_standalone_interaction_network(dev, hidden, conv, seed):
 
     ref64 = _block_reference(params, h, e, ei, wh, we, conv, torch.float64)
     ref32 = _block_reference(params, h, e, ei, wh, we, conv, torch.float32)
-    tol = _tolerances(ref64, ref32)
     allowance = functools.lru_cache(maxsize=None)(lambda: _block_flip_allowance(params, h, e, ei, wh, we, conv))
     got = _block_step(blk, h, e, ei, wh, we, dev)
     what = f"hub graph, standalone block, hidden {hidden}, {conv['flow']}"
-    _assert_within(what, got, ref64, tol, allowance)
+    _assert_within(what, got, ref64, ref32, allowance)
 
     # the same call again: identical bits
     again = _block_step(blk, h, e, ei, wh, we, dev)
@@ -381,12 +266,13 @@ def test_hub_graph_standalone_interaction_network(dev, hidden, conv, seed):
     ei_p, e_p, we_p = np.ascontiguousarray(ei[:, perm]), e[perm], we[perm]
     ref64_p = _block_reference(params, h, e_p, ei_p, wh, we_p, conv, torch.float64)
     ref32_p = _block_reference(params, h, e_p, ei_p, wh, we_p, conv, torch.float32)
-    tol_p = _tolerances(ref64_p, ref32_p)
     got_p = _block_step(blk, h, e_p, ei_p, wh, we_p, dev)
-    _assert_within(what + ", edges permuted", got_p, ref64_p, tol_p,
+    _assert_within(what + ", edges permuted", got_p, ref64_p, ref32_p,
                    functools.lru_cache(maxsize=None)(lambda: _block_flip_allowance(params, h, e_p, ei_p, wh, we_p, conv)))
     err = np.abs(got_p["de_in"].cpu().numpy() - got["de_in"].cpu().numpy()[perm])
-    bound = min(tol["de_in"], tol_p["de_in"])
+    tol, scale, _ = yardstick.tolerance(ref64["de_in"], ref32["de_in"])
+    tol_p, scale_p, _ = yardstick.tolerance(ref64_p["de_in"], ref32_p["de_in"])
+    bound = min(tol * scale, tol_p * scale_p)
     print(f"[regimes] {what}: de_in of the permuted call against de_in[perm]: err/tol {err.max() / bound:.3f}")
     if err.max() > bound:     # two evaluations may disagree on the sign of the same near-zero units (the same set in either edge order)
         assert (err <= bound + allowance()[0]["de_in"][perm]).all(), (float(err.max()), bound)

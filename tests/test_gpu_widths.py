@@ -3,7 +3,7 @@ test_width_cases.py, which also shows that every forward case is well conditione
 
 Part A -- models at (node_dim, edge_dim, out_dim) other than (25, 4, 3): the fused forward with every processor kernel and hidden
 size, the standalone encoder, training and the GraphIndependent input gradients, each at the bar the suite already uses for it
-(assert_forward_close; rtol 1e-5 / atol 3e-6 for the encoder's latents; test_gpu_train.py's gradient yardstick, imported).
+(assert_forward_close; rtol 1e-5 / atol 3e-6 for the encoder's latents; the gradient yardstick of tests/yardstick.py through gpu_support.check_training_step).
 Part B -- feature descriptors other than (k 6, D 8, cart 2, material 1, control 5): the stand-alone feature / integrator / state
 kernels against the oracle and a numpy restatement, gm_rigid_rank against numpy.cumsum, one gm_rollout_step against the chain of
 stand-alone entry points include/gnn_manip_hip.h documents it as (bit for bit), and rollouts against the oracle's."""
@@ -17,28 +17,11 @@ import graph_cases as gc
 import width_cases as wc
 from conftest import BOUNDS, STATS, assert_forward_close
 from oracle import epd_oracle as orc
-from test_gpu_train import _check
+from gpu_support import check_training_step as _check, dev, feature_desc, graph_attr, load_model as _model, rollout_engine, to_dev as _t
 
 pytestmark = pytest.mark.gpu
 
 GM_ERR_INVALID_ARGUMENT = -1
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
-
-
-def _t(a, dev):
-    return torch.from_numpy(np.array(a, order="C", copy=True)).to(dev)     # a copy: the cases' arrays are read-only
-
-
-def _model(params, dims, dev, **conv):
-    from gnn_manip_amd import EncProcDecGNN
-    m = EncProcDecGNN(*dims, **conv)
-    m.load_state_dict({k: torch.from_numpy(v) for k, v in params.items()}, strict=True)
-    return m.to(dev)
 
 
 def _dims(name, hidden=wc.HIDDEN, m_steps=wc.M_STEPS):
@@ -107,7 +90,7 @@ def test_standalone_encoder_and_its_non_finite_rows(dev, name):
 @pytest.mark.parametrize("hidden", [128, 64])
 @pytest.mark.parametrize("name", list(wc.WIDTHS))
 def test_training_at_every_width(dev, name, hidden):
-    """test_gpu_train.py's _check as it stands (forward 1e-5, every parameter gradient against float64 autograd inside its
+    """gpu_support.check_training_step as it stands (forward 1e-5, every parameter gradient against float64 autograd inside its
     yardstick); then, by name, the tensors whose shape follows the widths: the right shape, and a reference gradient that is not
     zero, so that passing the yardstick means something."""
     nd, ed, od = wc.WIDTHS[name][0]
@@ -148,20 +131,6 @@ def test_graph_independent_input_gradients_at_every_width(dev, name):
 
 
 # ================================================================== Part B: features and state
-def _fdesc(L, n_per=0):
-    from gnn_manip_amd.graph import make_feature_desc
-    d = make_feature_desc(wc.R, STATS, BOUNDS, L.cart_idx, [L.mat], L.ctrl_idx, L.k, L.D)
-    d.nodes_per_graph = n_per
-    return d
-
-
-def _ga(L):
-    from gnn_manip_amd import GraphBoundedMultimaterial, GraphBoundedMultimaterialControl
-    if L.ctrl < 0:
-        return GraphBoundedMultimaterial(wc.R, STATS, L.cart_idx, [L.mat], BOUNDS)
-    return GraphBoundedMultimaterialControl(wc.R, STATS, L.cart_idx, [L.mat], L.ctrl_idx, BOUNDS)
-
-
 class _Abi:
     """The stand-alone entry points through ctypes: device tensors in, status codes checked."""
 
@@ -205,11 +174,11 @@ class _Abi:
 def test_node_features_and_integrator_per_layout(dev, name):
     L = wc.LAYOUTS[name]
     obs = wc.scene_in_layout(name)
-    abi, fd = _Abi(dev), _fdesc(L)
+    abi, fd = _Abi(dev), feature_desc(wc.R, L)
     tobs = _t(obs, dev)
     ref = orc.compute_nodes(obs, STATS, BOUNDS, wc.R, L.cart_idx, [L.mat], L.ctrl_idx)
     assert ref.shape[1] == L.node_dim
-    for got in (abi.node_features(tobs, fd, L.node_dim), _ga(L).compute_nodes(tobs)):
+    for got in (abi.node_features(tobs, fd, L.node_dim), graph_attr(wc.R, L).compute_nodes(tobs)):
         got = got.cpu().numpy()
         np.testing.assert_allclose(got, ref, rtol=2e-7, atol=1e-7)
         mat_col = 3 * (L.k - 1) + 6
@@ -229,7 +198,7 @@ def test_state_pre_and_post_per_layout(dev, name, with_target):
     is rejected by the stand-alone gm_state_pre (documented), and leaves the state alone."""
     L = wc.LAYOUTS[name]
     obs = wc.scene_in_layout(name)
-    abi, fd = _Abi(dev), _fdesc(L)
+    abi, fd = _Abi(dev), feature_desc(wc.R, L)
     state = _t(obs, dev).clone()
     rank, n_rigid = abi.rank(state, fd)
     rigid = wc.rigid_rows(obs, L)
@@ -269,7 +238,7 @@ def test_rigid_rank_is_a_cumsum(dev, n):
     abi = _Abi(dev)
     for lname in ("default", "moved"):
         L = wc.LAYOUTS[lname]
-        fd = _fdesc(L)
+        fd = feature_desc(wc.R, L)
         for pattern in ("placed", "none", "all"):
             mat = wc.rank_material(n, pattern)
             rigid = mat == 1
@@ -295,7 +264,7 @@ def _step_and_chain(dev, name, kernel, obs=None, K=20, flow=0):
     m = _model(params, dims, dev, **(dict(flow="target_to_source") if flow else {}))
     m.set_edge_kernel(kernel)
     handle = m.device_handle(dev)
-    abi, fd, md = _Abi(dev), _fdesc(L), ModelDesc(*m.model_desc())
+    abi, fd, md = _Abi(dev), feature_desc(wc.R, L), ModelDesc(*m.model_desc())
     lib, p, check = abi.L, abi.p, abi.check
     target = _t(wc.drift_trajectory(obs, L, 1, 811)[0], dev)
     # --- one fused step
@@ -371,11 +340,6 @@ def _rollout_model(name, dev):
     return L, params, _model(params, dims, dev)
 
 
-def _engine(m, L, dev, **kw):
-    from gnn_manip_amd import RolloutEngine
-    return RolloutEngine(m, _ga(L), wc.SCENE_N, k_steps=L.k, data_dim=L.D, device=dev, **kw)
-
-
 def _oracle_rollout(params, obs, traj, horizon, L):
     return orc.rollout(params, obs, traj, horizon, STATS, BOUNDS, wc.R, L.cart_idx, [L.mat], L.ctrl_idx, wc.NUM_LAYERS, wc.M_STEPS, record=True)
 
@@ -399,7 +363,7 @@ def test_rollout_with_records_against_the_oracle(dev, name, t_len):
     traj = wc.drift_trajectory(obs, L, t_len, 830)
     ref, ref_rec = _oracle_rollout(params, obs, traj, 2, L)
     with torch.no_grad():
-        eng = _engine(m, L, dev)
+        eng = rollout_engine(m, wc.R, L, wc.SCENE_N, dev)
         final, recs = eng.rollout(_t(obs, dev), _t(traj, dev), horizon=2, record=True)
         e = eng.status()
         plain = eng.rollout(_t(obs, dev), _t(traj, dev), horizon=2)
@@ -417,9 +381,9 @@ def test_candidates_without_control_columns(dev):
     obs = wc.scene_in_layout(name)
     trajs = np.stack([wc.drift_trajectory(obs, L, 2, 840 + c) for c in range(3)])
     with torch.no_grad():
-        one = _engine(m, L, dev)
+        one = rollout_engine(m, wc.R, L, wc.SCENE_N, dev)
         singles = [one.rollout(_t(obs, dev), _t(trajs[c], dev), horizon=2).cpu().numpy() for c in range(3)]
-        out = _engine(m, L, dev, candidates=3).rollout_candidates(_t(obs, dev), _t(trajs, dev)).cpu().numpy()
+        out = rollout_engine(m, wc.R, L, wc.SCENE_N, dev, candidates=3).rollout_candidates(_t(obs, dev), _t(trajs, dev)).cpu().numpy()
     for c in range(3):
         assert np.array_equal(out[c], singles[c]), (c, np.abs(out[c] - singles[c]).max())
     assert not np.array_equal(singles[0], singles[1])
@@ -434,8 +398,8 @@ def test_renumbered_rollout_with_moved_columns(dev):
     obs = np.ascontiguousarray(obs[:, np.random.Generator(np.random.PCG64(850)).permutation(obs.shape[1])])   # rigid rows scattered
     traj = wc.drift_trajectory(obs, L, 2, 851)
     with torch.no_grad():
-        f0, r0 = _engine(m, L, dev, renumber=False).rollout(_t(obs, dev), _t(traj, dev), horizon=2, record=True)
-        ren = _engine(m, L, dev, renumber=True)
+        f0, r0 = rollout_engine(m, wc.R, L, wc.SCENE_N, dev, renumber=False).rollout(_t(obs, dev), _t(traj, dev), horizon=2, record=True)
+        ren = rollout_engine(m, wc.R, L, wc.SCENE_N, dev, renumber=True)
         ren.RENUMBER_EVERY = 1
         f1, r1 = ren.rollout(_t(obs, dev), _t(traj, dev), horizon=2, record=True)
         assert ren.status() > 0 and ren.renumber

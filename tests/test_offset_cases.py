@@ -6,6 +6,7 @@ import pytest
 import torch
 
 import offset_cases as oc
+import yardstick
 from oracle import epd_oracle as orc
 from oracle import torch_epd
 
@@ -82,7 +83,7 @@ def test_tiled_forward_and_gradients_are_the_class_references(fam, params, t):
     # the float32 yardstick assembles the same way
     refs32 = oc.class_grad_refs(fam, params, targets, nl, ms, dtype=torch.float32)
     g32 = oc.assemble_param_grads(refs32, t)
-    worst = oc.compare_gradients({k: v.grad.numpy() for k, v in p.items()}, g, g32, 2e-4)
+    worst, _ = yardstick.compare({k: v.grad.numpy() for k, v in p.items()}, g, g32, tag="[offsets]")
     assert worst[1] < 1e-6
 
 
@@ -96,9 +97,9 @@ def test_compare_gradients_rejects_a_wrong_tensor(params):
     name = "processor.0.phi_edge.0.weight"
     bad[name][3, 5] += 1e-3 * np.abs(g[name]).max()
     with pytest.raises(AssertionError):
-        oc.compare_gradients(bad, g, g32, 2e-4)
+        yardstick.compare(bad, g, g32, tag="[offsets]")
     with pytest.raises(AssertionError):
-        oc.compare_gradients(bad, g, g32, 2e-4, allowance=lambda: {k: 0.0 for k in g})
+        yardstick.compare(bad, g, g32, allowance=lambda: ({k: 0.0 for k in g}, None), tag="[offsets]")
 
 
 def test_wrap_safety_rejects_an_even_node_period():

@@ -18,7 +18,7 @@ from oracle import epd_oracle as orc
 import grad_cases as gc
 import rollout_grad_cases as rc
 import rollout_train_cases as tc
-from test_rollout_vjp_cases import _ctype
+from rollout_vjp_cases import ctype as _ctype
 
 NEW_SYMBOLS = ("gm_rollout_step_backward_train", "gm_rollout_backward_train")
 BAR = 1e-12              # tests/test_rollout_grad_cases.py: test_reverse_sweep_is_autograd_through_the_unrolled_chain

@@ -16,6 +16,7 @@ import torch
 from conftest import ROOT
 import grad_cases as gc
 import rollout_vjp_cases as vc
+from rollout_vjp_cases import ctype as _ctype
 
 NEW_SYMBOLS = ("gm_state_pre_backward", "gm_state_post_backward", "gm_rollout_step_backward_workspace_bytes", "gm_rollout_step_backward",
                "gm_rollout_backward_workspace_bytes", "gm_rollout_backward")
@@ -76,21 +77,6 @@ def test_symbol_is_declared_bound_and_exported(name):
     assert name in _lib.PROTOTYPES, "not bound in _lib.py"
     assert hasattr(_lib.lib(), name), "not exported by the library"
     assert _lib.lib().gm_abi_version() == 7
-
-
-def _ctype(decl):
-    """The ctypes type _lib.py uses for a C parameter declaration."""
-    from gnn_manip_amd import _lib
-    decl = decl.strip()
-    if "*" in decl:
-        if decl.startswith("const gm_feature_desc"):
-            return _lib._FD
-        if decl.startswith("const gm_model_desc"):
-            return _lib._MD
-        if decl.startswith("int64_t*"):
-            return C.POINTER(C.c_int64)
-        return C.c_void_p
-    return {"int64_t": C.c_int64, "int": C.c_int, "size_t": C.c_size_t}[decl.rsplit(" ", 1)[0]]
 
 
 @pytest.mark.parametrize("name", NEW_SYMBOLS)

@@ -1,4 +1,4 @@
-"""CPU: the float64 restatement of the Sinkhorn gradient convention (sinkhorn_grad_ref in test_gpu_sinkhorn_grad.py, the yardstick
+"""CPU: the float64 restatement of the Sinkhorn gradient convention (sinkhorn_grad_ref in sinkhorn_cases.py, the yardstick
 of the HIP backward) against central finite differences of oracle.sinkhorn_divergence.
 
 The convention differentiates only the last extrapolation with the potentials detached; that is the gradient of the divergence
@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 from oracle import epd_oracle as orc
-from test_gpu_sinkhorn_grad import sinkhorn_grad_ref
+from sinkhorn_cases import sinkhorn_grad_ref
 
 
 def _fd(x, y, d, scaling, h=1e-6):

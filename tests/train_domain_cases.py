@@ -8,7 +8,7 @@ Three kinds of cases:
      bit for bit; what is checked here is that the scaled float32 arrays themselves are exact (nothing overflows or goes subnormal).
   2. Models whose biases are calibrated so that NO pre-activation can sit within rounding distance of zero (`calibrated`): the
      gradient is then continuous at the case, float32 PyTorch reproduces the float64 gradient to a few 1e-7 of a tensor's maximum,
-     and the device is held to four times that (`tol_case`) instead of test_gpu_train.py's 2e-4 floor.
+     and the device is held to four times that (`tol_case`) instead of the 2e-4 floor of tests/yardstick.py.
   3. Non-finite features and parameters: the contract is the float32 restatement's NaN rows (`nan_case`).
 
 Losses: (out * w).sum() with seeded w (tests/grad_cases.weights), so grad_out is exactly w; the non-finite cases use the L1 loss of
@@ -186,7 +186,7 @@ class Calibrated:
         self.out64, self.g64 = reference(self.params, self.nodes, self.ea, self.ei, self.w, nl, ms, torch.float64)
         self.out32, self.g32 = reference(self.params, self.nodes, self.ea, self.ei, self.w, nl, ms, torch.float32)
         self.err32 = {k: rel_err(self.g32[k], v) for k, v in self.g64.items() if np.abs(v).max() > 0}
-        # 4 x the largest error of plain float32 PyTorch among this case's gradient tensors (the factor is test_gpu_train.py's):
+        # 4 x the largest error of plain float32 PyTorch among this case's gradient tensors (the factor is tests/yardstick.py's):
         # no 2e-4 floor, no flip allowance.  The order of PyTorch's float32 sums over a few thousand rows differs between hosts,
         # and so does this figure (by a factor of up to six on the [128, 4] gradient of encoder.phi_edge.0.weight, a sum over
         # 4347 edges), so it is capped at TOL_CASE_MAX: a host with a sloppier float32 sum leaves the bar where it is.  The
