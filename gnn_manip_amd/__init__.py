@@ -5,4 +5,4 @@ from .epd_gnn import EncProcDecGNN, GraphIndependent, InteractionNetwork  # noqa
 from .dataset import CoffeeDataset, CoffeeTestDataset, GraphData, GraphLoader, collate_graphs, read_metadata  # noqa: F401
 from .graph import (GraphBoundedMultimaterial, GraphBoundedMultimaterialControl, compute_acceleration,  # noqa: F401
                     get_connectivity, get_edges_displacement, random_walk_noise)
-from .rollout import RolloutEngine, get_position_from_prediction  # noqa: F401
+from .rollout import RolloutEngine, evaluate_rollout, get_position_from_prediction  # noqa: F401

@@ -105,6 +105,9 @@ PROTOTYPES = {
     "gm_rollout_renumber_workspace_bytes": (_sz, [_FD, _i64]),
     "gm_rollout": (_i32, [_vp, _vp, _i64, _FD, _i32, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _sz, _vp, _sz, _vp]),
     "gm_rollout_status": (_i32, [_vp, _MD, _i64, _i32, C.POINTER(_i64), _vp]),
+    "gm_state_recorded": (_i32, [_vp, _i64, _FD, _vp, _vp, _vp, _i32, _vp]),
+    "gm_rollout_recorded": (_i32, [_vp, _vp, _i64, _FD, _i32, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _sz, _vp, _sz, _vp]),
+    "gm_rollout_errors": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _FD, _vp, _vp]),
     "gm_rollout_step_backward_workspace_bytes": (_sz, [_MD, _FD, _i64, _i32]),
     "gm_rollout_step_backward": (_i32, [_vp, _vp, _i32, _vp, _i64, _FD, _i32, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64), _vp, _sz, _vp]),
     "gm_rollout_backward_workspace_bytes": (_sz, [_MD, _FD, _i64, _i32]),

@@ -173,11 +173,20 @@ struct ProfScope {
 };
 
 struct StepClear;
-// fused kernels of the rollout step (features.hip)
+// One step of the recorded drive (gm_rollout_recorded), as the step's two fused launches take it: the arrays are in the CALLER's
+// numbering, state row j is the caller's row row_map[j]
+struct RecordedDrive {
+    const float* frame;    // [N, D] the recorded frame of this step: control columns before the step, xyz after it (rigid rows)
+    const int* row_map;    // or nullptr: the identity
+    float* record;         // [N, D] or nullptr: receives the last frame after the control overwrite
+    float* pred;           // [N, 3] or nullptr: receives the model's normalised acceleration
+};
+// fused kernels of the rollout step (features.hip); rec (or nullptr: the scripted drive of `target`): the recorded drive
 int rollout_pre_features(float* obs, int64_t n, const gm_feature_desc* d, const int* rank, const float* target, float* out,
-                         hipStream_t s, const StepClear* clear);   // clear (or nullptr): the step's resets, done by the same launch
+                         hipStream_t s, const StepClear* clear,   // clear (or nullptr): the step's resets, done by the same launch
+                         const RecordedDrive* rec = nullptr);
 int rollout_integrate_post(float* obs, int64_t n, const gm_feature_desc* d, const float* pred, const int* rank,
-                           const float* target, float* pred_out, hipStream_t s);
+                           const float* target, float* pred_out, hipStream_t s, const RecordedDrive* rec = nullptr);
 // renumbered rollout (features.hip): out[t][j] = in[t][src(j)] over the k frames, src = perm (or the identity when the order was
 // skipped: GraphHeader::order_skip of graph_ws); total_out[j] = total_in ? total_in[src] : src; rank_out[j] = rank_caller[total_out[j]]
 int renumber_gather(const float* in, float* out, int k, int64_t n, int D, const int* perm, const void* graph_ws, const int* total_in,

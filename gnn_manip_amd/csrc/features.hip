@@ -73,38 +73,63 @@ __global__ void __launch_bounds__(256) integrate_kernel(const float* __restrict_
 }
 
 // rollout step, fused: state_pre + node features (one thread owns row i of every frame) -- and, as the step's first launch, the
-// resets of everything the step's later launches build on (StepClear: graph / destination-sort workspaces, scan states, agg)
+// resets of everything the step's later launches build on (StepClear: graph / destination-sort workspaces, scan states, agg).
+// Rec: empty -- the scripted drive, `target` its pose -- or one RecordedDrive: the recorded control in place of the scripted one,
+// and the step's record (the last frame as it then stands) written by the same thread, at the caller's row
+template <class... Rec>
 __global__ void __launch_bounds__(256) pre_features_kernel(float* __restrict__ obs, int64_t n, FeatParams P,
                                                             const int* __restrict__ rank, const float* __restrict__ target,
-                                                            float* __restrict__ out, StepClear clr) {
+                                                            float* __restrict__ out, StepClear clr, Rec... rec) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     step_clear_run(clr, i, (long long)gridDim.x * blockDim.x);
     if (i >= n) return;
     const int64_t fs = n * P.D;
     float* row = obs + i * P.D;
-    if (rank && P.ctrl >= 0) {
+    if constexpr (sizeof...(Rec) > 0) {
+        const RecordedDrive& R = (rec, ...);
+        float* last = row + (int64_t)(P.k - 1) * fs;
+        const int64_t c = R.row_map ? (int64_t)R.row_map[i] : i;
+        if (rank && P.ctrl >= 0 && rank[i] >= 0) recorded_control_row(last, P, R.frame + c * P.D);
+        if (R.record)
+            for (int d = 0; d < P.D; ++d) R.record[c * P.D + d] = last[d];
+    } else if (rank && P.ctrl >= 0) {
         const int rk = rank[i];
         if (rk >= 0) control_overwrite_row(row + (int64_t)(P.k - 1) * fs, P, target ? target + (int64_t)rk * 3 : nullptr);
     }
     node_features_row(row, fs, P, out + i * node_feature_dim(P.k, P.ctrl));
 }
 
-// rollout step, fused: integrator + window shift + write-back (+ optional copy of the prediction)
+// rollout step, fused: integrator + window shift + write-back (+ optional copy of the prediction).  Rec as above: under the
+// recorded drive EVERY row takes its integrated position, then a rigid row's xyz the recorded one, and the copy of the
+// prediction goes to the caller's row
+template <class... Rec>
 __global__ void __launch_bounds__(256) integrate_post_kernel(float* __restrict__ obs, int64_t n, FeatParams P,
                                                               const float* __restrict__ pred, const int* __restrict__ rank,
-                                                              const float* __restrict__ target, float* __restrict__ pred_out) {
+                                                              const float* __restrict__ target, float* __restrict__ pred_out, Rec... rec) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const int64_t fs = n * P.D;
     float* row = obs + i * P.D;
     const float* l1 = row + (int64_t)(P.k - 1) * fs + P.cart;
-    if (pred_out) {
+    if constexpr (sizeof...(Rec) > 0) {
+        const RecordedDrive& R = (rec, ...);
+        const int64_t c = R.row_map ? (int64_t)R.row_map[i] : i;
+        if (R.pred) {
 #pragma unroll
-        for (int a = 0; a < 3; ++a) pred_out[i * 3 + a] = pred[i * 3 + a];
+            for (int a = 0; a < 3; ++a) R.pred[c * 3 + a] = pred[i * 3 + a];
+        }
+        const float3 nxt = integrate_row(l1, l1 - fs, pred + i * 3, P);
+        shift_write_row(row, fs, P, -1, nxt, nullptr);
+        if (rank && rank[i] >= 0) recorded_pose_row(row + (int64_t)(P.k - 1) * fs, P, R.frame + c * P.D);
+    } else {
+        if (pred_out) {
+#pragma unroll
+            for (int a = 0; a < 3; ++a) pred_out[i * 3 + a] = pred[i * 3 + a];
+        }
+        const float3 nxt = integrate_row(l1, l1 - fs, pred + i * 3, P);
+        const int rk = rank ? rank[i] : -1;
+        shift_write_row(row, fs, P, rk, nxt, (rk >= 0 && target) ? target + (int64_t)rk * 3 : nullptr);
     }
-    const float3 nxt = integrate_row(l1, l1 - fs, pred + i * 3, P);
-    const int rk = rank ? rank[i] : -1;
-    shift_write_row(row, fs, P, rk, nxt, (rk >= 0 && target) ? target + (int64_t)rk * 3 : nullptr);
 }
 
 // rank of each rigid row (material == 1) among the rigid rows; one block, running carry
@@ -155,6 +180,68 @@ __global__ void __launch_bounds__(256) state_post_kernel(float* __restrict__ obs
     const float* np = next_pos + i * 3;
     const float3 nxt = rk < 0 ? make_float3(np[0], np[1], np[2]) : make_float3(0.f, 0.f, 0.f);   // read for the rows that take it only
     shift_write_row(obs + i * P.D, n * P.D, P, rk, nxt, (rk >= 0 && target) ? target + (int64_t)rk * 3 : nullptr);
+}
+
+// one half of the recorded drive on the last frame, no shift: what = GM_RECORDED_CONTROL / GM_RECORDED_POSE
+__global__ void __launch_bounds__(256) state_recorded_kernel(float* __restrict__ obs, int64_t n, FeatParams P, const int* __restrict__ rank,
+                                                              const float* __restrict__ frame, const int* __restrict__ row_map, int what) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || rank[i] < 0) return;
+    float* last = obs + (int64_t)(P.k - 1) * n * P.D + i * P.D;
+    const float* fr = frame + (row_map ? (int64_t)row_map[i] : i) * P.D;
+    if (what == GM_RECORDED_CONTROL) recorded_control_row(last, P, fr);
+    else recorded_pose_row(last, P, fr);
+}
+
+// Squared-error sums of a recorded rollout, one workgroup per (step, graph).  Thread t walks the graph's rows t, t + 256, ... in
+// order, then the 256 partial sums go down a fixed tree in LDS: one order of additions per (step, graph) whatever the grid, no
+// atomics.  Every term is formed in float64 from the float32 inputs, without contraction into multiply-adds, so a term has the
+// bits of the same expression on a host.
+__global__ void __launch_bounds__(256) rollout_errors_kernel(const float* __restrict__ rec, const float* __restrict__ pred,
+                                                              const float* __restrict__ sim, int64_t first, int64_t n, int64_t n_per,
+                                                              FeatParams P, double* __restrict__ sums) {
+#pragma clang fp contract(off)
+    __shared__ double red[4][256];
+    const int tid = threadIdx.x;
+    const int64_t graphs = n / n_per;
+    const int64_t step = blockIdx.x / graphs, g = blockIdx.x - step * graphs;
+    const int64_t fs = n * P.D;
+    const float* rf = rec + step * fs;
+    const float* gf = sim + (first + step) * fs;
+    double s_all = 0.0, s_cof = 0.0, s_acc = 0.0, cnt = 0.0;
+    for (int64_t r = g * n_per + tid; r < (g + 1) * n_per; r += 256) {
+        const float* a = rf + r * P.D + P.cart;
+        const float* b = gf + r * P.D + P.cart;
+        double e = 0.0;
+#pragma unroll
+        for (int x = 0; x < 3; ++x) {
+            const double d = (double)a[x] - (double)b[x];
+            e += d * d;
+        }
+        s_all += e;
+        if (gf[r * P.D + P.mat] != 0.0f) continue;
+        s_cof += e;
+        cnt += 1.0;
+        if (!pred) continue;
+        double ea = 0.0;
+#pragma unroll
+        for (int x = 0; x < 3; ++x) {
+            const double acc = ((double)b[fs + x] - 2.0 * (double)b[x]) + (double)b[x - fs];
+            const double d = (double)pred[(step * n + r) * 3 + x] - (acc - (double)P.am[x]) / (double)P.as[x];
+            ea += d * d;
+        }
+        s_acc += ea;
+    }
+    red[0][tid] = s_all; red[1][tid] = s_cof; red[2][tid] = s_acc; red[3][tid] = cnt;
+    __syncthreads();
+    for (int w = 128; w >= 1; w >>= 1) {
+        if (tid < w) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) red[q][tid] += red[q][tid + w];
+        }
+        __syncthreads();
+    }
+    if (tid < 4) sums[(int64_t)blockIdx.x * 4 + tid] = red[tid][0];
 }
 
 // traj_utils.py:167-194: rotation about X in the cup frame with the y/z axis swap
@@ -246,19 +333,22 @@ int renumber_scatter(const float* in, float* out, int frames, int64_t n, int D, 
 }
 
 int rollout_pre_features(float* obs, int64_t n, const gm_feature_desc* d, const int* rank, const float* target, float* out,
-                         hipStream_t s, const StepClear* clear) {
+                         hipStream_t s, const StepClear* clear, const RecordedDrive* rec) {
     FeatParams P;
     int rc = to_params(d, &P, "gm_rollout_step");
     if (rc != GM_OK) return rc;
-    return launch_rows(pre_features_kernel, n, s, obs, n, P, rank, target, out, clear ? *clear : StepClear{});
+    const StepClear clr = clear ? *clear : StepClear{};
+    if (rec) return launch_rows(pre_features_kernel<RecordedDrive>, n, s, obs, n, P, rank, target, out, clr, *rec);
+    return launch_rows(pre_features_kernel<>, n, s, obs, n, P, rank, target, out, clr);
 }
 
 int rollout_integrate_post(float* obs, int64_t n, const gm_feature_desc* d, const float* pred, const int* rank,
-                           const float* target, float* pred_out, hipStream_t s) {
+                           const float* target, float* pred_out, hipStream_t s, const RecordedDrive* rec) {
     FeatParams P;
     int rc = to_params(d, &P, "gm_rollout_step");
     if (rc != GM_OK) return rc;
-    return launch_rows(integrate_post_kernel, n, s, obs, n, P, pred, rank, target, pred_out);
+    if (rec) return launch_rows(integrate_post_kernel<RecordedDrive>, n, s, obs, n, P, pred, rank, target, pred_out, *rec);
+    return launch_rows(integrate_post_kernel<>, n, s, obs, n, P, pred, rank, target, pred_out);
 }
 
 
@@ -592,6 +682,44 @@ int gm_state_post(float* obs, int64_t n, const gm_feature_desc* desc, const floa
     GM_REQUIRE(n >= 0 && (n == 0 || (obs && next_pos)), GM_ERR_INVALID_ARGUMENT, "gm_state_post: null pointer");
     if (n == 0) return GM_OK;
     return launch_rows(state_post_kernel, n, (hipStream_t)stream, obs, n, P, next_pos, rank, target);
+}
+
+int gm_state_recorded(float* obs, int64_t n, const gm_feature_desc* desc, const int32_t* rank, const float* frame,
+                      const int32_t* row_map, int what, void* stream) {
+    gm::DevGuard dev_guard(obs);
+    FeatParams P;
+    int rc = to_params(desc, &P, "gm_state_recorded");
+    if (rc != GM_OK) return rc;
+    GM_REQUIRE(what == GM_RECORDED_CONTROL || what == GM_RECORDED_POSE, GM_ERR_INVALID_ARGUMENT,
+               "gm_state_recorded: what=%d (GM_RECORDED_CONTROL = 1, GM_RECORDED_POSE = 4)", what);
+    GM_REQUIRE(what != GM_RECORDED_CONTROL || P.ctrl >= 0, GM_ERR_INVALID_ARGUMENT, "gm_state_recorded: descriptor has no control columns");
+    GM_REQUIRE(n >= 0 && (n == 0 || (obs && rank && frame)), GM_ERR_INVALID_ARGUMENT, "gm_state_recorded: null pointer");
+    if (n == 0) return GM_OK;
+    return launch_rows(state_recorded_kernel, n, (hipStream_t)stream, obs, n, P, rank, frame, row_map, what);
+}
+
+int gm_rollout_errors(const float* record_last, const float* record_pred, const float* sim, int64_t n_frames, int64_t first_frame,
+                      int64_t steps, int64_t n, const gm_feature_desc* desc, double* sums, void* stream) {
+    gm::DevGuard dev_guard(sums);
+    FeatParams P;
+    int rc = to_params(desc, &P, "gm_rollout_errors");
+    if (rc != GM_OK) return rc;
+    GM_REQUIRE(steps >= 0 && n >= 0 && n_frames >= 0, GM_ERR_INVALID_ARGUMENT, "gm_rollout_errors: negative count");
+    // the acceleration target of frame f reads frames f - 1 and f + 1 of the recording
+    const int64_t lo = record_pred ? 1 : 0, hi = record_pred ? n_frames - 1 : n_frames;
+    GM_REQUIRE(first_frame >= lo && first_frame <= hi && steps <= hi - first_frame, GM_ERR_INVALID_ARGUMENT,
+               "gm_rollout_errors: frames [%lld, %lld) outside [%lld, %lld) of the recording%s", (long long)first_frame,
+               (long long)(first_frame + steps), (long long)lo, (long long)hi, record_pred ? " (record_pred needs a frame on either side)" : "");
+    const int64_t n_per = graph_nodes(desc, n);
+    GM_REQUIRE(n == 0 || n % n_per == 0, GM_ERR_INVALID_ARGUMENT, "gm_rollout_errors: n_nodes is not a multiple of nodes_per_graph");
+    if (steps == 0 || n == 0) return GM_OK;
+    GM_REQUIRE(record_last && sim && sums, GM_ERR_INVALID_ARGUMENT, "gm_rollout_errors: null pointer");
+    const int64_t blocks = steps * (n / n_per);
+    GM_REQUIRE(blocks < ((int64_t)1 << 31), GM_ERR_UNSUPPORTED, "gm_rollout_errors: steps * graphs overflows the grid");
+    hipLaunchKernelGGL(rollout_errors_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, record_last, record_pred, sim,
+                       first_frame, n, n_per, P, sums);
+    GM_LAUNCH_CHECK();
+    return GM_OK;
 }
 
 int gm_state_pre_backward(const float* d_obs_after, int64_t n, const gm_feature_desc* desc, const int32_t* rank, int has_target,

@@ -741,8 +741,13 @@ size_t gm_rollout_workspace_bytes(const gm_model_desc* desc, int64_t n, int K) {
     return carve_rollout(nullptr, desc, n, K).bytes;
 }
 
-int gm_rollout_step(const gm_model* m, float* obs, int64_t n, const gm_feature_desc* fd, int K, const int32_t* rigid_rank,
-                    const float* rigid_target, float* pred_acc_out, void* ws, size_t ws_bytes, void* stream) {
+}  // extern "C"
+
+namespace {
+// gm_rollout_step under either drive: the scripted one (rigid_target, pred_acc_out) or -- rec given -- the recorded one
+int rollout_step_impl(const gm_model* m, float* obs, int64_t n, const gm_feature_desc* fd, int K, const int32_t* rigid_rank,
+                      const float* rigid_target, float* pred_acc_out, const gm::RecordedDrive* rec, void* ws, size_t ws_bytes,
+                      void* stream) {
     gm::DevGuard dev_guard(obs);
     GM_REQUIRE(m && obs && fd && ws, GM_ERR_INVALID_ARGUMENT, "gm_rollout_step: null pointer");
     int rc = gm::check_model_for_scene(m->d, fd, "gm_rollout_step");
@@ -763,7 +768,7 @@ int gm_rollout_step(const gm_model* m, float* obs, int64_t n, const gm_feature_d
         if (rc == GM_OK) rc = clr.add(reinterpret_cast<int*>(f.agg), (long long)n * m->Hp, 0);
         if (rc != GM_OK) return rc;
         ProfScope prof(m->prof, PROF_REST, hs);
-        rc = gm::rollout_pre_features(obs, n, fd, rigid_rank, rigid_target, r.x, hs, &clr);
+        rc = gm::rollout_pre_features(obs, n, fd, rigid_rank, rigid_target, r.x, hs, &clr, rec);
     }
     if (rc != GM_OK) return rc;
     const float* last_pos = obs + (size_t)(fd->k_steps - 1) * n * fd->data_dim + fd->cart_col;
@@ -784,7 +789,15 @@ int gm_rollout_step(const gm_model* m, float* obs, int64_t n, const gm_feature_d
     if (rc != GM_OK) return rc;
     // integrator + window shift + write-back (+ copy of the prediction) in one launch
     ProfScope prof(m->prof, PROF_REST, hs);
-    return gm::rollout_integrate_post(obs, n, fd, r.pred, rigid_rank, rigid_target, pred_acc_out, hs);
+    return gm::rollout_integrate_post(obs, n, fd, r.pred, rigid_rank, rigid_target, pred_acc_out, hs, rec);
+}
+}  // namespace
+
+extern "C" {
+
+int gm_rollout_step(const gm_model* m, float* obs, int64_t n, const gm_feature_desc* fd, int K, const int32_t* rigid_rank,
+                    const float* rigid_target, float* pred_acc_out, void* ws, size_t ws_bytes, void* stream) {
+    return rollout_step_impl(m, obs, n, fd, K, rigid_rank, rigid_target, pred_acc_out, nullptr, ws, ws_bytes, stream);
 }
 
 size_t gm_rollout_renumber_workspace_bytes(const gm_feature_desc* fd, int64_t n) {
@@ -792,27 +805,34 @@ size_t gm_rollout_renumber_workspace_bytes(const gm_feature_desc* fd, int64_t n)
     return carve_renumber(nullptr, fd, n).bytes;
 }
 
-int gm_rollout(const gm_model* m, float* obs, int64_t n, const gm_feature_desc* fd, int K, const int32_t* rigid_rank,
-               const float* rigid_targets, int64_t n_targets, int64_t n_rigid, int64_t steps, float* record_last,
-               int64_t renumber_every, void* renumber_ws, size_t renumber_ws_bytes, void* ws, size_t ws_bytes, void* stream) {
-    gm::DevGuard dev_guard(obs);
-    GM_REQUIRE(m && obs && fd && ws, GM_ERR_INVALID_ARGUMENT, "gm_rollout: null pointer");
-    GM_REQUIRE(steps >= 0 && n_targets >= 0 && n_rigid >= 0 && renumber_every >= 0, GM_ERR_INVALID_ARGUMENT, "gm_rollout: negative count");
-    // a scene without rigid rows has an empty trajectory ([steps, 0, 3]: a null pointer); the reference's loop runs on it unchanged
-    GM_REQUIRE(rigid_targets || n_targets == 0 || n_rigid == 0, GM_ERR_INVALID_ARGUMENT, "gm_rollout: n_targets > 0 without rigid_targets");
-    GM_REQUIRE(!rigid_targets || rigid_rank, GM_ERR_INVALID_ARGUMENT, "gm_rollout: rigid_targets need rigid_rank");
+}  // extern "C"
+
+namespace {
+// What moves the rigid rows of a rollout: scripted poses (gm_rollout: targets) or the frames of a recording (gm_rollout_recorded:
+// frames).  The loop below is the one loop of both.
+struct RolloutDrive {
+    const float* targets = nullptr;   // [n_targets, n_rigid, 3]
+    int64_t n_targets = 0, n_rigid = 0;
+    const float* frames = nullptr;    // [steps, N, D], the caller's numbering
+    float* record_pred = nullptr;     // [steps, N, 3] or nullptr (recorded drive only)
+};
+int rollout_loop(const char* who, const gm_model* m, float* obs, int64_t n, const gm_feature_desc* fd, int K, const int32_t* rigid_rank,
+                 const RolloutDrive& drive, int64_t steps, float* record_last, int64_t renumber_every, void* renumber_ws,
+                 size_t renumber_ws_bytes, void* ws, size_t ws_bytes, void* stream) {
     hipStream_t hs = (hipStream_t)stream;
+    const float* rigid_targets = drive.targets;
+    const int64_t n_targets = drive.n_targets, n_rigid = drive.n_rigid;
     const size_t frame = (size_t)n * fd->data_dim;
     const bool renum = renumber_every > 0 && n > 0 && steps > 0;
     RenumberWs rw{};
     RolloutWs r{};
     if (renum) {
-        GM_REQUIRE(renumber_ws, GM_ERR_INVALID_ARGUMENT, "gm_rollout: renumber_every > 0 needs renumber_ws (gm_rollout_renumber_workspace_bytes)");
+        GM_REQUIRE(renumber_ws, GM_ERR_INVALID_ARGUMENT, "%s: renumber_every > 0 needs renumber_ws (gm_rollout_renumber_workspace_bytes)", who);
         rw = carve_renumber(renumber_ws, fd, n);
-        GM_REQUIRE(renumber_ws_bytes >= rw.bytes, GM_ERR_WORKSPACE, "gm_rollout: renumber workspace %zu < %zu", renumber_ws_bytes, rw.bytes);
-        GM_REQUIRE(n < ((int64_t)1 << 31) / (K > 0 ? K : 1), GM_ERR_UNSUPPORTED, "gm_rollout: n*max_neighbours overflows int32");
+        GM_REQUIRE(renumber_ws_bytes >= rw.bytes, GM_ERR_WORKSPACE, "%s: renumber workspace %zu < %zu", who, renumber_ws_bytes, rw.bytes);
+        GM_REQUIRE(n < ((int64_t)1 << 31) / (K > 0 ? K : 1), GM_ERR_UNSUPPORTED, "%s: n*max_neighbours overflows int32", who);
         r = carve_rollout(ws, &m->d, n, K);
-        GM_REQUIRE(ws_bytes >= r.bytes, GM_ERR_WORKSPACE, "gm_rollout: workspace %zu < %zu", ws_bytes, r.bytes);
+        GM_REQUIRE(ws_bytes >= r.bytes, GM_ERR_WORKSPACE, "%s: workspace %zu < %zu", who, ws_bytes, r.bytes);
     }
     // The renumbered rollout works on a copy of the state whose rows are in grid-cell order (gm::cell_order: the radius graph's own
     // grid; scenes of a batch stay apart), re-ordered every `renumber_every` steps: state[j] is the caller's row total[j], its rigid
@@ -837,6 +857,15 @@ int gm_rollout(const gm_model* m, float* obs, int64_t n, const gm_feature_desc* 
             rank = rigid_rank ? rw.rank : nullptr;
             flip ^= 1;
         }
+        if (drive.frames) {
+            // the recorded drive: control overwrite, record, pose and the copy of the prediction ride in the step's two fused
+            // launches, reaching the caller's arrays through `total`
+            const gm::RecordedDrive rec{drive.frames + (size_t)i * frame, total, record_last ? record_last + (size_t)i * frame : nullptr,
+                                        drive.record_pred ? drive.record_pred + (size_t)i * n * 3 : nullptr};
+            int rc = rollout_step_impl(m, state, n, fd, K, rank, nullptr, nullptr, &rec, ws, ws_bytes, stream);
+            if (rc != GM_OK) return rc;
+            continue;
+        }
         float* last = state + (size_t)(fd->k_steps - 1) * frame;
         // traj_utils.py:126-134: steps past the scripted trajectory keep the rigid body where it is (control = 0 displacement)
         const float* target = i < n_targets ? rigid_targets + (size_t)i * n_rigid * 3 : nullptr;
@@ -853,6 +882,41 @@ int gm_rollout(const gm_model* m, float* obs, int64_t n, const gm_feature_desc* 
     }
     if (total) return gm::renumber_scatter(state, obs, fd->k_steps, n, fd->data_dim, total, hs);
     return GM_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int gm_rollout(const gm_model* m, float* obs, int64_t n, const gm_feature_desc* fd, int K, const int32_t* rigid_rank,
+               const float* rigid_targets, int64_t n_targets, int64_t n_rigid, int64_t steps, float* record_last,
+               int64_t renumber_every, void* renumber_ws, size_t renumber_ws_bytes, void* ws, size_t ws_bytes, void* stream) {
+    gm::DevGuard dev_guard(obs);
+    GM_REQUIRE(m && obs && fd && ws, GM_ERR_INVALID_ARGUMENT, "gm_rollout: null pointer");
+    GM_REQUIRE(steps >= 0 && n_targets >= 0 && n_rigid >= 0 && renumber_every >= 0, GM_ERR_INVALID_ARGUMENT, "gm_rollout: negative count");
+    // a scene without rigid rows has an empty trajectory ([steps, 0, 3]: a null pointer); the reference's loop runs on it unchanged
+    GM_REQUIRE(rigid_targets || n_targets == 0 || n_rigid == 0, GM_ERR_INVALID_ARGUMENT, "gm_rollout: n_targets > 0 without rigid_targets");
+    GM_REQUIRE(!rigid_targets || rigid_rank, GM_ERR_INVALID_ARGUMENT, "gm_rollout: rigid_targets need rigid_rank");
+    RolloutDrive drive;
+    drive.targets = rigid_targets; drive.n_targets = n_targets; drive.n_rigid = n_rigid;
+    return rollout_loop("gm_rollout", m, obs, n, fd, K, rigid_rank, drive, steps, record_last, renumber_every, renumber_ws, renumber_ws_bytes,
+                        ws, ws_bytes, stream);
+}
+
+// compute_rollout's ground-truth mode (rollout_utils.py:38-61, args.cma_traj None): gm_rollout's loop under the recorded drive.
+// Step i takes the control columns of frames[i] before it runs (:45) and the xyz of the SAME frames[i] after it (:60): the pose
+// lags the window by one step, as the reference's does.
+int gm_rollout_recorded(const gm_model* m, float* obs, int64_t n, const gm_feature_desc* fd, int K, const int32_t* rigid_rank,
+                        const float* frames, int64_t steps, float* record_last, float* record_pred, int64_t renumber_every,
+                        void* renumber_ws, size_t renumber_ws_bytes, void* ws, size_t ws_bytes, void* stream) {
+    gm::DevGuard dev_guard(obs);
+    GM_REQUIRE(m && obs && fd && ws, GM_ERR_INVALID_ARGUMENT, "gm_rollout_recorded: null pointer");
+    GM_REQUIRE(steps >= 0 && renumber_every >= 0, GM_ERR_INVALID_ARGUMENT, "gm_rollout_recorded: negative count");
+    GM_REQUIRE(frames || steps == 0 || n == 0, GM_ERR_INVALID_ARGUMENT, "gm_rollout_recorded: steps > 0 without frames");
+    if (steps == 0 || n <= 0) return GM_OK;
+    RolloutDrive drive;
+    drive.frames = frames; drive.record_pred = record_pred;
+    return rollout_loop("gm_rollout_recorded", m, obs, n, fd, K, rigid_rank, drive, steps, record_last, renumber_every, renumber_ws,
+                        renumber_ws_bytes, ws, ws_bytes, stream);
 }
 
 int gm_rollout_status(const void* ws, const gm_model_desc* desc, int64_t n, int K, int64_t* n_edges_host, void* stream) {

@@ -80,6 +80,19 @@ __device__ __forceinline__ void control_overwrite_row(float* __restrict__ last, 
     }
 }
 
+// The recorded drive (compute_rollout's ground-truth mode): fr = the particle's row of the recorded frame of this step.
+// Before the step the control columns of a rigid particle take the recording's (rollout_utils.py:45) ...
+__device__ __forceinline__ void recorded_control_row(float* __restrict__ last, const FeatParams& P, const float* __restrict__ fr) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) last[P.ctrl + a] = fr[P.ctrl + a];
+}
+// ... and after it, on the new last frame, its xyz takes the xyz of the SAME recorded frame (rollout_utils.py:60: the pose lags
+// the window by one step); the row's other columns are what the shift left there
+__device__ __forceinline__ void recorded_pose_row(float* __restrict__ last, const FeatParams& P, const float* __restrict__ fr) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) last[P.cart + a] = fr[P.cart + a];
+}
+
 // Next xyz of one particle from its xyz in the last two frames (l1, l2) and its predicted, normalised acceleration:
 // l1 + ((l1 - l2) + (pred * acc_std + acc_mean)) (rollout_utils.py:145-158)
 __device__ __forceinline__ float3 integrate_row(const float* __restrict__ l1, const float* __restrict__ l2, const float* __restrict__ pred,

@@ -450,19 +450,43 @@ class RolloutEngine:
             self._check_tensor(trajectory, "trajectory", ("T", self.n_rigid, 3))
         recs = torch.empty((steps, self.n, self.data_dim), dtype=torch.float32, device=self.device) if record else None
         handle = self.model.device_handle(self.device)  # resolved once per rollout
-        L = lib()
-        every, rws = 0, None
-        if self.renumber and self.n > 0 and steps > 0:
-            # rows in grid-cell order inside the library (gm_rollout, renumber_every): order, row maps, gathers and the write-back
-            # are device kernels of the same call -- nothing is sorted or synchronised here
-            every = self.RENUMBER_EVERY
-            if self._renumber_ws is None:
-                self._renumber_ws = _ws(L.gm_rollout_renumber_workspace_bytes(C.byref(self.fdesc), self.n), self.device)
-            rws = self._renumber_ws
-        check(L.gm_rollout(handle, ptr(obs), self.n, C.byref(self.fdesc), self.max_neighbours, ptr(self.rigid_rank),
+        every, rws = self._renumbering(steps)
+        check(lib().gm_rollout(handle, ptr(obs), self.n, C.byref(self.fdesc), self.max_neighbours, ptr(self.rigid_rank),
                            ptr(trajectory), T, self.n_rigid, steps, ptr(recs), every, ptr(rws), 0 if rws is None else rws.numel(),
                            ptr(self.ws), self.ws.numel(), current_stream()))
         return recs
+
+    def _renumbering(self, steps):
+        """(renumber_every, renumber workspace or None) of a library rollout of `steps` steps: rows in grid-cell order inside the
+        library -- order, row maps, gathers and the write-back are device kernels of the same call, nothing is sorted or
+        synchronised here."""
+        if not (self.renumber and self.n > 0 and steps > 0):
+            return 0, None
+        if self._renumber_ws is None:
+            self._renumber_ws = _ws(lib().gm_rollout_renumber_workspace_bytes(C.byref(self.fdesc), self.n), self.device)
+        return self.RENUMBER_EVERY, self._renumber_ws
+
+    def run_recorded(self, obs, frames, steps=None, record=False, record_pred=False):
+        """`steps` steps of compute_rollout's ground-truth loop (rollout_utils.py:38-61 with ``args.cma_traj`` None) in place on
+        ``obs`` inside ONE library call (gm_rollout_recorded): before step i the control columns of the rigid rows take those of
+        ``frames[i]``, after it their xyz takes that of the same ``frames[i]`` (the reference's pose lags the window by one step).
+        frames: [T, N, D] contiguous device tensor of recorded frames, T >= steps (default: all of them).  Returns
+        (records [steps, N, D] -- the last frame after each control overwrite, the reference's ``prediction`` -- or None,
+        predictions [steps, N, 3] -- the model's normalised acceleration of each step -- or None).  The same checks and the same
+        renumbering as ``run``; no host synchronisation."""
+        self._check_state(obs, None, None, True)
+        self._check_tensor(frames, "frames", ("T", self.n, self.data_dim))
+        steps = int(frames.shape[0]) if steps is None else int(steps)
+        if not 0 <= steps <= frames.shape[0]:
+            raise ValueError(f"steps must be between 0 and the {frames.shape[0]} frames given, got {steps}")
+        recs = torch.empty((steps, self.n, self.data_dim), dtype=torch.float32, device=self.device) if record else None
+        preds = torch.empty((steps, self.n, 3), dtype=torch.float32, device=self.device) if record_pred else None
+        handle = self.model.device_handle(self.device)
+        every, rws = self._renumbering(steps)
+        check(lib().gm_rollout_recorded(handle, ptr(obs), self.n, C.byref(self.fdesc), self.max_neighbours, ptr(self.rigid_rank),
+                                        ptr(frames), steps, ptr(recs), ptr(preds), every, ptr(rws), 0 if rws is None else rws.numel(),
+                                        ptr(self.ws), self.ws.numel(), current_stream()))
+        return recs, preds
 
     def rollout_candidates(self, obs0, trajectories, horizon=None):
         """Roll `candidates` copies of one initial state [k, N, D] under per-candidate scripted rigid poses
@@ -509,19 +533,20 @@ def compute_rollout(dataset, model, args):
     ``CoffeeTestDataset``, driving the rigid body either with a planned trajectory (``args.cma_traj``: .npy of
     absolute [rotation, translation] per step) or with the recorded ground truth.  Returns the reference's
     ``prediction`` array [nof_steps, N, D] (numpy): the last frame of every step after the control overwrite.
-    The step itself (graph, features, model, integration, window shift) is gm_rollout_step on the device; only the
-    ground-truth mode's control / pose overwrite -- taken verbatim from recorded frames -- is done with tensor
-    indexing around it."""
+    Both modes are one library call: gm_rollout under the planned poses, gm_rollout_recorded under the recorded frames
+    (``RolloutEngine.run_recorded``) -- no Python and no host synchronisation between steps."""
     import numpy as np
     obs0, _ = dataset[0]
     k, n, dd = obs0.shape
     dev = obs0.device
     nof_steps = dataset.time_steps if args.cma_traj is not None else dataset.time_steps - args.k_steps
-    eng = RolloutEngine(model, dataset.graph_attr, n, k_steps=k, data_dim=dd, max_neighbours=20, device=dev)
+    # the ground-truth mode never renumbered (it stepped through gm_rollout_step): its records keep their bits at every size
+    eng = RolloutEngine(model, dataset.graph_attr, n, k_steps=k, data_dim=dd, max_neighbours=20, device=dev,
+                        renumber="auto" if args.cma_traj is not None else False)
     obs = obs0.clone().contiguous()
     eng.set_scene(obs)
     rigid = obs[0, :, dataset.material_id] == 1
-    c0, u0 = dataset.cartesian_idx[0], dataset.control_idx[0]
+    c0 = dataset.cartesian_idx[0]
     with torch.no_grad():
         if args.cma_traj is not None:
             npy_trajectory = np.load(args.cma_traj) if isinstance(args.cma_traj, str) else np.asarray(args.cma_traj)
@@ -529,14 +554,134 @@ def compute_rollout(dataset, model, args):
             trajectory = get_rigid_body_trajectory_from_diff(npy_trajectory, nof_steps, [0.5, 0.5, 0.4], rigid_pos)
             _, recs = eng.rollout(obs, trajectory, horizon=nof_steps, record=True)
             return recs.cpu().numpy().astype(np.float64)
-        groundtruth = extract_groundtruth(dataset, nof_steps)
-        prediction = []
-        for i in range(nof_steps):
-            obs[-1, rigid, u0:u0 + 3] = groundtruth[i, rigid, u0:u0 + 3]          # control from the recording (:43)
-            prediction.append(obs[-1].clone())
-            eng.step(obs, None, use_rigid=False)                                  # predict, integrate, shift
-            new_rigid = prediction[-1][rigid].clone()                             # rigid rows keep the frame's attributes ...
-            new_rigid[:, c0:c0 + 3] = groundtruth[i, rigid, c0:c0 + 3]            # ... with the recorded pose (:57)
-            obs[-1, rigid] = new_rigid
+        groundtruth = extract_groundtruth(dataset, nof_steps).contiguous()
+        # per step: control from the recording (:45), record, predict / integrate / shift, the recorded pose (:60)
+        recs, _ = eng.run_recorded(obs, groundtruth, nof_steps, record=True)
         eng.status()
-        return torch.stack(prediction).cpu().numpy().astype(np.float64)
+        return recs.cpu().numpy().astype(np.float64)
+
+
+# SamplesLoss.batched over (step, simulation) pairs: the default block keeps gm_sinkhorn_batched_workspace_bytes under this
+SINKHORN_WORKSPACE_CAP = 1 << 30
+
+
+def _recorded_frames(sim, graph_attr, material_id):
+    """A resident simulation [T, N, D0] as the windows' frames [T, N, D]: with control columns in the layout, frame t gets the
+    control input of coffee_dataset.py:91-97 -- xyz[t + 1] - xyz[t] on the rigid rows (material == 1), 0 elsewhere and on the
+    last frame -- so that frame t is ``dataset[t - k + 1][0][-1]``, bit for bit."""
+    sim = sim.float()
+    if graph_attr.control_idx is None:
+        return sim.contiguous()
+    c0 = graph_attr.cartesian_idx[0]
+    ctr = torch.zeros(sim.shape[:2] + (3,), dtype=torch.float32, device=sim.device)
+    ctr[:-1] = sim[1:, :, c0:c0 + 3] - sim[:-1, :, c0:c0 + 3]
+    ctr = torch.where((sim[:, :, material_id] != 1).unsqueeze(-1), torch.zeros_like(ctr), ctr)
+    return torch.cat((sim, ctr), dim=-1).contiguous()
+
+
+def evaluate_rollout(dataset_or_sims, model, graph_attr=None, k_steps=6, max_neighbours=20, sinkhorn=True, blur=0.05, pair_block=None):
+    """How good is ``model`` on recorded simulations: the numbers of the reference's model comparison
+    (scripts/plot_rmses.py:176-198), computed on the device.
+
+    dataset_or_sims: a ``CoffeeTestDataset`` (its ``sims``, ``graph_attr`` and window length are used) or a list of resident
+    [T, N, D] float32 device tensors with ``graph_attr`` given.  Each simulation is rolled T - k steps from its first window under
+    the recorded drive (``RolloutEngine.run_recorded``: compute_rollout's ground-truth mode).  Simulations of equal (T, N) are
+    evaluated together as one block-diagonal batch, others in groups of their own, in the order they first appear; one
+    ``status()`` per group, after its rollout.
+
+    Returns a list, one dict per simulation, in the order given:
+      prediction, groundtruth   [steps, N, D] device tensors: the records of the rollout (the reference's ``prediction``) and
+                                the recorded frames they stand against (``extract_groundtruth``); ``prediction[0]`` is
+                                ``groundtruth[0]`` exactly;
+      acceleration              [steps, N, 3] device tensor: the model's normalised acceleration of every step;
+      sums                     [steps, 4] float64 host tensor, gm_rollout_errors' per-step sums: squared position error over
+                                all rows, over the coffee rows (material == 0), squared error of the normalised acceleration
+                                over the coffee rows, number of coffee rows;
+      rmse_position, rmse_position_coffee, rmse_acceleration
+                                floats formed on the host in float64 from the sums: sqrt(sum over steps and rows of |delta|^2 /
+                                (steps * rows)), |delta| the 3-vector's norm.  The reference's ``get_rmse`` lives in a module
+                                (``rollout_sand_dyn``) that is not in its tree: this definition is the engine's own and
+                                UNPINNED against the reference.  NaN where there is no row to average over;
+      sinkhorn, mean_sinkhorn   (sinkhorn=True) [steps] float32 device tensor and its mean as a float: entry i is
+                                ``SamplesLoss("sinkhorn", p=2, blur=blur)(groundtruth_i[coffee, xyz], prediction_i[coffee, xyz])``,
+                                the argument order of plot_rmses.py:188-191, bit-equal to that single call; None / NaN for a
+                                simulation without coffee rows.
+    pair_block: how many (step, simulation) pairs of a group one ``SamplesLoss.batched`` call takes, each pair with its own
+    right-hand cloud (y_shared = 0); any value gives the same bits.  Default: as many as keep the call's workspace
+    (gm_sinkhorn_batched_workspace_bytes) under SINKHORN_WORKSPACE_CAP (1 GiB), at least one.  The coffee rows are compacted into
+    clouds with tensor indexing once per simulation, not per step; simulations of a group with equally many coffee rows share
+    the calls."""
+    from .losses import SamplesLoss
+    if hasattr(dataset_or_sims, "sims"):
+        sims, k = list(dataset_or_sims.sims), int(dataset_or_sims.k)
+        graph_attr = dataset_or_sims.graph_attr if graph_attr is None else graph_attr
+    else:
+        sims, k = list(dataset_or_sims), int(k_steps)
+    if graph_attr is None:
+        raise ValueError("evaluate_rollout: a list of simulations needs graph_attr")
+    mat, c0 = graph_attr.material_idx[0], graph_attr.cartesian_idx[0]
+    groups = {}
+    for s, sim in enumerate(sims):
+        _need_cuda(sim, "every simulation")
+        if sim.dim() != 3 or sim.shape[0] <= k:
+            raise ValueError(f"evaluate_rollout: simulation {s} must be [T > {k}, N, D], got {tuple(sim.shape)}")
+        groups.setdefault((int(sim.shape[0]), int(sim.shape[1]), sim.device), []).append(s)
+    loss = SamplesLoss("sinkhorn", p=2, blur=blur) if sinkhorn else None
+    results = [None] * len(sims)
+    with torch.no_grad():
+        for (T, n, dev), members in groups.items():
+            G, steps = len(members), T - k
+            # the group's recording, simulations back to back along the node axis: [T, G * n, D]
+            rec = torch.cat([_recorded_frames(sims[s], graph_attr, mat) for s in members], dim=1).contiguous()
+            dd = int(rec.shape[2])
+            eng = RolloutEngine(model, graph_attr, n, k_steps=k, data_dim=dd, max_neighbours=max_neighbours, device=dev, candidates=G)
+            obs = rec[:k].clone().contiguous()
+            if graph_attr.control_idx is not None:   # the first window as the dataset stores it: every frame's control looks at frame k
+                u0 = graph_attr.control_idx[0]
+                way = rec[k, :, c0:c0 + 3].unsqueeze(0) - obs[:, :, c0:c0 + 3]
+                obs[:, :, u0:u0 + 3] = torch.where((obs[:, :, mat] != 1).unsqueeze(-1), torch.zeros_like(way), way)
+            eng.set_scene(obs)
+            frames = rec[k - 1:k - 1 + steps]
+            pred, acc = eng.run_recorded(obs, frames, steps, record=True, record_pred=True)
+            eng.status()
+            sums = torch.empty((steps, G, 4), dtype=torch.float64, device=dev)
+            check(lib().gm_rollout_errors(ptr(pred), ptr(acc), ptr(rec), T, k - 1, steps, eng.n, C.byref(eng.fdesc), ptr(sums),
+                                          current_stream()))
+            sums = sums.cpu()
+            coffee = rec[0, :, mat] == 0
+            for g, s in enumerate(members):
+                rows = slice(g * n, (g + 1) * n)
+                res = dict(prediction=pred[:, rows], groundtruth=frames[:, rows], acceleration=acc[:, rows], sums=sums[:, g].clone())
+                tot = res["sums"].sum(dim=0)
+                cnt = float(res["sums"][0, 3])
+                mean = lambda v, rows_: float(torch.sqrt(v / (steps * rows_))) if steps * rows_ > 0 else float("nan")
+                res["rmse_position"] = mean(tot[0], n)
+                res["rmse_position_coffee"] = mean(tot[1], cnt)
+                res["rmse_acceleration"] = mean(tot[2], cnt)
+                if sinkhorn:
+                    res["sinkhorn"], res["mean_sinkhorn"] = None, float("nan")
+                results[s] = res
+            if not sinkhorn or steps == 0:
+                continue
+            # the (step, simulation) pairs of the group: the coffee rows of a simulation compacted once, simulations with equally
+            # many of them stacked into one list of pairs, which goes through SamplesLoss.batched block by block
+            clouds = {}
+            for g, s in enumerate(members):
+                idx = torch.nonzero(coffee[g * n:(g + 1) * n]).flatten() + g * n
+                if idx.numel() > 0:
+                    clouds.setdefault(int(idx.numel()), []).append((s, idx))
+            for nc, items in clouds.items():
+                x = torch.cat([frames[:, idx, c0:c0 + 3] for _, idx in items]).contiguous()     # [S * steps, Nc, 3] ground truth
+                y = torch.cat([pred[:, idx, c0:c0 + 3] for _, idx in items]).contiguous()       # [S * steps, Nc, 3] prediction
+                pairs = int(x.shape[0])
+                block = pair_block
+                if block is None:
+                    block = pairs
+                    while block > 1 and lib().gm_sinkhorn_batched_workspace_bytes(block, nc, nc) > SINKHORN_WORKSPACE_CAP:
+                        block = (block + 1) // 2
+                block = max(1, int(block))
+                losses = torch.cat([loss.batched(x[b:b + block], y[b:b + block]) for b in range(0, pairs, block)])
+                for j, (s, _) in enumerate(items):
+                    results[s]["sinkhorn"] = losses[j * steps:(j + 1) * steps]
+                    results[s]["mean_sinkhorn"] = float(results[s]["sinkhorn"].double().mean())
+    return results

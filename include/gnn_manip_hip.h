@@ -484,6 +484,56 @@ int gm_rollout_status(const void* rollout_ws, const gm_model_desc* desc, int64_t
                       int max_neighbours, int64_t* n_edges_host, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Evaluation against a recorded simulation: compute_rollout's ground-truth mode (rollout_utils.py:38-61 with
+ * args.cma_traj None) and the sums behind the model comparison of scripts/plot_rmses.py:176-198.
+ *
+ * The recorded drive.  Step i, frame = frames[i] ([N,D], a recorded frame in the caller's row numbering):
+ *   1. the control columns of the rigid rows (rigid_rank >= 0) of the last frame take frame's control columns
+ *      (rollout_utils.py:45; control_col < 0: nothing to overwrite);
+ *   2. the record is the last frame as it now stands (:48);
+ *   3. the step runs as always and EVERY row, rigid ones included, takes its integrated position (:51-54);
+ *   4. xyz of the rigid rows of the new last frame takes frame's xyz (:60) -- frame i again, the frame of 1: the reference's
+ *      pose LAGS the window by one step, and so does this one.  The other columns of those rows are the record's.
+ *
+ * gm_state_recorded is 1 (what = GM_RECORDED_CONTROL) or 4 (GM_RECORDED_POSE) alone: a plain overwrite on the last frame of obs
+ * [k,N,D], no shift.  row_map[j] (int32, each in [0, N)) is the row of `frame` that state row j is; NULL: the identity.
+ * GM_RECORDED_CONTROL on a descriptor without control columns is refused (GM_ERR_INVALID_ARGUMENT), like gm_state_pre.
+ *
+ * gm_rollout_recorded runs `steps` such steps inside one call: gm_rollout's loop under the other drive, with its workspaces,
+ * no host synchronisation, no allocation.  1, 2 and 4 ride in the two fused launches of the step, so a recorded step has
+ * exactly the launches of a gm_rollout_step, records included.  record_pred[i] is the model's normalised acceleration of step i
+ * (gm_rollout_step's pred_acc_out).  renumber_every > 0: as in gm_rollout; obs, frames, record_last and record_pred stay in the
+ * caller's numbering and are reached through the row map inside the fused launches.  nodes_per_graph > 0: a batch of
+ * equal-sized recorded simulations stored back to back.  frames, the records and obs must not overlap.
+ *
+ * gm_rollout_errors: per step i and graph g (G = N / nodes_per_graph, else 1), with gt = sim[first_frame + i],
+ *   sums[i][g][0] = sum over all rows of |xyz(record_last[i]) - xyz(gt)|^2
+ *   sums[i][g][1] = the same over the rows with material == 0 (gt's material column)
+ *   sums[i][g][2] = sum over those rows of |record_pred[i] - a_gt|^2,  a_gt = ((p[f+1] - 2 p[f] + p[f-1]) - acc_mean) / acc_std
+ *                   over xyz of sim, f = first_frame + i: the training target (collate_utils.py compute_acceleration);
+ *                   0 when record_pred is NULL
+ *   sums[i][g][3] = the number of rows with material == 0.
+ * sim [n_frames,N,D] is read in place through the row stride D.  With record_pred: 1 <= first_frame and first_frame + steps <=
+ * n_frames - 1; without: 0 <= first_frame and first_frame + steps <= n_frames; else GM_ERR_INVALID_ARGUMENT.  Every difference,
+ * square, normalisation and sum is float64 from the float32 inputs.  One workgroup per (step, graph): each thread sums rows
+ * t, t + 256, ... of the graph in order, the 256 partial sums go down a fixed tree -- no float atomics, no dependence on the
+ * grid, the same call twice gives the same bits.  A NaN / inf coordinate makes its own (step, graph) sums non-finite only.
+ * ------------------------------------------------------------------------------------------ */
+#define GM_RECORDED_CONTROL 1
+#define GM_RECORDED_POSE 4
+int gm_state_recorded(float* obs, int64_t n_nodes, const gm_feature_desc* desc, const int32_t* rigid_rank, const float* frame,
+                      const int32_t* row_map, int what, void* stream);
+int gm_rollout_recorded(const gm_model* m, float* obs, int64_t n_nodes, const gm_feature_desc* fdesc,
+                        int max_neighbours, const int32_t* rigid_rank, const float* frames, int64_t steps,
+                        float* record_last, float* record_pred,
+                        int64_t renumber_every, void* renumber_ws, size_t renumber_ws_bytes,
+                        void* rollout_ws, size_t rollout_ws_bytes, void* stream);
+int gm_rollout_errors(const float* record_last, const float* record_pred,
+                      const float* sim, int64_t n_frames, int64_t first_frame,
+                      int64_t steps, int64_t n_nodes, const gm_feature_desc* fdesc,
+                      double* sums, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * The reverse sweep of a rollout (no reference counterpart: the reference's planner is derivative-free, traj_utils.py:247-259).
  * gm_rollout_step_backward is the vector-Jacobian product of ONE gm_rollout_step with the model's parameters as constants:
  * d_obs_before [k,N,D] and d_rigid_target [N_rigid,3] (may be NULL; zeros without a rigid_target) from d_obs_after [k,N,D], the
