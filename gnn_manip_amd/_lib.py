@@ -37,7 +37,7 @@ class ModelDesc(C.Structure):
                 ("node_agg_first", C.c_int32)]
 
 
-_vp, _i64, _i32, _sz, _f32, _f64 = C.c_void_p, C.c_int64, C.c_int, C.c_size_t, C.c_float, C.c_double
+_vp, _i64, _i32, _sz, _f32, _f64, _u64 = C.c_void_p, C.c_int64, C.c_int, C.c_size_t, C.c_float, C.c_double, C.c_uint64
 _FD, _MD = C.POINTER(FeatureDesc), C.POINTER(ModelDesc)
 
 # name -> (restype, argtypes); every symbol declared in include/gnn_manip_hip.h
@@ -116,6 +116,11 @@ PROTOTYPES = {
                                               _vp]),
     "gm_rollout_backward_train": (_i32, [_vp, _vp, _i32, _vp, _i64, _FD, _i32, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
                                          _vp]),
+    "gm_train_batch_workspace_bytes": (_sz, [_FD, _i64, _i64, _i32]),
+    "gm_train_batch_build": (_i32, [_vp, _i64, _i64, _i32, _FD, _i32, _f64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "gm_train_batch_edges": (_i32, [_vp, _i64, _i64, _FD, _i32, _i64, _vp, _vp, _vp]),
+    "gm_train_batch_num_edges": (_i32, [_vp, C.POINTER(_i64), _vp]),
+    "gm_train_batch_status": (_i32, [_vp, C.POINTER(_i64)]),
     "gm_model_profile": (_i32, [_vp, _i32]),
     "gm_model_set_edge_kernel": (_i32, [_vp, _i32]),
     "gm_model_set_node_fusion": (_i32, [_vp, _i32]),

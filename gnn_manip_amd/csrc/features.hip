@@ -5,7 +5,7 @@
 
 namespace gm {
 
-static int to_params(const gm_feature_desc* d, FeatParams* p, const char* who) {
+int to_params(const gm_feature_desc* d, FeatParams* p, const char* who) {
     GM_REQUIRE(d != nullptr, GM_ERR_INVALID_ARGUMENT, "%s: null feature descriptor", who);
     GM_REQUIRE(d->k_steps >= 2 && d->k_steps <= 64, GM_ERR_INVALID_ARGUMENT, "%s: k_steps=%d out of range", who, d->k_steps);
     GM_REQUIRE(d->data_dim >= 4 && d->cart_col >= 0 && d->cart_col + 3 <= d->data_dim, GM_ERR_INVALID_ARGUMENT,

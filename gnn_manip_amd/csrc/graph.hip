@@ -894,6 +894,12 @@ int launch_neighbor(const GraphWs& g, int64_t n, double r2, int K, int* indeg, i
     return GM_OK;
 }
 
+}  // namespace
+namespace gm {
+// for the builds composed outside this file (train_batch.hip)
+int radius_graph_check_args(const float* pos, int64_t pos_stride, int64_t n, int64_t n_per, double conn_r, int K, const void* ws) {
+    return check_build_args(pos, pos_stride, n, n_per, conn_r, K, ws);
+}
 // The build behind its resets (StepClear: a launch of its own in the stand-alone entry point, part of the step's first launch in the
 // rollout): the grid phase and the two neighbour kernels.  The scan of cnt (-> out_ptr, E) is the caller's: the rollout path runs it
 // together with the in-degree scan of the destination sort.
@@ -908,7 +914,7 @@ int radius_graph_build_core(const float* pos, int64_t pos_stride, int64_t n, int
                        g.hdr, n, r2, K, g.cnt, g.nbr, indeg, slot, flow);
     return K <= 64 ? launch_neighbor<128>(g, n, r2, K, indeg, slot, flow, s) : launch_neighbor<64>(g, n, r2, K, indeg, slot, flow, s);
 }
-}  // namespace
+}  // namespace gm
 
 extern "C" {
 

@@ -13,6 +13,16 @@ struct FeatParams {
     float vm[3], vs[3], am[3], as[3], lo[3], hi[3];
 };
 
+// A descriptor checked and turned into the kernels' parameters (features.hip); `who` opens the message of a refusal
+int to_params(const gm_feature_desc* d, FeatParams* p, const char* who);
+
+// The radius-graph build behind its resets (graph.hip, graph_clear_jobs): grid phase and neighbour search into g.cnt / g.nbr; the
+// scan of g.cnt (-> g.out_ptr, E) is the caller's.  radius_graph_check_args: the limits gm_radius_graph_build_batched puts on its
+// arguments.  Declared here, not in common.h, for the callers that compose a build with their own row kernels (train_batch.hip).
+int radius_graph_check_args(const float* pos, int64_t pos_stride, int64_t n, int64_t n_per, double conn_r, int K, const void* ws);
+int radius_graph_build_core(const float* pos, int64_t pos_stride, int64_t n, int64_t n_per, double conn_r, int K, const GraphWs& g,
+                            int* indeg, int* slot, int flow, hipStream_t s);
+
 // Width of a scene's node features: 3 (k_steps - 1) velocities, 6 boundary terms, the material, and 3 more with control columns
 __host__ __device__ static inline int node_feature_dim(int k_steps, int control_col) { return 3 * (k_steps - 1) + 7 + (control_col >= 0 ? 3 : 0); }
 inline int node_feature_dim(const gm_feature_desc* fd) { return node_feature_dim(fd->k_steps, fd->control_col); }
@@ -105,6 +115,20 @@ __device__ __forceinline__ float3 integrate_row(const float* __restrict__ l1, co
         nxt[a] = __fadd_rn(l1[a], __fadd_rn(lv, acc));
     }
     return make_float3(nxt[0], nxt[1], nxt[2]);
+}
+
+// Training target of one particle: its normalised acceleration from the xyz that follows the window (nxt) and its xyz in the last
+// two frames (l1, l2), (((nxt - 2 l1) + l2) - acc_mean) / acc_std in compute_target's op order (utils.py:10-24,
+// collate_utils.py:150-159) -- integrate_row's inverse up to rounding
+__device__ __forceinline__ float3 target_row(const float* __restrict__ nxt, const float* __restrict__ l1, const float* __restrict__ l2,
+                                             const FeatParams& P) {
+    float t[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float acc = __fadd_rn(__fsub_rn(nxt[a], __fmul_rn(2.f, l1[a])), l2[a]);
+        t[a] = __fdiv_rn(__fsub_rn(acc, P.am[a]), P.as[a]);
+    }
+    return make_float3(t[0], t[1], t[2]);
 }
 
 // Window shift and write-back of one particle, row = its row of frame 0: frame t takes frame t + 1, then the last frame's xyz takes

@@ -7,12 +7,14 @@ MI355X layout: every simulation file is parsed once and kept as one ``[T, N, D]`
 kernels of graph.py when it is requested.  The reference materialises every window on the host instead
 (k-fold duplication, coffee_dataset.py:82-102).
 """
+import ctypes as C
 import json
 
 import numpy as np
 import torch
 
-from .graph import GraphBoundedMultimaterial, GraphBoundedMultimaterialControl
+from ._lib import check, current_stream, lib, ptr
+from .graph import GraphBoundedMultimaterial, GraphBoundedMultimaterialControl, _ws, make_feature_desc
 
 
 def read_metadata(metadata_file):
@@ -62,6 +64,74 @@ def collate_graphs(items):
     return GraphData(torch.cat(xs), torch.cat(es), torch.cat(idx, dim=1), y)
 
 
+class _QueuedBatch:
+    """Phase 1 of one batch, queued (gm_train_batch_build): one build per group of samples of equal N, each in a workspace of its
+    own, the 16-byte records of the workspaces on their way into pinned rows and an event behind the copies -- the _HeaderWatch
+    pattern of epd_gnn.py.  ``finish`` waits for that event alone, reads the edge counts and queues phase 2."""
+
+    def __init__(self, dataset, indices, seed, first_stream, workspaces, pinned):
+        """workspaces: a list this batch may grow (one uint8 tensor per build, reused where large enough); pinned: int32
+        [>= builds, 4] in pinned memory.  Both belong to the caller and stay untouched by it until ``finish`` has returned."""
+        ds = self.ds = dataset
+        L, dev = lib(), ds.device
+        self.fd = ds._window_desc()
+        f = 3 * (ds.k - 1) + 7 + (3 if ds.use_control else 0)
+        # the quirk of the reference kept: the noise-free path builds its graph with the default 20 neighbours (graph.py)
+        self.k_nb = 20 if ds.noise is None else int(ds.max_neighbours)
+        noise_std = 0.0 if ds.noise is None else float(ds.noise)
+        ns = [int(ds.sims[ds.index[int(i)][0]].shape[1]) for i in indices]
+        # samples of equal N ride in one build; a batch that mixes sizes is built sample by sample
+        groups = [list(indices)] if len(set(ns)) == 1 else [[i] for i in indices]
+        assert len(groups) <= pinned.shape[0]
+        self.builds, self.pinned = [], pinned
+        stream = current_stream(dev)
+        done = 0
+        with torch.cuda.device(dev):
+            for g, idx in enumerate(groups):
+                frames = (C.c_void_p * len(idx))()
+                for b, i in enumerate(idx):
+                    sim, t = ds.index[int(i)]
+                    data = ds.sims[sim]
+                    assert data.is_contiguous() and data.dtype == torch.float32, "resident recordings are row-major float32"
+                    frames[b] = data.data_ptr() + t * data.shape[1] * data.shape[2] * 4
+                n = int(ds.sims[ds.index[int(idx[0])][0]].shape[1])
+                need = L.gm_train_batch_workspace_bytes(C.byref(self.fd), len(idx), n, self.k_nb)
+                if g == len(workspaces):
+                    workspaces.append(None)
+                if workspaces[g] is None or workspaces[g].numel() < need:
+                    workspaces[g] = _ws(need, dev)
+                ws = workspaces[g]
+                nodes = torch.empty((len(idx) * n, f), dtype=torch.float32, device=dev)
+                target = torch.empty((len(idx) * n, 3), dtype=torch.float32, device=dev)
+                check(L.gm_train_batch_build(frames, len(idx), n, ds.data_dim, C.byref(self.fd), self.k_nb, noise_std, int(seed),
+                                             int(first_stream) + done, None, ptr(nodes), ptr(target), None, ptr(ws), ws.numel(), stream))
+                pinned[g].copy_(ws[:16].view(torch.int32), non_blocking=True)
+                self.builds.append((ws, len(idx), n, nodes, target))
+                done += len(idx)
+            self.event = torch.cuda.Event()
+            self.event.record(torch.cuda.current_stream(dev))
+
+    def finish(self):
+        """The batch: waits for the records (not for the stream), then phase 2 of every build."""
+        L, dev = lib(), self.ds.device
+        self.event.synchronize()
+        items = []
+        for g, (ws, b, n, nodes, target) in enumerate(self.builds):
+            e = C.c_int64(0)
+            check(L.gm_train_batch_status(C.c_void_p(self.pinned[g].data_ptr()), C.byref(e)))
+            e = int(e.value)
+            edge_index = torch.empty((2, e), dtype=torch.int64, device=dev)
+            edge_attr = torch.empty((e, 4), dtype=torch.float32, device=dev)
+            check(L.gm_train_batch_edges(ptr(ws), b, n, C.byref(self.fd), self.k_nb, e, ptr(edge_index), ptr(edge_attr),
+                                         current_stream(dev)))
+            items.append(GraphData(nodes, edge_attr, edge_index, target))
+        return items[0] if len(items) == 1 else collate_graphs(items)
+
+
+def _pinned_records(rows):
+    return torch.zeros((max(int(rows), 1), 4), dtype=torch.int32).pin_memory()
+
+
 class CoffeeDataset(torch.utils.data.Dataset):
     """Mirror of coffee_dataset.py:46-133 (same constructor arguments); ``device`` must be a HIP device."""
 
@@ -83,12 +153,33 @@ class CoffeeDataset(torch.utils.data.Dataset):
         self._load_data(self.files)
         self.graph_attr = self._get_graph_attr()
 
+    @classmethod
+    def from_recordings(cls, sims, k, conn_r, stats, bounds, cartesian_idx=(2, 3, 4), material_id=1, control_idx=(5, 6, 7), noise=None,
+                        use_control=False, max_neighbours=20):
+        """The dataset over recordings that are resident already: ``sims`` a list of float32 [T, N, data_dim] tensors on one HIP
+        device (N may differ between them), the other arguments what metadata.json and the constructor give."""
+        self = cls.__new__(cls)
+        self.sims = [s.contiguous() for s in sims]
+        if not self.sims or any(s.dtype != torch.float32 or s.dim() != 3 or not s.is_cuda for s in self.sims):
+            raise RuntimeError("CoffeeDataset.from_recordings: float32 [T, N, data_dim] tensors on the HIP device")
+        self.dir = self.split = self.metadata_file = None
+        self.files = []
+        self.k, self.conn_r, self.max_neighbours, self.device = k, conn_r, max_neighbours, self.sims[0].device
+        self.noise, self.use_control = noise, use_control
+        self.data_dim, self.time_steps = int(self.sims[0].shape[2]), int(self.sims[0].shape[0])
+        self.cartesian_idx, self.control_idx, self.material_id = list(cartesian_idx), list(control_idx), int(material_id)
+        self.bounds, self.stats = bounds, stats
+        self.index = [(s, t) for s, data in enumerate(self.sims) for t in range(data.shape[0] - k)]
+        self.graph_attr = self._get_graph_attr()
+        return self
+
     def _load_data(self, files):
         # one resident [T, N, D] tensor per simulation; samples index (simulation, first frame)
         self.sims, self.index = [], []
         for s, file in enumerate(files):
             data = read_simulation(file, self.time_steps, self.data_dim)
-            self.sims.append(torch.from_numpy(data).float().to(self.device))
+            # row-major whatever layout the parser left: the library reads a sample's frames through one pointer
+            self.sims.append(torch.from_numpy(data).float().contiguous().to(self.device))
             self.index += [(s, t) for t in range(self.time_steps - self.k)]
 
     def __len__(self):
@@ -114,6 +205,22 @@ class CoffeeDataset(torch.utils.data.Dataset):
         obs_seq, next_pos = self.sample(idx)
         nodes, edge_attr, senders, receivers, tgt = self.graph_attr.process(obs_seq, next_pos)
         return GraphData(nodes, edge_attr, torch.stack((senders, receivers)).long(), tgt)
+
+    def _window_desc(self):
+        """gm_feature_desc of a sample's window: the recording's columns, and with use_control the three control columns behind."""
+        return make_feature_desc(self.conn_r, self.stats, self.bounds, self.cartesian_idx, [self.material_id],
+                                 self.control_idx if self.use_control else None, self.k, self.data_dim + (3 if self.use_control else 0))
+
+    def batch(self, indices, seed=0, first_stream=0):
+        """The collated batch of the samples ``indices`` -- what ``collate_graphs([self[i] for i in indices])`` returns -- built
+        in the library (gm_train_batch_build / gm_train_batch_edges) with one wait for the edge counts.  Honours ``noise``,
+        ``use_control`` and ``max_neighbours`` like ``__getitem__``.  The noise is the library's counter-based draw: sample j of
+        the call draws from stream ``first_stream + j`` of ``seed``, whatever batch it rides in; ``graph_attr.generator`` plays
+        no part."""
+        indices = [int(i) for i in indices]
+        if not indices:
+            raise ValueError("CoffeeDataset.batch: no samples")
+        return _QueuedBatch(self, indices, seed, first_stream, [], _pinned_records(len(indices))).finish()
 
     def _get_graph_attr(self):
         if self.use_control:
@@ -151,16 +258,53 @@ class CoffeeTestDataset(CoffeeDataset):
 
 class GraphLoader:
     """What train_dyn.py gets from ``torch_geometric.data.DataLoader(dataset, batch_size, shuffle)``: an iterable of
-    collated batches.  Everything stays on the dataset's device."""
+    collated batches.  Everything stays on the dataset's device.
 
-    def __init__(self, dataset, batch_size=2, shuffle=False, seed=None):
+    ``fused=True`` builds the batches in the library (``CoffeeDataset.batch``'s two phases) instead of sample by sample in torch
+    calls.  The noise is then the library's counter-based draw, not torch's: its seed is ``seed`` (or one drawn from the loader's
+    ``rng`` when None), and sample i of the run -- counted over all epochs of this loader object, an epoch begun counting in full
+    -- draws from stream i, so epochs differ and a run with a given seed repeats.  ``graph_attr.generator`` plays no part in the
+    fused path.  ``prefetch=1`` queues the first phase of the next batch, in a second workspace on the same stream, before a
+    batch is handed out: when the next batch is asked for, its edge count has long arrived (it was computed before the
+    caller's training step began), nothing waits and the stream is never synchronised.  ``prefetch=0`` waits for its own build.
+    A batch larger than 64 (GM_TRAIN_BATCH_MAX) is refused by the library."""
+
+    def __init__(self, dataset, batch_size=2, shuffle=False, seed=None, fused=False, prefetch=1):
         self.dataset, self.batch_size, self.shuffle = dataset, batch_size, shuffle
         self.rng = np.random.default_rng(seed)
+        self.fused, self.prefetch = bool(fused), int(prefetch)
+        if self.prefetch not in (0, 1):
+            raise ValueError("GraphLoader: prefetch is 0 or 1")
+        if self.fused:
+            self.noise_seed = int(seed) if seed is not None else int(self.rng.integers(0, 2 ** 63))
+            self._samples_begun = 0                      # samples of the epochs begun so far: the next epoch's first stream
+            self._workspaces = ([], [])                  # batch i builds in set i % 2
+            self._pinned = _pinned_records(2 * int(batch_size)).view(2, -1, 4)
 
     def __len__(self):
         return (len(self.dataset) + self.batch_size - 1) // self.batch_size
 
     def __iter__(self):
         order = self.rng.permutation(len(self.dataset)) if self.shuffle else np.arange(len(self.dataset))
+        if self.fused:
+            yield from self._iter_fused(order)
+            return
         for b in range(0, len(order), self.batch_size):
             yield collate_graphs([self.dataset[int(i)] for i in order[b:b + self.batch_size]])
+
+    def _iter_fused(self, order):
+        base = self._samples_begun
+        self._samples_begun += len(order)
+        starts = list(range(0, len(order), self.batch_size))
+
+        def queue(j):
+            b = starts[j]
+            return _QueuedBatch(self.dataset, [int(i) for i in order[b:b + self.batch_size]], self.noise_seed, base + b,
+                                self._workspaces[j % 2], self._pinned[j % 2])
+
+        queued = None
+        for j in range(len(starts)):
+            batch = (queued or queue(j)).finish()
+            # phase 1 of the next batch goes in front of whatever the caller queues for this one, in the other workspaces
+            queued = queue(j + 1) if self.prefetch and j + 1 < len(starts) else None
+            yield batch

@@ -613,6 +613,61 @@ int gm_rollout_backward_train(const gm_model* m, const float* const* tensors, in
                               float* d_trajectory /*[n_targets,Nr,3] or NULL*/, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Training batches from resident recordings (an addition to ABI 7).  Replaces, for a batch of samples, CoffeeDataset's
+ * stored windows (coffee_dataset.py:82-102), random_walk_noise (utils.py:96-115), _process_noisy / _process_simple
+ * (collate_utils.py:169-193, 29-40) and the collate (collate_utils.py:68-87): the nodes / edge_attr / edge_index / target that
+ * gm_epd_forward_train and a loss take, in two phases around the one number the host has to learn, the edge count.
+ *
+ * gm_train_batch_build (phase 1; no host synchronisation, no allocation).  first_frames is a HOST array of `batch` device
+ * pointers; first_frames[b] points at frame t_b of a resident recording [T, N, rec_dim].  The call reads the k + 1 frames from
+ * there -- the window and the frame that follows it -- and writes nothing to them; samples may come from different recordings or
+ * overlap in one.  The pointers travel by value in the kernel arguments.  fdesc describes the WINDOW the features are computed
+ * on: without control columns data_dim == rec_dim and control_col < 0; with them data_dim == rec_dim + 3 and
+ * control_col == rec_dim (the dataset's layout: the three columns are appended).  Refused with GM_ERR_INVALID_ARGUMENT and a
+ * "gm_train_batch_build: ..." message, before any device call: any other layout, k_steps < 2, batch outside
+ * 1..GM_TRAIN_BATCH_MAX, nodes_per_graph < 1, the graph builder's limits (batch * N < 2^30, max_neighbours 1..160,
+ * batch * N * max_neighbours < 2^31), a workspace below gm_train_batch_workspace_bytes (which is 0 for such arguments), a null
+ * pointer.  k_steps above 8 is GM_ERR_UNSUPPORTED: a thread keeps its window's positions in registers, the kernel is
+ * instantiated for k_steps 2..8.
+ *   window   the recording's columns; the control columns of frame t are next_xyz - xyz_t where that frame's material column
+ *            equals 1, else 0, from the CLEAN positions.
+ *   noise    seq[0] = 0, vel_t = vel_(t-1) + n_t, seq_t = seq_(t-1) + vel_t in float32, left to right (the first term of a sum
+ *            is the term itself); the window's xyz becomes xyz + seq, the position after the window next + seq[k-1].
+ *            noise_sample [batch, k-1, N, 3] non-NULL gives n as it stands (already scaled, as random_walk_noise takes it);
+ *            else noise_std > 0 draws n_t = z * (float)(noise_std / sqrt(k - 1)); else there is no noise (and nothing is added).
+ *   the draw Philox4x32-10, key (seed & 0xffffffff, seed >> 32), counter (particle index inside its graph, j,
+ *            stream & 0xffffffff, stream >> 32) with stream = first_stream + b for slot b.  Normal number q = 3 (t - 1) + a
+ *            (frame step t = 1..k-1, axis a) is lane q % 4 of call j = q / 4; lanes (0, 1) are the Box-Muller pair of words
+ *            (0, 1), lanes (2, 3) that of words (2, 3): u1 = ((w_even >> 8) + 1) * 2^-24, u2 = (w_odd >> 8) * 2^-24,
+ *            z = sqrt(-2 ln u1) * (cos, sin)(2 pi u2), every operation in float32 (2 pi = 6.2831855f), logf / sincosf the
+ *            accurate ones.  A sample's noise depends on (seed, stream, particle) alone -- not on the batch it rides in, its
+ *            slot, the launch shape or which workspace is used.
+ *   nodes    [batch * N, F] gm_node_features of each (noisy) window;  target [batch * N, 3]
+ *            (((next' - 2 p_(k-1)) + p_(k-2)) - acc_mean) / acc_std on it (compute_target's op order);  windows
+ *            [batch, k, N, data_dim] or NULL: the windows themselves.  Graph b owns rows [b N, (b + 1) N).
+ *   graph    gm_radius_graph_build_batched's, on the noisy last positions, nodes_per_graph = N, fdesc->conn_r.
+ * The workspace begins with a 16-byte record (int32 n_edges, int32 error flags, 8 bytes reserved) that a caller may copy
+ * asynchronously behind the build; gm_train_batch_status turns a HOST copy of it into E (no device access, like
+ * gm_csr_header_status), or into GM_ERR_DATA where a position in one of the k + 1 recorded frames (or the noise) was not finite.
+ * gm_train_batch_num_edges copies the record itself and synchronises `stream`, like gm_radius_graph_num_edges.
+ *
+ * gm_train_batch_edges (phase 2; the caller knows E): edge_index[0] = senders, edge_index[1] = receivers in the reference
+ * order (grouped by sender ascending, distance ascending, batch offsets N * b included), edge_attr in that order.  Arguments as
+ * in phase 1, on its workspace.  n_edges other than the build's count is the caller's error: nothing is written past n_edges
+ * entries, and entries past the build's count are not written at all.
+ * ------------------------------------------------------------------------------------------ */
+#define GM_TRAIN_BATCH_MAX 64
+size_t gm_train_batch_workspace_bytes(const gm_feature_desc* fdesc, int64_t batch, int64_t nodes_per_graph, int max_neighbours);
+int gm_train_batch_build(const float* const* first_frames_host, int64_t batch, int64_t nodes_per_graph, int rec_dim,
+                         const gm_feature_desc* fdesc, int max_neighbours, double noise_std, uint64_t seed, uint64_t first_stream,
+                         const float* noise_sample, float* nodes, float* target, float* windows, void* ws, size_t ws_bytes,
+                         void* stream);
+int gm_train_batch_edges(const void* ws, int64_t batch, int64_t nodes_per_graph, const gm_feature_desc* fdesc, int max_neighbours,
+                         int64_t n_edges, int64_t* edge_index, float* edge_attr, void* stream);
+int gm_train_batch_num_edges(const void* ws, int64_t* n_edges_host, void* stream);
+int gm_train_batch_status(const int32_t* record_host, int64_t* n_edges_host);
+
+/* ------------------------------------------------------------------------------------------
  * Measurement hooks (no reference counterpart; the reference only wraps model.forward in
  * time.time(), examples/optimise_traj.py:99-103).  Per model handle: when enabled, launches made on behalf of THIS
  * model are bracketed with HIP events on their launch stream; other handles and streams are unaffected.
