@@ -48,6 +48,8 @@ PROTOTYPES = {
     "gm_graph_workspace_bytes": (_sz, [_i64, _i32]),
     "gm_radius_graph_build": (_i32, [_vp, _i64, _i64, _f64, _i32, _vp, _sz, _vp]),
     "gm_radius_graph_build_batched": (_i32, [_vp, _i64, _i64, _i64, _f64, _i32, _vp, _sz, _vp]),
+    "gm_graph_ragged_workspace_bytes": (_sz, [_i64, _i64, _i32]),
+    "gm_radius_graph_build_ragged": (_i32, [_vp, _i64, _vp, _i64, _f64, _i32, _vp, _sz, _vp]),
     "gm_radius_graph_num_edges": (_i32, [_vp, C.POINTER(_i64), _vp]),
     "gm_radius_graph_edges": (_i32, [_vp, _i64, _i32, _vp, _vp, _i64, _vp]),
     "gm_csr_workspace_bytes": (_sz, [_i64, _i64]),
@@ -119,6 +121,9 @@ PROTOTYPES = {
     "gm_train_batch_workspace_bytes": (_sz, [_FD, _i64, _i64, _i32]),
     "gm_train_batch_build": (_i32, [_vp, _i64, _i64, _i32, _FD, _i32, _f64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "gm_train_batch_edges": (_i32, [_vp, _i64, _i64, _FD, _i32, _i64, _vp, _vp, _vp]),
+    "gm_train_batch_ragged_workspace_bytes": (_sz, [_FD, _i64, _i64, _i32]),
+    "gm_train_batch_build_ragged": (_i32, [_vp, _vp, _i64, _i32, _FD, _i32, _f64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "gm_train_batch_edges_ragged": (_i32, [_vp, _vp, _i64, _FD, _i32, _i64, _vp, _vp, _vp]),
     "gm_train_batch_num_edges": (_i32, [_vp, C.POINTER(_i64), _vp]),
     "gm_train_batch_status": (_i32, [_vp, C.POINTER(_i64)]),
     "gm_model_profile": (_i32, [_vp, _i32]),

@@ -273,9 +273,12 @@ __device__ __forceinline__ float ord2f(unsigned u) {
     return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
 }
 
+// RAGGED (gm_radius_graph_build_ragged): n_per carries the NUMBER of graphs, not their size
+template <bool RAGGED>
 __device__ void grid_params(GraphHeader* hdr, double r, int max_cells, int64_t n, int64_t n_per);
 
 // bounding box; the block that finishes last derives the grid from it (no separate launch)
+template <bool RAGGED>
 __global__ void __launch_bounds__(256) bbox_kernel(const float* __restrict__ pos, int64_t stride, int64_t n,
                                                     GraphHeader* hdr, double r, int max_cells, int64_t n_per) {
     unsigned mn[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, mx[3] = {0u, 0u, 0u};
@@ -331,16 +334,17 @@ __global__ void __launch_bounds__(256) bbox_kernel(const float* __restrict__ pos
             hdr->bbox_min[a] = atomicMin(&hdr->bbox_min[a], 0xffffffffu);
             hdr->bbox_max[a] = atomicMax(&hdr->bbox_max[a], 0u);
         }
-        grid_params(hdr, r, max_cells, n, n_per);
+        grid_params<RAGGED>(hdr, r, max_cells, n, n_per);
     }
 }
 
 // One thread: grid origin, cell edge h >= r*(1+2^-10) (so |x_i-x_j| <= r implies cell coordinates
 // differ by at most 1 on every axis despite rounding), enlarged until the grid fits max_cells.
+template <bool RAGGED>
 __device__ void grid_params(GraphHeader* hdr, double r, int max_cells, int64_t n, int64_t n_per) {
-    // a batch of equal-sized graphs shares one grid geometry; every graph gets its own block of cells, so
+    // a batch of graphs shares one grid geometry; every graph gets its own block of cells, so
     // no edge can cross graphs (the batch offset rule of collate_utils.py:76)
-    const int64_t n_graphs = n_per > 0 && n > 0 ? (n + n_per - 1) / n_per : 1;
+    const int64_t n_graphs = RAGGED ? n_per : (n_per > 0 && n > 0 ? (n + n_per - 1) / n_per : 1);
     max_cells = (int)(max_cells / n_graphs) > 0 ? (int)(max_cells / n_graphs) : 1;
     double lo[3], ext[3];
     for (int a = 0; a < 3; ++a) {
@@ -373,7 +377,8 @@ __device__ void grid_params(GraphHeader* hdr, double r, int max_cells, int64_t n
     hdr->inv_h = 1.0 / h;
     hdr->ncells_local = d[0] * d[1] * d[2];
     hdr->ncells = hdr->ncells_local * (int)n_graphs;
-    hdr->n_per_graph = (int)(n_per > 0 ? n_per : (n > 0 ? n : 1));
+    // a ragged build has no such number: it reports one graph of n rows, and the destination sort lays out its block tables so
+    hdr->n_per_graph = RAGGED ? (int)n : (int)(n_per > 0 ? n_per : (n > 0 ? n : 1));
 }
 
 __device__ __forceinline__ int cell_coord(float v, double origin, double inv_h, int dim) {
@@ -382,10 +387,28 @@ __device__ __forceinline__ int cell_coord(float v, double origin, double inv_h, 
     return ci;
 }
 
+// The graph of row i of a ragged build: the g with off[g] <= i < off[g + 1].  The table comes by value in the kernel arguments; a
+// search by a divergent index needs it in memory, so the workgroup stages it in LDS first (every thread of the workgroup calls this).
+__device__ __forceinline__ int ragged_graph_of_row(const RaggedOffsets& R, int64_t i) {
+    __shared__ int s_off[GM_RAGGED_MAX_GRAPHS + 1];
+    for (int t = threadIdx.x; t <= R.n_graphs; t += blockDim.x) s_off[t] = R.off[t];
+    __syncthreads();
+    int lo = 0, hi = R.n_graphs;   // off[lo] <= i < off[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if ((int64_t)s_off[mid] <= i) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// Ragged: nothing (row i belongs to graph i / n_per_graph: the instantiation of every equal-sized build), or RaggedOffsets
+template <typename... Ragged>
 __global__ void __launch_bounds__(256) cell_assign_kernel(const float* __restrict__ pos, int64_t stride, int64_t n,
                                                            const GraphHeader* __restrict__ hdr,
-                                                           int* __restrict__ cell_of, int* __restrict__ cell_count) {
+                                                           int* __restrict__ cell_of, int* __restrict__ cell_count, Ragged... ragged) {
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int graph = 0;
+    if constexpr (sizeof...(Ragged) != 0) graph = ragged_graph_of_row(ragged..., i < n ? i : n - 1);
     if (i >= n) return;
     const int dx = hdr->dims[0], dy = hdr->dims[1], dz = hdr->dims[2];
     float x = pos[i * stride], y = pos[i * stride + 1], z = pos[i * stride + 2];
@@ -395,7 +418,8 @@ __global__ void __launch_bounds__(256) cell_assign_kernel(const float* __restric
     int cx = cell_coord(x, hdr->origin[0], hdr->inv_h, dx);
     int cy = cell_coord(y, hdr->origin[1], hdr->inv_h, dy);
     int cz = cell_coord(z, hdr->origin[2], hdr->inv_h, dz);
-    int c = (int)(i / hdr->n_per_graph) * hdr->ncells_local + (cz * dy + cy) * dx + cx;
+    if constexpr (sizeof...(Ragged) == 0) graph = (int)(i / hdr->n_per_graph);
+    int c = graph * hdr->ncells_local + (cz * dy + cy) * dx + cx;
     cell_of[i] = c;
     atomicAdd(&cell_count[c], 1);
 }
@@ -459,7 +483,10 @@ struct Query {
         e = cell_start[row + x1 + 1];
     }
 };
-__device__ __forceinline__ Query decode_query(const float4 q, const GraphHeader* __restrict__ hdr) {
+// cell_of: nothing (the query's graph is qi / n_per_graph), or the rows' cells of a ragged build: the block of cells the query's
+// own cell lies in is its graph's
+template <typename... CellOf>
+__device__ __forceinline__ Query decode_query(const float4 q, const GraphHeader* __restrict__ hdr, CellOf... cell_of) {
     Query Q;
     Q.qi = __float_as_int(q.w);
     Q.dx = hdr->dims[0];
@@ -470,7 +497,12 @@ __device__ __forceinline__ Query decode_query(const float4 q, const GraphHeader*
     const int cy = cell_coord(q.y, hdr->origin[1], inv_h, Q.dy);
     const int cz = cell_coord(q.z, hdr->origin[2], inv_h, dz);
     Q.x = (double)q.x; Q.y = (double)q.y; Q.z = (double)q.z;
-    Q.cbase = (Q.qi / hdr->n_per_graph) * hdr->ncells_local;  // this graph's block of cells
+    if constexpr (sizeof...(CellOf) == 0) {
+        Q.cbase = (Q.qi / hdr->n_per_graph) * hdr->ncells_local;  // this graph's block of cells
+    } else {
+        const int own = (cell_of[Q.qi], ...);
+        Q.cbase = own - own % hdr->ncells_local;
+    }
     Q.x0 = max(cx - 1, 0); Q.x1 = min(cx + 1, Q.dx - 1);
     Q.y0 = max(cy - 1, 0); Q.y1 = min(cy + 1, Q.dy - 1);
     Q.z0 = max(cz - 1, 0); Q.z1 = min(cz + 1, dz - 1);
@@ -491,18 +523,21 @@ __device__ __forceinline__ double query_dist2(const Query& Q, const float4 p) {
 // indeg / arrival (optional: the rollout step's fused path): the counting pass of the destination sort rides along -- every kept
 // neighbour takes its arrival number within its aggregation node's segment (flow 0: the neighbour, 1: the query) from an atomic on
 // indeg[], so that the fill pass places the edge with plain stores (see indeg_graph_kernel, the stand-alone form of the same count).
+// CellOf: see decode_query (nothing for every equal-sized build, const int* for a ragged one)
+template <typename... CellOf>
 __global__ void __launch_bounds__(256) neighbor_fast_kernel(const float4* __restrict__ sorted,
                                                              const int* __restrict__ cell_start,
                                                              const GraphHeader* __restrict__ hdr, int64_t n, double r2,
                                                              int K, int* __restrict__ cnt, int* __restrict__ nbr,
-                                                             int* __restrict__ indeg, int* __restrict__ arrival, int flow) {
+                                                             int* __restrict__ indeg, int* __restrict__ arrival, int flow,
+                                                             CellOf... cell_of) {
     __shared__ double sd2[NB_QPB * NB_STRIDE];
     __shared__ int sj[NB_QPB * NB_STRIDE];
     const int tid = threadIdx.x, sub = tid & (NB_LPQ - 1), ql = tid / NB_LPQ, lane = tid & 63;
     const int grp_shift = (lane / NB_LPQ) * NB_LPQ;  // position of this group's bits in the wave ballot
     const int64_t slot = (int64_t)blockIdx.x * NB_QPB + ql;
     const bool active = slot < n;
-    const Query Q = decode_query(sorted[active ? slot : 0], hdr);
+    const Query Q = decode_query(sorted[active ? slot : 0], hdr, cell_of...);
     const int qi = Q.qi;
     double* ld = sd2 + ql * NB_STRIDE;
     int* lj = sj + ql * NB_STRIDE;
@@ -572,12 +607,13 @@ __global__ void __launch_bounds__(256) neighbor_fast_kernel(const float4* __rest
 // neighbour search: thread t owns the query in sorted slot t; candidate lists live in LDS as
 // [slot][thread] (conflict-free), kept sorted by (d2, index).
 // ------------------------------------------------------------------------------------------
-template <int BS>
+template <int BS, typename... CellOf>
 __global__ void __launch_bounds__(BS) neighbor_kernel(const float4* __restrict__ sorted,
                                                        const int* __restrict__ cell_start,
                                                        const GraphHeader* __restrict__ hdr, int64_t n, double r2,
                                                        int K, int* __restrict__ cnt, int* __restrict__ nbr,
-                                                       int* __restrict__ indeg, int* __restrict__ arrival, int flow) {
+                                                       int* __restrict__ indeg, int* __restrict__ arrival, int flow,
+                                                       CellOf... cell_of) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     double* kd = reinterpret_cast<double*>(smem);                   // [K][BS]
     int* ki = reinterpret_cast<int*>(smem + (size_t)K * BS * 8);    // [K][BS]
@@ -586,7 +622,7 @@ __global__ void __launch_bounds__(BS) neighbor_kernel(const float4* __restrict__
     if (slot >= n) return;
     const float4 q = sorted[slot];
     if (cnt[__float_as_int(q.w)] != -1) return;  // done by neighbor_fast_kernel
-    const Query Q = decode_query(q, hdr);
+    const Query Q = decode_query(q, hdr, cell_of...);
     const int qi = Q.qi;
     int kept = 0;
     for (int z = Q.z0; z <= Q.z1; ++z) {
@@ -812,10 +848,19 @@ __global__ void __launch_bounds__(256) segment_sort_kernel(const int* __restrict
 
 // The grid phase of a build, behind its resets: bounding box + grid, cell assignment, ONE-launch scan of the cell counts, cell fill
 // (-> g.sorted: the rows grouped by cell, g.cell_start: where each cell's rows begin)
-static int grid_phase(const float* pos, int64_t pos_stride, int64_t n, int64_t n_per, double conn_r, const GraphWs& g, hipStream_t s) {
+// ragged (or nullptr: graphs of n_per rows): the graphs' offsets
+static int grid_phase(const float* pos, int64_t pos_stride, int64_t n, int64_t n_per, double conn_r, const GraphWs& g, hipStream_t s,
+                      const RaggedOffsets* ragged = nullptr) {
     const int nb = (int)cdiv(n, 256);
-    hipLaunchKernelGGL(bbox_kernel, dim3(nb < 64 ? nb : 64), dim3(256), 0, s, pos, pos_stride, n, g.hdr, conn_r, g.max_cells, n_per);
-    hipLaunchKernelGGL(cell_assign_kernel, dim3(nb), dim3(256), 0, s, pos, pos_stride, n, g.hdr, g.cell_of, g.cell_start);
+    if (ragged) {
+        hipLaunchKernelGGL(bbox_kernel<true>, dim3(nb < 64 ? nb : 64), dim3(256), 0, s, pos, pos_stride, n, g.hdr, conn_r, g.max_cells,
+                           (int64_t)ragged->n_graphs);
+        hipLaunchKernelGGL(cell_assign_kernel<RaggedOffsets>, dim3(nb), dim3(256), 0, s, pos, pos_stride, n, g.hdr, g.cell_of, g.cell_start,
+                           *ragged);
+    } else {
+        hipLaunchKernelGGL(bbox_kernel<false>, dim3(nb < 64 ? nb : 64), dim3(256), 0, s, pos, pos_stride, n, g.hdr, conn_r, g.max_cells, n_per);
+        hipLaunchKernelGGL(cell_assign_kernel<>, dim3(nb), dim3(256), 0, s, pos, pos_stride, n, g.hdr, g.cell_of, g.cell_start);
+    }
     const ScanJob sj{g.cell_start, g.cell_start, (long long)g.max_cells + 1, nullptr, g.scan_cells};
     const int rc = scan_lookback(&sj, 1, s);
     if (rc != GM_OK) return rc;
@@ -876,20 +921,21 @@ int check_build_args(const float* pos, int64_t pos_stride, int64_t n, int64_t n_
 
 // The general neighbour kernel at BS queries per workgroup: K * BS (d2, index) entries of LDS, above 64 KiB behind the attribute
 // that allows it (raised once per device)
-template <int BS>
-int launch_neighbor(const GraphWs& g, int64_t n, double r2, int K, int* indeg, int* slot, int flow, hipStream_t s) {
+template <int BS, typename... CellOf>
+int launch_neighbor(const GraphWs& g, int64_t n, double r2, int K, int* indeg, int* slot, int flow, hipStream_t s, CellOf... cell_of) {
+    const auto kernel = neighbor_kernel<BS, CellOf...>;
     const size_t lds = (size_t)K * BS * 12;
     GM_REQUIRE(lds <= 160 * 1024, GM_ERR_UNSUPPORTED, "gm_radius_graph_build: max_neighbours=%d needs %zu bytes of LDS", K, lds);
     if (lds > 64 * 1024) {
         static PerDeviceOnce big_lds;
-        const int rc_attr = big_lds.run([]() -> int {
-            GM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(neighbor_kernel<BS>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        const int rc_attr = big_lds.run([kernel]() -> int {
+            GM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
             return GM_OK;
         });
         if (rc_attr != GM_OK) return rc_attr;
     }
-    hipLaunchKernelGGL(neighbor_kernel<BS>, dim3((int)cdiv(n, BS)), dim3(BS), lds, s, g.sorted, g.cell_start, g.hdr, n, r2, K, g.cnt, g.nbr,
-                       indeg, slot, flow);
+    hipLaunchKernelGGL(kernel, dim3((int)cdiv(n, BS)), dim3(BS), lds, s, g.sorted, g.cell_start, g.hdr, n, r2, K, g.cnt, g.nbr,
+                       indeg, slot, flow, cell_of...);
     GM_LAUNCH_CHECK();
     return GM_OK;
 }
@@ -910,9 +956,43 @@ int radius_graph_build_core(const float* pos, int64_t pos_stride, int64_t n, int
     const int rc = grid_phase(pos, pos_stride, n, n_per, conn_r, g, s);
     if (rc != GM_OK) return rc;
     const double r2 = conn_r * conn_r;  // KDTree compares rdist with r*r in float64
-    hipLaunchKernelGGL(neighbor_fast_kernel, dim3((unsigned)cdiv(n, NB_QPB)), dim3(256), 0, s, g.sorted, g.cell_start,
+    hipLaunchKernelGGL(neighbor_fast_kernel<>, dim3((unsigned)cdiv(n, NB_QPB)), dim3(256), 0, s, g.sorted, g.cell_start,
                        g.hdr, n, r2, K, g.cnt, g.nbr, indeg, slot, flow);
     return K <= 64 ? launch_neighbor<128>(g, n, r2, K, indeg, slot, flow, s) : launch_neighbor<64>(g, n, r2, K, indeg, slot, flow, s);
+}
+// The same six launches for graphs of any sizes: the table gives cell_assign_kernel the graph of a row, and a query takes its
+// graph's block of cells from its own cell
+int radius_graph_build_ragged_core(const float* pos, int64_t pos_stride, const RaggedOffsets& R, double conn_r, int K, const GraphWs& g,
+                                   hipStream_t s) {
+    const int64_t n = R.off[R.n_graphs];
+    const int rc = grid_phase(pos, pos_stride, n, 0, conn_r, g, s, &R);
+    if (rc != GM_OK) return rc;
+    const double r2 = conn_r * conn_r;
+    const int* cell_of = g.cell_of;
+    hipLaunchKernelGGL(neighbor_fast_kernel<const int*>, dim3((unsigned)cdiv(n, NB_QPB)), dim3(256), 0, s, g.sorted, g.cell_start,
+                       g.hdr, n, r2, K, g.cnt, g.nbr, (int*)nullptr, (int*)nullptr, 0, cell_of);
+    return K <= 64 ? launch_neighbor<128>(g, n, r2, K, nullptr, nullptr, 0, s, cell_of) : launch_neighbor<64>(g, n, r2, K, nullptr, nullptr, 0, s, cell_of);
+}
+// What gm_radius_graph_build_ragged checks of its arguments, and the table
+int ragged_offsets(const int64_t* off, int64_t n_graphs, double conn_r, int K, const void* ws, const char* who, RaggedOffsets* out) {
+    GM_REQUIRE(n_graphs >= 1 && n_graphs <= GM_RAGGED_MAX_GRAPHS, GM_ERR_INVALID_ARGUMENT, "%s: n_graphs=%lld outside 1..%d", who,
+               (long long)n_graphs, GM_RAGGED_MAX_GRAPHS);
+    GM_REQUIRE(off && ws, GM_ERR_INVALID_ARGUMENT, "%s: null pointer", who);
+    GM_REQUIRE(off[0] == 0, GM_ERR_INVALID_ARGUMENT, "%s: graph_offsets[0]=%lld, not 0", who, (long long)off[0]);
+    out->n_graphs = (int)n_graphs;
+    out->off[0] = 0;
+    for (int64_t g = 0; g < n_graphs; ++g) {
+        GM_REQUIRE(off[g + 1] > off[g], GM_ERR_INVALID_ARGUMENT, "%s: graph %lld has %lld rows (< 1)", who, (long long)g,
+                   (long long)(off[g + 1] - off[g]));
+        GM_REQUIRE(off[g + 1] < (int64_t)1 << 30, GM_ERR_INVALID_ARGUMENT, "%s: n_nodes=%lld out of range (< 2^30)", who, (long long)off[g + 1]);
+        out->off[g + 1] = (int)off[g + 1];
+    }
+    for (int64_t g = n_graphs + 1; g <= GM_RAGGED_MAX_GRAPHS; ++g) out->off[g] = out->off[n_graphs];
+    const int64_t n = off[n_graphs];
+    GM_REQUIRE(K >= 1 && K <= 160, GM_ERR_INVALID_ARGUMENT, "%s: max_neighbours=%d unsupported (1..160)", who, K);
+    GM_REQUIRE(n * (int64_t)K < (int64_t)1 << 31, GM_ERR_INVALID_ARGUMENT, "%s: n_nodes * max_neighbours overflows int32", who);
+    GM_REQUIRE(conn_r > 0.0 && conn_r == conn_r, GM_ERR_INVALID_ARGUMENT, "%s: conn_r must be > 0", who);
+    return GM_OK;
 }
 }  // namespace gm
 
@@ -930,6 +1010,34 @@ int gm_radius_graph_build_batched(const float* pos, int64_t pos_stride, int64_t 
     rc = graph_clear_jobs(clr, g, n);
     if (rc == GM_OK) rc = launch_step_clear(clr, s);
     if (rc == GM_OK) rc = radius_graph_build_core(pos, pos_stride, n, n_per, conn_r, K, g, nullptr, nullptr, 0, s);
+    if (rc != GM_OK) return rc;
+    const ScanJob sj{g.cnt, g.out_ptr, (long long)n + 1, &g.hdr->n_edges, g.scan_cnt};
+    return scan_lookback(&sj, 1, s);
+}
+
+size_t gm_graph_ragged_workspace_bytes(int64_t n_nodes, int64_t n_graphs, int max_neighbours) {
+    if (n_graphs < 1 || n_graphs > GM_RAGGED_MAX_GRAPHS || n_nodes < n_graphs || n_nodes >= (int64_t)1 << 30) return 0;
+    if (max_neighbours < 1 || max_neighbours > 160 || n_nodes * max_neighbours >= (int64_t)1 << 31) return 0;
+    return carve_graph(nullptr, n_nodes, max_neighbours).bytes;   // the offsets travel in the kernel arguments: nothing is added
+}
+
+int gm_radius_graph_build_ragged(const float* pos, int64_t pos_stride, const int64_t* graph_offsets_host, int64_t n_graphs, double conn_r,
+                                 int K, void* ws, size_t ws_bytes, void* stream) {
+    const char* who = "gm_radius_graph_build_ragged";
+    RaggedOffsets R;
+    int rc = ragged_offsets(graph_offsets_host, n_graphs, conn_r, K, ws, who, &R);
+    if (rc != GM_OK) return rc;
+    GM_REQUIRE(pos, GM_ERR_INVALID_ARGUMENT, "%s: null pointer", who);
+    GM_REQUIRE(pos_stride >= 3, GM_ERR_INVALID_ARGUMENT, "%s: pos_stride < 3", who);
+    const int64_t n = R.off[R.n_graphs];
+    GraphWs g = carve_graph(ws, n, K);
+    GM_REQUIRE(ws_bytes >= g.bytes, GM_ERR_INVALID_ARGUMENT, "%s: workspace %zu < %zu", who, ws_bytes, g.bytes);
+    gm::DevGuard dev_guard(pos);
+    hipStream_t s = (hipStream_t)stream;
+    StepClear clr;
+    rc = graph_clear_jobs(clr, g, n);
+    if (rc == GM_OK) rc = launch_step_clear(clr, s);
+    if (rc == GM_OK) rc = radius_graph_build_ragged_core(pos, pos_stride, R, conn_r, K, g, s);
     if (rc != GM_OK) return rc;
     const ScanJob sj{g.cnt, g.out_ptr, (long long)n + 1, &g.hdr->n_edges, g.scan_cnt};
     return scan_lookback(&sj, 1, s);

@@ -23,6 +23,18 @@ int radius_graph_check_args(const float* pos, int64_t pos_stride, int64_t n, int
 int radius_graph_build_core(const float* pos, int64_t pos_stride, int64_t n, int64_t n_per, double conn_r, int K, const GraphWs& g,
                             int* indeg, int* slot, int flow, hipStream_t s);
 
+// The graphs of a ragged build (gm_radius_graph_build_ragged): graph g owns rows [off[g], off[g + 1]).  The table travels by value
+// in the kernel arguments -- no copy, no allocation; the one kernel that needs the graph of a row stages it in LDS.
+struct RaggedOffsets {
+    int n_graphs;
+    int off[GM_RAGGED_MAX_GRAPHS + 1];
+};
+// host offsets -> table, behind every check gm_radius_graph_build_ragged makes of them and of the other arguments (`who` opens
+// the message of a refusal); radius_graph_build_ragged_core: radius_graph_build_core with the graph of a row from the table
+int ragged_offsets(const int64_t* offsets_host, int64_t n_graphs, double conn_r, int K, const void* ws, const char* who, RaggedOffsets* out);
+int radius_graph_build_ragged_core(const float* pos, int64_t pos_stride, const RaggedOffsets& R, double conn_r, int K, const GraphWs& g,
+                                   hipStream_t s);
+
 // Width of a scene's node features: 3 (k_steps - 1) velocities, 6 boundary terms, the material, and 3 more with control columns
 __host__ __device__ static inline int node_feature_dim(int k_steps, int control_col) { return 3 * (k_steps - 1) + 7 + (control_col >= 0 ? 3 : 0); }
 inline int node_feature_dim(const gm_feature_desc* fd) { return node_feature_dim(fd->k_steps, fd->control_col); }

@@ -65,13 +65,14 @@ def collate_graphs(items):
 
 
 class _QueuedBatch:
-    """Phase 1 of one batch, queued (gm_train_batch_build): one build per group of samples of equal N, each in a workspace of its
-    own, the 16-byte records of the workspaces on their way into pinned rows and an event behind the copies -- the _HeaderWatch
-    pattern of epd_gnn.py.  ``finish`` waits for that event alone, reads the edge counts and queues phase 2."""
+    """Phase 1 of one batch, queued: ONE build in one workspace -- gm_train_batch_build where the samples have equal N,
+    gm_train_batch_build_ragged where they do not -- the workspace's 16-byte record on its way into a pinned row and an event
+    behind the copy: the _HeaderWatch pattern of epd_gnn.py.  ``finish`` waits for that event alone, reads the edge count and
+    queues phase 2."""
 
     def __init__(self, dataset, indices, seed, first_stream, workspaces, pinned):
-        """workspaces: a list this batch may grow (one uint8 tensor per build, reused where large enough); pinned: int32
-        [>= builds, 4] in pinned memory.  Both belong to the caller and stay untouched by it until ``finish`` has returned."""
+        """workspaces: a list this batch may grow (the build's uint8 tensor, reused where large enough); pinned: int32 [>= 1, 4]
+        in pinned memory.  Both belong to the caller and stay untouched by it until ``finish`` has returned."""
         ds = self.ds = dataset
         L, dev = lib(), ds.device
         self.fd = ds._window_desc()
@@ -79,53 +80,58 @@ class _QueuedBatch:
         # the quirk of the reference kept: the noise-free path builds its graph with the default 20 neighbours (graph.py)
         self.k_nb = 20 if ds.noise is None else int(ds.max_neighbours)
         noise_std = 0.0 if ds.noise is None else float(ds.noise)
+        batch = self.batch = len(indices)
         ns = [int(ds.sims[ds.index[int(i)][0]].shape[1]) for i in indices]
-        # samples of equal N ride in one build; a batch that mixes sizes is built sample by sample
-        groups = [list(indices)] if len(set(ns)) == 1 else [[i] for i in indices]
-        assert len(groups) <= pinned.shape[0]
-        self.builds, self.pinned = [], pinned
-        stream = current_stream(dev)
-        done = 0
+        rows = sum(ns)
+        # samples of equal N: the equal-sized entry points; a batch that mixes sizes: the ragged ones, with the sizes as a host array
+        self.sizes = None if len(set(ns)) == 1 else (C.c_int64 * batch)(*ns)
+        self.n, self.pinned = ns[0], pinned
+        frames = (C.c_void_p * batch)()
+        for b, i in enumerate(indices):
+            sim, t = ds.index[int(i)]
+            data = ds.sims[sim]
+            assert data.is_contiguous() and data.dtype == torch.float32, "resident recordings are row-major float32"
+            frames[b] = data.data_ptr() + t * data.shape[1] * data.shape[2] * 4
         with torch.cuda.device(dev):
-            for g, idx in enumerate(groups):
-                frames = (C.c_void_p * len(idx))()
-                for b, i in enumerate(idx):
-                    sim, t = ds.index[int(i)]
-                    data = ds.sims[sim]
-                    assert data.is_contiguous() and data.dtype == torch.float32, "resident recordings are row-major float32"
-                    frames[b] = data.data_ptr() + t * data.shape[1] * data.shape[2] * 4
-                n = int(ds.sims[ds.index[int(idx[0])][0]].shape[1])
-                need = L.gm_train_batch_workspace_bytes(C.byref(self.fd), len(idx), n, self.k_nb)
-                if g == len(workspaces):
-                    workspaces.append(None)
-                if workspaces[g] is None or workspaces[g].numel() < need:
-                    workspaces[g] = _ws(need, dev)
-                ws = workspaces[g]
-                nodes = torch.empty((len(idx) * n, f), dtype=torch.float32, device=dev)
-                target = torch.empty((len(idx) * n, 3), dtype=torch.float32, device=dev)
-                check(L.gm_train_batch_build(frames, len(idx), n, ds.data_dim, C.byref(self.fd), self.k_nb, noise_std, int(seed),
-                                             int(first_stream) + done, None, ptr(nodes), ptr(target), None, ptr(ws), ws.numel(), stream))
-                pinned[g].copy_(ws[:16].view(torch.int32), non_blocking=True)
-                self.builds.append((ws, len(idx), n, nodes, target))
-                done += len(idx)
+            if self.sizes is None:
+                need = L.gm_train_batch_workspace_bytes(C.byref(self.fd), batch, self.n, self.k_nb)
+            else:
+                need = L.gm_train_batch_ragged_workspace_bytes(C.byref(self.fd), rows, batch, self.k_nb)
+            if not workspaces:
+                workspaces.append(None)
+            if workspaces[0] is None or workspaces[0].numel() < need:
+                workspaces[0] = _ws(need, dev)
+            ws = self.ws = workspaces[0]
+            self.nodes = torch.empty((rows, f), dtype=torch.float32, device=dev)
+            self.target = torch.empty((rows, 3), dtype=torch.float32, device=dev)
+            stream = current_stream(dev)
+            if self.sizes is None:
+                check(L.gm_train_batch_build(frames, batch, self.n, ds.data_dim, C.byref(self.fd), self.k_nb, noise_std, int(seed),
+                                             int(first_stream), None, ptr(self.nodes), ptr(self.target), None, ptr(ws), ws.numel(), stream))
+            else:
+                check(L.gm_train_batch_build_ragged(frames, self.sizes, batch, ds.data_dim, C.byref(self.fd), self.k_nb, noise_std,
+                                                    int(seed), int(first_stream), None, ptr(self.nodes), ptr(self.target), None, ptr(ws),
+                                                    ws.numel(), stream))
+            pinned[0].copy_(ws[:16].view(torch.int32), non_blocking=True)
             self.event = torch.cuda.Event()
             self.event.record(torch.cuda.current_stream(dev))
 
     def finish(self):
-        """The batch: waits for the records (not for the stream), then phase 2 of every build."""
+        """The batch: waits for the record (not for the stream), then phase 2."""
         L, dev = lib(), self.ds.device
         self.event.synchronize()
-        items = []
-        for g, (ws, b, n, nodes, target) in enumerate(self.builds):
-            e = C.c_int64(0)
-            check(L.gm_train_batch_status(C.c_void_p(self.pinned[g].data_ptr()), C.byref(e)))
-            e = int(e.value)
-            edge_index = torch.empty((2, e), dtype=torch.int64, device=dev)
-            edge_attr = torch.empty((e, 4), dtype=torch.float32, device=dev)
-            check(L.gm_train_batch_edges(ptr(ws), b, n, C.byref(self.fd), self.k_nb, e, ptr(edge_index), ptr(edge_attr),
-                                         current_stream(dev)))
-            items.append(GraphData(nodes, edge_attr, edge_index, target))
-        return items[0] if len(items) == 1 else collate_graphs(items)
+        e = C.c_int64(0)
+        check(L.gm_train_batch_status(C.c_void_p(self.pinned[0].data_ptr()), C.byref(e)))
+        e = int(e.value)
+        edge_index = torch.empty((2, e), dtype=torch.int64, device=dev)
+        edge_attr = torch.empty((e, 4), dtype=torch.float32, device=dev)
+        if self.sizes is None:
+            check(L.gm_train_batch_edges(ptr(self.ws), self.batch, self.n, C.byref(self.fd), self.k_nb, e, ptr(edge_index),
+                                         ptr(edge_attr), current_stream(dev)))
+        else:
+            check(L.gm_train_batch_edges_ragged(ptr(self.ws), self.sizes, self.batch, C.byref(self.fd), self.k_nb, e, ptr(edge_index),
+                                                ptr(edge_attr), current_stream(dev)))
+        return GraphData(self.nodes, edge_attr, edge_index, self.target)
 
 
 def _pinned_records(rows):
@@ -267,7 +273,8 @@ class GraphLoader:
     fused path.  ``prefetch=1`` queues the first phase of the next batch, in a second workspace on the same stream, before a
     batch is handed out: when the next batch is asked for, its edge count has long arrived (it was computed before the
     caller's training step began), nothing waits and the stream is never synchronised.  ``prefetch=0`` waits for its own build.
-    A batch larger than 64 (GM_TRAIN_BATCH_MAX) is refused by the library."""
+    A batch whose samples differ in N (recordings of different sizes) is one ragged build, like a batch of equal sizes one
+    equal-sized build.  A batch larger than 64 (GM_TRAIN_BATCH_MAX) is refused by the library."""
 
     def __init__(self, dataset, batch_size=2, shuffle=False, seed=None, fused=False, prefetch=1):
         self.dataset, self.batch_size, self.shuffle = dataset, batch_size, shuffle

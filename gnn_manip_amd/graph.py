@@ -7,6 +7,7 @@ rejected: there is no CPU fallback in the product path.
 """
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -35,7 +36,7 @@ def _pos_view(pos):
 class RadiusGraph:
     """Device-resident result of one radius-graph build (neighbour lists in a workspace)."""
 
-    def __init__(self, pos_nodes, conn_r, max_neighbours=20, nodes_per_graph=None):
+    def __init__(self, pos_nodes, conn_r, max_neighbours=20, nodes_per_graph=None, graph_sizes=None):
         _need_cuda(pos_nodes, "pos_nodes")
         pos, stride = _pos_view(pos_nodes)
         self._keep = pos
@@ -43,6 +44,18 @@ class RadiusGraph:
         self.max_neighbours = int(max_neighbours)
         self.device = pos.device
         L = lib()
+        if graph_sizes is not None:
+            if nodes_per_graph is not None:
+                raise ValueError("RadiusGraph: nodes_per_graph and graph_sizes exclude each other")
+            sizes = [int(v) for v in graph_sizes]
+            if sum(sizes) != self.n:
+                raise ValueError(f"RadiusGraph: graph_sizes add up to {sum(sizes)}, the positions have {self.n} rows")
+            offsets = (C.c_int64 * (len(sizes) + 1))(0, *np.cumsum(sizes, dtype=np.int64).tolist())
+            # a refused shape has a query of 0: the build then says why
+            self.ws = _ws(L.gm_graph_ragged_workspace_bytes(self.n, len(sizes), self.max_neighbours), self.device)
+            check(L.gm_radius_graph_build_ragged(C.c_void_p(pos.data_ptr()), stride, offsets, len(sizes), float(conn_r),
+                                                 self.max_neighbours, ptr(self.ws), self.ws.numel(), current_stream()))
+            return
         self.ws = _ws(L.gm_graph_workspace_bytes(self.n, self.max_neighbours), self.device)
         per = self.n if nodes_per_graph is None else int(nodes_per_graph)
         check(L.gm_radius_graph_build_batched(C.c_void_p(pos.data_ptr()), stride, self.n, per, float(conn_r),
@@ -62,14 +75,16 @@ class RadiusGraph:
         return senders, receivers
 
 
-def get_connectivity(pos_nodes, conn_r, max_neighbours=20, nodes_per_graph=None):
+def get_connectivity(pos_nodes, conn_r, max_neighbours=20, nodes_per_graph=None, graph_sizes=None):
     """Reference ``get_connectivity`` (gnn_manip/utils/utils.py:64-93).
 
     Returns (senders, receivers) int64: senders = query node repeated, receivers = its in-radius
     neighbours by ascending distance, at most ``max_neighbours`` (self edge first).
     ``nodes_per_graph``: the positions are a batch of equal-sized graphs stored back to back; edges never
-    cross graphs and indices carry the batch offset (collate_utils.py:76)."""
-    return RadiusGraph(pos_nodes, conn_r, max_neighbours, nodes_per_graph).edges()
+    cross graphs and indices carry the batch offset (collate_utils.py:76).
+    ``graph_sizes``: the same for graphs of any sizes (at most 64), given as the list of their row counts; graph g owns the rows
+    behind those of the graphs before it, as torch_geometric's loader collates them.  Not together with ``nodes_per_graph``."""
+    return RadiusGraph(pos_nodes, conn_r, max_neighbours, nodes_per_graph, graph_sizes).edges()
 
 
 class _EdgeFeaturesFunction(torch.autograd.Function):

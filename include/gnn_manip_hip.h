@@ -65,6 +65,27 @@ int gm_radius_graph_build(const float* pos, int64_t pos_stride, int64_t n_nodes,
 int gm_radius_graph_build_batched(const float* pos, int64_t pos_stride, int64_t n_nodes, int64_t nodes_per_graph,
                                   double conn_r, int max_neighbours, void* graph_ws, size_t graph_ws_bytes, void* stream);
 
+/* Same for n_graphs graphs of ANY sizes stored back to back (an addition to ABI 7): graph g owns rows
+ * [graph_offsets_host[g], graph_offsets_host[g + 1]), n_nodes = graph_offsets_host[n_graphs] -- the batch torch_geometric's
+ * loader collates (edge indices offset by the running node count).  The result is gm_radius_graph_build's on each graph alone
+ * with the graph's row offset on its indices: the edge list equals the concatenation of the per-graph lists bit for bit, ties
+ * included (a graph's rows keep their order, so (d2, index) ranks the same), and with all sizes equal it is
+ * gm_radius_graph_build_batched's.  graph_offsets_host is a HOST array; the offsets travel by value in the kernel arguments
+ * (no copy, no allocation, no host synchronisation), which is why a build takes at most GM_RAGGED_MAX_GRAPHS graphs.  Refused
+ * with GM_ERR_INVALID_ARGUMENT and a "gm_radius_graph_build_ragged: ..." message, before any device call: n_graphs outside
+ * 1..GM_RAGGED_MAX_GRAPHS, graph_offsets_host[0] != 0, a graph of fewer than 1 row, a null pointer, n_nodes >= 2^30,
+ * max_neighbours outside 1..160, n_nodes * max_neighbours >= 2^31, conn_r <= 0, pos_stride < 3, a workspace below
+ * gm_graph_ragged_workspace_bytes (which is 0 for such arguments).
+ * The workspace has the layout of gm_graph_workspace_bytes(n_nodes, max_neighbours) -- nothing but the kernels reads the offsets
+ * -- so gm_radius_graph_num_edges and gm_radius_graph_edges(graph_ws, n_nodes, max_neighbours, ...) read it as they read any
+ * other.  Its device header reports nodes_per_graph = n_nodes: gm_csr_from_graph(_flow) on a ragged workspace lays out its
+ * block tables as for ONE graph, which is exactly what a collated edge_index gets from gm_csr_from_edge_index. */
+#define GM_RAGGED_MAX_GRAPHS 64 /* == GM_TRAIN_BATCH_MAX */
+size_t gm_graph_ragged_workspace_bytes(int64_t n_nodes, int64_t n_graphs, int max_neighbours);
+int gm_radius_graph_build_ragged(const float* pos, int64_t pos_stride, const int64_t* graph_offsets_host /*[n_graphs+1]*/,
+                                 int64_t n_graphs, double conn_r, int max_neighbours, void* graph_ws, size_t graph_ws_bytes,
+                                 void* stream);
+
 /* Synchronises `stream`; returns E and the device error flags of the last build. */
 int gm_radius_graph_num_edges(const void* graph_ws, int64_t* n_edges_host, void* stream);
 
@@ -666,6 +687,28 @@ int gm_train_batch_edges(const void* ws, int64_t batch, int64_t nodes_per_graph,
                          int64_t n_edges, int64_t* edge_index, float* edge_attr, void* stream);
 int gm_train_batch_num_edges(const void* ws, int64_t* n_edges_host, void* stream);
 int gm_train_batch_status(const int32_t* record_host, int64_t* n_edges_host);
+
+/* The same two phases for samples of DIFFERENT sizes (an addition to ABI 7): sizes_host is a HOST array, sizes_host[b] = N_b
+ * the rows of sample b's recording, first_frames_host[b] points at a frame of a resident recording [T, N_b, rec_dim].  Sample b
+ * owns rows [off_b, off_b + N_b) of nodes and target, off_b = N_0 + .. + N_(b-1); windows holds the samples' [k, N_b, data_dim]
+ * blocks back to back, noise_sample their [k-1, N_b, 3] blocks back to back.  Everything said of gm_train_batch_build holds per
+ * sample -- window, control columns from the clean positions, noise, features, target -- and the draw's counter is unchanged
+ * (particle index INSIDE its graph, j, stream = first_stream + b): a sample's noise does not depend on whether it rides in a
+ * ragged batch, in an equal-sized one or alone.  The graph is gm_radius_graph_build_ragged's; the record, gm_train_batch_status
+ * and gm_train_batch_num_edges serve it unchanged; phase 2 emits edge_index in the reference order with the samples' row
+ * offsets, and edge_attr.  With all sizes equal every output is bit-equal to gm_train_batch_build / gm_train_batch_edges.  One
+ * clear launch, one row kernel (grid: the largest sample x batch), the graph build and one scan, as for an equal-sized batch;
+ * the sizes travel by value in the kernel arguments.  Refusals ("gm_train_batch_build_ragged: ..." / "gm_train_batch_edges_ragged:
+ * ...", GM_ERR_INVALID_ARGUMENT, before any device call) are gm_train_batch_build's, with: a size below 1, and the graph
+ * builder's limits on the total of the sizes.  gm_train_batch_ragged_workspace_bytes takes that total; it is 0 for refused
+ * shapes (total_rows < batch among them) and depends on the sizes through (total_rows, batch) alone. */
+size_t gm_train_batch_ragged_workspace_bytes(const gm_feature_desc* fdesc, int64_t total_rows, int64_t batch, int max_neighbours);
+int gm_train_batch_build_ragged(const float* const* first_frames_host, const int64_t* sizes_host, int64_t batch, int rec_dim,
+                                const gm_feature_desc* fdesc, int max_neighbours, double noise_std, uint64_t seed,
+                                uint64_t first_stream, const float* noise_sample, float* nodes, float* target, float* windows,
+                                void* ws, size_t ws_bytes, void* stream);
+int gm_train_batch_edges_ragged(const void* ws, const int64_t* sizes_host, int64_t batch, const gm_feature_desc* fdesc,
+                                int max_neighbours, int64_t n_edges, int64_t* edge_index, float* edge_attr, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Measurement hooks (no reference counterpart; the reference only wraps model.forward in

@@ -11,6 +11,9 @@ hidden 128, 10 message-passing steps, L1 loss, Adam).  Every variant is warmed, 
 --rounds rounds; a window is --steps steps and ends in a synchronise.  Prints one JSON line with every round.
 
     python tools/bench_loader.py [--n 5000] [--sims 2] [--frames 206] [--steps 200] [--rounds 3]
+
+--n-list 5000,4000 gives the recordings those sizes in turn (recording s has n_list[s % len] rows, each at its own size's density):
+a shuffled loader then meets batches that mix sizes, which the fused variants build in one ragged library call.
 """
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -37,6 +40,7 @@ def recording(n, frames, seed, side):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=5000)
+    ap.add_argument("--n-list", type=str, default=None, help="comma-separated recording sizes, taken in turn (overrides --n)")
     ap.add_argument("--sims", type=int, default=2)
     ap.add_argument("--frames", type=int, default=206, help="frames per recording: an epoch is sims * (frames - k) / batch batches")
     ap.add_argument("--k", type=int, default=6)
@@ -51,8 +55,10 @@ def main():
         raise SystemExit("bench_loader: no HIP device (there is no CPU fallback)")
     from gnn_manip_amd import CoffeeDataset, EncProcDecGNN, GraphLoader, scene
     dev = torch.device("cuda:0")
-    side = 0.152 * (args.n / 5000.0) ** (1.0 / 3.0) * 0.8            # tools/bench_train.py's density
-    sims = [torch.from_numpy(recording(args.n, args.frames, 300 + s, side)).to(dev) for s in range(args.sims)]
+    n_list = [int(v) for v in args.n_list.split(",")] if args.n_list else [args.n]
+    sizes = [n_list[s % len(n_list)] for s in range(args.sims)]
+    side = lambda n: 0.152 * (n / 5000.0) ** (1.0 / 3.0) * 0.8        # tools/bench_train.py's density
+    sims = [torch.from_numpy(recording(n, args.frames, 300 + s, side(n))).to(dev) for s, n in enumerate(sizes)]
     ds = CoffeeDataset.from_recordings(sims, args.k, 0.015, scene.STATS, scene.BOUNDS, scene.CART, scene.MAT[0], scene.CTRL, noise=args.noise,
                                        use_control=True)
     H, M = args.hidden, 10
@@ -110,7 +116,7 @@ def main():
            "value": float(np.median(rounds["fused_p1"])),
            "variants": {name: {"rounds": r, "median": float(np.median(r)), "min": min(r), "max": max(r), "mean_edges": edges[name]}
                         for name, r in rounds.items()},
-           "config": {"workload": f"batch of {args.batch} x N={args.n}, k={args.k}, noise {args.noise}, hidden={H}, 10 MP steps, L1, Adam",
+           "config": {"workload": f"batch of {args.batch} x N={'/'.join(str(n) for n in sorted(set(sizes)))}, k={args.k}, noise {args.noise}, hidden={H}, 10 MP steps, L1, Adam",
                       "recordings": args.sims, "frames": args.frames, "batches_per_epoch": len(ds) // args.batch,
                       "steps_per_window": args.steps, "rounds": args.rounds, "warmup_steps": args.warmup},
            "dtype": "f32", "data": "synthetic"}
