@@ -6,3 +6,4 @@ from .dataset import CoffeeDataset, CoffeeTestDataset, GraphData, GraphLoader, c
 from .graph import (GraphBoundedMultimaterial, GraphBoundedMultimaterialControl, compute_acceleration,  # noqa: F401
                     get_connectivity, get_edges_displacement, random_walk_noise)
 from .rollout import RolloutEngine, evaluate_rollout, get_position_from_prediction  # noqa: F401
+from .train import Trainer  # noqa: F401

@@ -88,4 +88,7 @@ struct gm_model {
 };
 int ensure_inference_images(const gm_model* m, hipStream_t s);   // model.hip; called by every inference entry point
 int weights_ready_on(const gm_model* m, hipStream_t s);          // model.hip; called by every entry point that reads the packed weights
+// model.hip; a kernel queued on s has rewritten m->raw (train_step.hip: Adam works on it): what a load does after its copy -- vec and
+// the training streams re-packed on s, the inference images stale, `ready` recorded
+int weights_changed_in_place(gm_model* m, hipStream_t s);
 

@@ -321,6 +321,14 @@ int ensure_inference_images(const gm_model* cm, hipStream_t s) {
     return rc;
 }
 
+int weights_changed_in_place(gm_model* m, hipStream_t s) {
+    std::lock_guard<std::mutex> guard(m->lazy_mu);
+    m->infer_stale = true;
+    int rc = pack_common(m, s);
+    if (rc == GM_OK) rc = mark_ready(m, s);
+    return rc;
+}
+
 int weights_ready_on(const gm_model* cm, hipStream_t s) {
     gm_model* m = const_cast<gm_model*>(cm);
     std::lock_guard<std::mutex> guard(m->lazy_mu);

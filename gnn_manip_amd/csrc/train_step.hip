@@ -1,0 +1,456 @@
+// The training step in the library: the L1 loss of examples/train_dyn.py:58-65 with its gradient, Adam on the model's own flat
+// weight buffer, and gm_train_step, which strings forward, loss, backward and update together on one stream without a host
+// synchronisation (host orchestration here; the model's kernels are train.hip's, reached through gm_epd_forward_train /
+// gm_epd_backward).  The arithmetic of the loss and of Adam is stated in include/gnn_manip_hip.h and restated in numpy by
+// tests/train_step_cases.py.
+#include <math.h>
+#include <vector>
+#include "common.h"
+#include "model.h"
+
+using namespace gm;
+
+namespace {
+
+constexpr int kLossThreads = 256;
+constexpr int kLossGridMax = 128;   // one partial per workgroup, summed by ONE workgroup; rows past 128 * 256 are a further pass of the grid
+
+// what the finish of a loss leaves on the device for the launches behind it
+struct LossState {
+    double loss;     // sum / count (NaN for count 0)
+    int64_t count;   // rows counted
+    float scale;     // (float)(1.0 / count): the magnitude of every gradient element
+    int skip;        // gm_train_step: the edge_index was flagged or the loss is not finite -- no update
+};
+static_assert(sizeof(LossState) == 24, "LossState layout");
+
+struct LossWs {
+    double* part_sum;     // [kLossGridMax]
+    int64_t* part_cnt;    // [kLossGridMax]
+    LossState* state;
+    size_t bytes;
+};
+LossWs carve_loss(void* ws) {
+    LossWs w;
+    Carver c(ws);
+    w.part_sum = c.take<double>(kLossGridMax);
+    w.part_cnt = c.take<int64_t>(kLossGridMax);
+    w.state = c.take<LossState>(1);
+    w.bytes = c.used();
+    return w;
+}
+unsigned loss_grid(int64_t rows) {
+    const int64_t g = cdiv(rows, kLossThreads);
+    return (unsigned)(g < 1 ? 1 : (g > kLossGridMax ? kLossGridMax : g));
+}
+
+__device__ inline bool row_counts(const float* nodes, int node_dim, int mask_col, int64_t r) {
+    return mask_col < 0 || nodes[(size_t)r * node_dim + mask_col] < 0.5f;
+}
+
+// The sum of 256 threads' values in a fixed tree; every thread calls it, thread 0 holds the result.
+template <typename T>
+__device__ inline T block_sum(T v, T* sh) {
+    sh[threadIdx.x] = v;
+    __syncthreads();
+    for (int w = kLossThreads / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
+        __syncthreads();
+    }
+    const T r = sh[0];
+    __syncthreads();
+    return r;
+}
+
+// Pass 1: a thread walks its rows (row, then column), adding the float32 values |pred - target| in float64; a workgroup's threads
+// are summed in a fixed tree.  One partial per workgroup: no atomics, the same order at every run.
+__global__ void __launch_bounds__(kLossThreads) l1_partials_kernel(const float* pred, const float* target, int64_t rows, int od,
+                                                                   const float* nodes, int node_dim, int mask_col, double* part_sum,
+                                                                   int64_t* part_cnt) {
+    __shared__ double sh_s[kLossThreads];
+    __shared__ int64_t sh_c[kLossThreads];
+    double s = 0.0;
+    int64_t cnt = 0;
+    for (int64_t r = (int64_t)blockIdx.x * kLossThreads + threadIdx.x; r < rows; r += (int64_t)gridDim.x * kLossThreads) {
+        if (!row_counts(nodes, node_dim, mask_col, r)) continue;
+        ++cnt;
+        for (int c = 0; c < od; ++c) {
+            const size_t i = (size_t)r * od + c;
+            s += (double)fabsf(pred[i] - target[i]);
+        }
+    }
+    s = block_sum(s, sh_s);
+    cnt = block_sum(cnt, sh_c);
+    if (threadIdx.x == 0) {
+        part_sum[blockIdx.x] = s;
+        part_cnt[blockIdx.x] = cnt;
+    }
+}
+
+// Pass 2, one workgroup: the partials in a fixed tree, then the loss, the count, the gradient's scale and the skip decision.
+// ha / hb (gm_train_step; else null): the two CSR headers of the forward's tape.
+__global__ void __launch_bounds__(kLossThreads) l1_finish_kernel(const double* part_sum, const int64_t* part_cnt, int n_part,
+                                                                 const CsrHeader* ha, const CsrHeader* hb, LossState* st, double* loss_out,
+                                                                 int64_t* rows_out) {
+    __shared__ double sh_s[kLossThreads];
+    __shared__ int64_t sh_c[kLossThreads];
+    double s = 0.0;
+    int64_t cnt = 0;
+    for (int i = threadIdx.x; i < n_part; i += kLossThreads) {
+        s += part_sum[i];
+        cnt += part_cnt[i];
+    }
+    s = block_sum(s, sh_s);
+    cnt = block_sum(cnt, sh_c);
+    if (threadIdx.x != 0) return;
+    const double loss = cnt > 0 ? s / (double)cnt : (double)__builtin_nanf("");
+    const bool flagged = ha && hb && ((ha->error_flags | hb->error_flags) & ERRF_BAD_EDGE_INDEX);
+    st->loss = loss;
+    st->count = cnt;
+    st->scale = cnt > 0 ? (float)(1.0 / (double)cnt) : 0.f;
+    st->skip = (flagged || !isfinite(loss)) ? 1 : 0;
+    if (loss_out) *loss_out = loss;
+    if (rows_out) *rows_out = cnt;
+}
+
+// Pass 3: d loss / d pred.  sign(0) = 0; a row that does not count gets 0.
+__global__ void __launch_bounds__(kLossThreads) l1_grad_kernel(const float* pred, const float* target, int64_t rows, int od,
+                                                               const float* nodes, int node_dim, int mask_col, const LossState* st,
+                                                               float* grad) {
+    const float scale = st->scale;
+    for (int64_t r = (int64_t)blockIdx.x * kLossThreads + threadIdx.x; r < rows; r += (int64_t)gridDim.x * kLossThreads) {
+        const bool counts = row_counts(nodes, node_dim, mask_col, r);
+        for (int c = 0; c < od; ++c) {
+            const size_t i = (size_t)r * od + c;
+            const float d = pred[i] - target[i];
+            grad[i] = !counts ? 0.f : (d > 0.f ? scale : (d < 0.f ? -scale : 0.f));
+        }
+    }
+}
+
+int check_loss_args(const float* pred, const float* target, int64_t rows, int od, const float* nodes, int node_dim, int mask_col,
+                    const char* who) {
+    GM_REQUIRE(pred && target, GM_ERR_INVALID_ARGUMENT, "%s: null pointer", who);
+    GM_REQUIRE(rows >= 1 && od >= 1 && rows < ((int64_t)1 << 40), GM_ERR_INVALID_ARGUMENT, "%s: sizes out of range (n_rows=%lld, out_dim=%d)", who,
+               (long long)rows, od);
+    GM_REQUIRE(mask_col < 0 || mask_col < node_dim, GM_ERR_INVALID_ARGUMENT, "%s: mask_col=%d outside the %d node columns", who, mask_col,
+               node_dim);
+    GM_REQUIRE(mask_col < 0 || nodes, GM_ERR_INVALID_ARGUMENT, "%s: null nodes with mask_col=%d", who, mask_col);
+    return GM_OK;
+}
+
+// the three launches of a loss; the arguments are checked
+int run_loss(const float* pred, const float* target, int64_t rows, int od, const float* nodes, int node_dim, int mask_col,
+             const CsrHeader* ha, const CsrHeader* hb, const LossWs& w, double* loss_out, int64_t* rows_out, float* grad, hipStream_t s) {
+    const unsigned g = loss_grid(rows);
+    hipLaunchKernelGGL(l1_partials_kernel, dim3(g), dim3(kLossThreads), 0, s, pred, target, rows, od, nodes, node_dim, mask_col, w.part_sum,
+                       w.part_cnt);
+    GM_LAUNCH_CHECK();
+    hipLaunchKernelGGL(l1_finish_kernel, dim3(1), dim3(kLossThreads), 0, s, w.part_sum, w.part_cnt, (int)g, ha, hb, w.state, loss_out, rows_out);
+    GM_LAUNCH_CHECK();
+    if (grad) {
+        hipLaunchKernelGGL(l1_grad_kernel, dim3(g), dim3(kLossThreads), 0, s, pred, target, rows, od, nodes, node_dim, mask_col, w.state, grad);
+        GM_LAUNCH_CHECK();
+    }
+    return GM_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- Adam
+struct TrainerRecord {   // the 32-byte device record gm_trainer_record copies out
+    int64_t steps_applied, steps_skipped;
+    double beta1_pow, beta2_pow;
+};
+static_assert(sizeof(TrainerRecord) == 32, "TrainerRecord layout");
+struct AdamScalars {     // what the prepare launch leaves for the flat launch
+    float step, s2;
+    int skip, pad;
+};
+
+__global__ void trainer_record_set_kernel(TrainerRecord* rec, int64_t applied, int64_t skipped, int keep_skipped, double b1p, double b2p) {
+    rec->steps_applied = applied;
+    if (!keep_skipped) rec->steps_skipped = skipped;
+    rec->beta1_pow = b1p;
+    rec->beta2_pow = b2p;
+}
+
+// One thread: the step's float64 scalars.  The powers are RUNNING PRODUCTS, so that a host loop reproduces them exactly.
+__global__ void adam_prepare_kernel(const LossState* st, TrainerRecord* rec, AdamScalars* sc, double beta1, double beta2, double lr,
+                                    double* loss_out) {
+    if (loss_out) *loss_out = st->loss;
+    sc->skip = st->skip;
+    if (st->skip) {
+        rec->steps_skipped += 1;
+        return;
+    }
+    const double b1p = rec->beta1_pow * beta1, b2p = rec->beta2_pow * beta2;
+    rec->beta1_pow = b1p;
+    rec->beta2_pow = b2p;
+    rec->steps_applied += 1;
+    sc->step = (float)(lr / (1.0 - b1p));
+    sc->s2 = (float)sqrt(1.0 - b2p);
+}
+
+struct AdamConsts { float b1, o1, b2, o2, eps; };
+
+// One element, every float32 operation rounded on its own: no contraction into fused multiply-adds in this function.
+__device__ inline void adam_element(float& p, float& m, float& v, float g, const AdamConsts& k, float step, float s2) {
+#pragma clang fp contract(off)
+    const float m1 = k.b1 * m;
+    const float m2 = k.o1 * g;
+    m = m1 + m2;
+    const float v1 = k.b2 * v;
+    const float v2 = k.o2 * g;
+    const float v3 = v2 * g;
+    v = v1 + v3;
+    const float den = sqrtf(v) / s2;
+    const float den2 = den + k.eps;
+    const float q = m / den2;
+    const float u = step * q;
+    p = p - u;
+}
+
+// The flat launch over the model's weight buffer: 16-byte accesses, a scalar tail for a count that is no multiple of 4.  A skipped
+// step returns before it touches anything.
+__global__ void __launch_bounds__(256) adam_flat_kernel(float* p, float* m, float* v, const float* g, size_t count, AdamConsts k,
+                                                         const AdamScalars* sc) {
+    if (sc->skip) return;
+    const float step = sc->step, s2 = sc->s2;
+    const size_t n4 = count >> 2, t = (size_t)blockIdx.x * blockDim.x + threadIdx.x, nt = (size_t)gridDim.x * blockDim.x;
+    float4* p4 = reinterpret_cast<float4*>(p);
+    float4* m4 = reinterpret_cast<float4*>(m);
+    float4* v4 = reinterpret_cast<float4*>(v);
+    const float4* g4 = reinterpret_cast<const float4*>(g);
+    for (size_t i = t; i < n4; i += nt) {
+        float4 pp = p4[i], mm = m4[i], vv = v4[i];
+        const float4 gg = g4[i];
+        adam_element(pp.x, mm.x, vv.x, gg.x, k, step, s2);
+        adam_element(pp.y, mm.y, vv.y, gg.y, k, step, s2);
+        adam_element(pp.z, mm.z, vv.z, gg.z, k, step, s2);
+        adam_element(pp.w, mm.w, vv.w, gg.w, k, step, s2);
+        p4[i] = pp; m4[i] = mm; v4[i] = vv;
+    }
+    for (size_t i = (n4 << 2) + t; i < count; i += nt) adam_element(p[i], m[i], v[i], g[i], k, step, s2);
+}
+
+}  // namespace
+
+struct gm_trainer {
+    gm_model* m = nullptr;   // not owned: the caller destroys the trainer first
+    double beta1 = 0.9, beta2 = 0.999, eps = 1e-8;
+    size_t count = 0;        // floats from the start of m->raw to the end of its last tensor: what Adam walks
+    size_t alloc = 0;        // floats of m->raw (each tensor starts on 16 bytes), and of each buffer below
+    float *exp_avg = nullptr, *exp_avg_sq = nullptr, *grad = nullptr;   // laid out like m->raw; the gaps stay zero
+    TrainerRecord* rec = nullptr;
+    AdamScalars* sc = nullptr;
+    void* loss_ws = nullptr;   // gm_l1_loss's workspace of gm_train_step
+    std::vector<const float*> T;   // tensor t of m->raw
+    std::vector<float*> G;         // its gradient: what gm_epd_backward takes as grads[t]
+};
+
+namespace {
+
+struct StepWs {
+    char* tape;   // first: the tape's CSR header is the workspace's first 16 bytes (the edge_index verdict)
+    char* bwd;
+    float *out, *go;
+    size_t tape_bytes, bwd_bytes, bytes;
+};
+StepWs carve_step(void* ws, const gm_model_desc* d, int64_t n, int64_t e) {
+    StepWs w;
+    w.tape_bytes = gm_train_tape_bytes(d, n, e);
+    w.bwd_bytes = gm_train_backward_workspace_bytes(d, n, e);
+    Carver c(ws);
+    w.tape = c.take<char>(w.tape_bytes);
+    w.bwd = c.take<char>(w.bwd_bytes);
+    const size_t od = (size_t)n * (d->out_dim > 0 ? d->out_dim : 1);
+    w.out = c.take<float>(od);
+    w.go = c.take<float>(od);
+    w.bytes = c.used();
+    return w;
+}
+
+float* flat_of(const gm_trainer* t, int what) {
+    switch (what) {
+        case GM_TRAINER_PARAMS: return t->m->raw;
+        case GM_TRAINER_EXP_AVG: return t->exp_avg;
+        case GM_TRAINER_EXP_AVG_SQ: return t->exp_avg_sq;
+        case GM_TRAINER_GRADS: return t->grad;
+        default: return nullptr;
+    }
+}
+int check_tensor_list(const gm_trainer* t, const void* const* tensors, int n_tensors, const char* who) {
+    const int nt = (int)t->m->raw_jobs.size();
+    GM_REQUIRE(n_tensors == nt, GM_ERR_INVALID_ARGUMENT, "%s: expected %d tensors, got %d", who, nt, n_tensors);
+    for (int i = 0; i < nt; ++i) GM_REQUIRE(tensors[i], GM_ERR_INVALID_ARGUMENT, "%s: tensor %d is null", who, i);
+    return GM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t gm_l1_loss_workspace_bytes(int64_t n_rows, int out_dim) {
+    if (n_rows < 1 || out_dim < 1) return 0;
+    return carve_loss(nullptr).bytes;
+}
+
+int gm_l1_loss(const float* pred, const float* target, int64_t n_rows, int out_dim, const float* nodes, int node_dim, int mask_col,
+               double* loss_out, int64_t* rows_counted_out, float* grad_out, void* ws, size_t ws_bytes, void* stream) {
+    int rc = check_loss_args(pred, target, n_rows, out_dim, nodes, node_dim, mask_col, __func__);
+    if (rc != GM_OK) return rc;
+    GM_REQUIRE(loss_out && ws, GM_ERR_INVALID_ARGUMENT, "%s: null pointer", __func__);
+    const LossWs w = carve_loss(ws);
+    GM_REQUIRE(ws_bytes >= w.bytes, GM_ERR_WORKSPACE, "%s: workspace %zu < %zu", __func__, ws_bytes, w.bytes);
+    gm::DevGuard dev_guard(pred);
+    return run_loss(pred, target, n_rows, out_dim, nodes, node_dim, mask_col, nullptr, nullptr, w, loss_out, rows_counted_out, grad_out,
+                    (hipStream_t)stream);
+}
+
+int gm_trainer_create(gm_model* m, double beta1, double beta2, double eps, void* stream, gm_trainer** out) {
+    GM_REQUIRE(!m || m->packed_t3, GM_ERR_UNSUPPORTED, "%s: the training kernels are instantiated for hidden_size 64 / 128 / 256", __func__);
+    GM_REQUIRE(m, GM_ERR_INVALID_ARGUMENT, "%s: null model", __func__);
+    GM_REQUIRE(out, GM_ERR_INVALID_ARGUMENT, "%s: null pointer", __func__);
+    GM_REQUIRE(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0, GM_ERR_INVALID_ARGUMENT,
+               "%s: betas (%g, %g) outside [0, 1) or eps %g negative", __func__, beta1, beta2, eps);
+    gm::DevGuard dev_guard(m->raw);
+    hipStream_t s = (hipStream_t)stream;
+    gm_trainer* t = new gm_trainer();
+    t->m = m;
+    t->beta1 = beta1; t->beta2 = beta2; t->eps = eps;
+    for (const VecJob& j : m->raw_jobs) {
+        t->T.push_back(m->raw + j.dst_off);
+        t->count = j.dst_off + (size_t)j.count;
+        t->alloc = j.dst_off + (((size_t)j.count + 3) & ~(size_t)3);
+    }
+    const size_t loss_bytes = carve_loss(nullptr).bytes;
+    const size_t fb = t->alloc * sizeof(float);
+    if (hipMalloc(&t->exp_avg, fb) != hipSuccess || hipMalloc(&t->exp_avg_sq, fb) != hipSuccess || hipMalloc(&t->grad, fb) != hipSuccess ||
+        hipMalloc(&t->rec, sizeof(TrainerRecord)) != hipSuccess || hipMalloc(&t->sc, sizeof(AdamScalars)) != hipSuccess ||
+        hipMalloc(&t->loss_ws, loss_bytes) != hipSuccess) {
+        gm::set_error("%s: hipMalloc failed", __func__);
+        gm_trainer_destroy(t);
+        return GM_ERR_HIP;
+    }
+    for (const VecJob& j : m->raw_jobs) t->G.push_back(t->grad + j.dst_off);
+    int rc = [&]() -> int {
+        GM_HIP_CHECK(hipMemsetAsync(t->exp_avg, 0, fb, s));
+        GM_HIP_CHECK(hipMemsetAsync(t->exp_avg_sq, 0, fb, s));
+        GM_HIP_CHECK(hipMemsetAsync(t->grad, 0, fb, s));
+        GM_HIP_CHECK(hipMemsetAsync(t->sc, 0, sizeof(AdamScalars), s));
+        hipLaunchKernelGGL(trainer_record_set_kernel, dim3(1), dim3(1), 0, s, t->rec, (int64_t)0, (int64_t)0, 0, 1.0, 1.0);
+        GM_LAUNCH_CHECK();
+        return GM_OK;
+    }();
+    if (rc != GM_OK) {
+        gm_trainer_destroy(t);
+        return rc;
+    }
+    *out = t;
+    return GM_OK;
+}
+
+void gm_trainer_destroy(gm_trainer* t) {
+    if (!t) return;
+    for (void* p : std::initializer_list<void*>{t->exp_avg, t->exp_avg_sq, t->grad, t->rec, t->sc, t->loss_ws}) (void)hipFree(p);
+    delete t;
+}
+
+size_t gm_train_step_workspace_bytes(const gm_model_desc* desc, int64_t n, int64_t e) {
+    if (!desc || n < 1 || e < 0) return 0;
+    return carve_step(nullptr, desc, n, e).bytes;
+}
+
+int gm_train_step(gm_trainer* t, const float* nodes, int64_t n, const float* edge_attr, const int64_t* edge_index, int64_t e,
+                  const float* target, int mask_col, double lr, double* loss_out, void* ws, size_t ws_bytes, void* stream) {
+    GM_REQUIRE(t, GM_ERR_INVALID_ARGUMENT, "%s: null trainer", __func__);
+    gm_model* m = t->m;
+    GM_REQUIRE(n >= 1 && e >= 0 && n < ((int64_t)1 << 31) && e < ((int64_t)1 << 31) / m->H, GM_ERR_INVALID_ARGUMENT,
+               "%s: sizes out of range (n=%lld, e=%lld)", __func__, (long long)n, (long long)e);
+    GM_REQUIRE(nodes && target && ws && (e == 0 || (edge_attr && edge_index)), GM_ERR_INVALID_ARGUMENT, "%s: null pointer", __func__);
+    GM_REQUIRE(mask_col < 0 || mask_col < m->d.node_dim, GM_ERR_INVALID_ARGUMENT, "%s: mask_col=%d outside the %d node columns", __func__,
+               mask_col, m->d.node_dim);
+    GM_REQUIRE(lr == lr, GM_ERR_INVALID_ARGUMENT, "%s: lr is NaN", __func__);
+    const StepWs w = carve_step(ws, &m->d, n, e);
+    GM_REQUIRE(ws_bytes >= w.bytes, GM_ERR_WORKSPACE, "%s: workspace %zu < %zu", __func__, ws_bytes, w.bytes);
+    gm::DevGuard dev_guard(nodes);
+    hipStream_t s = (hipStream_t)stream;
+    const int nt = (int)t->T.size(), od = m->d.out_dim;
+    const LossWs lw = carve_loss(t->loss_ws);
+
+    GM_HIP_CHECK(hipMemsetAsync(t->grad, 0, t->alloc * sizeof(float), s));
+    int rc = gm_epd_forward_train(m, nodes, n, edge_attr, edge_index, e, w.out, w.tape, w.tape_bytes, s);
+    if (rc != GM_OK) return rc;
+    // the tape begins with the destination sort's workspace, the source sort's follows it (train_model.hip: take_csr): the two
+    // headers that carry the edge_index verdict
+    const CsrHeader* ha = reinterpret_cast<const CsrHeader*>(w.tape);
+    const CsrHeader* hb = reinterpret_cast<const CsrHeader*>(w.tape + align_up(gm_csr_workspace_bytes(n, e), 256));
+    rc = run_loss(w.out, target, n, od, nodes, m->d.node_dim, mask_col, ha, hb, lw, nullptr, nullptr, w.go, s);
+    if (rc != GM_OK) return rc;
+    rc = gm_epd_backward(m, t->T.data(), nt, nodes, edge_attr, n, e, w.go, t->G.data(), w.tape, w.tape_bytes, w.bwd, w.bwd_bytes, s);
+    if (rc != GM_OK) return rc;
+    hipLaunchKernelGGL(adam_prepare_kernel, dim3(1), dim3(1), 0, s, lw.state, t->rec, t->sc, t->beta1, t->beta2, lr, loss_out);
+    GM_LAUNCH_CHECK();
+    const AdamConsts k{(float)t->beta1, (float)(1.0 - t->beta1), (float)t->beta2, (float)(1.0 - t->beta2), (float)t->eps};
+    const size_t g = cdiv((int64_t)(t->count / 4 + 1), 256);
+    hipLaunchKernelGGL(adam_flat_kernel, dim3((unsigned)(g > 2048 ? 2048 : g)), dim3(256), 0, s, m->raw, t->exp_avg, t->exp_avg_sq, t->grad,
+                       t->count, k, t->sc);
+    GM_LAUNCH_CHECK();
+    return weights_changed_in_place(m, s);
+}
+
+int gm_trainer_record(const gm_trainer* t, void* record_host, void* stream) {
+    GM_REQUIRE(t, GM_ERR_INVALID_ARGUMENT, "%s: null trainer", __func__);
+    GM_REQUIRE(record_host, GM_ERR_INVALID_ARGUMENT, "%s: null pointer", __func__);
+    gm::DevGuard dev_guard(t->rec);
+    GM_HIP_CHECK(hipMemcpyAsync(record_host, t->rec, sizeof(TrainerRecord), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    return GM_OK;
+}
+
+int gm_trainer_export(const gm_trainer* t, int what, float* const* tensors_out, int n_tensors, void* stream) {
+    GM_REQUIRE(t, GM_ERR_INVALID_ARGUMENT, "%s: null trainer", __func__);
+    GM_REQUIRE(tensors_out, GM_ERR_INVALID_ARGUMENT, "%s: null pointer", __func__);
+    const float* flat = flat_of(t, what);
+    GM_REQUIRE(flat, GM_ERR_INVALID_ARGUMENT, "%s: unknown what=%d", __func__, what);
+    int rc = check_tensor_list(t, reinterpret_cast<const void* const*>(tensors_out), n_tensors, __func__);
+    if (rc != GM_OK) return rc;
+    gm::DevGuard dev_guard(flat);
+    hipStream_t s = (hipStream_t)stream;
+    if (what == GM_TRAINER_PARAMS) {   // the weights may have been loaded on another stream
+        rc = weights_ready_on(t->m, s);
+        if (rc != GM_OK) return rc;
+    }
+    for (int i = 0; i < n_tensors; ++i) {
+        const VecJob& j = t->m->raw_jobs[(size_t)i];
+        GM_HIP_CHECK(hipMemcpyAsync(tensors_out[i], flat + j.dst_off, (size_t)j.count * sizeof(float), hipMemcpyDeviceToDevice, s));
+    }
+    return GM_OK;
+}
+
+int gm_trainer_import(gm_trainer* t, int what, const float* const* tensors_in, int n_tensors, int64_t step_count, void* stream) {
+    GM_REQUIRE(t, GM_ERR_INVALID_ARGUMENT, "%s: null trainer", __func__);
+    GM_REQUIRE(tensors_in, GM_ERR_INVALID_ARGUMENT, "%s: null pointer", __func__);
+    float* flat = flat_of(t, what);
+    GM_REQUIRE(flat && what != GM_TRAINER_GRADS, GM_ERR_INVALID_ARGUMENT, "%s: %s what=%d", __func__,
+               flat ? "the gradients are an output," : "unknown", what);
+    int rc = check_tensor_list(t, reinterpret_cast<const void* const*>(tensors_in), n_tensors, __func__);
+    if (rc != GM_OK) return rc;
+    GM_REQUIRE(what != GM_TRAINER_EXP_AVG || (step_count >= 0 && step_count < ((int64_t)1 << 40)), GM_ERR_INVALID_ARGUMENT,
+               "%s: step_count=%lld out of range", __func__, (long long)step_count);
+    if (what == GM_TRAINER_PARAMS) return gm_model_update(t->m, tensors_in, n_tensors, 1, stream);   // copies, then re-packs the images
+    gm::DevGuard dev_guard(flat);
+    hipStream_t s = (hipStream_t)stream;
+    for (int i = 0; i < n_tensors; ++i) {
+        const VecJob& j = t->m->raw_jobs[(size_t)i];
+        GM_HIP_CHECK(hipMemcpyAsync(flat + j.dst_off, tensors_in[i], (size_t)j.count * sizeof(float), hipMemcpyDeviceToDevice, s));
+    }
+    if (what == GM_TRAINER_EXP_AVG) {
+        // the powers as the steps themselves would have left them: running products (which end at zero and stay there)
+        double b1p = 1.0, b2p = 1.0;
+        for (int64_t i = 0; i < step_count && (b1p != 0.0 || b2p != 0.0); ++i) { b1p *= t->beta1; b2p *= t->beta2; }
+        hipLaunchKernelGGL(trainer_record_set_kernel, dim3(1), dim3(1), 0, s, t->rec, step_count, (int64_t)0, 1, b1p, b2p);
+        GM_LAUNCH_CHECK();
+    }
+    return GM_OK;
+}
+
+}  // extern "C"

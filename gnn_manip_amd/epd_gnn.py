@@ -762,6 +762,7 @@ class EncProcDecGNN(nn.Module):
             # as the reference's raise at the forward for every optimiser: plain SGD leaves the weights alone on a zero gradient,
             # but Adam (train_dyn.py:58) still advances its step count, decays its moment estimates and moves the weights along its
             # first-moment history, and weight decay applies as always -- for the one to eight steps until the error is raised.
+            # (The library trainer, gnn_manip_amd.train.Trainer, reads the flag on the device and skips a flagged step altogether.)
             _check_edge_index(edge_index, n, e, ranges=False)
             if self.auto_status:
                 self._reap_watched(block=False)

@@ -1,0 +1,258 @@
+"""The training step of examples/train_dyn.py:49-72 in the library: ``Trainer`` owns a gm_model built from a module's parameters
+and a gm_trainer (Adam's moments, the gradients, a device record) and runs forward, L1 loss, backward and Adam as ONE library call
+per batch (gm_train_step) -- no autograd graph, no optimiser object, no host synchronisation.  The arithmetic of the loss and of
+Adam is the contract stated in include/gnn_manip_hip.h.
+
+The two learning-rate schedules of train_dyn.py:100-107,143-144 are one-line host formulas on ``trainer.lr``."""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from ._lib import ModelDesc, check, current_stream, lib, ptr
+from .dataset import GraphData
+from .epd_gnn import TRAIN_WIDTHS, DstCsr, _check_edge_index, _device_arrays, _Model, _pointers
+from .graph import _need_cuda, _ws
+
+PARAMS, EXP_AVG, EXP_AVG_SQ, GRADS = 1, 2, 3, 4   # GM_TRAINER_* of include/gnn_manip_hip.h
+
+
+def normalise_material_col(material_col, node_dim):
+    """The column of the node features that holds the material flag, as the library takes it: the reference indexes it from the
+    end (train_dyn.py:60: ``-1 - len(control_idx)``, or ``-1`` without control columns)."""
+    col = int(material_col)
+    if col < 0:
+        col += int(node_dim)
+    if not 0 <= col < int(node_dim):
+        raise ValueError(f"material_col={material_col} is outside the {node_dim} node feature columns")
+    return col
+
+
+def adam_state_dict(exp_avg, exp_avg_sq, step, lr, betas, eps):
+    """``torch.optim.Adam.state_dict()``'s layout for one parameter group over ``len(exp_avg)`` parameters: what
+    train_dyn.py:33-43 stores in a checkpoint, so that a run resumes in either direction."""
+    ref = torch.optim.Adam([torch.zeros(1)], lr=float(lr), betas=tuple(float(b) for b in betas), eps=float(eps))
+    group = dict(ref.state_dict()["param_groups"][0])     # every hyper-parameter key this torch's Adam expects, at its default
+    group["params"] = list(range(len(exp_avg)))
+    state = {i: {"step": torch.tensor(float(step)), "exp_avg": m, "exp_avg_sq": v} for i, (m, v) in enumerate(zip(exp_avg, exp_avg_sq))}
+    return {"state": state, "param_groups": [group]}
+
+
+def parse_adam_state_dict(sd, shapes):
+    """The other direction: (exp_avg list or None, exp_avg_sq list or None, step, param group) of an Adam state_dict over parameters
+    of `shapes`.  An optimiser that has not stepped has an empty state: the moments are then None (zeros) and step is 0."""
+    groups = sd["param_groups"]
+    if len(groups) != 1 or len(groups[0]["params"]) != len(shapes):
+        raise ValueError(f"Trainer.load_state_dict: expected one parameter group of {len(shapes)} parameters")
+    g = groups[0]
+    if g.get("weight_decay", 0) or g.get("amsgrad", False) or g.get("maximize", False):
+        raise ValueError("Trainer.load_state_dict: weight decay, AMSGrad and maximize are not part of the library's Adam")
+    state = sd["state"]
+    if len(state) == 0:
+        return None, None, 0, g
+    if sorted(state) != list(range(len(shapes))):
+        raise ValueError("Trainer.load_state_dict: the state does not cover every parameter")
+    steps = {int(float(state[i]["step"])) for i in range(len(shapes))}
+    if len(steps) != 1:
+        raise ValueError(f"Trainer.load_state_dict: the parameters disagree on the step count: {sorted(steps)}")
+    for i, shape in enumerate(shapes):
+        for key in ("exp_avg", "exp_avg_sq"):
+            if tuple(state[i][key].shape) != tuple(shape):
+                raise ValueError(f"Trainer.load_state_dict: {key} of parameter {i} has shape {tuple(state[i][key].shape)}, not {tuple(shape)}")
+    return [state[i]["exp_avg"] for i in range(len(shapes))], [state[i]["exp_avg_sq"] for i in range(len(shapes))], steps.pop(), g
+
+
+class _TrainerHandle:
+    """A gm_trainer* and the gm_model it updates: the trainer is destroyed first."""
+
+    def __init__(self, pointer, model):
+        self._as_parameter_, self.model = pointer, model
+
+    def __del__(self):
+        try:
+            lib().gm_trainer_destroy(self._as_parameter_)
+        except Exception:
+            pass
+        self.model = None
+
+
+class Trainer:
+    """``Trainer(model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, sand_only=False, material_col=None)``: Adam on an ``EncProcDecGNN``
+    with the L1 loss of train_dyn.py:58-65 -- ``sand_only`` is ``--use_updated_loss`` (the loss over the rows whose node feature
+    ``material_col`` is below 0.5, divided by their count; ``material_col`` may be the reference's negative index).
+
+    The trainer builds its OWN library model from the module's parameters, on the module's device, and trains that: the module's
+    ``nn.Parameter`` s do not move until ``sync_module()`` copies the weights back.  ``step`` returns nothing and synchronises
+    nothing: the loss goes into a slot on the device (``last_loss``, or the ``loss_out`` the caller passes); ``fit_epoch`` /
+    ``eval_epoch`` return an epoch's losses after one synchronisation at its end.  ``lr`` is a plain attribute: set it between steps.
+
+    A step whose edge_index holds an entry outside [0, N), or whose loss is not finite, is SKIPPED on the device: weights, moments
+    and step count stay as they were, ``record()`` counts it, its loss slot holds NaN.  The edge_index error itself surfaces as
+    ``GMError`` at a later step or at ``status()``, like a training forward's.
+
+    Hidden sizes 64 / 128 / 256 only.  A module of another hidden size trains zero-padded through ``model.forward`` under autograd
+    with a torch optimiser (``EncProcDecGNN._padded_training``): that path stays with autograd."""
+
+    def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, sand_only=False, material_col=None):
+        if model.dims[3] not in TRAIN_WIDTHS:
+            raise ValueError(f"Trainer: hidden_size={model.dims[3]}; the library step runs at hidden sizes 64, 128 and 256 "
+                             "(other sizes train through model.forward under autograd)")
+        self.model, self.lr = model, float(lr)
+        self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
+        self.sand_only = bool(sand_only)
+        if self.sand_only and material_col is None:
+            raise ValueError("Trainer: sand_only needs material_col, the node feature column of the material flag")
+        self.mask_col = normalise_material_col(material_col, model.dims[0]) if self.sand_only else -1
+        params = list(model.parameters())
+        self.device = params[0].device
+        _need_cuda(params[0], "the model's parameters")
+        self._shapes = [tuple(p.shape) for p in params]
+        self.desc = ModelDesc(*model.model_desc())
+        L = lib()
+        tensors, arr = _device_arrays(params, self.device)
+        with torch.cuda.device(self.device):
+            stream = current_stream(self.device)
+            out = C.c_void_p()
+            check(L.gm_model_create(C.byref(self.desc), arr, len(tensors), 1, stream, C.byref(out)))
+            gm_model = _Model(out)
+            out = C.c_void_p()
+            check(L.gm_trainer_create(gm_model, self.betas[0], self.betas[1], self.eps, stream, C.byref(out)))
+        self._h = _TrainerHandle(out, gm_model)
+        self._ws = None
+        self._loss = torch.full((1,), float("nan"), dtype=torch.float64, device=self.device)
+        self._loss_ws = _ws(L.gm_l1_loss_workspace_bytes(1, 1), self.device)
+        self._pin_record = torch.zeros(4, dtype=torch.int64).pin_memory()
+        self._pin_losses = None
+
+    # ------------------------------------------------------------------------------------------ one batch
+    @property
+    def last_loss(self):
+        """The loss of the last ``step`` / ``evaluate`` that was given no ``loss_out``: a float64 device tensor of one element."""
+        return self._loss
+
+    def _batch(self, x, edge_attr, edge_index, y):
+        if isinstance(x, GraphData):
+            x, edge_attr, edge_index, y = x.x, x.edge_attr, x.edge_index, x.y
+        _need_cuda(x, "x")
+        x, edge_attr, y = x.contiguous().float(), edge_attr.contiguous().float(), y.contiguous().float()
+        n, e = int(x.shape[0]), int(edge_attr.shape[0])
+        if x.shape[1] != self.model.dims[0] or edge_attr.shape[1] != self.model.dims[1]:
+            raise ValueError("x / edge_attr feature widths do not match the model")
+        if tuple(y.shape) != (n, self.model.dims[2]):
+            raise ValueError(f"y must be [{n}, {self.model.dims[2]}]")
+        _check_edge_index(edge_index, n, e, ranges=False)
+        return x, edge_attr, edge_index.contiguous(), y, n, e
+
+    def _slot(self, loss_out):
+        if loss_out is None:
+            return self._loss
+        if loss_out.dtype != torch.float64 or loss_out.numel() != 1 or loss_out.device != self.device:
+            raise ValueError("loss_out must be one float64 element on the trainer's device")
+        return loss_out
+
+    def step(self, x, edge_attr=None, edge_index=None, y=None, loss_out=None):
+        """One training step on a batch (four tensors, or a ``GraphData``): gm_train_step.  Nothing is returned and nothing waits."""
+        x, edge_attr, edge_index, y, n, e = self._batch(x, edge_attr, edge_index, y)
+        slot = self._slot(loss_out)
+        L = lib()
+        if self.model.auto_status:
+            self.model._reap_watched(block=False)
+        need = L.gm_train_step_workspace_bytes(C.byref(self.desc), n, e)
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = _ws(need, self.device)
+        check(L.gm_train_step(self._h, ptr(x), n, ptr(edge_attr), ptr(edge_index), e, ptr(y), self.mask_col, self.lr, ptr(slot),
+                              ptr(self._ws), self._ws.numel(), current_stream(x)))
+        self.model._watch(self._ws)   # the workspace begins with the tape's CSR header: the edge_index verdict
+
+    def evaluate(self, x, edge_attr=None, edge_index=None, y=None, loss_out=None):
+        """train_dyn.py's ``test_epoch`` on one batch: the inference forward of the trainer's weights and the same loss, no update."""
+        x, edge_attr, edge_index, y, n, e = self._batch(x, edge_attr, edge_index, y)
+        slot = self._slot(loss_out)
+        L = lib()
+        if self.model.auto_status:
+            self.model._reap_watched(block=False)
+        csr = DstCsr(edge_index, n, flow=self.model.convention[0])
+        fwd = _ws(L.gm_forward_workspace_bytes(C.byref(self.desc), n, e), self.device)
+        out = torch.empty((n, self.model.dims[2]), dtype=torch.float32, device=self.device)
+        check(L.gm_epd_forward(self._h.model, ptr(x), n, ptr(edge_attr), 0, ptr(csr.ws), e, ptr(out), ptr(fwd), fwd.numel(), current_stream(x)))
+        check(L.gm_l1_loss(ptr(out), ptr(y), n, self.model.dims[2], ptr(x), self.model.dims[0], self.mask_col, ptr(slot), None, None,
+                           ptr(self._loss_ws), self._loss_ws.numel(), current_stream(x)))
+        self.model._last_csr = csr
+        if self.model.auto_status:
+            self.model._watch(csr)
+
+    # ------------------------------------------------------------------------------------------ an epoch
+    def _epoch(self, loader, one):
+        losses = torch.full((max(len(loader), 1),), float("nan"), dtype=torch.float64, device=self.device)
+        count = 0
+        for batch in loader:
+            if count == losses.numel():
+                losses = torch.cat((losses, torch.full_like(losses, float("nan"))))
+            one(batch, loss_out=losses[count:count + 1])
+            count += 1
+        if self._pin_losses is None or self._pin_losses.numel() < losses.numel():
+            self._pin_losses = torch.empty(losses.numel(), dtype=torch.float64).pin_memory()
+        host = self._pin_losses[:losses.numel()]
+        host.copy_(losses, non_blocking=True)
+        torch.cuda.current_stream(self.device).synchronize()   # the epoch's one synchronisation
+        return host[:count].numpy().copy()
+
+    def fit_epoch(self, loader):
+        """``step`` over every batch of `loader` (a ``GraphLoader``, fused and prefetching or not): the per-batch losses as a
+        float64 numpy array, after a single synchronisation at the end.  A skipped batch's loss is NaN."""
+        return self._epoch(loader, self.step)
+
+    def eval_epoch(self, loader):
+        """``evaluate`` over every batch of `loader`, as ``fit_epoch``."""
+        return self._epoch(loader, self.evaluate)
+
+    # ------------------------------------------------------------------------------------------ state
+    def record(self):
+        """{'steps_applied', 'steps_skipped', 'beta1_pow', 'beta2_pow'} of the device record (synchronises)."""
+        check(lib().gm_trainer_record(self._h, C.c_void_p(self._pin_record.data_ptr()), current_stream(self.device)))
+        torch.cuda.current_stream(self.device).synchronize()
+        powers = self._pin_record[2:].view(torch.float64)
+        return {"steps_applied": int(self._pin_record[0]), "steps_skipped": int(self._pin_record[1]),
+                "beta1_pow": float(powers[0]), "beta2_pow": float(powers[1])}
+
+    def status(self):
+        """Raises ``GMError`` if a step or evaluation so far had an edge_index entry outside [0, N) (synchronises)."""
+        return self.model.status()
+
+    def export(self, what=PARAMS):
+        """Copies of one of the trainer's buffers (PARAMS, EXP_AVG, EXP_AVG_SQ, GRADS), shaped like the module's parameters."""
+        tensors = [torch.empty(s, dtype=torch.float32, device=self.device) for s in self._shapes]
+        check(lib().gm_trainer_export(self._h, int(what), _pointers(tensors), len(tensors), current_stream(self.device)))
+        return tensors
+
+    def _import(self, what, tensors, step_count=0):
+        tensors, arr = _device_arrays(tensors, self.device)
+        check(lib().gm_trainer_import(self._h, int(what), arr, len(tensors), int(step_count), current_stream(self.device)))
+
+    def sync_module(self):
+        """Copies the trained weights into the module's ``nn.Parameter`` s and has the module re-pack its own images."""
+        with torch.no_grad():
+            for p, w in zip(self.model.parameters(), self.export(PARAMS)):
+                p.data.copy_(w)
+        self.model.invalidate_packed_weights()
+
+    def load_module(self):
+        """The other direction: the module's current parameters become the trainer's weights (moments and step count stay)."""
+        self._import(PARAMS, list(self.model.parameters()))
+
+    def state_dict(self):
+        """``torch.optim.Adam``'s layout (``state[i] = {step, exp_avg, exp_avg_sq}``, ``param_groups``): with ``sync_module()`` and
+        the module's own state_dict, the checkpoint of train_dyn.py:33-43."""
+        return adam_state_dict(self.export(EXP_AVG), self.export(EXP_AVG_SQ), self.record()["steps_applied"], self.lr, self.betas, self.eps)
+
+    def load_state_dict(self, sd):
+        """Resumes from an Adam state_dict (the trainer's, or ``torch.optim.Adam``'s over the same parameters).  The betas and eps
+        must be the trainer's; the learning rate is taken over."""
+        m, v, step, group = parse_adam_state_dict(sd, self._shapes)
+        if tuple(float(b) for b in group["betas"]) != self.betas or float(group["eps"]) != self.eps:
+            raise ValueError(f"Trainer.load_state_dict: betas / eps {group['betas']} / {group['eps']} are not the trainer's "
+                             f"{self.betas} / {self.eps}")
+        zeros = lambda: [torch.zeros(s, dtype=torch.float32, device=self.device) for s in self._shapes]
+        self._import(EXP_AVG, zeros() if m is None else m, step)
+        self._import(EXP_AVG_SQ, zeros() if v is None else v)
+        self.lr = float(group["lr"])

@@ -711,6 +711,71 @@ int gm_train_batch_edges_ragged(const void* ws, const int64_t* sizes_host, int64
                                 int max_neighbours, int64_t n_edges, int64_t* edge_index, float* edge_attr, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The training step in the library (examples/train_dyn.py:49-72: loss, zero_grad, backward, optimizer.step): additions to ABI 7.
+ *
+ * gm_l1_loss == L1Loss(reduction='sum') / rows (train_dyn.py:58-65).  mask_col < 0: every row counts.  mask_col in [0, node_dim):
+ * the rows with nodes[row][mask_col] < 0.5 count (--use_updated_loss: the sand particles; a NaN there does not count).  The loss
+ * is the float64 sum, in one fixed order (no atomics), of the float32 values |pred - target| over the counted rows, divided by
+ * their count.  grad_out[r][c] = sign(pred - target) * (float)(1.0 / count) on counted rows, with sign(0) = 0; rows that do not
+ * count get 0.  A count of 0 gives a NaN loss and an all-zero grad_out.  loss_out / rows_counted_out / grad_out are device
+ * memory; rows_counted_out and grad_out may be NULL, nodes may be NULL iff mask_col < 0.  Refused before any device call
+ * (GM_ERR_INVALID_ARGUMENT, "gm_l1_loss: ..."): a null pointer, n_rows or out_dim below 1, mask_col >= node_dim; a workspace
+ * below gm_l1_loss_workspace_bytes is GM_ERR_WORKSPACE.  The workspace is written before it is read.
+ *
+ * A gm_trainer owns, for one gm_model, Adam's two moment estimates and a gradient buffer, each laid out like the model's own
+ * flat copy of its tensors, and a 32-byte device record { int64 steps_applied, int64 steps_skipped, double beta1_pow, double
+ * beta2_pow }.  The weights it updates ARE the model's copy: no tensor is copied in or out by a step.  The model must outlive
+ * the trainer, and between gm_trainer_create and gm_trainer_destroy the trainer's calls are the only ones that change its weights.
+ * Hidden 64 / 128 / 256 only, like every training entry point (GM_ERR_UNSUPPORTED).
+ *
+ * gm_train_step, on one stream and without a host synchronisation: clears the gradients; gm_epd_forward_train; gm_l1_loss of the
+ * prediction against `target` [N, out_dim] (mask_col as above, over `nodes`); gm_epd_backward into the trainer's gradients; one
+ * Adam step at learning rate lr; the model's training images re-packed, its inference images marked stale (the next inference
+ * call re-packs them).  loss_out (device, may be NULL) receives the loss.  The workspace (gm_train_step_workspace_bytes) begins
+ * with the forward's tape, so its first 16 bytes are the CSR header that carries the edge_index verdict (gm_csr_header_status).
+ * SKIPPED STEPS: when that header flags an edge_index entry outside [0, N), or the loss is not finite, the update does not
+ * happen: weights, both moments, steps_applied and the beta powers keep their bits, steps_skipped goes up by one, and loss_out
+ * still receives the loss (NaN for a flagged edge_index).
+ *
+ * ADAM'S ARITHMETIC (no weight decay, no AMSGrad).  Scalars, in float64 on the device: beta1_pow <- beta1_pow * beta1 and
+ * beta2_pow <- beta2_pow * beta2 (running products, not pow: a host loop reproduces them exactly); step = (float)(lr / (1 -
+ * beta1_pow)); s2 = (float)sqrt(1 - beta2_pow).  Per element, every float32 operation rounded on its own (no fused multiply-add,
+ * correctly rounded sqrt and division), with b1 = (float)beta1, o1 = (float)(1 - beta1), b2 = (float)beta2, o2 = (float)(1 -
+ * beta2), e = (float)eps:
+ *     m <- (b1 * m) + (o1 * g)
+ *     v <- (b2 * v) + ((o2 * g) * g)
+ *     p <- p - step * (m / ((sqrt(v) / s2) + e))
+ * This sequence is the library's own (torch.optim.Adam uses lerp and a fused addcdiv): it agrees with float64 Adam as closely as
+ * float32 torch does, not bit for bit with torch.
+ *
+ * gm_trainer_record copies the record into the caller's (pinned) host memory, asynchronously.  gm_trainer_export / _import copy
+ * between ONE of the trainer's buffers (`what`) and caller tensors on the device, in gm_model_create's order and shapes.
+ * Importing GM_TRAINER_PARAMS is gm_model_update; importing GM_TRAINER_EXP_AVG also sets steps_applied = step_count and the beta
+ * powers to the running products of step_count steps; the gradients are an output and cannot be imported.  A wrong n_tensors, a
+ * null tensor or an unknown `what` is GM_ERR_INVALID_ARGUMENT before any device call.
+ * ------------------------------------------------------------------------------------------ */
+size_t gm_l1_loss_workspace_bytes(int64_t n_rows, int out_dim);
+int gm_l1_loss(const float* pred, const float* target, int64_t n_rows, int out_dim, const float* nodes /* may be NULL iff mask_col < 0 */,
+               int node_dim, int mask_col, double* loss_out /* device, 1 */, int64_t* rows_counted_out /* device, may be NULL */,
+               float* grad_out /* [n_rows, out_dim] device, may be NULL */, void* ws, size_t ws_bytes, void* stream);
+
+typedef struct gm_trainer gm_trainer; /* opaque */
+#define GM_TRAINER_PARAMS 1
+#define GM_TRAINER_EXP_AVG 2
+#define GM_TRAINER_EXP_AVG_SQ 3
+#define GM_TRAINER_GRADS 4
+int gm_trainer_create(gm_model* m, double beta1, double beta2, double eps, void* stream, gm_trainer** out);
+void gm_trainer_destroy(gm_trainer* t);
+size_t gm_train_step_workspace_bytes(const gm_model_desc* desc, int64_t n_nodes, int64_t n_edges);
+int gm_train_step(gm_trainer* t, const float* nodes, int64_t n_nodes, const float* edge_attr, const int64_t* edge_index,
+                  int64_t n_edges, const float* target, int mask_col, double lr, double* loss_out /* device, may be NULL */,
+                  void* ws, size_t ws_bytes, void* stream);
+int gm_trainer_record(const gm_trainer* t, void* record_host /* 32 bytes */, void* stream);
+int gm_trainer_export(const gm_trainer* t, int what, float* const* tensors_out, int n_tensors, void* stream);
+int gm_trainer_import(gm_trainer* t, int what, const float* const* tensors_in, int n_tensors, int64_t step_count /* used with EXP_AVG */,
+                      void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Measurement hooks (no reference counterpart; the reference only wraps model.forward in
  * time.time(), examples/optimise_traj.py:99-103).  Per model handle: when enabled, launches made on behalf of THIS
  * model are bracketed with HIP events on their launch stream; other handles and streams are unaffected.

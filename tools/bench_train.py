@@ -3,6 +3,11 @@ reference's training configuration (examples/train_dyn.py defaults: batch of 2 g
 10 message-passing steps), synthetic scenes.  Prints one JSON line.
 
     python tools/bench_train.py [--n 5000] [--batch 2] [--steps 20] [--warmup 3] [--no-cpu-baseline]
+
+--step torch (the default) is the measurement above: model.forward under autograd, torch's loss and torch.optim.Adam.
+--step library times gnn_manip_amd.Trainer.step (gm_train_step: loss, backward and Adam in the library, no host synchronisation);
+--step both alternates the two in ONE process, --rounds blocks of --steps steps each, on the same batch and the same start
+weights, and reports each variant's median block and its spread (min, max) in ms per step.
 """
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -20,6 +25,8 @@ def main():
     ap.add_argument("--hidden", type=int, default=128)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--adam", choices=["foreach", "fused"], default="foreach", help="torch.optim.Adam implementation (the reference's train_dyn.py takes the default: foreach)")
+    ap.add_argument("--step", choices=["torch", "library", "both"], default="torch")
+    ap.add_argument("--rounds", type=int, default=7, help="--step library / both: timed blocks per variant")
     args = ap.parse_args()
     from gnn_manip_amd import EncProcDecGNN, GraphBoundedMultimaterialControl, scene
     dev = torch.device("cuda:0")
@@ -46,6 +53,39 @@ def main():
         opt.step()
         return loss
 
+    if args.step != "torch":
+        from gnn_manip_amd import Trainer
+        trainer = Trainer(model, lr=1e-4)                # its own copy of the same start weights
+
+        def block(fn):
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            for _ in range(args.steps):
+                fn()
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t) / args.steps * 1e3
+
+        variants = {"library": lambda: trainer.step(nodes, edge_attr, edge_index, tgt)}
+        if args.step == "both":
+            variants["torch"] = step
+        for fn in variants.values():
+            for _ in range(args.warmup):
+                fn()
+        times = {k: [] for k in variants}
+        for _ in range(args.rounds):                     # alternating: drift of the clocks reaches every variant alike
+            for k, fn in variants.items():
+                times[k].append(block(fn))
+        out = {"metric": "training step, ms per step: median of blocks [min, max]", "unit": "ms", "steps_per_block": args.steps, "rounds": args.rounds,
+               "config": {"workload": f"batch of {args.batch} scenes x N={args.n} (collated), hidden={H}, 10 MP steps", "nodes": n, "edges": e,
+                          "adam": args.adam},
+               "record": trainer.record()}
+        for k, v in times.items():
+            out[k] = {"median_ms": float(np.median(v)), "min_ms": min(v), "max_ms": max(v)}
+        if args.step == "both":
+            out["library_over_torch"] = out["library"]["median_ms"] / out["torch"]["median_ms"]
+        trainer.status()
+        print(json.dumps(out))
+        return
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
