@@ -135,6 +135,11 @@ PROTOTYPES = {
     "gm_trainer_record": (_i32, [_vp, _vp, _vp]),
     "gm_trainer_export": (_i32, [_vp, _i32, C.POINTER(_vp), _i32, _vp]),
     "gm_trainer_import": (_i32, [_vp, _i32, C.POINTER(_vp), _i32, _i64, _vp]),
+    "gm_rollout_l1_loss_workspace_bytes": (_sz, [_i64, _i64]),
+    "gm_rollout_l1_loss": (_i32, [_vp, _vp, _vp, _i32, _i64, _i64, _FD, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "gm_train_rollout_step_workspace_bytes": (_sz, [_MD, _FD, _i64, _i64, _i32, _i64]),
+    "gm_train_rollout_step": (_i32, [_vp, _vp, _i64, _FD, _i32, _vp, _i64, _vp, _i32, _i64, _i32, _vp, _f64, _i32, _vp, _vp,
+                                     _sz, _vp]),
     "gm_model_profile": (_i32, [_vp, _i32]),
     "gm_model_set_edge_kernel": (_i32, [_vp, _i32]),
     "gm_model_set_node_fusion": (_i32, [_vp, _i32]),

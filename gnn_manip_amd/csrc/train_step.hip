@@ -2,7 +2,9 @@
 // weight buffer, and gm_train_step, which strings forward, loss, backward and update together on one stream without a host
 // synchronisation (host orchestration here; the model's kernels are train.hip's, reached through gm_epd_forward_train /
 // gm_epd_backward).  The arithmetic of the loss and of Adam is stated in include/gnn_manip_hip.h and restated in numpy by
-// tests/train_step_cases.py.
+// tests/train_step_cases.py.  The other training mode, a loss on every frame of a rollout against a recording, is here too:
+// gm_rollout_l1_loss with its transpose and gm_train_rollout_step, which runs the inference rollout keeping its windows, that loss,
+// gm_rollout_backward_train (rollout_grad.hip) and the same Adam (restated by tests/train_rollout_cases.py).
 #include <math.h>
 #include <vector>
 #include "common.h"
@@ -155,6 +157,174 @@ int run_loss(const float* pred, const float* target, int64_t rows, int od, const
     return GM_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- the rollout's loss
+// The L1 loss of a rollout against recorded frames and its transpose.  Step t is scored on the last frame of the
+// window the step left: windows[t + 1] for t < steps - 1, `fin` for the last step.
+struct RolloutLossArgs {
+    const float *windows, *fin, *frames;   // [steps,k,N,D], [k,N,D], [steps,N,frame_dim]
+    const int32_t* rank;                   // [N] or null
+    int64_t n, steps;
+    int k, D, frame_dim, cart, mat;        // mat: the state's material column, < 0: off
+};
+
+__device__ inline const float* predicted_frame(const RolloutLossArgs& a, int64_t t) {
+    const size_t frame = (size_t)a.n * a.D;
+    return (t + 1 < a.steps ? a.windows + (size_t)(t + 1) * a.k * frame : a.fin) + (size_t)(a.k - 1) * frame;
+}
+// a row counts when it is not rigid and, with a material column, its flag in the last frame of windows[0] is below 0.5
+__device__ inline bool rollout_row_counts(const RolloutLossArgs& a, int64_t r) {
+    if (a.rank && a.rank[r] >= 0) return false;
+    return a.mat < 0 || a.windows[((size_t)(a.k - 1) * a.n + r) * a.D + a.mat] < 0.5f;
+}
+
+struct RolloutLossWs {
+    double* part_sum;     // [3][kLossGridMax]: one row per axis
+    int64_t* part_cnt;    // [kLossGridMax]
+    LossState* state;
+    size_t bytes;
+};
+RolloutLossWs carve_rollout_loss(void* ws) {
+    RolloutLossWs w;
+    Carver c(ws);
+    w.part_sum = c.take<double>(3 * kLossGridMax);
+    w.part_cnt = c.take<int64_t>(kLossGridMax);
+    w.state = c.take<LossState>(1);
+    w.bytes = c.used();
+    return w;
+}
+
+// Pass 1, l1_partials_kernel's pattern with the step as a further loop: a thread walks its rows (row, then step, then axis) and adds
+// the float32 values |pred - frame| in float64, one sum per axis; a workgroup's threads are summed in a fixed tree.
+__global__ void __launch_bounds__(kLossThreads) rollout_l1_partials_kernel(RolloutLossArgs a, double* part_sum, int64_t* part_cnt) {
+    __shared__ double sh_s[kLossThreads];
+    __shared__ int64_t sh_c[kLossThreads];
+    double s[3] = {0.0, 0.0, 0.0};
+    int64_t cnt = 0;
+    for (int64_t r = (int64_t)blockIdx.x * kLossThreads + threadIdx.x; r < a.n; r += (int64_t)gridDim.x * kLossThreads) {
+        if (!rollout_row_counts(a, r)) continue;
+        ++cnt;
+        for (int64_t t = 0; t < a.steps; ++t) {
+            const float* p = predicted_frame(a, t) + (size_t)r * a.D + a.cart;
+            const float* f = a.frames + ((size_t)t * a.n + r) * a.frame_dim + a.cart;
+            for (int c = 0; c < 3; ++c) s[c] += (double)fabsf(p[c] - f[c]);
+        }
+    }
+    for (int c = 0; c < 3; ++c) {
+        const double v = block_sum(s[c], sh_s);
+        if (threadIdx.x == 0) part_sum[c * kLossGridMax + blockIdx.x] = v;
+    }
+    cnt = block_sum(cnt, sh_c);
+    if (threadIdx.x == 0) part_cnt[blockIdx.x] = cnt;
+}
+
+struct PosScale { double s[3]; };
+
+// Pass 2, one workgroup: loss = (s_0 / scale_0 + s_1 / scale_1 + s_2 / scale_2) / (steps * count), and the skip decision.
+__global__ void __launch_bounds__(kLossThreads) rollout_l1_finish_kernel(const double* part_sum, const int64_t* part_cnt, int n_part,
+                                                                         int64_t steps, PosScale ps, LossState* st, double* loss_out,
+                                                                         int64_t* rows_out) {
+    __shared__ double sh_s[kLossThreads];
+    __shared__ int64_t sh_c[kLossThreads];
+    double s[3];
+    for (int c = 0; c < 3; ++c) {
+        double v = 0.0;
+        for (int i = threadIdx.x; i < n_part; i += kLossThreads) v += part_sum[c * kLossGridMax + i];
+        s[c] = block_sum(v, sh_s);
+    }
+    int64_t cnt = 0;
+    for (int i = threadIdx.x; i < n_part; i += kLossThreads) cnt += part_cnt[i];
+    cnt = block_sum(cnt, sh_c);
+    if (threadIdx.x != 0) return;
+    const double terms = (double)steps * (double)cnt;
+    const double loss = cnt > 0 ? ((s[0] / ps.s[0] + s[1] / ps.s[1]) + s[2] / ps.s[2]) / terms : (double)__builtin_nanf("");
+    st->loss = loss;
+    st->count = cnt;
+    st->scale = cnt > 0 ? (float)(1.0 / terms) : 0.f;
+    st->skip = isfinite(loss) ? 0 : 1;
+    if (loss_out) *loss_out = loss;
+    if (rows_out) *rows_out = cnt;
+}
+
+// Pass 3: the transpose, every element of d_records [steps,N,D] and d_final [k,N,D] written.  blockIdx.y is the [N,D] slab: slab
+// j < steps is d_records[j], which takes step j - 1's gradient (slab 0: zeros); slab steps + f is frame f of d_final, whose last frame
+// takes the last step's.  An element is sign(pred - frame) * (float)(1.0 / ((scale_c * steps) * count)) on the xyz columns of a
+// counted row, with sign(0) = 0, and 0 everywhere else.
+__global__ void __launch_bounds__(kLossThreads) rollout_l1_grad_kernel(RolloutLossArgs a, PosScale ps, const LossState* st, float* d_records,
+                                                                       float* d_final) {
+    const int64_t slab = blockIdx.y;
+    const size_t frame = (size_t)a.n * a.D;
+    float* out = slab < a.steps ? d_records + (size_t)slab * frame : d_final + (size_t)(slab - a.steps) * frame;
+    const int64_t t = slab < a.steps ? slab - 1 : (slab == a.steps + a.k - 1 ? a.steps - 1 : -1);
+    const int64_t cnt = st->count;
+    float g[3] = {0.f, 0.f, 0.f};
+    if (cnt > 0)
+        for (int c = 0; c < 3; ++c) g[c] = (float)(1.0 / ((ps.s[c] * (double)a.steps) * (double)cnt));
+    const float* pred = t >= 0 ? predicted_frame(a, t) : nullptr;
+    for (int64_t r = (int64_t)blockIdx.x * kLossThreads + threadIdx.x; r < a.n; r += (int64_t)gridDim.x * kLossThreads) {
+        const bool counts = t >= 0 && cnt > 0 && rollout_row_counts(a, r);
+        for (int c = 0; c < a.D; ++c) {
+            float v = 0.f;
+            const int ax = c - a.cart;
+            if (counts && ax >= 0 && ax < 3) {
+                const float d = pred[(size_t)r * a.D + c] - a.frames[((size_t)t * a.n + r) * a.frame_dim + c];
+                v = d > 0.f ? g[ax] : (d < 0.f ? -g[ax] : 0.f);
+            }
+            out[(size_t)r * a.D + c] = v;
+        }
+    }
+}
+
+// The scripted poses of a recorded drive: trajectory[t][rigid_rank[r]] = xyz(frames[t][r]).
+__global__ void __launch_bounds__(kLossThreads) recorded_poses_kernel(const float* frames, int frame_dim, int cart, const int32_t* rank,
+                                                                      int64_t n, int64_t n_rigid, float* trajectory) {
+    const int64_t r = (int64_t)blockIdx.x * kLossThreads + threadIdx.x, t = blockIdx.y;
+    if (r >= n) return;
+    const int64_t j = rank[r];
+    if (j < 0 || j >= n_rigid) return;
+    const float* f = frames + ((size_t)t * n + r) * frame_dim + cart;
+    float* o = trajectory + ((size_t)t * n_rigid + j) * 3;
+    o[0] = f[0]; o[1] = f[1]; o[2] = f[2];
+}
+
+constexpr int64_t kRolloutStepsMax = 32768;   // the step is a grid dimension of the launches above
+
+int check_rollout_loss_args(const gm_feature_desc* fd, int64_t n, int64_t steps, int frame_dim, int material_col, const double* pos_scale,
+                            const char* who) {
+    GM_REQUIRE(fd, GM_ERR_INVALID_ARGUMENT, "%s: null pointer", who);
+    GM_REQUIRE(steps >= 1 && steps <= kRolloutStepsMax, GM_ERR_INVALID_ARGUMENT, "%s: steps=%lld outside 1..%lld", who, (long long)steps,
+               (long long)kRolloutStepsMax);
+    GM_REQUIRE(n >= 1 && n < ((int64_t)1 << 31) && fd->k_steps >= 2 && fd->k_steps <= 64 && fd->data_dim >= 4 && fd->cart_col >= 0 &&
+                   fd->cart_col + 3 <= fd->data_dim,
+               GM_ERR_INVALID_ARGUMENT, "%s: sizes out of range (n_nodes=%lld, k_steps=%d, data_dim=%d, cart_col=%d)", who, (long long)n,
+               fd->k_steps, fd->data_dim, fd->cart_col);
+    GM_REQUIRE((frame_dim == fd->data_dim || frame_dim == fd->data_dim - 3) && fd->cart_col + 3 <= frame_dim, GM_ERR_INVALID_ARGUMENT,
+               "%s: frame_dim=%d is neither data_dim=%d nor data_dim - 3 with the xyz columns inside", who, frame_dim, fd->data_dim);
+    GM_REQUIRE(material_col < fd->data_dim, GM_ERR_INVALID_ARGUMENT, "%s: material_col=%d outside the %d state columns", who, material_col,
+               fd->data_dim);
+    for (int c = 0; pos_scale && c < 3; ++c)
+        GM_REQUIRE(pos_scale[c] == pos_scale[c] && pos_scale[c] != 0.0, GM_ERR_INVALID_ARGUMENT, "%s: pos_scale[%d] is zero or NaN", who, c);
+    return GM_OK;
+}
+
+// the launches of a rollout loss; the arguments are checked.  d_records / d_final: both or neither.
+int run_rollout_loss(const RolloutLossArgs& a, const double* pos_scale, const RolloutLossWs& w, double* loss_out, int64_t* rows_out,
+                     float* d_records, float* d_final, hipStream_t s) {
+    PosScale ps{{1.0, 1.0, 1.0}};
+    for (int c = 0; pos_scale && c < 3; ++c) ps.s[c] = pos_scale[c];
+    const unsigned g = loss_grid(a.n);
+    hipLaunchKernelGGL(rollout_l1_partials_kernel, dim3(g), dim3(kLossThreads), 0, s, a, w.part_sum, w.part_cnt);
+    GM_LAUNCH_CHECK();
+    hipLaunchKernelGGL(rollout_l1_finish_kernel, dim3(1), dim3(kLossThreads), 0, s, w.part_sum, w.part_cnt, (int)g, a.steps, ps, w.state,
+                       loss_out, rows_out);
+    GM_LAUNCH_CHECK();
+    if (d_records && d_final) {
+        hipLaunchKernelGGL(rollout_l1_grad_kernel, dim3(g, (unsigned)(a.steps + a.k)), dim3(kLossThreads), 0, s, a, ps, w.state, d_records,
+                           d_final);
+        GM_LAUNCH_CHECK();
+    }
+    return GM_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------------------- Adam
 struct TrainerRecord {   // the 32-byte device record gm_trainer_record copies out
     int64_t steps_applied, steps_skipped;
@@ -267,6 +437,48 @@ StepWs carve_step(void* ws, const gm_model_desc* d, int64_t n, int64_t e) {
     w.go = c.take<float>(od);
     w.bytes = c.used();
     return w;
+}
+
+// gm_train_rollout_step's workspace.  The windows come first: window t < steps is the state before step t, window `steps` the state
+// the forward left.
+struct RolloutStepWs {
+    float *windows, *d_records, *d_final, *d_obs0, *trajectory;
+    char *loss, *rollout, *sweep;
+    size_t rollout_bytes, sweep_bytes, bytes;
+};
+bool rollout_step_sizes_ok(const gm_model_desc* d, const gm_feature_desc* fd, int64_t n, int64_t n_rigid, int K, int64_t steps) {
+    return d && fd && n >= 1 && n_rigid >= 0 && n_rigid <= n && K >= 1 && steps >= 1 && steps <= kRolloutStepsMax && fd->k_steps >= 2 &&
+           fd->k_steps <= 64 && fd->data_dim >= 4 && n < ((int64_t)1 << 31) / K;
+}
+RolloutStepWs carve_rollout_step(void* ws, const gm_model_desc* d, const gm_feature_desc* fd, int64_t n, int64_t n_rigid, int K,
+                                 int64_t steps) {
+    RolloutStepWs w;
+    const size_t window = (size_t)fd->k_steps * n * fd->data_dim;
+    w.rollout_bytes = gm_rollout_workspace_bytes(d, n, K);
+    w.sweep_bytes = gm_rollout_backward_workspace_bytes(d, fd, n, K);
+    Carver c(ws);
+    w.windows = c.take<float>((size_t)(steps + 1) * window);
+    w.d_records = c.take<float>((size_t)steps * n * fd->data_dim);
+    w.d_final = c.take<float>(window);
+    w.d_obs0 = c.take<float>(window);
+    w.trajectory = c.take<float>((size_t)steps * n_rigid * 3);
+    w.loss = c.take<char>(carve_rollout_loss(nullptr).bytes);
+    w.rollout = c.take<char>(w.rollout_bytes);
+    w.sweep = c.take<char>(w.sweep_bytes);
+    w.bytes = c.used();
+    return w;
+}
+
+// One Adam step on the trainer's gradients under the skip decision a loss left in `st`; the model's images follow the new weights.
+int adam_update(gm_trainer* t, const LossState* st, double lr, double* loss_out, hipStream_t s) {
+    hipLaunchKernelGGL(adam_prepare_kernel, dim3(1), dim3(1), 0, s, st, t->rec, t->sc, t->beta1, t->beta2, lr, loss_out);
+    GM_LAUNCH_CHECK();
+    const AdamConsts k{(float)t->beta1, (float)(1.0 - t->beta1), (float)t->beta2, (float)(1.0 - t->beta2), (float)t->eps};
+    const size_t g = cdiv((int64_t)(t->count / 4 + 1), 256);
+    hipLaunchKernelGGL(adam_flat_kernel, dim3((unsigned)(g > 2048 ? 2048 : g)), dim3(256), 0, s, t->m->raw, t->exp_avg, t->exp_avg_sq, t->grad,
+                       t->count, k, t->sc);
+    GM_LAUNCH_CHECK();
+    return weights_changed_in_place(t->m, s);
 }
 
 float* flat_of(const gm_trainer* t, int what) {
@@ -388,14 +600,83 @@ int gm_train_step(gm_trainer* t, const float* nodes, int64_t n, const float* edg
     if (rc != GM_OK) return rc;
     rc = gm_epd_backward(m, t->T.data(), nt, nodes, edge_attr, n, e, w.go, t->G.data(), w.tape, w.tape_bytes, w.bwd, w.bwd_bytes, s);
     if (rc != GM_OK) return rc;
-    hipLaunchKernelGGL(adam_prepare_kernel, dim3(1), dim3(1), 0, s, lw.state, t->rec, t->sc, t->beta1, t->beta2, lr, loss_out);
-    GM_LAUNCH_CHECK();
-    const AdamConsts k{(float)t->beta1, (float)(1.0 - t->beta1), (float)t->beta2, (float)(1.0 - t->beta2), (float)t->eps};
-    const size_t g = cdiv((int64_t)(t->count / 4 + 1), 256);
-    hipLaunchKernelGGL(adam_flat_kernel, dim3((unsigned)(g > 2048 ? 2048 : g)), dim3(256), 0, s, m->raw, t->exp_avg, t->exp_avg_sq, t->grad,
-                       t->count, k, t->sc);
-    GM_LAUNCH_CHECK();
-    return weights_changed_in_place(m, s);
+    return adam_update(t, lw.state, lr, loss_out, s);
+}
+
+size_t gm_rollout_l1_loss_workspace_bytes(int64_t n_nodes, int64_t steps) {
+    if (n_nodes < 1 || steps < 1 || steps > kRolloutStepsMax) return 0;
+    return carve_rollout_loss(nullptr).bytes;
+}
+
+int gm_rollout_l1_loss(const float* windows, const float* final_state, const float* frames, int frame_dim, int64_t steps, int64_t n,
+                       const gm_feature_desc* fd, const int32_t* rigid_rank, int material_col, const double* pos_scale, double* loss_out,
+                       int64_t* rows_counted_out, float* d_records, float* d_final, void* ws, size_t ws_bytes, void* stream) {
+    int rc = check_rollout_loss_args(fd, n, steps, frame_dim, material_col, pos_scale, __func__);
+    if (rc != GM_OK) return rc;
+    GM_REQUIRE(windows && final_state && frames && loss_out && ws, GM_ERR_INVALID_ARGUMENT, "%s: null pointer", __func__);
+    GM_REQUIRE((d_records != nullptr) == (d_final != nullptr), GM_ERR_INVALID_ARGUMENT, "%s: d_records and d_final go together", __func__);
+    const RolloutLossWs w = carve_rollout_loss(ws);
+    GM_REQUIRE(ws_bytes >= w.bytes, GM_ERR_WORKSPACE, "%s: workspace %zu < %zu", __func__, ws_bytes, w.bytes);
+    gm::DevGuard dev_guard(windows);
+    const RolloutLossArgs a{windows, final_state, frames, rigid_rank, n, steps, fd->k_steps, fd->data_dim, frame_dim, fd->cart_col,
+                            material_col < 0 ? -1 : material_col};
+    return run_rollout_loss(a, pos_scale, w, loss_out, rows_counted_out, d_records, d_final, (hipStream_t)stream);
+}
+
+size_t gm_train_rollout_step_workspace_bytes(const gm_model_desc* desc, const gm_feature_desc* fdesc, int64_t n, int64_t n_rigid, int K,
+                                             int64_t steps) {
+    if (!rollout_step_sizes_ok(desc, fdesc, n, n_rigid, K, steps)) return 0;
+    return carve_rollout_step(nullptr, desc, fdesc, n, n_rigid, K, steps).bytes;
+}
+
+int gm_train_rollout_step(gm_trainer* t, const float* obs0, int64_t n, const gm_feature_desc* fd, int K, const int32_t* rigid_rank,
+                          int64_t n_rigid, const float* frames, int frame_dim, int64_t steps, int material_col, const double* pos_scale,
+                          double lr, int update, double* loss_out, void* ws, size_t ws_bytes, void* stream) {
+    GM_REQUIRE(t, GM_ERR_INVALID_ARGUMENT, "%s: null trainer", __func__);
+    gm_model* m = t->m;
+    int rc = check_rollout_loss_args(fd, n, steps, frame_dim, material_col, pos_scale, __func__);
+    if (rc != GM_OK) return rc;
+    GM_REQUIRE(rollout_step_sizes_ok(&m->d, fd, n, n_rigid, K, steps), GM_ERR_INVALID_ARGUMENT,
+               "%s: sizes out of range (n_nodes=%lld, n_rigid=%lld, max_neighbours=%d)", __func__, (long long)n, (long long)n_rigid, K);
+    GM_REQUIRE(obs0 && frames && ws && (rigid_rank || n_rigid == 0), GM_ERR_INVALID_ARGUMENT, "%s: null pointer", __func__);
+    GM_REQUIRE(lr == lr, GM_ERR_INVALID_ARGUMENT, "%s: lr is NaN", __func__);
+    rc = gm::check_model_for_scene(m->d, fd, __func__);
+    if (rc != GM_OK) return rc;
+    const RolloutStepWs w = carve_rollout_step(ws, &m->d, fd, n, n_rigid, K, steps);
+    GM_REQUIRE(ws_bytes >= w.bytes, GM_ERR_WORKSPACE, "%s: workspace %zu < %zu", __func__, ws_bytes, w.bytes);
+    gm::DevGuard dev_guard(obs0);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t window = (size_t)fd->k_steps * n * fd->data_dim;
+    const bool scripted = n_rigid > 0;
+    const float* trajectory = scripted ? w.trajectory : nullptr;
+
+    // 1. the recorded poses of the rigid rows as a trajectory
+    if (scripted) {
+        hipLaunchKernelGGL(recorded_poses_kernel, dim3((unsigned)cdiv(n, kLossThreads), (unsigned)steps), dim3(kLossThreads), 0, s, frames,
+                           frame_dim, fd->cart_col, rigid_rank, n, n_rigid, w.trajectory);
+        GM_LAUNCH_CHECK();
+    }
+    // 2. the inference rollout, each step in place on a copy of the window before it: window t stays behind as step t's pre-step window
+    GM_HIP_CHECK(hipMemcpyAsync(w.windows, obs0, window * sizeof(float), hipMemcpyDeviceToDevice, s));
+    for (int64_t i = 0; i < steps; ++i) {
+        float* next = w.windows + (size_t)(i + 1) * window;
+        GM_HIP_CHECK(hipMemcpyAsync(next, next - window, window * sizeof(float), hipMemcpyDeviceToDevice, s));
+        rc = gm_rollout_step(m, next, n, fd, K, rigid_rank, scripted ? trajectory + (size_t)i * n_rigid * 3 : nullptr, nullptr, w.rollout,
+                             w.rollout_bytes, stream);
+        if (rc != GM_OK) return rc;
+    }
+    // 3. the loss, and for an update its transpose
+    const RolloutLossArgs a{w.windows, w.windows + (size_t)steps * window, frames, rigid_rank, n, steps, fd->k_steps, fd->data_dim, frame_dim,
+                            fd->cart_col, material_col < 0 ? -1 : material_col};
+    const RolloutLossWs lw = carve_rollout_loss(w.loss);
+    rc = run_rollout_loss(a, pos_scale, lw, loss_out, nullptr, update ? w.d_records : nullptr, update ? w.d_final : nullptr, s);
+    if (rc != GM_OK || !update) return rc;
+    // 4. the reverse sweep into the trainer's gradients, then Adam under gm_train_step's skip rule
+    GM_HIP_CHECK(hipMemsetAsync(t->grad, 0, t->alloc * sizeof(float), s));
+    rc = gm_rollout_backward_train(m, t->T.data(), (int)t->T.size(), w.windows, n, fd, K, rigid_rank, trajectory, scripted ? steps : 0, n_rigid,
+                                   steps, w.d_final, w.d_records, t->G.data(), w.d_obs0, nullptr, w.sweep, w.sweep_bytes, stream);
+    if (rc != GM_OK) return rc;
+    return adam_update(t, lw.state, lr, loss_out, s);
 }
 
 int gm_trainer_record(const gm_trainer* t, void* record_host, void* stream) {

@@ -228,6 +228,32 @@ class CoffeeDataset(torch.utils.data.Dataset):
             raise ValueError("CoffeeDataset.batch: no samples")
         return _QueuedBatch(self, indices, seed, first_stream, [], _pinned_records(len(indices))).finish()
 
+    def rollout_sample(self, idx, steps, seed=0, stream=0):
+        """(window [k, N, D(+3)], frames [steps, N, data_dim]) of sample idx for training on a rollout (``Trainer.step_rollout``):
+        the window as ``batch([idx], seed, stream)`` builds it -- gm_train_batch_build at batch 1: control columns from the clean
+        positions, the library's random-walk noise when the dataset has ``noise`` -- and the ``steps`` recorded frames behind it,
+        a VIEW into the resident recording.  IndexError when the recording ends before them."""
+        idx, steps = int(idx), int(steps)
+        if not 0 <= idx < len(self.index):
+            raise IndexError(f"CoffeeDataset.rollout_sample: sample {idx} outside the {len(self.index)} samples")
+        s, t = self.index[idx]
+        data = self.sims[s]
+        if steps < 1 or t + self.k + steps > data.shape[0]:
+            raise IndexError(f"CoffeeDataset.rollout_sample: frames {t + self.k} .. {t + self.k + steps - 1} of a recording of "
+                             f"{int(data.shape[0])} frames")
+        L, dev, fd, n = lib(), self.device, self._window_desc(), int(data.shape[1])
+        k_nb = 20 if self.noise is None else int(self.max_neighbours)      # _QueuedBatch's: the graph is built and not used
+        first = (C.c_void_p * 1)(data.data_ptr() + t * n * int(data.shape[2]) * 4)
+        with torch.cuda.device(dev):
+            ws = _ws(L.gm_train_batch_workspace_bytes(C.byref(fd), 1, n, k_nb), dev)
+            nodes = torch.empty((n, 3 * (self.k - 1) + 7 + (3 if self.use_control else 0)), dtype=torch.float32, device=dev)
+            target = torch.empty((n, 3), dtype=torch.float32, device=dev)
+            window = torch.empty((self.k, n, fd.data_dim), dtype=torch.float32, device=dev)
+            check(L.gm_train_batch_build(first, 1, n, self.data_dim, C.byref(fd), k_nb, 0.0 if self.noise is None else float(self.noise),
+                                         int(seed), int(stream), None, ptr(nodes), ptr(target), ptr(window), ptr(ws), ws.numel(),
+                                         current_stream(dev)))
+        return window, data[t + self.k:t + self.k + steps]
+
     def _get_graph_attr(self):
         if self.use_control:
             return GraphBoundedMultimaterialControl(conn_r=self.conn_r, stats=self.stats, cartesian_idx=self.cartesian_idx,

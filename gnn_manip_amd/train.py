@@ -90,6 +90,9 @@ class Trainer:
     and step count stay as they were, ``record()`` counts it, its loss slot holds NaN.  The edge_index error itself surfaces as
     ``GMError`` at a later step or at ``status()``, like a training forward's.
 
+    ``step_rollout`` / ``evaluate_rollout`` / ``fit_rollout_epoch`` are the same for the other training mode, a loss on every
+    frame of a T-step rollout against a recording: one library call per sample (gm_train_rollout_step).
+
     Hidden sizes 64 / 128 / 256 only.  A module of another hidden size trains zero-padded through ``model.forward`` under autograd
     with a torch optimiser (``EncProcDecGNN._padded_training``): that path stays with autograd."""
 
@@ -119,6 +122,7 @@ class Trainer:
             check(L.gm_trainer_create(gm_model, self.betas[0], self.betas[1], self.eps, stream, C.byref(out)))
         self._h = _TrainerHandle(out, gm_model)
         self._ws = None
+        self._rollout_ws, self._kept = None, None   # step_rollout's workspace and the shape of the windows at its head
         self._loss = torch.full((1,), float("nan"), dtype=torch.float64, device=self.device)
         self._loss_ws = _ws(L.gm_l1_loss_workspace_bytes(1, 1), self.device)
         self._pin_record = torch.zeros(4, dtype=torch.int64).pin_memory()
@@ -205,6 +209,90 @@ class Trainer:
     def eval_epoch(self, loader):
         """``evaluate`` over every batch of `loader`, as ``fit_epoch``."""
         return self._epoch(loader, self.evaluate)
+
+    # ------------------------------------------------------------------------------------------ a rollout
+    def _rollout(self, engine, obs0, frames, steps, pos_scale, loss_out, state_material_col, update):
+        if engine.rigid_rank is None:
+            raise ValueError("engine.set_scene(obs0) must be called before a rollout step")
+        engine._check_tensor(obs0, "obs0", (engine.k, engine.n, engine.data_dim))
+        engine._check_tensor(frames, "frames", ("steps", engine.n, "frame_dim"))
+        if frames.shape[2] not in (engine.data_dim, engine.data_dim - 3):
+            raise ValueError(f"frames must have {engine.data_dim} or {engine.data_dim - 3} columns, got {frames.shape[2]}")
+        steps = int(frames.shape[0]) if steps is None else int(steps)
+        if not 1 <= steps <= frames.shape[0]:
+            raise ValueError(f"steps={steps} outside 1..{frames.shape[0]}, the frames given")
+        if engine.device != self.device:
+            raise ValueError(f"the engine is on {engine.device}, the trainer on {self.device}")
+        scale = None
+        if pos_scale is not None:
+            scale = [float(v) for v in np.asarray(pos_scale, np.float64).reshape(-1)]
+            if len(scale) != 3 or not all(v == v and v != 0.0 for v in scale):
+                raise ValueError("pos_scale must be three non-zero numbers")
+            scale = (C.c_double * 3)(*scale)
+        col = -1
+        if self.sand_only:
+            col = engine.fdesc.material_col if state_material_col is None else int(state_material_col)
+            if col < 0:
+                col += engine.data_dim
+            if not 0 <= col < engine.data_dim:
+                raise ValueError(f"state_material_col={state_material_col} is outside the {engine.data_dim} state columns")
+        slot = self._slot(loss_out)
+        L = lib()
+        need = L.gm_train_rollout_step_workspace_bytes(C.byref(self.desc), C.byref(engine.fdesc), engine.n, engine.n_rigid,
+                                                       engine.max_neighbours, steps)
+        if need == 0:
+            raise ValueError("Trainer: no rollout workspace for these sizes")
+        if self._rollout_ws is None or self._rollout_ws.numel() < need:
+            self._rollout_ws = _ws(need, self.device)
+        self._kept = (steps + 1, engine.k, engine.n, engine.data_dim)
+        check(L.gm_train_rollout_step(self._h, ptr(obs0), engine.n, C.byref(engine.fdesc), engine.max_neighbours, ptr(engine.rigid_rank),
+                                      engine.n_rigid, ptr(frames), int(frames.shape[2]), steps, col, scale, self.lr, int(update), ptr(slot),
+                                      ptr(self._rollout_ws), self._rollout_ws.numel(), current_stream(obs0)))
+
+    def step_rollout(self, engine, obs0, frames, steps=None, pos_scale=None, loss_out=None, state_material_col=None):
+        """One training step on a ``steps``-step rollout: gm_train_rollout_step.  ``engine`` is a
+        ``RolloutEngine`` after ``set_scene``: it supplies the feature descriptor, the rigid rows and the neighbour cap; the model
+        that runs is the TRAINER's.  ``obs0`` [k, N, D] is the window the rollout starts from (not written); ``frames``
+        [>= steps, N, D or D - 3] the recorded frame that follows each step, which may be a view into a resident recording.  The
+        rigid rows follow the recording, the loss is the L1 distance of every other row's predicted position to the recorded one,
+        each axis divided by ``pos_scale`` (three numbers; None: ones), over ``steps`` x the rows counted.  ``sand_only`` counts
+        the rows whose STATE material column (the engine's, or ``state_material_col``) is below 0.5 in ``obs0``'s last frame.
+        Nothing is returned; the loss goes into ``last_loss`` or ``loss_out``.  The reverse sweep reads one edge count per step
+        back, so the call synchronises ``steps`` times; a non-finite loss skips the update on the device like ``step``."""
+        self._rollout(engine, obs0, frames, steps, pos_scale, loss_out, state_material_col, True)
+
+    def evaluate_rollout(self, engine, obs0, frames, steps=None, pos_scale=None, loss_out=None, state_material_col=None):
+        """``step_rollout``'s rollout and loss without the update: a validation pass that changes nothing and never synchronises."""
+        self._rollout(engine, obs0, frames, steps, pos_scale, loss_out, state_material_col, False)
+
+    def kept_windows(self):
+        """[steps + 1, k, N, D]: the windows the last ``step_rollout`` / ``evaluate_rollout`` passed through, a view of its
+        workspace -- window t < steps the state before step t, the last one the final state -- valid until the next such call."""
+        count = int(np.prod(self._kept))
+        return self._rollout_ws[:4 * count].view(torch.float32).view(self._kept)
+
+    def fit_rollout_epoch(self, dataset, engine, steps, starts=None, seed=0, pos_scale=None):
+        """``step_rollout`` over the samples ``starts`` of ``dataset`` (default: every non-overlapping start, ``steps`` apart, of
+        every recording that has ``steps`` frames behind the window), each built by ``dataset.rollout_sample(start, steps, seed,
+        stream=start)``.  ``engine.set_scene`` is called whenever the recording changes.  The per-sample losses come back as a
+        float64 numpy array after the last step; a skipped sample's loss is NaN."""
+        steps = int(steps)
+        if starts is None:
+            starts, first = [], 0
+            for sim in dataset.sims:
+                last = int(sim.shape[0]) - dataset.k - steps       # the last start whose frames are all recorded
+                starts += [first + t for t in range(0, last + 1, steps)]
+                first += int(sim.shape[0]) - dataset.k
+        starts = [int(i) for i in starts]
+        scene = [None]
+
+        def one(start, loss_out):
+            window, frames = dataset.rollout_sample(start, steps, seed=seed, stream=start)
+            if scene[0] != dataset.index[start][0]:
+                engine.set_scene(window)
+                scene[0] = dataset.index[start][0]
+            self.step_rollout(engine, window, frames, steps, pos_scale=pos_scale, loss_out=loss_out)
+        return self._epoch(starts, one)
 
     # ------------------------------------------------------------------------------------------ state
     def record(self):

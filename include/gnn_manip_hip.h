@@ -776,6 +776,62 @@ int gm_trainer_import(gm_trainer* t, int what, const float* const* tensors_in, i
                       void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Training on a rollout in the library (no reference counterpart: the reference trains one step ahead only): additions to ABI 7.
+ *
+ * gm_rollout_l1_loss is the L1 loss of a `steps`-step rollout against recorded frames, and its transpose.  windows [steps,k,N,D] are
+ * the pre-step windows of a forward (gm_rollout_backward's argument), final_state [k,N,D] the state it left, frames
+ * [steps,N,frame_dim] the recorded frame that follows step t, read in place from a resident recording: frame_dim is data_dim, or
+ * data_dim - 3 for a recording without the three control columns a window appends.  The xyz columns are fdesc->cart_col .. + 2 in both.
+ * The PREDICTED frame of step t is the last frame of windows[t + 1] for t < steps - 1 and of final_state for t = steps - 1.  A row
+ * COUNTS when rigid_rank[r] < 0 (rigid_rank NULL: every row) and, with material_col >= 0 (a column of the STATE), when
+ * windows[0][k-1][r][material_col] < 0.5.  s_c is the float64 sum, over the counted rows and the steps, of the float32 values
+ * |pred - frame| on axis c, in one fixed order (no atomics: gm_l1_loss's two passes, a thread walking row, step, axis), and
+ *     loss = ((s_0 / scale_0 + s_1 / scale_1) + s_2 / scale_2) / (steps * count)
+ * with scale = pos_scale[3], HOST doubles (NULL: ones; acc_std makes a one-step rollout's loss the one-step training loss).
+ * The transpose: an element is sign(pred - frame) * (float)(1.0 / ((scale_c * steps) * count)) with sign(0) = 0, written into the
+ * xyz columns of d_records[t + 1] for t < steps - 1 -- gm_rollout_backward_train's argument: record t + 1 is that predicted frame --
+ * and of the last frame of d_final for t = steps - 1.  d_records [steps,N,D] and d_final [k,N,D] are WRITTEN IN FULL, zeros
+ * everywhere else, all of d_records[0] included: there is no memset in front.  Both NULL: the loss alone.  A count of 0 gives a
+ * NaN loss and all-zero gradients.  loss_out / rows_counted_out (may be NULL) are device memory.  Refused before any device call
+ * (GM_ERR_INVALID_ARGUMENT, "gm_rollout_l1_loss: ..."): a null pointer, steps outside 1..32768, n_nodes below 1, a frame_dim that is
+ * neither data_dim nor data_dim - 3 or does not hold the xyz columns, material_col >= data_dim, a zero or NaN pos_scale, one of
+ * d_records / d_final without the other; a workspace below gm_rollout_l1_loss_workspace_bytes is GM_ERR_WORKSPACE.  The workspace is
+ * written before it is read.
+ *
+ * gm_train_rollout_step is one training step on a rollout of the trainer's model, on one stream; obs0 [k,N,D] is not written.
+ *   1. one row kernel writes the scripted poses trajectory[t][rigid_rank[r]] = xyz(frames[t][r]) of the rigid rows (n_rigid of them;
+ *      rigid_rank / n_rigid as gm_rigid_rank returns them; n_rigid == 0: no poses);
+ *   2. the inference rollout runs from a copy of obs0 under that trajectory, a device-to-device copy of the window in front of each
+ *      gm_rollout_step, so that every pre-step window stays behind; the final state is bit-equal to gm_rollout's;
+ *   3. gm_rollout_l1_loss (material_col, pos_scale as above); loss_out (device, may be NULL) receives the loss;
+ *   4. update != 0: the trainer's gradients are cleared, gm_rollout_backward_train runs on the windows with the loss's d_final and
+ *      d_records and accumulates into them, and one Adam step at learning rate lr follows as in gm_train_step, with its rule for
+ *      SKIPPED STEPS: a loss that is not finite leaves weights, both moments, steps_applied and the beta powers with their bits and
+ *      raises steps_skipped by one.  update == 0 stops after the loss: a validation pass that changes nothing and never synchronises.
+ * LIMITS.  The sweep reads one edge count per step back to the host (gm_rollout_backward), so an updating call synchronises `steps`
+ * times.  A non-finite position reported there returns GM_ERR_DATA before Adam's launches: loss_out is written, weights, moments
+ * and the record keep their bits.  Hidden sizes 64 / 128 / 256 (a gm_trainer exists for no other).  The workspace
+ * (gm_train_rollout_step_workspace_bytes; 0 for refused sizes) holds the rollout's and the sweep's workspaces, steps + 1 windows,
+ * d_records, two [k,N,D] gradient windows and the trajectory, and BEGINS with the windows: window t < steps at float offset
+ * t k N D is the state before step t, window `steps` the final state.  Nothing in it needs initialising.  Refusals
+ * ("gm_train_rollout_step: ...", before any device call): gm_rollout_l1_loss's, a null trainer, n_rigid outside [0, n_nodes], a null
+ * rigid_rank with n_rigid > 0, a NaN lr, a model that does not fit the scene; a short workspace is GM_ERR_WORKSPACE.
+ * ------------------------------------------------------------------------------------------ */
+size_t gm_rollout_l1_loss_workspace_bytes(int64_t n_nodes, int64_t steps);
+int gm_rollout_l1_loss(const float* windows /*[steps,k,N,D]*/, const float* final_state /*[k,N,D]*/,
+                       const float* frames /*[steps,N,frame_dim]*/, int frame_dim, int64_t steps, int64_t n_nodes,
+                       const gm_feature_desc* fdesc, const int32_t* rigid_rank /* may be NULL */, int material_col,
+                       const double* pos_scale /* host [3], may be NULL */, double* loss_out /* device, 1 */,
+                       int64_t* rows_counted_out /* device, may be NULL */, float* d_records /*[steps,N,D] or NULL*/,
+                       float* d_final /*[k,N,D] or NULL*/, void* ws, size_t ws_bytes, void* stream);
+size_t gm_train_rollout_step_workspace_bytes(const gm_model_desc* desc, const gm_feature_desc* fdesc, int64_t n_nodes, int64_t n_rigid,
+                                             int max_neighbours, int64_t steps);
+int gm_train_rollout_step(gm_trainer* t, const float* obs0 /*[k,N,D]*/, int64_t n_nodes, const gm_feature_desc* fdesc, int max_neighbours,
+                          const int32_t* rigid_rank, int64_t n_rigid, const float* frames /*[steps,N,frame_dim]*/, int frame_dim,
+                          int64_t steps, int material_col, const double* pos_scale /* host [3], may be NULL */, double lr, int update,
+                          double* loss_out /* device, may be NULL */, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Measurement hooks (no reference counterpart; the reference only wraps model.forward in
  * time.time(), examples/optimise_traj.py:99-103).  Per model handle: when enabled, launches made on behalf of THIS
  * model are bracketed with HIP events on their launch stream; other handles and streams are unaffected.

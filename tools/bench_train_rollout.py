@@ -1,0 +1,120 @@
+"""Milliseconds per rollout step of one TRAINING step on a T-step rollout, for
+its two forms on the same windows --
+
+  python     2e's loop: differentiable_rollout(sweep="library", record=True, params=True) under autograd, the recorded poses by
+             boolean indexing, torch's L1 loss, torch.optim.Adam over the module's parameters
+  library    Trainer.step_rollout: gm_train_rollout_step, one call per sample
+
+on two synthetic 5000-node recordings rolled side by side as one block-diagonal scene (tools/bench_loader.py's recordings), hidden
+128, 10 message-passing steps.  Both forms run the same reverse sweep (gm_rollout_backward_train) and read one edge count per step
+back; what differs is the host side.  Every variant is warmed, then the variants alternate in one process for --rounds rounds; a
+window is --samples training steps and ends in a synchronise.  Prints one JSON line with every round.
+
+    python tools/bench_train_rollout.py [--n 5000] [--horizons 4,8] [--samples 10] [--rounds 5]
+"""
+import argparse, json, os, sys, time
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np
+import torch
+
+from bench_loader import recording
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=5000)
+    ap.add_argument("--scenes", type=int, default=2)
+    ap.add_argument("--k", type=int, default=6)
+    ap.add_argument("--hidden", type=int, default=128)
+    ap.add_argument("--horizons", type=str, default="4,8")
+    ap.add_argument("--samples", type=int, default=10, help="training steps per timed window")
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--lr", type=float, default=1e-5)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_train_rollout: no HIP device (there is no CPU fallback)")
+    from gnn_manip_amd import CoffeeDataset, EncProcDecGNN, RolloutEngine, Trainer, scene
+    dev = torch.device("cuda:0")
+    horizons = [int(v) for v in args.horizons.split(",")]
+    frames_needed = args.k + max(horizons) * (args.samples + 1)
+    side = 0.152 * (args.n / 5000.0) ** (1.0 / 3.0) * 0.8             # tools/bench_train.py's density
+    sets = [CoffeeDataset.from_recordings([torch.from_numpy(recording(args.n, frames_needed, 300 + s, side)).to(dev)], args.k, 0.015,
+                                          scene.STATS, scene.BOUNDS, scene.CART, scene.MAT[0], scene.CTRL, use_control=True)
+            for s in range(args.scenes)]
+
+    def samples(T):
+        """(window [k, scenes * n, 8], frames [T, scenes * n, 5]) of every non-overlapping start: the scenes side by side."""
+        out = []
+        for i in range(args.samples):
+            parts = [ds.rollout_sample(i * T, T) for ds in sets]
+            out.append((torch.cat([w for w, _ in parts], dim=1).contiguous(), torch.cat([f for _, f in parts], dim=1).contiguous()))
+        return out
+
+    def module():
+        torch.manual_seed(0)
+        m = EncProcDecGNN(3 * (args.k - 1) + 10, 4, 3, args.hidden, 2, 10).to(dev)
+        with torch.no_grad():
+            list(m.parameters())[-2].mul_(1e-3)                        # a random decoder damped: the rollout stays in the box
+        return m
+
+    results = {}
+    for T in horizons:
+        data = samples(T)
+        m_py, m_lib = module(), module()
+        eng_py = RolloutEngine(m_py, sets[0].graph_attr, args.n, k_steps=args.k, data_dim=8, device=dev, candidates=args.scenes)
+        eng_lib = RolloutEngine(m_lib, sets[0].graph_attr, args.n, k_steps=args.k, data_dim=8, device=dev, candidates=args.scenes)
+        eng_py.set_scene(data[0][0])
+        eng_lib.set_scene(data[0][0])
+        rigid = data[0][0][-1][:, 1] == 1
+        free = int((~rigid).sum())
+        opt = torch.optim.Adam(m_py.parameters(), lr=args.lr)
+        l1 = torch.nn.L1Loss(reduction="sum")
+        trainer = Trainer(m_lib, lr=args.lr)
+        slot = torch.zeros(1, dtype=torch.float64, device=dev)
+
+        def python_step(window, frames):
+            poses = frames[:, rigid, 2:5].contiguous()
+            final, records = eng_py.differentiable_rollout(window, poses, horizon=T, sweep="library", record=True, params=True)
+            pred = torch.cat((records[1:], final[-1:]))
+            loss = l1(pred[:, ~rigid, 2:5], frames[:, ~rigid, 2:5]) / (T * free)
+            opt.zero_grad()
+            loss.backward()
+            opt.step()
+            return loss
+
+        def library_step(window, frames):
+            trainer.step_rollout(eng_lib, window, frames, T, loss_out=slot)
+            return slot
+
+        variants = {"python": python_step, "library": library_step}
+
+        def window(fn, count):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for i in range(count):
+                loss = fn(*data[i % len(data)])
+            torch.cuda.synchronize()
+            return 1e3 * (time.perf_counter() - t0) / (count * T), float(loss.detach())
+
+        for fn in variants.values():
+            window(fn, args.warmup)
+        rounds = {name: [] for name in variants}
+        for _ in range(args.rounds):
+            for name, fn in variants.items():
+                ms, loss = window(fn, args.samples)
+                assert np.isfinite(loss), (name, T, loss)
+                rounds[name].append(round(ms, 3))
+        results[f"T={T}"] = {name: {"rounds": r, "median": float(np.median(r)), "min": min(r), "max": max(r)} for name, r in rounds.items()}
+        results[f"T={T}"]["edges_last_step"] = eng_py.status()       # the python form's last forward step (the engine's own workspace)
+    out = {"metric": "ms per rollout step of a training step on a T-step rollout (forward + loss + reverse sweep + Adam)", "unit": "ms",
+           "value": results[f"T={horizons[0]}"]["library"]["median"], "horizons": results,
+           "config": {"workload": f"{args.scenes} x N={args.n} side by side, k={args.k}, hidden={args.hidden}, 10 MP steps, L1 on the free rows, Adam",
+                      "samples_per_window": args.samples, "rounds": args.rounds, "warmup_samples": args.warmup, "lr": args.lr},
+           "dtype": "f32", "data": "synthetic"}
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
