@@ -140,6 +140,13 @@ PROTOTYPES = {
     "gm_train_rollout_step_workspace_bytes": (_sz, [_MD, _FD, _i64, _i64, _i32, _i64]),
     "gm_train_rollout_step": (_i32, [_vp, _vp, _i64, _FD, _i32, _vp, _i64, _vp, _i32, _i64, _i32, _vp, _f64, _i32, _vp, _vp,
                                      _sz, _vp]),
+    "gm_trainer_begin": (_i32, [_vp, _vp]),
+    "gm_train_step_accumulate": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _sz, _vp]),
+    "gm_train_rollout_accumulate": (_i32, [_vp, _vp, _i64, _FD, _i32, _vp, _i64, _vp, _i32, _i64, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "gm_trainer_apply": (_i32, [_vp, _f64, _f64, _vp, _vp, _vp]),
+    "gm_trainer_accum_record": (_i32, [_vp, _vp, _vp]),
+    "gm_grad_sumsq_workspace_bytes": (_sz, [_i64]),
+    "gm_grad_sumsq": (_i32, [_vp, _i64, _vp, _vp, _sz, _vp]),
     "gm_model_profile": (_i32, [_vp, _i32]),
     "gm_model_set_edge_kernel": (_i32, [_vp, _i32]),
     "gm_model_set_node_fusion": (_i32, [_vp, _i32]),

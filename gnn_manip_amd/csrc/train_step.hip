@@ -4,7 +4,9 @@
 // gm_epd_backward).  The arithmetic of the loss and of Adam is stated in include/gnn_manip_hip.h and restated in numpy by
 // tests/train_step_cases.py.  The other training mode, a loss on every frame of a rollout against a recording, is here too:
 // gm_rollout_l1_loss with its transpose and gm_train_rollout_step, which runs the inference rollout keeping its windows, that loss,
-// gm_rollout_backward_train (rollout_grad.hip) and the same Adam (restated by tests/train_rollout_cases.py).
+// gm_rollout_backward_train (rollout_grad.hip) and the same Adam (restated by tests/train_rollout_cases.py).  Both steps are also
+// available in three phases -- gm_trainer_begin, gm_train_step_accumulate / gm_train_rollout_accumulate per sample, gm_trainer_apply
+// -- for an update from the mean of several samples' gradients, its norm (gm_grad_sumsq) clipped (tests/train_accum_cases.py).
 #include <math.h>
 #include <vector>
 #include "common.h"
@@ -333,8 +335,15 @@ struct TrainerRecord {   // the 32-byte device record gm_trainer_record copies o
 static_assert(sizeof(TrainerRecord) == 32, "TrainerRecord layout");
 struct AdamScalars {     // what the prepare launch leaves for the flat launch
     float step, s2;
-    int skip, pad;
+    int skip;
+    float gscale;        // gm_trainer_apply: what multiplies every gradient element first (the mean and the clip)
 };
+static_assert(sizeof(AdamScalars) == 16, "AdamScalars layout");
+struct AccumRecord {     // the 48-byte device record of a mini-batch gm_trainer_accum_record copies out
+    int64_t samples, bad;
+    double loss_sum, sumsq, grad_norm, scale;
+};
+static_assert(sizeof(AccumRecord) == 48, "AccumRecord layout");
 
 __global__ void trainer_record_set_kernel(TrainerRecord* rec, int64_t applied, int64_t skipped, int keep_skipped, double b1p, double b2p) {
     rec->steps_applied = applied;
@@ -360,7 +369,103 @@ __global__ void adam_prepare_kernel(const LossState* st, TrainerRecord* rec, Ada
     sc->s2 = (float)sqrt(1.0 - b2p);
 }
 
+// gm_trainer_begin: an empty mini-batch.  sumsq stays 0 (finite) where no norm is asked for.
+__global__ void accum_reset_kernel(AccumRecord* acc) {
+    acc->samples = 0;
+    acc->bad = 0;
+    acc->loss_sum = 0.0;
+    acc->sumsq = 0.0;
+    acc->grad_norm = (double)__builtin_nanf("");
+    acc->scale = (double)__builtin_nanf("");
+}
+
+// One thread: a sample joins the mini-batch, in arrival order.
+__global__ void accum_add_kernel(const LossState* st, AccumRecord* acc) {
+    acc->samples += 1;
+    acc->loss_sum += st->loss;
+    if (st->skip) acc->bad += 1;
+}
+
+// The float64 sum of squares, l1_partials_kernel's shape.  Pass 1: a thread walks its 16-byte groups in a fixed stride, then its
+// elements of the scalar tail, squaring and adding in float64; a workgroup's threads are summed in a fixed tree.  x is 16-byte aligned.
+__global__ void __launch_bounds__(kLossThreads) sumsq_partials_kernel(const float* x, size_t count, double* part) {
+    __shared__ double sh[kLossThreads];
+    const size_t n4 = count >> 2, t = (size_t)blockIdx.x * kLossThreads + threadIdx.x, nt = (size_t)gridDim.x * kLossThreads;
+    const float4* x4 = reinterpret_cast<const float4*>(x);
+    double s = 0.0;
+    for (size_t i = t; i < n4; i += nt) {
+        const float4 v = x4[i];
+        s += (double)v.x * (double)v.x;
+        s += (double)v.y * (double)v.y;
+        s += (double)v.z * (double)v.z;
+        s += (double)v.w * (double)v.w;
+    }
+    for (size_t i = (n4 << 2) + t; i < count; i += nt) s += (double)x[i] * (double)x[i];
+    s = block_sum(s, sh);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+// Pass 2, one workgroup: the partials in a fixed tree.
+__global__ void __launch_bounds__(kLossThreads) sumsq_finish_kernel(const double* part, int n_part, double* out) {
+    __shared__ double sh[kLossThreads];
+    double s = 0.0;
+    for (int i = threadIdx.x; i < n_part; i += kLossThreads) s += part[i];
+    s = block_sum(s, sh);
+    if (threadIdx.x == 0) *out = s;
+}
+
+unsigned sumsq_grid(size_t count) {
+    const int64_t g = cdiv((int64_t)cdiv((int64_t)count, 4), kLossThreads);
+    return (unsigned)(g < 1 ? 1 : (g > kLossGridMax ? kLossGridMax : g));
+}
+int run_sumsq(const float* x, size_t count, double* part, double* out, hipStream_t s) {
+    const unsigned g = sumsq_grid(count);
+    hipLaunchKernelGGL(sumsq_partials_kernel, dim3(g), dim3(kLossThreads), 0, s, x, count, part);
+    GM_LAUNCH_CHECK();
+    hipLaunchKernelGGL(sumsq_finish_kernel, dim3(1), dim3(kLossThreads), 0, s, part, (int)g, out);
+    GM_LAUNCH_CHECK();
+    return GM_OK;
+}
+
+// One thread: gm_trainer_apply's float64 scalars -- the mean's and the clip's scale, the skip decision, then adam_prepare_kernel's.
+// have_norm: acc->sumsq holds this mini-batch's sum of squares.  clip: max_norm is in force.
+__global__ void apply_prepare_kernel(AccumRecord* acc, TrainerRecord* rec, AdamScalars* sc, double beta1, double beta2, double lr,
+                                     double max_norm, int clip, int have_norm, double* loss_out, double* norm_out) {
+    const double S = (double)acc->samples;
+    const double norm = have_norm ? sqrt(acc->sumsq) / S : (double)__builtin_nanf("");
+    double coef = 1.0;
+    if (clip) {
+        const double c = max_norm / (norm + 1e-6);
+        coef = c < 1.0 ? c : 1.0;
+    }
+    const float scale = (float)(coef / S);
+    acc->grad_norm = norm;
+    acc->scale = (double)scale;
+    if (norm_out) *norm_out = norm;
+    const int skip = (acc->bad > 0 || !isfinite(acc->sumsq)) ? 1 : 0;
+    sc->skip = skip;
+    sc->gscale = scale;
+    if (loss_out) *loss_out = skip ? (double)__builtin_nanf("") : acc->loss_sum / S;
+    if (skip) {
+        rec->steps_skipped += 1;
+        return;
+    }
+    const double b1p = rec->beta1_pow * beta1, b2p = rec->beta2_pow * beta2;
+    rec->beta1_pow = b1p;
+    rec->beta2_pow = b2p;
+    rec->steps_applied += 1;
+    sc->step = (float)(lr / (1.0 - b1p));
+    sc->s2 = (float)sqrt(1.0 - b2p);
+}
+
 struct AdamConsts { float b1, o1, b2, o2, eps; };
+
+// gm_trainer_apply's first operation on an element, rounded on its own
+__device__ inline float scaled_gradient(float g, float scale) {
+#pragma clang fp contract(off)
+    const float g1 = scale * g;
+    return g1;
+}
 
 // One element, every float32 operation rounded on its own: no contraction into fused multiply-adds in this function.
 __device__ inline void adam_element(float& p, float& m, float& v, float g, const AdamConsts& k, float step, float s2) {
@@ -380,11 +485,12 @@ __device__ inline void adam_element(float& p, float& m, float& v, float g, const
 }
 
 // The flat launch over the model's weight buffer: 16-byte accesses, a scalar tail for a count that is no multiple of 4.  A skipped
-// step returns before it touches anything.
+// step returns before it touches anything.  kScaled (gm_trainer_apply): every gradient element is multiplied by sc->gscale first.
+template <bool kScaled>
 __global__ void __launch_bounds__(256) adam_flat_kernel(float* p, float* m, float* v, const float* g, size_t count, AdamConsts k,
                                                          const AdamScalars* sc) {
     if (sc->skip) return;
-    const float step = sc->step, s2 = sc->s2;
+    const float step = sc->step, s2 = sc->s2, gs = kScaled ? sc->gscale : 1.f;
     const size_t n4 = count >> 2, t = (size_t)blockIdx.x * blockDim.x + threadIdx.x, nt = (size_t)gridDim.x * blockDim.x;
     float4* p4 = reinterpret_cast<float4*>(p);
     float4* m4 = reinterpret_cast<float4*>(m);
@@ -392,14 +498,18 @@ __global__ void __launch_bounds__(256) adam_flat_kernel(float* p, float* m, floa
     const float4* g4 = reinterpret_cast<const float4*>(g);
     for (size_t i = t; i < n4; i += nt) {
         float4 pp = p4[i], mm = m4[i], vv = v4[i];
-        const float4 gg = g4[i];
+        float4 gg = g4[i];
+        if (kScaled) {
+            gg.x = scaled_gradient(gg.x, gs); gg.y = scaled_gradient(gg.y, gs);
+            gg.z = scaled_gradient(gg.z, gs); gg.w = scaled_gradient(gg.w, gs);
+        }
         adam_element(pp.x, mm.x, vv.x, gg.x, k, step, s2);
         adam_element(pp.y, mm.y, vv.y, gg.y, k, step, s2);
         adam_element(pp.z, mm.z, vv.z, gg.z, k, step, s2);
         adam_element(pp.w, mm.w, vv.w, gg.w, k, step, s2);
         p4[i] = pp; m4[i] = mm; v4[i] = vv;
     }
-    for (size_t i = (n4 << 2) + t; i < count; i += nt) adam_element(p[i], m[i], v[i], g[i], k, step, s2);
+    for (size_t i = (n4 << 2) + t; i < count; i += nt) adam_element(p[i], m[i], v[i], kScaled ? scaled_gradient(g[i], gs) : g[i], k, step, s2);
 }
 
 }  // namespace
@@ -413,6 +523,9 @@ struct gm_trainer {
     TrainerRecord* rec = nullptr;
     AdamScalars* sc = nullptr;
     void* loss_ws = nullptr;   // gm_l1_loss's workspace of gm_train_step
+    AccumRecord* acc = nullptr;    // the mini-batch's record
+    double* norm_part = nullptr;   // [kLossGridMax]: the partials of the gradient norm
+    int64_t pending = -1;          // host side of a mini-batch: samples accumulated since gm_trainer_begin; < 0: none begun
     std::vector<const float*> T;   // tensor t of m->raw
     std::vector<float*> G;         // its gradient: what gm_epd_backward takes as grads[t]
 };
@@ -470,15 +583,63 @@ RolloutStepWs carve_rollout_step(void* ws, const gm_model_desc* d, const gm_feat
 }
 
 // One Adam step on the trainer's gradients under the skip decision a loss left in `st`; the model's images follow the new weights.
+template <bool kScaled>
+int adam_flat(gm_trainer* t, hipStream_t s) {
+    const AdamConsts k{(float)t->beta1, (float)(1.0 - t->beta1), (float)t->beta2, (float)(1.0 - t->beta2), (float)t->eps};
+    const size_t g = cdiv((int64_t)(t->count / 4 + 1), 256);
+    hipLaunchKernelGGL(adam_flat_kernel<kScaled>, dim3((unsigned)(g > 2048 ? 2048 : g)), dim3(256), 0, s, t->m->raw, t->exp_avg,
+                       t->exp_avg_sq, t->grad, t->count, k, t->sc);
+    GM_LAUNCH_CHECK();
+    return weights_changed_in_place(t->m, s);
+}
 int adam_update(gm_trainer* t, const LossState* st, double lr, double* loss_out, hipStream_t s) {
     hipLaunchKernelGGL(adam_prepare_kernel, dim3(1), dim3(1), 0, s, st, t->rec, t->sc, t->beta1, t->beta2, lr, loss_out);
     GM_LAUNCH_CHECK();
-    const AdamConsts k{(float)t->beta1, (float)(1.0 - t->beta1), (float)t->beta2, (float)(1.0 - t->beta2), (float)t->eps};
-    const size_t g = cdiv((int64_t)(t->count / 4 + 1), 256);
-    hipLaunchKernelGGL(adam_flat_kernel, dim3((unsigned)(g > 2048 ? 2048 : g)), dim3(256), 0, s, t->m->raw, t->exp_avg, t->exp_avg_sq, t->grad,
-                       t->count, k, t->sc);
+    return adam_flat<false>(t, s);
+}
+
+// A sample joins the pending mini-batch: the device record, then the host count.
+int accumulate_sample(gm_trainer* t, const LossState* st, hipStream_t s) {
+    hipLaunchKernelGGL(accum_add_kernel, dim3(1), dim3(1), 0, s, st, t->acc);
     GM_LAUNCH_CHECK();
-    return weights_changed_in_place(t->m, s);
+    t->pending += 1;
+    return GM_OK;
+}
+
+// What gm_train_step and gm_train_step_accumulate refuse before any device call.
+int check_step_args(const gm_trainer* t, const float* nodes, int64_t n, const float* edge_attr, const int64_t* edge_index, int64_t e,
+                    const float* target, int mask_col, double lr, const void* ws, size_t ws_bytes, const char* who) {
+    GM_REQUIRE(t, GM_ERR_INVALID_ARGUMENT, "%s: null trainer", who);
+    const gm_model* m = t->m;
+    GM_REQUIRE(n >= 1 && e >= 0 && n < ((int64_t)1 << 31) && e < ((int64_t)1 << 31) / m->H, GM_ERR_INVALID_ARGUMENT,
+               "%s: sizes out of range (n=%lld, e=%lld)", who, (long long)n, (long long)e);
+    GM_REQUIRE(nodes && target && ws && (e == 0 || (edge_attr && edge_index)), GM_ERR_INVALID_ARGUMENT, "%s: null pointer", who);
+    GM_REQUIRE(mask_col < 0 || mask_col < m->d.node_dim, GM_ERR_INVALID_ARGUMENT, "%s: mask_col=%d outside the %d node columns", who,
+               mask_col, m->d.node_dim);
+    GM_REQUIRE(lr == lr, GM_ERR_INVALID_ARGUMENT, "%s: lr is NaN", who);
+    const size_t need = carve_step(nullptr, &m->d, n, e).bytes;
+    GM_REQUIRE(ws_bytes >= need, GM_ERR_WORKSPACE, "%s: workspace %zu < %zu", who, ws_bytes, need);
+    return GM_OK;
+}
+
+// A batch's forward, loss and backward into the trainer's gradients (clear: zeroed first; else added to); the loss's state is left
+// in the trainer's loss workspace.  The arguments are checked.
+int step_gradients(gm_trainer* t, const float* nodes, int64_t n, const float* edge_attr, const int64_t* edge_index, int64_t e,
+                   const float* target, int mask_col, bool clear, double* loss_out, void* ws, hipStream_t s) {
+    gm_model* m = t->m;
+    const StepWs w = carve_step(ws, &m->d, n, e);
+    const int nt = (int)t->T.size(), od = m->d.out_dim;
+    const LossWs lw = carve_loss(t->loss_ws);
+    if (clear) GM_HIP_CHECK(hipMemsetAsync(t->grad, 0, t->alloc * sizeof(float), s));
+    int rc = gm_epd_forward_train(m, nodes, n, edge_attr, edge_index, e, w.out, w.tape, w.tape_bytes, s);
+    if (rc != GM_OK) return rc;
+    // the tape begins with the destination sort's workspace, the source sort's follows it (train_model.hip: take_csr): the two
+    // headers that carry the edge_index verdict
+    const CsrHeader* ha = reinterpret_cast<const CsrHeader*>(w.tape);
+    const CsrHeader* hb = reinterpret_cast<const CsrHeader*>(w.tape + align_up(gm_csr_workspace_bytes(n, e), 256));
+    rc = run_loss(w.out, target, n, od, nodes, m->d.node_dim, mask_col, ha, hb, lw, loss_out, nullptr, w.go, s);
+    if (rc != GM_OK) return rc;
+    return gm_epd_backward(m, t->T.data(), nt, nodes, edge_attr, n, e, w.go, t->G.data(), w.tape, w.tape_bytes, w.bwd, w.bwd_bytes, s);
 }
 
 float* flat_of(const gm_trainer* t, int what) {
@@ -538,7 +699,8 @@ int gm_trainer_create(gm_model* m, double beta1, double beta2, double eps, void*
     const size_t fb = t->alloc * sizeof(float);
     if (hipMalloc(&t->exp_avg, fb) != hipSuccess || hipMalloc(&t->exp_avg_sq, fb) != hipSuccess || hipMalloc(&t->grad, fb) != hipSuccess ||
         hipMalloc(&t->rec, sizeof(TrainerRecord)) != hipSuccess || hipMalloc(&t->sc, sizeof(AdamScalars)) != hipSuccess ||
-        hipMalloc(&t->loss_ws, loss_bytes) != hipSuccess) {
+        hipMalloc(&t->loss_ws, loss_bytes) != hipSuccess || hipMalloc(&t->acc, sizeof(AccumRecord)) != hipSuccess ||
+        hipMalloc(&t->norm_part, kLossGridMax * sizeof(double)) != hipSuccess) {
         gm::set_error("%s: hipMalloc failed", __func__);
         gm_trainer_destroy(t);
         return GM_ERR_HIP;
@@ -550,6 +712,8 @@ int gm_trainer_create(gm_model* m, double beta1, double beta2, double eps, void*
         GM_HIP_CHECK(hipMemsetAsync(t->grad, 0, fb, s));
         GM_HIP_CHECK(hipMemsetAsync(t->sc, 0, sizeof(AdamScalars), s));
         hipLaunchKernelGGL(trainer_record_set_kernel, dim3(1), dim3(1), 0, s, t->rec, (int64_t)0, (int64_t)0, 0, 1.0, 1.0);
+        GM_LAUNCH_CHECK();
+        hipLaunchKernelGGL(accum_reset_kernel, dim3(1), dim3(1), 0, s, t->acc);
         GM_LAUNCH_CHECK();
         return GM_OK;
     }();
@@ -563,7 +727,8 @@ int gm_trainer_create(gm_model* m, double beta1, double beta2, double eps, void*
 
 void gm_trainer_destroy(gm_trainer* t) {
     if (!t) return;
-    for (void* p : std::initializer_list<void*>{t->exp_avg, t->exp_avg_sq, t->grad, t->rec, t->sc, t->loss_ws}) (void)hipFree(p);
+    for (void* p : std::initializer_list<void*>{t->exp_avg, t->exp_avg_sq, t->grad, t->rec, t->sc, t->loss_ws, t->acc, t->norm_part})
+        (void)hipFree(p);
     delete t;
 }
 
@@ -574,33 +739,85 @@ size_t gm_train_step_workspace_bytes(const gm_model_desc* desc, int64_t n, int64
 
 int gm_train_step(gm_trainer* t, const float* nodes, int64_t n, const float* edge_attr, const int64_t* edge_index, int64_t e,
                   const float* target, int mask_col, double lr, double* loss_out, void* ws, size_t ws_bytes, void* stream) {
-    GM_REQUIRE(t, GM_ERR_INVALID_ARGUMENT, "%s: null trainer", __func__);
-    gm_model* m = t->m;
-    GM_REQUIRE(n >= 1 && e >= 0 && n < ((int64_t)1 << 31) && e < ((int64_t)1 << 31) / m->H, GM_ERR_INVALID_ARGUMENT,
-               "%s: sizes out of range (n=%lld, e=%lld)", __func__, (long long)n, (long long)e);
-    GM_REQUIRE(nodes && target && ws && (e == 0 || (edge_attr && edge_index)), GM_ERR_INVALID_ARGUMENT, "%s: null pointer", __func__);
-    GM_REQUIRE(mask_col < 0 || mask_col < m->d.node_dim, GM_ERR_INVALID_ARGUMENT, "%s: mask_col=%d outside the %d node columns", __func__,
-               mask_col, m->d.node_dim);
-    GM_REQUIRE(lr == lr, GM_ERR_INVALID_ARGUMENT, "%s: lr is NaN", __func__);
-    const StepWs w = carve_step(ws, &m->d, n, e);
-    GM_REQUIRE(ws_bytes >= w.bytes, GM_ERR_WORKSPACE, "%s: workspace %zu < %zu", __func__, ws_bytes, w.bytes);
+    int rc = check_step_args(t, nodes, n, edge_attr, edge_index, e, target, mask_col, lr, ws, ws_bytes, __func__);
+    if (rc != GM_OK) return rc;
     gm::DevGuard dev_guard(nodes);
     hipStream_t s = (hipStream_t)stream;
-    const int nt = (int)t->T.size(), od = m->d.out_dim;
-    const LossWs lw = carve_loss(t->loss_ws);
+    t->pending = -1;   // the gradients are cleared: a mini-batch that was pending is gone
+    rc = step_gradients(t, nodes, n, edge_attr, edge_index, e, target, mask_col, true, nullptr, ws, s);
+    if (rc != GM_OK) return rc;
+    return adam_update(t, carve_loss(t->loss_ws).state, lr, loss_out, s);
+}
 
+int gm_trainer_begin(gm_trainer* t, void* stream) {
+    GM_REQUIRE(t, GM_ERR_INVALID_ARGUMENT, "%s: null trainer", __func__);
+    gm::DevGuard dev_guard(t->grad);
+    hipStream_t s = (hipStream_t)stream;
+    t->pending = -1;
     GM_HIP_CHECK(hipMemsetAsync(t->grad, 0, t->alloc * sizeof(float), s));
-    int rc = gm_epd_forward_train(m, nodes, n, edge_attr, edge_index, e, w.out, w.tape, w.tape_bytes, s);
+    hipLaunchKernelGGL(accum_reset_kernel, dim3(1), dim3(1), 0, s, t->acc);
+    GM_LAUNCH_CHECK();
+    t->pending = 0;
+    return GM_OK;
+}
+
+int gm_train_step_accumulate(gm_trainer* t, const float* nodes, int64_t n, const float* edge_attr, const int64_t* edge_index, int64_t e,
+                             const float* target, int mask_col, double* loss_out, void* ws, size_t ws_bytes, void* stream) {
+    int rc = check_step_args(t, nodes, n, edge_attr, edge_index, e, target, mask_col, 0.0, ws, ws_bytes, __func__);
     if (rc != GM_OK) return rc;
-    // the tape begins with the destination sort's workspace, the source sort's follows it (train_model.hip: take_csr): the two
-    // headers that carry the edge_index verdict
-    const CsrHeader* ha = reinterpret_cast<const CsrHeader*>(w.tape);
-    const CsrHeader* hb = reinterpret_cast<const CsrHeader*>(w.tape + align_up(gm_csr_workspace_bytes(n, e), 256));
-    rc = run_loss(w.out, target, n, od, nodes, m->d.node_dim, mask_col, ha, hb, lw, nullptr, nullptr, w.go, s);
+    GM_REQUIRE(t->pending >= 0, GM_ERR_INVALID_ARGUMENT, "%s: no mini-batch begun (gm_trainer_begin)", __func__);
+    gm::DevGuard dev_guard(nodes);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t pending = t->pending;
+    t->pending = -1;   // until the sample has joined: a failure below leaves the mini-batch undefined
+    rc = step_gradients(t, nodes, n, edge_attr, edge_index, e, target, mask_col, false, loss_out, ws, s);
     if (rc != GM_OK) return rc;
-    rc = gm_epd_backward(m, t->T.data(), nt, nodes, edge_attr, n, e, w.go, t->G.data(), w.tape, w.tape_bytes, w.bwd, w.bwd_bytes, s);
-    if (rc != GM_OK) return rc;
-    return adam_update(t, lw.state, lr, loss_out, s);
+    t->pending = pending;
+    return accumulate_sample(t, carve_loss(t->loss_ws).state, s);
+}
+
+int gm_trainer_apply(gm_trainer* t, double lr, double max_grad_norm, double* loss_out, double* grad_norm_out, void* stream) {
+    GM_REQUIRE(t, GM_ERR_INVALID_ARGUMENT, "%s: null trainer", __func__);
+    GM_REQUIRE(lr == lr, GM_ERR_INVALID_ARGUMENT, "%s: lr is NaN", __func__);
+    GM_REQUIRE(max_grad_norm == max_grad_norm, GM_ERR_INVALID_ARGUMENT, "%s: max_grad_norm is NaN", __func__);
+    GM_REQUIRE(t->pending >= 0, GM_ERR_INVALID_ARGUMENT, "%s: no mini-batch begun (gm_trainer_begin)", __func__);
+    GM_REQUIRE(t->pending >= 1, GM_ERR_INVALID_ARGUMENT, "%s: no sample accumulated", __func__);
+    gm::DevGuard dev_guard(t->grad);
+    hipStream_t s = (hipStream_t)stream;
+    const int clip = (max_grad_norm > 0.0 && max_grad_norm <= 1.7976931348623157e308) ? 1 : 0;
+    const int have_norm = (clip || grad_norm_out) ? 1 : 0;
+    t->pending = -1;   // one update per mini-batch
+    if (have_norm) {
+        int rc = run_sumsq(t->grad, t->count, t->norm_part, &t->acc->sumsq, s);
+        if (rc != GM_OK) return rc;
+    }
+    hipLaunchKernelGGL(apply_prepare_kernel, dim3(1), dim3(1), 0, s, t->acc, t->rec, t->sc, t->beta1, t->beta2, lr, max_grad_norm, clip,
+                       have_norm, loss_out, grad_norm_out);
+    GM_LAUNCH_CHECK();
+    return adam_flat<true>(t, s);
+}
+
+int gm_trainer_accum_record(const gm_trainer* t, void* record_host, void* stream) {
+    GM_REQUIRE(t, GM_ERR_INVALID_ARGUMENT, "%s: null trainer", __func__);
+    GM_REQUIRE(record_host, GM_ERR_INVALID_ARGUMENT, "%s: null pointer", __func__);
+    gm::DevGuard dev_guard(t->acc);
+    GM_HIP_CHECK(hipMemcpyAsync(record_host, t->acc, sizeof(AccumRecord), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    return GM_OK;
+}
+
+size_t gm_grad_sumsq_workspace_bytes(int64_t count) {
+    if (count < 1) return 0;
+    return kLossGridMax * sizeof(double);
+}
+
+int gm_grad_sumsq(const float* x, int64_t count, double* sumsq_out, void* ws, size_t ws_bytes, void* stream) {
+    GM_REQUIRE(x && sumsq_out && ws, GM_ERR_INVALID_ARGUMENT, "%s: null pointer", __func__);
+    GM_REQUIRE(count >= 1 && count < ((int64_t)1 << 40), GM_ERR_INVALID_ARGUMENT, "%s: count=%lld out of range", __func__, (long long)count);
+    GM_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)ws & 7) == 0, GM_ERR_INVALID_ARGUMENT, "%s: x must lie on 16 bytes, ws on 8", __func__);
+    const size_t need = gm_grad_sumsq_workspace_bytes(count);
+    GM_REQUIRE(ws_bytes >= need, GM_ERR_WORKSPACE, "%s: workspace %zu < %zu", __func__, ws_bytes, need);
+    gm::DevGuard dev_guard(x);
+    return run_sumsq(x, (size_t)count, static_cast<double*>(ws), sumsq_out, (hipStream_t)stream);
 }
 
 size_t gm_rollout_l1_loss_workspace_bytes(int64_t n_nodes, int64_t steps) {
@@ -629,23 +846,29 @@ size_t gm_train_rollout_step_workspace_bytes(const gm_model_desc* desc, const gm
     return carve_rollout_step(nullptr, desc, fdesc, n, n_rigid, K, steps).bytes;
 }
 
-int gm_train_rollout_step(gm_trainer* t, const float* obs0, int64_t n, const gm_feature_desc* fd, int K, const int32_t* rigid_rank,
-                          int64_t n_rigid, const float* frames, int frame_dim, int64_t steps, int material_col, const double* pos_scale,
-                          double lr, int update, double* loss_out, void* ws, size_t ws_bytes, void* stream) {
-    GM_REQUIRE(t, GM_ERR_INVALID_ARGUMENT, "%s: null trainer", __func__);
+// gm_train_rollout_step (mode kRolloutEvaluate for update == 0, kRolloutStep) and gm_train_rollout_accumulate (kRolloutAccumulate)
+enum { kRolloutEvaluate = 0, kRolloutStep = 1, kRolloutAccumulate = 2 };
+static int train_rollout(gm_trainer* t, const float* obs0, int64_t n, const gm_feature_desc* fd, int K, const int32_t* rigid_rank,
+                         int64_t n_rigid, const float* frames, int frame_dim, int64_t steps, int material_col, const double* pos_scale,
+                         double lr, int mode, double* loss_out, void* ws, size_t ws_bytes, void* stream, const char* who) {
+    GM_REQUIRE(t, GM_ERR_INVALID_ARGUMENT, "%s: null trainer", who);
     gm_model* m = t->m;
-    int rc = check_rollout_loss_args(fd, n, steps, frame_dim, material_col, pos_scale, __func__);
+    int rc = check_rollout_loss_args(fd, n, steps, frame_dim, material_col, pos_scale, who);
     if (rc != GM_OK) return rc;
     GM_REQUIRE(rollout_step_sizes_ok(&m->d, fd, n, n_rigid, K, steps), GM_ERR_INVALID_ARGUMENT,
-               "%s: sizes out of range (n_nodes=%lld, n_rigid=%lld, max_neighbours=%d)", __func__, (long long)n, (long long)n_rigid, K);
-    GM_REQUIRE(obs0 && frames && ws && (rigid_rank || n_rigid == 0), GM_ERR_INVALID_ARGUMENT, "%s: null pointer", __func__);
-    GM_REQUIRE(lr == lr, GM_ERR_INVALID_ARGUMENT, "%s: lr is NaN", __func__);
-    rc = gm::check_model_for_scene(m->d, fd, __func__);
+               "%s: sizes out of range (n_nodes=%lld, n_rigid=%lld, max_neighbours=%d)", who, (long long)n, (long long)n_rigid, K);
+    GM_REQUIRE(obs0 && frames && ws && (rigid_rank || n_rigid == 0), GM_ERR_INVALID_ARGUMENT, "%s: null pointer", who);
+    GM_REQUIRE(lr == lr, GM_ERR_INVALID_ARGUMENT, "%s: lr is NaN", who);
+    rc = gm::check_model_for_scene(m->d, fd, who);
     if (rc != GM_OK) return rc;
     const RolloutStepWs w = carve_rollout_step(ws, &m->d, fd, n, n_rigid, K, steps);
-    GM_REQUIRE(ws_bytes >= w.bytes, GM_ERR_WORKSPACE, "%s: workspace %zu < %zu", __func__, ws_bytes, w.bytes);
+    GM_REQUIRE(ws_bytes >= w.bytes, GM_ERR_WORKSPACE, "%s: workspace %zu < %zu", who, ws_bytes, w.bytes);
+    GM_REQUIRE(mode != kRolloutAccumulate || t->pending >= 0, GM_ERR_INVALID_ARGUMENT, "%s: no mini-batch begun (gm_trainer_begin)", who);
     gm::DevGuard dev_guard(obs0);
     hipStream_t s = (hipStream_t)stream;
+    const bool update = mode != kRolloutEvaluate;
+    const int64_t pending = t->pending;
+    if (update) t->pending = -1;   // a step clears the gradients; a failing accumulate leaves the mini-batch undefined
     const size_t window = (size_t)fd->k_steps * n * fd->data_dim;
     const bool scripted = n_rigid > 0;
     const float* trajectory = scripted ? w.trajectory : nullptr;
@@ -671,12 +894,29 @@ int gm_train_rollout_step(gm_trainer* t, const float* obs0, int64_t n, const gm_
     const RolloutLossWs lw = carve_rollout_loss(w.loss);
     rc = run_rollout_loss(a, pos_scale, lw, loss_out, nullptr, update ? w.d_records : nullptr, update ? w.d_final : nullptr, s);
     if (rc != GM_OK || !update) return rc;
-    // 4. the reverse sweep into the trainer's gradients, then Adam under gm_train_step's skip rule
-    GM_HIP_CHECK(hipMemsetAsync(t->grad, 0, t->alloc * sizeof(float), s));
+    // 4. the reverse sweep into the trainer's gradients (a step clears them first), then Adam under gm_train_step's skip rule, or the
+    //    sample joins the pending mini-batch
+    if (mode == kRolloutStep) GM_HIP_CHECK(hipMemsetAsync(t->grad, 0, t->alloc * sizeof(float), s));
     rc = gm_rollout_backward_train(m, t->T.data(), (int)t->T.size(), w.windows, n, fd, K, rigid_rank, trajectory, scripted ? steps : 0, n_rigid,
                                    steps, w.d_final, w.d_records, t->G.data(), w.d_obs0, nullptr, w.sweep, w.sweep_bytes, stream);
     if (rc != GM_OK) return rc;
-    return adam_update(t, lw.state, lr, loss_out, s);
+    if (mode == kRolloutStep) return adam_update(t, lw.state, lr, loss_out, s);
+    t->pending = pending;
+    return accumulate_sample(t, lw.state, s);
+}
+
+int gm_train_rollout_step(gm_trainer* t, const float* obs0, int64_t n, const gm_feature_desc* fd, int K, const int32_t* rigid_rank,
+                          int64_t n_rigid, const float* frames, int frame_dim, int64_t steps, int material_col, const double* pos_scale,
+                          double lr, int update, double* loss_out, void* ws, size_t ws_bytes, void* stream) {
+    return train_rollout(t, obs0, n, fd, K, rigid_rank, n_rigid, frames, frame_dim, steps, material_col, pos_scale, lr,
+                         update ? kRolloutStep : kRolloutEvaluate, loss_out, ws, ws_bytes, stream, __func__);
+}
+
+int gm_train_rollout_accumulate(gm_trainer* t, const float* obs0, int64_t n, const gm_feature_desc* fd, int K, const int32_t* rigid_rank,
+                                int64_t n_rigid, const float* frames, int frame_dim, int64_t steps, int material_col,
+                                const double* pos_scale, double* loss_out, void* ws, size_t ws_bytes, void* stream) {
+    return train_rollout(t, obs0, n, fd, K, rigid_rank, n_rigid, frames, frame_dim, steps, material_col, pos_scale, 0.0, kRolloutAccumulate,
+                         loss_out, ws, ws_bytes, stream, __func__);
 }
 
 int gm_trainer_record(const gm_trainer* t, void* record_host, void* stream) {

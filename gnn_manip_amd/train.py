@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._lib import ModelDesc, check, current_stream, lib, ptr
+from ._lib import GMError, ModelDesc, check, current_stream, lib, ptr
 from .dataset import GraphData
 from .epd_gnn import TRAIN_WIDTHS, DstCsr, _check_edge_index, _device_arrays, _Model, _pointers
 from .graph import _need_cuda, _ws
@@ -93,8 +93,17 @@ class Trainer:
     ``step_rollout`` / ``evaluate_rollout`` / ``fit_rollout_epoch`` are the same for the other training mode, a loss on every
     frame of a T-step rollout against a recording: one library call per sample (gm_train_rollout_step).
 
+    MINI-BATCHES AND THE CLIP.  ``zero_grad()``, then ``accumulate(batch)`` / ``accumulate_rollout(...)`` any
+    number of times, then ``apply()``: one update from the MEAN of the samples' gradients, its norm clipped to ``max_grad_norm`` by
+    ``torch.nn.utils.clip_grad_norm_``'s formula (a plain attribute like ``lr``, set after construction; None: no clip).  With
+    ``max_grad_norm`` set, ``step`` and ``step_rollout`` are those three calls on one sample; with None they are the single
+    library call.  One skipped sample skips its whole mini-batch.  ``fit_epoch(loader, accumulate=B)`` / ``fit_rollout_epoch(..., batch_size=B)`` run epochs
+    of such mini-batches.  The clip is not part of ``state_dict()``.
+
     Hidden sizes 64 / 128 / 256 only.  A module of another hidden size trains zero-padded through ``model.forward`` under autograd
     with a torch optimiser (``EncProcDecGNN._padded_training``): that path stays with autograd."""
+
+    max_grad_norm = None   # a plain attribute like ``lr``, set after construction: the clip of ``apply`` (None: no clip)
 
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, sand_only=False, material_col=None):
         if model.dims[3] not in TRAIN_WIDTHS:
@@ -126,7 +135,10 @@ class Trainer:
         self._loss = torch.full((1,), float("nan"), dtype=torch.float64, device=self.device)
         self._loss_ws = _ws(L.gm_l1_loss_workspace_bytes(1, 1), self.device)
         self._pin_record = torch.zeros(4, dtype=torch.int64).pin_memory()
+        self._pin_accum = torch.zeros(6, dtype=torch.int64).pin_memory()
         self._pin_losses = None
+        self._grad_norm = torch.full((1,), float("nan"), dtype=torch.float64, device=self.device)
+        self.last_epoch_grad_norms = None
 
     # ------------------------------------------------------------------------------------------ one batch
     @property
@@ -156,17 +168,81 @@ class Trainer:
 
     def step(self, x, edge_attr=None, edge_index=None, y=None, loss_out=None):
         """One training step on a batch (four tensors, or a ``GraphData``): gm_train_step.  Nothing is returned and nothing waits."""
+        if self.max_grad_norm is not None:
+            self.zero_grad()
+            self.accumulate(x, edge_attr, edge_index, y)
+            return self.apply(loss_out=loss_out)
+        self._one_batch(x, edge_attr, edge_index, y, self._slot(loss_out), True)
+
+    def _one_batch(self, x, edge_attr, edge_index, y, slot, update):
+        """gm_train_step (update) or gm_train_step_accumulate on a checked batch; slot: the loss's, or None."""
         x, edge_attr, edge_index, y, n, e = self._batch(x, edge_attr, edge_index, y)
-        slot = self._slot(loss_out)
         L = lib()
         if self.model.auto_status:
             self.model._reap_watched(block=False)
         need = L.gm_train_step_workspace_bytes(C.byref(self.desc), n, e)
         if self._ws is None or self._ws.numel() < need:
             self._ws = _ws(need, self.device)
-        check(L.gm_train_step(self._h, ptr(x), n, ptr(edge_attr), ptr(edge_index), e, ptr(y), self.mask_col, self.lr, ptr(slot),
-                              ptr(self._ws), self._ws.numel(), current_stream(x)))
+        head = (self._h, ptr(x), n, ptr(edge_attr), ptr(edge_index), e, ptr(y), self.mask_col)
+        tail = (ptr(slot), ptr(self._ws), self._ws.numel(), current_stream(x))
+        check(L.gm_train_step(*head, self.lr, *tail) if update else L.gm_train_step_accumulate(*head, *tail))
         self.model._watch(self._ws)   # the workspace begins with the tape's CSR header: the edge_index verdict
+
+    # ------------------------------------------------------------------------------------------ a mini-batch
+    @property
+    def last_grad_norm(self):
+        """The norm of the mean gradient of the last ``apply`` that computed one and was given no ``norm_out``: a float64 device
+        tensor of one element."""
+        return self._grad_norm
+
+    def _clipping(self):
+        g = self.max_grad_norm
+        if g is not None and float(g) != float(g):
+            raise ValueError("max_grad_norm is NaN")
+        return g is not None and 0.0 < float(g) < float("inf")
+
+    def zero_grad(self):
+        """Starts a mini-batch: gm_trainer_begin clears the gradients and the mini-batch's record."""
+        check(lib().gm_trainer_begin(self._h, current_stream(self.device)))
+
+    def _accumulated(self, call):
+        try:
+            call()
+        except GMError:
+            self.zero_grad()          # the failed sample may be partly in the gradients: the pending mini-batch is dropped
+            raise
+
+    def accumulate(self, x, edge_attr=None, edge_index=None, y=None, loss_out=None):
+        """Adds a batch's gradient to the pending mini-batch (``step``'s arguments and checks): gm_train_step_accumulate.  The
+        batch's own loss goes into ``loss_out`` when one is given.  A ``GMError`` drops the pending mini-batch."""
+        slot = None if loss_out is None else self._slot(loss_out)
+        self._accumulated(lambda: self._one_batch(x, edge_attr, edge_index, y, slot, False))
+
+    def accumulate_rollout(self, engine, obs0, frames, steps=None, pos_scale=None, loss_out=None, state_material_col=None):
+        """Adds a rollout sample's gradient to the pending mini-batch (``step_rollout``'s arguments and checks):
+        gm_train_rollout_accumulate.  Samples of different scenes and sizes may share a mini-batch."""
+        self._accumulated(lambda: self._rollout(engine, obs0, frames, steps, pos_scale, loss_out, state_material_col, "accumulate"))
+
+    def apply(self, loss_out=None, norm_out=None, want_norm=False):
+        """One Adam update from the MEAN of the accumulated gradients, clipped to ``max_grad_norm`` (None, <= 0 or inf: no clip)
+        by ``clip_grad_norm_``'s formula: gm_trainer_apply.  The mean of the samples' losses goes into ``last_loss`` or
+        ``loss_out``.  The gradient norm is computed when the clip is in force, ``want_norm`` is set or ``norm_out`` (one float64
+        element on the device) is given, and goes into ``norm_out`` or ``last_grad_norm``.  A mini-batch with a skipped sample, or
+        whose gradient norm is not finite, changes nothing: ``record()`` counts it, its loss is NaN."""
+        slot = self._slot(loss_out)
+        norm = None
+        if self._clipping() or want_norm or norm_out is not None:
+            norm = self._grad_norm if norm_out is None else self._slot(norm_out)
+        mg = 0.0 if self.max_grad_norm is None else float(self.max_grad_norm)
+        check(lib().gm_trainer_apply(self._h, self.lr, mg, ptr(slot), ptr(norm), current_stream(self.device)))
+
+    def accum_record(self):
+        """{'samples', 'bad', 'loss_sum', 'sumsq', 'grad_norm', 'scale'} of the mini-batch's device record (synchronises)."""
+        check(lib().gm_trainer_accum_record(self._h, C.c_void_p(self._pin_accum.data_ptr()), current_stream(self.device)))
+        torch.cuda.current_stream(self.device).synchronize()
+        f = self._pin_accum[2:].view(torch.float64)
+        return {"samples": int(self._pin_accum[0]), "bad": int(self._pin_accum[1]), "loss_sum": float(f[0]), "sumsq": float(f[1]),
+                "grad_norm": float(f[2]), "scale": float(f[3])}
 
     def evaluate(self, x, edge_attr=None, edge_index=None, y=None, loss_out=None):
         """train_dyn.py's ``test_epoch`` on one batch: the inference forward of the trainer's weights and the same loss, no update."""
@@ -201,17 +277,65 @@ class Trainer:
         torch.cuda.current_stream(self.device).synchronize()   # the epoch's one synchronisation
         return host[:count].numpy().copy()
 
-    def fit_epoch(self, loader):
+    def _epoch_of_mini_batches(self, items, size, accumulate_one):
+        """Consecutive `size` items of `items` form a mini-batch (the last may be shorter): zero_grad, accumulate_one(item) each,
+        apply.  One float64 loss per UPDATE, the gradient norms in ``last_epoch_grad_norms``, one synchronisation at the end."""
+        size = int(size)
+        if size < 1:
+            raise ValueError(f"a mini-batch holds at least one sample, got {size}")
+        slots = torch.full((2, max(-(-len(items) // size), 1)), float("nan"), dtype=torch.float64, device=self.device)   # losses, norms
+        with_norm = self._clipping()
+        updates = pending = 0
+
+        def update():
+            nonlocal slots, updates
+            if updates == slots.shape[1]:
+                slots = torch.cat((slots, torch.full_like(slots, float("nan"))), dim=1)
+            self.apply(loss_out=slots[0, updates:updates + 1], norm_out=slots[1, updates:updates + 1] if with_norm else None)
+            updates += 1
+        for item in items:
+            if pending == 0:
+                self.zero_grad()
+            try:
+                accumulate_one(item)
+            except GMError:
+                pending = 0
+                raise
+            pending += 1
+            if pending == size:
+                update()
+                pending = 0
+        if pending:
+            update()
+        if self._pin_losses is None or self._pin_losses.numel() < slots.numel():
+            self._pin_losses = torch.empty(slots.numel(), dtype=torch.float64).pin_memory()
+        host = self._pin_losses[:slots.numel()].view(slots.shape)
+        host.copy_(slots, non_blocking=True)
+        torch.cuda.current_stream(self.device).synchronize()   # the epoch's one synchronisation
+        self.last_epoch_grad_norms = host[1, :updates].numpy().copy()
+        return host[0, :updates].numpy().copy()
+
+    def fit_epoch(self, loader, accumulate=1):
         """``step`` over every batch of `loader` (a ``GraphLoader``, fused and prefetching or not): the per-batch losses as a
-        float64 numpy array, after a single synchronisation at the end.  A skipped batch's loss is NaN."""
-        return self._epoch(loader, self.step)
+        float64 numpy array, after a single synchronisation at the end.  A skipped batch's loss is NaN.
+
+        ``accumulate`` > 1: every ``accumulate`` consecutive batches (the last group may be shorter) form a mini-batch with ONE
+        update from the mean of their gradients (``zero_grad`` / ``accumulate`` / ``apply``); the array then holds one loss per
+        update, the mean over its batches.  ``last_epoch_grad_norms`` holds the updates' gradient norms, NaN where none was
+        computed (no clip in force)."""
+        if int(accumulate) == 1 and self.max_grad_norm is None:
+            losses = self._epoch(loader, self.step)
+            self.last_epoch_grad_norms = np.full(len(losses), np.nan)
+            return losses
+        return self._epoch_of_mini_batches(loader, accumulate, self.accumulate)
 
     def eval_epoch(self, loader):
         """``evaluate`` over every batch of `loader`, as ``fit_epoch``."""
         return self._epoch(loader, self.evaluate)
 
     # ------------------------------------------------------------------------------------------ a rollout
-    def _rollout(self, engine, obs0, frames, steps, pos_scale, loss_out, state_material_col, update):
+    def _rollout(self, engine, obs0, frames, steps, pos_scale, loss_out, state_material_col, mode):
+        """gm_train_rollout_step (mode "step" / "evaluate") or gm_train_rollout_accumulate ("accumulate") on checked arguments."""
         if engine.rigid_rank is None:
             raise ValueError("engine.set_scene(obs0) must be called before a rollout step")
         engine._check_tensor(obs0, "obs0", (engine.k, engine.n, engine.data_dim))
@@ -236,7 +360,7 @@ class Trainer:
                 col += engine.data_dim
             if not 0 <= col < engine.data_dim:
                 raise ValueError(f"state_material_col={state_material_col} is outside the {engine.data_dim} state columns")
-        slot = self._slot(loss_out)
+        slot = None if mode == "accumulate" and loss_out is None else self._slot(loss_out)
         L = lib()
         need = L.gm_train_rollout_step_workspace_bytes(C.byref(self.desc), C.byref(engine.fdesc), engine.n, engine.n_rigid,
                                                        engine.max_neighbours, steps)
@@ -245,9 +369,13 @@ class Trainer:
         if self._rollout_ws is None or self._rollout_ws.numel() < need:
             self._rollout_ws = _ws(need, self.device)
         self._kept = (steps + 1, engine.k, engine.n, engine.data_dim)
-        check(L.gm_train_rollout_step(self._h, ptr(obs0), engine.n, C.byref(engine.fdesc), engine.max_neighbours, ptr(engine.rigid_rank),
-                                      engine.n_rigid, ptr(frames), int(frames.shape[2]), steps, col, scale, self.lr, int(update), ptr(slot),
-                                      ptr(self._rollout_ws), self._rollout_ws.numel(), current_stream(obs0)))
+        head = (self._h, ptr(obs0), engine.n, C.byref(engine.fdesc), engine.max_neighbours, ptr(engine.rigid_rank), engine.n_rigid,
+                ptr(frames), int(frames.shape[2]), steps, col, scale)
+        tail = (ptr(slot), ptr(self._rollout_ws), self._rollout_ws.numel(), current_stream(obs0))
+        if mode == "accumulate":
+            check(L.gm_train_rollout_accumulate(*head, *tail))
+        else:
+            check(L.gm_train_rollout_step(*head, self.lr, int(mode == "step"), *tail))
 
     def step_rollout(self, engine, obs0, frames, steps=None, pos_scale=None, loss_out=None, state_material_col=None):
         """One training step on a ``steps``-step rollout: gm_train_rollout_step.  ``engine`` is a
@@ -259,11 +387,15 @@ class Trainer:
         the rows whose STATE material column (the engine's, or ``state_material_col``) is below 0.5 in ``obs0``'s last frame.
         Nothing is returned; the loss goes into ``last_loss`` or ``loss_out``.  The reverse sweep reads one edge count per step
         back, so the call synchronises ``steps`` times; a non-finite loss skips the update on the device like ``step``."""
-        self._rollout(engine, obs0, frames, steps, pos_scale, loss_out, state_material_col, True)
+        if self.max_grad_norm is not None:
+            self.zero_grad()
+            self.accumulate_rollout(engine, obs0, frames, steps, pos_scale=pos_scale, state_material_col=state_material_col)
+            return self.apply(loss_out=loss_out)
+        self._rollout(engine, obs0, frames, steps, pos_scale, loss_out, state_material_col, "step")
 
     def evaluate_rollout(self, engine, obs0, frames, steps=None, pos_scale=None, loss_out=None, state_material_col=None):
         """``step_rollout``'s rollout and loss without the update: a validation pass that changes nothing and never synchronises."""
-        self._rollout(engine, obs0, frames, steps, pos_scale, loss_out, state_material_col, False)
+        self._rollout(engine, obs0, frames, steps, pos_scale, loss_out, state_material_col, "evaluate")
 
     def kept_windows(self):
         """[steps + 1, k, N, D]: the windows the last ``step_rollout`` / ``evaluate_rollout`` passed through, a view of its
@@ -271,11 +403,16 @@ class Trainer:
         count = int(np.prod(self._kept))
         return self._rollout_ws[:4 * count].view(torch.float32).view(self._kept)
 
-    def fit_rollout_epoch(self, dataset, engine, steps, starts=None, seed=0, pos_scale=None):
+    def fit_rollout_epoch(self, dataset, engine, steps, starts=None, seed=0, pos_scale=None, batch_size=1, shuffle=False):
         """``step_rollout`` over the samples ``starts`` of ``dataset`` (default: every non-overlapping start, ``steps`` apart, of
         every recording that has ``steps`` frames behind the window), each built by ``dataset.rollout_sample(start, steps, seed,
         stream=start)``.  ``engine.set_scene`` is called whenever the recording changes.  The per-sample losses come back as a
-        float64 numpy array after the last step; a skipped sample's loss is NaN."""
+        float64 numpy array after the last step; a skipped sample's loss is NaN.
+
+        ``batch_size`` > 1: every ``batch_size`` consecutive samples (the last group may be shorter) form a mini-batch with ONE
+        update from the mean of their gradients -- samples of different recordings and sizes may share one: for recordings of
+        different node counts ``engine`` is a dict {node count: RolloutEngine}; the array then holds one loss per update, the mean over its samples.  ``shuffle``: the starts in a
+        permutation seeded by ``seed``.  ``last_epoch_grad_norms`` holds the updates' gradient norms, NaN where none was computed."""
         steps = int(steps)
         if starts is None:
             starts, first = [], 0
@@ -284,15 +421,34 @@ class Trainer:
                 starts += [first + t for t in range(0, last + 1, steps)]
                 first += int(sim.shape[0]) - dataset.k
         starts = [int(i) for i in starts]
+        if shuffle:
+            starts = [starts[i] for i in np.random.default_rng(seed).permutation(len(starts))]
         scene = [None]
 
-        def one(start, loss_out):
+        def sample(start):
             window, frames = dataset.rollout_sample(start, steps, seed=seed, stream=start)
+            eng = engine
+            if isinstance(engine, dict):
+                if int(window.shape[1]) not in engine:
+                    raise ValueError(f"fit_rollout_epoch: no engine for a recording of {int(window.shape[1])} nodes")
+                eng = engine[int(window.shape[1])]
             if scene[0] != dataset.index[start][0]:
-                engine.set_scene(window)
+                eng.set_scene(window)
                 scene[0] = dataset.index[start][0]
-            self.step_rollout(engine, window, frames, steps, pos_scale=pos_scale, loss_out=loss_out)
-        return self._epoch(starts, one)
+            return eng, window, frames
+
+        def one(start, loss_out):
+            eng, window, frames = sample(start)
+            self.step_rollout(eng, window, frames, steps, pos_scale=pos_scale, loss_out=loss_out)
+
+        def accumulate_one(start):
+            eng, window, frames = sample(start)
+            self.accumulate_rollout(eng, window, frames, steps, pos_scale=pos_scale)
+        if int(batch_size) == 1 and self.max_grad_norm is None:
+            losses = self._epoch(starts, one)
+            self.last_epoch_grad_norms = np.full(len(losses), np.nan)
+            return losses
+        return self._epoch_of_mini_batches(starts, batch_size, accumulate_one)
 
     # ------------------------------------------------------------------------------------------ state
     def record(self):

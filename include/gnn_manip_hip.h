@@ -832,6 +832,67 @@ int gm_train_rollout_step(gm_trainer* t, const float* obs0 /*[k,N,D]*/, int64_t 
                           double* loss_out /* device, may be NULL */, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Mini-batches and gradient clipping in the library (train_dyn.py:242 trains at batch_size = 2; clipping is
+ * torch.nn.utils.clip_grad_norm_'s): additions to ABI 7.  gm_train_step and gm_train_rollout_step are one sample and one update per
+ * call; the calls below split that into three phases a caller drives, on one stream:
+ *
+ *     gm_trainer_begin;  S >= 1 times gm_train_step_accumulate / gm_train_rollout_accumulate, in any mix;  gm_trainer_apply.
+ *
+ * gm_trainer_begin clears the trainer's gradient buffer and resets a second device record, the MINI-BATCH's, 48 bytes and separate
+ * from the trainer's 32-byte record (whose layout does not change):
+ *     { int64 samples, int64 bad, double loss_sum, double sumsq, double grad_norm, double scale }
+ * (begin: 0, 0, 0.0, 0.0, NaN, NaN).  gm_trainer_accum_record copies it into the caller's (pinned) host memory, asynchronously.
+ *
+ * gm_train_step_accumulate takes gm_train_step's arguments without lr, gm_train_rollout_accumulate gm_train_rollout_step's without
+ * lr and update; the workspaces are gm_train_step_workspace_bytes' and gm_train_rollout_step_workspace_bytes'.  Each runs exactly
+ * what its parent runs up to, and not including, Adam, WITHOUT clearing the gradients: the backward entry points add the sample's
+ * gradient to the buffer.  One single-thread launch then adds the sample to the record: samples += 1; loss_sum += the sample's
+ * loss, in arrival order; bad += 1 when the parent would have SKIPPED its step (a flagged edge_index, a loss that is not finite).
+ * loss_out (device, may be NULL) receives the sample's own loss.  The refusals are the parent's under the new name, and
+ * "...: no mini-batch begun (gm_trainer_begin)".  A call that FAILS after its argument checks (GM_ERR_DATA from the sweep's edge-count
+ * read, GM_ERR_HIP) leaves the mini-batch UNDEFINED: part of the sample may be in the gradients.  The handle then refuses
+ * accumulate and apply until the caller calls gm_trainer_begin again.  gm_train_step and an updating gm_train_rollout_step clear
+ * the gradients and so end a pending mini-batch the same way; gm_train_rollout_step(update = 0) does not touch it.
+ *
+ * gm_trainer_apply is ONE update from the sum of the S accumulated gradients.  One single-thread launch computes, in float64,
+ *     norm  = sqrt(sumsq) / S                                  -- the norm of the MEAN gradient; sumsq: gm_grad_sumsq of the buffer
+ *     coef  = clipping ? min(1.0, max_grad_norm / (norm + 1e-6)) : 1.0          -- clip_grad_norm_'s formula
+ *     scale = (float)(coef / (double)S)
+ * and leaves norm and (double)scale in the record.  Per element g1 = scale * g, rounded on its own, then ADAM'S ARITHMETIC above
+ * on g1, no operation contracted with another.  With S = 1 and no clipping scale is exactly 1.0f and the update has gm_train_step's
+ * bits.  max_grad_norm <= 0 or +inf: no clipping.  The two launches of the norm are enqueued only when clipping is in force or
+ * grad_norm_out (device, may be NULL) is given -- a non-NULL grad_norm_out REQUESTS the norm and receives it; without either,
+ * grad_norm in the record is NaN and sumsq stays 0.  The update is SKIPPED when bad > 0 or sumsq is not finite: weights, both
+ * moments, steps_applied and the beta powers keep their bits, steps_skipped goes up by one, and loss_out (device, may be NULL)
+ * receives NaN; otherwise loss_out receives loss_sum / S.  One bad sample costs its whole mini-batch: with NaN activations on the
+ * tape 0 * NaN has already reached the buffer, so nothing is taken back out of the sum.  After apply the mini-batch is over:
+ * the next one starts with gm_trainer_begin.  Refused before any device call ("gm_trainer_apply: ...", GM_ERR_INVALID_ARGUMENT): a
+ * null trainer, a NaN lr, a NaN max_grad_norm, no mini-batch begun, no sample accumulated (the handle counts them on the host).
+ *
+ * gm_grad_sumsq is the reduction on its own: sumsq_out[0] (device) = the float64 sum of (double)x[i] * (double)x[i] over `count`
+ * floats -- squared in float64, so that 1e-30f and 1e30f both contribute.  gm_l1_loss's two passes: at most 128 workgroups of 256
+ * threads; a thread walks its 16-byte groups in a fixed stride, then its elements of the scalar tail (count % 4), adding in
+ * float64; a fixed tree inside the workgroup; one partial per workgroup, summed by one workgroup; no atomics: the same bits at every
+ * run.  The trainer's gradient buffer has zero gaps between its tensors, so one call over it is the whole norm.  Refused before any
+ * device call: a null pointer, count < 1, x off a 16-byte or ws off an 8-byte boundary (GM_ERR_INVALID_ARGUMENT); a workspace
+ * below gm_grad_sumsq_workspace_bytes (0 for count < 1) is GM_ERR_WORKSPACE.  The workspace is written before it is read.
+ * ------------------------------------------------------------------------------------------ */
+int gm_trainer_begin(gm_trainer* t, void* stream);
+int gm_train_step_accumulate(gm_trainer* t, const float* nodes, int64_t n_nodes, const float* edge_attr, const int64_t* edge_index,
+                             int64_t n_edges, const float* target, int mask_col, double* loss_out /* device, may be NULL */,
+                             void* ws, size_t ws_bytes, void* stream);
+int gm_train_rollout_accumulate(gm_trainer* t, const float* obs0 /*[k,N,D]*/, int64_t n_nodes, const gm_feature_desc* fdesc,
+                                int max_neighbours, const int32_t* rigid_rank, int64_t n_rigid,
+                                const float* frames /*[steps,N,frame_dim]*/, int frame_dim, int64_t steps, int material_col,
+                                const double* pos_scale /* host [3], may be NULL */, double* loss_out /* device, may be NULL */,
+                                void* ws, size_t ws_bytes, void* stream);
+int gm_trainer_apply(gm_trainer* t, double lr, double max_grad_norm, double* loss_out /* device, may be NULL */,
+                     double* grad_norm_out /* device, may be NULL: non-NULL requests the norm */, void* stream);
+int gm_trainer_accum_record(const gm_trainer* t, void* record_host /* 48 bytes */, void* stream);
+size_t gm_grad_sumsq_workspace_bytes(int64_t count);
+int gm_grad_sumsq(const float* x, int64_t count, double* sumsq_out /* device, 1 */, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Measurement hooks (no reference counterpart; the reference only wraps model.forward in
  * time.time(), examples/optimise_traj.py:99-103).  Per model handle: when enabled, launches made on behalf of THIS
  * model are bracketed with HIP events on their launch stream; other handles and streams are unaffected.

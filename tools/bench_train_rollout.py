@@ -3,14 +3,17 @@ its two forms on the same windows --
 
   python     2e's loop: differentiable_rollout(sweep="library", record=True, params=True) under autograd, the recorded poses by
              boolean indexing, torch's L1 loss, torch.optim.Adam over the module's parameters
-  library    Trainer.step_rollout: gm_train_rollout_step, one call per sample
+  library    Trainer.step_rollout: gm_train_rollout_step, one call per sample; with --accumulate B > 1 or --max-grad-norm X the
+             mini-batch form instead: zero_grad, B x accumulate_rollout, apply (one update per B samples, the norm of the mean
+             gradient clipped to X)
 
 on two synthetic 5000-node recordings rolled side by side as one block-diagonal scene (tools/bench_loader.py's recordings), hidden
 128, 10 message-passing steps.  Both forms run the same reverse sweep (gm_rollout_backward_train) and read one edge count per step
 back; what differs is the host side.  Every variant is warmed, then the variants alternate in one process for --rounds rounds; a
 window is --samples training steps and ends in a synchronise.  Prints one JSON line with every round.
 
-    python tools/bench_train_rollout.py [--n 5000] [--horizons 4,8] [--samples 10] [--rounds 5]
+    python tools/bench_train_rollout.py [--n 5000] [--horizons 4,8] [--samples 10] [--rounds 5] [--accumulate B] [--max-grad-norm X]
+                                        [--variants python,library]
 """
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -32,12 +35,19 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--lr", type=float, default=1e-5)
+    ap.add_argument("--accumulate", type=int, default=1, help="samples per update of the library form")
+    ap.add_argument("--max-grad-norm", type=float, default=None, help="the library form's clip (default: none)")
+    ap.add_argument("--variants", type=str, default="python,library")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_train_rollout: no HIP device (there is no CPU fallback)")
     from gnn_manip_amd import CoffeeDataset, EncProcDecGNN, RolloutEngine, Trainer, scene
     dev = torch.device("cuda:0")
     horizons = [int(v) for v in args.horizons.split(",")]
+    B = args.accumulate
+    if B < 1 or args.samples % B or args.warmup % B:
+        raise SystemExit("bench_train_rollout: --samples and --warmup must be multiples of --accumulate")
+    mini_batches = B > 1 or args.max_grad_norm is not None
     frames_needed = args.k + max(horizons) * (args.samples + 1)
     side = 0.152 * (args.n / 5000.0) ** (1.0 / 3.0) * 0.8             # tools/bench_train.py's density
     sets = [CoffeeDataset.from_recordings([torch.from_numpy(recording(args.n, frames_needed, 300 + s, side)).to(dev)], args.k, 0.015,
@@ -73,6 +83,7 @@ def main():
         l1 = torch.nn.L1Loss(reduction="sum")
         trainer = Trainer(m_lib, lr=args.lr)
         slot = torch.zeros(1, dtype=torch.float64, device=dev)
+        pending = [0]
 
         def python_step(window, frames):
             poses = frames[:, rigid, 2:5].contiguous()
@@ -88,7 +99,19 @@ def main():
             trainer.step_rollout(eng_lib, window, frames, T, loss_out=slot)
             return slot
 
-        variants = {"python": python_step, "library": library_step}
+        def library_mini_batch_step(window, frames):
+            if pending[0] == 0:
+                trainer.zero_grad()
+            trainer.accumulate_rollout(eng_lib, window, frames, T)
+            pending[0] += 1
+            if pending[0] == B:
+                trainer.max_grad_norm = args.max_grad_norm
+                trainer.apply(loss_out=slot)
+                pending[0] = 0
+            return slot
+
+        variants = {"python": python_step, "library": library_mini_batch_step if mini_batches else library_step}
+        variants = {name: variants[name] for name in args.variants.split(",")}
 
         def window(fn, count):
             torch.cuda.synchronize()
@@ -107,11 +130,14 @@ def main():
                 assert np.isfinite(loss), (name, T, loss)
                 rounds[name].append(round(ms, 3))
         results[f"T={T}"] = {name: {"rounds": r, "median": float(np.median(r)), "min": min(r), "max": max(r)} for name, r in rounds.items()}
-        results[f"T={T}"]["edges_last_step"] = eng_py.status()       # the python form's last forward step (the engine's own workspace)
+        if "python" in variants:
+            results[f"T={T}"]["edges_last_step"] = eng_py.status()   # the python form's last forward step (the engine's own workspace)
+    first = results[f"T={horizons[0]}"]
     out = {"metric": "ms per rollout step of a training step on a T-step rollout (forward + loss + reverse sweep + Adam)", "unit": "ms",
-           "value": results[f"T={horizons[0]}"]["library"]["median"], "horizons": results,
+           "value": first["library" if "library" in first else "python"]["median"], "horizons": results,
            "config": {"workload": f"{args.scenes} x N={args.n} side by side, k={args.k}, hidden={args.hidden}, 10 MP steps, L1 on the free rows, Adam",
-                      "samples_per_window": args.samples, "rounds": args.rounds, "warmup_samples": args.warmup, "lr": args.lr},
+                      "samples_per_window": args.samples, "rounds": args.rounds, "warmup_samples": args.warmup, "lr": args.lr,
+                      "accumulate": B, "max_grad_norm": args.max_grad_norm},
            "dtype": "f32", "data": "synthetic"}
     print(json.dumps(out))
 
