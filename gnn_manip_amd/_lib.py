@@ -147,6 +147,10 @@ PROTOTYPES = {
     "gm_trainer_accum_record": (_i32, [_vp, _vp, _vp]),
     "gm_grad_sumsq_workspace_bytes": (_sz, [_i64]),
     "gm_grad_sumsq": (_i32, [_vp, _i64, _vp, _vp, _sz, _vp]),
+    "gm_rank_sum": (_i32, [_vp, _i64, _i32, _i64, _vp, _vp]),
+    "gm_trainer_contribution_bytes": (_sz, [_vp]),
+    "gm_trainer_contribution": (_i32, [_vp, _vp, _sz, _i32, _vp]),
+    "gm_trainer_reduce": (_i32, [_vp, _vp, _i32, _sz, _i64, _vp]),
     "gm_model_profile": (_i32, [_vp, _i32]),
     "gm_model_set_edge_kernel": (_i32, [_vp, _i32]),
     "gm_model_set_node_fusion": (_i32, [_vp, _i32]),

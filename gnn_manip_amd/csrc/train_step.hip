@@ -7,6 +7,8 @@
 // gm_rollout_backward_train (rollout_grad.hip) and the same Adam (restated by tests/train_rollout_cases.py).  Both steps are also
 // available in three phases -- gm_trainer_begin, gm_train_step_accumulate / gm_train_rollout_accumulate per sample, gm_trainer_apply
 // -- for an update from the mean of several samples' gradients, its norm (gm_grad_sumsq) clipped (tests/train_accum_cases.py).
+// Between accumulate and apply several processes may merge their mini-batches: gm_trainer_contribution, the caller's all-gather,
+// gm_trainer_reduce (gm_rank_sum: a float32 sum in rank order; tests/train_dp_cases.py).  No communication library is linked.
 #include <math.h>
 #include <vector>
 #include "common.h"
@@ -512,6 +514,76 @@ __global__ void __launch_bounds__(256) adam_flat_kernel(float* p, float* m, floa
     for (size_t i = (n4 << 2) + t; i < count; i += nt) adam_element(p[i], m[i], v[i], kScaled ? scaled_gradient(g[i], gs) : g[i], k, step, s2);
 }
 
+// ---------------------------------------------------------------------------------------------------------------- data-parallel exchange
+struct ContributionTail {   // the 32 bytes behind a contribution's gradients
+    int64_t samples, bad;
+    double loss_sum;
+    int64_t steps_applied;
+};
+static_assert(sizeof(ContributionTail) == 32, "ContributionTail layout");
+constexpr int kRankSumWorldMax = 64;
+
+// gm_rank_sum: dst[i] = ((src[i] + src[stride + i]) + src[2 * stride + i]) + ..., every add a float32 add of its own, in rank order.
+// An element is summed by one thread from its first rank to its last: nothing depends on the grid.  adam_flat_kernel's walk: 16-byte
+// groups in a grid stride, then the scalar tail.  (Unrolling the rank loop for 4 and 8 ranks was measured and bought nothing.)
+__global__ void __launch_bounds__(256) rank_sum_kernel(const float* src, size_t count, int world, size_t stride, float* dst) {
+    const size_t n4 = count >> 2, s4 = stride >> 2, t = (size_t)blockIdx.x * blockDim.x + threadIdx.x, nt = (size_t)gridDim.x * blockDim.x;
+    const float4* x4 = reinterpret_cast<const float4*>(src);
+    float4* d4 = reinterpret_cast<float4*>(dst);
+    for (size_t i = t; i < n4; i += nt) {
+        float4 a = x4[i];
+        for (int r = 1; r < world; ++r) {
+            const float4 v = x4[(size_t)r * s4 + i];
+            a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
+        }
+        d4[i] = a;
+    }
+    for (size_t i = (n4 << 2) + t; i < count; i += nt) {
+        float a = src[i];
+        for (int r = 1; r < world; ++r) a += src[(size_t)r * stride + i];
+        dst[i] = a;
+    }
+}
+
+int run_rank_sum(const float* src, size_t count, int world, size_t stride, float* dst, hipStream_t s) {
+    const size_t g = cdiv((int64_t)(count / 4 + 1), 256);
+    hipLaunchKernelGGL(rank_sum_kernel, dim3((unsigned)(g > 2048 ? 2048 : g)), dim3(256), 0, s, src, count, world, stride, dst);
+    GM_LAUNCH_CHECK();
+    return GM_OK;
+}
+
+// One thread: the tail of a contribution.  A poisoned one reports no sample and one bad one.
+__global__ void contribution_tail_kernel(const AccumRecord* acc, const TrainerRecord* rec, ContributionTail* tail, int poisoned) {
+    tail->samples = poisoned ? 0 : acc->samples;
+    tail->bad = poisoned ? 1 : acc->bad;
+    tail->loss_sum = poisoned ? 0.0 : acc->loss_sum;
+    tail->steps_applied = rec->steps_applied;
+}
+
+// One thread: the merged mini-batch record of gm_trainer_reduce from the ranks' tails, in rank order.
+__global__ void reduce_record_kernel(const char* contributions, int world, size_t stride_bytes, size_t tail_off, int64_t samples_total,
+                                     AccumRecord* acc) {
+    const ContributionTail* first = reinterpret_cast<const ContributionTail*>(contributions + tail_off);
+    int64_t samples = first->samples, bad = first->bad;
+    double loss_sum = first->loss_sum;
+    bool in_step = true;
+    for (int r = 1; r < world; ++r) {
+        const ContributionTail* tail = reinterpret_cast<const ContributionTail*>(contributions + (size_t)r * stride_bytes + tail_off);
+        samples += tail->samples;
+        bad += tail->bad;
+        loss_sum += tail->loss_sum;
+        if (tail->steps_applied != first->steps_applied) in_step = false;
+    }
+    if (!in_step) bad += 1;                    // replicas out of step
+    if (samples != samples_total) bad += 1;    // not the mini-batch the caller sharded
+    acc->samples = samples;
+    acc->bad = bad;
+    acc->loss_sum = loss_sum;
+    acc->sumsq = 0.0;
+    acc->grad_norm = (double)__builtin_nanf("");
+    acc->scale = (double)__builtin_nanf("");
+}
+
 }  // namespace
 
 struct gm_trainer {
@@ -818,6 +890,70 @@ int gm_grad_sumsq(const float* x, int64_t count, double* sumsq_out, void* ws, si
     GM_REQUIRE(ws_bytes >= need, GM_ERR_WORKSPACE, "%s: workspace %zu < %zu", __func__, ws_bytes, need);
     gm::DevGuard dev_guard(x);
     return run_sumsq(x, (size_t)count, static_cast<double*>(ws), sumsq_out, (hipStream_t)stream);
+}
+
+int gm_rank_sum(const float* src, int64_t count, int world, int64_t stride_floats, float* dst, void* stream) {
+    GM_REQUIRE(src && dst, GM_ERR_INVALID_ARGUMENT, "%s: null pointer", __func__);
+    GM_REQUIRE(count >= 1 && count < ((int64_t)1 << 40), GM_ERR_INVALID_ARGUMENT, "%s: count=%lld out of range", __func__, (long long)count);
+    GM_REQUIRE(world >= 1 && world <= kRankSumWorldMax, GM_ERR_INVALID_ARGUMENT, "%s: world=%d outside 1..%d", __func__, world,
+               kRankSumWorldMax);
+    GM_REQUIRE(stride_floats >= count && (stride_floats & 3) == 0, GM_ERR_INVALID_ARGUMENT,
+               "%s: stride_floats=%lld below count=%lld or no multiple of 4", __func__, (long long)stride_floats, (long long)count);
+    GM_REQUIRE(((uintptr_t)src & 15) == 0 && ((uintptr_t)dst & 15) == 0, GM_ERR_INVALID_ARGUMENT, "%s: src and dst must lie on 16 bytes",
+               __func__);
+    gm::DevGuard dev_guard(src);
+    return run_rank_sum(src, (size_t)count, world, (size_t)stride_floats, dst, (hipStream_t)stream);
+}
+
+size_t gm_trainer_contribution_bytes(const gm_trainer* t) {
+    if (!t) return 0;
+    return t->alloc * sizeof(float) + sizeof(ContributionTail);
+}
+
+int gm_trainer_contribution(gm_trainer* t, void* out_dev, size_t out_bytes, int poisoned, void* stream) {
+    GM_REQUIRE(t, GM_ERR_INVALID_ARGUMENT, "%s: null trainer", __func__);
+    GM_REQUIRE(out_dev, GM_ERR_INVALID_ARGUMENT, "%s: null pointer", __func__);
+    const size_t need = gm_trainer_contribution_bytes(t), grad_bytes = t->alloc * sizeof(float);
+    GM_REQUIRE(out_bytes >= need, GM_ERR_INVALID_ARGUMENT, "%s: out_bytes %zu < %zu", __func__, out_bytes, need);
+    GM_REQUIRE(((uintptr_t)out_dev & 15) == 0, GM_ERR_INVALID_ARGUMENT, "%s: out_dev must lie on 16 bytes", __func__);
+    GM_REQUIRE(poisoned || t->pending >= 0, GM_ERR_INVALID_ARGUMENT, "%s: no mini-batch begun (gm_trainer_begin)", __func__);
+    gm::DevGuard dev_guard(t->grad);
+    hipStream_t s = (hipStream_t)stream;
+    char* out = static_cast<char*>(out_dev);
+    if (poisoned) {
+        GM_HIP_CHECK(hipMemsetAsync(out, 0, grad_bytes, s));
+    } else {
+        GM_HIP_CHECK(hipMemcpyAsync(out, t->grad, grad_bytes, hipMemcpyDeviceToDevice, s));
+    }
+    hipLaunchKernelGGL(contribution_tail_kernel, dim3(1), dim3(1), 0, s, t->acc, t->rec, reinterpret_cast<ContributionTail*>(out + grad_bytes),
+                       poisoned ? 1 : 0);
+    GM_LAUNCH_CHECK();
+    return GM_OK;
+}
+
+int gm_trainer_reduce(gm_trainer* t, const void* contributions_dev, int world, size_t stride_bytes, int64_t samples_total_host,
+                      void* stream) {
+    GM_REQUIRE(t, GM_ERR_INVALID_ARGUMENT, "%s: null trainer", __func__);
+    GM_REQUIRE(contributions_dev, GM_ERR_INVALID_ARGUMENT, "%s: null pointer", __func__);
+    GM_REQUIRE(world >= 1 && world <= kRankSumWorldMax, GM_ERR_INVALID_ARGUMENT, "%s: world=%d outside 1..%d", __func__, world,
+               kRankSumWorldMax);
+    const size_t need = gm_trainer_contribution_bytes(t), grad_bytes = t->alloc * sizeof(float);
+    GM_REQUIRE(stride_bytes >= need && (stride_bytes & 15) == 0, GM_ERR_INVALID_ARGUMENT,
+               "%s: stride_bytes=%zu below %zu or no multiple of 16", __func__, stride_bytes, need);
+    GM_REQUIRE(((uintptr_t)contributions_dev & 15) == 0, GM_ERR_INVALID_ARGUMENT, "%s: contributions_dev must lie on 16 bytes", __func__);
+    GM_REQUIRE(samples_total_host >= 1, GM_ERR_INVALID_ARGUMENT, "%s: samples_total_host=%lld below 1", __func__,
+               (long long)samples_total_host);
+    GM_REQUIRE(t->pending >= 0, GM_ERR_INVALID_ARGUMENT, "%s: no mini-batch begun (gm_trainer_begin)", __func__);
+    gm::DevGuard dev_guard(t->grad);
+    hipStream_t s = (hipStream_t)stream;
+    t->pending = -1;   // until the merged mini-batch stands
+    int rc = run_rank_sum(static_cast<const float*>(contributions_dev), t->alloc, world, stride_bytes / sizeof(float), t->grad, s);
+    if (rc != GM_OK) return rc;
+    hipLaunchKernelGGL(reduce_record_kernel, dim3(1), dim3(1), 0, s, static_cast<const char*>(contributions_dev), world, stride_bytes,
+                       grad_bytes, samples_total_host, t->acc);
+    GM_LAUNCH_CHECK();
+    t->pending = samples_total_host;
+    return GM_OK;
 }
 
 size_t gm_rollout_l1_loss_workspace_bytes(int64_t n_nodes, int64_t steps) {

@@ -288,6 +288,21 @@ class CoffeeTestDataset(CoffeeDataset):
         return self.sample(index)
 
 
+def owned_positions(n_items, shard):
+    """The positions in 0 .. n_items - 1 that ``shard`` = (rank, world, group) owns: of every `group` consecutive positions (the
+    last group may be shorter) the contiguous block ``planner.shard_range(len(group), world, rank)``.  None owns everything.  Over
+    the ranks of a world every position is owned exactly once; a group shorter than the world leaves the last ranks empty."""
+    if shard is None:
+        return list(range(n_items))
+    from .planner import shard_range
+    rank, world, group = shard
+    owned = []
+    for first in range(0, n_items, group):
+        lo, hi = shard_range(min(group, n_items - first), world, rank)
+        owned += range(first + lo, first + hi)
+    return owned
+
+
 class GraphLoader:
     """What train_dyn.py gets from ``torch_geometric.data.DataLoader(dataset, batch_size, shuffle)``: an iterable of
     collated batches.  Everything stays on the dataset's device.
@@ -300,10 +315,22 @@ class GraphLoader:
     batch is handed out: when the next batch is asked for, its edge count has long arrived (it was computed before the
     caller's training step began), nothing waits and the stream is never synchronised.  ``prefetch=0`` waits for its own build.
     A batch whose samples differ in N (recordings of different sizes) is one ragged build, like a batch of equal sizes one
-    equal-sized build.  A batch larger than 64 (GM_TRAIN_BATCH_MAX) is refused by the library."""
+    equal-sized build.  A batch larger than 64 (GM_TRAIN_BATCH_MAX) is refused by the library.
 
-    def __init__(self, dataset, batch_size=2, shuffle=False, seed=None, fused=False, prefetch=1):
+    ``shard=(rank, world, group)``: one of ``world`` data-parallel loaders over the same dataset, seed and shuffle.  Of every
+    ``group`` consecutive batches (a trainer's global mini-batch; the last group may be shorter) it yields only the contiguous block
+    ``planner.shard_range(len(group), world, rank)``; ``len()`` counts those, ``batches_in_all`` all of them.  A batch keeps the
+    order and the noise streams of its GLOBAL position, so the noise a sample sees does not depend on ``world``; the prefetch runs
+    over the owned batches."""
+
+    def __init__(self, dataset, batch_size=2, shuffle=False, seed=None, fused=False, prefetch=1, shard=None):
         self.dataset, self.batch_size, self.shuffle = dataset, batch_size, shuffle
+        self.shard = None
+        if shard is not None:
+            rank, world, group = (int(v) for v in shard)
+            if not (0 <= rank < world and group >= 1):
+                raise ValueError(f"GraphLoader: shard=(rank, world, group)={tuple(shard)}: need 0 <= rank < world and group >= 1")
+            self.shard = (rank, world, group)
         self.rng = np.random.default_rng(seed)
         self.fused, self.prefetch = bool(fused), int(prefetch)
         if self.prefetch not in (0, 1):
@@ -314,21 +341,31 @@ class GraphLoader:
             self._workspaces = ([], [])                  # batch i builds in set i % 2
             self._pinned = _pinned_records(2 * int(batch_size)).view(2, -1, 4)
 
-    def __len__(self):
+    @property
+    def batches_in_all(self):
+        """The batches of an epoch over all shards (``len()`` of the loader without ``shard``)."""
         return (len(self.dataset) + self.batch_size - 1) // self.batch_size
+
+    def owned_batches(self):
+        """The positions, among an epoch's ``batches_in_all`` batches, of those this loader yields: all of them without ``shard``."""
+        return owned_positions(self.batches_in_all, self.shard)
+
+    def __len__(self):
+        return self.batches_in_all if self.shard is None else len(self.owned_batches())
 
     def __iter__(self):
         order = self.rng.permutation(len(self.dataset)) if self.shuffle else np.arange(len(self.dataset))
         if self.fused:
             yield from self._iter_fused(order)
             return
-        for b in range(0, len(order), self.batch_size):
+        for j in self.owned_batches():
+            b = j * self.batch_size
             yield collate_graphs([self.dataset[int(i)] for i in order[b:b + self.batch_size]])
 
     def _iter_fused(self, order):
         base = self._samples_begun
         self._samples_begun += len(order)
-        starts = list(range(0, len(order), self.batch_size))
+        starts = [j * self.batch_size for j in self.owned_batches()]
 
         def queue(j):
             b = starts[j]

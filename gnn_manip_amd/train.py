@@ -62,6 +62,37 @@ def parse_adam_state_dict(sd, shapes):
     return [state[i]["exp_avg"] for i in range(len(shapes))], [state[i]["exp_avg_sq"] for i in range(len(shapes))], steps.pop(), g
 
 
+def exchange_bytes(local, gathered, group=None, staging=None):
+    """The byte exchange of data-parallel training, and nothing else (no library call): every rank's ``local`` [bytes] arrives as
+    row r of ``gathered`` [world, bytes] on every rank, in rank order.  Device tensors go through ``all_gather_into_tensor`` (RCCL):
+    stream-ordered, nothing waits on the host.  Host tensors go through ``all_gather`` (gloo).  ``staging`` = (pinned [bytes],
+    pinned [world, bytes]): device tensors are staged through these for a host collective -- the planner's rehearsal pattern --
+    which synchronises."""
+    import torch.distributed as dist
+    if staging is not None:
+        host_local, host_all = staging
+        host_local.copy_(local)                                      # waits for the stream: the payload is complete
+        dist.all_gather(list(host_all.unbind(0)), host_local, group=group)
+        gathered.copy_(host_all, non_blocking=True)
+    elif local.is_cuda:
+        dist.all_gather_into_tensor(gathered.view(-1), local, group=group)
+    else:
+        dist.all_gather(list(gathered.unbind(0)), local, group=group)
+    return gathered
+
+
+class _Replicas:
+    """What ``Trainer.distribute`` leaves on a trainer: the group, this rank in it, and the exchange buffers, allocated once."""
+
+    def __init__(self, group, world, rank, nbytes, device, host):
+        self.group, self.world, self.rank, self.host = group, world, rank, host
+        self.local = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        self.gathered = torch.empty((world, nbytes), dtype=torch.uint8, device=device)
+        self.staging = None
+        if host:
+            self.staging = (torch.empty(nbytes, dtype=torch.uint8).pin_memory(), torch.empty((world, nbytes), dtype=torch.uint8).pin_memory())
+
+
 class _TrainerHandle:
     """A gm_trainer* and the gm_model it updates: the trainer is destroyed first."""
 
@@ -99,6 +130,12 @@ class Trainer:
     ``max_grad_norm`` set, ``step`` and ``step_rollout`` are those three calls on one sample; with None they are the single
     library call.  One skipped sample skips its whole mini-batch.  ``fit_epoch(loader, accumulate=B)`` / ``fit_rollout_epoch(..., batch_size=B)`` run epochs
     of such mini-batches.  The clip is not part of ``state_dict()``.
+
+    SEVERAL GPUS.  ``distribute()`` under ``torch.distributed`` makes the trainer one of ``world`` replicas:
+    ``apply(samples_total=S)`` then merges the ranks' mini-batches before the update -- ``contribution()``, one all-gather,
+    ``reduce()``: a float32 sum of the gradients in RANK ORDER, so every rank applies the same bits whatever the collective does --
+    and ``fit_epoch`` / ``fit_rollout_epoch`` shard every mini-batch over the ranks.  A trainer that is never distributed runs
+    exactly what it ran before.
 
     Hidden sizes 64 / 128 / 256 only.  A module of another hidden size trains zero-padded through ``model.forward`` under autograd
     with a torch optimiser (``EncProcDecGNN._padded_training``): that path stays with autograd."""
@@ -139,6 +176,7 @@ class Trainer:
         self._pin_losses = None
         self._grad_norm = torch.full((1,), float("nan"), dtype=torch.float64, device=self.device)
         self.last_epoch_grad_norms = None
+        self._dp, self._dp_error = None, None       # distribute(): the replicas' exchange; a sample's GMError kept until apply
 
     # ------------------------------------------------------------------------------------------ one batch
     @property
@@ -168,6 +206,7 @@ class Trainer:
 
     def step(self, x, edge_attr=None, edge_index=None, y=None, loss_out=None):
         """One training step on a batch (four tensors, or a ``GraphData``): gm_train_step.  Nothing is returned and nothing waits."""
+        self._not_distributed("step")
         if self.max_grad_norm is not None:
             self.zero_grad()
             self.accumulate(x, edge_attr, edge_index, y)
@@ -204,13 +243,23 @@ class Trainer:
     def zero_grad(self):
         """Starts a mini-batch: gm_trainer_begin clears the gradients and the mini-batch's record."""
         check(lib().gm_trainer_begin(self._h, current_stream(self.device)))
+        self._dp_error = None
 
     def _accumulated(self, call):
+        if self._dp_error is not None:
+            return                    # a distributed trainer whose mini-batch has failed already: it will be skipped as a whole
         try:
             call()
-        except GMError:
+        except GMError as error:
             self.zero_grad()          # the failed sample may be partly in the gradients: the pending mini-batch is dropped
-            raise
+            if self._dp is None:
+                raise
+            self._dp_error = error    # the peers wait in apply's exchange: the error is raised there, after it
+
+    def _not_distributed(self, what):
+        if self._dp is not None:
+            raise ValueError(f"Trainer.{what} updates this replica alone: on a distributed trainer use zero_grad / accumulate / "
+                             "apply(samples_total=), or the epoch methods")
 
     def accumulate(self, x, edge_attr=None, edge_index=None, y=None, loss_out=None):
         """Adds a batch's gradient to the pending mini-batch (``step``'s arguments and checks): gm_train_step_accumulate.  The
@@ -223,18 +272,108 @@ class Trainer:
         gm_train_rollout_accumulate.  Samples of different scenes and sizes may share a mini-batch."""
         self._accumulated(lambda: self._rollout(engine, obs0, frames, steps, pos_scale, loss_out, state_material_col, "accumulate"))
 
-    def apply(self, loss_out=None, norm_out=None, want_norm=False):
+    def apply(self, loss_out=None, norm_out=None, want_norm=False, samples_total=None):
         """One Adam update from the MEAN of the accumulated gradients, clipped to ``max_grad_norm`` (None, <= 0 or inf: no clip)
         by ``clip_grad_norm_``'s formula: gm_trainer_apply.  The mean of the samples' losses goes into ``last_loss`` or
         ``loss_out``.  The gradient norm is computed when the clip is in force, ``want_norm`` is set or ``norm_out`` (one float64
         element on the device) is given, and goes into ``norm_out`` or ``last_grad_norm``.  A mini-batch with a skipped sample, or
-        whose gradient norm is not finite, changes nothing: ``record()`` counts it, its loss is NaN."""
+        whose gradient norm is not finite, changes nothing: ``record()`` counts it, its loss is NaN.
+
+        On a distributed trainer every rank calls it, with ``samples_total`` the samples of the mini-batch over ALL ranks (a rank
+        may hold none): the ranks' gradients and records are merged first (``contribution``, one all-gather, ``reduce``), and the
+        update, its loss and its norm are the global ones, the same bits on every rank.  A sample that raised ``GMError`` on this
+        rank skips the update on every rank; the error is raised here, after the exchange."""
         slot = self._slot(loss_out)
         norm = None
         if self._clipping() or want_norm or norm_out is not None:
             norm = self._grad_norm if norm_out is None else self._slot(norm_out)
         mg = 0.0 if self.max_grad_norm is None else float(self.max_grad_norm)
+        error = None
+        if self._dp is not None:
+            if samples_total is None or int(samples_total) < 1:
+                raise ValueError("apply on a distributed trainer needs samples_total, the mini-batch's samples over all ranks")
+            error, self._dp_error = self._dp_error, None
+            local = self.contribution(out=self._dp.local, poisoned=error is not None)
+            exchange_bytes(local, self._dp.gathered, self._dp.group, self._dp.staging)
+            self.reduce(self._dp.gathered, samples_total)
+        elif samples_total is not None:
+            raise ValueError("samples_total belongs to a distributed trainer (distribute())")
         check(lib().gm_trainer_apply(self._h, self.lr, mg, ptr(slot), ptr(norm), current_stream(self.device)))
+        if error is not None:
+            raise error
+
+    # ------------------------------------------------------------------------------------------ several replicas
+    def contribution_bytes(self):
+        """The bytes of one rank's contribution: the flat gradient buffer and the 32-byte tail (gm_trainer_contribution_bytes)."""
+        return int(lib().gm_trainer_contribution_bytes(self._h))
+
+    def contribution(self, out=None, poisoned=False):
+        """What this rank brings to a shared mini-batch, as a ``uint8`` device tensor (``out``, or a new one): the accumulated
+        gradients and {samples, bad, loss_sum, steps_applied} (gm_trainer_contribution).  ``poisoned``: zeros and one bad sample,
+        which skips the update on every rank."""
+        need = self.contribution_bytes()
+        if out is None:
+            out = torch.empty(need, dtype=torch.uint8, device=self.device)
+        if out.dtype != torch.uint8 or out.device != self.device or out.dim() != 1 or out.numel() < need or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous uint8 tensor of at least {need} bytes on the trainer's device")
+        check(lib().gm_trainer_contribution(self._h, ptr(out), out.numel(), int(bool(poisoned)), current_stream(self.device)))
+        return out
+
+    def reduce(self, gathered, samples_total):
+        """Merges the ranks' contributions, ``gathered`` [world, bytes] ``uint8`` in rank order, into this trainer's pending
+        mini-batch: the gradients summed in float32 in rank order, the records merged (gm_trainer_reduce).  ``samples_total`` is
+        the global sample count; ``apply()`` then updates from the merged mini-batch."""
+        if gathered.dtype != torch.uint8 or gathered.device != self.device or gathered.dim() != 2 or not gathered.is_contiguous():
+            raise ValueError("gathered must be a contiguous [world, bytes] uint8 tensor on the trainer's device")
+        check(lib().gm_trainer_reduce(self._h, ptr(gathered), int(gathered.shape[0]), int(gathered.shape[1]), int(samples_total),
+                                      current_stream(self.device)))
+
+    def distribute(self, group=None, collective_device=None, src=0):
+        """Makes this trainer one replica of ``torch.distributed``'s ``group`` (None: the default group).  Rank ``src``'s weights,
+        both moments and step count are broadcast to the group, the exchange buffers are allocated once, and ``apply`` from now on
+        merges the ranks' mini-batches before it updates.  ``collective_device=None``: the payload stays on the device
+        (``all_gather_into_tensor`` on RCCL, stream-ordered; the trainer adds no host synchronisation, an epoch keeps its single
+        one).  ``collective_device="cpu"``: staged through pinned host memory for gloo, which synchronises at every update -- the
+        planner's rehearsal pattern, for several ranks on one GPU."""
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()):
+            raise RuntimeError("Trainer.distribute: torch.distributed is not initialised")
+        host = collective_device is not None and torch.device(collective_device).type == "cpu"
+        world, rank = dist.get_world_size(group), dist.get_rank(group)
+        steps = torch.tensor([self.record()["steps_applied"]], dtype=torch.int64, device="cpu" if host else self.device)
+        dist.broadcast(steps, src=src, group=group)
+        state = {}
+        for what in (PARAMS, EXP_AVG, EXP_AVG_SQ):
+            flat = torch.cat([t.reshape(-1) for t in self.export(what)])
+            payload = flat.cpu() if host else flat
+            dist.broadcast(payload, src=src, group=group)
+            state[what] = [t.view(s) for t, s in zip(payload.to(self.device).split([int(np.prod(s)) for s in self._shapes]), self._shapes)]
+        if dist.get_rank() != src:
+            self._import(EXP_AVG, state[EXP_AVG], int(steps[0]))
+            self._import(EXP_AVG_SQ, state[EXP_AVG_SQ])
+            self._import(PARAMS, state[PARAMS])
+        self._dp = _Replicas(group, world, rank, self.contribution_bytes(), self.device, host)
+        self._dp_error = None
+        return self
+
+    def replicas_in_step(self):
+        """True when every replica of the group holds the same weights and step count: a float64 gm_grad_sumsq of the exported
+        weights and ``steps_applied``, compared bit for bit across the ranks.  Synchronises; for use between epochs."""
+        if self._dp is None:
+            raise ValueError("replicas_in_step: the trainer is not distributed")
+        L = lib()
+        flat = torch.cat([t.reshape(-1) for t in self.export(PARAMS)])
+        mine = torch.empty(2, dtype=torch.float64, device=self.device)
+        mine[1] = float(self.record()["steps_applied"])
+        ws = _ws(L.gm_grad_sumsq_workspace_bytes(flat.numel()), self.device)
+        check(L.gm_grad_sumsq(ptr(flat), flat.numel(), ptr(mine), ptr(ws), ws.numel(), current_stream(self.device)))
+        local = mine.view(torch.uint8)
+        everyone = torch.empty((self._dp.world, local.numel()), dtype=torch.uint8, device=self.device)
+        staging = None
+        if self._dp.host:
+            staging = (torch.empty_like(local, device="cpu").pin_memory(), torch.empty_like(everyone, device="cpu").pin_memory())
+        exchange_bytes(local, everyone, self._dp.group, staging)
+        return bool((everyone.cpu() == everyone[0].cpu()).all())
 
     def accum_record(self):
         """{'samples', 'bad', 'loss_sum', 'sumsq', 'grad_norm', 'scale'} of the mini-batch's device record (synchronises)."""
@@ -307,6 +446,41 @@ class Trainer:
                 pending = 0
         if pending:
             update()
+        return self._updates_of_epoch(slots, updates)
+
+    def _epoch_of_shared_mini_batches(self, items, size, accumulate_one, total=None):
+        """``_epoch_of_mini_batches`` on a distributed trainer: `size` is the GLOBAL mini-batch.  Of every group of `size`
+        consecutive items this rank accumulates the contiguous block ``planner.shard_range(len(group), world, rank)`` and calls
+        ``apply`` even when that block is empty.  `items` is the global sequence, of which the other ranks' items are passed over
+        unused -- or, with `total` (the global item count), an iterable of this rank's items alone, in order.  The losses and norms
+        are the global ones, identical on all ranks.  An item that raises ``GMError`` poisons its mini-batch on every rank; the
+        error is raised after that mini-batch's exchange, and the epoch ends there ON THIS RANK."""
+        from .planner import shard_range
+        size = int(size)
+        if size < 1:
+            raise ValueError(f"a mini-batch holds at least one sample, got {size}")
+        own_only = total is not None
+        total = int(total) if own_only else len(items)
+        slots = torch.full((2, max(-(-total // size), 1)), float("nan"), dtype=torch.float64, device=self.device)   # losses, norms
+        with_norm = self._clipping()
+        it = iter(items)
+        updates = 0
+        for first in range(0, total, size):
+            count = min(size, total - first)
+            lo, hi = shard_range(count, self._dp.world, self._dp.rank)
+            self.zero_grad()
+            for j in range(count):
+                if lo <= j < hi:
+                    accumulate_one(next(it))
+                elif not own_only:
+                    next(it)
+            self.apply(loss_out=slots[0, updates:updates + 1], norm_out=slots[1, updates:updates + 1] if with_norm else None,
+                       samples_total=count)
+            updates += 1
+        return self._updates_of_epoch(slots, updates)
+
+    def _updates_of_epoch(self, slots, updates):
+        """The losses of an epoch's updates on the host, their norms in ``last_epoch_grad_norms``: the epoch's one synchronisation."""
         if self._pin_losses is None or self._pin_losses.numel() < slots.numel():
             self._pin_losses = torch.empty(slots.numel(), dtype=torch.float64).pin_memory()
         host = self._pin_losses[:slots.numel()].view(slots.shape)
@@ -322,7 +496,19 @@ class Trainer:
         ``accumulate`` > 1: every ``accumulate`` consecutive batches (the last group may be shorter) form a mini-batch with ONE
         update from the mean of their gradients (``zero_grad`` / ``accumulate`` / ``apply``); the array then holds one loss per
         update, the mean over its batches.  ``last_epoch_grad_norms`` holds the updates' gradient norms, NaN where none was
-        computed (no clip in force)."""
+        computed (no clip in force).
+
+        On a distributed trainer ``accumulate`` is the GLOBAL mini-batch, shared out over the ranks block by block; `loader` is a
+        ``GraphLoader(..., shard=(rank, world, accumulate))``, which builds this rank's batches only, or any sequence of all the
+        batches.  The losses and norms are the global ones, the same on every rank."""
+        if self._dp is not None:
+            shard = getattr(loader, "shard", None)
+            if shard is None:
+                return self._epoch_of_shared_mini_batches(loader, accumulate, self.accumulate)
+            if tuple(int(v) for v in shard) != (self._dp.rank, self._dp.world, int(accumulate)):
+                raise ValueError(f"fit_epoch: the loader's shard {tuple(shard)} is not (rank, world, accumulate) = "
+                                 f"{(self._dp.rank, self._dp.world, int(accumulate))}")
+            return self._epoch_of_shared_mini_batches(loader, accumulate, self.accumulate, total=loader.batches_in_all)
         if int(accumulate) == 1 and self.max_grad_norm is None:
             losses = self._epoch(loader, self.step)
             self.last_epoch_grad_norms = np.full(len(losses), np.nan)
@@ -387,6 +573,7 @@ class Trainer:
         the rows whose STATE material column (the engine's, or ``state_material_col``) is below 0.5 in ``obs0``'s last frame.
         Nothing is returned; the loss goes into ``last_loss`` or ``loss_out``.  The reverse sweep reads one edge count per step
         back, so the call synchronises ``steps`` times; a non-finite loss skips the update on the device like ``step``."""
+        self._not_distributed("step_rollout")
         if self.max_grad_norm is not None:
             self.zero_grad()
             self.accumulate_rollout(engine, obs0, frames, steps, pos_scale=pos_scale, state_material_col=state_material_col)
@@ -412,7 +599,10 @@ class Trainer:
         ``batch_size`` > 1: every ``batch_size`` consecutive samples (the last group may be shorter) form a mini-batch with ONE
         update from the mean of their gradients -- samples of different recordings and sizes may share one: for recordings of
         different node counts ``engine`` is a dict {node count: RolloutEngine}; the array then holds one loss per update, the mean over its samples.  ``shuffle``: the starts in a
-        permutation seeded by ``seed``.  ``last_epoch_grad_norms`` holds the updates' gradient norms, NaN where none was computed."""
+        permutation seeded by ``seed``.  ``last_epoch_grad_norms`` holds the updates' gradient norms, NaN where none was computed.
+
+        On a distributed trainer every rank passes the same ``starts`` and ``seed``; ``batch_size`` is the GLOBAL mini-batch, of
+        which this rank runs its contiguous block; the losses and norms are the global ones, the same on every rank."""
         steps = int(steps)
         if starts is None:
             starts, first = [], 0
@@ -444,6 +634,8 @@ class Trainer:
         def accumulate_one(start):
             eng, window, frames = sample(start)
             self.accumulate_rollout(eng, window, frames, steps, pos_scale=pos_scale)
+        if self._dp is not None:
+            return self._epoch_of_shared_mini_batches(starts, batch_size, accumulate_one)
         if int(batch_size) == 1 and self.max_grad_norm is None:
             losses = self._epoch(starts, one)
             self.last_epoch_grad_norms = np.full(len(losses), np.nan)

@@ -893,6 +893,55 @@ size_t gm_grad_sumsq_workspace_bytes(int64_t count);
 int gm_grad_sumsq(const float* x, int64_t count, double* sumsq_out /* device, 1 */, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Data-parallel training: several processes ("ranks"), each with a trainer over the same weights, share a mini-batch (additions to
+ * ABI 7; no struct changes).  Every rank runs gm_trainer_begin and accumulates ITS samples; then, between accumulate and apply,
+ *
+ *     gm_trainer_contribution;  the caller's all-gather of the ranks' contributions;  gm_trainer_reduce;  gm_trainer_apply.
+ *
+ * The library links no communication library: it writes one contiguous device buffer per rank and reads `world` of them.  Who moves
+ * the bytes (RCCL, MPI, gloo through host memory) is the caller's choice.  Every rank reduces the same bytes in the same order and
+ * so applies the same update, bit for bit, whatever the collective does inside.
+ *
+ * A CONTRIBUTION is gm_trainer_contribution_bytes(t) bytes (0 for a null trainer): the trainer's flat gradient buffer -- its floats
+ * in gm_model_create's tensor order, each tensor on a 16-byte boundary with zeros in the gaps, zeros up to a multiple of 16 bytes
+ * -- and behind it a 32-byte tail
+ *     { int64 samples, int64 bad, double loss_sum, int64 steps_applied }
+ * whose first three fields are the mini-batch record's and whose fourth is the trainer record's.  gm_trainer_contribution writes
+ * it to out_dev: one device-to-device copy and one single-thread launch.  It needs a begun mini-batch and changes nothing of it;
+ * zero accumulated samples are allowed (a rank that owns nothing of a short last mini-batch contributes zeros).  poisoned != 0
+ * writes all-zero gradients and the tail { 0, 1, 0.0, steps_applied } instead, begun mini-batch or not: what a rank sends after one
+ * of its samples failed on the host, so that no peer waits for it and every rank skips the update.  Refused before any device call
+ * ("gm_trainer_contribution: ...", GM_ERR_INVALID_ARGUMENT): a null trainer or pointer, out_bytes below the contribution's, out_dev
+ * off a 16-byte boundary, no mini-batch begun (unless poisoned).
+ *
+ * gm_trainer_reduce reads `world` contributions, rank r's at contributions_dev + r * stride_bytes, all ranks in the same order.
+ * gm_rank_sum adds their gradient parts into the trainer's own gradient buffer (which the contributions must not overlap), then one
+ * single-thread launch sets the mini-batch record: samples and bad are the integer sums; loss_sum is rank 0's plus rank 1's plus
+ * ..., float64 adds in rank order; sumsq, grad_norm and scale are as gm_trainer_begin leaves them (0.0, NaN, NaN).  bad goes up by
+ * one more when the ranks' steps_applied are not all equal (replicas out of step), and by one more when the summed samples differ
+ * from samples_total_host, the global sample count the caller knows from its sharding.  samples_total_host becomes the handle's
+ * host-side count, so that gm_trainer_apply accepts the mini-batch without a read-back; apply then runs unchanged on the merged
+ * record -- S, the norm, the clip, the skip rule, Adam -- so a bad sample on any rank skips the update on every rank.  With
+ * world == 1 the gradient and the record keep their bits: contribution, reduce, apply is apply.  Refused before any device call
+ * ("gm_trainer_reduce: ...", GM_ERR_INVALID_ARGUMENT): a null trainer or pointer, world outside 1..64, stride_bytes below
+ * gm_trainer_contribution_bytes or no multiple of 16, contributions_dev off a 16-byte boundary, samples_total_host < 1, no
+ * mini-batch begun.
+ *
+ * gm_rank_sum is the reduction on its own:  dst[i] = ((src[i] + src[stride_floats + i]) + src[2 * stride_floats + i]) + ...  over
+ * `world` rows of `count` floats, every add a float32 add rounded on its own, strictly in rank order; world == 1 copies the bits.
+ * One thread sums an element from its first rank to its last: no atomics, nothing depends on the grid, the same bits at every run.
+ * Adam's flat walk: 16-byte groups in a grid stride over at most 2048 workgroups of 256 threads, then the scalar tail (count % 4).
+ * It moves world reads and one write per element.  dst must not overlap src.  Refused before any device call ("gm_rank_sum: ...",
+ * GM_ERR_INVALID_ARGUMENT): a null pointer, count < 1, world outside 1..64, stride_floats below count or no multiple of 4, src or
+ * dst off a 16-byte boundary.
+ * ------------------------------------------------------------------------------------------ */
+int gm_rank_sum(const float* src, int64_t count, int world, int64_t stride_floats, float* dst, void* stream);
+size_t gm_trainer_contribution_bytes(const gm_trainer* t);
+int gm_trainer_contribution(gm_trainer* t, void* out_dev, size_t out_bytes, int poisoned, void* stream);
+int gm_trainer_reduce(gm_trainer* t, const void* contributions_dev, int world, size_t stride_bytes, int64_t samples_total_host,
+                      void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Measurement hooks (no reference counterpart; the reference only wraps model.forward in
  * time.time(), examples/optimise_traj.py:99-103).  Per model handle: when enabled, launches made on behalf of THIS
  * model are bracketed with HIP events on their launch stream; other handles and streams are unaffected.
