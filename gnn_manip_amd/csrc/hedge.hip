@@ -1396,19 +1396,24 @@ constexpr int H3_PACK_THREADS = 1024;
 __global__ void __launch_bounds__(H3_PACK_THREADS) pack_h3_kernel(PackH3Jobs J) {
     __shared__ float red[H3_PACK_THREADS];
     __shared__ float tsc[4];
-    __shared__ float cmean[H + 1];   // Linear 3: mean of every column of W3 over the output features, then the mean of b3
+    __shared__ float cmean[H + 1];   // Linear 3: mean of every column of W3 over the output features, then the mean of b3 --
+    __shared__ float coarse[H + 1];  // of what is left once the coarse mean is taken off (mlp.h; pack_hm_kernel says why)
     const int job = blockIdx.x, tid = threadIdx.x;
     const float* Wl[3] = {J.W1[job], J.W2[job], J.W3[job]};
     // LayerNorm subtracts the mean over the output features of Linear 3; with W3' = W3 - 1 mean_rows(W3), b3' = b3 - mean(b3)
     // the outputs are z - mean(z) exactly, so the kernel needs no mean: variance = mean square, x_hat = z' / sigma.
     if (tid < H) {
+        const float c = coarse_mean_of(J.W3[job] + tid, (size_t)H, H);
         float a = 0.f;
-        for (int o = 0; o < H; ++o) a += J.W3[job][(size_t)o * H + tid];
+        for (int o = 0; o < H; ++o) a += (float)((double)J.W3[job][(size_t)o * H + tid] - (double)c);
         cmean[tid] = a * (1.0f / H);
+        coarse[tid] = c;
     } else if (tid == H) {
+        const float c = coarse_mean_of(J.b3[job], 1, H);
         float a = 0.f;
-        for (int o = 0; o < H; ++o) a += J.b3[job][o];
+        for (int o = 0; o < H; ++o) a += (float)((double)J.b3[job][o] - (double)c);
         cmean[H] = a * (1.0f / H);
+        coarse[H] = c;
     }
     __syncthreads();
     const int k1 = J.enc_k1[job];          // > 0: encoder image (Linear 1 takes k1 raw features)
@@ -1431,7 +1436,7 @@ __global__ void __launch_bounds__(H3_PACK_THREADS) pack_h3_kernel(PackH3Jobs J) 
         for (int i = tid; i < H * cols; i += H3_PACK_THREADS) {
             const int col = i % cols;
             float v = Wl[l][(size_t)(i / cols) * ld[l] + (l == 0 ? 0 : c0[l]) + col];
-            if (l == 2) v -= cmean[col];
+            if (l == 2) v = (float)((double)v - (double)coarse[col]) - cmean[col];
             ss = fmaf(v, v, ss);
             if (l != 0 || enc || (col >= c0[0] && col < c0[0] + H)) wm = fmaxf(wm, fabsf(v));   // the packed block
         }
@@ -1453,7 +1458,7 @@ __global__ void __launch_bounds__(H3_PACK_THREADS) pack_h3_kernel(PackH3Jobs J) 
             const float wmax = red[0];
             float bs = 0.f, bmax = 0.f;
             for (int o = 0; o < H; ++o) {
-                const float bv = bl[l][o] - (l == 2 ? cmean[H] : 0.f);
+                const float bv = l == 2 ? (float)((double)bl[l][o] - (double)coarse[H]) - cmean[H] : bl[l][o];
                 bs = fmaf(bv, bv, bs);
                 bmax = fmaxf(bmax, fabsf(bv));
             }
@@ -1489,7 +1494,7 @@ __global__ void __launch_bounds__(H3_PACK_THREADS) pack_h3_kernel(PackH3Jobs J) 
     for (int i = tid; i < H; i += H3_PACK_THREADS) {
         vec[4 * H + i] = J.b1[job][i] * T1;
         vec[i] = J.b2[job][i] * T2;
-        vec[H + i] = (J.b3[job][i] - cmean[H]) * T3;
+        vec[H + i] = ((float)((double)J.b3[job][i] - (double)coarse[H]) - cmean[H]) * T3;
         vec[2 * H + i] = J.gamma[job][i];
         vec[3 * H + i] = J.beta[job][i];
     }
@@ -1500,7 +1505,8 @@ __global__ void __launch_bounds__(H3_PACK_THREADS) pack_h3_kernel(PackH3Jobs J) 
         const int i = lane & 31, kg = lane >> 5;
         const int kcol = 16 * ks + 8 * (j >> 2) + 4 * kg + (j & 3);
         const bool pad = l == 0 && enc && kcol >= k1;   // the encoder's first Linear: zero beyond its k1 inputs
-        const float v = pad ? 0.f : (Wl[l][(size_t)(32 * w + i) * ld[l] + c0[l] + kcol] - (l == 2 ? cmean[kcol] : 0.f)) * tsc[l];
+        const float wv = pad ? 0.f : Wl[l][(size_t)(32 * w + i) * ld[l] + c0[l] + kcol];
+        const float v = (l == 2 ? (float)((double)wv - (double)coarse[kcol]) - cmean[kcol] : wv) * tsc[l];
         const _Float16 h = (_Float16)v;
         const _Float16 lo = (_Float16)(v - (float)h);
         const size_t base = ((((size_t)(l * 4 + w) * 8 + ks) * 2) * 64 + lane) * 8 + j;

@@ -916,12 +916,32 @@ __device__ __forceinline__ float hm_value(const PackHmJob& j, int o, int k) {
     return j.W[(size_t)ro * j.ld + j.col0[os + is] + rk];
 }
 
+// coarse mean (mlp.h) of column k of a centred Linear over its valid outputs
+__device__ __forceinline__ float hm_coarse_col(const PackHmJob& j, int k) {
+    if (j.out_valid <= 0) return 0.f;
+    double m = 0.0;
+    for (int o = 0; o < j.out_valid; ++o) m += (double)hm_value(j, o, k);
+    m /= (double)j.out_valid;
+    float s = 0.f;
+    for (int o = 0; o < j.out_valid; ++o) s = fmaxf(s, fabsf((float)((double)hm_value(j, o, k) - m)));
+    return coarse_mean(m, s);
+}
+
 // phase 1: statistics of every Linear -> stats[4 job ..]: gain ||W||_F / sqrt(out) / sqrt(2) over the columns that make its
 // pre-activation, rms and maximum of the bias, maximum |W| of the packed block.  Also resets the job's row-scale cap slot.
 __global__ void __launch_bounds__(HM_PACK_THREADS) pack_hm_stats_kernel(PackHmJobs J, float* __restrict__ stats) {
     const PackHmJob& j = J.job[blockIdx.x];
     __shared__ float red[HM_PACK_THREADS];
     const int tid = threadIdx.x;
+    // a centred Linear's statistics are those of what is packed once the coarse mean is off (0 for most weights: nothing changes)
+    __shared__ float coarse[513];
+    for (int k = tid; k < 513; k += HM_PACK_THREADS) {
+        float c = 0.f;
+        if (j.center && k < j.k_pad && k < 512) c = hm_coarse_col(j, k);
+        else if (j.center && k == 512 && j.bias && j.bias_n > 0) c = coarse_mean_of(j.bias, 1, j.bias_n);
+        coarse[k] = c;
+    }
+    __syncthreads();
     float ss = 0.f, wm = 0.f;
     if (j.gain_cols > 0) {
         for (int i = tid; i < j.out_valid * j.gain_cols; i += HM_PACK_THREADS) {
@@ -930,7 +950,9 @@ __global__ void __launch_bounds__(HM_PACK_THREADS) pack_hm_stats_kernel(PackHmJo
         }
     }
     for (int i = tid; i < j.out_pad * j.k_pad; i += HM_PACK_THREADS) {
-        const float v = hm_value(j, i / j.k_pad, i % j.k_pad);
+        const int o = i / j.k_pad, k = i % j.k_pad;
+        const bool valid = (o % j.out_seg) < j.out_valid && (k % j.k_seg) < j.k_valid;
+        const float v = (float)((double)hm_value(j, o, k) - (valid ? (double)coarse[k < 512 ? k : 0] : 0.0));
         if (j.gain_cols <= 0) ss = fmaf(v, v, ss);
         wm = fmaxf(wm, fabsf(v));
     }
@@ -949,7 +971,11 @@ __global__ void __launch_bounds__(HM_PACK_THREADS) pack_hm_stats_kernel(PackHmJo
     wm = reduce(wm, true);
     if (tid == 0) {
         float bs = 0.f, bm = 0.f;
-        if (j.bias) for (int o = 0; o < j.bias_n; ++o) { bs = fmaf(j.bias[o], j.bias[o], bs); bm = fmaxf(bm, fabsf(j.bias[o])); }
+        if (j.bias) for (int o = 0; o < j.bias_n; ++o) {
+            const float b = (float)((double)j.bias[o] - (double)coarse[512]);
+            bs = fmaf(b, b, bs);
+            bm = fmaxf(bm, fabsf(b));
+        }
         const int outs = j.out_valid * (j.out_pad / j.out_seg);
         float* st = stats + 4 * (J.first + blockIdx.x);
         st[0] = sqrtf(ss / (float)(outs > 0 ? outs : 1) * 0.5f);
@@ -1017,28 +1043,36 @@ __global__ void __launch_bounds__(HM_PACK_THREADS) pack_hm_kernel(PackHmJobs J, 
         sc[0] = t;
         sc[1] = U;
     }
-    // centred form (this Linear feeds a LayerNorm): column means of W over the valid outputs and the mean of the bias
-    __shared__ float cmean[513];
+    // centred form (this Linear feeds a LayerNorm): column means of W over the valid outputs and the mean of the bias, in two parts.
+    // First the coarse mean (mlp.h), taken off before anything is rounded: a float32 mean of entries with a common offset c is off
+    // by c * 2^-24, the same in every output, which the kernels' mean-free LayerNorm would take for signal
+    // (tests/layernorm_cases.py: offset(c)).  Then the float32 mean of what is left.  Where the coarse part is 0 -- weights whose
+    // mean is below their spread -- this is the float32 centring alone, bit for bit.
+    __shared__ float cmean[513], coarse[513];
     for (int k = tid; k < j.k_pad && k < 512; k += HM_PACK_THREADS) {
-        float a = 0.f;
-        if (j.center) {
-            for (int o = 0; o < j.out_valid; ++o) a += hm_value(j, o, k);
-            a /= (float)(j.out_valid > 0 ? j.out_valid : 1);
+        float a = 0.f, c = 0.f;
+        if (j.center && j.out_valid > 0) {
+            c = hm_coarse_col(j, k);
+            for (int o = 0; o < j.out_valid; ++o) a += (float)((double)hm_value(j, o, k) - (double)c);
+            a /= (float)j.out_valid;
         }
         cmean[k] = a;
+        coarse[k] = c;
     }
     if (tid == 0) {
-        float a = 0.f;
-        if (j.center && j.bias) {
-            for (int o = 0; o < j.bias_n; ++o) a += j.bias[o];
-            a /= (float)(j.bias_n > 0 ? j.bias_n : 1);
+        float a = 0.f, c = 0.f;
+        if (j.center && j.bias && j.bias_n > 0) {
+            c = coarse_mean_of(j.bias, 1, j.bias_n);
+            for (int o = 0; o < j.bias_n; ++o) a += (float)((double)j.bias[o] - (double)c);
+            a /= (float)j.bias_n;
         }
         cmean[512] = a;
+        coarse[512] = c;
     }
     __syncthreads();
     const float t = sc[0], U = sc[1];
     if (tid == 0) { j.dst[0] = t; j.dst[1] = 1.f / U; j.dst[2] = U; }
-    for (int o = tid; o < j.out_pad; o += HM_PACK_THREADS) j.dst[4 + o] = (j.bias && o < j.bias_n) ? (j.bias[o] - cmean[512]) * U : 0.f;
+    for (int o = tid; o < j.out_pad; o += HM_PACK_THREADS) j.dst[4 + o] = (j.bias && o < j.bias_n) ? ((float)((double)j.bias[o] - (double)coarse[512]) - cmean[512]) * U : 0.f;
     _Float16* frag = reinterpret_cast<_Float16*>(j.dst + 4 + j.out_pad);
     const int ksn = j.k_pad / 16;
     const int entries = (j.out_pad / 32) * ksn * 64;   // (jb, ks, lane); two parts each
@@ -1050,7 +1084,8 @@ __global__ void __launch_bounds__(HM_PACK_THREADS) pack_hm_kernel(PackHmJobs J, 
         for (int q = 0; q < 8; ++q) {
             const int k = 16 * ks + 8 * (q >> 2) + 4 * kg + (q & 3);
             const bool valid = (o % j.out_seg) < j.out_valid && (k % j.k_seg) < j.k_valid;   // padding stays exactly zero
-            const float v = (hm_value(j, o, k) - (valid ? cmean[k < 512 ? k : 0] : 0.f)) * t;
+            const int kc = k < 512 ? k : 0;
+            const float v = ((float)((double)hm_value(j, o, k) - (valid ? (double)coarse[kc] : 0.0)) - (valid ? cmean[kc] : 0.f)) * t;
             const _Float16 h = (_Float16)v;
             hi_p[q] = h;
             lo_p[q] = (_Float16)(v - (float)h);

@@ -40,13 +40,41 @@ struct EdgeArgs {
     int precision;         // kPrecisionF32 / kPrecisionF16 (the model's)
 };
 
+#ifdef __HIPCC__
+// The Linear in front of a LayerNorm is held with the common offset of its outputs taken off -- of every column of W over the
+// outputs, and of the bias: the LayerNorm removes it anyway, and removed here it never meets a float32 sum, where an offset c on a
+// deviation sigma costs c / sigma ulps (tests/layernorm_cases.py: offset(c)).  What is taken off is the COARSE part of the mean: its
+// nearest multiple of g, the power of two with 2 s < g <= 4 s, s the largest deviation from the mean.  Weights whose mean is below
+// their own spread -- any initialisation, most trained layers -- give 0 and are held as they are, bit for bit; an offset beyond the
+// spread is removed down to at most 2 s.  s = 0 (all entries equal): the mean itself, so nothing is left.
+__device__ __forceinline__ float coarse_mean(double mean, float spread) {
+    if (!(spread > 0.f)) return (float)mean;
+    if (!(spread < 1.0e30f)) return 0.f;
+    int ex;
+    (void)frexpf(spread, &ex);                  // spread in [2^(ex-1), 2^ex)
+    const double g = ldexp(1.0, ex + 1);
+    return (float)(rint(mean / g) * g);
+}
+// of n floats at p[0], p[stride], ..
+__device__ __forceinline__ float coarse_mean_of(const float* p, size_t stride, int n) {
+    if (n <= 0) return 0.f;
+    double a = 0.0;
+    for (int r = 0; r < n; ++r) a += (double)p[(size_t)r * stride];
+    a /= (double)n;
+    float s = 0.f;
+    for (int r = 0; r < n; ++r) s = fmaxf(s, fabsf((float)((double)p[(size_t)r * stride] - a)));
+    return coarse_mean(a, s);
+}
+#endif
+
 struct VecJob {
     const float* src;
     size_t dst_off;
     int count;   // floats copied
     int zero_to; // destination floats [count, zero_to) are zeroed (padding), 0 = none
+    int center;  // the bias in front of a LayerNorm as the training kernels read it: b - coarse_mean(b)
 };
-constexpr int kVecJobsMax = 128;
+constexpr int kVecJobsMax = 96;   // (a batch is a kernel argument: 96 jobs of 32 bytes)
 struct VecJobs {
     int n;
     VecJob job[kVecJobsMax];

@@ -17,8 +17,11 @@ namespace gm {
 // ------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) vec_batch_kernel(VecJobs J, float* __restrict__ base) {
     const VecJob j = J.job[blockIdx.x];   // blockIdx.y: slice of the tensor (a weight matrix is 16k .. 49k floats: not one workgroup's job)
+    // (a centred job is a bias: at most a few hundred floats, walked by every thread in the same order -- redundant on purpose, the
+    // pack is no hot path; 0 leaves the bits alone)
+    const float off = j.center ? coarse_mean_of(j.src, 1, j.count) : 0.f;
     for (int i = blockIdx.y * blockDim.x + threadIdx.x; i < max(j.count, j.zero_to); i += gridDim.y * blockDim.x)
-        base[j.dst_off + i] = i < j.count ? j.src[i] : 0.f;
+        base[j.dst_off + i] = i < j.count ? (float)((double)j.src[i] - (double)off) : 0.f;
 }
 
 int launch_vec_batch(const VecJobs& jobs, float* base, hipStream_t s) {

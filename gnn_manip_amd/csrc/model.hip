@@ -106,11 +106,12 @@ WeightSizes plan_weights(gm_model* m) {
     m->vec_jobs.clear();
     auto vecs = [&](const MlpSpec& p) {
         const size_t start = z.vec;
-        auto put = [&](int ti, int count, int width) {
-            m->vec_jobs.push_back({T[ti], z.vec, count, count < width ? width : 0});
+        auto put = [&](int ti, int count, int width, int center = 0) {
+            m->vec_jobs.push_back({T[ti], z.vec, count, count < width ? width : 0, center});
             z.vec += width;
         };
-        for (int l = 0; l <= NL; ++l) put(p.base + 2 * l + 1, l == NL ? p.out : Hv, p.normed || l < NL ? H : 32);
+        // (the bias in front of a LayerNorm is kept centred, like that Linear's training images: PackTJob::center)
+        for (int l = 0; l <= NL; ++l) put(p.base + 2 * l + 1, l == NL ? p.out : Hv, p.normed || l < NL ? H : 32, p.normed && l == NL);
         if (p.normed) { put(p.base + 2 * NL + 2, Hv, H); put(p.base + 2 * NL + 3, Hv, H); }
         return start;
     };
@@ -127,12 +128,12 @@ WeightSizes plan_weights(gm_model* m) {
     if (Hv == 64 || Hv == 128 || Hv == 256) {
         TStream* cur = nullptr;   // the stream being laid out: begin() opens it, every Linear packed from there on counts into it
         auto begin = [&](TStream& t) { t = {z.t3, 0, 0}; cur = &t; };
-        auto t3 = [&](int ti, int out_rows, int ld, int col0, int k) {
-            m->t_jobs.push_back({T[ti], k, ld, col0, out_rows, 1, z.t3});
+        auto t3 = [&](int ti, int out_rows, int ld, int col0, int k, int center = 0) {
+            m->t_jobs.push_back({T[ti], k, ld, col0, out_rows, 1, center, z.t3});
             cur->stages += layer_stages_b3(k, out_rows);
             z.t3 += (size_t)layer_stages_b3(k, out_rows) * kStageFloatsB3;
         };
-        auto hidden3 = [&](const MlpSpec& p) { for (int l = 1; l <= NL; ++l) t3(p.base + 2 * l, l == NL ? p.out : H, H, 0, H); };
+        auto hidden3 = [&](const MlpSpec& p) { for (int l = 1; l <= NL; ++l) t3(p.base + 2 * l, l == NL ? p.out : H, H, 0, H, p.normed && l == NL); };
         auto whole3 = [&](const MlpSpec& p) { t3(p.base, H, p.in, 0, p.in); hidden3(p); };   // Linear 0 in one block: encoders, decoder
         begin(m->t_enc_edge);
         whole3(enc_edge);

@@ -73,6 +73,8 @@ struct TrainBwdArgs {
 struct PackTJob {
     const float* W;
     int w_rows, ld, col0, ksub, fwd;
+    int center;       // the Linear in front of a LayerNorm: the image holds W - 1 coarse_mean(columns of W) (mlp.h), so that its outputs
+                      // carry no large common offset into the products' and the LayerNorm mean's float32 rounding
     size_t dst_off;   // floats from the base of the packed buffer
 };
 constexpr int kPackTJobsMax = 96;

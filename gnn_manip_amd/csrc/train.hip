@@ -785,13 +785,27 @@ __global__ void __launch_bounds__(256) pack_b3_batch_kernel(PackTJobs J, float* 
     const int groups = nkg * njb;
     const int total = ((groups + B3_STAGE_GROUPS - 1) / B3_STAGE_GROUPS) * B3_STAGE_GROUPS * 512;   // (group, lane, e)
     unsigned short* dst = reinterpret_cast<unsigned short*>(base + j.dst_off);
+    // centred (PackTJob::center): the coarse mean (mlp.h) of every column of W over its rows -- the Linear's outputs -- is taken
+    // off; the LayerNorm behind it removes it anyway.  dz of a LayerNorm sums to zero over the features, so dX = dz W is the same
+    // with the centred W, and dW = dz^T a never saw W: the gradients are those of the raw weights.
+    __shared__ float cmean[256];
+    // (every one of the job's 16 workgroups works the means out for itself, on purpose: a pack is a few microseconds of an optimiser
+    // step, and a pass of its own would cost a launch)
+    if (j.center) {   // (uniform over the workgroup: j is blockIdx.y's)
+        const int rows = j.fwd ? j.ksub : j.w_rows, cols = j.fwd ? j.w_rows : j.ksub;
+        for (int c = threadIdx.x; c < cols && c < 256; c += blockDim.x) cmean[c] = coarse_mean_of(j.W + j.col0 + c, (size_t)j.ld, rows);
+        __syncthreads();
+    }
     for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
         const int e = idx & 7, lane = (idx >> 3) & 63, g = idx >> 9;
         float v = 0.f;
         if (g < groups) {
             const int kg = g / njb, jb = g % njb;
             const int o = 32 * jb + (lane & 31), k = 16 * kg + 8 * (e >> 2) + 4 * (lane >> 5) + (e & 3);
-            if (o < j.ksub && k < j.w_rows) v = j.fwd ? j.W[(int64_t)o * j.ld + j.col0 + k] : j.W[(int64_t)k * j.ld + j.col0 + o];
+            if (o < j.ksub && k < j.w_rows) {
+                v = j.fwd ? j.W[(int64_t)o * j.ld + j.col0 + k] : j.W[(int64_t)k * j.ld + j.col0 + o];
+                if (j.center) v = (float)((double)v - (double)cmean[j.fwd ? k : o]);
+            }
         }
         const unsigned short hi = bf16_rne_bits(v);
         const float r1 = v - __uint_as_float((unsigned)hi << 16);

@@ -158,7 +158,7 @@ struct PackBwd {
     const float* W(int i, int l) const { return m ? T[m->mlp[i].base + 2 * l] : nullptr; }
     int col(int gm_model::*c) const { return m ? m->*c * H : 0; }
     Slot& begin(Slot& sl) { if (m) sl.stages = 0; else sl = {laid, 0, 0}; return sl; }
-    void job(Slot& sl, const float* W, int w_rows, int ld, int col0, int ksub) {
+    void job(Slot& sl, const float* W, int w_rows, int ld, int col0, int ksub, int center = 0) {
         const int st = layer_stages_b3(w_rows, ksub);
         if (!m) { sl.cap += st; laid = sl.off + (size_t)sl.cap * kStageFloatsB3; return; }
         if (rc == GM_OK) rc = [&]() -> int {
@@ -168,12 +168,12 @@ struct PackBwd {
         if (rc != GM_OK) return;
         if (jobs.n == kPackTJobsMax) flush();
         PackTJob& j = jobs.job[jobs.n++];
-        j.W = W; j.w_rows = w_rows; j.ld = ld; j.col0 = col0; j.ksub = ksub; j.fwd = 0;
+        j.W = W; j.w_rows = w_rows; j.ld = ld; j.col0 = col0; j.ksub = ksub; j.fwd = 0; j.center = center;
         j.dst_off = sl.off + (size_t)sl.stages * kStageFloatsB3;
         sl.stages += st;
     }
-    // the hidden Linears NL + 1 .. 2 of MLP i
-    void hidden(Slot& sl, int i) { for (int l = NL; l >= 1; --l) job(sl, W(i, l), H, H, 0, H); }
+    // the hidden Linears NL + 1 .. 2 of MLP i, which ends in a LayerNorm: the Linear in front of it centred, as in the forward's stream
+    void hidden(Slot& sl, int i) { for (int l = NL; l >= 1; --l) job(sl, W(i, l), H, H, 0, H, l == NL); }
     void ij(Slot& sl, int k) {   // W_i, W_j: the column blocks of step k's first edge Linear that multiply h_i, h_j
         job(sl, W(2 + 2 * k, 0), H, 3 * H, col(&gm_model::ci), H);
         job(sl, W(2 + 2 * k, 0), H, 3 * H, col(&gm_model::cj), H);

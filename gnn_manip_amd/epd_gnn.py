@@ -62,6 +62,18 @@ def _mlp_dims(seq):
     return lin, norm
 
 
+def _common_eps(norms, who):
+    """The one eps of `norms` (LayerNorm modules; 1e-5 where there is none): the library has one ln_eps per model, so LayerNorms that
+    disagree are an error, not a silent choice of the first."""
+    eps = None
+    for m in norms:
+        if eps is None:
+            eps = m.eps
+        elif m.eps != eps:
+            raise ValueError(f"{who}: the LayerNorm modules disagree on eps ({eps} and {m.eps}); the library takes one per model")
+    return 1e-5 if eps is None else float(eps)
+
+
 def _pointers(tensors):
     """The void* array a library call takes for a list of contiguous tensors."""
     return (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
@@ -397,7 +409,7 @@ class GraphIndependent(_StandaloneBlock):
         le, ne = _mlp_dims(self.phi_edge)
         ln, nn_ = _mlp_dims(self.phi_node)
         hidden, nl = le[-1].out_features, len(le) - 1
-        eps = ne[0].eps if ne else 1e-5
+        eps = _common_eps(ne + nn_, "GraphIndependent")
         desc = (ln[0].in_features, le[0].in_features, 1, hidden, nl, 1, float(eps))
         pad = self._placeholders(device, lambda: (_zeros_mlp(3 * hidden, hidden, hidden, nl, True, device)
                                                   + _zeros_mlp(2 * hidden, hidden, hidden, nl, True, device)
@@ -442,7 +454,7 @@ class InteractionNetwork(_StandaloneBlock):
         hidden, nl = le[-1].out_features, len(le) - 1
         if le[0].in_features != 3 * hidden:
             raise ValueError("InteractionNetwork.phi_edge must take 3*hidden inputs ([h_i, h_j, e])")
-        eps = ne[0].eps if ne else 1e-5
+        eps = _common_eps(ne + _mlp_dims(self.phi_node)[1], "InteractionNetwork")
         desc = (1, 1, 1, hidden, nl, 1, float(eps)) + self.convention
         # the placeholder encoders come before the block's own tensors, the placeholder decoder after them
         pre, post = self._placeholders(device, lambda: (_zeros_mlp(1, hidden, hidden, nl, True, device)
@@ -599,8 +611,12 @@ class EncProcDecGNN(nn.Module):
 
     # -- device handle
     def model_desc(self):
-        eps = self.encoder.phi_edge[-1].eps
-        return tuple(int(v) for v in self.dims) + (float(eps),) + self.convention
+        """The library's descriptor of this model.  ln_eps is the eps of the LayerNorm modules, which must agree on it (ValueError)."""
+        # each MLP's last module, `block.phi_edge[-1]`, read from the module dictionaries: 9 us for ten steps where the attribute
+        # and index lookups of nn.Module take 30 us -- this runs at every forward and every RolloutEngine.step
+        norms = [next(reversed(block._modules[name]._modules.values()))
+                 for block in [self.encoder] + list(self.processor._modules.values()) for name in ("phi_edge", "phi_node")]
+        return tuple(int(v) for v in self.dims) + (_common_eps(norms, "EncProcDecGNN"),) + self.convention
 
     def device_handle(self, device):
         """gm_model* for the current parameters on `device` (packed once, re-packed on change)."""
@@ -652,7 +668,7 @@ class EncProcDecGNN(nn.Module):
         for _ in range(m_steps):
             padded += mlp([(hv, True)] * 3, True, hv) + mlp([(hv, True)] * 2, True, hv)
         padded += mlp([(hv, True)], False, out_dim)
-        eps = float(self.encoder.phi_edge[-1].eps) * hv / hp
+        eps = self.model_desc()[6] * hv / hp
         desc = (int(node_dim), int(edge_dim), int(out_dim), hp, int(nl), int(m_steps), eps) + self.convention
         if "_pad_handle" not in self.__dict__:
             self.__dict__["_pad_handle"] = _Handle()

@@ -278,7 +278,7 @@ typedef struct gm_model_desc {
     int32_t hidden_size;   /* 1 .. 256 (epd_gnn.py:13-14 takes any int); see gm_padded_hidden_size */
     int32_t num_layers;    /* >= 2: hidden layers per MLP (epd_gnn.py:26) */
     int32_t m_steps;       /* >= 1 */
-    float ln_eps;          /* 1e-5 */
+    float ln_eps;          /* 1e-5; the eps of every LayerNorm of the model.  Must be > 0: 0, negative and NaN are refused */
     /* Convention of the torch_graphnet.InteractionNetwork block, whose source is absent from the reference tree
      * (.gitmodules:1-3).  All zero = the default of DESIGN.md section 2 (BASELINE.json north_star wording, PyG
      * source_to_target).  Exposed so that a checkpoint trained with another convention can be matched. */

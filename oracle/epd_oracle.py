@@ -298,16 +298,16 @@ def dataset_samples(sim_tables, time_steps, data_dim, k, cartesian_idx, material
 # --------------------------------------------------------------------------------------
 # K4-K9  encode-process-decode  (gnn_manip/models/epd_gnn.py)
 # --------------------------------------------------------------------------------------
-def layer_norm(x, weight, bias, eps=1e-5):
+def layer_norm(x, weight, bias, ln_eps=1e-5):
     """torch.nn.LayerNorm over the last dim (epd_gnn.py:60-61,80-81), float32."""
     x = np.asarray(x, F32)
     mean = x.mean(axis=-1, keepdims=True, dtype=F32)
     xc = x - mean
     var = (xc * xc).mean(axis=-1, keepdims=True, dtype=F32)
-    return (xc / np.sqrt(var + F32(eps))) * weight + bias
+    return (xc / np.sqrt(var + F32(ln_eps))) * weight + bias
 
 
-def mlp(params, prefix, x, num_layers, norm):
+def mlp(params, prefix, x, num_layers, norm, ln_eps=1e-5):
     """``_build_mlp`` (epd_gnn.py:72-84): Linear ReLU [Linear ReLU]*(L-1) Linear [LayerNorm].
 
     Sequential indices: linears at 0,2,...,2L; LayerNorm at 2L+1.
@@ -321,18 +321,18 @@ def mlp(params, prefix, x, num_layers, norm):
             h = np.maximum(h, F32(0))
     if norm:
         h = layer_norm(h, params[f"{prefix}.{2 * num_layers + 1}.weight"],
-                       params[f"{prefix}.{2 * num_layers + 1}.bias"])
+                       params[f"{prefix}.{2 * num_layers + 1}.bias"], ln_eps=ln_eps)
     return h.astype(F32)
 
 
-def graph_independent(params, prefix, x, edge_attr, num_layers):
+def graph_independent(params, prefix, x, edge_attr, num_layers, ln_eps=1e-5):
     """GraphIndependent block (call site epd_gnn.py:88): independent node / edge MLPs."""
-    return (mlp(params, f"{prefix}.phi_node", x, num_layers, True),
-            mlp(params, f"{prefix}.phi_edge", edge_attr, num_layers, True))
+    return (mlp(params, f"{prefix}.phi_node", x, num_layers, True, ln_eps),
+            mlp(params, f"{prefix}.phi_edge", edge_attr, num_layers, True, ln_eps))
 
 
 def interaction_network(params, prefix, h, e, edge_index, num_layers, flow="source_to_target", concat=("i", "j", "e"),
-                        node_concat=("h", "agg")):
+                        node_concat=("h", "agg"), ln_eps=1e-5):
     """InteractionNetwork block (call site epd_gnn.py:101); semantics per north_star.
 
     Default convention: j = edge_index[0] (source), i = edge_index[1] (target / aggregation index),
@@ -348,20 +348,20 @@ def interaction_network(params, prefix, h, e, edge_index, num_layers, flow="sour
         i, j = np.asarray(edge_index[0]), np.asarray(edge_index[1])
     parts = {"i": h[i], "j": h[j], "e": e}
     e_in = np.concatenate([parts[c] for c in concat], axis=-1)
-    e_new = mlp(params, f"{prefix}.phi_edge", e_in, num_layers, True)
+    e_new = mlp(params, f"{prefix}.phi_edge", e_in, num_layers, True, ln_eps)
     agg = np.zeros_like(h)
     np.add.at(agg, i, e_new)
     nparts = {"h": h, "agg": agg}
     h_in = np.concatenate([nparts[c] for c in node_concat], axis=-1)
-    h_new = mlp(params, f"{prefix}.phi_node", h_in, num_layers, True)
+    h_new = mlp(params, f"{prefix}.phi_node", h_in, num_layers, True, ln_eps)
     return h_new, e_new
 
 
-def epd_forward(params, nodes, edge_attr, edge_index, num_layers=2, m_steps=10, **convention):
-    """EncProcDecGNN.forward (epd_gnn.py:86-105)."""
-    h, e = graph_independent(params, "encoder", nodes, edge_attr, num_layers)
+def epd_forward(params, nodes, edge_attr, edge_index, num_layers=2, m_steps=10, ln_eps=1e-5, **convention):
+    """EncProcDecGNN.forward (epd_gnn.py:86-105).  ln_eps: the eps of every LayerNorm (torch's default)."""
+    h, e = graph_independent(params, "encoder", nodes, edge_attr, num_layers, ln_eps)
     for k in range(m_steps):
-        hn, en = interaction_network(params, f"processor.{k}", h, e, edge_index, num_layers, **convention)
+        hn, en = interaction_network(params, f"processor.{k}", h, e, edge_index, num_layers, ln_eps=ln_eps, **convention)
         h = hn + h  # epd_gnn.py:103
         e = en + e  # epd_gnn.py:104
     return mlp(params, "decoder", h, num_layers, False)

@@ -104,14 +104,14 @@ def l1_step(m, nodes, ea, ei, target, dev):
     return out, loss
 
 
-def compare_parameter_gradients(m, params, nodes, ea, ei, target, num_layers, m_steps, ref_g, g32):
+def compare_parameter_gradients(m, params, nodes, ea, ei, target, num_layers, m_steps, ref_g, g32, ln_eps=1e-5):
     """Every parameter gradient of m against float64 by the rule of tests/yardstick.py, the allowance per tensor
-    (torch_epd.relu_flip_allowance of THIS input): no seed is exempt.  Returns yardstick.compare's two worst tensors."""
+    (torch_epd.relu_flip_allowance of THIS input, at the model's ln_eps): no seed is exempt.  Returns yardstick.compare's two worst tensors."""
     got = {}
     for name, p in m.named_parameters():
         assert p.grad is not None, name
         got[name] = p.grad.cpu().numpy()
-    return yardstick.compare(got, ref_g, g32, lambda: torch_epd.relu_flip_allowance(params, nodes, ea, ei, target, num_layers, m_steps))
+    return yardstick.compare(got, ref_g, g32, lambda: torch_epd.relu_flip_allowance(params, nodes, ea, ei, target, num_layers, m_steps, ln_eps=ln_eps))
 
 
 def check_training_step(m, params, nodes, ea, ei, dims, dev, seed, ref=None):

@@ -7,7 +7,8 @@ and the latents stay float32.  The kernels hold their operands at power-of-two s
 "round each Linear's weight matrix and input to fp16, multiply exactly" -- what ``mlp`` below does, with two details of the kernels
 that are visible at the mode's precision:
   * the Linear in front of a LayerNorm is packed centred over its outputs (W - mean_rows(W), b - mean(b), float32, the pack
-    kernels' summation order), and it is the CENTRED matrix that is rounded;
+    kernels' summation order -- after the coarse part of the mean, which is zero unless the mean exceeds the entries' spread, has
+    been taken off unrounded: csrc/mlp.h, coarse_mean), and it is the CENTRED matrix that is rounded;
   * the LayerNorm behind it takes the mean square of those outputs as their variance and subtracts no mean (csrc/hmlp.hip:
     ln_merge) -- exact for the centred float32 weights, off by the mean of the rounding errors (about 3e-5 of the outputs' rms) for
     the rounded ones.
@@ -39,9 +40,25 @@ def r16(a):
         return np.asarray(a).astype(F32).astype(np.float16).astype(F64)
 
 
+def coarse_mean(x):
+    """csrc/mlp.h: per column of x, the multiple of g nearest to the mean, g the power of two with 2 s < g <= 4 s, s the largest
+    deviation from the mean; s = 0: the mean itself.  float32, zero for entries whose mean is below their spread."""
+    x = np.asarray(x, F32).astype(F64)
+    m = np.zeros(x.shape[1:], F64)
+    for row in x:
+        m = m + row
+    m = m / x.shape[0]
+    s = np.abs((x - m).astype(F32)).max(axis=0)
+    g = np.ldexp(1.0, np.frexp(np.where(s > 0, s, 1).astype(F32))[1] + 1)
+    return np.where(s > 0, np.rint(m / g) * g, m).astype(F32)
+
+
 def centred(w, b):
-    """(W - mean_rows(W), b - mean(b)) in float32, summed output after output like pack_hm_kernel / pack_h3_kernel do."""
+    """(W - mean_rows(W), b - mean(b)) as pack_hm_kernel / pack_h3_kernel form them: the coarse mean taken off (float64 subtraction,
+    rounded to float32 once), then the float32 mean of what is left, summed output after output."""
     w, b = np.asarray(w, F32), np.asarray(b, F32)
+    w = (w.astype(F64) - coarse_mean(w).astype(F64)).astype(F32)
+    b = (b.astype(F64) - coarse_mean(b[:, None]).astype(F64)).astype(F32)
     cm = np.zeros(w.shape[1], F32)
     for o in range(w.shape[0]):
         cm = cm + w[o]
@@ -53,10 +70,11 @@ def centred(w, b):
     return w - cm, b - bm
 
 
-def mlp(p, prefix, blocks, num_layers, norm, acc=F64, round_w=True, round_x=True):
+def mlp(p, prefix, blocks, num_layers, norm, acc=F64, round_w=True, round_x=True, ln_eps=EPS):
     """One MLP of the model on the concatenation of `blocks`: Linear ReLU [Linear ReLU] x (L - 1) Linear [LayerNorm].
     round_w / round_x: round the weights / the inputs of every Linear to fp16 (both: the mode; neither: the float32 path's
-    function in float64).  acc: the dtype the products are accumulated -- and everything behind them computed -- in."""
+    function in float64).  acc: the dtype the products are accumulated -- and everything behind them computed -- in.  ln_eps: the eps
+    of the LayerNorm (the callers below pass it on in **kw)."""
     x = np.concatenate([np.asarray(b, F64) for b in blocks], axis=1)
     for l in range(num_layers + 1):
         w, b = p[f"{prefix}.{2 * l}.weight"], p[f"{prefix}.{2 * l}.bias"]
@@ -70,7 +88,7 @@ def mlp(p, prefix, blocks, num_layers, norm, acc=F64, round_w=True, round_x=True
     if norm:
         g, bt = p[f"{prefix}.{2 * num_layers + 1}.weight"], p[f"{prefix}.{2 * num_layers + 1}.bias"]
         z = x.astype(acc)
-        k = 1.0 / np.sqrt((z * z).mean(axis=1, keepdims=True, dtype=acc) + acc(EPS))
+        k = 1.0 / np.sqrt((z * z).mean(axis=1, keepdims=True, dtype=acc) + acc(ln_eps))
         x = ((z * k) * np.asarray(g, acc) + np.asarray(bt, acc)).astype(F64)
     return x
 
@@ -209,15 +227,15 @@ def hm_case(name):
     return random_graph(n, e, 8500 + n)
 
 
-def b_reference(params, nodes, ea, ei, nl, ms):
+def b_reference(params, nodes, ea, ei, nl, ms, ln_eps=EPS):
     """(float64 forward of oracle/torch_epd.py, err of the restatement against it): the envelope of check B is err / 4 .. 4 err."""
     import torch
     from oracle import torch_epd
     p = {k: torch.tensor(v, dtype=torch.float64) for k, v in params.items()}
     with torch.no_grad():
         ref = torch_epd.epd_forward(p, torch.tensor(nodes, dtype=torch.float64), torch.tensor(ea, dtype=torch.float64),
-                                    torch.tensor(ei, dtype=torch.int64), nl, ms).numpy()
-    rest = epd_forward(params, nodes, ea, ei, nl, ms)
+                                    torch.tensor(ei, dtype=torch.int64), nl, ms, ln_eps).numpy()
+    rest = epd_forward(params, nodes, ea, ei, nl, ms, ln_eps=ln_eps)
     return ref, max_err(rest, ref, B_FLOOR)
 
 

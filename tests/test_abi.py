@@ -39,6 +39,18 @@ def test_workspace_queries_and_host_side_errors():
     assert rc == -1
 
 
+def test_model_create_refuses_an_eps_that_is_not_positive():
+    """ln_eps = 0, negative or NaN (which fails `> 0` like any comparison) is refused before any pointer is read or device call made."""
+    import ctypes as C
+    from gnn_manip_amd import _lib
+    L = _lib.lib()
+    arr = (C.c_void_p * 1)()
+    for eps in (0.0, -0.0, -1e-5, float("-inf"), float("nan")):
+        out = C.c_void_p()
+        rc = L.gm_model_create(C.byref(_lib.ModelDesc(25, 4, 3, 128, 2, 10, eps)), arr, 1, 0, None, C.byref(out))
+        assert rc == -1 and b"ln_eps must be > 0" in L.gm_last_error() and not out.value, eps
+
+
 def test_product_modules_reject_cpu_tensors():
     import pytest
     import torch
