@@ -110,6 +110,19 @@ PROTOTYPES = {
     "gm_state_recorded": (_i32, [_vp, _i64, _FD, _vp, _vp, _vp, _i32, _vp]),
     "gm_rollout_recorded": (_i32, [_vp, _vp, _i64, _FD, _i32, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _sz, _vp, _sz, _vp]),
     "gm_rollout_errors": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _FD, _vp, _vp]),
+    "gm_rollout_step_ragged": (_i32, [_vp, _vp, _vp, _i64, _FD, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "gm_rollout_ragged": (_i32, [_vp, _vp, _vp, _i64, _FD, _i32, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _sz, _vp]),
+    "gm_rollout_recorded_ragged": (_i32, [_vp, _vp, _vp, _i64, _FD, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "gm_rollout_errors_ragged": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _FD, _vp, _vp]),
+    "gm_rollout_step_backward_train_ragged": (_i32, [_vp, _vp, _i32, _vp, _vp, _i64, _FD, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
+                                                     _vp]),
+    "gm_rollout_backward_train_ragged": (_i32, [_vp, _vp, _i32, _vp, _vp, _i64, _FD, _i32, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp,
+                                                _vp, _sz, _vp]),
+    "gm_rollout_l1_loss_ragged_workspace_bytes": (_sz, [_i64]),
+    "gm_rollout_l1_loss_ragged": (_i32, [_vp, _vp, _vp, _i32, _i64, _vp, _i64, _FD, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "gm_train_rollout_ragged_workspace_bytes": (_sz, [_MD, _FD, _i64, _i64, _i64, _i32, _i64]),
+    "gm_train_rollout_accumulate_ragged": (_i32, [_vp, _vp, _vp, _i64, _FD, _i32, _vp, _i64, _vp, _i32, _i64, _i32, _vp, _i32, _vp, _vp, _sz,
+                                                  _vp]),
     "gm_rollout_step_backward_workspace_bytes": (_sz, [_MD, _FD, _i64, _i32]),
     "gm_rollout_step_backward": (_i32, [_vp, _vp, _i32, _vp, _i64, _FD, _i32, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64), _vp, _sz, _vp]),
     "gm_rollout_backward_workspace_bytes": (_sz, [_MD, _FD, _i64, _i32]),

@@ -33,14 +33,33 @@ __device__ inline void edge_blocks_plan(const int* __restrict__ in_ptr, int n_no
     tab->n_per_graph = n_per;
     tab->n_stitch = 0;   // counted by the fill pass (a later launch)
 }
+// The same plan for graphs of any sizes: graph g owns rows [off[g], off[g + 1]) (off[n_graphs] = n_nodes) and is padded to whole groups
+// like a graph of an equal-sized batch, so its blocks, groups and partial sums are those it has alone.  `off` may be the kernel's own
+// argument (one thread walks it in order); n_per_graph = 0 marks the table as ragged.
+__device__ inline void edge_blocks_plan_ragged(const int* __restrict__ in_ptr, const int* off, int n_graphs, EdgeBlockHeader* tab, int* gblk) {
+    int pb = 0;
+    for (int g = 0; g < n_graphs; ++g) {
+        gblk[g] = pb;
+        pb += edge_blocks_padded(in_ptr[off[g + 1]] - in_ptr[off[g]]);
+    }
+    gblk[n_graphs] = pb;
+    tab->n_blocks = pb;
+    tab->n_groups = pb / 4;
+    tab->n_graphs = n_graphs;
+    tab->n_per_graph = 0;
+    tab->n_stitch = 0;
+}
 
 // blk[b] = (first edge, count | flags << 8) with flags 1 = first block of its group, 2 = last;
 // head[g] = the destination whose segment continues from group g - 1 into group g (its sum over group g is a "head
 // partial", stored to the side buffer), or -1;  stitch[v] = first group of the run of head partials of destination v
 // (the caller has set stitch[] to -1).  Thread `t` of `nt` takes blocks t, t + nt, ...
+// RAGGED: graph g owns rows [off[g], off[g + 1]) (edge_blocks_plan_ragged); `off` is indexed by a divergent g, so it lies in memory
+// (the caller stages a table that came in its kernel arguments in LDS).  Otherwise off is unused and the graphs have n_per_graph rows.
+template <bool RAGGED = false>
 __device__ inline void edge_blocks_fill(const int* __restrict__ in_ptr, const int* __restrict__ dst, int n_nodes, EdgeBlockHeader* tab,
                                         const int* __restrict__ gblk, int2* blk, int2* seg, int* __restrict__ head, int* __restrict__ stitch,
-                                        int* __restrict__ stitch_list, int t, int nt) {
+                                        int* __restrict__ stitch_list, int t, int nt, const int* off = nullptr) {
     constexpr int BE = kBlockEdges;
     const int nblk = tab->n_blocks, G = tab->n_graphs, n_per = tab->n_per_graph;
     for (int b = t; b < nblk; b += nt) {
@@ -50,7 +69,14 @@ __device__ inline void edge_blocks_fill(const int* __restrict__ in_ptr, const in
             if (gblk[mid] <= b) lo = mid; else hi = mid;
         }
         const int g = lo, j = b - gblk[g];
-        const int e0 = in_ptr[g * n_per], e1 = in_ptr[min(n_nodes, (g + 1) * n_per)];
+        int e0, e1;
+        if constexpr (RAGGED) {
+            e0 = in_ptr[off[g]];
+            e1 = in_ptr[off[g + 1]];
+        } else {
+            e0 = in_ptr[g * n_per];
+            e1 = in_ptr[min(n_nodes, (g + 1) * n_per)];
+        }
         const int start = min(e0 + j * BE, e1);          // padding blocks: (end of the graph, 0 edges)
         const int cnt = min(BE, e1 - start);
         const int fl = ((j & 3) == 0 ? 1 : 0) | ((j & 3) == 3 ? 2 : 0);

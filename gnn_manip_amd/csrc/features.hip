@@ -197,19 +197,24 @@ __global__ void __launch_bounds__(256) state_recorded_kernel(float* __restrict__
 // order, then the 256 partial sums go down a fixed tree in LDS: one order of additions per (step, graph) whatever the grid, no
 // atomics.  Every term is formed in float64 from the float32 inputs, without contraction into multiply-adds, so a term has the
 // bits of the same expression on a host.
+// Ragged: nothing (graph g owns rows [g n_per, (g + 1) n_per)), or RaggedOffsets (rows [off[g], off[g + 1]), n_per = the number of
+// graphs): g is the workgroup's, so the table is read where it came, in the kernel arguments
+template <typename... Ragged>
 __global__ void __launch_bounds__(256) rollout_errors_kernel(const float* __restrict__ rec, const float* __restrict__ pred,
                                                               const float* __restrict__ sim, int64_t first, int64_t n, int64_t n_per,
-                                                              FeatParams P, double* __restrict__ sums) {
+                                                              FeatParams P, double* __restrict__ sums, Ragged... ragged) {
 #pragma clang fp contract(off)
     __shared__ double red[4][256];
     const int tid = threadIdx.x;
-    const int64_t graphs = n / n_per;
+    const int64_t graphs = sizeof...(Ragged) != 0 ? n_per : n / n_per;
     const int64_t step = blockIdx.x / graphs, g = blockIdx.x - step * graphs;
+    int64_t row_lo = g * n_per, row_hi = (g + 1) * n_per;
+    if constexpr (sizeof...(Ragged) != 0) ((row_lo = ragged.off[g], row_hi = ragged.off[g + 1]), ...);
     const int64_t fs = n * P.D;
     const float* rf = rec + step * fs;
     const float* gf = sim + (first + step) * fs;
     double s_all = 0.0, s_cof = 0.0, s_acc = 0.0, cnt = 0.0;
-    for (int64_t r = g * n_per + tid; r < (g + 1) * n_per; r += 256) {
+    for (int64_t r = row_lo + tid; r < row_hi; r += 256) {
         const float* a = rf + r * P.D + P.cart;
         const float* b = gf + r * P.D + P.cart;
         double e = 0.0;
@@ -716,8 +721,36 @@ int gm_rollout_errors(const float* record_last, const float* record_pred, const 
     GM_REQUIRE(record_last && sim && sums, GM_ERR_INVALID_ARGUMENT, "gm_rollout_errors: null pointer");
     const int64_t blocks = steps * (n / n_per);
     GM_REQUIRE(blocks < ((int64_t)1 << 31), GM_ERR_UNSUPPORTED, "gm_rollout_errors: steps * graphs overflows the grid");
-    hipLaunchKernelGGL(rollout_errors_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, record_last, record_pred, sim,
+    hipLaunchKernelGGL(rollout_errors_kernel<>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, record_last, record_pred, sim,
                        first_frame, n, n_per, P, sums);
+    GM_LAUNCH_CHECK();
+    return GM_OK;
+}
+
+int gm_rollout_errors_ragged(const float* record_last, const float* record_pred, const float* sim, int64_t n_frames, int64_t first_frame,
+                             int64_t steps, const int64_t* graph_offsets_host, int64_t n_graphs, const gm_feature_desc* desc, double* sums,
+                             void* stream) {
+    const char* who = "gm_rollout_errors_ragged";
+    FeatParams P;
+    int rc = to_params(desc, &P, who);
+    if (rc != GM_OK) return rc;
+    GM_REQUIRE(desc->nodes_per_graph == 0, GM_ERR_INVALID_ARGUMENT, "%s: nodes_per_graph=%lld, must be 0 (the graphs come in graph_offsets)", who,
+               (long long)desc->nodes_per_graph);
+    GM_REQUIRE(record_last && sim && sums, GM_ERR_INVALID_ARGUMENT, "%s: null pointer", who);
+    RaggedOffsets R;
+    rc = ragged_offsets(graph_offsets_host, n_graphs, desc->conn_r, 1, sums, who, &R);   // no graph is built: max_neighbours plays no part
+    if (rc != GM_OK) return rc;
+    GM_REQUIRE(steps >= 0 && n_frames >= 0, GM_ERR_INVALID_ARGUMENT, "%s: negative count", who);
+    const int64_t lo = record_pred ? 1 : 0, hi = record_pred ? n_frames - 1 : n_frames;
+    GM_REQUIRE(first_frame >= lo && first_frame <= hi && steps <= hi - first_frame, GM_ERR_INVALID_ARGUMENT,
+               "%s: frames [%lld, %lld) outside [%lld, %lld) of the recording%s", who, (long long)first_frame,
+               (long long)(first_frame + steps), (long long)lo, (long long)hi, record_pred ? " (record_pred needs a frame on either side)" : "");
+    if (steps == 0) return GM_OK;
+    gm::DevGuard dev_guard(sums);
+    const int64_t blocks = steps * n_graphs;
+    GM_REQUIRE(blocks < ((int64_t)1 << 31), GM_ERR_UNSUPPORTED, "%s: steps * graphs overflows the grid", who);
+    hipLaunchKernelGGL(rollout_errors_kernel<RaggedOffsets>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, record_last, record_pred,
+                       sim, first_frame, (int64_t)R.off[R.n_graphs], n_graphs, P, sums, R);
     GM_LAUNCH_CHECK();
     return GM_OK;
 }

@@ -387,12 +387,16 @@ __device__ __forceinline__ int cell_coord(float v, double origin, double inv_h, 
     return ci;
 }
 
-// The graph of row i of a ragged build: the g with off[g] <= i < off[g + 1].  The table comes by value in the kernel arguments; a
-// search by a divergent index needs it in memory, so the workgroup stages it in LDS first (every thread of the workgroup calls this).
-__device__ __forceinline__ int ragged_graph_of_row(const RaggedOffsets& R, int64_t i) {
-    __shared__ int s_off[GM_RAGGED_MAX_GRAPHS + 1];
+// The table of a ragged build comes by value in the kernel arguments; a search by a divergent index needs it in memory, so the
+// workgroup stages it in LDS first (every thread of the workgroup calls this).
+__device__ __forceinline__ void stage_ragged_offsets(const RaggedOffsets& R, int* s_off /* LDS, n_graphs + 1 ints */) {
     for (int t = threadIdx.x; t <= R.n_graphs; t += blockDim.x) s_off[t] = R.off[t];
     __syncthreads();
+}
+// The graph of row i of a ragged build: the g with off[g] <= i < off[g + 1] (every thread of the workgroup calls this).
+__device__ __forceinline__ int ragged_graph_of_row(const RaggedOffsets& R, int64_t i) {
+    __shared__ int s_off[GM_RAGGED_MAX_GRAPHS + 1];
+    stage_ragged_offsets(R, s_off);
     int lo = 0, hi = R.n_graphs;   // off[lo] <= i < off[hi]
     while (hi - lo > 1) {
         const int mid = (lo + hi) >> 1;
@@ -702,15 +706,20 @@ __global__ void __launch_bounds__(256) indeg_graph_kernel(const int* __restrict_
 
 // One thread of the launch also lays out the 32-edge block tables' plan (per-graph block counts: it needs in_ptr only, which the scan
 // in front has finished) -- the tables themselves are filled by the launch that follows (segment_sort_kernel).
+// Ragged: nothing (graphs of *n_per_dev rows), or RaggedOffsets: the plan pads every graph of the table to whole groups
+template <typename... Ragged>
 __global__ void __launch_bounds__(256) fill_graph_kernel(const int* __restrict__ cnt, const int* __restrict__ out_ptr,
                                                           const int* __restrict__ nbr, int64_t n, int K,
                                                           const int* __restrict__ in_ptr, const int* __restrict__ slot,
                                                           int64_t cap, int flow, int* __restrict__ dst, int* __restrict__ src,
                                                           int* __restrict__ eid, CsrHeader* hdr, const int* n_per_dev,
-                                                          EdgeBlockHeader* tab, int* gblk) {
+                                                          EdgeBlockHeader* tab, int* gblk, Ragged... ragged) {
     int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, i;
     int s;
-    if (id == 0 && tab) edge_blocks_plan(in_ptr, (int)n, n_per_dev, 0, tab, gblk, (int)n + 1);
+    if (id == 0 && tab) {
+        if constexpr (sizeof...(Ragged) != 0) (edge_blocks_plan_ragged(in_ptr, ragged.off, ragged.n_graphs, tab, gblk), ...);
+        else edge_blocks_plan(in_ptr, (int)n, n_per_dev, 0, tab, gblk, (int)n + 1);
+    }
     if (!decode_slot(id, n, K, cnt, i, s)) return;
     const int d = flow ? (int)i : nbr[id];
     int p = in_ptr[d] + slot[id];
@@ -781,17 +790,27 @@ struct BlockTabArgs {
     int* stitch_list;
     int n_tab;   // workgroups of the launch that fill the tables
 };
+// Ragged: as in fill_graph_kernel; the table workgroups search the offsets by a divergent graph index, so they stage them in LDS
+template <typename... Ragged>
 __global__ void __launch_bounds__(256) segment_sort_kernel(const int* __restrict__ in_ptr, int64_t n,
                                                             int* __restrict__ src, int* __restrict__ eid,
                                                             CsrHeader* hdr, const float* __restrict__ pos,
                                                             int64_t pos_stride, float conn_r, float* __restrict__ edge_attr, int flow,
-                                                            int* __restrict__ tmp_eid, int* __restrict__ tmp_src, BlockTabArgs bt) {
+                                                            int* __restrict__ tmp_eid, int* __restrict__ tmp_src, BlockTabArgs bt,
+                                                            Ragged... ragged) {
     __shared__ int se[SEG_PER_WG * SEG_STRIDE];
     __shared__ int ss[SEG_PER_WG * SEG_STRIDE];
     __shared__ int s_long[SEG_PER_WG];
     if ((int)blockIdx.x < bt.n_tab) {
-        edge_blocks_fill(in_ptr, bt.dst, (int)n, bt.hdr, bt.gblk, bt.blk, bt.seg, bt.head, bt.stitch, bt.stitch_list,
-                         (int)blockIdx.x * 256 + (int)threadIdx.x, bt.n_tab * 256);
+        if constexpr (sizeof...(Ragged) != 0) {
+            int* s_off = se;   // the sort's staging area is free in a table workgroup
+            (stage_ragged_offsets(ragged, s_off), ...);
+            edge_blocks_fill<true>(in_ptr, bt.dst, (int)n, bt.hdr, bt.gblk, bt.blk, bt.seg, bt.head, bt.stitch, bt.stitch_list,
+                                   (int)blockIdx.x * 256 + (int)threadIdx.x, bt.n_tab * 256, s_off);
+        } else {
+            edge_blocks_fill(in_ptr, bt.dst, (int)n, bt.hdr, bt.gblk, bt.blk, bt.seg, bt.head, bt.stitch, bt.stitch_list,
+                             (int)blockIdx.x * 256 + (int)threadIdx.x, bt.n_tab * 256);
+        }
         return;
     }
     const int wg = (int)blockIdx.x - bt.n_tab;   // this workgroup's SEG_PER_WG segments
@@ -963,15 +982,15 @@ int radius_graph_build_core(const float* pos, int64_t pos_stride, int64_t n, int
 // The same six launches for graphs of any sizes: the table gives cell_assign_kernel the graph of a row, and a query takes its
 // graph's block of cells from its own cell
 int radius_graph_build_ragged_core(const float* pos, int64_t pos_stride, const RaggedOffsets& R, double conn_r, int K, const GraphWs& g,
-                                   hipStream_t s) {
+                                   int* indeg, int* slot, int flow, hipStream_t s) {
     const int64_t n = R.off[R.n_graphs];
     const int rc = grid_phase(pos, pos_stride, n, 0, conn_r, g, s, &R);
     if (rc != GM_OK) return rc;
     const double r2 = conn_r * conn_r;
     const int* cell_of = g.cell_of;
     hipLaunchKernelGGL(neighbor_fast_kernel<const int*>, dim3((unsigned)cdiv(n, NB_QPB)), dim3(256), 0, s, g.sorted, g.cell_start,
-                       g.hdr, n, r2, K, g.cnt, g.nbr, (int*)nullptr, (int*)nullptr, 0, cell_of);
-    return K <= 64 ? launch_neighbor<128>(g, n, r2, K, nullptr, nullptr, 0, s, cell_of) : launch_neighbor<64>(g, n, r2, K, nullptr, nullptr, 0, s, cell_of);
+                       g.hdr, n, r2, K, g.cnt, g.nbr, indeg, slot, flow, cell_of);
+    return K <= 64 ? launch_neighbor<128>(g, n, r2, K, indeg, slot, flow, s, cell_of) : launch_neighbor<64>(g, n, r2, K, indeg, slot, flow, s, cell_of);
 }
 // What gm_radius_graph_build_ragged checks of its arguments, and the table
 int ragged_offsets(const int64_t* off, int64_t n_graphs, double conn_r, int K, const void* ws, const char* who, RaggedOffsets* out) {
@@ -1037,7 +1056,7 @@ int gm_radius_graph_build_ragged(const float* pos, int64_t pos_stride, const int
     StepClear clr;
     rc = graph_clear_jobs(clr, g, n);
     if (rc == GM_OK) rc = launch_step_clear(clr, s);
-    if (rc == GM_OK) rc = radius_graph_build_ragged_core(pos, pos_stride, R, conn_r, K, g, s);
+    if (rc == GM_OK) rc = radius_graph_build_ragged_core(pos, pos_stride, R, conn_r, K, g, nullptr, nullptr, 0, s);
     if (rc != GM_OK) return rc;
     const ScanJob sj{g.cnt, g.out_ptr, (long long)n + 1, &g.hdr->n_edges, g.scan_cnt};
     return scan_lookback(&sj, 1, s);
@@ -1087,7 +1106,7 @@ namespace {
 // scan(s) -> fill (+ block-table plan) -> segment sort + edge features + block tables.  with_cnt_scan: the radius graph's own scan
 // of cnt (-> out_ptr, E) shares the scan launch (the fused rollout path; the stand-alone build has already run it).
 int csr_tail(const GraphWs& g, int64_t n, int K, const CsrWs& c, const float* pos, int64_t pos_stride, float conn_r, float* edge_attr,
-             int flow, bool with_cnt_scan, hipStream_t s) {
+             int flow, bool with_cnt_scan, hipStream_t s, const RaggedOffsets* ragged = nullptr) {
     const int64_t cap = n * K;
     const unsigned nb = (unsigned)cdiv(cap, 256);
     int* slot = c.sort_tmp;   // [cap]: free until segment_sort_kernel (which runs after the fill) needs it for long segments
@@ -1096,15 +1115,23 @@ int csr_tail(const GraphWs& g, int64_t n, int K, const CsrWs& c, const float* po
     int rc = scan_lookback(sj, with_cnt_scan ? 2 : 1, s);
     if (rc != GM_OK) return rc;
     const EdgeBlocks t = carve_edge_blocks(c.blocks, n, cap);
-    hipLaunchKernelGGL(fill_graph_kernel, dim3(nb), dim3(256), 0, s, g.cnt, g.out_ptr, g.nbr, n, K, c.in_ptr,
-                       slot, cap, flow, c.dst, c.src, c.eid, c.hdr, &g.hdr->n_per_graph, t.hdr, t.gblk);
+    if (ragged)
+        hipLaunchKernelGGL(fill_graph_kernel<RaggedOffsets>, dim3(nb), dim3(256), 0, s, g.cnt, g.out_ptr, g.nbr, n, K, c.in_ptr,
+                           slot, cap, flow, c.dst, c.src, c.eid, c.hdr, (const int*)nullptr, t.hdr, t.gblk, *ragged);
+    else
+        hipLaunchKernelGGL(fill_graph_kernel<>, dim3(nb), dim3(256), 0, s, g.cnt, g.out_ptr, g.nbr, n, K, c.in_ptr,
+                           slot, cap, flow, c.dst, c.src, c.eid, c.hdr, &g.hdr->n_per_graph, t.hdr, t.gblk);
     // 32-edge blocks aligned to every graph's first edge (the systolic processor edge kernel walks them): extra workgroups of the sort
     // a thread per block of the list's capacity (cap / 32 + the per-graph padding blocks), at most 512 workgroups: they loop
     int gb = (int)cdiv(cdiv(cap, kBlockEdges) + 8, 256);
     gb = gb < 1 ? 1 : (gb > 512 ? 512 : gb);
     const BlockTabArgs bt{c.dst, t.hdr, t.gblk, t.blk, t.seg, t.head, t.stitch, t.stitch_list, gb};
-    hipLaunchKernelGGL(segment_sort_kernel, dim3((unsigned)cdiv(n, SEG_PER_WG) + (unsigned)gb), dim3(256), 0, s, c.in_ptr, n, c.src, c.eid, c.hdr,
-                       pos, pos_stride, conn_r, edge_attr, flow, c.sort_tmp, c.sort_tmp + c.cap, bt);
+    if (ragged)
+        hipLaunchKernelGGL(segment_sort_kernel<RaggedOffsets>, dim3((unsigned)cdiv(n, SEG_PER_WG) + (unsigned)gb), dim3(256), 0, s, c.in_ptr, n,
+                           c.src, c.eid, c.hdr, pos, pos_stride, conn_r, edge_attr, flow, c.sort_tmp, c.sort_tmp + c.cap, bt, *ragged);
+    else
+        hipLaunchKernelGGL(segment_sort_kernel<>, dim3((unsigned)cdiv(n, SEG_PER_WG) + (unsigned)gb), dim3(256), 0, s, c.in_ptr, n, c.src, c.eid, c.hdr,
+                           pos, pos_stride, conn_r, edge_attr, flow, c.sort_tmp, c.sort_tmp + c.cap, bt);
     GM_LAUNCH_CHECK();
     return GM_OK;
 }
@@ -1146,6 +1173,26 @@ int csr_from_graph_fused(const void* graph_ws, int64_t n, int K, void* csr_ws, s
     CsrWs c = carve_csr(csr_ws, n, n * K);
     GM_REQUIRE(csr_ws_bytes >= c.bytes, GM_ERR_WORKSPACE, "csr_from_graph_fused: workspace %zu < %zu", csr_ws_bytes, c.bytes);
     return csr_tail(g, n, K, c, pos, pos_stride, conn_r, edge_attr, flow, true, s);
+}
+// The same two halves for graphs of any sizes (gm_rollout_step_ragged): the search takes the graph of a row from the table and still
+// counts the in-degrees; the plan and the block tables pad every graph of the table to whole groups (blocks_dev.h).  The same launches.
+int radius_graph_build_fused_ragged(const float* pos, int64_t pos_stride, const RaggedOffsets& R, double conn_r, int K, void* graph_ws,
+                                    size_t graph_ws_bytes, void* csr_ws, size_t csr_ws_bytes, int flow, hipStream_t s) {
+    const int64_t n = R.off[R.n_graphs];
+    GM_REQUIRE(pos && graph_ws && csr_ws && pos_stride >= 3 && (flow == 0 || flow == 1), GM_ERR_INVALID_ARGUMENT,
+               "radius_graph_build_fused_ragged: bad argument");
+    GraphWs g = carve_graph(graph_ws, n, K);
+    CsrWs c = carve_csr(csr_ws, n, n * K);
+    GM_REQUIRE(graph_ws_bytes >= g.bytes && csr_ws_bytes >= c.bytes, GM_ERR_WORKSPACE, "radius_graph_build_fused_ragged: workspace too small");
+    return radius_graph_build_ragged_core(pos, pos_stride, R, conn_r, K, g, c.in_ptr, c.sort_tmp, flow, s);
+}
+int csr_from_graph_fused_ragged(const void* graph_ws, const RaggedOffsets& R, int K, void* csr_ws, size_t csr_ws_bytes, const float* pos,
+                                int64_t pos_stride, float conn_r, float* edge_attr, int flow, hipStream_t s) {
+    const int64_t n = R.off[R.n_graphs];
+    GraphWs g = carve_graph(const_cast<void*>(graph_ws), n, K);
+    CsrWs c = carve_csr(csr_ws, n, n * K);
+    GM_REQUIRE(csr_ws_bytes >= c.bytes, GM_ERR_WORKSPACE, "csr_from_graph_fused_ragged: workspace %zu < %zu", csr_ws_bytes, c.bytes);
+    return csr_tail(g, n, K, c, pos, pos_stride, conn_r, edge_attr, flow, true, s, &R);
 }
 }  // namespace gm
 
@@ -1189,7 +1236,7 @@ int csr_from_edge_index(const int64_t* ei, int64_t n, int64_t e, int flow, void*
         hipLaunchKernelGGL(fill_ei_kernel, dim3(nb), dim3(256), 0, s, ei, n, e, flow, c.in_ptr, c.cursor, c.dst, c.src, c.eid, c.hdr);
     }
     if (n > 0)
-        hipLaunchKernelGGL(segment_sort_kernel, dim3((unsigned)cdiv(n, SEG_PER_WG)), dim3(256), 0, s, c.in_ptr, n, c.src, c.eid, c.hdr, nullptr, 3, 1.f, nullptr, 0, c.sort_tmp, c.sort_tmp + c.cap, BlockTabArgs{});
+        hipLaunchKernelGGL(segment_sort_kernel<>, dim3((unsigned)cdiv(n, SEG_PER_WG)), dim3(256), 0, s, c.in_ptr, n, c.src, c.eid, c.hdr, nullptr, 3, 1.f, nullptr, 0, c.sort_tmp, c.sort_tmp + c.cap, BlockTabArgs{});
     GM_LAUNCH_CHECK();
     if (!with_blocks) return GM_OK;
     return build_edge_blocks(c.in_ptr, c.dst, n, nullptr, (int)n, carve_edge_blocks(c.blocks, n, e), s);

@@ -5,7 +5,8 @@
 
 namespace gm {
 
-// ---- tables of 32-edge blocks over a destination-sorted edge list (one or more equal-sized graphs back to back).
+// ---- tables of 32-edge blocks over a destination-sorted edge list (one or more equal-sized graphs back to back, or -- the ragged
+// rollout step -- graphs of any sizes from an offset table: blocks_dev.h).
 // The scatter-add keeps a running sum over a GROUP of 4 blocks.  A segment that begins in a group is stored to agg by
 // that group (whole, or its first piece); the pieces that later groups hold of it ("head partials") go to a side
 // buffer [n_groups][H] and are added in group order by the node kernel: no atomics, one summation order.
@@ -101,6 +102,9 @@ int launch_agg_stitch(float* agg, const float* side, const EdgeBlocks& t, int64_
 // different orders, so a choice by the batch's total would make candidate c of a batch of 10 differ in the last bits from candidate c
 // of a batch of 8 -- or alone.  (Round 6 measured the systolic path at + 1 % on a C5 batch, 8 scenes x 5k = 40k nodes; the batch
 // invariance is worth more than that.)
+// A ragged batch (gm_rollout_step_ragged) passes the size of its SMALLEST graph: the systolic node path is taken only if every graph
+// would take it alone.  So a graph computes in a batch what it computes alone whenever all graphs of the batch lie on the same side
+// of this size -- the one condition of the ragged entry points' batch invariance.
 constexpr int64_t kSysNodeMinNodes = 32 * 256 * 6;
 // encoder phi_e in the same weight-stationary form: raw rows [E][4] in sorted order -> e [E][128] (LayerNorm output)
 int launch_edge_sys_enc(const EdgeArgs& a, hipStream_t s);

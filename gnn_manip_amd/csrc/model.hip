@@ -753,10 +753,25 @@ size_t gm_rollout_workspace_bytes(const gm_model_desc* desc, int64_t n, int K) {
 }  // extern "C"
 
 namespace {
+// What every _ragged rollout entry point checks before anything else: a descriptor of ONE scene per graph and the table
+int ragged_rollout_table(const char* who, const gm_feature_desc* fd, const int64_t* offsets_host, int64_t n_graphs, int K, const void* ws,
+                         gm::RaggedOffsets* R) {
+    GM_REQUIRE(fd && ws, GM_ERR_INVALID_ARGUMENT, "%s: null pointer", who);
+    GM_REQUIRE(fd->nodes_per_graph == 0, GM_ERR_INVALID_ARGUMENT, "%s: nodes_per_graph=%lld, must be 0 (the graphs come in graph_offsets)", who,
+               (long long)fd->nodes_per_graph);
+    return gm::ragged_offsets(offsets_host, n_graphs, fd->conn_r, K, ws, who, R);
+}
+int64_t ragged_min_rows(const gm::RaggedOffsets& R) {
+    int64_t lo = R.off[1] - R.off[0];
+    for (int g = 1; g < R.n_graphs; ++g) lo = std::min<int64_t>(lo, R.off[g + 1] - R.off[g]);
+    return lo;
+}
+
 // gm_rollout_step under either drive: the scripted one (rigid_target, pred_acc_out) or -- rec given -- the recorded one
+// R (or nullptr: graphs of fd->nodes_per_graph rows): the graphs of a ragged batch, n = R->off[R->n_graphs]
 int rollout_step_impl(const gm_model* m, float* obs, int64_t n, const gm_feature_desc* fd, int K, const int32_t* rigid_rank,
                       const float* rigid_target, float* pred_acc_out, const gm::RecordedDrive* rec, void* ws, size_t ws_bytes,
-                      void* stream) {
+                      void* stream, const gm::RaggedOffsets* R = nullptr) {
     gm::DevGuard dev_guard(obs);
     GM_REQUIRE(m && obs && fd && ws, GM_ERR_INVALID_ARGUMENT, "gm_rollout_step: null pointer");
     int rc = gm::check_model_for_scene(m->d, fd, "gm_rollout_step");
@@ -783,18 +798,24 @@ int rollout_step_impl(const gm_model* m, float* obs, int64_t n, const gm_feature
     const float* last_pos = obs + (size_t)(fd->k_steps - 1) * n * fd->data_dim + fd->cart_col;
     {   // the in-degree count of the destination sort rides in the neighbour search
         ProfScope prof(m->prof, PROF_GRAPH, hs);
-        rc = gm::radius_graph_build_fused(last_pos, fd->data_dim, n, gm::graph_nodes(fd, n), fd->conn_r, K,
-                                          r.graph, r.graph_bytes, r.csr, r.csr_bytes, m->d.flow, hs);
+        rc = R ? gm::radius_graph_build_fused_ragged(last_pos, fd->data_dim, *R, fd->conn_r, K, r.graph, r.graph_bytes, r.csr, r.csr_bytes,
+                                                     m->d.flow, hs)
+               : gm::radius_graph_build_fused(last_pos, fd->data_dim, n, gm::graph_nodes(fd, n), fd->conn_r, K,
+                                              r.graph, r.graph_bytes, r.csr, r.csr_bytes, m->d.flow, hs);
     }
     if (rc != GM_OK) return rc;
     // destination sort; the edge features and the block tables are written by the same pass that fixes each segment's order
     {
         ProfScope prof(m->prof, PROF_REST, hs);
-        rc = gm::csr_from_graph_fused(r.graph, n, K, r.csr, r.csr_bytes, last_pos, fd->data_dim, (float)fd->conn_r, r.edge_attr,
-                                      m->d.flow, hs);
+        rc = R ? gm::csr_from_graph_fused_ragged(r.graph, *R, K, r.csr, r.csr_bytes, last_pos, fd->data_dim, (float)fd->conn_r, r.edge_attr,
+                                                 m->d.flow, hs)
+               : gm::csr_from_graph_fused(r.graph, n, K, r.csr, r.csr_bytes, last_pos, fd->data_dim, (float)fd->conn_r, r.edge_attr,
+                                          m->d.flow, hs);
     }
     if (rc != GM_OK) return rc;
-    rc = epd_forward_impl(m, r.x, n, r.edge_attr, 1, r.csr, cap, r.pred, r.fwd, r.fwd_bytes, stream, true, gm::graph_nodes(fd, n));
+    // a ragged batch routes by its smallest graph (hedge.h, kSysNodeMinNodes)
+    rc = epd_forward_impl(m, r.x, n, r.edge_attr, 1, r.csr, cap, r.pred, r.fwd, r.fwd_bytes, stream, true,
+                          R ? ragged_min_rows(*R) : gm::graph_nodes(fd, n));
     if (rc != GM_OK) return rc;
     // integrator + window shift + write-back (+ copy of the prediction) in one launch
     ProfScope prof(m->prof, PROF_REST, hs);
@@ -807,6 +828,18 @@ extern "C" {
 int gm_rollout_step(const gm_model* m, float* obs, int64_t n, const gm_feature_desc* fd, int K, const int32_t* rigid_rank,
                     const float* rigid_target, float* pred_acc_out, void* ws, size_t ws_bytes, void* stream) {
     return rollout_step_impl(m, obs, n, fd, K, rigid_rank, rigid_target, pred_acc_out, nullptr, ws, ws_bytes, stream);
+}
+
+int gm_rollout_step_ragged(const gm_model* m, float* obs, const int64_t* graph_offsets_host, int64_t n_graphs, const gm_feature_desc* fd, int K,
+                           const int32_t* rigid_rank, const float* rigid_target, float* pred_acc_out, void* ws, size_t ws_bytes,
+                           void* stream) {
+    gm::RaggedOffsets R;
+    const int rc = ragged_rollout_table("gm_rollout_step_ragged", fd, graph_offsets_host, n_graphs, K, ws, &R);
+    if (rc != GM_OK) return rc;
+    GM_REQUIRE(m && obs, GM_ERR_INVALID_ARGUMENT, "gm_rollout_step_ragged: null pointer");
+    const size_t need = carve_rollout(nullptr, &m->d, R.off[R.n_graphs], K).bytes;
+    GM_REQUIRE(ws_bytes >= need, GM_ERR_WORKSPACE, "gm_rollout_step_ragged: workspace %zu < %zu", ws_bytes, need);
+    return rollout_step_impl(m, obs, R.off[R.n_graphs], fd, K, rigid_rank, rigid_target, pred_acc_out, nullptr, ws, ws_bytes, stream, &R);
 }
 
 size_t gm_rollout_renumber_workspace_bytes(const gm_feature_desc* fd, int64_t n) {
@@ -827,7 +860,7 @@ struct RolloutDrive {
 };
 int rollout_loop(const char* who, const gm_model* m, float* obs, int64_t n, const gm_feature_desc* fd, int K, const int32_t* rigid_rank,
                  const RolloutDrive& drive, int64_t steps, float* record_last, int64_t renumber_every, void* renumber_ws,
-                 size_t renumber_ws_bytes, void* ws, size_t ws_bytes, void* stream) {
+                 size_t renumber_ws_bytes, void* ws, size_t ws_bytes, void* stream, const gm::RaggedOffsets* R = nullptr) {
     hipStream_t hs = (hipStream_t)stream;
     const float* rigid_targets = drive.targets;
     const int64_t n_targets = drive.n_targets, n_rigid = drive.n_rigid;
@@ -871,7 +904,7 @@ int rollout_loop(const char* who, const gm_model* m, float* obs, int64_t n, cons
             // launches, reaching the caller's arrays through `total`
             const gm::RecordedDrive rec{drive.frames + (size_t)i * frame, total, record_last ? record_last + (size_t)i * frame : nullptr,
                                         drive.record_pred ? drive.record_pred + (size_t)i * n * 3 : nullptr};
-            int rc = rollout_step_impl(m, state, n, fd, K, rank, nullptr, nullptr, &rec, ws, ws_bytes, stream);
+            int rc = rollout_step_impl(m, state, n, fd, K, rank, nullptr, nullptr, &rec, ws, ws_bytes, stream, R);
             if (rc != GM_OK) return rc;
             continue;
         }
@@ -886,7 +919,7 @@ int rollout_loop(const char* who, const gm_model* m, float* obs, int64_t n, cons
             else GM_HIP_CHECK(hipMemcpyAsync(record_last + (size_t)i * frame, last, frame * sizeof(float), hipMemcpyDeviceToDevice, hs));
             if (rc != GM_OK) return rc;
         }
-        int rc = gm_rollout_step(m, state, n, fd, K, rank, target, nullptr, ws, ws_bytes, stream);
+        int rc = rollout_step_impl(m, state, n, fd, K, rank, target, nullptr, nullptr, ws, ws_bytes, stream, R);
         if (rc != GM_OK) return rc;
     }
     if (total) return gm::renumber_scatter(state, obs, fd->k_steps, n, fd->data_dim, total, hs);
@@ -926,6 +959,47 @@ int gm_rollout_recorded(const gm_model* m, float* obs, int64_t n, const gm_featu
     drive.frames = frames; drive.record_pred = record_pred;
     return rollout_loop("gm_rollout_recorded", m, obs, n, fd, K, rigid_rank, drive, steps, record_last, renumber_every, renumber_ws,
                         renumber_ws_bytes, ws, ws_bytes, stream);
+}
+
+// gm_rollout / gm_rollout_recorded on graphs of any sizes: the same loop and launches, the table in every step's graph path, no
+// renumbering.  The workspace is checked here, before the first launch, so that a refusal leaves every output as it was.
+int gm_rollout_ragged(const gm_model* m, float* obs, const int64_t* graph_offsets_host, int64_t n_graphs, const gm_feature_desc* fd, int K,
+                      const int32_t* rigid_rank, const float* rigid_targets, int64_t n_targets, int64_t n_rigid, int64_t steps,
+                      float* record_last, void* ws, size_t ws_bytes, void* stream) {
+    gm::RaggedOffsets R;
+    const int rc = ragged_rollout_table("gm_rollout_ragged", fd, graph_offsets_host, n_graphs, K, ws, &R);
+    if (rc != GM_OK) return rc;
+    gm::DevGuard dev_guard(obs);
+    GM_REQUIRE(m && obs, GM_ERR_INVALID_ARGUMENT, "gm_rollout_ragged: null pointer");
+    GM_REQUIRE(steps >= 0 && n_targets >= 0 && n_rigid >= 0, GM_ERR_INVALID_ARGUMENT, "gm_rollout_ragged: negative count");
+    GM_REQUIRE(rigid_targets || n_targets == 0 || n_rigid == 0, GM_ERR_INVALID_ARGUMENT, "gm_rollout_ragged: n_targets > 0 without rigid_targets");
+    GM_REQUIRE(!rigid_targets || rigid_rank, GM_ERR_INVALID_ARGUMENT, "gm_rollout_ragged: rigid_targets need rigid_rank");
+    const int64_t n = R.off[R.n_graphs];
+    const size_t need = carve_rollout(nullptr, &m->d, n, K).bytes;
+    GM_REQUIRE(ws_bytes >= need, GM_ERR_WORKSPACE, "gm_rollout_ragged: workspace %zu < %zu", ws_bytes, need);
+    RolloutDrive drive;
+    drive.targets = rigid_targets; drive.n_targets = n_targets; drive.n_rigid = n_rigid;
+    return rollout_loop("gm_rollout_ragged", m, obs, n, fd, K, rigid_rank, drive, steps, record_last, 0, nullptr, 0, ws, ws_bytes, stream, &R);
+}
+
+int gm_rollout_recorded_ragged(const gm_model* m, float* obs, const int64_t* graph_offsets_host, int64_t n_graphs, const gm_feature_desc* fd,
+                               int K, const int32_t* rigid_rank, const float* frames, int64_t steps, float* record_last, float* record_pred,
+                               void* ws, size_t ws_bytes, void* stream) {
+    gm::RaggedOffsets R;
+    const int rc = ragged_rollout_table("gm_rollout_recorded_ragged", fd, graph_offsets_host, n_graphs, K, ws, &R);
+    if (rc != GM_OK) return rc;
+    gm::DevGuard dev_guard(obs);
+    GM_REQUIRE(m && obs, GM_ERR_INVALID_ARGUMENT, "gm_rollout_recorded_ragged: null pointer");
+    GM_REQUIRE(steps >= 0, GM_ERR_INVALID_ARGUMENT, "gm_rollout_recorded_ragged: negative count");
+    GM_REQUIRE(frames || steps == 0, GM_ERR_INVALID_ARGUMENT, "gm_rollout_recorded_ragged: steps > 0 without frames");
+    const int64_t n = R.off[R.n_graphs];
+    const size_t need = carve_rollout(nullptr, &m->d, n, K).bytes;
+    GM_REQUIRE(ws_bytes >= need, GM_ERR_WORKSPACE, "gm_rollout_recorded_ragged: workspace %zu < %zu", ws_bytes, need);
+    if (steps == 0) return GM_OK;
+    RolloutDrive drive;
+    drive.frames = frames; drive.record_pred = record_pred;
+    return rollout_loop("gm_rollout_recorded_ragged", m, obs, n, fd, K, rigid_rank, drive, steps, record_last, 0, nullptr, 0, ws, ws_bytes,
+                        stream, &R);
 }
 
 int gm_rollout_status(const void* ws, const gm_model_desc* desc, int64_t n, int K, int64_t* n_edges_host, void* stream) {

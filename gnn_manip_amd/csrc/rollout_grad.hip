@@ -5,6 +5,7 @@
 // step_assemble_bwd_kernel), so every number is the one a caller of those entry points would get.
 #include "common.h"
 #include "model.h"
+#include "step_rows.h"
 
 namespace gm {
 // features.hip
@@ -89,11 +90,12 @@ size_t gm_rollout_step_backward_workspace_bytes(const gm_model_desc* desc, const
     return carve_step_bwd(nullptr, desc, fdesc, n, K).bytes;
 }
 
-// both step entry points; `who` names the one that was called in its messages
+// both step entry points; `who` names the one that was called in its messages.  R (or nullptr: graphs of fd->nodes_per_graph rows): the
+// graphs of a ragged batch -- the step's graph is then gm_radius_graph_build_ragged's; everything else is per row or per edge
 static int step_backward(const gm_model* m, const float* const* tensors, int n_tensors, const float* obs_before, int64_t n,
                          const gm_feature_desc* fd, int K, const int32_t* rigid_rank, const float* rigid_target, const float* d_obs_after,
                          const float* d_record, float* const* grads, float* d_obs_before, float* d_rigid_target, int64_t* n_edges_host,
-                         void* ws, size_t ws_bytes, void* stream, const char* who) {
+                         void* ws, size_t ws_bytes, void* stream, const char* who, const gm::RaggedOffsets* R = nullptr) {
     gm::DevGuard dev_guard(obs_before);
     GM_REQUIRE(m && tensors && fd && ws, GM_ERR_INVALID_ARGUMENT, "%s: null pointer", who);
     GM_REQUIRE(sizes_ok(&m->d, fd, n, K), GM_ERR_INVALID_ARGUMENT, "%s: sizes out of range", who);
@@ -120,8 +122,14 @@ static int step_backward(const gm_model* m, const float* const* tensors, int n_t
     rc = gm_node_features(w.pre, n, fd, w.nodes, stream);
     if (rc != GM_OK) return rc;
     const float* last_pos = w.pre + (size_t)(fd->k_steps - 1) * n * fd->data_dim + fd->cart_col;
-    rc = gm_radius_graph_build_batched(last_pos, fd->data_dim, n, gm::graph_nodes(fd, n), fd->conn_r, K, w.graph,
-                                       w.graph_bytes, stream);
+    if (R) {
+        int64_t off[GM_RAGGED_MAX_GRAPHS + 1];
+        for (int g = 0; g <= R->n_graphs; ++g) off[g] = R->off[g];
+        rc = gm_radius_graph_build_ragged(last_pos, fd->data_dim, off, R->n_graphs, fd->conn_r, K, w.graph, w.graph_bytes, stream);
+    } else {
+        rc = gm_radius_graph_build_batched(last_pos, fd->data_dim, n, gm::graph_nodes(fd, n), fd->conn_r, K, w.graph,
+                                           w.graph_bytes, stream);
+    }
     if (rc != GM_OK) return rc;
     int64_t e = 0;
     rc = gm_radius_graph_num_edges(w.graph, &e, stream);   // the one number read back: the training forward takes E on the host
@@ -184,7 +192,7 @@ size_t gm_rollout_backward_workspace_bytes(const gm_model_desc* desc, const gm_f
 static int sweep_backward(const gm_model* m, const float* const* tensors, int n_tensors, const float* windows, int64_t n,
                           const gm_feature_desc* fd, int K, const int32_t* rigid_rank, const float* trajectory, int64_t n_targets,
                           int64_t n_rigid, int64_t steps, const float* d_final, const float* d_records, float* const* grads, float* d_obs0,
-                          float* d_trajectory, void* ws, size_t ws_bytes, void* stream, const char* who) {
+                          float* d_trajectory, void* ws, size_t ws_bytes, void* stream, const char* who, const gm::RaggedOffsets* R = nullptr) {
     gm::DevGuard dev_guard(d_final);
     GM_REQUIRE(m && tensors && fd && ws, GM_ERR_INVALID_ARGUMENT, "%s: null pointer", who);
     GM_REQUIRE(steps >= 0 && n_targets >= 0 && n_rigid >= 0, GM_ERR_INVALID_ARGUMENT, "%s: negative count", who);
@@ -214,7 +222,7 @@ static int sweep_backward(const gm_model* m, const float* const* tensors, int n_
         int rc = step_backward(m, tensors, n_tensors, windows + (size_t)t * window, n, fd, K, rigid_rank,
                                scripted ? trajectory + (size_t)t * pose : nullptr, g_after, d_records ? d_records + (size_t)t * record : nullptr,
                                grads, g_before, scripted && d_trajectory ? d_trajectory + (size_t)t * pose : nullptr, nullptr, w.step,
-                               w.step_bytes, stream, step_who);
+                               w.step_bytes, stream, step_who, R);
         if (rc != GM_OK) return rc;
         g_after = g_before;
     }
@@ -236,6 +244,40 @@ int gm_rollout_backward_train(const gm_model* m, const float* const* tensors, in
                               float* d_obs0, float* d_trajectory, void* ws, size_t ws_bytes, void* stream) {
     return sweep_backward(m, tensors, n_tensors, windows, n, fd, K, rigid_rank, trajectory, n_targets, n_rigid, steps, d_final, d_records,
                           grads, d_obs0, d_trajectory, ws, ws_bytes, stream, __func__);
+}
+
+// The two training sweeps on graphs of any sizes (the table as in gm_radius_graph_build_ragged, fd->nodes_per_graph == 0): still one
+// edge-count read per step, for the whole batch.  d_record / d_records and grads both NULL: the plain vector-Jacobian product.
+static int ragged_table(const char* who, const gm_feature_desc* fd, const int64_t* offsets_host, int64_t n_graphs, int K, const void* ws,
+                        gm::RaggedOffsets* R) {
+    GM_REQUIRE(fd && ws, GM_ERR_INVALID_ARGUMENT, "%s: null pointer", who);
+    GM_REQUIRE(fd->nodes_per_graph == 0, GM_ERR_INVALID_ARGUMENT, "%s: nodes_per_graph=%lld, must be 0 (the graphs come in graph_offsets)", who,
+               (long long)fd->nodes_per_graph);
+    return gm::ragged_offsets(offsets_host, n_graphs, fd->conn_r, K, ws, who, R);
+}
+
+int gm_rollout_step_backward_train_ragged(const gm_model* m, const float* const* tensors, int n_tensors, const float* obs_before,
+                                          const int64_t* graph_offsets_host, int64_t n_graphs, const gm_feature_desc* fd, int K,
+                                          const int32_t* rigid_rank, const float* rigid_target, const float* d_obs_after, const float* d_record,
+                                          float* const* grads, float* d_obs_before, float* d_rigid_target, int64_t* n_edges_host, void* ws,
+                                          size_t ws_bytes, void* stream) {
+    gm::RaggedOffsets R;
+    const int rc = ragged_table(__func__, fd, graph_offsets_host, n_graphs, K, ws, &R);
+    if (rc != GM_OK) return rc;
+    return step_backward(m, tensors, n_tensors, obs_before, R.off[R.n_graphs], fd, K, rigid_rank, rigid_target, d_obs_after, d_record, grads,
+                         d_obs_before, d_rigid_target, n_edges_host, ws, ws_bytes, stream, __func__, &R);
+}
+
+int gm_rollout_backward_train_ragged(const gm_model* m, const float* const* tensors, int n_tensors, const float* windows,
+                                     const int64_t* graph_offsets_host, int64_t n_graphs, const gm_feature_desc* fd, int K,
+                                     const int32_t* rigid_rank, const float* trajectory, int64_t n_targets, int64_t n_rigid, int64_t steps,
+                                     const float* d_final, const float* d_records, float* const* grads, float* d_obs0, float* d_trajectory,
+                                     void* ws, size_t ws_bytes, void* stream) {
+    gm::RaggedOffsets R;
+    const int rc = ragged_table(__func__, fd, graph_offsets_host, n_graphs, K, ws, &R);
+    if (rc != GM_OK) return rc;
+    return sweep_backward(m, tensors, n_tensors, windows, R.off[R.n_graphs], fd, K, rigid_rank, trajectory, n_targets, n_rigid, steps, d_final,
+                          d_records, grads, d_obs0, d_trajectory, ws, ws_bytes, stream, __func__, &R);
 }
 
 }  // extern "C"

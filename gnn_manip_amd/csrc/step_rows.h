@@ -33,7 +33,12 @@ struct RaggedOffsets {
 // the message of a refusal); radius_graph_build_ragged_core: radius_graph_build_core with the graph of a row from the table
 int ragged_offsets(const int64_t* offsets_host, int64_t n_graphs, double conn_r, int K, const void* ws, const char* who, RaggedOffsets* out);
 int radius_graph_build_ragged_core(const float* pos, int64_t pos_stride, const RaggedOffsets& R, double conn_r, int K, const GraphWs& g,
-                                   hipStream_t s);
+                                   int* indeg, int* slot, int flow, hipStream_t s);
+// radius_graph_build_fused / csr_from_graph_fused (common.h) for the graphs of a table: the rollout step's graph path of a ragged batch
+int radius_graph_build_fused_ragged(const float* pos, int64_t pos_stride, const RaggedOffsets& R, double conn_r, int K, void* graph_ws,
+                                    size_t graph_ws_bytes, void* csr_ws, size_t csr_ws_bytes, int flow, hipStream_t s);
+int csr_from_graph_fused_ragged(const void* graph_ws, const RaggedOffsets& R, int K, void* csr_ws, size_t csr_ws_bytes, const float* pos,
+                                int64_t pos_stride, float conn_r, float* edge_attr, int flow, hipStream_t s);
 
 // Width of a scene's node features: 3 (k_steps - 1) velocities, 6 boundary terms, the material, and 3 more with control columns
 __host__ __device__ static inline int node_feature_dim(int k_steps, int control_col) { return 3 * (k_steps - 1) + 7 + (control_col >= 0 ? 3 : 0); }

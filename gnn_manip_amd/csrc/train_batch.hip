@@ -338,7 +338,7 @@ int train_batch_build(const char* who, bool ragged, const float* const* first_fr
     if (rc != GM_OK) return rc;
     rc = ragged ? launch_train_batch_k(P.k, F, A, batch, s, S) : launch_train_batch_k(P.k, F, A, batch, s);
     if (rc == GM_OK)
-        rc = ragged ? radius_graph_build_ragged_core(w.pos, 3, R, fdesc->conn_r, max_neighbours, g, s)
+        rc = ragged ? radius_graph_build_ragged_core(w.pos, 3, R, fdesc->conn_r, max_neighbours, g, nullptr, nullptr, 0, s)
                     : radius_graph_build_core(w.pos, 3, rows, n, fdesc->conn_r, max_neighbours, g, nullptr, nullptr, 0, s);
     if (rc != GM_OK) return rc;
     const ScanJob sj{g.cnt, g.out_ptr, (long long)rows + 1, &w.rec->n_edges, g.scan_cnt};   // E goes to the record

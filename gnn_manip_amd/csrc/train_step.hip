@@ -10,9 +10,11 @@
 // Between accumulate and apply several processes may merge their mini-batches: gm_trainer_contribution, the caller's all-gather,
 // gm_trainer_reduce (gm_rank_sum: a float32 sum in rank order; tests/train_dp_cases.py).  No communication library is linked.
 #include <math.h>
+#include <algorithm>
 #include <vector>
 #include "common.h"
 #include "model.h"
+#include "step_rows.h"
 
 using namespace gm;
 
@@ -290,6 +292,176 @@ __global__ void __launch_bounds__(kLossThreads) recorded_poses_kernel(const floa
     o[0] = f[0]; o[1] = f[1]; o[2] = f[2];
 }
 
+// ---- the same loss for a ragged batch (gm_rollout_l1_loss_ragged): one loss per graph, each the single call's on that graph alone.
+// The recorded frames of graph g are an array of their own ([steps, n_g, frame_dim], a view into its recording): the pointers and the
+// offsets travel by value in the kernel arguments; a kernel that needs them by a row's (divergent) graph stages them in LDS first.
+struct RaggedFrames { const float* p[GM_RAGGED_MAX_GRAPHS]; };
+struct GraphLoss {      // what the finish leaves per graph for the transpose
+    double loss;
+    int64_t count;
+};
+struct RaggedRowTable {   // in LDS
+    int off[GM_RAGGED_MAX_GRAPHS + 1];
+    const float* frames[GM_RAGGED_MAX_GRAPHS];
+};
+// every thread of the workgroup calls it
+__device__ inline void stage_row_table(const RaggedOffsets& R, const RaggedFrames& F, RaggedRowTable* tab) {
+    for (int t = threadIdx.x; t <= R.n_graphs; t += blockDim.x) tab->off[t] = R.off[t];
+    for (int t = threadIdx.x; t < R.n_graphs; t += blockDim.x) tab->frames[t] = F.p[t];
+    __syncthreads();
+}
+__device__ inline int graph_of_row(const RaggedRowTable* tab, int n_graphs, int64_t r) {
+    int lo = 0, hi = n_graphs;   // off[lo] <= r < off[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if ((int64_t)tab->off[mid] <= r) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+__host__ __device__ inline unsigned loss_grid_of(int64_t rows) {
+    const int64_t g = (rows + kLossThreads - 1) / kLossThreads;
+    return (unsigned)(g < 1 ? 1 : (g > kLossGridMax ? kLossGridMax : g));
+}
+
+struct RolloutLossRaggedWs {
+    double* part_sum;     // [n_graphs][3][kLossGridMax]
+    int64_t* part_cnt;    // [n_graphs][kLossGridMax]
+    GraphLoss* graph;     // [n_graphs]
+    LossState* state;     // the mini-batch's: loss = the sum of the graphs' losses, skip = how many of them are not finite
+    size_t bytes;
+};
+RolloutLossRaggedWs carve_rollout_loss_ragged(void* ws, int64_t n_graphs) {
+    RolloutLossRaggedWs w;
+    Carver c(ws);
+    w.part_sum = c.take<double>((size_t)n_graphs * 3 * kLossGridMax);
+    w.part_cnt = c.take<int64_t>((size_t)n_graphs * kLossGridMax);
+    w.graph = c.take<GraphLoss>((size_t)n_graphs);
+    w.state = c.take<LossState>(1);
+    w.bytes = c.used();
+    return w;
+}
+
+// Pass 1: blockIdx.y is the graph.  Graph g is walked by the loss_grid(n_g) workgroups the single call launches for it, in that
+// call's stride, so its partial sums -- and everything behind them -- depend on its own rows alone; the other workgroups of the row leave.
+__global__ void __launch_bounds__(kLossThreads) rollout_l1_partials_ragged_kernel(RolloutLossArgs a, RaggedOffsets R, RaggedFrames F,
+                                                                                  double* part_sum, int64_t* part_cnt) {
+    __shared__ double sh_s[kLossThreads];
+    __shared__ int64_t sh_c[kLossThreads];
+    const int g = blockIdx.y;
+    const int64_t lo = R.off[g], n_g = R.off[g + 1] - lo;
+    const unsigned grid = loss_grid_of(n_g);
+    if (blockIdx.x >= grid) return;
+    const float* frames = F.p[g];
+    double s[3] = {0.0, 0.0, 0.0};
+    int64_t cnt = 0;
+    for (int64_t q = (int64_t)blockIdx.x * kLossThreads + threadIdx.x; q < n_g; q += (int64_t)grid * kLossThreads) {
+        const int64_t r = lo + q;
+        if (!rollout_row_counts(a, r)) continue;
+        ++cnt;
+        for (int64_t t = 0; t < a.steps; ++t) {
+            const float* p = predicted_frame(a, t) + (size_t)r * a.D + a.cart;
+            const float* f = frames + ((size_t)t * n_g + q) * a.frame_dim + a.cart;
+            for (int c = 0; c < 3; ++c) s[c] += (double)fabsf(p[c] - f[c]);
+        }
+    }
+    for (int c = 0; c < 3; ++c) {
+        const double v = block_sum(s[c], sh_s);
+        if (threadIdx.x == 0) part_sum[((size_t)g * 3 + c) * kLossGridMax + blockIdx.x] = v;
+    }
+    cnt = block_sum(cnt, sh_c);
+    if (threadIdx.x == 0) part_cnt[(size_t)g * kLossGridMax + blockIdx.x] = cnt;
+}
+
+// Pass 2, one workgroup per graph: rollout_l1_finish_kernel's sums and formula on the graph's own partials.
+__global__ void __launch_bounds__(kLossThreads) rollout_l1_finish_ragged_kernel(const double* part_sum, const int64_t* part_cnt, RaggedOffsets R,
+                                                                                int64_t steps, PosScale ps, GraphLoss* graph, double* losses_out,
+                                                                                int64_t* rows_out) {
+    __shared__ double sh_s[kLossThreads];
+    __shared__ int64_t sh_c[kLossThreads];
+    const int g = blockIdx.x;
+    const int n_part = (int)loss_grid_of(R.off[g + 1] - R.off[g]);
+    double s[3];
+    for (int c = 0; c < 3; ++c) {
+        double v = 0.0;
+        for (int i = threadIdx.x; i < n_part; i += kLossThreads) v += part_sum[((size_t)g * 3 + c) * kLossGridMax + i];
+        s[c] = block_sum(v, sh_s);
+    }
+    int64_t cnt = 0;
+    for (int i = threadIdx.x; i < n_part; i += kLossThreads) cnt += part_cnt[(size_t)g * kLossGridMax + i];
+    cnt = block_sum(cnt, sh_c);
+    if (threadIdx.x != 0) return;
+    const double terms = (double)steps * (double)cnt;
+    const double loss = cnt > 0 ? ((s[0] / ps.s[0] + s[1] / ps.s[1]) + s[2] / ps.s[2]) / terms : (double)__builtin_nanf("");
+    graph[g].loss = loss;
+    graph[g].count = cnt;
+    if (losses_out) losses_out[g] = loss;
+    if (rows_out) rows_out[g] = cnt;
+}
+
+// One thread: the mini-batch's state -- the graphs' losses added in graph order, and how many of them are not finite.
+__global__ void rollout_l1_total_ragged_kernel(const GraphLoss* graph, int n_graphs, LossState* st) {
+    double loss = graph[0].loss;
+    int64_t cnt = graph[0].count;
+    int bad = isfinite(graph[0].loss) ? 0 : 1;
+    for (int g = 1; g < n_graphs; ++g) {
+        loss += graph[g].loss;
+        cnt += graph[g].count;
+        bad += isfinite(graph[g].loss) ? 0 : 1;
+    }
+    st->loss = loss;
+    st->count = cnt;
+    st->scale = 0.f;
+    st->skip = bad;
+}
+
+// Pass 3: rollout_l1_grad_kernel with the row's graph deciding the count and the recorded frame.
+__global__ void __launch_bounds__(kLossThreads) rollout_l1_grad_ragged_kernel(RolloutLossArgs a, RaggedOffsets R, RaggedFrames F, PosScale ps,
+                                                                              const GraphLoss* graph, float* d_records, float* d_final) {
+    __shared__ RaggedRowTable tab;
+    __shared__ float sg[GM_RAGGED_MAX_GRAPHS][3];
+    for (int g = threadIdx.x; g < R.n_graphs; g += blockDim.x) {
+        const int64_t cnt = graph[g].count;
+        for (int c = 0; c < 3; ++c) sg[g][c] = cnt > 0 ? (float)(1.0 / ((ps.s[c] * (double)a.steps) * (double)cnt)) : 0.f;
+    }
+    stage_row_table(R, F, &tab);
+    const int64_t slab = blockIdx.y;
+    const size_t frame = (size_t)a.n * a.D;
+    float* out = slab < a.steps ? d_records + (size_t)slab * frame : d_final + (size_t)(slab - a.steps) * frame;
+    const int64_t t = slab < a.steps ? slab - 1 : (slab == a.steps + a.k - 1 ? a.steps - 1 : -1);
+    const float* pred = t >= 0 ? predicted_frame(a, t) : nullptr;
+    for (int64_t r = (int64_t)blockIdx.x * kLossThreads + threadIdx.x; r < a.n; r += (int64_t)gridDim.x * kLossThreads) {
+        const int g = graph_of_row(&tab, R.n_graphs, r);
+        const int64_t lo = tab.off[g], n_g = tab.off[g + 1] - lo;
+        const bool counts = t >= 0 && sg[g][0] != 0.f && rollout_row_counts(a, r);
+        for (int c = 0; c < a.D; ++c) {
+            float v = 0.f;
+            const int ax = c - a.cart;
+            if (counts && ax >= 0 && ax < 3) {
+                const float d = pred[(size_t)r * a.D + c] - tab.frames[g][((size_t)t * n_g + (r - lo)) * a.frame_dim + c];
+                v = d > 0.f ? sg[g][ax] : (d < 0.f ? -sg[g][ax] : 0.f);
+            }
+            out[(size_t)r * a.D + c] = v;
+        }
+    }
+}
+
+// recorded_poses_kernel for a ragged batch: ranks are global, the frame of a row is its graph's.
+__global__ void __launch_bounds__(kLossThreads) recorded_poses_ragged_kernel(RaggedOffsets R, RaggedFrames F, int frame_dim, int cart,
+                                                                             const int32_t* rank, int64_t n, int64_t n_rigid,
+                                                                             float* trajectory) {
+    __shared__ RaggedRowTable tab;
+    stage_row_table(R, F, &tab);
+    const int64_t r = (int64_t)blockIdx.x * kLossThreads + threadIdx.x, t = blockIdx.y;
+    if (r >= n) return;
+    const int64_t j = rank[r];
+    if (j < 0 || j >= n_rigid) return;
+    const int g = graph_of_row(&tab, R.n_graphs, r);
+    const int64_t lo = tab.off[g], n_g = tab.off[g + 1] - lo;
+    const float* f = tab.frames[g] + ((size_t)t * n_g + (r - lo)) * frame_dim + cart;
+    float* o = trajectory + ((size_t)t * n_rigid + j) * 3;
+    o[0] = f[0]; o[1] = f[1]; o[2] = f[2];
+}
+
 constexpr int64_t kRolloutStepsMax = 32768;   // the step is a grid dimension of the launches above
 
 int check_rollout_loss_args(const gm_feature_desc* fd, int64_t n, int64_t steps, int frame_dim, int material_col, const double* pos_scale,
@@ -325,6 +497,44 @@ int run_rollout_loss(const RolloutLossArgs& a, const double* pos_scale, const Ro
         hipLaunchKernelGGL(rollout_l1_grad_kernel, dim3(g, (unsigned)(a.steps + a.k)), dim3(kLossThreads), 0, s, a, ps, w.state, d_records,
                            d_final);
         GM_LAUNCH_CHECK();
+    }
+    return GM_OK;
+}
+
+// the launches of a ragged rollout loss; the arguments are checked.  a.n: the total rows, a.frames unused.
+int run_rollout_loss_ragged(const RolloutLossArgs& a, const RaggedOffsets& R, const RaggedFrames& F, const double* pos_scale,
+                            const RolloutLossRaggedWs& w, double* losses_out, int64_t* rows_out, float* d_records, float* d_final,
+                            hipStream_t s) {
+    PosScale ps{{1.0, 1.0, 1.0}};
+    for (int c = 0; pos_scale && c < 3; ++c) ps.s[c] = pos_scale[c];
+    unsigned gmax = 1;
+    for (int g = 0; g < R.n_graphs; ++g) gmax = std::max(gmax, loss_grid_of(R.off[g + 1] - R.off[g]));
+    hipLaunchKernelGGL(rollout_l1_partials_ragged_kernel, dim3(gmax, (unsigned)R.n_graphs), dim3(kLossThreads), 0, s, a, R, F, w.part_sum,
+                       w.part_cnt);
+    GM_LAUNCH_CHECK();
+    hipLaunchKernelGGL(rollout_l1_finish_ragged_kernel, dim3((unsigned)R.n_graphs), dim3(kLossThreads), 0, s, w.part_sum, w.part_cnt, R, a.steps,
+                       ps, w.graph, losses_out, rows_out);
+    GM_LAUNCH_CHECK();
+    hipLaunchKernelGGL(rollout_l1_total_ragged_kernel, dim3(1), dim3(1), 0, s, w.graph, R.n_graphs, w.state);
+    GM_LAUNCH_CHECK();
+    if (d_records && d_final) {
+        hipLaunchKernelGGL(rollout_l1_grad_ragged_kernel, dim3(loss_grid(a.n), (unsigned)(a.steps + a.k)), dim3(kLossThreads), 0, s, a, R, F, ps,
+                           w.graph, d_records, d_final);
+        GM_LAUNCH_CHECK();
+    }
+    return GM_OK;
+}
+// the table and the frame pointers of a ragged loss, checked
+int ragged_loss_table(const char* who, const gm_feature_desc* fd, const int64_t* offsets_host, int64_t n_graphs, int K, const void* ws,
+                      const float* const* frames_host, RaggedOffsets* R, RaggedFrames* F) {
+    GM_REQUIRE(fd && ws && frames_host, GM_ERR_INVALID_ARGUMENT, "%s: null pointer", who);
+    GM_REQUIRE(fd->nodes_per_graph == 0, GM_ERR_INVALID_ARGUMENT, "%s: nodes_per_graph=%lld, must be 0 (the graphs come in graph_offsets)", who,
+               (long long)fd->nodes_per_graph);
+    const int rc = ragged_offsets(offsets_host, n_graphs, fd->conn_r, K, ws, who, R);
+    if (rc != GM_OK) return rc;
+    for (int g = 0; g < GM_RAGGED_MAX_GRAPHS; ++g) {
+        F->p[g] = g < R->n_graphs ? frames_host[g] : nullptr;
+        GM_REQUIRE(g >= R->n_graphs || F->p[g], GM_ERR_INVALID_ARGUMENT, "%s: null pointer (frames[%d])", who, g);
     }
     return GM_OK;
 }
@@ -386,6 +596,13 @@ __global__ void accum_add_kernel(const LossState* st, AccumRecord* acc) {
     acc->samples += 1;
     acc->loss_sum += st->loss;
     if (st->skip) acc->bad += 1;
+}
+
+// One thread: the graphs of a ragged rollout batch join the mini-batch together.  st: run_rollout_loss_ragged's.
+__global__ void accum_add_batch_kernel(const LossState* st, AccumRecord* acc, int n_graphs) {
+    acc->samples += n_graphs;
+    acc->bad += st->skip;
+    acc->loss_sum += st->loss;
 }
 
 // The float64 sum of squares, l1_partials_kernel's shape.  Pass 1: a thread walks its 16-byte groups in a fixed stride, then its
@@ -635,8 +852,9 @@ bool rollout_step_sizes_ok(const gm_model_desc* d, const gm_feature_desc* fd, in
     return d && fd && n >= 1 && n_rigid >= 0 && n_rigid <= n && K >= 1 && steps >= 1 && steps <= kRolloutStepsMax && fd->k_steps >= 2 &&
            fd->k_steps <= 64 && fd->data_dim >= 4 && n < ((int64_t)1 << 31) / K;
 }
+// loss_bytes: the loss's workspace (0: gm_rollout_l1_loss's; a ragged batch passes gm_rollout_l1_loss_ragged's)
 RolloutStepWs carve_rollout_step(void* ws, const gm_model_desc* d, const gm_feature_desc* fd, int64_t n, int64_t n_rigid, int K,
-                                 int64_t steps) {
+                                 int64_t steps, size_t loss_bytes = 0) {
     RolloutStepWs w;
     const size_t window = (size_t)fd->k_steps * n * fd->data_dim;
     w.rollout_bytes = gm_rollout_workspace_bytes(d, n, K);
@@ -647,7 +865,7 @@ RolloutStepWs carve_rollout_step(void* ws, const gm_model_desc* d, const gm_feat
     w.d_final = c.take<float>(window);
     w.d_obs0 = c.take<float>(window);
     w.trajectory = c.take<float>((size_t)steps * n_rigid * 3);
-    w.loss = c.take<char>(carve_rollout_loss(nullptr).bytes);
+    w.loss = c.take<char>(loss_bytes ? loss_bytes : carve_rollout_loss(nullptr).bytes);
     w.rollout = c.take<char>(w.rollout_bytes);
     w.sweep = c.take<char>(w.sweep_bytes);
     w.bytes = c.used();
@@ -1053,6 +1271,105 @@ int gm_train_rollout_accumulate(gm_trainer* t, const float* obs0, int64_t n, con
                                 const double* pos_scale, double* loss_out, void* ws, size_t ws_bytes, void* stream) {
     return train_rollout(t, obs0, n, fd, K, rigid_rank, n_rigid, frames, frame_dim, steps, material_col, pos_scale, 0.0, kRolloutAccumulate,
                          loss_out, ws, ws_bytes, stream, __func__);
+}
+
+// ---- the same on a ragged batch of rollout windows
+size_t gm_rollout_l1_loss_ragged_workspace_bytes(int64_t n_graphs) {
+    if (n_graphs < 1 || n_graphs > GM_RAGGED_MAX_GRAPHS) return 0;
+    return carve_rollout_loss_ragged(nullptr, n_graphs).bytes;
+}
+
+int gm_rollout_l1_loss_ragged(const float* windows, const float* final_state, const float* const* frames_host, int frame_dim, int64_t steps,
+                              const int64_t* graph_offsets_host, int64_t n_graphs, const gm_feature_desc* fd, const int32_t* rigid_rank,
+                              int material_col, const double* pos_scale, double* losses_out, int64_t* rows_counted_out, float* d_records,
+                              float* d_final, void* ws, size_t ws_bytes, void* stream) {
+    RaggedOffsets R;
+    RaggedFrames F;
+    int rc = ragged_loss_table(__func__, fd, graph_offsets_host, n_graphs, 1, ws, frames_host, &R, &F);
+    if (rc != GM_OK) return rc;
+    const int64_t n = R.off[R.n_graphs];
+    rc = check_rollout_loss_args(fd, n, steps, frame_dim, material_col, pos_scale, __func__);
+    if (rc != GM_OK) return rc;
+    GM_REQUIRE(windows && final_state && losses_out, GM_ERR_INVALID_ARGUMENT, "%s: null pointer", __func__);
+    GM_REQUIRE((d_records != nullptr) == (d_final != nullptr), GM_ERR_INVALID_ARGUMENT, "%s: d_records and d_final go together", __func__);
+    const RolloutLossRaggedWs w = carve_rollout_loss_ragged(ws, n_graphs);
+    GM_REQUIRE(ws_bytes >= w.bytes, GM_ERR_WORKSPACE, "%s: workspace %zu < %zu", __func__, ws_bytes, w.bytes);
+    gm::DevGuard dev_guard(windows);
+    const RolloutLossArgs a{windows, final_state, nullptr, rigid_rank, n, steps, fd->k_steps, fd->data_dim, frame_dim, fd->cart_col,
+                            material_col < 0 ? -1 : material_col};
+    return run_rollout_loss_ragged(a, R, F, pos_scale, w, losses_out, rows_counted_out, d_records, d_final, (hipStream_t)stream);
+}
+
+size_t gm_train_rollout_ragged_workspace_bytes(const gm_model_desc* desc, const gm_feature_desc* fdesc, int64_t n_total, int64_t n_rigid_total,
+                                               int64_t n_graphs, int K, int64_t steps) {
+    if (n_graphs < 1 || n_graphs > GM_RAGGED_MAX_GRAPHS || n_total < n_graphs) return 0;
+    if (!rollout_step_sizes_ok(desc, fdesc, n_total, n_rigid_total, K, steps)) return 0;
+    return carve_rollout_step(nullptr, desc, fdesc, n_total, n_rigid_total, K, steps, carve_rollout_loss_ragged(nullptr, n_graphs).bytes).bytes;
+}
+
+// train_rollout's accumulate (update != 0) and evaluate (update == 0) on a mini-batch of rollout windows as ONE ragged rollout, one
+// loss, one sweep and one update of the mini-batch's record
+int gm_train_rollout_accumulate_ragged(gm_trainer* t, const float* obs0, const int64_t* graph_offsets_host, int64_t n_graphs,
+                                       const gm_feature_desc* fd, int K, const int32_t* rigid_rank, int64_t n_rigid,
+                                       const float* const* frames_host, int frame_dim, int64_t steps, int material_col,
+                                       const double* pos_scale, int update, double* losses_out, void* ws, size_t ws_bytes, void* stream) {
+    const char* who = __func__;
+    GM_REQUIRE(t, GM_ERR_INVALID_ARGUMENT, "%s: null trainer", who);
+    gm_model* m = t->m;
+    RaggedOffsets R;
+    RaggedFrames F;
+    int rc = ragged_loss_table(who, fd, graph_offsets_host, n_graphs, K, ws, frames_host, &R, &F);
+    if (rc != GM_OK) return rc;
+    const int64_t n = R.off[R.n_graphs];
+    rc = check_rollout_loss_args(fd, n, steps, frame_dim, material_col, pos_scale, who);
+    if (rc != GM_OK) return rc;
+    GM_REQUIRE(rollout_step_sizes_ok(&m->d, fd, n, n_rigid, K, steps), GM_ERR_INVALID_ARGUMENT,
+               "%s: sizes out of range (n_nodes=%lld, n_rigid=%lld, max_neighbours=%d)", who, (long long)n, (long long)n_rigid, K);
+    GM_REQUIRE(obs0 && losses_out && (rigid_rank || n_rigid == 0), GM_ERR_INVALID_ARGUMENT, "%s: null pointer", who);
+    rc = gm::check_model_for_scene(m->d, fd, who);
+    if (rc != GM_OK) return rc;
+    const size_t loss_bytes = carve_rollout_loss_ragged(nullptr, n_graphs).bytes;
+    const RolloutStepWs w = carve_rollout_step(ws, &m->d, fd, n, n_rigid, K, steps, loss_bytes);
+    GM_REQUIRE(ws_bytes >= w.bytes, GM_ERR_WORKSPACE, "%s: workspace %zu < %zu", who, ws_bytes, w.bytes);
+    GM_REQUIRE(!update || t->pending >= 0, GM_ERR_INVALID_ARGUMENT, "%s: no mini-batch begun (gm_trainer_begin)", who);
+    gm::DevGuard dev_guard(obs0);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t pending = t->pending;
+    if (update) t->pending = -1;   // a failing accumulate leaves the mini-batch undefined
+    const size_t window = (size_t)fd->k_steps * n * fd->data_dim;
+    const bool scripted = n_rigid > 0;
+    const float* trajectory = scripted ? w.trajectory : nullptr;
+
+    // 1. the recorded poses of every graph's rigid rows as one trajectory [steps, n_rigid, 3]: ranks are global
+    if (scripted) {
+        hipLaunchKernelGGL(recorded_poses_ragged_kernel, dim3((unsigned)cdiv(n, kLossThreads), (unsigned)steps), dim3(kLossThreads), 0, s, R, F,
+                           frame_dim, fd->cart_col, rigid_rank, n, n_rigid, w.trajectory);
+        GM_LAUNCH_CHECK();
+    }
+    // 2. the ragged inference rollout keeping its windows
+    GM_HIP_CHECK(hipMemcpyAsync(w.windows, obs0, window * sizeof(float), hipMemcpyDeviceToDevice, s));
+    for (int64_t i = 0; i < steps; ++i) {
+        float* next = w.windows + (size_t)(i + 1) * window;
+        GM_HIP_CHECK(hipMemcpyAsync(next, next - window, window * sizeof(float), hipMemcpyDeviceToDevice, s));
+        rc = gm_rollout_step_ragged(m, next, graph_offsets_host, n_graphs, fd, K, rigid_rank,
+                                    scripted ? trajectory + (size_t)i * n_rigid * 3 : nullptr, nullptr, w.rollout, w.rollout_bytes, stream);
+        if (rc != GM_OK) return rc;
+    }
+    // 3. one loss per graph and the mini-batch's state, and for an update the transpose
+    const RolloutLossArgs a{w.windows, w.windows + (size_t)steps * window, nullptr, rigid_rank, n, steps, fd->k_steps, fd->data_dim, frame_dim,
+                            fd->cart_col, material_col < 0 ? -1 : material_col};
+    const RolloutLossRaggedWs lw = carve_rollout_loss_ragged(w.loss, n_graphs);
+    rc = run_rollout_loss_ragged(a, R, F, pos_scale, lw, losses_out, nullptr, update ? w.d_records : nullptr, update ? w.d_final : nullptr, s);
+    if (rc != GM_OK || !update) return rc;
+    // 4. one sweep into the trainer's gradients, one launch on the mini-batch's record
+    rc = gm_rollout_backward_train_ragged(m, t->T.data(), (int)t->T.size(), w.windows, graph_offsets_host, n_graphs, fd, K, rigid_rank,
+                                          trajectory, scripted ? steps : 0, n_rigid, steps, w.d_final, w.d_records, t->G.data(), w.d_obs0,
+                                          nullptr, w.sweep, w.sweep_bytes, stream);
+    if (rc != GM_OK) return rc;
+    hipLaunchKernelGGL(accum_add_batch_kernel, dim3(1), dim3(1), 0, s, lw.state, t->acc, (int)n_graphs);
+    GM_LAUNCH_CHECK();
+    t->pending = pending + n_graphs;
+    return GM_OK;
 }
 
 int gm_trainer_record(const gm_trainer* t, void* record_host, void* stream) {

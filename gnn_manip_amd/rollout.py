@@ -170,8 +170,8 @@ class RolloutEngine:
     RENUMBER_MIN_NODES = 20000
     RENUMBER_EVERY = 64
 
-    def __init__(self, model, graph_attr, n_nodes, k_steps=6, data_dim=None, max_neighbours=20, device="cuda:0",
-                 candidates=1, renumber="auto"):
+    def __init__(self, model, graph_attr, n_nodes=None, k_steps=6, data_dim=None, max_neighbours=20, device="cuda:0",
+                 candidates=1, renumber="auto", sizes=None):
         """candidates > 1: the engine steps that many equal-sized scenes at once, stored back to back along the
         node axis ([k, candidates*n_nodes, D]); the radius graph never links two scenes (block-diagonal batch,
         the offset rule of collate_utils.py:76), everything else is per node / per edge.
@@ -183,10 +183,37 @@ class RolloutEngine:
         fraction of a cell per step), and to write the result back in the caller's numbering.  A radius graph does not depend on the numbering
         (neighbours are ranked by distance; only an exact tie in distance falls back on the index) and every per-node /
         per-edge function is numbering-free, so what changes is the order in which a node's incoming messages are
-        summed: float32 rounding, far inside the 1e-5 parity bound."""
+        summed: float32 rounding, far inside the 1e-5 parity bound.
+
+        sizes=[n0, n1, ...] (with n_nodes=None): a RAGGED engine, which steps scenes of these sizes at once, stored back to back
+        along the node axis ([k, n0 + n1 + ..., D]; ``offsets``, ``rows(g)``), through the library's ``_ragged`` entry points:
+        ``step``, ``run``, ``run_recorded``, ``rollout``, ``set_scene`` and ``status``.  The rows of scene g are bit for bit what
+        an engine of n_g nodes computes for that scene alone (include/gnn_manip_hip.h states the one condition).  Rigid ranks are
+        global: row j of a pose array belongs to the j-th rigid row of the assembled window, scene 0's first.  Up to 64 scenes;
+        equal sizes are allowed.  ``step_backward`` and ``differentiable_rollout(sweep="library", record=, params=)`` run the
+        library's ragged sweeps on it.  A ragged engine does not renumber (``renumber=True`` raises ValueError); ``differentiable_step``,
+        ``sweep="autograd"`` and ``rollout_candidates`` raise ValueError on it."""
         self.model = model
         self.graph_attr = graph_attr
         self.candidates = int(candidates)
+        self.offsets = self._offsets_host = None
+        if sizes is not None:
+            sizes = [int(v) for v in sizes]
+            if n_nodes is not None or self.candidates != 1:
+                raise ValueError("RolloutEngine: sizes= describes the whole batch; give neither n_nodes nor candidates with it")
+            if not 1 <= len(sizes) <= 64 or min(sizes) < 1:
+                raise ValueError(f"RolloutEngine: sizes must be 1..64 scenes of at least one node each, got {sizes}")
+            if renumber is True:
+                raise ValueError("RolloutEngine: a ragged engine (sizes=) does not renumber")
+            renumber = False
+            self.offsets = [0]
+            for v in sizes:
+                self.offsets.append(self.offsets[-1] + v)
+            self._offsets_host = (C.c_int64 * len(self.offsets))(*self.offsets)   # read by the library during each call
+            n_nodes = self.offsets[-1]
+        elif n_nodes is None:
+            raise ValueError("RolloutEngine needs n_nodes or sizes")
+        self.sizes = sizes
         self.n_per = int(n_nodes)
         self.n = int(n_nodes) * self.candidates
         self.k = int(k_steps)
@@ -208,6 +235,20 @@ class RolloutEngine:
             renumber = os.environ["GM_RENUMBER"] == "1"
         self.renumber = (self.n_per >= self.RENUMBER_MIN_NODES) if renumber == "auto" else bool(renumber)
         self._renumber_ws = None
+
+    @property
+    def ragged(self):
+        return getattr(self, "sizes", None) is not None
+
+    def rows(self, g):
+        """The rows of scene g of a ragged engine's arrays, as a slice of the node axis."""
+        if not self.ragged:
+            raise ValueError("rows(g) is a ragged engine's (sizes=)")
+        return slice(self.offsets[g], self.offsets[g + 1])
+
+    def _no_ragged(self, what):
+        if self.ragged:
+            raise ValueError(f"RolloutEngine.{what} is not available on a ragged engine (sizes=)")
 
     def _rank_rigid(self, obs):
         rank = torch.empty(self.n, dtype=torch.int32, device=self.device)
@@ -256,6 +297,10 @@ class RolloutEngine:
         self._check_state(obs, rigid_target, pred_out, use_rigid)
         handle = self.model.device_handle(self.device)
         rr = self.rigid_rank if use_rigid else None
+        if self.ragged:
+            check(lib().gm_rollout_step_ragged(handle, ptr(obs), self._offsets_host, len(self.sizes), C.byref(self.fdesc), self.max_neighbours,
+                                               ptr(rr), ptr(rigid_target), ptr(pred_out), ptr(self.ws), self.ws.numel(), current_stream()))
+            return
         check(lib().gm_rollout_step(handle, ptr(obs), self.n, C.byref(self.fdesc), self.max_neighbours, ptr(rr),
                                     ptr(rigid_target), ptr(pred_out), ptr(self.ws), self.ws.numel(), current_stream()))
 
@@ -274,6 +319,7 @@ class RolloutEngine:
 
         inputs_only: the model's parameters are constants of the step whatever their requires_grad flags say
         (``EncProcDecGNN.forward_inputs_only``: no weight-gradient work in the backward, no parameter's ``.grad`` touched)."""
+        self._no_ragged("differentiable_step")
         self._check_state(obs, rigid_target, None, True)
         ga = self.graph_attr
         c0 = ga.cartesian_idx[0]
@@ -351,9 +397,12 @@ class RolloutEngine:
         d_obs = torch.empty_like(obs_before)
         d_tgt = None if rigid_target is None else torch.empty_like(rigid_target)
         e = C.c_int64(0)
-        check(lib().gm_rollout_step_backward_train(h, t_arr, len(tensors), ptr(obs_before), self.n, C.byref(self.fdesc), self.max_neighbours,
-                                                   ptr(self.rigid_rank), ptr(rigid_target), ptr(d_obs_after), ptr(d_record), g_arr,
-                                                   ptr(d_obs), ptr(d_tgt), C.byref(e), ptr(ws), ws.numel(), current_stream()))
+        tail = (C.byref(self.fdesc), self.max_neighbours, ptr(self.rigid_rank), ptr(rigid_target), ptr(d_obs_after), ptr(d_record), g_arr,
+                ptr(d_obs), ptr(d_tgt), C.byref(e), ptr(ws), ws.numel(), current_stream())
+        if self.ragged:
+            check(lib().gm_rollout_step_backward_train_ragged(h, t_arr, len(tensors), ptr(obs_before), self._offsets_host, len(self.sizes), *tail))
+        else:
+            check(lib().gm_rollout_step_backward_train(h, t_arr, len(tensors), ptr(obs_before), self.n, *tail))
         return (d_obs, d_tgt, int(e.value)) if return_edge_count else (d_obs, d_tgt)
 
     def _sweep_backward(self, windows, traj, steps, d_final, scene, need_traj, d_records=None, model=None, grads=None):
@@ -373,9 +422,12 @@ class RolloutEngine:
         d_obs0 = torch.empty_like(d_final)
         d_traj = torch.empty_like(traj) if need_traj else None
         n_targets = 0 if traj is None else int(traj.shape[0])
-        check(lib().gm_rollout_backward_train(h, t_arr, len(tensors), ptr(windows), self.n, C.byref(self.fdesc), self.max_neighbours,
-                                              ptr(rank), ptr(traj), n_targets, n_rigid, steps, ptr(d_final), ptr(d_records), g_arr,
-                                              ptr(d_obs0), ptr(d_traj), ptr(ws), ws.numel(), current_stream()))
+        tail = (C.byref(self.fdesc), self.max_neighbours, ptr(rank), ptr(traj), n_targets, n_rigid, steps, ptr(d_final), ptr(d_records), g_arr,
+                ptr(d_obs0), ptr(d_traj), ptr(ws), ws.numel(), current_stream())
+        if self.ragged:
+            check(lib().gm_rollout_backward_train_ragged(h, t_arr, len(tensors), ptr(windows), self._offsets_host, len(self.sizes), *tail))
+        else:
+            check(lib().gm_rollout_backward_train(h, t_arr, len(tensors), ptr(windows), self.n, *tail))
         return d_obs0, d_traj
 
     def differentiable_rollout(self, obs0, trajectory=None, horizon=None, return_edges=False, sweep="autograd", record=False,
@@ -419,6 +471,8 @@ class RolloutEngine:
         if sweep != "library" and (record or params):
             raise ValueError("record=True / params=True need sweep='library' (the autograd sweep returns the final state alone, "
                              "with the parameters as constants)")
+        if self.ragged and sweep != "library":
+            raise ValueError("a ragged engine (sizes=) has the library's sweep only: differentiable_rollout(sweep='library')")
         steps = int(horizon) if horizon is not None else (int(trajectory.shape[0]) if trajectory is not None else 0)
         self._check_state(obs0, None, None, False)
         if trajectory is not None:
@@ -450,6 +504,11 @@ class RolloutEngine:
             self._check_tensor(trajectory, "trajectory", ("T", self.n_rigid, 3))
         recs = torch.empty((steps, self.n, self.data_dim), dtype=torch.float32, device=self.device) if record else None
         handle = self.model.device_handle(self.device)  # resolved once per rollout
+        if self.ragged:
+            check(lib().gm_rollout_ragged(handle, ptr(obs), self._offsets_host, len(self.sizes), C.byref(self.fdesc), self.max_neighbours,
+                                          ptr(self.rigid_rank), ptr(trajectory), T, self.n_rigid, steps, ptr(recs), ptr(self.ws),
+                                          self.ws.numel(), current_stream()))
+            return recs
         every, rws = self._renumbering(steps)
         check(lib().gm_rollout(handle, ptr(obs), self.n, C.byref(self.fdesc), self.max_neighbours, ptr(self.rigid_rank),
                            ptr(trajectory), T, self.n_rigid, steps, ptr(recs), every, ptr(rws), 0 if rws is None else rws.numel(),
@@ -482,6 +541,11 @@ class RolloutEngine:
         recs = torch.empty((steps, self.n, self.data_dim), dtype=torch.float32, device=self.device) if record else None
         preds = torch.empty((steps, self.n, 3), dtype=torch.float32, device=self.device) if record_pred else None
         handle = self.model.device_handle(self.device)
+        if self.ragged:
+            check(lib().gm_rollout_recorded_ragged(handle, ptr(obs), self._offsets_host, len(self.sizes), C.byref(self.fdesc),
+                                                   self.max_neighbours, ptr(self.rigid_rank), ptr(frames), steps, ptr(recs), ptr(preds),
+                                                   ptr(self.ws), self.ws.numel(), current_stream()))
+            return recs, preds
         every, rws = self._renumbering(steps)
         check(lib().gm_rollout_recorded(handle, ptr(obs), self.n, C.byref(self.fdesc), self.max_neighbours, ptr(self.rigid_rank),
                                         ptr(frames), steps, ptr(recs), ptr(preds), every, ptr(rws), 0 if rws is None else rws.numel(),
@@ -492,6 +556,7 @@ class RolloutEngine:
         """Roll `candidates` copies of one initial state [k, N, D] under per-candidate scripted rigid poses
         `trajectories` [B, T, N_rigid, 3] (the CMA-ES population of traj_utils.py:247-259, evaluated together
         instead of serially).  Returns the final states [B, k, N, D]."""
+        self._no_ragged("rollout_candidates")
         b, k, n = self.candidates, self.k, self.n_per
         assert trajectories.shape[0] == b
         obs = obs0.unsqueeze(1).repeat(1, b, 1, 1).reshape(k, b * n, self.data_dim).contiguous()
@@ -579,7 +644,8 @@ def _recorded_frames(sim, graph_attr, material_id):
     return torch.cat((sim, ctr), dim=-1).contiguous()
 
 
-def evaluate_rollout(dataset_or_sims, model, graph_attr=None, k_steps=6, max_neighbours=20, sinkhorn=True, blur=0.05, pair_block=None):
+def evaluate_rollout(dataset_or_sims, model, graph_attr=None, k_steps=6, max_neighbours=20, sinkhorn=True, blur=0.05, pair_block=None,
+                     ragged=False):
     """How good is ``model`` on recorded simulations: the numbers of the reference's model comparison
     (scripts/plot_rmses.py:176-198), computed on the device.
 
@@ -587,7 +653,10 @@ def evaluate_rollout(dataset_or_sims, model, graph_attr=None, k_steps=6, max_nei
     [T, N, D] float32 device tensors with ``graph_attr`` given.  Each simulation is rolled T - k steps from its first window under
     the recorded drive (``RolloutEngine.run_recorded``: compute_rollout's ground-truth mode).  Simulations of equal (T, N) are
     evaluated together as one block-diagonal batch, others in groups of their own, in the order they first appear; one
-    ``status()`` per group, after its rollout.
+    ``status()`` per group, after its rollout.  ragged=True: simulations of equal T on one device form ONE group whatever their N
+    (at most 64 to a group), rolled as a ragged batch -- one engine (``RolloutEngine(sizes=...)``), one ``run_recorded``, one
+    ``status()`` and one gm_rollout_errors_ragged per group; every tensor and every float returned is the default call's, bit for
+    bit.  The Sinkhorn part groups the clouds by their number of coffee rows either way.
 
     Returns a list, one dict per simulation, in the order given:
       prediction, groundtruth   [steps, N, D] device tensors: the records of the rollout (the reference's ``prediction``) and
@@ -625,16 +694,27 @@ def evaluate_rollout(dataset_or_sims, model, graph_attr=None, k_steps=6, max_nei
         _need_cuda(sim, "every simulation")
         if sim.dim() != 3 or sim.shape[0] <= k:
             raise ValueError(f"evaluate_rollout: simulation {s} must be [T > {k}, N, D], got {tuple(sim.shape)}")
-        groups.setdefault((int(sim.shape[0]), int(sim.shape[1]), sim.device), []).append(s)
+        key = (int(sim.shape[0]), None if ragged else int(sim.shape[1]), sim.device)
+        part = 0   # a ragged group takes what one table holds; the simulations beyond it open the next group
+        while ragged and len(groups.get(key + (part,), ())) >= 64:
+            part += 1
+        groups.setdefault(key + (part,), []).append(s)
     loss = SamplesLoss("sinkhorn", p=2, blur=blur) if sinkhorn else None
     results = [None] * len(sims)
     with torch.no_grad():
-        for (T, n, dev), members in groups.items():
+        for (T, _, dev, _), members in groups.items():
             G, steps = len(members), T - k
+            off = [0]
+            for s in members:
+                off.append(off[-1] + int(sims[s].shape[1]))
             # the group's recording, simulations back to back along the node axis: [T, G * n, D]
             rec = torch.cat([_recorded_frames(sims[s], graph_attr, mat) for s in members], dim=1).contiguous()
             dd = int(rec.shape[2])
-            eng = RolloutEngine(model, graph_attr, n, k_steps=k, data_dim=dd, max_neighbours=max_neighbours, device=dev, candidates=G)
+            if ragged:
+                eng = RolloutEngine(model, graph_attr, k_steps=k, data_dim=dd, max_neighbours=max_neighbours, device=dev,
+                                    sizes=[b - a for a, b in zip(off, off[1:])])
+            else:
+                eng = RolloutEngine(model, graph_attr, off[1], k_steps=k, data_dim=dd, max_neighbours=max_neighbours, device=dev, candidates=G)
             obs = rec[:k].clone().contiguous()
             if graph_attr.control_idx is not None:   # the first window as the dataset stores it: every frame's control looks at frame k
                 u0 = graph_attr.control_idx[0]
@@ -645,12 +725,16 @@ def evaluate_rollout(dataset_or_sims, model, graph_attr=None, k_steps=6, max_nei
             pred, acc = eng.run_recorded(obs, frames, steps, record=True, record_pred=True)
             eng.status()
             sums = torch.empty((steps, G, 4), dtype=torch.float64, device=dev)
-            check(lib().gm_rollout_errors(ptr(pred), ptr(acc), ptr(rec), T, k - 1, steps, eng.n, C.byref(eng.fdesc), ptr(sums),
-                                          current_stream()))
+            if ragged:
+                check(lib().gm_rollout_errors_ragged(ptr(pred), ptr(acc), ptr(rec), T, k - 1, steps, eng._offsets_host, G, C.byref(eng.fdesc),
+                                                     ptr(sums), current_stream()))
+            else:
+                check(lib().gm_rollout_errors(ptr(pred), ptr(acc), ptr(rec), T, k - 1, steps, eng.n, C.byref(eng.fdesc), ptr(sums),
+                                              current_stream()))
             sums = sums.cpu()
             coffee = rec[0, :, mat] == 0
             for g, s in enumerate(members):
-                rows = slice(g * n, (g + 1) * n)
+                rows, n = slice(off[g], off[g + 1]), off[g + 1] - off[g]
                 res = dict(prediction=pred[:, rows], groundtruth=frames[:, rows], acceleration=acc[:, rows], sums=sums[:, g].clone())
                 tot = res["sums"].sum(dim=0)
                 cnt = float(res["sums"][0, 3])
@@ -667,7 +751,7 @@ def evaluate_rollout(dataset_or_sims, model, graph_attr=None, k_steps=6, max_nei
             # many of them stacked into one list of pairs, which goes through SamplesLoss.batched block by block
             clouds = {}
             for g, s in enumerate(members):
-                idx = torch.nonzero(coffee[g * n:(g + 1) * n]).flatten() + g * n
+                idx = torch.nonzero(coffee[off[g]:off[g + 1]]).flatten() + off[g]
                 if idx.numel() > 0:
                     clouds.setdefault(int(idx.numel()), []).append((s, idx))
             for nc, items in clouds.items():

@@ -272,6 +272,76 @@ class Trainer:
         gm_train_rollout_accumulate.  Samples of different scenes and sizes may share a mini-batch."""
         self._accumulated(lambda: self._rollout(engine, obs0, frames, steps, pos_scale, loss_out, state_material_col, "accumulate"))
 
+    def accumulate_rollout_batch(self, engine, obs0, frames_list, steps=None, pos_scale=None, losses_out=None, state_material_col=None):
+        """Adds a whole mini-batch of rollout windows of different sizes to the pending mini-batch as ONE ragged rollout, one loss,
+        one reverse sweep and one update of the mini-batch's record: gm_train_rollout_accumulate_ragged.  ``engine`` is a ragged
+        ``RolloutEngine(sizes=...)`` after ``set_scene(obs0)``; ``obs0`` [k, N, D] holds the windows side by side along the node
+        axis; ``frames_list`` holds one [>= steps, n_g, D or D - 3] tensor per scene (views into resident recordings).  Every
+        scene counts as one sample with its own loss (``accumulate_rollout``'s, with that scene's row count): ``apply`` divides by
+        the number of scenes.  ``losses_out``: a float64 device tensor of one element per scene, or None.  The sweep reads one edge
+        count per step back for the WHOLE batch.  Not on a distributed trainer."""
+        self._not_distributed("accumulate_rollout_batch")
+        self._accumulated(lambda: self._rollout_batch(engine, obs0, frames_list, steps, pos_scale, losses_out, state_material_col, 1))
+
+    def evaluate_rollout_batch(self, engine, obs0, frames_list, steps=None, pos_scale=None, losses_out=None, state_material_col=None):
+        """``accumulate_rollout_batch``'s rollout and per-scene losses without gradients or the record: changes nothing, needs no
+        pending mini-batch and never synchronises."""
+        self._not_distributed("evaluate_rollout_batch")
+        self._rollout_batch(engine, obs0, frames_list, steps, pos_scale, losses_out, state_material_col, 0)
+
+    def _rollout_batch(self, engine, obs0, frames_list, steps, pos_scale, losses_out, state_material_col, update):
+        if not getattr(engine, "ragged", False):
+            raise ValueError("a rollout batch needs a ragged engine: RolloutEngine(model, graph_attr, sizes=[...])")
+        if engine.rigid_rank is None:
+            raise ValueError("engine.set_scene(obs0) must be called before a rollout step")
+        engine._check_tensor(obs0, "obs0", (engine.k, engine.n, engine.data_dim))
+        frames_list = list(frames_list)
+        if len(frames_list) != len(engine.sizes):
+            raise ValueError(f"frames_list must hold one tensor per scene ({len(engine.sizes)}), got {len(frames_list)}")
+        frame_dim = int(frames_list[0].shape[-1]) if isinstance(frames_list[0], torch.Tensor) and frames_list[0].dim() == 3 else -1
+        if frame_dim not in (engine.data_dim, engine.data_dim - 3):
+            raise ValueError(f"frames must have {engine.data_dim} or {engine.data_dim - 3} columns, got {frame_dim}")
+        for g, f in enumerate(frames_list):
+            engine._check_tensor(f, f"frames_list[{g}]", ("steps", engine.sizes[g], frame_dim))
+        most = min(int(f.shape[0]) for f in frames_list)
+        steps = most if steps is None else int(steps)
+        if not 1 <= steps <= most:
+            raise ValueError(f"steps={steps} outside 1..{most}, the frames given")
+        if engine.device != self.device:
+            raise ValueError(f"the engine is on {engine.device}, the trainer on {self.device}")
+        scale = None
+        if pos_scale is not None:
+            scale = [float(v) for v in np.asarray(pos_scale, np.float64).reshape(-1)]
+            if len(scale) != 3 or not all(v == v and v != 0.0 for v in scale):
+                raise ValueError("pos_scale must be three non-zero numbers")
+            scale = (C.c_double * 3)(*scale)
+        col = -1
+        if self.sand_only:
+            col = engine.fdesc.material_col if state_material_col is None else int(state_material_col)
+            if col < 0:
+                col += engine.data_dim
+            if not 0 <= col < engine.data_dim:
+                raise ValueError(f"state_material_col={state_material_col} is outside the {engine.data_dim} state columns")
+        G = len(engine.sizes)
+        if losses_out is None:
+            if getattr(self, "_batch_losses", None) is None or self._batch_losses.numel() < G:
+                self._batch_losses = torch.empty(64, dtype=torch.float64, device=self.device)
+            losses_out = self._batch_losses[:G]
+        elif losses_out.dtype != torch.float64 or losses_out.numel() != G or losses_out.device != self.device or not losses_out.is_contiguous():
+            raise ValueError(f"losses_out must be {G} contiguous float64 elements on the trainer's device")
+        L = lib()
+        need = L.gm_train_rollout_ragged_workspace_bytes(C.byref(self.desc), C.byref(engine.fdesc), engine.n, engine.n_rigid, G,
+                                                         engine.max_neighbours, steps)
+        if need == 0:
+            raise ValueError("Trainer: no rollout workspace for these sizes")
+        if self._rollout_ws is None or self._rollout_ws.numel() < need:
+            self._rollout_ws = _ws(need, self.device)
+        self._kept = (steps + 1, engine.k, engine.n, engine.data_dim)
+        views = (C.c_void_p * G)(*[f.data_ptr() for f in frames_list])     # read during the call: the tensors outlive it in frames_list
+        check(L.gm_train_rollout_accumulate_ragged(self._h, ptr(obs0), engine._offsets_host, G, C.byref(engine.fdesc), engine.max_neighbours,
+                                                   ptr(engine.rigid_rank), engine.n_rigid, views, frame_dim, steps, col, scale, int(update),
+                                                   ptr(losses_out), ptr(self._rollout_ws), self._rollout_ws.numel(), current_stream(obs0)))
+
     def apply(self, loss_out=None, norm_out=None, want_norm=False, samples_total=None):
         """One Adam update from the MEAN of the accumulated gradients, clipped to ``max_grad_norm`` (None, <= 0 or inf: no clip)
         by ``clip_grad_norm_``'s formula: gm_trainer_apply.  The mean of the samples' losses goes into ``last_loss`` or
@@ -590,7 +660,7 @@ class Trainer:
         count = int(np.prod(self._kept))
         return self._rollout_ws[:4 * count].view(torch.float32).view(self._kept)
 
-    def fit_rollout_epoch(self, dataset, engine, steps, starts=None, seed=0, pos_scale=None, batch_size=1, shuffle=False):
+    def fit_rollout_epoch(self, dataset, engine, steps, starts=None, seed=0, pos_scale=None, batch_size=1, shuffle=False, batched=False):
         """``step_rollout`` over the samples ``starts`` of ``dataset`` (default: every non-overlapping start, ``steps`` apart, of
         every recording that has ``steps`` frames behind the window), each built by ``dataset.rollout_sample(start, steps, seed,
         stream=start)``.  ``engine.set_scene`` is called whenever the recording changes.  The per-sample losses come back as a
@@ -601,9 +671,19 @@ class Trainer:
         different node counts ``engine`` is a dict {node count: RolloutEngine}; the array then holds one loss per update, the mean over its samples.  ``shuffle``: the starts in a
         permutation seeded by ``seed``.  ``last_epoch_grad_norms`` holds the updates' gradient norms, NaN where none was computed.
 
+        ``batched=True`` with ``batch_size`` > 1: a mini-batch is ONE ragged rollout instead of ``batch_size`` rollouts one after
+        the other -- ``zero_grad``, one ``torch.cat`` of its windows along the node axis, a ragged ``RolloutEngine(sizes=...)`` per
+        distinct tuple of sizes (made at first use and kept for the epoch; ``engine`` may be None: ``graph_attr``, ``k``, the
+        state's width and the neighbour cap come from the dataset, or from the engine(s) given), ``set_scene``,
+        ``accumulate_rollout_batch``, ``apply``.  The losses are those of the unbatched epoch on the same weights; the gradients
+        differ in the order the samples' contributions are added.  Opt-in: INTEGRATION.md 2e has the measurement.
+
         On a distributed trainer every rank passes the same ``starts`` and ``seed``; ``batch_size`` is the GLOBAL mini-batch, of
-        which this rank runs its contiguous block; the losses and norms are the global ones, the same on every rank."""
+        which this rank runs its contiguous block; the losses and norms are the global ones, the same on every rank.
+        ``batched=True`` raises ValueError there."""
         steps = int(steps)
+        if batched and self._dp is not None:
+            raise ValueError("fit_rollout_epoch(batched=True) is not available on a distributed trainer")
         if starts is None:
             starts, first = [], 0
             for sim in dataset.sims:
@@ -634,6 +714,8 @@ class Trainer:
         def accumulate_one(start):
             eng, window, frames = sample(start)
             self.accumulate_rollout(eng, window, frames, steps, pos_scale=pos_scale)
+        if batched and int(batch_size) > 1:
+            return self._rollout_epoch_batched(dataset, engine, steps, starts, seed, pos_scale, int(batch_size))
         if self._dp is not None:
             return self._epoch_of_shared_mini_batches(starts, batch_size, accumulate_one)
         if int(batch_size) == 1 and self.max_grad_norm is None:
@@ -641,6 +723,32 @@ class Trainer:
             self.last_epoch_grad_norms = np.full(len(losses), np.nan)
             return losses
         return self._epoch_of_mini_batches(starts, batch_size, accumulate_one)
+
+    def _rollout_epoch_batched(self, dataset, engine, steps, starts, seed, pos_scale, size):
+        """fit_rollout_epoch(batched=True): every `size` consecutive starts are one ragged rollout."""
+        from .rollout import RolloutEngine
+        given = next(iter(engine.values())) if isinstance(engine, dict) and engine else (None if isinstance(engine, dict) else engine)
+        engines = {}
+        slots = torch.full((2, max(-(-len(starts) // size), 1)), float("nan"), dtype=torch.float64, device=self.device)   # losses, norms
+        with_norm = self._clipping()
+        updates = 0
+        for first in range(0, len(starts), size):
+            samples = [dataset.rollout_sample(start, steps, seed=seed, stream=start) for start in starts[first:first + size]]
+            sizes = tuple(int(w.shape[1]) for w, _ in samples)
+            if sizes not in engines:
+                window = samples[0][0]
+                engines[sizes] = RolloutEngine(
+                    self.model, dataset.graph_attr if given is None else given.graph_attr, k_steps=int(window.shape[0]),
+                    data_dim=int(window.shape[2]), max_neighbours=getattr(dataset, "max_neighbours", 20) if given is None else given.max_neighbours,
+                    device=self.device, sizes=sizes)
+            eng = engines[sizes]
+            self.zero_grad()
+            obs0 = torch.cat([w for w, _ in samples], dim=1).contiguous()
+            eng.set_scene(obs0)
+            self.accumulate_rollout_batch(eng, obs0, [f for _, f in samples], steps, pos_scale=pos_scale)
+            self.apply(loss_out=slots[0, updates:updates + 1], norm_out=slots[1, updates:updates + 1] if with_norm else None)
+            updates += 1
+        return self._updates_of_epoch(slots, updates)
 
     # ------------------------------------------------------------------------------------------ state
     def record(self):

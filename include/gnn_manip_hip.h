@@ -555,6 +555,53 @@ int gm_rollout_errors(const float* record_last, const float* record_pred,
                       double* sums, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Rollouts of scenes of different sizes as one ragged batch: gm_rollout_step, gm_rollout, gm_rollout_recorded and
+ * gm_rollout_errors for graphs of any sizes stored back to back.  The graphs travel as in gm_radius_graph_build_ragged: graph g
+ * owns rows [graph_offsets_host[g], graph_offsets_host[g + 1]) of every [.., N, ..] array, N = graph_offsets_host[n_graphs]; the
+ * table is read on the host during the call and rides in the kernel arguments (no copy, no allocation, no synchronisation),
+ * 1..GM_RAGGED_MAX_GRAPHS graphs.  fdesc->nodes_per_graph must be 0.  Workspace: gm_rollout_workspace_bytes(desc, N, K) -- the
+ * table adds nothing to it -- and gm_rollout_status(ws, desc, N, K) reads the whole batch's flags and edge count.
+ *
+ * Rows and ranks.  obs [k,N,D], record_last [steps,N,D], record_pred [steps,N,3], frames [steps,N,D] and sim [n_frames,N,D] hold
+ * the graphs' rows side by side along the node axis, in graph order.  rigid_rank [N] is GLOBAL: gm_rigid_rank on the assembled
+ * window numbers the rigid rows of graph g behind those of the graphs before it, and rigid_target(s) [.., n_rigid, 3] hold the
+ * poses in that order (n_rigid = all graphs' rigid rows; a graph may have none).
+ *
+ * Batch invariance.  No edge joins two graphs, every per-row and per-edge function sees its own row only, and the 32-edge block
+ * tables of the processor kernels pad every graph to whole 4-block groups exactly as those of an equal-sized batch do, so a
+ * graph's partial sums do not depend on what shares the launch: the rows of graph g of the state, of every record and of every
+ * prediction are BIT FOR BIT what the single-scene entry point computes for scene g alone, at either precision and with any
+ * gm_model_set_edge_kernel choice.  The one condition: under the automatic kernel choice at hidden 128 the processor's node path
+ * is chosen by the batch's SMALLEST graph (the systolic path only if every graph would take it alone), so all graphs of a batch
+ * must lie on the same side of that size (49 152 rows) -- as every batch of scenes of a few thousand to tens of thousands of rows
+ * does.  A batch of equal sizes equals the nodes_per_graph form, a batch of one graph the plain call.
+ *
+ * There is no renumbering on a ragged batch (no renumber_* arguments).  gm_rollout_errors_ragged writes sums [steps, n_graphs, 4]:
+ * still one workgroup per (step, graph), its threads over that graph's rows, the same fixed tree.
+ *
+ * Refused with GM_ERR_INVALID_ARGUMENT before anything is launched or written: nodes_per_graph != 0, and what
+ * gm_radius_graph_build_ragged refuses of a table (n_graphs outside 1..GM_RAGGED_MAX_GRAPHS, graph_offsets_host[0] != 0, a graph
+ * of fewer than 1 row, N >= 2^30, N * max_neighbours >= 2^31).  A workspace smaller than gm_rollout_workspace_bytes:
+ * GM_ERR_WORKSPACE, likewise before the first launch.
+ * ------------------------------------------------------------------------------------------ */
+int gm_rollout_step_ragged(const gm_model* m, float* obs /*[k,N,D] in/out*/, const int64_t* graph_offsets_host /*[n_graphs+1]*/,
+                           int64_t n_graphs, const gm_feature_desc* fdesc, int max_neighbours, const int32_t* rigid_rank,
+                           const float* rigid_target /*[Nr,3] or NULL*/, float* pred_acc_out /*[N,3] or NULL*/,
+                           void* rollout_ws, size_t rollout_ws_bytes, void* stream);
+int gm_rollout_ragged(const gm_model* m, float* obs /*[k,N,D] in/out*/, const int64_t* graph_offsets_host /*[n_graphs+1]*/,
+                      int64_t n_graphs, const gm_feature_desc* fdesc, int max_neighbours, const int32_t* rigid_rank,
+                      const float* rigid_targets, int64_t n_targets, int64_t n_rigid, int64_t steps, float* record_last,
+                      void* rollout_ws, size_t rollout_ws_bytes, void* stream);
+int gm_rollout_recorded_ragged(const gm_model* m, float* obs, const int64_t* graph_offsets_host /*[n_graphs+1]*/,
+                               int64_t n_graphs, const gm_feature_desc* fdesc, int max_neighbours, const int32_t* rigid_rank,
+                               const float* frames, int64_t steps, float* record_last, float* record_pred,
+                               void* rollout_ws, size_t rollout_ws_bytes, void* stream);
+int gm_rollout_errors_ragged(const float* record_last, const float* record_pred,
+                             const float* sim, int64_t n_frames, int64_t first_frame, int64_t steps,
+                             const int64_t* graph_offsets_host /*[n_graphs+1]*/, int64_t n_graphs,
+                             const gm_feature_desc* fdesc, double* sums, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * The reverse sweep of a rollout (no reference counterpart: the reference's planner is derivative-free, traj_utils.py:247-259).
  * gm_rollout_step_backward is the vector-Jacobian product of ONE gm_rollout_step with the model's parameters as constants:
  * d_obs_before [k,N,D] and d_rigid_target [N_rigid,3] (may be NULL; zeros without a rigid_target) from d_obs_after [k,N,D], the
@@ -632,6 +679,22 @@ int gm_rollout_backward_train(const gm_model* m, const float* const* tensors, in
                               const float* d_final /*[k,N,D]*/, const float* d_records /*[steps,N,D] or NULL*/,
                               float* const* grads /* or NULL */, float* d_obs0 /*[k,N,D]*/,
                               float* d_trajectory /*[n_targets,Nr,3] or NULL*/, void* ws, size_t ws_bytes, void* stream);
+/* The two training sweeps on a ragged batch (see "Rollouts of scenes of different sizes as one ragged batch" above for the table,
+ * the row and rank layout; fdesc->nodes_per_graph must be 0).  A step's graph is gm_radius_graph_build_ragged's; everything else is
+ * per row or per edge, so the input gradients of graph g's rows are those of scene g alone and the parameter gradients are the sum
+ * over the graphs, accumulated edge by edge and row by row in the batch's order.  Still ONE edge-count read per step, for the whole
+ * batch.  d_record / d_records and grads both NULL: the plain vector-Jacobian product (gm_rollout_step_backward /
+ * gm_rollout_backward).  Workspaces: gm_rollout_step_backward_workspace_bytes / gm_rollout_backward_workspace_bytes with N total. */
+int gm_rollout_step_backward_train_ragged(const gm_model* m, const float* const* tensors, int n_tensors, const float* obs_before /*[k,N,D]*/,
+                                          const int64_t* graph_offsets_host /*[n_graphs+1]*/, int64_t n_graphs, const gm_feature_desc* fdesc,
+                                          int max_neighbours, const int32_t* rigid_rank, const float* rigid_target, const float* d_obs_after,
+                                          const float* d_record, float* const* grads, float* d_obs_before, float* d_rigid_target,
+                                          int64_t* n_edges_host, void* ws, size_t ws_bytes, void* stream);
+int gm_rollout_backward_train_ragged(const gm_model* m, const float* const* tensors, int n_tensors, const float* windows /*[steps,k,N,D]*/,
+                                     const int64_t* graph_offsets_host /*[n_graphs+1]*/, int64_t n_graphs, const gm_feature_desc* fdesc,
+                                     int max_neighbours, const int32_t* rigid_rank, const float* trajectory, int64_t n_targets,
+                                     int64_t n_rigid, int64_t steps, const float* d_final, const float* d_records, float* const* grads,
+                                     float* d_obs0, float* d_trajectory, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Training batches from resident recordings (an addition to ABI 7).  Replaces, for a batch of samples, CoffeeDataset's
@@ -886,6 +949,40 @@ int gm_train_rollout_accumulate(gm_trainer* t, const float* obs0 /*[k,N,D]*/, in
                                 const float* frames /*[steps,N,frame_dim]*/, int frame_dim, int64_t steps, int material_col,
                                 const double* pos_scale /* host [3], may be NULL */, double* loss_out /* device, may be NULL */,
                                 void* ws, size_t ws_bytes, void* stream);
+/* A mini-batch of rollout windows of different sizes as ONE ragged rollout (additions to ABI 7; the table, rows and ranks as in
+ * gm_rollout_ragged, fdesc->nodes_per_graph == 0).
+ *
+ * gm_rollout_l1_loss_ragged is gm_rollout_l1_loss per graph.  frames_host [n_graphs] are HOST pointers to device arrays
+ * [steps, n_g, frame_dim] -- views into the graphs' recordings -- which travel by value in the kernel arguments.  losses_out
+ * [n_graphs] (device doubles) and rows_counted_out [n_graphs] (device, may be NULL) are written in full:
+ *     l_g = ((s0 / scale_0 + s1 / scale_1) + s2 / scale_2) / (steps * count_g)
+ * with float64 sums over graph g's counted rows in the order of the single call on graph g alone (its workgroups, its stride): l_g
+ * is that call's loss and does not depend on what shares the batch.  The transpose in d_records [steps,N,D] / d_final [k,N,D], both
+ * written in full, has on graph g's counted rows gm_rollout_l1_loss's element values with count_g in place of count.  The state it
+ * leaves for the launches behind it is the mini-batch's: the sum l_0 + l_1 + ... in graph order (float64) and the number of
+ * non-finite l_g.  Workspace: gm_rollout_l1_loss_ragged_workspace_bytes(n_graphs).
+ *
+ * gm_train_rollout_accumulate_ragged is gm_train_rollout_accumulate on such a batch: one row kernel gathers the recorded poses of
+ * every graph's rigid rows into one trajectory [steps, n_rigid, 3] (global ranks), then ONE ragged rollout keeping its windows, the
+ * loss above, ONE reverse sweep into the trainer's gradients (gm_rollout_backward_train_ragged: one edge-count read per step) and one
+ * single-thread launch on the mini-batch's record: samples += n_graphs, bad += the number of non-finite losses, loss_sum += their
+ * sum.  It needs a begun mini-batch; gm_trainer_apply is unchanged (it divides by samples and skips on bad > 0).  update == 0 stops
+ * after the loss: no gradient, no record, no mini-batch needed, no synchronisation.  losses_out [n_graphs]: device doubles.
+ * Workspace: gm_train_rollout_ragged_workspace_bytes.  Refusals as gm_train_rollout_accumulate's and gm_rollout_ragged's. */
+size_t gm_rollout_l1_loss_ragged_workspace_bytes(int64_t n_graphs);
+int gm_rollout_l1_loss_ragged(const float* windows /*[steps,k,N,D]*/, const float* final_state /*[k,N,D]*/,
+                              const float* const* frames_host /*[n_graphs]*/, int frame_dim, int64_t steps,
+                              const int64_t* graph_offsets_host /*[n_graphs+1]*/, int64_t n_graphs, const gm_feature_desc* fdesc,
+                              const int32_t* rigid_rank, int material_col, const double* pos_scale /* host [3], may be NULL */,
+                              double* losses_out /* device [n_graphs] */, int64_t* rows_counted_out /* device [n_graphs], may be NULL */,
+                              float* d_records, float* d_final, void* ws, size_t ws_bytes, void* stream);
+size_t gm_train_rollout_ragged_workspace_bytes(const gm_model_desc* desc, const gm_feature_desc* fdesc, int64_t n_total,
+                                               int64_t n_rigid_total, int64_t n_graphs, int max_neighbours, int64_t steps);
+int gm_train_rollout_accumulate_ragged(gm_trainer* t, const float* obs0 /*[k,N,D]*/, const int64_t* graph_offsets_host /*[n_graphs+1]*/,
+                                       int64_t n_graphs, const gm_feature_desc* fdesc, int max_neighbours, const int32_t* rigid_rank,
+                                       int64_t n_rigid, const float* const* frames_host /*[n_graphs]*/, int frame_dim, int64_t steps,
+                                       int material_col, const double* pos_scale /* host [3], may be NULL */, int update,
+                                       double* losses_out /* device [n_graphs] */, void* ws, size_t ws_bytes, void* stream);
 int gm_trainer_apply(gm_trainer* t, double lr, double max_grad_norm, double* loss_out /* device, may be NULL */,
                      double* grad_norm_out /* device, may be NULL: non-NULL requests the norm */, void* stream);
 int gm_trainer_accum_record(const gm_trainer* t, void* record_host /* 48 bytes */, void* stream);

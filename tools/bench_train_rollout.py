@@ -14,6 +14,16 @@ window is --samples training steps and ends in a synchronise.  Prints one JSON l
 
     python tools/bench_train_rollout.py [--n 5000] [--horizons 4,8] [--samples 10] [--rounds 5] [--accumulate B] [--max-grad-norm X]
                                         [--variants python,library]
+
+--batched: another measurement -- what a mini-batch of rollout windows buys as ONE ragged rollout.  The recordings have the sizes
+--sizes (a mini-batch of --batch-size windows cycles through them); the two forms of an update alternate in one process:
+
+  sequential  zero_grad, one accumulate_rollout per window on the engine of its size, apply
+  batched     zero_grad, one torch.cat of the windows, set_scene on the ragged engine, accumulate_rollout_batch, apply
+
+and the figure is milliseconds per rollout step PER SAMPLE: the update's time / (batch size x T), median [min, max] over the rounds.
+
+    python tools/bench_train_rollout.py --batched [--sizes 5000,4000] [--batch-size 2] [--horizons 4] [--samples 4] [--rounds 3]
 """
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -24,8 +34,78 @@ import torch
 from bench_loader import recording
 
 
+def batched_main(args):
+    """--batched: a mini-batch as one ragged rollout against the same mini-batch sample by sample."""
+    from gnn_manip_amd import CoffeeDataset, EncProcDecGNN, RolloutEngine, Trainer, scene
+    dev = torch.device("cuda:0")
+    sizes = [int(v) for v in args.sizes.split(",")]
+    B, T = args.batch_size, int(args.horizons.split(",")[0])
+    batch_sizes = [sizes[j % len(sizes)] for j in range(B)]
+    frames_needed = args.k + T * (args.samples + 1)
+    sets = []
+    for j, n in enumerate(batch_sizes):
+        side = 0.152 * (n / 5000.0) ** (1.0 / 3.0) * 0.8
+        sets.append(CoffeeDataset.from_recordings([torch.from_numpy(recording(n, frames_needed, 300 + j, side)).to(dev)], args.k, 0.015,
+                                                  scene.STATS, scene.BOUNDS, scene.CART, scene.MAT[0], scene.CTRL, use_control=True))
+    data = [[ds.rollout_sample(i * T, T) for ds in sets] for i in range(args.samples)]      # [update][sample] (window, frames)
+    torch.manual_seed(0)
+    models = []
+    for _ in range(2):
+        torch.manual_seed(0)
+        m = EncProcDecGNN(3 * (args.k - 1) + 10, 4, 3, args.hidden, 2, 10).to(dev)
+        with torch.no_grad():
+            list(m.parameters())[-2].mul_(1e-3)
+        models.append(m)
+    trainers = [Trainer(m, lr=args.lr) for m in models]
+    singles = [RolloutEngine(models[0], sets[0].graph_attr, n, k_steps=args.k, data_dim=8, device=dev) for n in batch_sizes]
+    ragged = RolloutEngine(models[1], sets[0].graph_attr, k_steps=args.k, data_dim=8, device=dev, sizes=batch_sizes)
+    slot = torch.zeros(1, dtype=torch.float64, device=dev)
+
+    def sequential(update):
+        t = trainers[0]
+        t.zero_grad()
+        for eng, (window, frames) in zip(singles, update):
+            eng.set_scene(window)
+            t.accumulate_rollout(eng, window, frames, T)
+        t.apply(loss_out=slot)
+
+    def batched(update):
+        t = trainers[1]
+        t.zero_grad()
+        obs0 = torch.cat([w for w, _ in update], dim=1).contiguous()
+        ragged.set_scene(obs0)
+        t.accumulate_rollout_batch(ragged, obs0, [f for _, f in update], T)
+        t.apply(loss_out=slot)
+
+    variants = {"sequential": sequential, "batched": batched}
+
+    def window(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for update in data:
+            fn(update)
+        torch.cuda.synchronize()
+        assert np.isfinite(float(slot)), float(slot)
+        return 1e3 * (time.perf_counter() - t0) / (len(data) * B * T)
+    for fn in variants.values():
+        fn(data[0])
+        fn(data[1 % len(data)])
+    rounds = {name: [] for name in variants}
+    for _ in range(args.rounds):
+        for name, fn in variants.items():
+            rounds[name].append(round(window(fn), 3))
+    res = {name: {"rounds": r, "median": float(np.median(r)), "min": min(r), "max": max(r)} for name, r in rounds.items()}
+    print(json.dumps({"metric": "ms per rollout step per sample of one update on a mini-batch of T-step rollouts", "unit": "ms",
+                      "value": res["batched"]["median"], "variants": res,
+                      "config": {"sizes": batch_sizes, "batch_size": B, "T": T, "hidden": args.hidden, "updates_per_window": args.samples,
+                                 "rounds": args.rounds}, "dtype": "f32", "data": "synthetic"}))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--batched", action="store_true", help="measure a mini-batch as one ragged rollout against sample by sample")
+    ap.add_argument("--sizes", type=str, default="5000,4000", help="--batched: the recordings' node counts")
+    ap.add_argument("--batch-size", type=int, default=2, help="--batched: windows per update")
     ap.add_argument("--n", type=int, default=5000)
     ap.add_argument("--scenes", type=int, default=2)
     ap.add_argument("--k", type=int, default=6)
@@ -41,6 +121,8 @@ def main():
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_train_rollout: no HIP device (there is no CPU fallback)")
+    if args.batched:
+        return batched_main(args)
     from gnn_manip_amd import CoffeeDataset, EncProcDecGNN, RolloutEngine, Trainer, scene
     dev = torch.device("cuda:0")
     horizons = [int(v) for v in args.horizons.split(",")]
