@@ -253,8 +253,11 @@ int gm_state_post_backward(const float* d_obs_after, int64_t n_nodes, const gm_f
  * Numeric domain of the fp16 mode (gm_model_set_precision(m, GM_PRECISION_F16); inference entry points only).  Every Linear
  * multiplies its weights and its inputs ROUNDED TO fp16 (round to nearest even; 11 significant bits) and accumulates the exact
  * products in float32: one matrix instruction per multiply instead of three.  Everything else is as above and stays float32: the
- * power-of-two scales (which commute with the rounding), the biases, P and Q as initial accumulators, LayerNorm, residuals, the
- * scatter-add and its summation order, the latents in memory.  The weight images are the same (the mode reads their hi halves), so the
+ * power-of-two scales, the biases, P and Q as initial accumulators, LayerNorm, residuals, the scatter-add and its summation order,
+ * the latents in memory.  An operand is rounded AT its scale: the packed weights t W, the hidden activations U x, a raw feature row
+ * times its own power of two.  That is the rounding of the unscaled value only while both are fp16 normals (>= 2^-14; below, fp16's
+ * spacing is 2^-24 whatever the value).  Rows or first-Linear weights of magnitude 1e-4 keep all 11 bits here and would lose them
+ * rounded as they stand; an entry more than 2^20 below its row's maximum keeps about 31 - k bits at 2^-k of it.  The weight images are the same (the mode reads their hi halves), so the
  * switch needs no re-pack.  Expect a decoder output about 1e-3 of its largest element away from float64 after 10 message-passing
  * steps (float32: 1e-6): enough to rank rollout candidates, not for parity.  The range is the same: a value of magnitude >= 65520 in an
  * operand image becomes +-inf, the row check of every kernel counts +-inf like NaN, the same flag is raised (GM_ERR_DATA, "fp16 split

@@ -3,9 +3,13 @@ by test_precision_cases.py (CPU) and test_gpu_precision.py (GPU).
 
 The mode's contract (include/gnn_manip_hip.h, "Numeric domain of the fp16 mode"): every Linear multiplies its weights and its inputs
 rounded to fp16 (round to nearest even) and accumulates the exact products in float32; biases, LayerNorm, residuals, the scatter-add
-and the latents stay float32.  The kernels hold their operands at power-of-two scales, which commute with the rounding, so this is
-"round each Linear's weight matrix and input to fp16, multiply exactly" -- what ``mlp`` below does, with two details of the kernels
-that are visible at the mode's precision:
+and the latents stay float32.  The kernels hold their operands at power-of-two scales and round them there.  A power of two
+commutes with the rounding as long as the value is an fp16 normal (>= 2^-14) at both scales, so on operands of ordinary magnitude
+this is "round each Linear's weight matrix and input to fp16, multiply exactly" -- what ``mlp`` below does by default.  Where an
+operand is below 2^-14 at one of the two scales it is not: raw feature rows or first-Linear weights of magnitude 1e-4, entries 2^20
+below their row's maximum.  ``round_first`` and ``weight_scale`` then say at which scale the kernels round
+(f16_rollout_cases.raw_rounding restates the scales; on standard-normal rows and the weights of ``init_params`` the two
+restatements are 1e-6 apart at the most, test_f16_rollout_cases.py).  Two details of the kernels are visible at the mode's precision:
   * the Linear in front of a LayerNorm is packed centred over its outputs (W - mean_rows(W), b - mean(b), float32, the pack
     kernels' summation order -- after the coarse part of the mean, which is zero unless the mean exceeds the entries' spread, has
     been taken off unrounded: csrc/mlp.h, coarse_mean), and it is the CENTRED matrix that is rounded;
@@ -70,18 +74,22 @@ def centred(w, b):
     return w - cm, b - bm
 
 
-def mlp(p, prefix, blocks, num_layers, norm, acc=F64, round_w=True, round_x=True, ln_eps=EPS):
+def mlp(p, prefix, blocks, num_layers, norm, acc=F64, round_w=True, round_x=True, ln_eps=EPS, round_first=None, weight_scale=None):
     """One MLP of the model on the concatenation of `blocks`: Linear ReLU [Linear ReLU] x (L - 1) Linear [LayerNorm].
     round_w / round_x: round the weights / the inputs of every Linear to fp16 (both: the mode; neither: the float32 path's
     function in float64).  acc: the dtype the products are accumulated -- and everything behind them computed -- in.  ln_eps: the eps
-    of the LayerNorm (the callers below pass it on in **kw)."""
+    of the LayerNorm (the callers below pass it on in **kw).  round_first: the rounding of the first Linear's input where it is not
+    r16 on the value as it stands (f16_rollout_cases.round_rows: the encoders round a raw feature row at its own scale).
+    weight_scale: per Linear, the power of two its weights are multiplied by before they are rounded (f16_rollout_cases.encoder_scales;
+    default: rounded as they stand -- the same thing unless entries are below 2^-14 at one of the two scales)."""
     x = np.concatenate([np.asarray(b, F64) for b in blocks], axis=1)
     for l in range(num_layers + 1):
         w, b = p[f"{prefix}.{2 * l}.weight"], p[f"{prefix}.{2 * l}.bias"]
         if norm and l == num_layers:
             w, b = centred(w, b)
-        w = r16(w) if round_w else np.asarray(w, F64)
-        xin = r16(x) if round_x else x
+        t = 1.0 if weight_scale is None else float(weight_scale[l])
+        w = r16(np.asarray(w, F32) * F32(t)) / t if round_w else np.asarray(w, F64)
+        xin = (round_first(x) if l == 0 and round_first is not None else r16(x)) if round_x else x
         z = xin.astype(acc) @ w.astype(acc).T + np.asarray(b, acc)
         x = np.maximum(z, 0) if l < num_layers else z
         x = x.astype(F64) if acc is F64 else x.astype(F32).astype(F64)
@@ -93,8 +101,10 @@ def mlp(p, prefix, blocks, num_layers, norm, acc=F64, round_w=True, round_x=True
     return x
 
 
-def graph_independent(p, prefix, nodes, edge_attr, num_layers, **kw):
-    return mlp(p, f"{prefix}.phi_node", [nodes], num_layers, True, **kw), mlp(p, f"{prefix}.phi_edge", [edge_attr], num_layers, True, **kw)
+def graph_independent(p, prefix, nodes, edge_attr, num_layers, enc_node=None, enc_edge=None, **kw):
+    """enc_node / enc_edge: keywords of `mlp` that hold for that one MLP alone, over those of **kw."""
+    return (mlp(p, f"{prefix}.phi_node", [nodes], num_layers, True, **{**kw, **(enc_node or {})}),
+            mlp(p, f"{prefix}.phi_edge", [edge_attr], num_layers, True, **{**kw, **(enc_edge or {})}))
 
 
 def interaction_network(p, prefix, h, e, edge_index, num_layers, **kw):
@@ -107,8 +117,8 @@ def interaction_network(p, prefix, h, e, edge_index, num_layers, **kw):
     return h_new, e_new
 
 
-def epd_forward(p, nodes, edge_attr, edge_index, num_layers, m_steps, **kw):
-    h, e = graph_independent(p, "encoder", nodes, edge_attr, num_layers, **kw)
+def epd_forward(p, nodes, edge_attr, edge_index, num_layers, m_steps, enc_node=None, enc_edge=None, **kw):
+    h, e = graph_independent(p, "encoder", nodes, edge_attr, num_layers, enc_node, enc_edge, **kw)
     for k in range(m_steps):
         hn, en = interaction_network(p, f"processor.{k}", h, e, edge_index, num_layers, **kw)
         h, e = h + hn, e + en
@@ -227,15 +237,16 @@ def hm_case(name):
     return random_graph(n, e, 8500 + n)
 
 
-def b_reference(params, nodes, ea, ei, nl, ms, ln_eps=EPS):
-    """(float64 forward of oracle/torch_epd.py, err of the restatement against it): the envelope of check B is err / 4 .. 4 err."""
+def b_reference(params, nodes, ea, ei, nl, ms, ln_eps=EPS, **kw):
+    """(float64 forward of oracle/torch_epd.py, err of the restatement against it): the envelope of check B is err / 4 .. 4 err.
+    **kw: keywords of `epd_forward` (a variant of the restatement)."""
     import torch
     from oracle import torch_epd
     p = {k: torch.tensor(v, dtype=torch.float64) for k, v in params.items()}
     with torch.no_grad():
         ref = torch_epd.epd_forward(p, torch.tensor(nodes, dtype=torch.float64), torch.tensor(ea, dtype=torch.float64),
                                     torch.tensor(ei, dtype=torch.int64), nl, ms, ln_eps).numpy()
-    rest = epd_forward(params, nodes, ea, ei, nl, ms, ln_eps=ln_eps)
+    rest = epd_forward(params, nodes, ea, ei, nl, ms, ln_eps=ln_eps, **kw)
     return ref, max_err(rest, ref, B_FLOOR)
 
 
