@@ -235,6 +235,22 @@ def refine_starts(block_objective, x0, half_widths, iters=20, lr=0.01, betas=(0.
     return rows[:, 1:1 + dim].copy(), rows[:, 0].copy(), {"f": rows[:, 1 + dim:].copy()}
 
 
+def density_target(cloud, cell):
+    """A particle cloud [M, 3] as a density on a grid of side ``cell``: (centres [M', 3] float32, weights [M'] float32), one entry
+    per occupied cell -- the mean of the cell's members and count / M (the weights sum to 1).  A point belongs to the cell
+    floor(p / cell) (float64); the cells come in ascending order of that integer key (x, then y, then z), whatever the order of
+    the points.  Plain torch, on the cloud's device; what ``SamplesLoss``'s weighted call takes as (y, b)."""
+    if cloud.dim() != 2 or cloud.shape[1] != 3 or cloud.shape[0] == 0 or not cell > 0:
+        raise ValueError("density_target: cloud must be [M, 3] with M >= 1, cell > 0")
+    pts = cloud.detach().double()
+    _, inverse, counts = torch.unique(torch.floor(pts / float(cell)).long(), dim=0, return_inverse=True, return_counts=True)
+    order = torch.sort(inverse, stable=True).indices
+    run = torch.cumsum(pts[order], dim=0)                  # a cell's sum: the running sum at its last member minus at the previous cell's
+    ends = torch.cumsum(counts, dim=0) - 1
+    sums = run[ends] - torch.cat((torch.zeros_like(run[:1]), run[ends[:-1]]))
+    return (sums / counts[:, None]).float(), (counts.double() / cloud.shape[0]).float()
+
+
 class TrajectoryCMAsolver:
     """Mirror of the reference's ``TrajectoryCMAsolver`` (traj_utils.py:14-76,197-285) with the population of a
     CMA-ES generation evaluated TOGETHER on the device(s) instead of one ``cma_objective`` call per candidate:
@@ -246,6 +262,11 @@ class TrajectoryCMAsolver:
     * ``optimize_trajectory(desired_position)``: ``cmaes.fmin2`` over that (the reference: ``cma.fmin2``, :257);
     * ``loss_and_grad(x)`` / ``population_loss_and_grad(X)`` / ``refine(X0)``: the objective's gradient with respect to the search
       vector, for one candidate and for blocks of them, and the projected Adam that runs on it (not in the reference).
+
+    ``desired_weights`` (None: the reference's behaviour, every point of ``desired_pos`` weighs 1/M): the masses [M] of the points of
+    ``desired_pos``, float32 on the device -- the goal as a density (``set_density_target(cloud, cell)`` sets both from a cloud
+    binned on a grid; ``optimize_trajectory`` replaces ``desired_pos`` alone).  Every objective above then compares the uniform end
+    cloud with the weighted goal (``SamplesLoss``'s four-argument call).
 
     Same constructor arguments as the reference (``state_init`` = (obs [k, N, D], next positions) on the device).
     The rollouts follow the model's ``set_precision``: ``model.set_precision('f16')`` before planning ranks the candidates with the
@@ -263,6 +284,7 @@ class TrajectoryCMAsolver:
         self.ty_init = ty_init
         self.sample_traj = None
         self.desired_pos = None
+        self.desired_weights = None
         self.model, self.graph_attr = model, graph_attr
         self.horizon = total_steps
         self.device = torch.device(device)
@@ -336,7 +358,19 @@ class TrajectoryCMAsolver:
 
     def compute_loss(self, end_position, actions, cup_states=None, coffee_states=None, x=None):
         """traj_utils.py:275-285 for one candidate (one device loss, one transfer)."""
-        return self._assemble_loss(float(self.loss(end_position, self.desired_pos).item()), actions, x)
+        return self._assemble_loss(float(self._wasserstein(end_position).item()), actions, x)
+
+    def set_density_target(self, cloud, cell):
+        """The goal as a density: ``density_target(cloud, cell)`` becomes ``desired_pos`` and ``desired_weights``."""
+        centres, weights = density_target(torch.as_tensor(cloud, dtype=torch.float32, device=self.device), cell)
+        self.desired_pos, self.desired_weights = centres.contiguous(), weights.contiguous()
+
+    def _wasserstein(self, end):
+        """The loss of one end cloud [Nc, 3] (uniform) against the goal, weighted where ``desired_weights`` is set (the batched calls
+        pass ``b=self.desired_weights`` themselves)."""
+        if self.desired_weights is None:
+            return self.loss(end, self.desired_pos)
+        return self.loss(None, end, self.desired_weights, self.desired_pos)
 
     def _assemble_loss(self, wasserstein_loss, actions, x=None):
         """Everything of compute_loss but the Wasserstein term itself: host float64 like the reference."""
@@ -392,7 +426,7 @@ class TrajectoryCMAsolver:
             e, a = self._block_ends(X[b:b + self.candidates_per_gpu])
             ends.append(e)
             acts += a
-        w = self.loss.batched(torch.cat(ends), self.desired_pos).double().cpu().numpy()
+        w = self.loss.batched(torch.cat(ends), self.desired_pos, b=self.desired_weights).double().cpu().numpy()
         return [self._assemble_loss(float(w[i]), acts[i], X[i] if self._loss_takes_x else None)[0] for i in range(len(X))]
 
     # ---- gradient of the objective
@@ -418,7 +452,7 @@ class TrajectoryCMAsolver:
         final, step_edges = out if edges is not None else (out, None)
         c0 = self.graph_attr.cartesian_idx[0]
         end = final[-1].index_select(0, self._coffee_rows)[:, c0:c0 + 3]
-        wasserstein = self.loss(end, self.desired_pos).double().cpu()
+        wasserstein = self._wasserstein(end).double().cpu()
         actions = torch.stack((rot[:h], ty[:h]), dim=1)
         limits = torch.tensor([float(self.max_rot), float(self.max_ty)], dtype=torch.float64)
         vel = actions[1:] - actions[:-1]
@@ -447,7 +481,7 @@ class TrajectoryCMAsolver:
         final = eng.differentiable_rollout(obs, traj, horizon=h, sweep=sweep)
         c0 = self.graph_attr.cartesian_idx[0]
         ends = final[-1].reshape(b, eng.n_per, eng.data_dim).index_select(1, self._coffee_rows)[:, :, c0:c0 + 3]
-        wasserstein = self.loss.batched(ends, self.desired_pos).double().cpu()
+        wasserstein = self.loss.batched(ends, self.desired_pos, b=self.desired_weights).double().cpu()
         limits = torch.tensor([float(self.max_rot), float(self.max_ty)], dtype=torch.float64)
         losses, penalties = [], []
         for i, (rot, ty) in enumerate(chains):

@@ -470,6 +470,37 @@ int gm_sinkhorn_divergence_batched_backward(const float* x, int64_t batch, int64
                                             float* dx /*[batch,n,3] or NULL*/,
                                             float* dy /*[batch,m,3]; [m,3] if y_shared; or NULL*/, const void* fwd_ws,
                                             size_t fwd_ws_bytes, void* bwd_ws, size_t bwd_ws_bytes, void* stream);
+/* Weighted clouds (an addition to ABI 7): geomloss's four-argument call loss(a, x, b, y).  Point i of x carries the mass
+ * a[b][i] ([batch, N]), point j of y the mass b[j] ([M] when y_shared, else [batch, M]); a NULL side is uniform (1/N, 1/M),
+ * and with both NULL the calls ARE gm_sinkhorn_divergence_batched and its backward, to the bit.  With la = log a, lb = log b:
+ *     softmin_eps(C, h)_i = -eps log sum_j exp(h_j - C_ij / eps),   h = la + f / eps  or  lb + f / eps  (the cloud summed over)
+ *     S = sum_i a_i (b_x - a_x)_i + sum_j b_j (a_y - b_y)_j
+ *     dS/dx_i = a_i (T_xx(x_i) - T_xy(x_i)),  dS/dy_j = b_j (T_yy(y_j) - T_yx(y_j)),  the barycentres' softmax carrying la / lb
+ * Conventions:
+ *  - A weight of zero drops its point: log 0 = -inf, its term of every sum is exactly +0 and its gradient row exactly 0.0.
+ *  - NO normalisation and NO mass-balance check, as in geomloss: the weights are used as given; clouds of different total mass
+ *    give what the formulas above give.  (planner.density_target hands out weights that sum to 1.)
+ *  - The diameter (diameter <= 0) stays geomloss's: the bounding box of ALL points of both clouds, whatever their weights.  A
+ *    zero-weight point outside the others' box therefore lengthens the epsilon schedule: pad with copies of real points, or
+ *    name the diameter.
+ *  - The weights are constants: no gradient with respect to a or b.
+ *  - A weight that is negative or not finite, or a cloud whose weights sum to 0, makes its pair's loss and gradients NaN, like
+ *    a non-finite coordinate.  With diameter <= 0 -- one host synchronisation per call, as above -- the call then returns
+ *    GM_ERR_DATA with a message naming the weights; with diameter > 0 no host synchronisation happens and nothing is reported:
+ *    the NaN is the report.
+ * ws: gm_sinkhorn_weighted_workspace_bytes bytes (the unweighted layout, then the logarithms of the weights that are given,
+ * computed once per call); the backward reads it as fwd_ws and takes the same a and b; bwd_ws is sized by
+ * gm_sinkhorn_batched_backward_workspace_bytes. */
+size_t gm_sinkhorn_weighted_workspace_bytes(int64_t batch, int64_t n, int64_t m, int has_a, int has_b, int y_shared);
+int gm_sinkhorn_divergence_weighted(const float* a /*[batch,n] or NULL: uniform*/, const float* x, int64_t batch, int64_t n,
+                                    const float* b /*[m] if y_shared else [batch,m]; or NULL*/, const float* y, int64_t m,
+                                    int y_shared, float blur, float scaling, float diameter, float* loss_device /*[batch]*/,
+                                    void* ws, size_t ws_bytes, void* stream);
+int gm_sinkhorn_divergence_weighted_backward(const float* a, const float* x, int64_t batch, int64_t n, const float* b,
+                                             const float* y, int64_t m, int y_shared, float blur, float scaling,
+                                             const float* grad_loss /*[batch], device*/, float* dx /*[batch,n,3] or NULL*/,
+                                             float* dy /*[batch,m,3]; [m,3] if y_shared; or NULL*/, const void* fwd_ws,
+                                             size_t fwd_ws_bytes, void* bwd_ws, size_t bwd_ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * One device-resident rollout step = compute_rollout's loop body, rollout_utils.py:38-61 ==

@@ -4,7 +4,10 @@ line per shape.
     python tools/bench_sinkhorn.py [--reps 20] [--warmup 3]
 
 Shapes: the planner's (64 candidates against the shared desired cloud, the 4500 non-rigid particles of the C5 scene at N = 5k)
-and one 2500 x 2500 pair.  Per shape, interleaved call by call: `fwd` = the planner's call (torch.no_grad(), shared workspace),
+and one 2500 x 2500 pair; and the weighted call at the planner's shape: `planner_weighted`, the same clouds with explicit random
+weights on the desired cloud (uniform candidates, the planner's weighted case), and `planner_density`, the desired cloud as
+`planner.density_target` at a cell of three particle spacings (216 cells of up to 27 particles).
+Per shape, interleaved call by call: `fwd` = the planner's call (torch.no_grad(), shared workspace),
 `fwd_grad` = the same call with x requiring grad (own workspace), `fwd_bwd` = that call plus backward() with respect to x (and
 to y for the single pair).  Each time is one call between two events on the current stream, host round trip of the default
 `diameter` path included; median and range over --reps calls.
@@ -29,21 +32,21 @@ def _time(fn):
     return a.elapsed_time(b)
 
 
-def bench(name, X, y, need_y, reps, warmup):
+def bench(name, X, y, need_y, reps, warmup, b=None):
     from gnn_manip_amd.losses import SamplesLoss
     loss = SamplesLoss(loss="sinkhorn", p=2, blur=0.05)
 
     def fwd():
         with torch.no_grad():
-            loss.batched(X, y)
+            loss.batched(X, y, b=b)
 
     def fwd_grad():
-        loss.batched(X.detach().requires_grad_(), y)
+        loss.batched(X.detach().requires_grad_(), y, b=b)
 
     def fwd_bwd():
         x = X.detach().requires_grad_()
         yy = y.detach().requires_grad_(need_y)
-        loss.batched(x, yy).sum().backward()
+        loss.batched(x, yy, b=b).sum().backward()
 
     runs = dict(fwd=fwd, fwd_grad=fwd_grad, fwd_bwd=fwd_bwd)
     for _ in range(warmup):
@@ -55,7 +58,8 @@ def bench(name, X, y, need_y, reps, warmup):
         for k, fn in runs.items():
             t[k].append(_time(fn))
     med = {k: float(np.median(v)) for k, v in t.items()}
-    rec = dict(shape=name, batch=int(X.shape[0]), n=int(X.shape[1]), m=int(y.shape[-2]), y_shared=y.dim() == 2, dy=need_y, reps=reps)
+    rec = dict(shape=name, batch=int(X.shape[0]), n=int(X.shape[1]), m=int(y.shape[-2]), y_shared=y.dim() == 2, weighted=b is not None, dy=need_y,
+               reps=reps)
     for k, v in t.items():
         rec[k + "_ms"] = round(med[k], 4)
         rec[k + "_range_ms"] = [round(float(min(v)), 4), round(float(max(v)), 4)]
@@ -76,7 +80,13 @@ def main():
     cloud = obs[-1][obs[-1][:, 1] != 1][:, 2:5].astype(np.float32)     # its non-rigid rows: the planner's clouds
     rng = np.random.default_rng(0)
     X = np.stack([cloud + 1e-3 * rng.standard_normal(cloud.shape).astype(np.float32) for _ in range(64)])
-    bench("planner", torch.from_numpy(X).to(dev), torch.from_numpy(cloud + 0.01).to(dev), False, args.reps, args.warmup)
+    Xd, target = torch.from_numpy(X).to(dev), torch.from_numpy(cloud + 0.01).to(dev)
+    bench("planner", Xd, target, False, args.reps, args.warmup)
+    w = torch.from_numpy(rng.dirichlet(np.ones(len(cloud))).astype(np.float32)).to(dev)
+    bench("planner_weighted", Xd, target, False, args.reps, args.warmup, b=w)
+    from gnn_manip_amd.planner import density_target
+    centres, weights = density_target(target, 0.025)     # the particles sit about 0.0083 apart
+    bench("planner_density", Xd, centres, False, args.reps, args.warmup, b=weights)
     x = (0.5 + 0.05 * rng.standard_normal((1, 2500, 3))).astype(np.float32)
     y = (0.53 + 0.07 * rng.standard_normal((2500, 3))).astype(np.float32)
     bench("pair_2500", torch.from_numpy(x).to(dev), torch.from_numpy(y).to(dev), True, args.reps, args.warmup)
