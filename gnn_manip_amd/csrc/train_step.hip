@@ -1418,9 +1418,11 @@ int gm_trainer_import(gm_trainer* t, int what, const float* const* tensors_in, i
         GM_HIP_CHECK(hipMemcpyAsync(flat + j.dst_off, tensors_in[i], (size_t)j.count * sizeof(float), hipMemcpyDeviceToDevice, s));
     }
     if (what == GM_TRAINER_EXP_AVG) {
-        // the powers as the steps themselves would have left them: running products (which end at zero and stay there)
+        // the powers as the steps themselves would have left them: running products.  A product ends at a FIXED POINT of the rounded
+        // multiplication -- zero for a beta up to 0.5, a non-zero denormal above it (0.9: 2.47e-323, 0.999: 2.465e-321; both reached
+        // by step 737,741) -- and the device's own products stop at the same one, so the loop ends once neither product changes.
         double b1p = 1.0, b2p = 1.0;
-        for (int64_t i = 0; i < step_count && (b1p != 0.0 || b2p != 0.0); ++i) { b1p *= t->beta1; b2p *= t->beta2; }
+        for (int64_t i = 0; i < step_count && !(b1p * t->beta1 == b1p && b2p * t->beta2 == b2p); ++i) { b1p *= t->beta1; b2p *= t->beta2; }
         hipLaunchKernelGGL(trainer_record_set_kernel, dim3(1), dim3(1), 0, s, t->rec, step_count, (int64_t)0, 1, b1p, b2p);
         GM_LAUNCH_CHECK();
     }

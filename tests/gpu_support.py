@@ -131,6 +131,18 @@ def check_training_step(m, params, nodes, ea, ei, dims, dev, seed, ref=None):
     return compare_parameter_gradients(m, params, nodes, ea, ei, target, dims[4], dims[5], ref_g, g32)
 
 
+def rank_sum(rows_np, count, dev, fill=float("nan"), guard=8):
+    """gm_rank_sum through ctypes over `rows_np` [world, stride] into a destination of count + guard floats filled with `fill`."""
+    from gnn_manip_amd._lib import check, current_stream, lib, ptr
+    world, stride = rows_np.shape
+    src = to_dev(rows_np, dev)
+    dst = torch.full((count + guard,), fill, dtype=torch.float32, device=dev)
+    check(lib().gm_rank_sum(ptr(src), count, world, stride, ptr(dst), current_stream(dev)))
+    out = dst.cpu().numpy()
+    assert np.array_equal(out[count:].view(np.uint32), np.full(guard, fill, np.float32).view(np.uint32)), "written past count"
+    return out[:count]
+
+
 # ------------------------------------------------------------------------------------------ the rollout's reverse sweep through ctypes
 def edges_of(window, eng):
     """The radius graph of a pre-step window: get_connectivity on its last frame's positions (state_pre moves no position)."""

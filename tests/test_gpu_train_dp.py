@@ -28,7 +28,7 @@ import train_accum_cases as ac
 import train_dp_cases as dp
 import train_rollout_cases as trc
 import train_step_cases as sc
-from gpu_support import dev, load_model, step_engine, to_dev
+from gpu_support import dev, load_model, rank_sum as _rank_sum, step_engine, to_dev
 from grad_cases import L0
 from yardstick import compare, same_bits
 
@@ -100,18 +100,6 @@ def _rollout_setup(dev, max_grad_norm=None):
 
 
 # ------------------------------------------------------------------------------------------ 1. gm_rank_sum
-def _rank_sum(rows_np, count, dev, fill=NAN, guard=8):
-    """gm_rank_sum through ctypes over `rows_np` [world, stride] into a destination of count + guard floats filled with `fill`."""
-    from gnn_manip_amd._lib import check, current_stream, lib, ptr
-    world, stride = rows_np.shape
-    src = to_dev(rows_np, dev)
-    dst = torch.full((count + guard,), fill, dtype=torch.float32, device=dev)
-    check(lib().gm_rank_sum(ptr(src), count, world, stride, ptr(dst), current_stream(dev)))
-    out = dst.cpu().numpy()
-    assert np.array_equal(out[count:].view(np.uint32), np.full(guard, fill, np.float32).view(np.uint32)), "written past count"
-    return out[:count]
-
-
 @pytest.mark.parametrize("count", dp.RANK_SUM_COUNTS)
 def test_rank_sum_is_the_restated_sum(dev, count):
     for world in dp.RANK_SUM_WORLDS:

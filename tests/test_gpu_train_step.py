@@ -111,7 +111,8 @@ def test_l1_loss_is_the_restatement(dev, n):
 
 
 # ------------------------------------------------------------------------------------------ one step
-@pytest.mark.parametrize("name,sand_only", [("h64", False), ("h64", True), ("h128", False), ("h256", True), ("h64_out4", False)])
+@pytest.mark.parametrize("name,sand_only", [("h64", False), ("h64", True), ("h128", False), ("h256", True), ("h64_out4", False),
+                                            ("h256_m3", False)])       # adam_flat_kernel<false> past one pass of its grid
 def test_one_step_has_the_existing_paths_gradients(dev, name, sand_only):
     from gnn_manip_amd import train
     t, m, batch, (nodes, _, _, target), _ = _setup(name, 301, dev, sand_only=sand_only, material_col=sc.MATERIAL_COL if sand_only else None)

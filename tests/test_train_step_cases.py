@@ -118,6 +118,8 @@ def test_models_cover_a_flat_count_with_and_without_a_vector_tail():
     counts = {name: sc.flat_count(dims) for name, dims in sc.STEP_MODELS.items()}
     assert counts["h64"] % 4 == 3 and counts["h128"] % 4 == 3 and counts["h256"] % 4 == 3     # out_dim 3: a scalar tail of three
     assert counts["h64_out4"] % 4 == 0                                                          # none
+    grid_pass = 2048 * 256 * 4                                                                  # floats of one pass of the flat Adam launch
+    assert counts["h256_m3"] % 4 == 3 and counts["h256_m3"] > grid_pass > counts["h256"]        # a second trip of the grid-stride loop
     assert sc.flat_count((25, 4, 3, 128, 2, 10)) >= sum(int(np.prod(s)) for s in sc.tensor_shapes((25, 4, 3, 128, 2, 10)))
     from gnn_manip_amd import EncProcDecGNN
     for dims in sc.STEP_MODELS.values():

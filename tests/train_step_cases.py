@@ -134,7 +134,9 @@ def flat_count(dims):
 
 # the models of the step tests: (dims, nodes, side of the scene, seed); N ~ 300 and E ~ 4000
 SMALL = (25, 4, 3, 64, 2, 2)
-STEP_MODELS = {"h64": SMALL, "h128": (25, 4, 3, 128, 2, 2), "h256": (25, 4, 3, 256, 2, 2), "h64_out4": (25, 4, 4, 64, 2, 2)}
+# "h256_m3": more floats than ONE pass of the flat Adam launch's capped grid walks (2048 workgroups x 256 threads x 4 floats)
+STEP_MODELS = {"h64": SMALL, "h128": (25, 4, 3, 128, 2, 2), "h256": (25, 4, 3, 256, 2, 2), "h64_out4": (25, 4, 4, 64, 2, 2),
+               "h256_m3": (25, 4, 3, 256, 2, 3)}
 SCENE = dict(n=300, side=0.05)
 MATERIAL_COL = -1 - 3        # train_dyn.py:60 with three control columns, from the end of the 25 node features
 
