@@ -11,6 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GM_LIB_PATH") or os.path.join(_HERE, "libgnnmanip_hip.so")   # GM_LIB_PATH: A/B builds of the same library
 
 GM_OK = 0
+RAGGED_MAX_GRAPHS = 64   # GM_RAGGED_MAX_GRAPHS (include/gnn_manip_hip.h): the graphs of a ragged batch at most
 
 
 class GMError(RuntimeError):

@@ -387,24 +387,6 @@ __device__ __forceinline__ int cell_coord(float v, double origin, double inv_h, 
     return ci;
 }
 
-// The table of a ragged build comes by value in the kernel arguments; a search by a divergent index needs it in memory, so the
-// workgroup stages it in LDS first (every thread of the workgroup calls this).
-__device__ __forceinline__ void stage_ragged_offsets(const RaggedOffsets& R, int* s_off /* LDS, n_graphs + 1 ints */) {
-    for (int t = threadIdx.x; t <= R.n_graphs; t += blockDim.x) s_off[t] = R.off[t];
-    __syncthreads();
-}
-// The graph of row i of a ragged build: the g with off[g] <= i < off[g + 1] (every thread of the workgroup calls this).
-__device__ __forceinline__ int ragged_graph_of_row(const RaggedOffsets& R, int64_t i) {
-    __shared__ int s_off[GM_RAGGED_MAX_GRAPHS + 1];
-    stage_ragged_offsets(R, s_off);
-    int lo = 0, hi = R.n_graphs;   // off[lo] <= i < off[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if ((int64_t)s_off[mid] <= i) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 // Ragged: nothing (row i belongs to graph i / n_per_graph: the instantiation of every equal-sized build), or RaggedOffsets
 template <typename... Ragged>
 __global__ void __launch_bounds__(256) cell_assign_kernel(const float* __restrict__ pos, int64_t stride, int64_t n,
@@ -1012,6 +994,13 @@ int ragged_offsets(const int64_t* off, int64_t n_graphs, double conn_r, int K, c
     GM_REQUIRE(n * (int64_t)K < (int64_t)1 << 31, GM_ERR_INVALID_ARGUMENT, "%s: n_nodes * max_neighbours overflows int32", who);
     GM_REQUIRE(conn_r > 0.0 && conn_r == conn_r, GM_ERR_INVALID_ARGUMENT, "%s: conn_r must be > 0", who);
     return GM_OK;
+}
+int ragged_scene_table(const char* who, const gm_feature_desc* fd, const int64_t* offsets_host, int64_t n_graphs, int K, const void* ws,
+                       RaggedOffsets* out) {
+    GM_REQUIRE(fd && ws, GM_ERR_INVALID_ARGUMENT, "%s: null pointer", who);
+    GM_REQUIRE(fd->nodes_per_graph == 0, GM_ERR_INVALID_ARGUMENT, "%s: nodes_per_graph=%lld, must be 0 (the graphs come in graph_offsets)", who,
+               (long long)fd->nodes_per_graph);
+    return ragged_offsets(offsets_host, n_graphs, fd->conn_r, K, ws, who, out);
 }
 }  // namespace gm
 

@@ -753,14 +753,6 @@ size_t gm_rollout_workspace_bytes(const gm_model_desc* desc, int64_t n, int K) {
 }  // extern "C"
 
 namespace {
-// What every _ragged rollout entry point checks before anything else: a descriptor of ONE scene per graph and the table
-int ragged_rollout_table(const char* who, const gm_feature_desc* fd, const int64_t* offsets_host, int64_t n_graphs, int K, const void* ws,
-                         gm::RaggedOffsets* R) {
-    GM_REQUIRE(fd && ws, GM_ERR_INVALID_ARGUMENT, "%s: null pointer", who);
-    GM_REQUIRE(fd->nodes_per_graph == 0, GM_ERR_INVALID_ARGUMENT, "%s: nodes_per_graph=%lld, must be 0 (the graphs come in graph_offsets)", who,
-               (long long)fd->nodes_per_graph);
-    return gm::ragged_offsets(offsets_host, n_graphs, fd->conn_r, K, ws, who, R);
-}
 int64_t ragged_min_rows(const gm::RaggedOffsets& R) {
     int64_t lo = R.off[1] - R.off[0];
     for (int g = 1; g < R.n_graphs; ++g) lo = std::min<int64_t>(lo, R.off[g + 1] - R.off[g]);
@@ -834,7 +826,7 @@ int gm_rollout_step_ragged(const gm_model* m, float* obs, const int64_t* graph_o
                            const int32_t* rigid_rank, const float* rigid_target, float* pred_acc_out, void* ws, size_t ws_bytes,
                            void* stream) {
     gm::RaggedOffsets R;
-    const int rc = ragged_rollout_table("gm_rollout_step_ragged", fd, graph_offsets_host, n_graphs, K, ws, &R);
+    const int rc = gm::ragged_scene_table("gm_rollout_step_ragged", fd, graph_offsets_host, n_graphs, K, ws, &R);
     if (rc != GM_OK) return rc;
     GM_REQUIRE(m && obs, GM_ERR_INVALID_ARGUMENT, "gm_rollout_step_ragged: null pointer");
     const size_t need = carve_rollout(nullptr, &m->d, R.off[R.n_graphs], K).bytes;
@@ -967,7 +959,7 @@ int gm_rollout_ragged(const gm_model* m, float* obs, const int64_t* graph_offset
                       const int32_t* rigid_rank, const float* rigid_targets, int64_t n_targets, int64_t n_rigid, int64_t steps,
                       float* record_last, void* ws, size_t ws_bytes, void* stream) {
     gm::RaggedOffsets R;
-    const int rc = ragged_rollout_table("gm_rollout_ragged", fd, graph_offsets_host, n_graphs, K, ws, &R);
+    const int rc = gm::ragged_scene_table("gm_rollout_ragged", fd, graph_offsets_host, n_graphs, K, ws, &R);
     if (rc != GM_OK) return rc;
     gm::DevGuard dev_guard(obs);
     GM_REQUIRE(m && obs, GM_ERR_INVALID_ARGUMENT, "gm_rollout_ragged: null pointer");
@@ -986,7 +978,7 @@ int gm_rollout_recorded_ragged(const gm_model* m, float* obs, const int64_t* gra
                                int K, const int32_t* rigid_rank, const float* frames, int64_t steps, float* record_last, float* record_pred,
                                void* ws, size_t ws_bytes, void* stream) {
     gm::RaggedOffsets R;
-    const int rc = ragged_rollout_table("gm_rollout_recorded_ragged", fd, graph_offsets_host, n_graphs, K, ws, &R);
+    const int rc = gm::ragged_scene_table("gm_rollout_recorded_ragged", fd, graph_offsets_host, n_graphs, K, ws, &R);
     if (rc != GM_OK) return rc;
     gm::DevGuard dev_guard(obs);
     GM_REQUIRE(m && obs, GM_ERR_INVALID_ARGUMENT, "gm_rollout_recorded_ragged: null pointer");

@@ -248,21 +248,13 @@ int gm_rollout_backward_train(const gm_model* m, const float* const* tensors, in
 
 // The two training sweeps on graphs of any sizes (the table as in gm_radius_graph_build_ragged, fd->nodes_per_graph == 0): still one
 // edge-count read per step, for the whole batch.  d_record / d_records and grads both NULL: the plain vector-Jacobian product.
-static int ragged_table(const char* who, const gm_feature_desc* fd, const int64_t* offsets_host, int64_t n_graphs, int K, const void* ws,
-                        gm::RaggedOffsets* R) {
-    GM_REQUIRE(fd && ws, GM_ERR_INVALID_ARGUMENT, "%s: null pointer", who);
-    GM_REQUIRE(fd->nodes_per_graph == 0, GM_ERR_INVALID_ARGUMENT, "%s: nodes_per_graph=%lld, must be 0 (the graphs come in graph_offsets)", who,
-               (long long)fd->nodes_per_graph);
-    return gm::ragged_offsets(offsets_host, n_graphs, fd->conn_r, K, ws, who, R);
-}
-
 int gm_rollout_step_backward_train_ragged(const gm_model* m, const float* const* tensors, int n_tensors, const float* obs_before,
                                           const int64_t* graph_offsets_host, int64_t n_graphs, const gm_feature_desc* fd, int K,
                                           const int32_t* rigid_rank, const float* rigid_target, const float* d_obs_after, const float* d_record,
                                           float* const* grads, float* d_obs_before, float* d_rigid_target, int64_t* n_edges_host, void* ws,
                                           size_t ws_bytes, void* stream) {
     gm::RaggedOffsets R;
-    const int rc = ragged_table(__func__, fd, graph_offsets_host, n_graphs, K, ws, &R);
+    const int rc = gm::ragged_scene_table(__func__, fd, graph_offsets_host, n_graphs, K, ws, &R);
     if (rc != GM_OK) return rc;
     return step_backward(m, tensors, n_tensors, obs_before, R.off[R.n_graphs], fd, K, rigid_rank, rigid_target, d_obs_after, d_record, grads,
                          d_obs_before, d_rigid_target, n_edges_host, ws, ws_bytes, stream, __func__, &R);
@@ -274,7 +266,7 @@ int gm_rollout_backward_train_ragged(const gm_model* m, const float* const* tens
                                      const float* d_final, const float* d_records, float* const* grads, float* d_obs0, float* d_trajectory,
                                      void* ws, size_t ws_bytes, void* stream) {
     gm::RaggedOffsets R;
-    const int rc = ragged_table(__func__, fd, graph_offsets_host, n_graphs, K, ws, &R);
+    const int rc = gm::ragged_scene_table(__func__, fd, graph_offsets_host, n_graphs, K, ws, &R);
     if (rc != GM_OK) return rc;
     return sweep_backward(m, tensors, n_tensors, windows, R.off[R.n_graphs], fd, K, rigid_rank, trajectory, n_targets, n_rigid, steps, d_final,
                           d_records, grads, d_obs0, d_trajectory, ws, ws_bytes, stream, __func__, &R);

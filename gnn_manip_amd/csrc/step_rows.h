@@ -32,6 +32,10 @@ struct RaggedOffsets {
 // host offsets -> table, behind every check gm_radius_graph_build_ragged makes of them and of the other arguments (`who` opens
 // the message of a refusal); radius_graph_build_ragged_core: radius_graph_build_core with the graph of a row from the table
 int ragged_offsets(const int64_t* offsets_host, int64_t n_graphs, double conn_r, int K, const void* ws, const char* who, RaggedOffsets* out);
+// What every _ragged rollout, sweep and loss entry point checks before anything else: fd and ws given, a descriptor of ONE scene
+// per graph (nodes_per_graph == 0), then ragged_offsets
+int ragged_scene_table(const char* who, const gm_feature_desc* fd, const int64_t* offsets_host, int64_t n_graphs, int K, const void* ws,
+                       RaggedOffsets* out);
 int radius_graph_build_ragged_core(const float* pos, int64_t pos_stride, const RaggedOffsets& R, double conn_r, int K, const GraphWs& g,
                                    int* indeg, int* slot, int flow, hipStream_t s);
 // radius_graph_build_fused / csr_from_graph_fused (common.h) for the graphs of a table: the rollout step's graph path of a ragged batch
@@ -47,6 +51,28 @@ inline int node_feature_dim(const gm_feature_desc* fd) { return node_feature_dim
 inline int64_t graph_nodes(const gm_feature_desc* fd, int64_t n) { return fd->nodes_per_graph > 0 ? fd->nodes_per_graph : n; }
 
 #if defined(__HIPCC__)
+// The table of a ragged build comes by value in the kernel arguments; a search by a divergent index needs it in memory, so the
+// workgroup stages it in LDS first (every thread of the workgroup calls this).
+__device__ __forceinline__ void stage_ragged_offsets(const RaggedOffsets& R, int* s_off /* LDS, n_graphs + 1 ints */) {
+    for (int t = threadIdx.x; t <= R.n_graphs; t += blockDim.x) s_off[t] = R.off[t];
+    __syncthreads();
+}
+// The graph of row i in a staged table: the g with s_off[g] <= i < s_off[g + 1].  One graph: no iteration.
+__device__ __forceinline__ int staged_graph_of_row(const int* s_off, int n_graphs, int64_t i) {
+    int lo = 0, hi = n_graphs;   // off[lo] <= i < off[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if ((int64_t)s_off[mid] <= i) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+// The graph of row i of a ragged build, staging included (every thread of the workgroup calls this).
+__device__ __forceinline__ int ragged_graph_of_row(const RaggedOffsets& R, int64_t i) {
+    __shared__ int s_off[GM_RAGGED_MAX_GRAPHS + 1];
+    stage_ragged_offsets(R, s_off);
+    return staged_graph_of_row(s_off, R.n_graphs, i);
+}
+
 // [(p_s - p_r) / r, |.|] of one edge, ps / pr = the xyz of its sender (edge_index[0]) / receiver (utils.py:43-61)
 __device__ __forceinline__ float4 edge_feature(const float* __restrict__ ps, const float* __restrict__ pr, float cr) {
     float d[3];

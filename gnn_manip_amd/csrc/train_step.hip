@@ -27,8 +27,11 @@ constexpr int kLossGridMax = 128;   // one partial per workgroup, summed by ONE 
 struct LossState {
     double loss;     // sum / count (NaN for count 0)
     int64_t count;   // rows counted
-    float scale;     // (float)(1.0 / count): the magnitude of every gradient element
-    int skip;        // gm_train_step: the edge_index was flagged or the loss is not finite -- no update
+    float scale;     // gm_l1_loss: (float)(1.0 / count), the magnitude of every gradient element.  A rollout loss writes 0 and reads
+                     // nothing here: its transpose takes each segment's scale from that segment's count
+    int bad;         // how many of the samples behind `loss` forbid an update.  One sample (gm_train_step, a rollout of one
+                     // segment): 1 when the edge_index was flagged or the loss is not finite; a ragged rollout batch: how many of
+                     // its graphs' losses are not finite
 };
 static_assert(sizeof(LossState) == 24, "LossState layout");
 
@@ -47,8 +50,8 @@ LossWs carve_loss(void* ws) {
     w.bytes = c.used();
     return w;
 }
-unsigned loss_grid(int64_t rows) {
-    const int64_t g = cdiv(rows, kLossThreads);
+__host__ __device__ inline unsigned loss_grid(int64_t rows) {
+    const int64_t g = (rows + kLossThreads - 1) / kLossThreads;
     return (unsigned)(g < 1 ? 1 : (g > kLossGridMax ? kLossGridMax : g));
 }
 
@@ -116,7 +119,7 @@ __global__ void __launch_bounds__(kLossThreads) l1_finish_kernel(const double* p
     st->loss = loss;
     st->count = cnt;
     st->scale = cnt > 0 ? (float)(1.0 / (double)cnt) : 0.f;
-    st->skip = (flagged || !isfinite(loss)) ? 1 : 0;
+    st->bad = (flagged || !isfinite(loss)) ? 1 : 0;
     if (loss_out) *loss_out = loss;
     if (rows_out) *rows_out = cnt;
 }
@@ -165,13 +168,40 @@ int run_loss(const float* pred, const float* target, int64_t rows, int od, const
 
 // ---------------------------------------------------------------------------------------------------------------- the rollout's loss
 // The L1 loss of a rollout against recorded frames and its transpose.  Step t is scored on the last frame of the
-// window the step left: windows[t + 1] for t < steps - 1, `fin` for the last step.
+// window the step left: windows[t + 1] for t < steps - 1, `fin` for the last step.  ONE set of kernels serves the single call
+// (gm_rollout_l1_loss) and the ragged batch (gm_rollout_l1_loss_ragged): the rows are segments, one loss per segment from its own
+// rows alone, and the single call is the batch of one segment [0, n) -- which is why graph g's loss in a batch is the single call's
+// on g alone, bit for bit.
 struct RolloutLossArgs {
-    const float *windows, *fin, *frames;   // [steps,k,N,D], [k,N,D], [steps,N,frame_dim]
+    const float *windows, *fin;            // [steps,k,N,D], [k,N,D]; N: the rows of all segments
     const int32_t* rank;                   // [N] or null
     int64_t n, steps;
     int k, D, frame_dim, cart, mat;        // mat: the state's material column, < 0: off
 };
+// The segments and the recorded frames of each, an array of its own ([steps, n_g, frame_dim], a view into its recording).  The
+// table travels by value in the kernel arguments; a kernel that needs it by a row's (divergent) graph stages it in LDS first.
+struct RolloutSegments {
+    RaggedOffsets R;
+    const float* frames[GM_RAGGED_MAX_GRAPHS];
+};
+// The single call's table, made on the host: one segment [0, n) (n < 2^31) with its frames, whatever fd->nodes_per_graph says --
+// a batch of equal-sized graphs is scored as ONE sample, and none of the graph builder's limits (ragged_offsets) applies.
+RolloutSegments one_segment(int64_t n, const float* frames) {
+    RolloutSegments S{};
+    S.R.n_graphs = 1;
+    for (int g = 1; g <= GM_RAGGED_MAX_GRAPHS; ++g) S.R.off[g] = (int)n;
+    S.frames[0] = frames;
+    return S;
+}
+struct SegmentRows {   // the table in LDS
+    int off[GM_RAGGED_MAX_GRAPHS + 1];
+    const float* frames[GM_RAGGED_MAX_GRAPHS];
+};
+// every thread of the workgroup calls it
+__device__ inline void stage_segments(const RolloutSegments& S, SegmentRows* tab) {
+    for (int t = threadIdx.x; t < S.R.n_graphs; t += blockDim.x) tab->frames[t] = S.frames[t];
+    stage_ragged_offsets(S.R, tab->off);
+}
 
 __device__ inline const float* predicted_frame(const RolloutLossArgs& a, int64_t t) {
     const size_t frame = (size_t)a.n * a.D;
@@ -183,155 +213,19 @@ __device__ inline bool rollout_row_counts(const RolloutLossArgs& a, int64_t r) {
     return a.mat < 0 || a.windows[((size_t)(a.k - 1) * a.n + r) * a.D + a.mat] < 0.5f;
 }
 
-struct RolloutLossWs {
-    double* part_sum;     // [3][kLossGridMax]: one row per axis
-    int64_t* part_cnt;    // [kLossGridMax]
-    LossState* state;
-    size_t bytes;
-};
-RolloutLossWs carve_rollout_loss(void* ws) {
-    RolloutLossWs w;
-    Carver c(ws);
-    w.part_sum = c.take<double>(3 * kLossGridMax);
-    w.part_cnt = c.take<int64_t>(kLossGridMax);
-    w.state = c.take<LossState>(1);
-    w.bytes = c.used();
-    return w;
-}
-
-// Pass 1, l1_partials_kernel's pattern with the step as a further loop: a thread walks its rows (row, then step, then axis) and adds
-// the float32 values |pred - frame| in float64, one sum per axis; a workgroup's threads are summed in a fixed tree.
-__global__ void __launch_bounds__(kLossThreads) rollout_l1_partials_kernel(RolloutLossArgs a, double* part_sum, int64_t* part_cnt) {
-    __shared__ double sh_s[kLossThreads];
-    __shared__ int64_t sh_c[kLossThreads];
-    double s[3] = {0.0, 0.0, 0.0};
-    int64_t cnt = 0;
-    for (int64_t r = (int64_t)blockIdx.x * kLossThreads + threadIdx.x; r < a.n; r += (int64_t)gridDim.x * kLossThreads) {
-        if (!rollout_row_counts(a, r)) continue;
-        ++cnt;
-        for (int64_t t = 0; t < a.steps; ++t) {
-            const float* p = predicted_frame(a, t) + (size_t)r * a.D + a.cart;
-            const float* f = a.frames + ((size_t)t * a.n + r) * a.frame_dim + a.cart;
-            for (int c = 0; c < 3; ++c) s[c] += (double)fabsf(p[c] - f[c]);
-        }
-    }
-    for (int c = 0; c < 3; ++c) {
-        const double v = block_sum(s[c], sh_s);
-        if (threadIdx.x == 0) part_sum[c * kLossGridMax + blockIdx.x] = v;
-    }
-    cnt = block_sum(cnt, sh_c);
-    if (threadIdx.x == 0) part_cnt[blockIdx.x] = cnt;
-}
-
-struct PosScale { double s[3]; };
-
-// Pass 2, one workgroup: loss = (s_0 / scale_0 + s_1 / scale_1 + s_2 / scale_2) / (steps * count), and the skip decision.
-__global__ void __launch_bounds__(kLossThreads) rollout_l1_finish_kernel(const double* part_sum, const int64_t* part_cnt, int n_part,
-                                                                         int64_t steps, PosScale ps, LossState* st, double* loss_out,
-                                                                         int64_t* rows_out) {
-    __shared__ double sh_s[kLossThreads];
-    __shared__ int64_t sh_c[kLossThreads];
-    double s[3];
-    for (int c = 0; c < 3; ++c) {
-        double v = 0.0;
-        for (int i = threadIdx.x; i < n_part; i += kLossThreads) v += part_sum[c * kLossGridMax + i];
-        s[c] = block_sum(v, sh_s);
-    }
-    int64_t cnt = 0;
-    for (int i = threadIdx.x; i < n_part; i += kLossThreads) cnt += part_cnt[i];
-    cnt = block_sum(cnt, sh_c);
-    if (threadIdx.x != 0) return;
-    const double terms = (double)steps * (double)cnt;
-    const double loss = cnt > 0 ? ((s[0] / ps.s[0] + s[1] / ps.s[1]) + s[2] / ps.s[2]) / terms : (double)__builtin_nanf("");
-    st->loss = loss;
-    st->count = cnt;
-    st->scale = cnt > 0 ? (float)(1.0 / terms) : 0.f;
-    st->skip = isfinite(loss) ? 0 : 1;
-    if (loss_out) *loss_out = loss;
-    if (rows_out) *rows_out = cnt;
-}
-
-// Pass 3: the transpose, every element of d_records [steps,N,D] and d_final [k,N,D] written.  blockIdx.y is the [N,D] slab: slab
-// j < steps is d_records[j], which takes step j - 1's gradient (slab 0: zeros); slab steps + f is frame f of d_final, whose last frame
-// takes the last step's.  An element is sign(pred - frame) * (float)(1.0 / ((scale_c * steps) * count)) on the xyz columns of a
-// counted row, with sign(0) = 0, and 0 everywhere else.
-__global__ void __launch_bounds__(kLossThreads) rollout_l1_grad_kernel(RolloutLossArgs a, PosScale ps, const LossState* st, float* d_records,
-                                                                       float* d_final) {
-    const int64_t slab = blockIdx.y;
-    const size_t frame = (size_t)a.n * a.D;
-    float* out = slab < a.steps ? d_records + (size_t)slab * frame : d_final + (size_t)(slab - a.steps) * frame;
-    const int64_t t = slab < a.steps ? slab - 1 : (slab == a.steps + a.k - 1 ? a.steps - 1 : -1);
-    const int64_t cnt = st->count;
-    float g[3] = {0.f, 0.f, 0.f};
-    if (cnt > 0)
-        for (int c = 0; c < 3; ++c) g[c] = (float)(1.0 / ((ps.s[c] * (double)a.steps) * (double)cnt));
-    const float* pred = t >= 0 ? predicted_frame(a, t) : nullptr;
-    for (int64_t r = (int64_t)blockIdx.x * kLossThreads + threadIdx.x; r < a.n; r += (int64_t)gridDim.x * kLossThreads) {
-        const bool counts = t >= 0 && cnt > 0 && rollout_row_counts(a, r);
-        for (int c = 0; c < a.D; ++c) {
-            float v = 0.f;
-            const int ax = c - a.cart;
-            if (counts && ax >= 0 && ax < 3) {
-                const float d = pred[(size_t)r * a.D + c] - a.frames[((size_t)t * a.n + r) * a.frame_dim + c];
-                v = d > 0.f ? g[ax] : (d < 0.f ? -g[ax] : 0.f);
-            }
-            out[(size_t)r * a.D + c] = v;
-        }
-    }
-}
-
-// The scripted poses of a recorded drive: trajectory[t][rigid_rank[r]] = xyz(frames[t][r]).
-__global__ void __launch_bounds__(kLossThreads) recorded_poses_kernel(const float* frames, int frame_dim, int cart, const int32_t* rank,
-                                                                      int64_t n, int64_t n_rigid, float* trajectory) {
-    const int64_t r = (int64_t)blockIdx.x * kLossThreads + threadIdx.x, t = blockIdx.y;
-    if (r >= n) return;
-    const int64_t j = rank[r];
-    if (j < 0 || j >= n_rigid) return;
-    const float* f = frames + ((size_t)t * n + r) * frame_dim + cart;
-    float* o = trajectory + ((size_t)t * n_rigid + j) * 3;
-    o[0] = f[0]; o[1] = f[1]; o[2] = f[2];
-}
-
-// ---- the same loss for a ragged batch (gm_rollout_l1_loss_ragged): one loss per graph, each the single call's on that graph alone.
-// The recorded frames of graph g are an array of their own ([steps, n_g, frame_dim], a view into its recording): the pointers and the
-// offsets travel by value in the kernel arguments; a kernel that needs them by a row's (divergent) graph stages them in LDS first.
-struct RaggedFrames { const float* p[GM_RAGGED_MAX_GRAPHS]; };
-struct GraphLoss {      // what the finish leaves per graph for the transpose
+struct GraphLoss {      // what the finish leaves per segment for the transpose
     double loss;
     int64_t count;
 };
-struct RaggedRowTable {   // in LDS
-    int off[GM_RAGGED_MAX_GRAPHS + 1];
-    const float* frames[GM_RAGGED_MAX_GRAPHS];
-};
-// every thread of the workgroup calls it
-__device__ inline void stage_row_table(const RaggedOffsets& R, const RaggedFrames& F, RaggedRowTable* tab) {
-    for (int t = threadIdx.x; t <= R.n_graphs; t += blockDim.x) tab->off[t] = R.off[t];
-    for (int t = threadIdx.x; t < R.n_graphs; t += blockDim.x) tab->frames[t] = F.p[t];
-    __syncthreads();
-}
-__device__ inline int graph_of_row(const RaggedRowTable* tab, int n_graphs, int64_t r) {
-    int lo = 0, hi = n_graphs;   // off[lo] <= r < off[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if ((int64_t)tab->off[mid] <= r) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-__host__ __device__ inline unsigned loss_grid_of(int64_t rows) {
-    const int64_t g = (rows + kLossThreads - 1) / kLossThreads;
-    return (unsigned)(g < 1 ? 1 : (g > kLossGridMax ? kLossGridMax : g));
-}
-
-struct RolloutLossRaggedWs {
-    double* part_sum;     // [n_graphs][3][kLossGridMax]
+struct RolloutLossWs {
+    double* part_sum;     // [n_graphs][3][kLossGridMax]: one row per axis
     int64_t* part_cnt;    // [n_graphs][kLossGridMax]
     GraphLoss* graph;     // [n_graphs]
-    LossState* state;     // the mini-batch's: loss = the sum of the graphs' losses, skip = how many of them are not finite
+    LossState* state;     // the call's: the segments' losses and counts added in order, bad = how many losses are not finite
     size_t bytes;
 };
-RolloutLossRaggedWs carve_rollout_loss_ragged(void* ws, int64_t n_graphs) {
-    RolloutLossRaggedWs w;
+RolloutLossWs carve_rollout_loss(void* ws, int64_t n_graphs) {
+    RolloutLossWs w;
     Carver c(ws);
     w.part_sum = c.take<double>((size_t)n_graphs * 3 * kLossGridMax);
     w.part_cnt = c.take<int64_t>((size_t)n_graphs * kLossGridMax);
@@ -341,17 +235,19 @@ RolloutLossRaggedWs carve_rollout_loss_ragged(void* ws, int64_t n_graphs) {
     return w;
 }
 
-// Pass 1: blockIdx.y is the graph.  Graph g is walked by the loss_grid(n_g) workgroups the single call launches for it, in that
-// call's stride, so its partial sums -- and everything behind them -- depend on its own rows alone; the other workgroups of the row leave.
-__global__ void __launch_bounds__(kLossThreads) rollout_l1_partials_ragged_kernel(RolloutLossArgs a, RaggedOffsets R, RaggedFrames F,
-                                                                                  double* part_sum, int64_t* part_cnt) {
+// Pass 1, l1_partials_kernel's pattern with the step as a further loop; blockIdx.y is the segment.  Segment g is walked by
+// loss_grid(n_g) workgroups in that stride -- the other workgroups of the launch row leave -- so its partial sums, and everything
+// behind them, depend on its own rows alone.  A thread walks its rows (row, then step, then axis) and adds the float32 values
+// |pred - frame| in float64, one sum per axis; a workgroup's threads are summed in a fixed tree.
+__global__ void __launch_bounds__(kLossThreads) rollout_l1_partials_kernel(RolloutLossArgs a, RolloutSegments S, double* part_sum,
+                                                                           int64_t* part_cnt) {
     __shared__ double sh_s[kLossThreads];
     __shared__ int64_t sh_c[kLossThreads];
     const int g = blockIdx.y;
-    const int64_t lo = R.off[g], n_g = R.off[g + 1] - lo;
-    const unsigned grid = loss_grid_of(n_g);
+    const int64_t lo = S.R.off[g], n_g = S.R.off[g + 1] - lo;
+    const unsigned grid = loss_grid(n_g);
     if (blockIdx.x >= grid) return;
-    const float* frames = F.p[g];
+    const float* frames = S.frames[g];
     double s[3] = {0.0, 0.0, 0.0};
     int64_t cnt = 0;
     for (int64_t q = (int64_t)blockIdx.x * kLossThreads + threadIdx.x; q < n_g; q += (int64_t)grid * kLossThreads) {
@@ -372,67 +268,69 @@ __global__ void __launch_bounds__(kLossThreads) rollout_l1_partials_ragged_kerne
     if (threadIdx.x == 0) part_cnt[(size_t)g * kLossGridMax + blockIdx.x] = cnt;
 }
 
-// Pass 2, one workgroup per graph: rollout_l1_finish_kernel's sums and formula on the graph's own partials.
-__global__ void __launch_bounds__(kLossThreads) rollout_l1_finish_ragged_kernel(const double* part_sum, const int64_t* part_cnt, RaggedOffsets R,
-                                                                                int64_t steps, PosScale ps, GraphLoss* graph, double* losses_out,
-                                                                                int64_t* rows_out) {
+struct PosScale { double s[3]; };
+
+// Pass 2, ONE workgroup, the segments in order: loss_g = (s_0 / scale_0 + s_1 / scale_1 + s_2 / scale_2) / (steps * count_g) from
+// the segment's own partials in a fixed tree; then the call's state, the losses and counts added in segment order.
+__global__ void __launch_bounds__(kLossThreads) rollout_l1_finish_kernel(const double* part_sum, const int64_t* part_cnt, RaggedOffsets R,
+                                                                         int64_t steps, PosScale ps, GraphLoss* graph, LossState* st,
+                                                                         double* losses_out, int64_t* rows_out) {
     __shared__ double sh_s[kLossThreads];
     __shared__ int64_t sh_c[kLossThreads];
-    const int g = blockIdx.x;
-    const int n_part = (int)loss_grid_of(R.off[g + 1] - R.off[g]);
-    double s[3];
-    for (int c = 0; c < 3; ++c) {
-        double v = 0.0;
-        for (int i = threadIdx.x; i < n_part; i += kLossThreads) v += part_sum[((size_t)g * 3 + c) * kLossGridMax + i];
-        s[c] = block_sum(v, sh_s);
+    double total = 0.0;      // thread 0's
+    int64_t rows = 0;
+    int bad = 0;
+    for (int g = 0; g < R.n_graphs; ++g) {
+        const int n_part = (int)loss_grid(R.off[g + 1] - R.off[g]);
+        double s[3];
+        for (int c = 0; c < 3; ++c) {
+            double v = 0.0;
+            for (int i = threadIdx.x; i < n_part; i += kLossThreads) v += part_sum[((size_t)g * 3 + c) * kLossGridMax + i];
+            s[c] = block_sum(v, sh_s);
+        }
+        int64_t cnt = 0;
+        for (int i = threadIdx.x; i < n_part; i += kLossThreads) cnt += part_cnt[(size_t)g * kLossGridMax + i];
+        cnt = block_sum(cnt, sh_c);
+        if (threadIdx.x != 0) continue;
+        const double terms = (double)steps * (double)cnt;
+        const double loss = cnt > 0 ? ((s[0] / ps.s[0] + s[1] / ps.s[1]) + s[2] / ps.s[2]) / terms : (double)__builtin_nanf("");
+        graph[g].loss = loss;
+        graph[g].count = cnt;
+        if (losses_out) losses_out[g] = loss;
+        if (rows_out) rows_out[g] = cnt;
+        total = g == 0 ? loss : total + loss;
+        rows += cnt;
+        bad += isfinite(loss) ? 0 : 1;
     }
-    int64_t cnt = 0;
-    for (int i = threadIdx.x; i < n_part; i += kLossThreads) cnt += part_cnt[(size_t)g * kLossGridMax + i];
-    cnt = block_sum(cnt, sh_c);
     if (threadIdx.x != 0) return;
-    const double terms = (double)steps * (double)cnt;
-    const double loss = cnt > 0 ? ((s[0] / ps.s[0] + s[1] / ps.s[1]) + s[2] / ps.s[2]) / terms : (double)__builtin_nanf("");
-    graph[g].loss = loss;
-    graph[g].count = cnt;
-    if (losses_out) losses_out[g] = loss;
-    if (rows_out) rows_out[g] = cnt;
-}
-
-// One thread: the mini-batch's state -- the graphs' losses added in graph order, and how many of them are not finite.
-__global__ void rollout_l1_total_ragged_kernel(const GraphLoss* graph, int n_graphs, LossState* st) {
-    double loss = graph[0].loss;
-    int64_t cnt = graph[0].count;
-    int bad = isfinite(graph[0].loss) ? 0 : 1;
-    for (int g = 1; g < n_graphs; ++g) {
-        loss += graph[g].loss;
-        cnt += graph[g].count;
-        bad += isfinite(graph[g].loss) ? 0 : 1;
-    }
-    st->loss = loss;
-    st->count = cnt;
+    st->loss = total;
+    st->count = rows;
     st->scale = 0.f;
-    st->skip = bad;
+    st->bad = bad;
 }
 
-// Pass 3: rollout_l1_grad_kernel with the row's graph deciding the count and the recorded frame.
-__global__ void __launch_bounds__(kLossThreads) rollout_l1_grad_ragged_kernel(RolloutLossArgs a, RaggedOffsets R, RaggedFrames F, PosScale ps,
-                                                                              const GraphLoss* graph, float* d_records, float* d_final) {
-    __shared__ RaggedRowTable tab;
+// Pass 3: the transpose, every element of d_records [steps,N,D] and d_final [k,N,D] written.  blockIdx.y is the [N,D] slab: slab
+// j < steps is d_records[j], which takes step j - 1's gradient (slab 0: zeros); slab steps + f is frame f of d_final, whose last frame
+// takes the last step's.  An element is sign(pred - frame) * (float)(1.0 / ((scale_c * steps) * count_g)) on the xyz columns of a
+// counted row, with sign(0) = 0, and 0 everywhere else; the row's segment (one segment: no search) decides the count and the frame.
+__global__ void __launch_bounds__(kLossThreads) rollout_l1_grad_kernel(RolloutLossArgs a, RolloutSegments S, PosScale ps, const GraphLoss* graph,
+                                                                       float* d_records, float* d_final) {
+    __shared__ SegmentRows tab;
     __shared__ float sg[GM_RAGGED_MAX_GRAPHS][3];
-    for (int g = threadIdx.x; g < R.n_graphs; g += blockDim.x) {
+    for (int g = threadIdx.x; g < S.R.n_graphs; g += blockDim.x) {
         const int64_t cnt = graph[g].count;
         for (int c = 0; c < 3; ++c) sg[g][c] = cnt > 0 ? (float)(1.0 / ((ps.s[c] * (double)a.steps) * (double)cnt)) : 0.f;
     }
-    stage_row_table(R, F, &tab);
+    stage_segments(S, &tab);
     const int64_t slab = blockIdx.y;
     const size_t frame = (size_t)a.n * a.D;
     float* out = slab < a.steps ? d_records + (size_t)slab * frame : d_final + (size_t)(slab - a.steps) * frame;
     const int64_t t = slab < a.steps ? slab - 1 : (slab == a.steps + a.k - 1 ? a.steps - 1 : -1);
     const float* pred = t >= 0 ? predicted_frame(a, t) : nullptr;
     for (int64_t r = (int64_t)blockIdx.x * kLossThreads + threadIdx.x; r < a.n; r += (int64_t)gridDim.x * kLossThreads) {
-        const int g = graph_of_row(&tab, R.n_graphs, r);
+        const int g = staged_graph_of_row(tab.off, S.R.n_graphs, r);
         const int64_t lo = tab.off[g], n_g = tab.off[g + 1] - lo;
-        const bool counts = t >= 0 && sg[g][0] != 0.f && rollout_row_counts(a, r);
+        const bool counts = t >= 0 && graph[g].count > 0 && rollout_row_counts(a, r);
         for (int c = 0; c < a.D; ++c) {
             float v = 0.f;
             const int ax = c - a.cart;
@@ -445,17 +343,17 @@ __global__ void __launch_bounds__(kLossThreads) rollout_l1_grad_ragged_kernel(Ro
     }
 }
 
-// recorded_poses_kernel for a ragged batch: ranks are global, the frame of a row is its graph's.
-__global__ void __launch_bounds__(kLossThreads) recorded_poses_ragged_kernel(RaggedOffsets R, RaggedFrames F, int frame_dim, int cart,
-                                                                             const int32_t* rank, int64_t n, int64_t n_rigid,
-                                                                             float* trajectory) {
-    __shared__ RaggedRowTable tab;
-    stage_row_table(R, F, &tab);
+// The scripted poses of a recorded drive: trajectory[t][rigid_rank[r]] = xyz(frames of r's segment [t][r - its first row]); ranks
+// are global.
+__global__ void __launch_bounds__(kLossThreads) recorded_poses_kernel(RolloutSegments S, int frame_dim, int cart, const int32_t* rank,
+                                                                      int64_t n, int64_t n_rigid, float* trajectory) {
+    __shared__ SegmentRows tab;
+    stage_segments(S, &tab);
     const int64_t r = (int64_t)blockIdx.x * kLossThreads + threadIdx.x, t = blockIdx.y;
     if (r >= n) return;
     const int64_t j = rank[r];
     if (j < 0 || j >= n_rigid) return;
-    const int g = graph_of_row(&tab, R.n_graphs, r);
+    const int g = staged_graph_of_row(tab.off, S.R.n_graphs, r);
     const int64_t lo = tab.off[g], n_g = tab.off[g + 1] - lo;
     const float* f = tab.frames[g] + ((size_t)t * n_g + (r - lo)) * frame_dim + cart;
     float* o = trajectory + ((size_t)t * n_rigid + j) * 3;
@@ -482,59 +380,35 @@ int check_rollout_loss_args(const gm_feature_desc* fd, int64_t n, int64_t steps,
     return GM_OK;
 }
 
-// the launches of a rollout loss; the arguments are checked.  d_records / d_final: both or neither.
-int run_rollout_loss(const RolloutLossArgs& a, const double* pos_scale, const RolloutLossWs& w, double* loss_out, int64_t* rows_out,
-                     float* d_records, float* d_final, hipStream_t s) {
-    PosScale ps{{1.0, 1.0, 1.0}};
-    for (int c = 0; pos_scale && c < 3; ++c) ps.s[c] = pos_scale[c];
-    const unsigned g = loss_grid(a.n);
-    hipLaunchKernelGGL(rollout_l1_partials_kernel, dim3(g), dim3(kLossThreads), 0, s, a, w.part_sum, w.part_cnt);
-    GM_LAUNCH_CHECK();
-    hipLaunchKernelGGL(rollout_l1_finish_kernel, dim3(1), dim3(kLossThreads), 0, s, w.part_sum, w.part_cnt, (int)g, a.steps, ps, w.state,
-                       loss_out, rows_out);
-    GM_LAUNCH_CHECK();
-    if (d_records && d_final) {
-        hipLaunchKernelGGL(rollout_l1_grad_kernel, dim3(g, (unsigned)(a.steps + a.k)), dim3(kLossThreads), 0, s, a, ps, w.state, d_records,
-                           d_final);
-        GM_LAUNCH_CHECK();
-    }
-    return GM_OK;
-}
-
-// the launches of a ragged rollout loss; the arguments are checked.  a.n: the total rows, a.frames unused.
-int run_rollout_loss_ragged(const RolloutLossArgs& a, const RaggedOffsets& R, const RaggedFrames& F, const double* pos_scale,
-                            const RolloutLossRaggedWs& w, double* losses_out, int64_t* rows_out, float* d_records, float* d_final,
-                            hipStream_t s) {
+// the launches of a rollout loss: partials, finish and, with d_records / d_final (both or neither), the transpose.  The arguments
+// are checked; a.n: the rows of all segments.
+int run_rollout_loss(const RolloutLossArgs& a, const RolloutSegments& S, const double* pos_scale, const RolloutLossWs& w, double* losses_out,
+                     int64_t* rows_out, float* d_records, float* d_final, hipStream_t s) {
     PosScale ps{{1.0, 1.0, 1.0}};
     for (int c = 0; pos_scale && c < 3; ++c) ps.s[c] = pos_scale[c];
     unsigned gmax = 1;
-    for (int g = 0; g < R.n_graphs; ++g) gmax = std::max(gmax, loss_grid_of(R.off[g + 1] - R.off[g]));
-    hipLaunchKernelGGL(rollout_l1_partials_ragged_kernel, dim3(gmax, (unsigned)R.n_graphs), dim3(kLossThreads), 0, s, a, R, F, w.part_sum,
-                       w.part_cnt);
+    for (int g = 0; g < S.R.n_graphs; ++g) gmax = std::max(gmax, loss_grid(S.R.off[g + 1] - S.R.off[g]));
+    hipLaunchKernelGGL(rollout_l1_partials_kernel, dim3(gmax, (unsigned)S.R.n_graphs), dim3(kLossThreads), 0, s, a, S, w.part_sum, w.part_cnt);
     GM_LAUNCH_CHECK();
-    hipLaunchKernelGGL(rollout_l1_finish_ragged_kernel, dim3((unsigned)R.n_graphs), dim3(kLossThreads), 0, s, w.part_sum, w.part_cnt, R, a.steps,
-                       ps, w.graph, losses_out, rows_out);
-    GM_LAUNCH_CHECK();
-    hipLaunchKernelGGL(rollout_l1_total_ragged_kernel, dim3(1), dim3(1), 0, s, w.graph, R.n_graphs, w.state);
+    hipLaunchKernelGGL(rollout_l1_finish_kernel, dim3(1), dim3(kLossThreads), 0, s, w.part_sum, w.part_cnt, S.R, a.steps, ps, w.graph, w.state,
+                       losses_out, rows_out);
     GM_LAUNCH_CHECK();
     if (d_records && d_final) {
-        hipLaunchKernelGGL(rollout_l1_grad_ragged_kernel, dim3(loss_grid(a.n), (unsigned)(a.steps + a.k)), dim3(kLossThreads), 0, s, a, R, F, ps,
-                           w.graph, d_records, d_final);
+        hipLaunchKernelGGL(rollout_l1_grad_kernel, dim3(loss_grid(a.n), (unsigned)(a.steps + a.k)), dim3(kLossThreads), 0, s, a, S, ps, w.graph,
+                           d_records, d_final);
         GM_LAUNCH_CHECK();
     }
     return GM_OK;
 }
 // the table and the frame pointers of a ragged loss, checked
 int ragged_loss_table(const char* who, const gm_feature_desc* fd, const int64_t* offsets_host, int64_t n_graphs, int K, const void* ws,
-                      const float* const* frames_host, RaggedOffsets* R, RaggedFrames* F) {
-    GM_REQUIRE(fd && ws && frames_host, GM_ERR_INVALID_ARGUMENT, "%s: null pointer", who);
-    GM_REQUIRE(fd->nodes_per_graph == 0, GM_ERR_INVALID_ARGUMENT, "%s: nodes_per_graph=%lld, must be 0 (the graphs come in graph_offsets)", who,
-               (long long)fd->nodes_per_graph);
-    const int rc = ragged_offsets(offsets_host, n_graphs, fd->conn_r, K, ws, who, R);
+                      const float* const* frames_host, RolloutSegments* S) {
+    GM_REQUIRE(frames_host, GM_ERR_INVALID_ARGUMENT, "%s: null pointer", who);
+    const int rc = ragged_scene_table(who, fd, offsets_host, n_graphs, K, ws, &S->R);
     if (rc != GM_OK) return rc;
     for (int g = 0; g < GM_RAGGED_MAX_GRAPHS; ++g) {
-        F->p[g] = g < R->n_graphs ? frames_host[g] : nullptr;
-        GM_REQUIRE(g >= R->n_graphs || F->p[g], GM_ERR_INVALID_ARGUMENT, "%s: null pointer (frames[%d])", who, g);
+        S->frames[g] = g < S->R.n_graphs ? frames_host[g] : nullptr;
+        GM_REQUIRE(g >= S->R.n_graphs || S->frames[g], GM_ERR_INVALID_ARGUMENT, "%s: null pointer (frames[%d])", who, g);
     }
     return GM_OK;
 }
@@ -568,8 +442,8 @@ __global__ void trainer_record_set_kernel(TrainerRecord* rec, int64_t applied, i
 __global__ void adam_prepare_kernel(const LossState* st, TrainerRecord* rec, AdamScalars* sc, double beta1, double beta2, double lr,
                                     double* loss_out) {
     if (loss_out) *loss_out = st->loss;
-    sc->skip = st->skip;
-    if (st->skip) {
+    sc->skip = st->bad != 0;
+    if (st->bad) {
         rec->steps_skipped += 1;
         return;
     }
@@ -591,17 +465,11 @@ __global__ void accum_reset_kernel(AccumRecord* acc) {
     acc->scale = (double)__builtin_nanf("");
 }
 
-// One thread: a sample joins the mini-batch, in arrival order.
-__global__ void accum_add_kernel(const LossState* st, AccumRecord* acc) {
-    acc->samples += 1;
-    acc->loss_sum += st->loss;
-    if (st->skip) acc->bad += 1;
-}
-
-// One thread: the graphs of a ragged rollout batch join the mini-batch together.  st: run_rollout_loss_ragged's.
-__global__ void accum_add_batch_kernel(const LossState* st, AccumRecord* acc, int n_graphs) {
-    acc->samples += n_graphs;
-    acc->bad += st->skip;
+// One thread: the samples behind a loss join the mini-batch together, in arrival order -- one sample, or the n_samples graphs of
+// a ragged rollout batch (st->loss their sum).
+__global__ void accum_add_batch_kernel(const LossState* st, AccumRecord* acc, int n_samples) {
+    acc->samples += n_samples;
+    acc->bad += st->bad;
     acc->loss_sum += st->loss;
 }
 
@@ -852,9 +720,9 @@ bool rollout_step_sizes_ok(const gm_model_desc* d, const gm_feature_desc* fd, in
     return d && fd && n >= 1 && n_rigid >= 0 && n_rigid <= n && K >= 1 && steps >= 1 && steps <= kRolloutStepsMax && fd->k_steps >= 2 &&
            fd->k_steps <= 64 && fd->data_dim >= 4 && n < ((int64_t)1 << 31) / K;
 }
-// loss_bytes: the loss's workspace (0: gm_rollout_l1_loss's; a ragged batch passes gm_rollout_l1_loss_ragged's)
+// n_graphs: the segments of the loss (1: gm_train_rollout_step's; a ragged batch: its graphs)
 RolloutStepWs carve_rollout_step(void* ws, const gm_model_desc* d, const gm_feature_desc* fd, int64_t n, int64_t n_rigid, int K,
-                                 int64_t steps, size_t loss_bytes = 0) {
+                                 int64_t steps, int64_t n_graphs) {
     RolloutStepWs w;
     const size_t window = (size_t)fd->k_steps * n * fd->data_dim;
     w.rollout_bytes = gm_rollout_workspace_bytes(d, n, K);
@@ -865,7 +733,7 @@ RolloutStepWs carve_rollout_step(void* ws, const gm_model_desc* d, const gm_feat
     w.d_final = c.take<float>(window);
     w.d_obs0 = c.take<float>(window);
     w.trajectory = c.take<float>((size_t)steps * n_rigid * 3);
-    w.loss = c.take<char>(loss_bytes ? loss_bytes : carve_rollout_loss(nullptr).bytes);
+    w.loss = c.take<char>(carve_rollout_loss(nullptr, n_graphs).bytes);
     w.rollout = c.take<char>(w.rollout_bytes);
     w.sweep = c.take<char>(w.sweep_bytes);
     w.bytes = c.used();
@@ -888,11 +756,11 @@ int adam_update(gm_trainer* t, const LossState* st, double lr, double* loss_out,
     return adam_flat<false>(t, s);
 }
 
-// A sample joins the pending mini-batch: the device record, then the host count.
-int accumulate_sample(gm_trainer* t, const LossState* st, hipStream_t s) {
-    hipLaunchKernelGGL(accum_add_kernel, dim3(1), dim3(1), 0, s, st, t->acc);
+// The samples behind a loss join the pending mini-batch: the device record, then the host count.
+int accumulate_samples(gm_trainer* t, const LossState* st, int64_t samples, hipStream_t s) {
+    hipLaunchKernelGGL(accum_add_batch_kernel, dim3(1), dim3(1), 0, s, st, t->acc, (int)samples);
     GM_LAUNCH_CHECK();
-    t->pending += 1;
+    t->pending += samples;
     return GM_OK;
 }
 
@@ -1063,7 +931,7 @@ int gm_train_step_accumulate(gm_trainer* t, const float* nodes, int64_t n, const
     rc = step_gradients(t, nodes, n, edge_attr, edge_index, e, target, mask_col, false, loss_out, ws, s);
     if (rc != GM_OK) return rc;
     t->pending = pending;
-    return accumulate_sample(t, carve_loss(t->loss_ws).state, s);
+    return accumulate_samples(t, carve_loss(t->loss_ws).state, 1, s);
 }
 
 int gm_trainer_apply(gm_trainer* t, double lr, double max_grad_norm, double* loss_out, double* grad_norm_out, void* stream) {
@@ -1176,7 +1044,7 @@ int gm_trainer_reduce(gm_trainer* t, const void* contributions_dev, int world, s
 
 size_t gm_rollout_l1_loss_workspace_bytes(int64_t n_nodes, int64_t steps) {
     if (n_nodes < 1 || steps < 1 || steps > kRolloutStepsMax) return 0;
-    return carve_rollout_loss(nullptr).bytes;
+    return carve_rollout_loss(nullptr, 1).bytes;
 }
 
 int gm_rollout_l1_loss(const float* windows, const float* final_state, const float* frames, int frame_dim, int64_t steps, int64_t n,
@@ -1186,36 +1054,80 @@ int gm_rollout_l1_loss(const float* windows, const float* final_state, const flo
     if (rc != GM_OK) return rc;
     GM_REQUIRE(windows && final_state && frames && loss_out && ws, GM_ERR_INVALID_ARGUMENT, "%s: null pointer", __func__);
     GM_REQUIRE((d_records != nullptr) == (d_final != nullptr), GM_ERR_INVALID_ARGUMENT, "%s: d_records and d_final go together", __func__);
-    const RolloutLossWs w = carve_rollout_loss(ws);
+    const RolloutLossWs w = carve_rollout_loss(ws, 1);
     GM_REQUIRE(ws_bytes >= w.bytes, GM_ERR_WORKSPACE, "%s: workspace %zu < %zu", __func__, ws_bytes, w.bytes);
     gm::DevGuard dev_guard(windows);
-    const RolloutLossArgs a{windows, final_state, frames, rigid_rank, n, steps, fd->k_steps, fd->data_dim, frame_dim, fd->cart_col,
+    const RolloutLossArgs a{windows, final_state, rigid_rank, n, steps, fd->k_steps, fd->data_dim, frame_dim, fd->cart_col,
                             material_col < 0 ? -1 : material_col};
-    return run_rollout_loss(a, pos_scale, w, loss_out, rows_counted_out, d_records, d_final, (hipStream_t)stream);
+    return run_rollout_loss(a, one_segment(n, frames), pos_scale, w, loss_out, rows_counted_out, d_records, d_final, (hipStream_t)stream);
+}
+
+size_t gm_rollout_l1_loss_ragged_workspace_bytes(int64_t n_graphs) {
+    if (n_graphs < 1 || n_graphs > GM_RAGGED_MAX_GRAPHS) return 0;
+    return carve_rollout_loss(nullptr, n_graphs).bytes;
+}
+
+int gm_rollout_l1_loss_ragged(const float* windows, const float* final_state, const float* const* frames_host, int frame_dim, int64_t steps,
+                              const int64_t* graph_offsets_host, int64_t n_graphs, const gm_feature_desc* fd, const int32_t* rigid_rank,
+                              int material_col, const double* pos_scale, double* losses_out, int64_t* rows_counted_out, float* d_records,
+                              float* d_final, void* ws, size_t ws_bytes, void* stream) {
+    RolloutSegments S;
+    int rc = ragged_loss_table(__func__, fd, graph_offsets_host, n_graphs, 1, ws, frames_host, &S);
+    if (rc != GM_OK) return rc;
+    const int64_t n = S.R.off[S.R.n_graphs];
+    rc = check_rollout_loss_args(fd, n, steps, frame_dim, material_col, pos_scale, __func__);
+    if (rc != GM_OK) return rc;
+    GM_REQUIRE(windows && final_state && losses_out, GM_ERR_INVALID_ARGUMENT, "%s: null pointer", __func__);
+    GM_REQUIRE((d_records != nullptr) == (d_final != nullptr), GM_ERR_INVALID_ARGUMENT, "%s: d_records and d_final go together", __func__);
+    const RolloutLossWs w = carve_rollout_loss(ws, n_graphs);
+    GM_REQUIRE(ws_bytes >= w.bytes, GM_ERR_WORKSPACE, "%s: workspace %zu < %zu", __func__, ws_bytes, w.bytes);
+    gm::DevGuard dev_guard(windows);
+    const RolloutLossArgs a{windows, final_state, rigid_rank, n, steps, fd->k_steps, fd->data_dim, frame_dim, fd->cart_col,
+                            material_col < 0 ? -1 : material_col};
+    return run_rollout_loss(a, S, pos_scale, w, losses_out, rows_counted_out, d_records, d_final, (hipStream_t)stream);
 }
 
 size_t gm_train_rollout_step_workspace_bytes(const gm_model_desc* desc, const gm_feature_desc* fdesc, int64_t n, int64_t n_rigid, int K,
                                              int64_t steps) {
     if (!rollout_step_sizes_ok(desc, fdesc, n, n_rigid, K, steps)) return 0;
-    return carve_rollout_step(nullptr, desc, fdesc, n, n_rigid, K, steps).bytes;
+    return carve_rollout_step(nullptr, desc, fdesc, n, n_rigid, K, steps, 1).bytes;
 }
 
-// gm_train_rollout_step (mode kRolloutEvaluate for update == 0, kRolloutStep) and gm_train_rollout_accumulate (kRolloutAccumulate)
+size_t gm_train_rollout_ragged_workspace_bytes(const gm_model_desc* desc, const gm_feature_desc* fdesc, int64_t n_total, int64_t n_rigid_total,
+                                               int64_t n_graphs, int K, int64_t steps) {
+    if (n_graphs < 1 || n_graphs > GM_RAGGED_MAX_GRAPHS || n_total < n_graphs) return 0;
+    if (!rollout_step_sizes_ok(desc, fdesc, n_total, n_rigid_total, K, steps)) return 0;
+    return carve_rollout_step(nullptr, desc, fdesc, n_total, n_rigid_total, K, steps, n_graphs).bytes;
+}
+
+// A training sample, or a mini-batch of them, on a rollout: gm_train_rollout_step (mode kRolloutEvaluate for update == 0,
+// kRolloutStep), gm_train_rollout_accumulate (kRolloutAccumulate) and, with a batch, gm_train_rollout_accumulate_ragged
+// (kRolloutAccumulate / kRolloutEvaluate): the windows of the batch's graphs side by side as ONE ragged rollout, one loss per graph,
+// one sweep and one update of the mini-batch's record.
 enum { kRolloutEvaluate = 0, kRolloutStep = 1, kRolloutAccumulate = 2 };
-static int train_rollout(gm_trainer* t, const float* obs0, int64_t n, const gm_feature_desc* fd, int K, const int32_t* rigid_rank,
-                         int64_t n_rigid, const float* frames, int frame_dim, int64_t steps, int material_col, const double* pos_scale,
-                         double lr, int mode, double* loss_out, void* ws, size_t ws_bytes, void* stream, const char* who) {
+struct RaggedBatch {   // checked (ragged_loss_table); its rows are n
+    const int64_t* offsets_host;
+    int64_t n_graphs;
+    RolloutSegments S;
+};
+// batch == null: one sample, its recording in `frames`, its loss into loss_out (optional).  Else one loss per graph (required).
+static int train_rollout(gm_trainer* t, const float* obs0, int64_t n, const RaggedBatch* batch, const gm_feature_desc* fd, int K,
+                         const int32_t* rigid_rank, int64_t n_rigid, const float* frames, int frame_dim, int64_t steps, int material_col,
+                         const double* pos_scale, double lr, int mode, double* loss_out, void* ws, size_t ws_bytes, void* stream,
+                         const char* who) {
     GM_REQUIRE(t, GM_ERR_INVALID_ARGUMENT, "%s: null trainer", who);
     gm_model* m = t->m;
     int rc = check_rollout_loss_args(fd, n, steps, frame_dim, material_col, pos_scale, who);
     if (rc != GM_OK) return rc;
     GM_REQUIRE(rollout_step_sizes_ok(&m->d, fd, n, n_rigid, K, steps), GM_ERR_INVALID_ARGUMENT,
                "%s: sizes out of range (n_nodes=%lld, n_rigid=%lld, max_neighbours=%d)", who, (long long)n, (long long)n_rigid, K);
-    GM_REQUIRE(obs0 && frames && ws && (rigid_rank || n_rigid == 0), GM_ERR_INVALID_ARGUMENT, "%s: null pointer", who);
+    GM_REQUIRE(obs0 && ws && (batch ? loss_out != nullptr : frames != nullptr) && (rigid_rank || n_rigid == 0), GM_ERR_INVALID_ARGUMENT,
+               "%s: null pointer", who);
     GM_REQUIRE(lr == lr, GM_ERR_INVALID_ARGUMENT, "%s: lr is NaN", who);
     rc = gm::check_model_for_scene(m->d, fd, who);
     if (rc != GM_OK) return rc;
-    const RolloutStepWs w = carve_rollout_step(ws, &m->d, fd, n, n_rigid, K, steps);
+    const int64_t samples = batch ? batch->n_graphs : 1;
+    const RolloutStepWs w = carve_rollout_step(ws, &m->d, fd, n, n_rigid, K, steps, samples);
     GM_REQUIRE(ws_bytes >= w.bytes, GM_ERR_WORKSPACE, "%s: workspace %zu < %zu", who, ws_bytes, w.bytes);
     GM_REQUIRE(mode != kRolloutAccumulate || t->pending >= 0, GM_ERR_INVALID_ARGUMENT, "%s: no mini-batch begun (gm_trainer_begin)", who);
     gm::DevGuard dev_guard(obs0);
@@ -1226,11 +1138,12 @@ static int train_rollout(gm_trainer* t, const float* obs0, int64_t n, const gm_f
     const size_t window = (size_t)fd->k_steps * n * fd->data_dim;
     const bool scripted = n_rigid > 0;
     const float* trajectory = scripted ? w.trajectory : nullptr;
+    const RolloutSegments S = batch ? batch->S : one_segment(n, frames);
 
-    // 1. the recorded poses of the rigid rows as a trajectory
+    // 1. the recorded poses of the rigid rows as one trajectory [steps, n_rigid, 3]: ranks are global
     if (scripted) {
-        hipLaunchKernelGGL(recorded_poses_kernel, dim3((unsigned)cdiv(n, kLossThreads), (unsigned)steps), dim3(kLossThreads), 0, s, frames,
-                           frame_dim, fd->cart_col, rigid_rank, n, n_rigid, w.trajectory);
+        hipLaunchKernelGGL(recorded_poses_kernel, dim3((unsigned)cdiv(n, kLossThreads), (unsigned)steps), dim3(kLossThreads), 0, s, S, frame_dim,
+                           fd->cart_col, rigid_rank, n, n_rigid, w.trajectory);
         GM_LAUNCH_CHECK();
     }
     // 2. the inference rollout, each step in place on a copy of the window before it: window t stays behind as step t's pre-step window
@@ -1238,138 +1151,58 @@ static int train_rollout(gm_trainer* t, const float* obs0, int64_t n, const gm_f
     for (int64_t i = 0; i < steps; ++i) {
         float* next = w.windows + (size_t)(i + 1) * window;
         GM_HIP_CHECK(hipMemcpyAsync(next, next - window, window * sizeof(float), hipMemcpyDeviceToDevice, s));
-        rc = gm_rollout_step(m, next, n, fd, K, rigid_rank, scripted ? trajectory + (size_t)i * n_rigid * 3 : nullptr, nullptr, w.rollout,
-                             w.rollout_bytes, stream);
+        const float* poses = scripted ? trajectory + (size_t)i * n_rigid * 3 : nullptr;
+        rc = batch ? gm_rollout_step_ragged(m, next, batch->offsets_host, batch->n_graphs, fd, K, rigid_rank, poses, nullptr, w.rollout,
+                                            w.rollout_bytes, stream)
+                   : gm_rollout_step(m, next, n, fd, K, rigid_rank, poses, nullptr, w.rollout, w.rollout_bytes, stream);
         if (rc != GM_OK) return rc;
     }
-    // 3. the loss, and for an update its transpose
-    const RolloutLossArgs a{w.windows, w.windows + (size_t)steps * window, frames, rigid_rank, n, steps, fd->k_steps, fd->data_dim, frame_dim,
+    // 3. the loss (one per graph of a batch, and the state of all), and for an update its transpose
+    const RolloutLossArgs a{w.windows, w.windows + (size_t)steps * window, rigid_rank, n, steps, fd->k_steps, fd->data_dim, frame_dim,
                             fd->cart_col, material_col < 0 ? -1 : material_col};
-    const RolloutLossWs lw = carve_rollout_loss(w.loss);
-    rc = run_rollout_loss(a, pos_scale, lw, loss_out, nullptr, update ? w.d_records : nullptr, update ? w.d_final : nullptr, s);
+    const RolloutLossWs lw = carve_rollout_loss(w.loss, samples);
+    rc = run_rollout_loss(a, S, pos_scale, lw, loss_out, nullptr, update ? w.d_records : nullptr, update ? w.d_final : nullptr, s);
     if (rc != GM_OK || !update) return rc;
     // 4. the reverse sweep into the trainer's gradients (a step clears them first), then Adam under gm_train_step's skip rule, or the
-    //    sample joins the pending mini-batch
+    //    samples join the pending mini-batch in one launch on its record
     if (mode == kRolloutStep) GM_HIP_CHECK(hipMemsetAsync(t->grad, 0, t->alloc * sizeof(float), s));
-    rc = gm_rollout_backward_train(m, t->T.data(), (int)t->T.size(), w.windows, n, fd, K, rigid_rank, trajectory, scripted ? steps : 0, n_rigid,
-                                   steps, w.d_final, w.d_records, t->G.data(), w.d_obs0, nullptr, w.sweep, w.sweep_bytes, stream);
+    const int nt = (int)t->T.size();
+    const int64_t n_targets = scripted ? steps : 0;
+    rc = batch ? gm_rollout_backward_train_ragged(m, t->T.data(), nt, w.windows, batch->offsets_host, batch->n_graphs, fd, K, rigid_rank,
+                                                  trajectory, n_targets, n_rigid, steps, w.d_final, w.d_records, t->G.data(), w.d_obs0,
+                                                  nullptr, w.sweep, w.sweep_bytes, stream)
+               : gm_rollout_backward_train(m, t->T.data(), nt, w.windows, n, fd, K, rigid_rank, trajectory, n_targets, n_rigid, steps,
+                                           w.d_final, w.d_records, t->G.data(), w.d_obs0, nullptr, w.sweep, w.sweep_bytes, stream);
     if (rc != GM_OK) return rc;
     if (mode == kRolloutStep) return adam_update(t, lw.state, lr, loss_out, s);
     t->pending = pending;
-    return accumulate_sample(t, lw.state, s);
+    return accumulate_samples(t, lw.state, samples, s);
 }
 
 int gm_train_rollout_step(gm_trainer* t, const float* obs0, int64_t n, const gm_feature_desc* fd, int K, const int32_t* rigid_rank,
                           int64_t n_rigid, const float* frames, int frame_dim, int64_t steps, int material_col, const double* pos_scale,
                           double lr, int update, double* loss_out, void* ws, size_t ws_bytes, void* stream) {
-    return train_rollout(t, obs0, n, fd, K, rigid_rank, n_rigid, frames, frame_dim, steps, material_col, pos_scale, lr,
+    return train_rollout(t, obs0, n, nullptr, fd, K, rigid_rank, n_rigid, frames, frame_dim, steps, material_col, pos_scale, lr,
                          update ? kRolloutStep : kRolloutEvaluate, loss_out, ws, ws_bytes, stream, __func__);
 }
 
 int gm_train_rollout_accumulate(gm_trainer* t, const float* obs0, int64_t n, const gm_feature_desc* fd, int K, const int32_t* rigid_rank,
                                 int64_t n_rigid, const float* frames, int frame_dim, int64_t steps, int material_col,
                                 const double* pos_scale, double* loss_out, void* ws, size_t ws_bytes, void* stream) {
-    return train_rollout(t, obs0, n, fd, K, rigid_rank, n_rigid, frames, frame_dim, steps, material_col, pos_scale, 0.0, kRolloutAccumulate,
-                         loss_out, ws, ws_bytes, stream, __func__);
+    return train_rollout(t, obs0, n, nullptr, fd, K, rigid_rank, n_rigid, frames, frame_dim, steps, material_col, pos_scale, 0.0,
+                         kRolloutAccumulate, loss_out, ws, ws_bytes, stream, __func__);
 }
 
-// ---- the same on a ragged batch of rollout windows
-size_t gm_rollout_l1_loss_ragged_workspace_bytes(int64_t n_graphs) {
-    if (n_graphs < 1 || n_graphs > GM_RAGGED_MAX_GRAPHS) return 0;
-    return carve_rollout_loss_ragged(nullptr, n_graphs).bytes;
-}
-
-int gm_rollout_l1_loss_ragged(const float* windows, const float* final_state, const float* const* frames_host, int frame_dim, int64_t steps,
-                              const int64_t* graph_offsets_host, int64_t n_graphs, const gm_feature_desc* fd, const int32_t* rigid_rank,
-                              int material_col, const double* pos_scale, double* losses_out, int64_t* rows_counted_out, float* d_records,
-                              float* d_final, void* ws, size_t ws_bytes, void* stream) {
-    RaggedOffsets R;
-    RaggedFrames F;
-    int rc = ragged_loss_table(__func__, fd, graph_offsets_host, n_graphs, 1, ws, frames_host, &R, &F);
-    if (rc != GM_OK) return rc;
-    const int64_t n = R.off[R.n_graphs];
-    rc = check_rollout_loss_args(fd, n, steps, frame_dim, material_col, pos_scale, __func__);
-    if (rc != GM_OK) return rc;
-    GM_REQUIRE(windows && final_state && losses_out, GM_ERR_INVALID_ARGUMENT, "%s: null pointer", __func__);
-    GM_REQUIRE((d_records != nullptr) == (d_final != nullptr), GM_ERR_INVALID_ARGUMENT, "%s: d_records and d_final go together", __func__);
-    const RolloutLossRaggedWs w = carve_rollout_loss_ragged(ws, n_graphs);
-    GM_REQUIRE(ws_bytes >= w.bytes, GM_ERR_WORKSPACE, "%s: workspace %zu < %zu", __func__, ws_bytes, w.bytes);
-    gm::DevGuard dev_guard(windows);
-    const RolloutLossArgs a{windows, final_state, nullptr, rigid_rank, n, steps, fd->k_steps, fd->data_dim, frame_dim, fd->cart_col,
-                            material_col < 0 ? -1 : material_col};
-    return run_rollout_loss_ragged(a, R, F, pos_scale, w, losses_out, rows_counted_out, d_records, d_final, (hipStream_t)stream);
-}
-
-size_t gm_train_rollout_ragged_workspace_bytes(const gm_model_desc* desc, const gm_feature_desc* fdesc, int64_t n_total, int64_t n_rigid_total,
-                                               int64_t n_graphs, int K, int64_t steps) {
-    if (n_graphs < 1 || n_graphs > GM_RAGGED_MAX_GRAPHS || n_total < n_graphs) return 0;
-    if (!rollout_step_sizes_ok(desc, fdesc, n_total, n_rigid_total, K, steps)) return 0;
-    return carve_rollout_step(nullptr, desc, fdesc, n_total, n_rigid_total, K, steps, carve_rollout_loss_ragged(nullptr, n_graphs).bytes).bytes;
-}
-
-// train_rollout's accumulate (update != 0) and evaluate (update == 0) on a mini-batch of rollout windows as ONE ragged rollout, one
-// loss, one sweep and one update of the mini-batch's record
 int gm_train_rollout_accumulate_ragged(gm_trainer* t, const float* obs0, const int64_t* graph_offsets_host, int64_t n_graphs,
                                        const gm_feature_desc* fd, int K, const int32_t* rigid_rank, int64_t n_rigid,
                                        const float* const* frames_host, int frame_dim, int64_t steps, int material_col,
                                        const double* pos_scale, int update, double* losses_out, void* ws, size_t ws_bytes, void* stream) {
-    const char* who = __func__;
-    GM_REQUIRE(t, GM_ERR_INVALID_ARGUMENT, "%s: null trainer", who);
-    gm_model* m = t->m;
-    RaggedOffsets R;
-    RaggedFrames F;
-    int rc = ragged_loss_table(who, fd, graph_offsets_host, n_graphs, K, ws, frames_host, &R, &F);
+    GM_REQUIRE(t, GM_ERR_INVALID_ARGUMENT, "%s: null trainer", __func__);
+    RaggedBatch batch{graph_offsets_host, n_graphs, {}};
+    const int rc = ragged_loss_table(__func__, fd, graph_offsets_host, n_graphs, K, ws, frames_host, &batch.S);
     if (rc != GM_OK) return rc;
-    const int64_t n = R.off[R.n_graphs];
-    rc = check_rollout_loss_args(fd, n, steps, frame_dim, material_col, pos_scale, who);
-    if (rc != GM_OK) return rc;
-    GM_REQUIRE(rollout_step_sizes_ok(&m->d, fd, n, n_rigid, K, steps), GM_ERR_INVALID_ARGUMENT,
-               "%s: sizes out of range (n_nodes=%lld, n_rigid=%lld, max_neighbours=%d)", who, (long long)n, (long long)n_rigid, K);
-    GM_REQUIRE(obs0 && losses_out && (rigid_rank || n_rigid == 0), GM_ERR_INVALID_ARGUMENT, "%s: null pointer", who);
-    rc = gm::check_model_for_scene(m->d, fd, who);
-    if (rc != GM_OK) return rc;
-    const size_t loss_bytes = carve_rollout_loss_ragged(nullptr, n_graphs).bytes;
-    const RolloutStepWs w = carve_rollout_step(ws, &m->d, fd, n, n_rigid, K, steps, loss_bytes);
-    GM_REQUIRE(ws_bytes >= w.bytes, GM_ERR_WORKSPACE, "%s: workspace %zu < %zu", who, ws_bytes, w.bytes);
-    GM_REQUIRE(!update || t->pending >= 0, GM_ERR_INVALID_ARGUMENT, "%s: no mini-batch begun (gm_trainer_begin)", who);
-    gm::DevGuard dev_guard(obs0);
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t pending = t->pending;
-    if (update) t->pending = -1;   // a failing accumulate leaves the mini-batch undefined
-    const size_t window = (size_t)fd->k_steps * n * fd->data_dim;
-    const bool scripted = n_rigid > 0;
-    const float* trajectory = scripted ? w.trajectory : nullptr;
-
-    // 1. the recorded poses of every graph's rigid rows as one trajectory [steps, n_rigid, 3]: ranks are global
-    if (scripted) {
-        hipLaunchKernelGGL(recorded_poses_ragged_kernel, dim3((unsigned)cdiv(n, kLossThreads), (unsigned)steps), dim3(kLossThreads), 0, s, R, F,
-                           frame_dim, fd->cart_col, rigid_rank, n, n_rigid, w.trajectory);
-        GM_LAUNCH_CHECK();
-    }
-    // 2. the ragged inference rollout keeping its windows
-    GM_HIP_CHECK(hipMemcpyAsync(w.windows, obs0, window * sizeof(float), hipMemcpyDeviceToDevice, s));
-    for (int64_t i = 0; i < steps; ++i) {
-        float* next = w.windows + (size_t)(i + 1) * window;
-        GM_HIP_CHECK(hipMemcpyAsync(next, next - window, window * sizeof(float), hipMemcpyDeviceToDevice, s));
-        rc = gm_rollout_step_ragged(m, next, graph_offsets_host, n_graphs, fd, K, rigid_rank,
-                                    scripted ? trajectory + (size_t)i * n_rigid * 3 : nullptr, nullptr, w.rollout, w.rollout_bytes, stream);
-        if (rc != GM_OK) return rc;
-    }
-    // 3. one loss per graph and the mini-batch's state, and for an update the transpose
-    const RolloutLossArgs a{w.windows, w.windows + (size_t)steps * window, nullptr, rigid_rank, n, steps, fd->k_steps, fd->data_dim, frame_dim,
-                            fd->cart_col, material_col < 0 ? -1 : material_col};
-    const RolloutLossRaggedWs lw = carve_rollout_loss_ragged(w.loss, n_graphs);
-    rc = run_rollout_loss_ragged(a, R, F, pos_scale, lw, losses_out, nullptr, update ? w.d_records : nullptr, update ? w.d_final : nullptr, s);
-    if (rc != GM_OK || !update) return rc;
-    // 4. one sweep into the trainer's gradients, one launch on the mini-batch's record
-    rc = gm_rollout_backward_train_ragged(m, t->T.data(), (int)t->T.size(), w.windows, graph_offsets_host, n_graphs, fd, K, rigid_rank,
-                                          trajectory, scripted ? steps : 0, n_rigid, steps, w.d_final, w.d_records, t->G.data(), w.d_obs0,
-                                          nullptr, w.sweep, w.sweep_bytes, stream);
-    if (rc != GM_OK) return rc;
-    hipLaunchKernelGGL(accum_add_batch_kernel, dim3(1), dim3(1), 0, s, lw.state, t->acc, (int)n_graphs);
-    GM_LAUNCH_CHECK();
-    t->pending = pending + n_graphs;
-    return GM_OK;
+    return train_rollout(t, obs0, batch.S.R.off[batch.S.R.n_graphs], &batch, fd, K, rigid_rank, n_rigid, nullptr, frame_dim, steps, material_col,
+                         pos_scale, 0.0, update ? kRolloutAccumulate : kRolloutEvaluate, losses_out, ws, ws_bytes, stream, __func__);
 }
 
 int gm_trainer_record(const gm_trainer* t, void* record_host, void* stream) {

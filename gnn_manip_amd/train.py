@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._lib import GMError, ModelDesc, check, current_stream, lib, ptr
+from ._lib import RAGGED_MAX_GRAPHS, GMError, ModelDesc, check, current_stream, lib, ptr
 from .dataset import GraphData
 from .epd_gnn import TRAIN_WIDTHS, DstCsr, _check_edge_index, _device_arrays, _Model, _pointers
 from .graph import _need_cuda, _ws
@@ -169,6 +169,8 @@ class Trainer:
         self._h = _TrainerHandle(out, gm_model)
         self._ws = None
         self._rollout_ws, self._kept = None, None   # step_rollout's workspace and the shape of the windows at its head
+        # a rollout batch's losses, given no losses_out: one per graph up to the library's cap
+        self._batch_losses = torch.empty(RAGGED_MAX_GRAPHS, dtype=torch.float64, device=self.device)
         self._loss = torch.full((1,), float("nan"), dtype=torch.float64, device=self.device)
         self._loss_ws = _ws(L.gm_l1_loss_workspace_bytes(1, 1), self.device)
         self._pin_record = torch.zeros(4, dtype=torch.int64).pin_memory()
@@ -290,57 +292,27 @@ class Trainer:
         self._rollout_batch(engine, obs0, frames_list, steps, pos_scale, losses_out, state_material_col, 0)
 
     def _rollout_batch(self, engine, obs0, frames_list, steps, pos_scale, losses_out, state_material_col, update):
+        """gm_train_rollout_accumulate_ragged (update: accumulate, else evaluate) on checked arguments."""
         if not getattr(engine, "ragged", False):
             raise ValueError("a rollout batch needs a ragged engine: RolloutEngine(model, graph_attr, sizes=[...])")
-        if engine.rigid_rank is None:
-            raise ValueError("engine.set_scene(obs0) must be called before a rollout step")
-        engine._check_tensor(obs0, "obs0", (engine.k, engine.n, engine.data_dim))
+        self._check_rollout_scene(engine, obs0)
         frames_list = list(frames_list)
-        if len(frames_list) != len(engine.sizes):
-            raise ValueError(f"frames_list must hold one tensor per scene ({len(engine.sizes)}), got {len(frames_list)}")
+        G = len(engine.sizes)
+        if len(frames_list) != G:
+            raise ValueError(f"frames_list must hold one tensor per scene ({G}), got {len(frames_list)}")
         frame_dim = int(frames_list[0].shape[-1]) if isinstance(frames_list[0], torch.Tensor) and frames_list[0].dim() == 3 else -1
-        if frame_dim not in (engine.data_dim, engine.data_dim - 3):
-            raise ValueError(f"frames must have {engine.data_dim} or {engine.data_dim - 3} columns, got {frame_dim}")
+        self._check_frame_width(engine, frame_dim)
         for g, f in enumerate(frames_list):
             engine._check_tensor(f, f"frames_list[{g}]", ("steps", engine.sizes[g], frame_dim))
-        most = min(int(f.shape[0]) for f in frames_list)
-        steps = most if steps is None else int(steps)
-        if not 1 <= steps <= most:
-            raise ValueError(f"steps={steps} outside 1..{most}, the frames given")
-        if engine.device != self.device:
-            raise ValueError(f"the engine is on {engine.device}, the trainer on {self.device}")
-        scale = None
-        if pos_scale is not None:
-            scale = [float(v) for v in np.asarray(pos_scale, np.float64).reshape(-1)]
-            if len(scale) != 3 or not all(v == v and v != 0.0 for v in scale):
-                raise ValueError("pos_scale must be three non-zero numbers")
-            scale = (C.c_double * 3)(*scale)
-        col = -1
-        if self.sand_only:
-            col = engine.fdesc.material_col if state_material_col is None else int(state_material_col)
-            if col < 0:
-                col += engine.data_dim
-            if not 0 <= col < engine.data_dim:
-                raise ValueError(f"state_material_col={state_material_col} is outside the {engine.data_dim} state columns")
-        G = len(engine.sizes)
+        steps, col, scale = self._rollout_args(engine, min(int(f.shape[0]) for f in frames_list), steps, pos_scale, state_material_col, G)
         if losses_out is None:
-            if getattr(self, "_batch_losses", None) is None or self._batch_losses.numel() < G:
-                self._batch_losses = torch.empty(64, dtype=torch.float64, device=self.device)
             losses_out = self._batch_losses[:G]
         elif losses_out.dtype != torch.float64 or losses_out.numel() != G or losses_out.device != self.device or not losses_out.is_contiguous():
             raise ValueError(f"losses_out must be {G} contiguous float64 elements on the trainer's device")
-        L = lib()
-        need = L.gm_train_rollout_ragged_workspace_bytes(C.byref(self.desc), C.byref(engine.fdesc), engine.n, engine.n_rigid, G,
-                                                         engine.max_neighbours, steps)
-        if need == 0:
-            raise ValueError("Trainer: no rollout workspace for these sizes")
-        if self._rollout_ws is None or self._rollout_ws.numel() < need:
-            self._rollout_ws = _ws(need, self.device)
-        self._kept = (steps + 1, engine.k, engine.n, engine.data_dim)
         views = (C.c_void_p * G)(*[f.data_ptr() for f in frames_list])     # read during the call: the tensors outlive it in frames_list
-        check(L.gm_train_rollout_accumulate_ragged(self._h, ptr(obs0), engine._offsets_host, G, C.byref(engine.fdesc), engine.max_neighbours,
-                                                   ptr(engine.rigid_rank), engine.n_rigid, views, frame_dim, steps, col, scale, int(update),
-                                                   ptr(losses_out), ptr(self._rollout_ws), self._rollout_ws.numel(), current_stream(obs0)))
+        check(lib().gm_train_rollout_accumulate_ragged(self._h, ptr(obs0), engine._offsets_host, G, C.byref(engine.fdesc), engine.max_neighbours,
+                                                       ptr(engine.rigid_rank), engine.n_rigid, views, frame_dim, steps, col, scale, int(update),
+                                                       ptr(losses_out), ptr(self._rollout_ws), self._rollout_ws.numel(), current_stream(obs0)))
 
     def apply(self, loss_out=None, norm_out=None, want_norm=False, samples_total=None):
         """One Adam update from the MEAN of the accumulated gradients, clipped to ``max_grad_norm`` (None, <= 0 or inf: no clip)
@@ -590,17 +562,25 @@ class Trainer:
         return self._epoch(loader, self.evaluate)
 
     # ------------------------------------------------------------------------------------------ a rollout
-    def _rollout(self, engine, obs0, frames, steps, pos_scale, loss_out, state_material_col, mode):
-        """gm_train_rollout_step (mode "step" / "evaluate") or gm_train_rollout_accumulate ("accumulate") on checked arguments."""
+    # What a rollout call and a rollout batch share around their own check of the frames: the scene before it, the frames' width
+    # where each of them knows it, and everything from the step count to the workspace after it.
+    @staticmethod
+    def _check_rollout_scene(engine, obs0):
         if engine.rigid_rank is None:
             raise ValueError("engine.set_scene(obs0) must be called before a rollout step")
         engine._check_tensor(obs0, "obs0", (engine.k, engine.n, engine.data_dim))
-        engine._check_tensor(frames, "frames", ("steps", engine.n, "frame_dim"))
-        if frames.shape[2] not in (engine.data_dim, engine.data_dim - 3):
-            raise ValueError(f"frames must have {engine.data_dim} or {engine.data_dim - 3} columns, got {frames.shape[2]}")
-        steps = int(frames.shape[0]) if steps is None else int(steps)
-        if not 1 <= steps <= frames.shape[0]:
-            raise ValueError(f"steps={steps} outside 1..{frames.shape[0]}, the frames given")
+
+    @staticmethod
+    def _check_frame_width(engine, frame_dim):
+        if frame_dim not in (engine.data_dim, engine.data_dim - 3):
+            raise ValueError(f"frames must have {engine.data_dim} or {engine.data_dim - 3} columns, got {frame_dim}")
+
+    def _rollout_args(self, engine, most, steps, pos_scale, state_material_col, graphs=None):
+        """`most`: the frames given; `graphs`: the scenes of a ragged batch.  Grows the rollout workspace, notes the shape
+        ``kept_windows`` views, and returns (steps, the state's material column or -1, pos_scale as c_double[3] or None)."""
+        steps = most if steps is None else int(steps)
+        if not 1 <= steps <= most:
+            raise ValueError(f"steps={steps} outside 1..{most}, the frames given")
         if engine.device != self.device:
             raise ValueError(f"the engine is on {engine.device}, the trainer on {self.device}")
         scale = None
@@ -616,17 +596,30 @@ class Trainer:
                 col += engine.data_dim
             if not 0 <= col < engine.data_dim:
                 raise ValueError(f"state_material_col={state_material_col} is outside the {engine.data_dim} state columns")
-        slot = None if mode == "accumulate" and loss_out is None else self._slot(loss_out)
         L = lib()
-        need = L.gm_train_rollout_step_workspace_bytes(C.byref(self.desc), C.byref(engine.fdesc), engine.n, engine.n_rigid,
-                                                       engine.max_neighbours, steps)
+        sizes = (C.byref(self.desc), C.byref(engine.fdesc), engine.n, engine.n_rigid)
+        if graphs is None:
+            need = L.gm_train_rollout_step_workspace_bytes(*sizes, engine.max_neighbours, steps)
+        else:
+            need = L.gm_train_rollout_ragged_workspace_bytes(*sizes, graphs, engine.max_neighbours, steps)
         if need == 0:
             raise ValueError("Trainer: no rollout workspace for these sizes")
         if self._rollout_ws is None or self._rollout_ws.numel() < need:
             self._rollout_ws = _ws(need, self.device)
         self._kept = (steps + 1, engine.k, engine.n, engine.data_dim)
+        return steps, col, scale
+
+    def _rollout(self, engine, obs0, frames, steps, pos_scale, loss_out, state_material_col, mode):
+        """gm_train_rollout_step (mode "step" / "evaluate") or gm_train_rollout_accumulate ("accumulate") on checked arguments."""
+        self._check_rollout_scene(engine, obs0)
+        engine._check_tensor(frames, "frames", ("steps", engine.n, "frame_dim"))
+        frame_dim = int(frames.shape[2])
+        self._check_frame_width(engine, frame_dim)
+        steps, col, scale = self._rollout_args(engine, int(frames.shape[0]), steps, pos_scale, state_material_col)
+        slot = None if mode == "accumulate" and loss_out is None else self._slot(loss_out)
+        L = lib()
         head = (self._h, ptr(obs0), engine.n, C.byref(engine.fdesc), engine.max_neighbours, ptr(engine.rigid_rank), engine.n_rigid,
-                ptr(frames), int(frames.shape[2]), steps, col, scale)
+                ptr(frames), frame_dim, steps, col, scale)
         tail = (ptr(slot), ptr(self._rollout_ws), self._rollout_ws.numel(), current_stream(obs0))
         if mode == "accumulate":
             check(L.gm_train_rollout_accumulate(*head, *tail))

@@ -893,7 +893,8 @@ int gm_trainer_import(gm_trainer* t, int what, const float* const* tensors_in, i
  * (GM_ERR_INVALID_ARGUMENT, "gm_rollout_l1_loss: ..."): a null pointer, steps outside 1..32768, n_nodes below 1, a frame_dim that is
  * neither data_dim nor data_dim - 3 or does not hold the xyz columns, material_col >= data_dim, a zero or NaN pos_scale, one of
  * d_records / d_final without the other; a workspace below gm_rollout_l1_loss_workspace_bytes is GM_ERR_WORKSPACE.  The workspace is
- * written before it is read.
+ * written before it is read; its size is gm_rollout_l1_loss_ragged_workspace_bytes(1): the call runs gm_rollout_l1_loss_ragged's
+ * kernels on one segment [0, n_nodes), whatever fdesc->nodes_per_graph says (equal-sized graphs side by side are ONE sample).
  *
  * gm_train_rollout_step is one training step on a rollout of the trainer's model, on one stream; obs0 [k,N,D] is not written.
  *   1. one row kernel writes the scripted poses trajectory[t][rigid_rank[r]] = xyz(frames[t][r]) of the rigid rows (n_rigid of them;
@@ -990,8 +991,8 @@ int gm_train_rollout_accumulate(gm_trainer* t, const float* obs0 /*[k,N,D]*/, in
  * [steps, n_g, frame_dim] -- views into the graphs' recordings -- which travel by value in the kernel arguments.  losses_out
  * [n_graphs] (device doubles) and rows_counted_out [n_graphs] (device, may be NULL) are written in full:
  *     l_g = ((s0 / scale_0 + s1 / scale_1) + s2 / scale_2) / (steps * count_g)
- * with float64 sums over graph g's counted rows in the order of the single call on graph g alone (its workgroups, its stride): l_g
- * is that call's loss and does not depend on what shares the batch.  The transpose in d_records [steps,N,D] / d_final [k,N,D], both
+ * with float64 sums over graph g's counted rows in the order of the single call on graph g alone (its workgroups, its stride --
+ * the same kernels: the single call is the batch of one graph): l_g is that call's loss and does not depend on what shares the batch.  The transpose in d_records [steps,N,D] / d_final [k,N,D], both
  * written in full, has on graph g's counted rows gm_rollout_l1_loss's element values with count_g in place of count.  The state it
  * leaves for the launches behind it is the mini-batch's: the sum l_0 + l_1 + ... in graph order (float64) and the number of
  * non-finite l_g.  Workspace: gm_rollout_l1_loss_ragged_workspace_bytes(n_graphs).

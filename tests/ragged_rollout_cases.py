@@ -193,11 +193,38 @@ LOSS_STEPS = 2
 LOSS_RTOL = 1e-12                           # float64 sums of at most 1e3 float32 terms in another order: 1e3 x 2^-53 = 1.1e-13
 
 
-def loss_batch(k, frame_dim, mask, sizes=LOSS_SIZES, steps=LOSS_STEPS):
-    """train_rollout_cases.loss_case per graph (its own seed), and the batch assembled from them: dict(parts=[case per graph],
-    windows [steps,k,N,D], final [k,N,D], frames=[per graph], rank int32 [N] with GLOBAL ranks or None, material_col, pos_scale)."""
+# The shapes at which ONE set of loss kernels, shared by the single call and the batch, can go wrong.  "tail": graph 1 is past one
+# pass of the capped grid with a ragged tail (33025 = 128 * 256 + 257: the second pass has one full workgroup and one with a
+# single row) beside a one-row graph, whose other 127 workgroups of the launch row leave without writing, and a graph of exactly
+# one full workgroup.  "cap": GM_RAGGED_MAX_GRAPHS graphs -- the table and the frame pointers at their cap, the search for a row's
+# graph through all its depths; with a material column the graphs LOSS_CAP_EMPTY count no row.
+LOSS_SHAPES = {"tail": (1, 33025, 256), "cap": tuple((1, 2, 3, 5)[g % 4] for g in range(rgc.GM_RAGGED_MAX_GRAPHS))}
+LOSS_SHAPE_MASKS = ("none", "rigid_material")
+LOSS_CAP_EMPTY = (0, 17, 42, 63)            # one graph of every size, the first and the last graph among them
+
+
+def loss_shape(name, k, frame_dim, mask):
+    """loss_batch at LOSS_SHAPES[name]; "cap" under a mask with a material column: the graphs LOSS_CAP_EMPTY count no row."""
     import train_rollout_cases as trc
-    parts = [trc.loss_case(n, steps, k, frame_dim, mask, seed=40 + g) for g, n in enumerate(sizes)]
+    empty = LOSS_CAP_EMPTY if name == "cap" and trc.LOSS_MASKS[mask][1] else ()
+    return loss_batch(k, frame_dim, mask, sizes=LOSS_SHAPES[name], empty=empty)
+
+
+def loss_rtol(steps, counted):
+    """Every term |pred - frame| is non-negative, so a float64 sum of T = steps * rows counted terms in another order differs by
+    at most T * 2^-53 relative; the divisions behind the sums are the restatement's own."""
+    return float(steps) * np.asarray(counted, np.float64) * 2.0 ** -53
+
+
+def loss_batch(k, frame_dim, mask, sizes=LOSS_SIZES, steps=LOSS_STEPS, empty=()):
+    """train_rollout_cases.loss_case per graph (its own seed), and the batch assembled from them: dict(parts=[case per graph],
+    windows [steps,k,N,D], final [k,N,D], frames=[per graph], rank int32 [N] with GLOBAL ranks or None, material_col, pos_scale).
+    empty: graphs built under the "empty" mask instead (every material flag 1: nothing counts), for a mask with a material column."""
+    import train_rollout_cases as trc
+    parts = [trc.loss_case(n, steps, k, frame_dim, "empty" if g in empty else mask, seed=40 + g) for g, n in enumerate(sizes)]
+    for g in empty:
+        assert trc.LOSS_MASKS[mask][:2] == (True, True), mask
+        parts[g]["pos_scale"] = trc.LOSS_MASKS[mask][2]                  # the single call on the graph alone takes the batch's scale
     rank = None
     if parts[0]["rank"] is not None:
         ranks, base = [], 0

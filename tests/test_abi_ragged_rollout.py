@@ -164,7 +164,8 @@ def test_training_entry_points_refuse_before_any_device_call_and_size_their_work
     q = lambda n, nr, g, steps=2: L.gm_train_rollout_ragged_workspace_bytes(C.byref(md), d, n, nr, g, 20, steps)
     assert [q(10, 1, 0), q(10, 1, 65), q(1, 0, 2), q(10, 11, 2), q(10, 1, 2, 0)] == [0] * 5
     one = L.gm_train_rollout_step_workspace_bytes(C.byref(md), d, 353, 30, 20, 2)
-    assert 0 < one < q(353, 30, 1) <= q(353, 30, 3) and q(353, 30, 3) - one < 1 << 20          # the table adds the per-graph partials only
+    # the plain step is the batch of one graph (one set of loss kernels); the table adds the per-graph partials only
+    assert 0 < one == q(353, 30, 1) < q(353, 30, 3) and q(353, 30, 3) - one < 1 << 20
 
 
 def test_python_surface():

@@ -359,6 +359,69 @@ def test_ragged_loss_per_graph(dev, mask, frame_dim):
     assert rc2 == 0 and none_r is None and np.array_equal(_bits64(only), _bits64(losses))
 
 
+@pytest.mark.parametrize("mask", rrc.LOSS_SHAPE_MASKS)
+@pytest.mark.parametrize("frame_dim", [L.D, L.D - 3])
+@pytest.mark.parametrize("shape", list(rrc.LOSS_SHAPES))
+def test_ragged_loss_at_the_shapes_one_kernel_set_can_miss(dev, shape, frame_dim, mask):
+    """test_ragged_loss_per_graph's assertions at ragged_rollout_cases.LOSS_SHAPES: a graph past one pass of the grid beside a
+    one-row graph, and the table at its cap with graphs that count no row."""
+    import train_rollout_cases as trc
+    b = rrc.loss_shape(shape, L.k, frame_dim, mask)
+    fd = feature_desc(rrc.R, L)
+    rc, losses, counted, d_rec, d_fin = _loss_ragged(b, fd, dev)
+    assert rc == 0, _lib().lib().gm_last_error()
+    want = rrc.rollout_l1_restated_ragged(b["windows"], b["final"], b["frames"], b["sizes"], trc.LOSS_CART, b["rank"], b["material_col"],
+                                          b["pos_scale"])
+    got = losses.cpu().numpy()
+    assert np.array_equal(counted.cpu().numpy(), want[1])
+    some = want[1] > 0
+    empty = tuple(int(g) for g in np.nonzero(~some)[0])
+    assert empty == (rrc.LOSS_CAP_EMPTY if (shape, mask) == ("cap", "rigid_material") else ())
+    err = np.abs(got[some] - want[0][some]) / np.abs(want[0][some])
+    print(f"\n[ragged loss] {shape} {mask} frame_dim {frame_dim}: worst loss error / bound {(err / rrc.loss_rtol(rrc.LOSS_STEPS, want[1][some])).max():.3g}")
+    assert np.isnan(got[~some]).all() and (err <= rrc.loss_rtol(rrc.LOSS_STEPS, want[1][some])).all(), (got, want[0])
+    assert same_bits(d_rec, want[2]) and same_bits(d_fin, want[3])
+    off = np.r_[0, np.cumsum(b["sizes"])]
+    for g, p in enumerate(b["parts"]):                                   # the single call on graph g alone: the same bits, a NaN loss included
+        loss, dr, df = _loss_single(p, fd, dev)
+        rows = slice(int(off[g]), int(off[g + 1]))
+        assert same_bits(d_rec[:, rows], dr) and same_bits(d_fin[:, rows], df), (shape, mask, g)
+        assert np.array_equal(_bits64(losses[g:g + 1]), _bits64(loss)), (shape, mask, g, float(losses[g]), float(loss))
+        if g in empty:
+            assert not d_rec[:, rows].any() and not d_fin[:, rows].any(), g
+    rc2, only, _, none_r, none_f = _loss_ragged(b, fd, dev, with_grads=False)           # the loss alone
+    assert rc2 == 0 and none_r is None and np.array_equal(_bits64(only), _bits64(losses))
+
+
+def test_a_scale_that_underflows_on_one_axis_leaves_the_other_axes(dev):
+    """pos_scale[0] = 1e300: (float)(1 / ((scale_0 * steps) * count)) is zero, so axis 0's gradient elements are signed zeros while
+    axes 1 and 2 keep theirs -- whether a graph counts any row is decided by its count, not by a scale.  The restatement, the
+    single call and the batch agree bit for bit."""
+    import train_rollout_cases as trc
+    b = rrc.loss_batch(L.k, L.D, "rigid")
+    b["pos_scale"] = (1e300, 2.0, 3.0)
+    for p in b["parts"]:
+        p["pos_scale"] = b["pos_scale"]
+    fd = feature_desc(rrc.R, L)
+    rc, losses, counted, d_rec, d_fin = _loss_ragged(b, fd, dev)
+    assert rc == 0, _lib().lib().gm_last_error()
+    want = rrc.rollout_l1_restated_ragged(b["windows"], b["final"], b["frames"], b["sizes"], trc.LOSS_CART, b["rank"], b["material_col"],
+                                          b["pos_scale"])
+    c0 = trc.LOSS_CART
+    assert np.float32(1.0 / ((1e300 * rrc.LOSS_STEPS) * 1)) == 0 and (want[1] > 0).all()
+    assert not want[3][-1][:, c0].any() and np.signbit(want[3][-1][:, c0]).any()               # axis 0: zeros of both signs
+    assert all(np.count_nonzero(want[3][-1][:, c0 + ax]) >= int(want[1].sum()) - len(b["sizes"]) for ax in (1, 2))   # (one sign 0 per graph)
+    assert same_bits(d_rec, want[2]) and same_bits(d_fin, want[3])
+    got = losses.cpu().numpy()
+    assert (np.abs(got - want[0]) <= rrc.LOSS_RTOL * np.abs(want[0])).all(), (got, want[0])
+    off = np.r_[0, np.cumsum(b["sizes"])]
+    for g, p in enumerate(b["parts"]):
+        loss, dr, df = _loss_single(p, fd, dev)
+        rows = slice(int(off[g]), int(off[g + 1]))
+        assert same_bits(d_rec[:, rows], dr) and same_bits(d_fin[:, rows], df), g
+        assert np.array_equal(_bits64(losses[g:g + 1]), _bits64(loss)), g
+
+
 def test_a_nan_frame_stays_in_its_graph(dev):
     import train_rollout_cases as trc
     b = rrc.loss_batch(L.k, L.D, "rigid")
@@ -598,6 +661,52 @@ def test_one_bad_graph_skips_the_whole_update(dev):
     assert np.isnan(float(slot))
     _same_state(_state(t), before, "a skipped update")
     assert t.record()["steps_applied"] == 0 and t.record()["steps_skipped"] == 1
+
+
+@pytest.mark.parametrize("max_grad_norm", [None, 1e-3])
+def test_a_batch_of_one_scene_is_accumulate_rollout(dev, max_grad_norm):
+    """A ragged batch of ONE scene through accumulate_rollout_batch + apply against accumulate_rollout + apply on a plain engine:
+    the loss, the mini-batch's record, the gradients before apply and the state after it, bit for bit."""
+    from conftest import STATS
+    from gnn_manip_amd import Trainer, train
+    import train_step_cases as tsc
+    scale = [float(v) for v in STATS["acceleration_std"]]
+    c = rrc.case(rrc.SWEEP_CASE)
+    s = c.scenes[0]
+    dims, params, _, _ = rrc.model("h64")
+
+    def run(batched):
+        m = load_model(params, dims, dev)
+        t = Trainer(m, lr=LR, sand_only=True, material_col=tsc.MATERIAL_COL)
+        t.max_grad_norm = max_grad_norm
+        eng = _ragged_engine(m, (s.n,), dev, c.max_nb) if batched else _single_engine(m, s.n, dev, c.max_nb)
+        obs0 = to_dev(s.window(), dev)
+        assert eng.set_scene(obs0) > 0
+        frames = to_dev(np.ascontiguousarray(s.sim[L.k:L.k + rrc.SWEEP_STEPS]), dev)
+        loss, slot, norm = (torch.full((1,), -7.0, dtype=torch.float64, device=dev) for _ in range(3))
+        t.zero_grad()
+        if batched:
+            t.accumulate_rollout_batch(eng, obs0, [frames], rrc.SWEEP_STEPS, pos_scale=scale, losses_out=loss)
+        else:
+            t.accumulate_rollout(eng, obs0, frames, rrc.SWEEP_STEPS, pos_scale=scale, loss_out=loss)
+        t.accum_record()
+        accumulated = t._pin_accum.numpy().copy()                          # the 48 bytes of the record
+        grads = t.export(train.GRADS)
+        t.apply(loss_out=slot, norm_out=norm if max_grad_norm else None)
+        t.accum_record()
+        return dict(loss=loss, accumulated=accumulated, grads=grads, slot=slot, norm=norm, applied=t._pin_accum.numpy().copy(),
+                    state=_state(t), record=t.record())
+
+    a, b = run(True), run(False)
+    assert np.isfinite(float(a["loss"])) and any(bool(g.any()) for g in a["grads"])
+    for key in ("loss", "slot", "norm"):
+        assert np.array_equal(_bits64(a[key]), _bits64(b[key])), (key, float(a[key]), float(b[key]))
+    assert np.array_equal(a["accumulated"], b["accumulated"]) and np.array_equal(a["applied"], b["applied"])
+    assert int(a["accumulated"][0]) == 1 and int(a["accumulated"][1]) == 0                  # one sample, none of them bad
+    for i, (u, v) in enumerate(zip(a["grads"], b["grads"])):
+        assert same_bits(u, v), ("gradients", i)
+    _same_state(a["state"], b["state"], ("apply", max_grad_norm))
+    assert a["record"] == b["record"] and a["record"]["steps_applied"] == 1
 
 
 def test_batch_methods_check_their_arguments(dev):

@@ -129,3 +129,30 @@ def test_ragged_loss_batch_has_global_ranks_and_its_own_regime():
     assert np.array_equal(rigid, np.arange(len(rigid))) and len(rigid) > 3
     assert [tsc.loss_regime(n)[0] for n in b["sizes"]] == [2, 1, 1] and all(n % tsc.LOSS_WG for n in b["sizes"])
     assert rrc.case(rrc.SWEEP_CASE).sizes == (130, 1, 77)
+
+
+def test_loss_shapes_are_in_the_regimes_they_were_built_for():
+    import train_rollout_cases as trc
+    import train_step_cases as tsc
+    tail, cap = rrc.LOSS_SHAPES["tail"], rrc.LOSS_SHAPES["cap"]
+    # tail: one row; past one pass of the capped grid, the second pass one full workgroup and one with a single row; one full workgroup
+    assert [tsc.loss_regime(n) for n in tail] == [(1, 1), (tsc.LOSS_GRID_MAX, 2), (1, 1)] and tail[0] == 1 and tail[2] == tsc.LOSS_WG
+    assert tail[1] - tsc.LOSS_GRID_MAX * tsc.LOSS_WG == tsc.LOSS_WG + 1
+    # cap: the table is full, and a binary search over it reaches every depth up to log2 of the cap
+    from gnn_manip_amd import _lib
+    assert len(cap) == rgc.GM_RAGGED_MAX_GRAPHS == _lib.RAGGED_MAX_GRAPHS == 64 and set(cap) == {1, 2, 3, 5} and sum(cap) < tsc.LOSS_WG
+    for name in rrc.LOSS_SHAPES:
+        for mask in rrc.LOSS_SHAPE_MASKS:
+            b = rrc.loss_shape(name, 6, 8, mask)
+            assert b["sizes"] == rrc.LOSS_SHAPES[name] and b["windows"].shape[:2] == (rrc.LOSS_STEPS, 6)
+            counts = [int(trc.counted_rows(p["windows"], p["rank"], p["material_col"]).sum()) for p in b["parts"]]
+            empty = rrc.LOSS_CAP_EMPTY if (name, mask) == ("cap", "rigid_material") else ()
+            assert all((c == 0) == (g in empty) for g, c in enumerate(counts)), (name, mask, counts)
+            if mask == "none":
+                assert counts == list(b["sizes"]) and b["rank"] is None
+            else:
+                rigid = b["rank"][b["rank"] >= 0]
+                assert np.array_equal(rigid, np.arange(len(rigid))) and len(rigid) > 3          # ranks are global
+                assert all(p["pos_scale"] == b["pos_scale"] for p in b["parts"])
+    assert {cap[g] for g in rrc.LOSS_CAP_EMPTY} == set(cap) and {0, len(cap) - 1} <= set(rrc.LOSS_CAP_EMPTY)
+    assert np.allclose(rrc.loss_rtol(2, [1, 33025]), [2.0 ** -52, 66050 * 2.0 ** -53], rtol=0, atol=0)
