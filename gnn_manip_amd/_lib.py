@@ -51,6 +51,10 @@ PROTOTYPES = {
     "gm_radius_graph_build_batched": (_i32, [_vp, _i64, _i64, _i64, _f64, _i32, _vp, _sz, _vp]),
     "gm_graph_ragged_workspace_bytes": (_sz, [_i64, _i64, _i32]),
     "gm_radius_graph_build_ragged": (_i32, [_vp, _i64, _vp, _i64, _f64, _i32, _vp, _sz, _vp]),
+    "gm_neighbour_census_workspace_bytes": (_sz, [_i64]),
+    "gm_neighbour_census": (_i32, [_vp, _i64, _i64, _f64, _vp, _vp, _sz, _vp]),
+    "gm_recording_stats_workspace_bytes": (_sz, [_i64, _i64]),
+    "gm_recording_stats": (_i32, [_vp, _i64, _i64, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _sz, _vp]),
     "gm_radius_graph_num_edges": (_i32, [_vp, C.POINTER(_i64), _vp]),
     "gm_radius_graph_edges": (_i32, [_vp, _i64, _i32, _vp, _vp, _i64, _vp]),
     "gm_csr_workspace_bytes": (_sz, [_i64, _i64]),

@@ -8,7 +8,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libgnnmanip_hip.so")
-SOURCES = ["graph.hip", "features.hip", "mlp.hip", "hedge.hip", "hmlp.hip", "model.hip", "train.hip", "train_model.hip", "train_step.hip", "sinkhorn.hip", "rollout_grad.hip", "train_batch.hip"]
+SOURCES = ["graph.hip", "features.hip", "mlp.hip", "hedge.hip", "hmlp.hip", "model.hip", "train.hip", "train_model.hip", "train_step.hip", "sinkhorn.hip", "rollout_grad.hip", "train_batch.hip", "dataset_stats.hip"]
 # hedge.hip: packed fp32 VALU (SLP-vectorised v_pk_fma_f32) returned wrong low lanes next to its LDS / MFMA traffic on gfx950
 EXTRA_FLAGS = {"hedge.hip": ["-fno-slp-vectorize"] + os.environ.get("GM_HEDGE_FLAGS", "").split(), "hmlp.hip": ["-fno-slp-vectorize"] + os.environ.get("GM_HM_FLAGS", "").split(),
                "train.hip": os.environ.get("GM_TRAIN_FLAGS", "").split(), "graph.hip": os.environ.get("GM_GRAPH_FLAGS", "").split()}

@@ -650,6 +650,31 @@ __global__ void __launch_bounds__(BS) neighbor_kernel(const float4* __restrict__
     }
 }
 
+// Neighbour census (gm_neighbour_census): the in-radius candidates of every query, counted and not kept -- the scan of
+// neighbor_fast_kernel (NB_LPQ lanes per query over the same cells, the same query_dist2, the same d2 <= r2) without the lists, so
+// without their cap.  counts[qi] = what either neighbour kernel would keep at an unbounded K.
+__global__ void __launch_bounds__(256) neighbor_count_kernel(const float4* __restrict__ sorted, const int* __restrict__ cell_start,
+                                                              const GraphHeader* __restrict__ hdr, int64_t n, double r2,
+                                                              int* __restrict__ counts) {
+    const int tid = threadIdx.x, sub = tid & (NB_LPQ - 1);
+    const int64_t slot = (int64_t)blockIdx.x * NB_QPB + tid / NB_LPQ;
+    const bool active = slot < n;
+    const Query Q = decode_query(sorted[active ? slot : 0], hdr);
+    int count = 0;
+    if (active) {
+        for (int z = Q.z0; z <= Q.z1; ++z) {
+            for (int y = Q.y0; y <= Q.y1; ++y) {
+                int b, e;
+                Q.row_range(cell_start, z, y, b, e);
+                for (int c = b + sub; c < e; c += NB_LPQ) count += query_dist2(Q, sorted[c]) <= r2 ? 1 : 0;
+            }
+        }
+    }
+#pragma unroll
+    for (int d = NB_LPQ / 2; d >= 1; d >>= 1) count += __shfl_xor(count, d, 64);   // the group's lanes are neighbours in the wave
+    if (active && sub == 0) counts[Q.qi] = count;
+}
+
 // Slot `id` of the [n][K] neighbour table: its query i and its place s in the query's list; false past the table or past the list
 __device__ __forceinline__ bool decode_slot(int64_t id, int64_t n, int K, const int* __restrict__ cnt, int64_t& i, int& s) {
     if (id >= n * K) return false;
@@ -1049,6 +1074,34 @@ int gm_radius_graph_build_ragged(const float* pos, int64_t pos_stride, const int
     if (rc != GM_OK) return rc;
     const ScanJob sj{g.cnt, g.out_ptr, (long long)n + 1, &g.hdr->n_edges, g.scan_cnt};
     return scan_lookback(&sj, 1, s);
+}
+
+size_t gm_neighbour_census_workspace_bytes(int64_t n_nodes) {
+    if (n_nodes < 1 || n_nodes >= (int64_t)1 << 30) return 0;
+    return carve_graph(nullptr, n_nodes, 1).bytes;   // the build's workspace at the smallest cap: the census keeps no lists
+}
+
+int gm_neighbour_census(const float* pos, int64_t pos_stride, int64_t n, double conn_r, int32_t* counts, void* ws, size_t ws_bytes,
+                        void* stream) {
+    const char* who = "gm_neighbour_census";
+    GM_REQUIRE(pos && counts && ws, GM_ERR_INVALID_ARGUMENT, "%s: null pointer", who);
+    GM_REQUIRE(n >= 1 && n < (int64_t)1 << 30, GM_ERR_INVALID_ARGUMENT, "%s: n_nodes=%lld out of range (1 .. 2^30 - 1)", who, (long long)n);
+    GM_REQUIRE(conn_r > 0.0 && conn_r == conn_r, GM_ERR_INVALID_ARGUMENT, "%s: conn_r must be > 0", who);
+    GM_REQUIRE(pos_stride >= 3, GM_ERR_INVALID_ARGUMENT, "%s: pos_stride < 3", who);
+    GraphWs g = carve_graph(ws, n, 1);
+    GM_REQUIRE(ws_bytes >= g.bytes, GM_ERR_INVALID_ARGUMENT, "%s: workspace %zu < %zu", who, ws_bytes, g.bytes);
+    gm::DevGuard dev_guard(pos);
+    hipStream_t s = (hipStream_t)stream;
+    // the build's resets and grid phase (one graph), then the count in place of the two neighbour kernels
+    StepClear clr;
+    int rc = graph_clear_jobs(clr, g, n);
+    if (rc == GM_OK) rc = launch_step_clear(clr, s);
+    if (rc == GM_OK) rc = grid_phase(pos, pos_stride, n, n, conn_r, g, s);
+    if (rc != GM_OK) return rc;
+    hipLaunchKernelGGL(neighbor_count_kernel, dim3((unsigned)cdiv(n, NB_QPB)), dim3(256), 0, s, g.sorted, g.cell_start, g.hdr, n,
+                       conn_r * conn_r, counts);
+    GM_LAUNCH_CHECK();
+    return GM_OK;
 }
 
 int gm_radius_graph_num_edges(const void* ws, int64_t* n_edges_host, void* stream) {

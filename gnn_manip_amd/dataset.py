@@ -35,6 +35,157 @@ def read_simulation(file, time_steps, data_dim):
     return np.array(pd.read_csv(file, header=None)).reshape(time_steps, -1, data_dim)
 
 
+STATS_DOUBLES = 24   # GM_RECORDING_STATS_DOUBLES (include/gnn_manip_hip.h): 8 per axis
+
+
+def _recordings(sims, who):
+    """``sims`` (one tensor or a list) as a list of resident float32 [T, N, D] tensors on one HIP device."""
+    sims = [sims] if torch.is_tensor(sims) else list(sims)
+    if not sims or any((not torch.is_tensor(s)) or s.dtype != torch.float32 or s.dim() != 3 or not s.is_cuda for s in sims):
+        raise RuntimeError(f"{who}: float32 [T, N, data_dim] tensors on the HIP device")
+    if len({s.device for s in sims}) != 1 or len({int(s.shape[2]) for s in sims}) != 1:
+        raise RuntimeError(f"{who}: the recordings share one device and one data_dim")
+    return [s.contiguous() for s in sims]
+
+
+def _contiguous_columns(cartesian_idx, who, want=None):
+    idx = [int(c) for c in cartesian_idx]
+    if not 1 <= len(idx) <= 3 or idx != list(range(idx[0], idx[0] + len(idx))) or (want is not None and len(idx) != want):
+        raise ValueError(f"{who}: cartesian_idx={idx}: {'1 to 3' if want is None else want} consecutive columns")
+    return idx
+
+
+def chan_merge(a, b):
+    """(count, mean, M2) of the union of two samples from theirs (Chan, Golub, LeVeque), in float64; means and M2 may be arrays."""
+    (na, ma, Ma), (nb, mb, Mb) = a, b
+    n = na + nb
+    if n == 0:
+        return a
+    d = mb - ma
+    return n, ma + d * (nb / n), Ma + Mb + d * d * (na * nb / n)
+
+
+def recording_statistics(sims, cartesian_idx=(2, 3, 4), material_id=None, material=None):
+    """The normalisation statistics of recordings that are resident already -- what simulation/generate_metadata.py:24-45 computes
+    with numpy on the host: mean and population standard deviation (``np.std``, ddof = 0) of the velocities ``np.diff(p, axis=0)``
+    and of the accelerations (``np.diff`` again) over all rows of all recordings.  One gm_recording_stats call per recording, ONE
+    transfer at the end; the per-recording (count, mean, M2) records are merged on the host in float64 (``chan_merge``).
+
+    ``material_id`` (a column) and ``material`` (a value), given together, count only the rows that carry that value in frame 0 --
+    the sand-only statistics that go with ``Trainer(sand_only=True)``; left None, every row counts, as in the reference.
+
+    Returns ``(stats, info)``: ``stats`` has the keys and dtypes of ``read_metadata``'s; ``info`` the float64 values
+    (``velocity_mean``, ``velocity_std``, ``velocity_m2``, ``acceleration_*`` alike), ``velocity_count``, ``acceleration_count``,
+    ``position_range`` [dim, 2] and the raw ``records`` [recordings, 3, 8].  ValueError names the recording whose result is not
+    finite, and is raised when no row is counted at all."""
+    who = "recording_statistics"
+    sims = _recordings(sims, who)
+    idx = _contiguous_columns(cartesian_idx, who)
+    if (material_id is None) != (material is None):
+        raise ValueError(f"{who}: material_id (the column) and material (the value) go together")
+    mcol, mval = (-1, 0.0) if material_id is None else (int(material_id), float(material))
+    L, dev, dim = lib(), sims[0].device, len(idx)
+    with torch.cuda.device(dev):
+        out = torch.empty((len(sims), STATS_DOUBLES), dtype=torch.float64, device=dev)
+        need = max(L.gm_recording_stats_workspace_bytes(int(s.shape[0]), int(s.shape[1])) for s in sims)
+        ws = _ws(max(need, 256), dev)
+        for r, s in enumerate(sims):
+            check(L.gm_recording_stats(ptr(s), int(s.shape[0]), int(s.shape[1]), int(s.shape[2]), idx[0], dim, mcol, mval,
+                                       C.c_void_p(out.data_ptr() + r * STATS_DOUBLES * 8), ptr(ws), ws.numel(), current_stream(dev)))
+        records = out.cpu().numpy().reshape(len(sims), 3, 8)[:, :dim]
+    vel = acc = (0.0, np.zeros(dim), np.zeros(dim))
+    lo, hi = np.full(dim, np.inf), np.full(dim, -np.inf)
+    for r, rec in enumerate(records):
+        if rec[0, 0] == 0:
+            continue    # no row of this recording carries the material
+        if not np.isfinite(rec).all():
+            bad = [a for a in range(dim) if not np.isfinite(rec[a]).all()]
+            raise ValueError(f"{who}: recording {r}: non-finite statistics on axis {bad} (a non-finite position in columns "
+                             f"{[idx[a] for a in bad]})")
+        vel = chan_merge(vel, (float(rec[0, 0]), rec[:, 1], rec[:, 2]))
+        acc = chan_merge(acc, (float(rec[0, 3]), rec[:, 4], rec[:, 5]))
+        lo, hi = np.minimum(lo, rec[:, 6]), np.maximum(hi, rec[:, 7])
+    if vel[0] == 0:
+        raise ValueError(f"{who}: no row counted: no row of any recording has column {mcol} == {mval} in frame 0")
+    info = {"velocity_count": int(vel[0]), "velocity_mean": vel[1], "velocity_m2": vel[2], "velocity_std": np.sqrt(vel[2] / vel[0]),
+            "acceleration_count": int(acc[0]), "acceleration_mean": acc[1], "acceleration_m2": acc[2],
+            "acceleration_std": np.sqrt(acc[2] / acc[0]), "position_range": np.stack((lo, hi), axis=1), "records": records}
+    stats = {k: torch.tensor([float(v) for v in info[k]]) for k in ("velocity_mean", "velocity_std", "acceleration_mean", "acceleration_std")}
+    return stats, info
+
+
+def write_metadata(path, sims, bounds, cartesian_idx=(2, 3, 4), control_idx=(5, 6, 7), material_id=1):
+    """metadata.json of the reference (simulation/generate_metadata.py:33-49) from resident recordings: the statistics are
+    ``recording_statistics(sims, cartesian_idx)`` -- every row, as the reference counts them.  ``bounds``: what ``read_metadata``
+    returns (``lower_bounds`` / ``upper_bounds``) or [[lower, upper], ...] per axis.  ``read_metadata(path)`` reads it back.
+    Returns the dictionary written."""
+    sims = _recordings(sims, "write_metadata")
+    _, info = recording_statistics(sims, cartesian_idx)
+    if isinstance(bounds, dict):
+        pairs = [[float(lo), float(hi)] for lo, hi in zip(bounds["lower_bounds"], bounds["upper_bounds"])]
+    else:
+        pairs = [[float(lo), float(hi)] for lo, hi in bounds]
+    metadata = {"cartesian_idx": [int(c) for c in cartesian_idx], "control_idx": [int(c) for c in control_idx],
+                "material_id": int(material_id), "bounds": pairs, "sequence_length": int(sims[0].shape[0]),
+                "dim": len(list(cartesian_idx)), "data_dim": int(sims[0].shape[2]),
+                "vel_mean": [float(v) for v in info["velocity_mean"]], "vel_std": [float(v) for v in info["velocity_std"]],
+                "acc_mean": [float(v) for v in info["acceleration_mean"]], "acc_std": [float(v) for v in info["acceleration_std"]]}
+    with open(path, "w") as fp:
+        json.dump(metadata, fp)
+    return metadata
+
+
+def neighbour_census(sims, conn_r, max_neighbours=20, cartesian_idx=(2, 3, 4), frames=None):
+    """How many rows of the recordings the radius graph truncates at ``conn_r`` / ``max_neighbours``.  For every chosen frame,
+    gm_neighbour_census counts per node the nodes ``gm_radius_graph_build`` would list without a cap (the node itself included,
+    as the build includes it); ``min(count, max_neighbours)`` is the out-degree the build gives the node.  ``frames``: None for
+    every frame, or a ``range`` / list of frame numbers applied to each recording.  The summary is formed on the device and comes
+    over in one transfer:
+
+    ``max_count``, ``mean_count``, ``rows_over_cap`` (node-frames with count > max_neighbours), ``frames_over_cap`` (frames that
+    hold one), ``fraction_over_cap`` (of the node-frames), ``rows``, ``frames`` and ``histogram`` -- ``np.bincount`` of the counts:
+    its length minus one is the smallest cap that truncates nothing."""
+    who = "neighbour_census"
+    sims = _recordings(sims, who)
+    idx = _contiguous_columns(cartesian_idx, who, want=3)
+    cap = int(max_neighbours)
+    if cap < 1:
+        raise ValueError(f"{who}: max_neighbours={cap} < 1")
+    L, dev = lib(), sims[0].device
+    with torch.cuda.device(dev):
+        n_max = max(int(s.shape[1]) for s in sims)
+        ws = _ws(L.gm_neighbour_census_workspace_bytes(n_max), dev)
+        hist = torch.zeros(n_max + 1, dtype=torch.int64, device=dev)      # a node sees at most the n nodes of its frame
+        scalars = torch.zeros(3, dtype=torch.int64, device=dev)           # rows over the cap, frames over the cap, the largest count
+        rows = n_frames = 0
+        for r, s in enumerate(sims):
+            t_all, n, d = (int(v) for v in s.shape)
+            chosen = list(range(t_all)) if frames is None else [int(t) for t in frames]
+            if any(not 0 <= t < t_all for t in chosen):
+                raise IndexError(f"{who}: frames outside the {t_all} frames of recording {r}")
+            if not chosen:
+                continue
+            counts = torch.empty((len(chosen), n), dtype=torch.int32, device=dev)
+            for j, t in enumerate(chosen):
+                check(L.gm_neighbour_census(C.c_void_p(s.data_ptr() + (t * n * d + idx[0]) * 4), d, n, float(conn_r),
+                                            C.c_void_p(counts.data_ptr() + j * n * 4), ptr(ws), ws.numel(), current_stream(dev)))
+            flat = counts.view(-1).long()
+            hist.scatter_add_(0, flat, torch.ones_like(flat))
+            over = counts > cap
+            scalars += torch.stack((over.sum(), over.any(dim=1).sum(), torch.zeros((), dtype=torch.int64, device=dev)))
+            scalars[2] = torch.maximum(scalars[2], flat.max())
+            rows += len(chosen) * n
+            n_frames += len(chosen)
+        if rows == 0:
+            raise ValueError(f"{who}: no frame chosen")
+        host = torch.cat((scalars, hist)).cpu().numpy()
+    over_rows, over_frames, max_count = (int(v) for v in host[:3])
+    histogram = host[3:3 + max_count + 1].copy()
+    return {"max_count": max_count, "mean_count": float((histogram * np.arange(max_count + 1)).sum()) / rows,
+            "rows_over_cap": over_rows, "frames_over_cap": over_frames, "fraction_over_cap": over_rows / rows, "rows": rows,
+            "frames": n_frames, "histogram": histogram}
+
+
 class GraphData:
     """The fields of ``torch_geometric.data.Data`` that train_dyn.py:49-53 reads (x, edge_attr, edge_index, y)."""
 
@@ -163,7 +314,9 @@ class CoffeeDataset(torch.utils.data.Dataset):
     def from_recordings(cls, sims, k, conn_r, stats, bounds, cartesian_idx=(2, 3, 4), material_id=1, control_idx=(5, 6, 7), noise=None,
                         use_control=False, max_neighbours=20):
         """The dataset over recordings that are resident already: ``sims`` a list of float32 [T, N, data_dim] tensors on one HIP
-        device (N may differ between them), the other arguments what metadata.json and the constructor give."""
+        device (N may differ between them), the other arguments what metadata.json and the constructor give.  ``stats=None``
+        computes the statistics from ``sims`` (``recording_statistics(sims, cartesian_idx)``: every row, as the reference's
+        metadata script counts them)."""
         self = cls.__new__(cls)
         self.sims = [s.contiguous() for s in sims]
         if not self.sims or any(s.dtype != torch.float32 or s.dim() != 3 or not s.is_cuda for s in self.sims):
@@ -174,7 +327,7 @@ class CoffeeDataset(torch.utils.data.Dataset):
         self.noise, self.use_control = noise, use_control
         self.data_dim, self.time_steps = int(self.sims[0].shape[2]), int(self.sims[0].shape[0])
         self.cartesian_idx, self.control_idx, self.material_id = list(cartesian_idx), list(control_idx), int(material_id)
-        self.bounds, self.stats = bounds, stats
+        self.bounds, self.stats = bounds, (recording_statistics(self.sims, self.cartesian_idx)[0] if stats is None else stats)
         self.index = [(s, t) for s, data in enumerate(self.sims) for t in range(data.shape[0] - k)]
         self.graph_attr = self._get_graph_attr()
         return self

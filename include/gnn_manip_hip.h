@@ -94,6 +94,21 @@ int gm_radius_graph_num_edges(const void* graph_ws, int64_t* n_edges_host, void*
 int gm_radius_graph_edges(const void* graph_ws, int64_t n_nodes, int max_neighbours,
                           int64_t* senders, int64_t* receivers, int64_t capacity, void* stream);
 
+/* Neighbour census (an addition to ABI 7; the reference has no counterpart: get_connectivity, utils.py:64-93, keeps the nearest
+ * max_neighbours of a query and drops the rest without a word).  counts_device[i] = the number of nodes gm_radius_graph_build
+ * would list for query i if it had no cap: the nodes j (i itself among them) with float64 d2 <= conn_r * conn_r, d2 accumulated
+ * x -> y -> z with separately rounded products and sums -- the build's own predicate, evaluated by the build's own code over the
+ * build's own cell list.  Hence min(counts[i], max_neighbours) is the out-degree the build gives node i, and counts[i] >
+ * max_neighbours says that row i is truncated at that cap.  Counts only: no candidate lists, so no 160 limit.  A row with a
+ * non-finite coordinate counts 0 and is counted by nobody.  One graph; pos / pos_stride as in gm_radius_graph_build.  The
+ * workspace has the layout of gm_graph_workspace_bytes(n_nodes, 1), and gm_neighbour_census_workspace_bytes returns its size (0
+ * for n_nodes outside 1 .. 2^30 - 1); it is written before it is read.  No host synchronisation.  Refused with
+ * GM_ERR_INVALID_ARGUMENT and a "gm_neighbour_census: ..." message, before any device call: a null pointer, n_nodes outside
+ * 1 .. 2^30 - 1, conn_r <= 0, pos_stride < 3, a workspace below the query. */
+size_t gm_neighbour_census_workspace_bytes(int64_t n_nodes);
+int gm_neighbour_census(const float* pos, int64_t pos_stride, int64_t n_nodes, double conn_r, int32_t* counts_device /*[N]*/,
+                        void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Destination-sorted edge structure (the engine's internal edge order).
  * Aggregation index i = edge_index[1], source j = edge_index[0] (PyG source_to_target, see
@@ -1072,6 +1087,45 @@ size_t gm_trainer_contribution_bytes(const gm_trainer* t);
 int gm_trainer_contribution(gm_trainer* t, void* out_dev, size_t out_bytes, int poisoned, void* stream);
 int gm_trainer_reduce(gm_trainer* t, const void* contributions_dev, int world, size_t stride_bytes, int64_t samples_total_host,
                       void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Moments of a resident recording (an addition to ABI 7).  Replaces the reduction of simulation/generate_metadata.py:24-45
+ * (np.diff over the frames, np.diff again, np.mean and np.std over all rows of all files): what vel_mean, vel_std, acc_mean and
+ * acc_std of metadata.json are made of.
+ *
+ * rec is one recording, [n_frames, n_nodes, data_dim] float32 row-major on the device; the positions are the `dim` (1..3)
+ * contiguous columns from cart0.  Velocities are p[t+1] - p[t], accelerations (p[t+2] - p[t+1]) - (p[t+1] - p[t]) in that order,
+ * both in float64 from the float32 positions.  material_col >= 0: only the rows whose column material_col equals material_value
+ * IN FRAME 0 are counted (sand-only statistics); material_col < 0: every row, rigid rows included, as the reference does.
+ *
+ * out_device receives GM_RECORDING_STATS_DOUBLES (24) doubles, 8 per axis a = 0..2 at out_device + 8 * a:
+ *     [0] number of velocities   [1] their mean   [2] their M2 = sum of (v - mean)^2
+ *     [3] number of accelerations [4] their mean  [5] their M2
+ *     [6] smallest position      [7] largest position        (exact float32 values, over every frame of the counted rows)
+ * Axes past `dim` hold zeros.  The population variance (np.std's, ddof = 0) is M2 / count; the records of several recordings merge
+ * by Chan's formula:  n = na + nb, d = mb - ma, mean = ma + d * nb / n, M2 = M2a + M2b + d * d * na * nb / n.  With no row
+ * counted the counts, means and M2 are 0 and the range is (+inf, -inf).  A non-finite position in a counted row makes the means,
+ * M2 and range of ITS axis non-finite and changes nothing else.
+ *
+ * Numerics: no sumsq - n * mean^2.  Every thread runs Welford's update on its samples, taken relative to the first velocity /
+ * acceleration of the first counted row (a sample of the data, so that the running means have the size of the spread whatever
+ * the drift); threads, waves, workgroups and the per-workgroup partials in the workspace are merged by Chan's formula, the
+ * partials by one workgroup in index order.  No floating-point atomics: the same recording gives the same bits at every call.
+ * A thread walks the frames of a node and then its next node, in a grid stride over at most GM_RECORDING_STATS_MAX_WORKGROUPS
+ * workgroups of 256 threads; every position is read once.  Three launches (the shifts, the partials, the finish), no host
+ * synchronisation.  The workspace (gm_recording_stats_workspace_bytes: 256 bytes for the shifts and one record per workgroup;
+ * 0 for n_frames < 3 or n_nodes < 1) is written before it is read.
+ *
+ * Refused with GM_ERR_INVALID_ARGUMENT and a "gm_recording_stats: ..." message, before any device call: a null pointer,
+ * n_frames < 3 (no acceleration exists), n_nodes < 1, dim outside 1..3, cart0 < 0 or cart0 + dim > data_dim, material_col >=
+ * data_dim, a workspace below the query.
+ * ------------------------------------------------------------------------------------------ */
+#define GM_RECORDING_STATS_DOUBLES 24
+#define GM_RECORDING_STATS_MAX_WORKGROUPS 1024
+size_t gm_recording_stats_workspace_bytes(int64_t n_frames, int64_t n_nodes);
+int gm_recording_stats(const float* rec /*[T,N,D] device*/, int64_t n_frames, int64_t n_nodes, int data_dim, int cart0,
+                       int dim /*1..3*/, int material_col /* <0: all rows */, float material_value, double* out_device, void* ws,
+                       size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Measurement hooks (no reference counterpart; the reference only wraps model.forward in
